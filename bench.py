@@ -12,11 +12,21 @@ gradient all-reduce over RCCL), Adam update.  Inputs are resident in HBM before 
 over graph replicas: each rank owns its own synthetic graph of the same shape (seed + rank), so
 per-GPU work is fixed ("weak").  value = L * E * N / t_step.
 
-Prints ONE JSON line on rank 0, including `roofline` (the kernel with the largest share of the
-timed region — found from HIP events around every launch of this repo's kernels — against the
-HBM roofline, plus whole-step aggregation / GEMM figures), `cpu_baseline` (the unmodified reference
-on the host cores, on a bounded sample of the same workload) and `parity_at_cpu_scale` (the same
-sample through the GPU stack: loss, output and every parameter gradient against the reference).
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `ms_per_step` = mean wall
+milliseconds per timed step over the `--steps` timed steps, ...) and the run's `config`.  A plain run does
+only that: set-up, `--warmup` steps, the timed steps, the line.  `--full` adds what takes runs
+or instrumentation of its own: `roofline` (the kernel with the largest share of the timed region
+— found from HIP events around every launch of this repo's kernels — against the HBM roofline,
+plus whole-step aggregation / GEMM figures, live PMC traffic and copy bandwidth), the side figures
+(other arithmetic / loss forms of the same step), `cpu_baseline` (the unmodified reference on the
+host cores, on a bounded sample of the same workload), `parity_at_cpu_scale` (the same sample
+through the GPU stack: loss, output and every parameter gradient against the reference) and
+`other_configs` (bench_configs.py).
+
+`--dump-outputs DIR` (full-batch mode) writes, after the timed steps, what the last timed step
+gave its caller as float32 `.npy` files: `loss`, `out_sample` (a fixed, seeded sample of rows of
+the model output), `grad.<parameter>` and `param.<parameter>` (after the Adam update).  The inputs
+are generated from fixed seeds, so two builds run with the same arguments compare file by file.
 """
 import argparse
 import json
@@ -457,6 +467,27 @@ def parity_cached(dev):
                       and all(gpu64[k] <= max(2 * ref64[k], 2e-5)
                               or gpu64_l2[k] <= max(1.5 * ref64_l2[k], 1e-5) for k in gpu64))
     return {k: (float(f'{v:.3e}') if isinstance(v, float) else v) for k, v in errs.items()}
+
+
+DUMP_OUT_ROWS = 65536   # rows of the model output `--dump-outputs` keeps (a seeded sample)
+
+
+def dump_outputs(path: str, loss, out, model) -> None:
+    """What one full-batch step hands its caller, as float32 ``path/<name>.npy``: the loss, a fixed
+    sample of ``DUMP_OUT_ROWS`` output rows (the same rows for the same graph size; the whole output
+    is 460 MB at the products shape), every parameter gradient and every parameter after the
+    optimizer update.  About 15 MB at the default shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = out.size(0)
+    rows = torch.randperm(n, generator=torch.Generator().manual_seed(2024))[:DUMP_OUT_ROWS]
+    rows = rows.sort().values.to(out.device)
+    arrays = {'loss': loss.detach().reshape(1), 'out_sample': out.detach()[rows]}
+    for name, p in model.named_parameters():
+        arrays[f'grad.{name}'] = p.grad.detach()
+        arrays[f'param.{name}'] = p.detach()
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f'{name}.npy'), t.float().cpu().numpy())
 
 
 def _print_line(result: dict) -> None:
@@ -1004,11 +1035,24 @@ def main():
     ap.add_argument('--capture', action='store_true',
                     help='minibatch mode: sampling + gather + forward + backward + Adam of a batch '
                          'as ONE hipGraph on static-shape (padded) batches')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need: roofline '
+                         '(per-launch events, PMC passes, copy bandwidth), side figures, CPU '
+                         'baseline, parity legs, other configs (each still subject to its --no-* '
+                         'option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='full-batch mode: after the timed steps, write the last step\'s loss, a '
+                         'seeded sample of output rows, the parameter gradients and the updated '
+                         'parameters as float32 DIR/<name>.npy')
     ap.add_argument('--init-dist', action='store_true',
                     help='initialise torch.distributed (nccl = RCCL) also for ONE rank and run the '
                          'broadcast / all-reduce / barrier collectives on it (exercises the '
                          'multi-GPU code path on a single-GPU box)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs is not None and (args.mode != 'fullbatch' or args.dry_run):
+        ap.error('--dump-outputs writes the outputs of the full-batch step only')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -1066,9 +1110,6 @@ def main():
     g = torch.Generator().manual_seed(7 + rank)
     train_idx = torch.randperm(N, generator=g)[:max(int(0.0803 * N), 1)].to(dev)
     y_train = y[train_idx]
-    # stored entries that point at a training node: the rows of the loss gradient the transposed
-    # aggregation of the output layer has to read (the others are zero and skipped, src_bits)
-    live_nnz = int(torch.bincount(ei[1].long(), minlength=N)[train_idx].sum().item())
 
     ar_events = []  # (start, end) HIP events around the gradient all-reduce, timed steps only
 
@@ -1079,10 +1120,13 @@ def main():
     # that step beside the headline (ms_per_step_torch_cross_entropy).
     from pytorch_geometric_amd.nn.functional import cross_entropy as rows_cross_entropy
     fused_loss = [not args.torch_loss]
+    last = {}   # the model output of the latest step (--dump-outputs only)
 
     def step():
         bucket.zero_()
         out = model(x, ei)
+        if args.dump_outputs is not None:
+            last['out'] = out.detach()
         if fused_loss[0]:
             loss = rows_cross_entropy(out, y, train_idx)
         else:
@@ -1108,7 +1152,8 @@ def main():
     fence()
     del ar_events[:]
     sink = []
-    _native.timing_sink = sink
+    if args.full:   # (per-launch HIP events for `roofline`)
+        _native.timing_sink = sink
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
@@ -1117,6 +1162,8 @@ def main():
     _native.timing_sink = None
     assert bucket.check_views(), 'gradient views were replaced: the all-reduce saw stale data'
     assert torch.isfinite(loss).item(), 'loss is not finite'
+    if args.dump_outputs is not None and rank == 0:   # (before anything else runs the step again)
+        dump_outputs(args.dump_outputs, loss, last['out'], model)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     per_rank_ms = [elapsed / args.steps * 1e3]
@@ -1133,164 +1180,169 @@ def main():
                     if ar_events else 0.0)
     n_pg = dist.get_world_size() if dist.is_initialized() else 1
 
-    # ---- roofline: every launch of this repo's kernels in the timed region carries HIP events
-    # (aggregation, one-kernel layers, GEMMs); the DOMINANT kernel is the device symbol with the
-    # largest summed time ----
-    def symbol(info):
-        if info.get('kind') == 'gemm':
-            # (csrc/gemm.hip: the weight gradient has its own kernel in the split arithmetic)
-            # (and, from 32 k rows, a narrow g — N <= 96, here the classifier layer's 2 x 48 columns
-            # against ONE x operand — its one-tile-per-workgroup form; the dispatch rule of
-            # pygamd_linear_wgrad2 restated for the label only)
-            tn = 'gemm_tn_split_kernel' if pga.get_gemm_mode() == 'split' else 'gemm_tn_kernel'
-            if (tn == 'gemm_tn_split_kernel' and info['op'] == 'wgrad' and info.get('N', 1 << 30) <= 96
-                    and info.get('N', 1) % 4 == 0 and info.get('K', 1) % 4 == 0
-                    and info.get('M', 0) >= 32768 and not info.get('x2')):
-                tn = 'gemm_tn_skinny_kernel'
-            return {'wgrad': tn, 'dgrad': 'gemm_nt_kernel', 'forward': 'gemm_nt_kernel'}[info['op']]
-        lpr = 4
-        while lpr < 64 and lpr * 4 < info['F']:
-            lpr <<= 1
-        it = 'long' if info['idx_bytes'] == 8 else 'int'
-        if info.get('fused_gemm'):
-            # (csrc/sage_fused.hip: the production kernel of the current arithmetic; the lab
-            # schedules of include/pyg_amd_lab.h when PYGAMD_FUSED_VARIANT asks for one)
-            prod = ('sage_fused_split_kernel' if pga.get_gemm_mode() == 'split'
-                    else 'sage_fused_fwd_kernel')
-            name = {0: prod, 1: 'sage_fused_probe_kernel', 2: 'sage_fused_stream_kernel',
-                    5: 'sage_fused_split_kernel', 6: 'sage_fused_fwd_kernel'}.get(
-                        _native.SAGE_FUSED_VARIANT, 'sage_fused_spec_kernel')
-            return f'{name}<{it},{lpr}>'
-        if info.get('src_bits'):
-            return f'spmm_sum_rows_sparse<{it},F={info["F"]}>'
-        return f'spmm_sum_rows<{it},F={info["F"]}>'
+    roofline, side = None, {}
+    if args.full:
+        # ---- roofline: every launch of this repo's kernels in the timed region carries HIP events
+        # (aggregation, one-kernel layers, GEMMs); the DOMINANT kernel is the device symbol with the
+        # largest summed time ----
+        # stored entries that point at a training node: the rows of the loss gradient the transposed
+        # aggregation of the output layer has to read (the others are zero and skipped, src_bits)
+        live_nnz = int(torch.bincount(ei[1].long(), minlength=N)[train_idx].sum().item())
 
-    def alg_bytes(info):
-        if info.get('src_bits'):
-            info = dict(info, live_nnz=live_nnz)
-        return (fused_algorithmic_bytes(info) if info.get('fused_gemm')
-                else spmm_algorithmic_bytes(info))
+        def symbol(info):
+            if info.get('kind') == 'gemm':
+                # (csrc/gemm.hip: the weight gradient has its own kernel in the split arithmetic)
+                # (and, from 32 k rows, a narrow g — N <= 96, here the classifier layer's 2 x 48 columns
+                # against ONE x operand — its one-tile-per-workgroup form; the dispatch rule of
+                # pygamd_linear_wgrad2 restated for the label only)
+                tn = 'gemm_tn_split_kernel' if pga.get_gemm_mode() == 'split' else 'gemm_tn_kernel'
+                if (tn == 'gemm_tn_split_kernel' and info['op'] == 'wgrad' and info.get('N', 1 << 30) <= 96
+                        and info.get('N', 1) % 4 == 0 and info.get('K', 1) % 4 == 0
+                        and info.get('M', 0) >= 32768 and not info.get('x2')):
+                    tn = 'gemm_tn_skinny_kernel'
+                return {'wgrad': tn, 'dgrad': 'gemm_nt_kernel', 'forward': 'gemm_nt_kernel'}[info['op']]
+            lpr = 4
+            while lpr < 64 and lpr * 4 < info['F']:
+                lpr <<= 1
+            it = 'long' if info['idx_bytes'] == 8 else 'int'
+            if info.get('fused_gemm'):
+                # (csrc/sage_fused.hip: the production kernel of the current arithmetic; the lab
+                # schedules of include/pyg_amd_lab.h when PYGAMD_FUSED_VARIANT asks for one)
+                prod = ('sage_fused_split_kernel' if pga.get_gemm_mode() == 'split'
+                        else 'sage_fused_fwd_kernel')
+                name = {0: prod, 1: 'sage_fused_probe_kernel', 2: 'sage_fused_stream_kernel',
+                        5: 'sage_fused_split_kernel', 6: 'sage_fused_fwd_kernel'}.get(
+                            _native.SAGE_FUSED_VARIANT, 'sage_fused_spec_kernel')
+                return f'{name}<{it},{lpr}>'
+            if info.get('src_bits'):
+                return f'spmm_sum_rows_sparse<{it},F={info["F"]}>'
+            return f'spmm_sum_rows<{it},F={info["F"]}>'
 
-    by_sym = {}
-    for info, ev0, ev1 in sink:
-        by_sym.setdefault(symbol(info), []).append((info, ev0.elapsed_time(ev1)))
-    tot_ms = {k: sum(ms for _, ms in v) for k, v in by_sym.items()}
-    agg_syms = [k for k in by_sym if not k.startswith('gemm')]
-    dom = max(agg_syms, key=tot_ms.get) if agg_syms else None
-    if tot_ms and max(tot_ms, key=tot_ms.get) != dom:
-        dom_any = max(tot_ms, key=tot_ms.get)
-    else:
-        dom_any = dom
+        def alg_bytes(info):
+            if info.get('src_bits'):
+                info = dict(info, live_nnz=live_nnz)
+            return (fused_algorithmic_bytes(info) if info.get('fused_gemm')
+                    else spmm_algorithmic_bytes(info))
 
-    def hbm_entry(sym):
-        items = by_sym[sym]
-        ms = sum(t for _, t in items) / len(items)
-        byts = sum(alg_bytes(i) for i, _ in items) / len(items)
-        strict = sum(spmm_algorithmic_bytes(dict(i, accumulate=False, relu_mask=False,
-                                                 relu_bits=False)) for i, _ in items) / len(items)
-        ach = byts / (ms * 1e-3) / 1e9
-        e = {'bound': 'hbm', 'achieved': round(ach, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-             'frac': round(ach / HBM_PEAK_GBS, 4), 'traffic': pmc_traffic(args, N, E, sym),
-             'kernel': sym, 'launches_per_step': round(len(items) / args.steps, 2),
-             'avg_launch_ms': round(ms, 4), 'ms_per_step': round(tot_ms[sym] / args.steps, 3),
-             'algorithmic_bytes_per_launch': byts,
-             'frac_strict_8d': round(strict / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-        fg = [i['fused_gemm'] for i, _ in items if i.get('fused_gemm')]
-        if fg:
-            flops = sum(2.0 * i['n_rows'] * i['fused_gemm']['K'] * i['fused_gemm']['Fo']
-                        for i, _ in items) / len(items)
-            e['mfma_frac_of_157.3'] = round(flops / (ms * 1e-3) / 1e12 / 157.3, 4)
-        return e
+        by_sym = {}
+        for info, ev0, ev1 in sink:
+            by_sym.setdefault(symbol(info), []).append((info, ev0.elapsed_time(ev1)))
+        tot_ms = {k: sum(ms for _, ms in v) for k, v in by_sym.items()}
+        agg_syms = [k for k in by_sym if not k.startswith('gemm')]
+        dom = max(agg_syms, key=tot_ms.get) if agg_syms else None
+        if tot_ms and max(tot_ms, key=tot_ms.get) != dom:
+            dom_any = max(tot_ms, key=tot_ms.get)
+        else:
+            dom_any = dom
 
-    # HBM traffic of this run: two PMC passes over this command in child processes (rank 0 of a
-    # one-GPU run, not for the short profiling invocations)
-    global _live_traffic
-    if (rank == 0 and world == 1 and not args.no_live_pmc and not args.no_side_figures
-            and not args.no_cpu_baseline):
-        _live_traffic = live_pmc_traffic(args)
-    roofline = hbm_entry(dom) if dom else {}
-    if dom:
-        roofline['traffic_source'] = (
-            'live: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, '
-            '--kernel-trace only) over this command with 2 steps, run by this process; '
-            '(2 x FETCH_SIZE + WRITE_SIZE) KiB per launch'
-            if _live_traffic is not None else
-            'committed profile (profiles/r06_pmc_bench.json, same command and workload)')
-    cp = None
-    if dom and rank == 0:  # the same launch against what plain device copies reach on THIS box
-        try:
-            cp = measured_copy_bandwidth(dev)
-        except RuntimeError as exc:  # (a side figure: never at the price of the bench line)
-            roofline['copy_bandwidth'] = {'error': str(exc)[:200]}
-    if cp is not None:
-        copy_gbs = max(cp['torch_copy'], cp['probe'])
-        roofline['copy_bandwidth'] = {
-            'measured': round(copy_gbs, 1), 'unit': 'GB/s',
-            'what': 'fastest device-to-device copy of 1 GiB on this box (read + written bytes), '
-                    'HIP events, this run',
-            'torch_copy': round(cp['torch_copy'], 1), 'lab_copy': round(cp['probe'], 1),
-            'lab_schedule': cp['probe_schedule'],
-            'lab_read_only': round(cp['read'], 1), 'lab_read_schedule': cp['read_schedule'],
-            'frac_of_read': round(roofline['achieved'] / cp['read'], 4),
-            'frac_of_copy': round(roofline['achieved'] / copy_gbs, 4)}
-    roofline['share_of_step'] = round(tot_ms.get(dom, 0.0) / (elapsed * 1e3), 4) if dom else None
-    roofline['others'] = {k: round(tot_ms[k] / args.steps, 3) for k in sorted(tot_ms) if k != dom}
-    if dom_any != dom:  # (a GEMM symbol leads: say so; the HBM entry above stays the aggregation)
-        roofline['largest_symbol'] = dom_any
-    second = sorted((k for k in agg_syms if k != dom), key=tot_ms.get, reverse=True)[:1]
-    if second:
-        e2 = hbm_entry(second[0])
-        roofline['second'] = {k: e2[k] for k in ('kernel', 'frac', 'achieved', 'avg_launch_ms',
-                                                 'ms_per_step', 'traffic')}
-    # whole-step figures: every aggregation launch against HBM, every stand-alone GEMM against the
-    # fp32 matrix peak (the flops inside the one-kernel layers are listed, not priced twice)
-    agg_ms = sum(tot_ms[k] for k in agg_syms) / args.steps
-    agg_bytes = sum(alg_bytes(i) for k in agg_syms for i, _ in by_sym[k]) / args.steps
-    gemm_items = [(i, ms) for k in by_sym if k.startswith('gemm') for i, ms in by_sym[k]]
-    gemm_ms = sum(ms for _, ms in gemm_items) / args.steps
-    gemm_flop = sum(2.0 * i['M'] * i['N'] * i['K'] for i, _ in gemm_items) / args.steps
-    fused_flop = sum(2.0 * i['n_rows'] * i['fused_gemm']['K'] * i['fused_gemm']['Fo']
-                     for k in agg_syms for i, _ in by_sym[k] if i.get('fused_gemm')) / args.steps
-    roofline['step'] = {
-        'agg_ms': round(agg_ms, 3), 'agg_GB': round(agg_bytes / 1e9, 2),
-        'agg_frac_of_hbm_peak': round(agg_bytes / (agg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        if agg_ms > 0 else None,
-        'gemm_ms': round(gemm_ms, 3), 'gemm_GFLOP': round(gemm_flop / 1e9, 1),
-        'gemm_frac_of_157.3TF': round(gemm_flop / (gemm_ms * 1e-3) / 1e12 / 157.3, 4)
-        if gemm_ms > 0 else None,
-        'GFLOP_inside_fused_layers': round(fused_flop / 1e9, 1),
-        'other_ms': round(ms_per_step - agg_ms - gemm_ms, 3)}
+        def hbm_entry(sym):
+            items = by_sym[sym]
+            ms = sum(t for _, t in items) / len(items)
+            byts = sum(alg_bytes(i) for i, _ in items) / len(items)
+            strict = sum(spmm_algorithmic_bytes(dict(i, accumulate=False, relu_mask=False,
+                                                     relu_bits=False)) for i, _ in items) / len(items)
+            ach = byts / (ms * 1e-3) / 1e9
+            e = {'bound': 'hbm', 'achieved': round(ach, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                 'frac': round(ach / HBM_PEAK_GBS, 4), 'traffic': pmc_traffic(args, N, E, sym),
+                 'kernel': sym, 'launches_per_step': round(len(items) / args.steps, 2),
+                 'avg_launch_ms': round(ms, 4), 'ms_per_step': round(tot_ms[sym] / args.steps, 3),
+                 'algorithmic_bytes_per_launch': byts,
+                 'frac_strict_8d': round(strict / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+            fg = [i['fused_gemm'] for i, _ in items if i.get('fused_gemm')]
+            if fg:
+                flops = sum(2.0 * i['n_rows'] * i['fused_gemm']['K'] * i['fused_gemm']['Fo']
+                            for i, _ in items) / len(items)
+                e['mfma_frac_of_157.3'] = round(flops / (ms * 1e-3) / 1e12 / 157.3, 4)
+            return e
 
-    # ---- figures printed BESIDE the headline (never the headline): the same step with the exact
-    # fp32 matrix instruction everywhere, and with the loss gradient treated as dense (no zero-row
-    # skipping in the output layer's transposed aggregation).  Every rank runs them (the step
-    # contains the all-reduce); short: 2 + 5 steps each.
-    def quick_ms(n_warm=2, n=5):
-        for _ in range(n_warm):
-            step()
-        fence()
-        q0 = time.perf_counter()
-        for _ in range(n):
-            step()
-        fence()
-        return (time.perf_counter() - q0) / n * 1e3
+        # HBM traffic of this run: two PMC passes over this command in child processes (rank 0 of a
+        # one-GPU run, not for the short profiling invocations)
+        global _live_traffic
+        if (rank == 0 and world == 1 and not args.no_live_pmc and not args.no_side_figures
+                and not args.no_cpu_baseline):
+            _live_traffic = live_pmc_traffic(args)
+        roofline = hbm_entry(dom) if dom else {}
+        if dom:
+            roofline['traffic_source'] = (
+                'live: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, '
+                '--kernel-trace only) over this command with 2 steps, run by this process; '
+                '(2 x FETCH_SIZE + WRITE_SIZE) KiB per launch'
+                if _live_traffic is not None else
+                'committed profile (profiles/r06_pmc_bench.json, same command and workload)')
+        cp = None
+        if dom and rank == 0:  # the same launch against what plain device copies reach on THIS box
+            try:
+                cp = measured_copy_bandwidth(dev)
+            except RuntimeError as exc:  # (a side figure: never at the price of the bench line)
+                roofline['copy_bandwidth'] = {'error': str(exc)[:200]}
+        if cp is not None:
+            copy_gbs = max(cp['torch_copy'], cp['probe'])
+            roofline['copy_bandwidth'] = {
+                'measured': round(copy_gbs, 1), 'unit': 'GB/s',
+                'what': 'fastest device-to-device copy of 1 GiB on this box (read + written bytes), '
+                        'HIP events, this run',
+                'torch_copy': round(cp['torch_copy'], 1), 'lab_copy': round(cp['probe'], 1),
+                'lab_schedule': cp['probe_schedule'],
+                'lab_read_only': round(cp['read'], 1), 'lab_read_schedule': cp['read_schedule'],
+                'frac_of_read': round(roofline['achieved'] / cp['read'], 4),
+                'frac_of_copy': round(roofline['achieved'] / copy_gbs, 4)}
+        roofline['share_of_step'] = round(tot_ms.get(dom, 0.0) / (elapsed * 1e3), 4) if dom else None
+        roofline['others'] = {k: round(tot_ms[k] / args.steps, 3) for k in sorted(tot_ms) if k != dom}
+        if dom_any != dom:  # (a GEMM symbol leads: say so; the HBM entry above stays the aggregation)
+            roofline['largest_symbol'] = dom_any
+        second = sorted((k for k in agg_syms if k != dom), key=tot_ms.get, reverse=True)[:1]
+        if second:
+            e2 = hbm_entry(second[0])
+            roofline['second'] = {k: e2[k] for k in ('kernel', 'frac', 'achieved', 'avg_launch_ms',
+                                                     'ms_per_step', 'traffic')}
+        # whole-step figures: every aggregation launch against HBM, every stand-alone GEMM against the
+        # fp32 matrix peak (the flops inside the one-kernel layers are listed, not priced twice)
+        agg_ms = sum(tot_ms[k] for k in agg_syms) / args.steps
+        agg_bytes = sum(alg_bytes(i) for k in agg_syms for i, _ in by_sym[k]) / args.steps
+        gemm_items = [(i, ms) for k in by_sym if k.startswith('gemm') for i, ms in by_sym[k]]
+        gemm_ms = sum(ms for _, ms in gemm_items) / args.steps
+        gemm_flop = sum(2.0 * i['M'] * i['N'] * i['K'] for i, _ in gemm_items) / args.steps
+        fused_flop = sum(2.0 * i['n_rows'] * i['fused_gemm']['K'] * i['fused_gemm']['Fo']
+                         for k in agg_syms for i, _ in by_sym[k] if i.get('fused_gemm')) / args.steps
+        roofline['step'] = {
+            'agg_ms': round(agg_ms, 3), 'agg_GB': round(agg_bytes / 1e9, 2),
+            'agg_frac_of_hbm_peak': round(agg_bytes / (agg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+            if agg_ms > 0 else None,
+            'gemm_ms': round(gemm_ms, 3), 'gemm_GFLOP': round(gemm_flop / 1e9, 1),
+            'gemm_frac_of_157.3TF': round(gemm_flop / (gemm_ms * 1e-3) / 1e12 / 157.3, 4)
+            if gemm_ms > 0 else None,
+            'GFLOP_inside_fused_layers': round(fused_flop / 1e9, 1),
+            'other_ms': round(ms_per_step - agg_ms - gemm_ms, 3)}
 
-    side = {}
-    if not args.no_side_figures:
-        from pytorch_geometric_amd.nn.models import _fused_sage
-        mode = pga.get_gemm_mode()
-        if mode != 'fp32':
-            pga.set_gemm_mode('fp32')
-            side['ms_per_step_exact_fp32_instruction'] = round(quick_ms(), 3)
-            pga.set_gemm_mode(mode)
-        if _fused_sage.SPARSE_GRAD:
-            _fused_sage.SPARSE_GRAD = False
-            side['dense_loss_ms_per_step'] = round(quick_ms(), 3)
-            _fused_sage.SPARSE_GRAD = True
-        if fused_loss[0]:
-            fused_loss[0] = False
-            side['ms_per_step_torch_cross_entropy'] = round(quick_ms(), 3)
-            fused_loss[0] = True
+        # ---- figures printed BESIDE the headline (never the headline): the same step with the exact
+        # fp32 matrix instruction everywhere, and with the loss gradient treated as dense (no zero-row
+        # skipping in the output layer's transposed aggregation).  Every rank runs them (the step
+        # contains the all-reduce); short: 2 + 5 steps each.
+        def quick_ms(n_warm=2, n=5):
+            for _ in range(n_warm):
+                step()
+            fence()
+            q0 = time.perf_counter()
+            for _ in range(n):
+                step()
+            fence()
+            return (time.perf_counter() - q0) / n * 1e3
+
+        if not args.no_side_figures:
+            from pytorch_geometric_amd.nn.models import _fused_sage
+            mode = pga.get_gemm_mode()
+            if mode != 'fp32':
+                pga.set_gemm_mode('fp32')
+                side['ms_per_step_exact_fp32_instruction'] = round(quick_ms(), 3)
+                pga.set_gemm_mode(mode)
+            if _fused_sage.SPARSE_GRAD:
+                _fused_sage.SPARSE_GRAD = False
+                side['dense_loss_ms_per_step'] = round(quick_ms(), 3)
+                _fused_sage.SPARSE_GRAD = True
+            if fused_loss[0]:
+                fused_loss[0] = False
+                side['ms_per_step_torch_cross_entropy'] = round(quick_ms(), 3)
+                fused_loss[0] = True
 
     arithmetic = (
         'fp32 in / fp32 out; products as 3 x bf16 split (x = x1 + x2 + x3 exactly), the 6 leading '
@@ -1332,9 +1384,10 @@ def main():
                             'aggregates at width 48; ReLU backward / bias grads / 1/deg in '
                             'epilogues',
             },
-            'roofline': roofline,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            result['roofline'] = roofline
+        if args.full and not args.no_cpu_baseline and world == 1:
             result['cpu_baseline'], sample = cpu_baseline(args.cpu_scale)
             result['parity_at_cpu_scale'] = parity_at_cpu_scale(sample, dev)
             # (the leg an N > 1 line carries instead, run here too so that it is exercised on
@@ -1347,7 +1400,7 @@ def main():
                 result['other_configs'] = bench_configs.run(
                     dev, headline=(x, ei, train_idx, y_train, num_classes,
                                    side.get('ms_per_step_torch_cross_entropy', ms_per_step)))
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             # N > 1: no live CPU run of the reference (rank 0 only, the other ranks wait at the
             # barrier below); the GPU leg against the committed reference sample
             result['cpu_baseline'] = None

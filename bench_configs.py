@@ -3,7 +3,7 @@ configs 1 (GCN, Cora shape), 3 (GAT, ogbn-arxiv shape), 5 (RGCN, FB15k-237 shape
 package's own classes AND with the REFERENCE's classes behind ``backend.install()`` — config 2 with
 the reference's ``GraphSAGE`` + ``install()``, and config 4 (captured mini-batch step) on one GPU.
 
-``bench.py`` calls :func:`run` AFTER its timed region, on rank 0 of a one-GPU run only; every value
+``bench.py --full`` calls :func:`run` AFTER its timed region, on rank 0 of a one-GPU run only; every value
 in the returned dict is a scalar or a short string (the driver's record keeps scalars and the
 first 120 characters of strings).  Nothing here is the headline.
 

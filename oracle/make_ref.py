@@ -120,7 +120,9 @@ def _unpacked_dir():
     """Extract the staged archive once per content hash into the temp directory."""
     with open(MANIFEST) as f:
         digest = json.load(f)['sha1']
-    root = os.path.join(tempfile.gettempdir(), f'pyg_reference_{digest[:16]}')
+    # (per user: a copy another account unpacked into the shared temp directory may not be ours
+    # to complete)
+    root = os.path.join(tempfile.gettempdir(), f'pyg_reference_{os.getuid()}_{digest[:16]}')
     marker = os.path.join(root, '.complete')
     if not os.path.exists(marker):
         os.makedirs(root, exist_ok=True)
@@ -132,29 +134,25 @@ def _unpacked_dir():
 
 
 def reference_tests():
-    """(directory, [test files]) of the reference's own test modules for the path: the mounted
-    ``<reference>/test`` in the build container, else the staged copies."""
-    if os.path.isdir(os.path.join(REF_ROOT, 'test')):
-        root = os.path.join(REF_ROOT, 'test')
-    elif staged_path() and os.path.exists(MANIFEST):
-        root = os.path.join(_unpacked_dir(), 'reference_tests')
-    else:
-        raise ImportError('no reference tests: neither /root/reference/test nor a staged archive')
+    """(directory, [test files]) of the reference's own test modules for the path: the staged
+    copies (never the reference tree itself: everything that checks against the reference reads
+    what ``stage()`` packed under ``oracle/_ref``)."""
+    if not (staged_path() and os.path.exists(MANIFEST)):
+        raise ImportError('no staged reference under oracle/_ref: run __graft_entry__.build() '
+                          'where the reference is present')
+    root = os.path.join(_unpacked_dir(), 'reference_tests')
     files = [os.path.join(root, t) for t in _test_files(root)
              if os.path.basename(t) != 'conftest.py']
     return root, files
 
 
 def import_reference():
-    """Put the reference first on ``sys.path`` and import it: the mounted one in the build
-    container, else the staged archive (unpacked under the temp directory)."""
-    if os.path.isdir(os.path.join(REF_ROOT, 'torch_geometric')):
-        path = REF_ROOT
-    elif staged_path() and os.path.exists(MANIFEST):
-        path = _unpacked_dir()
-    else:
-        raise ImportError('no /root/reference and no staged archive under oracle/_ref: run '
-                          '`python oracle/make_ref.py` in the build container')
+    """Put the reference first on ``sys.path`` and import it: the staged archive (unpacked under
+    the temp directory), the same copy in the build container and on the GPU box."""
+    if not (staged_path() and os.path.exists(MANIFEST)):
+        raise ImportError('no staged reference under oracle/_ref: run __graft_entry__.build() '
+                          'where the reference is present')
+    path = _unpacked_dir()
     if path not in sys.path:
         sys.path.insert(0, path)
     import torch_geometric

@@ -346,9 +346,9 @@ def test_reference_own_tests_pass_on_the_cpu_with_the_backend_installed():
     ref_root = os.path.dirname(os.path.dirname(os.path.abspath(pyg.__file__)))
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, ref_root]), FULL_TEST='1')
     cmd = [sys.executable, '-m', 'pytest', *pick, '-q', '-p', 'no:cacheprovider', '-p',
-           'tests._install_plugin', '--rootdir', '/tmp', '-c', os.devnull, '-k',
-           'not (test_gat_conv and not with_edge_attr and not empty_edge_index)']
-    res = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd='/tmp', timeout=550)
+           'tests._install_plugin', '--rootdir', root, '--confcutdir', root, '-c', os.devnull,
+           '-k', 'not (test_gat_conv and not with_edge_attr and not empty_edge_index)']
+    res = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=root, timeout=550)
     tail = (res.stdout + res.stderr)[-3000:]
     assert res.returncode == 0, tail
     assert ' passed' in tail and ' failed' not in tail, tail

@@ -26,30 +26,32 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(files, with_backend, extra=(), full=False, workers=None):
-    """One pytest process per test module, `workers` at a time (default: by the host's CPU count) (the modules are CPU-heavy —
+def _run(root, files, with_backend, extra=(), full=False, workers=None):
+    """One pytest process per test module, `workers` at a time (the modules are CPU-heavy —
     TorchScript, 2,700 small cases — and independent; pytest-xdist cannot split them: their
     parametrisations are not collected in a stable order).  Returns (failed node ids, a summary
     line, the concatenated output)."""
     from concurrent.futures import ThreadPoolExecutor
 
-    if workers is None:   # 4 threads per module process; the GPU boxes have 256 host CPUs
-        workers = 16   # (48 side by side measured slower: 245 s against 158-221 s for 275 modules)
+    if workers is None:   # 4 threads per module process
+        # (every module process opens the device, and so does this one: twelve side by side keep
+        # the count of processes holding the GPU well below sixteen)
+        workers = 12
     from oracle import make_ref
     ref = make_ref.import_reference()
     ref_root = os.path.dirname(os.path.dirname(os.path.abspath(ref.__file__)))
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT, ref_root]), OMP_NUM_THREADS='4',
-               MKL_NUM_THREADS='4')    # (sixteen processes side by side: no 128-thread pools each)
+               MKL_NUM_THREADS='4')    # (twelve processes side by side: no 128-thread pools each)
     env.pop('FULL_TEST', None)
     if full:
         env['FULL_TEST'] = '1'
 
     def one(path):
         cmd = [sys.executable, '-m', 'pytest', path, '-q', '-p', 'no:cacheprovider', '-rf',
-               '--rootdir', '/tmp', '-c', os.devnull, *extra]
+               '--rootdir', root, '--confcutdir', root, '-c', os.devnull, *extra]
         if with_backend:
             cmd += ['-p', 'tests._install_plugin']
-        res = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd='/tmp',
+        res = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=root,
                              timeout=1700)
         return res.stdout + res.stderr
 
@@ -90,16 +92,16 @@ def test_reference_test_modules_pass_with_the_backend_installed():
     if not full:
         files = [f for f in files if any(c in '/' + os.path.relpath(f, root) for c in CORE)]
         assert len(files) >= 135, len(files)
-    failed, line, out = _run(files, with_backend=True)
+    failed, line, out = _run(root, files, with_backend=True)
     m = re.search(r'(\d+) passed', line)
     assert m and int(m.group(1)) >= (3900 if full else 3300), line
     assert 'cuda:0' in out or not failed    # (ids of device cases carry the device name)
     new = sorted(failed)
     if new:
-        own, _, _ = _run(files, with_backend=False, extra=('-k', _names(new)))
+        own, _, _ = _run(root, files, with_backend=False, extra=('-k', _names(new)))
         new = sorted(set(new) - own)
     if new:
-        again, _, out = _run(files, with_backend=True, extra=('-k', _names(new)))
+        again, _, out = _run(root, files, with_backend=True, extra=('-k', _names(new)))
         new = sorted(set(new) & again)
     assert not new, (f'{len(new)} reference tests fail only with the backend installed: {new}\n'
                      f'installed: {line}\n' + out[-6000:])
