@@ -578,6 +578,33 @@ PYGAMD_API int pygamd_sample_neighbors(const void* colptr, const void* row, int 
                                        int flags, const uint64_t* seed_dev, void* src_out,
                                        void* dstpos_out, void* slot_out, void* stream);
 
+/* Weighted variant: the reference's NeighborLoader(..., weight_attr=...) -> NeighborSampler.
+ * edge_weight -> torch.ops.pyg.neighbor_sample(..., edge_weight, ...)
+ * (sampler/neighbor_sampler.py:559-571: "neighbors are more likely to get sampled the higher
+ * their edge weights").  Same arguments, flags and return codes as pygamd_sample_neighbors, plus
+ * weight_csc [E] fp32 in CSC slot order (the caller's edge weights permuted like `row`; finite,
+ * >= 0).  With in-degree d and count k:
+ *   k < 0, or no replacement and d <= k: every in-neighbour, in slot order (weights unused);
+ *   no replacement, d > k: successive sampling in proportion to weight (the first pick is slot j
+ *     with probability w_j / W, later picks renormalised over the slots left), realised with
+ *     Efraimidis-Spirakis keys log(-ln u_j) - log(w_j), u_j in (0, 1) the counter-based hash of
+ *     (seed, node, slot): the k smallest keys, emitted in key order.  Zero-weight slots are
+ *     taken only when fewer than k positive-weight slots exist, then uniformly among themselves;
+ *   replacement, d > 0: k independent draws, slot j with probability w_j / W; a zero-weight slot
+ *     is never drawn; W = 0 (outside the reference's domain) draws uniformly over the d slots.
+ * Every node's weights are read, one wave per node; the per-node sum must stay finite in fp32
+ * and the in-degree below 2^32.  Draws depend on (seed, node, slot or draw) only (plus the
+ * frontier position under flags bit 1, plus seed_dev): reproducible whatever the scheduling.
+ * NULL weight_csc returns PYGAMD_ERR_INVALID_ARG, max_per_node > pygamd_sample_max_fanout()
+ * PYGAMD_ERR_UNSUPPORTED, both before any launch.                                               */
+PYGAMD_API int pygamd_sample_neighbors_weighted(const void* colptr, const void* row,
+                                                int idx_dtype, const float* weight_csc,
+                                                const void* frontier, int64_t n_frontier,
+                                                const void* offsets, int64_t max_per_node,
+                                                uint64_t seed, int flags,
+                                                const uint64_t* seed_dev, void* src_out,
+                                                void* dstpos_out, void* slot_out, void* stream);
+
 /* cnt[f] = min(deg(frontier[f]), k) (k < 0: deg; replace != 0 and k >= 0: k wherever deg > 0, else
  * 0) — the per-node sample counts of one hop.
  * `n_valid` (device int64, may be NULL): only the first *n_valid entries of the fixed-capacity

@@ -137,6 +137,8 @@ SIGNATURES = {
     'pygamd_sample_max_fanout': (c_int, []),
     'pygamd_sample_neighbors': (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, c_uint64, c_int,
                                         _P, _P, _P, _P, _P]),
+    'pygamd_sample_neighbors_weighted': (c_int, [_P, _P, c_int, _P, _P, c_int64, _P, c_int64,
+                                                 c_uint64, c_int, _P, _P, _P, _P, _P]),
     'pygamd_slots_max_fanout': (c_int, []),
     'pygamd_slots_max_hops': (c_int, []),
     'pygamd_slots_seed': (c_int, [_P, c_int, c_int64, _P, _P, _P, _P]),

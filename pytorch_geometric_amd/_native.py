@@ -1620,21 +1620,32 @@ def segment_matmul_wgrad(x: Tensor, g: Tensor, plan, n_seg: int, blocks: int = 1
 def sample_neighbors(colptr: Tensor, row: Tensor, frontier: Tensor, offsets: Tensor, total: int,
                      max_per_node: int, seed: int, zero_fill: bool = False,
                      replace: bool = False, salt_position: bool = False,
-                     seed_dev: Optional[Tensor] = None):
+                     seed_dev: Optional[Tensor] = None, weight: Optional[Tensor] = None):
     """(src_global, dst_pos_in_frontier, csc_slot) for the sampled in-edges of `frontier`.
     ``total`` sizes the outputs; ``zero_fill`` for a static capacity larger than what the hop
     really samples (the tail then holds 0 = a valid node / slot id).  ``replace``: draws with
     replacement (``offsets`` from :func:`sample_counts` with the same flag).  ``salt_position``:
     the draws of a node also depend on its position in ``frontier`` (disjoint sampling: the same
     node in two trees draws independently).  ``seed_dev`` (int64 [1] on the device) is added to
-    ``seed`` on the device (a captured graph bumps it between replays)."""
-    _require_device(colptr, row, frontier, offsets)
+    ``seed`` on the device (a captured graph bumps it between replays).  ``weight`` (fp32 [E] in
+    CSC slot order, finite, >= 0): draws in proportion to edge weight
+    (``pygamd_sample_neighbors_weighted``)."""
+    _require_device(colptr, row, frontier, offsets, weight)
+    if weight is not None and (weight.dtype != torch.float32 or not weight.is_contiguous()
+                               or weight.numel() != row.numel()):
+        raise ValueError("'weight' must be a contiguous float32 tensor with one entry per edge")
     lib = _lib.load()
     alloc = torch.zeros if zero_fill else torch.empty
     src = alloc(total, dtype=colptr.dtype, device=colptr.device)
     dstpos = alloc(total, dtype=colptr.dtype, device=colptr.device)
     slot = alloc(total, dtype=colptr.dtype, device=colptr.device)
-    if total > 0:
+    if total > 0 and weight is not None:
+        check(lib.pygamd_sample_neighbors_weighted(
+            _p(colptr), _p(row), _idx_dtype(colptr), _p(weight), _p(frontier), frontier.numel(),
+            _p(offsets), max_per_node, seed & 0xFFFFFFFFFFFFFFFF,
+            int(replace) | (2 if salt_position else 0), _p(seed_dev), _p(src), _p(dstpos),
+            _p(slot), _stream(colptr)), 'sample_neighbors_weighted')
+    elif total > 0:
         check(lib.pygamd_sample_neighbors(_p(colptr), _p(row), _idx_dtype(colptr), _p(frontier),
                                           frontier.numel(), _p(offsets), max_per_node,
                                           seed & 0xFFFFFFFFFFFFFFFF,

@@ -38,7 +38,7 @@ exactly where the reference steps aside for its own extensions (utils/_scatter.p
 edge_index.py:1946).  ``uninstall()`` restores every binding.
 """
 import sys
-from typing import Any, Callable, Dict, List, Tuple
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -868,7 +868,8 @@ _sampler_cls = None
 
 
 def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: bool = False,
-                     disjoint: bool = False, subgraph_type='directional'):
+                     disjoint: bool = False, subgraph_type='directional',
+                     weight_attr: Optional[str] = None):
     """A ``torch_geometric.sampler.BaseSampler`` (sampler/base.py:932-998) whose
     ``sample_from_nodes(NodeSamplerInput) -> SamplerOutput`` runs on the GPU
     (:class:`pytorch_geometric_amd.sampler.NeighborSampler`), so that the reference's
@@ -877,7 +878,10 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     the device (``edge_index``, ``num_nodes``) or a ``(edge_index, num_nodes)`` pair.  ``replace``,
     ``disjoint`` and ``subgraph_type`` (``'directional'`` | ``'bidirectional'``, string or the
     reference's ``SubgraphType``) are the options ``NeighborLoader`` forwards to its sampler
-    (loader/neighbor_loader.py:209-233)."""
+    (loader/neighbor_loader.py:209-233).  ``weight_attr``: the name of an ``[E]`` edge attribute
+    of ``data`` holding non-negative sampling weights (loader/neighbor_loader.py:168-174:
+    neighbours are more likely to get sampled the higher their edge weights); it needs the
+    ``Data`` form."""
     global _sampler_cls
     import torch_geometric.sampler as pyg_sampler
     from .sampler import NeighborSampler
@@ -885,11 +889,15 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
 
         class MI355XNeighborSampler(pyg_sampler.BaseSampler):
             def __init__(self, edge_index, num_nodes, num_neighbors, seed=0, replace=False,
-                         disjoint=False, subgraph_type='directional'):
+                         disjoint=False, subgraph_type='directional', edge_weight=None,
+                         weight_attr=None):
                 self.impl = NeighborSampler(edge_index, num_nodes, num_neighbors, seed=seed,
                                             output_cls=pyg_sampler.SamplerOutput,
                                             replace=replace, disjoint=disjoint,
-                                            subgraph_type=subgraph_type)
+                                            subgraph_type=subgraph_type,
+                                            edge_weight=edge_weight)
+                self.weight_attr = weight_attr
+                self.edge_weight = self.impl.edge_weight  # fp32, CSC order
                 self.num_neighbors = list(num_neighbors)
                 self.replace, self.disjoint = self.impl.replace, self.impl.disjoint
                 self.subgraph_type = self.impl.subgraph_type
@@ -905,15 +913,21 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
                 return None  # `edge` already indexes the caller's edge_index
 
         _sampler_cls = MI355XNeighborSampler
+    edge_weight = None
     if isinstance(data, (tuple, list)):
+        if weight_attr is not None:
+            raise ValueError("'weight_attr' names an edge attribute of a 'Data' object; the "
+                             "(edge_index, num_nodes) form has none")
         edge_index, num_nodes = data
     else:
         edge_index, num_nodes = data.edge_index, data.num_nodes
+        if weight_attr is not None:
+            edge_weight = data[weight_attr]
     if not (isinstance(edge_index, Tensor) and edge_index.is_cuda):
         raise ValueError("the sampler needs 'edge_index' on the HIP device (there is no CPU "
                          "fallback): move the data with `.to('cuda')` first")
     return _sampler_cls(edge_index, int(num_nodes), num_neighbors, seed, replace, disjoint,
-                        subgraph_type)
+                        subgraph_type, edge_weight=edge_weight, weight_attr=weight_attr)
 
 
 def _wrap_linear_forward(cls):

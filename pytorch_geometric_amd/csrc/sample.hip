@@ -24,6 +24,33 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
   return z ^ (z >> 31);
 }
 
+// deg(v) <= count: lanes copy the slot range [s, s + deg), coalesced, in slot order
+template <typename IdxT>
+__device__ __forceinline__ void copy_all_slots(const IdxT* __restrict__ row, int64_t s,
+                                               int64_t deg, int64_t o, int64_t f,
+                                               IdxT* __restrict__ src_out,
+                                               IdxT* __restrict__ dstpos_out,
+                                               IdxT* __restrict__ slot_out) {
+  for (int64_t t = lane_id(); t < deg; t += kWave) {
+    src_out[o + t] = row[s + t];
+    dstpos_out[o + t] = static_cast<IdxT>(f);
+    slot_out[o + t] = static_cast<IdxT>(s + t);
+  }
+}
+
+// The hash stream of frontier node v at frontier position f: draw c of the node uses
+// mix64(key + c).
+__device__ __forceinline__ uint64_t node_key(uint64_t seed, const uint64_t* __restrict__ seed_dev,
+                                             int64_t v, int64_t f, int flags) {
+  // flags & 2: the draws depend on the frontier position too (disjoint trees)
+  const uint64_t salt = (flags & 2) ? mix64(0xD1B54A32D192ED03ull * static_cast<uint64_t>(f + 1)) : 0;
+  // (a captured graph bumps this word between replays.  It is mixed in on its own, not added:
+  // the host seed is rng * 1000003 + hop, so `seed + word` would hand hop h + 1 of one replay the
+  // stream of hop h of the next — ADVICE r3)
+  if (seed_dev) seed = mix64(seed ^ mix64(*seed_dev * 0x9E3779B97F4A7C15ull));
+  return mix64(seed ^ mix64(static_cast<uint64_t>(v)) ^ salt);
+}
+
 template <typename IdxT>
 __global__ void __launch_bounds__(kBlock)
     sample_neighbors_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
@@ -42,13 +69,7 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t cnt = static_cast<int64_t>(offsets[f + 1]) - o;
   if (cnt <= 0) return;
   const bool replace = (flags & 1) != 0;
-  // flags & 2: the draws depend on the frontier position too (disjoint trees)
-  const uint64_t salt = (flags & 2) ? mix64(0xD1B54A32D192ED03ull * static_cast<uint64_t>(f + 1)) : 0;
-  // (a captured graph bumps this word between replays.  It is mixed in on its own, not added:
-  // the host seed is rng * 1000003 + hop, so `seed + word` would hand hop h + 1 of one replay the
-  // stream of hop h of the next — ADVICE r3)
-  if (seed_dev) seed = mix64(seed ^ mix64(*seed_dev * 0x9E3779B97F4A7C15ull));
-  const uint64_t key = mix64(seed ^ mix64(static_cast<uint64_t>(v)) ^ salt);
+  const uint64_t key = node_key(seed, seed_dev, v, f, flags);
   if (replace) {  // cnt = k independent draws from the deg in-neighbours (deg > 0 here)
     if (lane < cnt) {
       const uint64_t r = mix64(key + static_cast<uint64_t>(lane));
@@ -60,11 +81,7 @@ __global__ void __launch_bounds__(kBlock)
     return;
   }
   if (deg <= cnt) {  // take every in-neighbour
-    for (int64_t t = lane; t < deg; t += kWave) {
-      src_out[o + t] = row[s + t];
-      dstpos_out[o + t] = static_cast<IdxT>(f);
-      slot_out[o + t] = static_cast<IdxT>(s + t);
-    }
+    copy_all_slots(row, s, deg, o, f, src_out, dstpos_out, slot_out);
     return;
   }
   // Floyd: for j = deg-k .. deg-1: t = U{0..j}; insert t, or j if t is already chosen.  Lane c
@@ -87,6 +104,212 @@ __global__ void __launch_bounds__(kBlock)
     src_out[o + lane] = row[s + mine];
     dstpos_out[o + lane] = static_cast<IdxT>(f);
     slot_out[o + lane] = static_cast<IdxT>(s + mine);
+  }
+}
+
+// ---- weighted draws (the reference's weight_attr -> NeighborSampler.edge_weight,
+// sampler/neighbor_sampler.py:110-114, 559-571).  One wave per frontier node, like the uniform
+// kernel; `weight` is in CSC slot order.  deg <= count without replacement: every in-neighbour, as
+// above.  Otherwise the wave streams ALL deg weights of the node in chunks of 64 slots, kWGroup
+// chunks per group, the loads of the next group in flight while the current one is processed.
+//   without replacement: Efraimidis-Spirakis — slot j gets key log(-ln u_j) - log(w_j) (u_j the
+//     hash of (seed, v, j) in (0, 1)), the k smallest keys are the sample (= successive sampling
+//     in proportion to weight).  The wave keeps the 64 smallest keys seen so far as a sorted list
+//     (lane c = the c-th smallest; the slot rides in the low word of a 64-bit composite key).  A
+//     chunk with no key below the current k-th is skipped on one ballot; otherwise it is bitonic-
+//     sorted descending, merged by an elementwise min against the running list and cleaned up by
+//     6 bitonic stages.  w = 0 keys sort after every positive weight, among themselves by hash.
+//     Lane c < k emits the c-th smallest key: a node's edges come out in key order.
+//   with replacement: pass 1 sums W with the same per-chunk inclusive scans pass 2 repeats, so
+//     the running prefix of pass 2 ends at W bit for bit; lane c's draw targets u_c * W and is
+//     resolved in the chunk whose prefix passes it by a 6-step binary search across the lanes.
+//     A target that rounding puts on a zero-weight slot moves to the last positive slot before
+//     it.  W = 0 (outside the reference's domain): k uniform draws over the deg slots.
+constexpr int kWGroup = 16;
+
+// u in (0, 1) from 23 hash bits: (h + 0.5) / 2^23 is exact in fp32 and never 0 or 1
+__device__ __forceinline__ float open_unit(uint64_t r) {
+  return (static_cast<float>(static_cast<uint32_t>(r >> 41)) + 0.5f) * 0x1p-23f;
+}
+
+// 64-bit composite key of slot j: high word = the ES key as an order-preserving uint (log2 in
+// place of ln: a positive scale and a common shift, the same order), or +inf plus 23 hash bits
+// for w = 0 (after every positive weight, ties broken by hash); low word = j
+__device__ __forceinline__ uint64_t es_key(float w, uint64_t r, uint32_t j) {
+  const float k = log2f(-log2f(open_unit(r))) - log2f(w);
+  const uint32_t b = __float_as_uint(k);
+  const uint32_t ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  const uint32_t hi = w > 0.f ? ord : (0xFF800000u | static_cast<uint32_t>(r & 0x7FFFFFu));
+  return (static_cast<uint64_t>(hi) << 32) | j;
+}
+
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t x, int m) {
+  return static_cast<uint64_t>(__shfl_xor(static_cast<unsigned long long>(x), m, kWave));
+}
+
+// bitonic sort of one key per lane across the wave (descending: lane 0 holds the largest)
+__device__ __forceinline__ uint64_t wave_sort_desc(uint64_t x) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int size = 2; size <= kWave; size <<= 1) {
+#pragma unroll
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      const uint64_t y = shfl_xor_u64(x, stride);
+      const bool keep_max = ((lane & stride) == 0) == ((lane & size) == 0);
+      x = keep_max ? (x > y ? x : y) : (x < y ? x : y);
+    }
+  }
+  return x;
+}
+
+// run ascending, c descending: min(run, c) lane by lane holds the 64 smallest of both as a
+// bitonic sequence; 6 half-cleaner stages sort it ascending
+__device__ __forceinline__ uint64_t merge_smallest(uint64_t run, uint64_t c) {
+  uint64_t x = run < c ? run : c;
+  const int lane = lane_id();
+#pragma unroll
+  for (int stride = kWave >> 1; stride > 0; stride >>= 1) {
+    const uint64_t y = shfl_xor_u64(x, stride);
+    x = ((lane & stride) == 0) ? (x < y ? x : y) : (x > y ? x : y);
+  }
+  return x;
+}
+
+__device__ __forceinline__ float wave_inclusive_scan(float x) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const float y = __shfl_up(x, d, kWave);
+    if (lane >= d) x += y;
+  }
+  return x;
+}
+
+// weights of slots [g, g + kWGroup * 64) of the node (0 past deg)
+__device__ __forceinline__ void load_weight_group(const float* __restrict__ wv, int64_t deg,
+                                                  int64_t g, float (&w)[kWGroup]) {
+#pragma unroll
+  for (int i = 0; i < kWGroup; ++i) {
+    const int64_t j = g + i * kWave + lane_id();
+    w[i] = j < deg ? wv[j] : 0.f;
+  }
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    sample_neighbors_weighted_kernel(const IdxT* __restrict__ colptr,
+                                     const IdxT* __restrict__ row,
+                                     const float* __restrict__ weight,
+                                     const IdxT* __restrict__ frontier, int64_t n_frontier,
+                                     const IdxT* __restrict__ offsets, uint64_t seed, int flags,
+                                     const uint64_t* __restrict__ seed_dev,
+                                     IdxT* __restrict__ src_out, IdxT* __restrict__ dstpos_out,
+                                     IdxT* __restrict__ slot_out) {
+  constexpr int64_t kGroupSlots = kWGroup * kWave;
+  const int lane = lane_id();
+  const int64_t f = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+  if (f >= n_frontier) return;
+  const int64_t v = frontier[f];
+  const int64_t s = colptr[v];
+  const int64_t deg = static_cast<int64_t>(colptr[v + 1]) - s;
+  const int64_t o = offsets[f];
+  const int64_t cnt = static_cast<int64_t>(offsets[f + 1]) - o;
+  if (cnt <= 0) return;
+  const bool replace = (flags & 1) != 0;
+  if (!replace && deg <= cnt) {  // take every in-neighbour
+    copy_all_slots(row, s, deg, o, f, src_out, dstpos_out, slot_out);
+    return;
+  }
+  const uint64_t key = node_key(seed, seed_dev, v, f, flags);
+  const float* wv = weight + s;
+  float wn[kWGroup];
+  int64_t pick = 0;  // lane c < cnt: the chosen slot, relative to s
+  if (!replace) {
+    const int k = static_cast<int>(cnt);
+    uint64_t run = ~0ull;  // lane c: the c-th smallest key so far
+    uint64_t thr = ~0ull;  // the k-th smallest (wave-uniform)
+    load_weight_group(wv, deg, 0, wn);
+    for (int64_t g = 0; g < deg; g += kGroupSlots) {
+      float w[kWGroup];
+#pragma unroll
+      for (int i = 0; i < kWGroup; ++i) w[i] = wn[i];
+      if (g + kGroupSlots < deg) load_weight_group(wv, deg, g + kGroupSlots, wn);
+#pragma unroll
+      for (int i = 0; i < kWGroup; ++i) {
+        const int64_t j = g + i * kWave + lane;
+        const uint64_t kj = j < deg ? es_key(w[i], mix64(key + static_cast<uint64_t>(j)),
+                                             static_cast<uint32_t>(j))
+                                    : ~0ull;
+        if (__ballot(kj < thr) == 0) continue;  // nothing below the current k-th
+        run = merge_smallest(run, wave_sort_desc(kj));
+        thr = static_cast<uint64_t>(bcast_uniform(static_cast<int64_t>(run), k - 1));
+      }
+    }
+    pick = static_cast<int64_t>(static_cast<uint32_t>(run));
+  } else {
+    // pass 1: W as the running sum of the chunks' scan totals
+    float base = 0.f;
+    load_weight_group(wv, deg, 0, wn);
+    for (int64_t g = 0; g < deg; g += kGroupSlots) {
+      float w[kWGroup];
+#pragma unroll
+      for (int i = 0; i < kWGroup; ++i) w[i] = wn[i];
+      if (g + kGroupSlots < deg) load_weight_group(wv, deg, g + kGroupSlots, wn);
+#pragma unroll
+      for (int i = 0; i < kWGroup; ++i)
+        base = base + bcast_uniform(wave_inclusive_scan(w[i]), kWave - 1);
+    }
+    const float W = base;
+    const uint64_t r = mix64(key + static_cast<uint64_t>(lane));  // draw `lane`
+    if (!(W > 0.f)) {  // every weight 0: uniform over the deg slots
+      pick = static_cast<int64_t>(__umul64hi(r, static_cast<uint64_t>(deg)));
+    } else {
+      // pass 2: the same prefix sums; resolve every target in the chunk whose prefix passes it
+      const float target = open_unit(r) * W;
+      bool open = lane < cnt;
+      int64_t last_pos = -1;  // the last positive-weight slot so far (wave-uniform)
+      pick = -1;
+      base = 0.f;
+      load_weight_group(wv, deg, 0, wn);
+      for (int64_t g = 0; g < deg; g += kGroupSlots) {
+        float w[kWGroup];
+#pragma unroll
+        for (int i = 0; i < kWGroup; ++i) w[i] = wn[i];
+        if (g + kGroupSlots < deg) load_weight_group(wv, deg, g + kGroupSlots, wn);
+#pragma unroll
+        for (int i = 0; i < kWGroup; ++i) {
+          const float P = base + wave_inclusive_scan(w[i]);
+          const float end = bcast_uniform(P, kWave - 1);
+          const uint64_t positive = __ballot(w[i] > 0.f);
+          const bool here = open && target < end;
+          if (__ballot(here) != 0) {
+            int p = 0;  // the first lane whose prefix exceeds the target
+#pragma unroll
+            for (int step = kWave >> 1; step > 0; step >>= 1)
+              if (bcast_lane(P, p + step - 1) <= target) p += step;
+            const float wp = bcast_lane(w[i], p);
+            if (here) {
+              int q = p;
+              if (!(wp > 0.f)) {  // rounding landed on a zero-weight slot
+                const uint64_t below = positive & ((1ull << p) - 1);
+                q = below ? 63 - __clzll(static_cast<long long>(below)) : -1;
+              }
+              pick = q >= 0 ? g + i * kWave + q : last_pos;
+              open = false;
+            }
+          }
+          if (positive) last_pos = g + i * kWave + 63 - __clzll(static_cast<long long>(positive));
+          base = end;
+        }
+      }
+      if (open || pick < 0) pick = last_pos;  // u * W rounded up to W
+    }
+  }
+  if (lane < cnt) {
+    const int64_t t = s + pick;
+    src_out[o + lane] = row[t];
+    dstpos_out[o + lane] = static_cast<IdxT>(f);
+    slot_out[o + lane] = static_cast<IdxT>(t);
   }
 }
 
@@ -204,6 +427,32 @@ int pygamd_sample_neighbors(const void* colptr, const void* row, int idx_dtype,
                        as_stream(stream), static_cast<const IdxT*>(colptr),
                        static_cast<const IdxT*>(row), static_cast<const IdxT*>(frontier),
                        n_frontier, static_cast<const IdxT*>(offsets), seed, flags, seed_dev,
+                       static_cast<IdxT*>(src_out), static_cast<IdxT*>(dstpos_out),
+                       static_cast<IdxT*>(slot_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_sample_neighbors_weighted(const void* colptr, const void* row, int idx_dtype,
+                                     const float* weight_csc, const void* frontier,
+                                     int64_t n_frontier, const void* offsets,
+                                     int64_t max_per_node, uint64_t seed, int flags,
+                                     const uint64_t* seed_dev, void* src_out, void* dstpos_out,
+                                     void* slot_out, void* stream) {
+  if (n_frontier < 0 || !weight_csc) return PYGAMD_ERR_INVALID_ARG;
+  if (max_per_node > kMaxFanout) return PYGAMD_ERR_UNSUPPORTED;  // one key per lane
+  if (n_frontier == 0) return PYGAMD_OK;
+  if (!colptr || !row || !frontier || !offsets || !src_out || !dstpos_out || !slot_out)
+    return PYGAMD_ERR_INVALID_ARG;
+  if ((flags & 1) && max_per_node <= 0) return PYGAMD_ERR_INVALID_ARG;  // "all": no replacement
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid = static_cast<unsigned>(ceil_div(n_frontier, kWavesPerBlock));
+    hipLaunchKernelGGL((sample_neighbors_weighted_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(colptr),
+                       static_cast<const IdxT*>(row), weight_csc,
+                       static_cast<const IdxT*>(frontier), n_frontier,
+                       static_cast<const IdxT*>(offsets), seed, flags, seed_dev,
                        static_cast<IdxT*>(src_out), static_cast<IdxT*>(dstpos_out),
                        static_cast<IdxT*>(slot_out));
     PYGAMD_LAUNCH_CHECK();

@@ -80,6 +80,10 @@ class NeighborLoader:
             waits on.
         replace, disjoint, subgraph_type: the sampler options of the reference's loader
             (loader/neighbor_loader.py:209-233; see :class:`~.sampler.NeighborSampler`).
+        edge_weight: ``[E]`` edge weights for biased sampling, the tensor the reference's
+            ``weight_attr`` names (loader/neighbor_loader.py:168-174; see
+            :class:`~.sampler.NeighborSampler`).  The slot layout (:meth:`collate_slots`) stays
+            uniform and refuses it.
     """
 
     def __init__(self, x: Tensor, edge_index: Tensor, num_neighbors: List[int],
@@ -87,7 +91,7 @@ class NeighborLoader:
                  input_nodes: Optional[Tensor] = None, shuffle: bool = False,
                  drop_last: bool = False, seed: int = 0, prefetch: int = 0,
                  replace: bool = False, disjoint: bool = False,
-                 subgraph_type: str = 'directional'):
+                 subgraph_type: str = 'directional', edge_weight: Optional[Tensor] = None):
         self.prefetch = int(prefetch)
         self._side = None
         self._slots = None  # the static-shape sampler of `collate_slots`, built on first use
@@ -95,7 +99,7 @@ class NeighborLoader:
         self.num_nodes = x.size(0)
         self.sampler = NeighborSampler(edge_index, self.num_nodes, num_neighbors, seed=seed,
                                        replace=replace, disjoint=disjoint,
-                                       subgraph_type=subgraph_type)
+                                       subgraph_type=subgraph_type, edge_weight=edge_weight)
         if input_nodes is None:
             input_nodes = torch.arange(self.num_nodes, device=x.device)
         self.input_nodes = input_nodes.to(x.device)
@@ -142,6 +146,9 @@ class NeighborLoader:
         — ``slots.SlotTrainer`` reads them from ``self.y`` inside its loss launch)."""
         from .slots import SlotPlan, SlotSampler
         smp = self.sampler
+        if smp.edge_weight is not None:
+            raise NotImplementedError("'collate_slots' samples uniformly: weighted sampling "
+                                      "(edge_weight) is served by 'collate' / 'collate_padded'")
         if smp.replace or smp.disjoint or smp.subgraph_type != 'directional' \
                 or any(k < 1 for k in smp.num_neighbors):
             raise ValueError("'collate_slots' covers bounded fan-outs, directional, non-disjoint, "
