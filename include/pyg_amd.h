@@ -605,6 +605,51 @@ PYGAMD_API int pygamd_sample_neighbors_weighted(const void* colptr, const void* 
                                                 const uint64_t* seed_dev, void* src_out,
                                                 void* dstpos_out, void* slot_out, void* stream);
 
+/* Temporal variant: the reference's NeighborLoader(..., time_attr=..., input_time=...,
+ * temporal_strategy=...) -> torch.ops.pyg.neighbor_sample(..., node_time, edge_time, seed_time,
+ * ..., temporal_strategy) (sampler/neighbor_sampler.py:550-571).  Two launches per hop, window
+ * then draw.  The CSC must be sorted like the reference's sort_csc (sampler/utils.py:24-42):
+ * inside every column the slots ascend in time, ties in edge_index order (a stable lexsort).
+ * The time key of slot j is time[row[j]] (level 0: node-level time, `time` [N]) or time[j]
+ * (level 1: edge-level time already in CSC slot order, `time` [E]); int64.
+ * pygamd_sample_temporal_window: for frontier node v = frontier[f] with seed time
+ * t = frontier_time[f] (int64 [n_frontier], the seed time of f's tree: every node of a tree is
+ * bounded by its root's time, not its own), the in-edge in slot j is eligible iff key(j) <= t;
+ * the eligible slots are the prefix [s, hi) of v's column [s, e), hi the upper bound of t (one
+ * wave per node, ceil(log64(deg)) rounds of 64 probes and one ballot).  Then
+ *   strategy 0 ('uniform'): lo = s;
+ *   strategy 1 ('last'):    lo = max(s, hi - k) for k >= 0, lo = s for k < 0;
+ * and cnt[f] is pygamd_sample_counts' rule on the window w = hi - lo: min(w, k) (k < 0: w;
+ * replace != 0 and k >= 0: k wherever w > 0, else 0).  lo_out / hi_out / cnt_out are [n_frontier]
+ * in idx_dtype.  `n_valid` (device int64, may be NULL): entries past *n_valid get lo = hi = cnt = 0.
+ * pygamd_sample_neighbors_temporal: the uniform draws of pygamd_sample_neighbors (same flags,
+ * seed, seed_dev, outputs) on the slot range [lo[f], hi[f]) in place of the whole column, offsets
+ * being the exclusive scan of cnt: Floyd without replacement (every slot of the window if it
+ * holds at most cnt), cnt independent draws with replacement, the whole window for k < 0.  The
+ * hash stream is the plain kernel's, so a window equal to the column draws, bit for bit, what
+ * pygamd_sample_neighbors draws for the same (seed, node, frontier position).  With 'last' and
+ * no replacement the node takes its min(k, w) most recent eligible edges (deterministic); with
+ * replacement k draws among them.
+ * Rejected before any launch: NULL time / frontier_time / lo / hi (and, when n_frontier > 0, any
+ * other NULL pointer) or n_frontier < 0 -> PYGAMD_ERR_INVALID_ARG; a level or strategy other than
+ * 0 / 1 -> PYGAMD_ERR_INVALID_ARG; k (max_per_node) > pygamd_sample_max_fanout() ->
+ * PYGAMD_ERR_UNSUPPORTED; replacement without a bounded fan-out (k < 0 for the window,
+ * max_per_node <= 0 for the draw) -> PYGAMD_ERR_INVALID_ARG; an unknown idx_dtype ->
+ * PYGAMD_ERR_INVALID_ARG.                                                                       */
+PYGAMD_API int pygamd_sample_temporal_window(const void* colptr, const void* row, int idx_dtype,
+                                             const int64_t* time, int level,
+                                             const void* frontier, const int64_t* frontier_time,
+                                             int64_t n_frontier, int64_t k, int replace,
+                                             int strategy, const int64_t* n_valid, void* lo_out,
+                                             void* hi_out, void* cnt_out, void* stream);
+PYGAMD_API int pygamd_sample_neighbors_temporal(const void* row, int idx_dtype,
+                                                const void* frontier, int64_t n_frontier,
+                                                const void* lo, const void* hi,
+                                                const void* offsets, int64_t max_per_node,
+                                                uint64_t seed, int flags,
+                                                const uint64_t* seed_dev, void* src_out,
+                                                void* dstpos_out, void* slot_out, void* stream);
+
 /* cnt[f] = min(deg(frontier[f]), k) (k < 0: deg; replace != 0 and k >= 0: k wherever deg > 0, else
  * 0) — the per-node sample counts of one hop.
  * `n_valid` (device int64, may be NULL): only the first *n_valid entries of the fixed-capacity

@@ -139,6 +139,10 @@ SIGNATURES = {
                                         _P, _P, _P, _P, _P]),
     'pygamd_sample_neighbors_weighted': (c_int, [_P, _P, c_int, _P, _P, c_int64, _P, c_int64,
                                                  c_uint64, c_int, _P, _P, _P, _P, _P]),
+    'pygamd_sample_temporal_window': (c_int, [_P, _P, c_int, _P, c_int, _P, _P, c_int64, c_int64,
+                                              c_int, c_int, _P, _P, _P, _P, _P]),
+    'pygamd_sample_neighbors_temporal': (c_int, [_P, c_int, _P, c_int64, _P, _P, _P, c_int64,
+                                                 c_uint64, c_int, _P, _P, _P, _P, _P]),
     'pygamd_slots_max_fanout': (c_int, []),
     'pygamd_slots_max_hops': (c_int, []),
     'pygamd_slots_seed': (c_int, [_P, c_int, c_int64, _P, _P, _P, _P]),

@@ -1748,6 +1748,54 @@ def sample_counts(colptr: Tensor, frontier: Tensor, k: int,
     return cnt
 
 
+def sample_temporal_window(colptr: Tensor, row: Tensor, time: Tensor, frontier: Tensor,
+                           frontier_time: Tensor, k: int, edge_level: bool = False,
+                           replace: bool = False, last: bool = False,
+                           n_valid: Optional[Tensor] = None):
+    """(lo, hi, cnt) per frontier entry (``pygamd_sample_temporal_window``): the eligible window
+    ``[s, hi)`` of the node's time-sorted column (time key <= ``frontier_time``, int64 [F]), narrowed
+    to its last ``k`` slots for ``last`` (``k >= 0``), and :func:`sample_counts`' rule on it.
+    ``time``: int64 node times ``[N]``, or edge times ``[E]`` in CSC slot order with
+    ``edge_level``."""
+    _require_device(colptr, row, time, frontier, frontier_time, n_valid)
+    if time.dtype != torch.int64 or frontier_time.dtype != torch.int64:
+        raise ValueError("'time' and 'frontier_time' must be int64")
+    if frontier_time.numel() != frontier.numel():
+        raise ValueError("'frontier_time' needs one entry per frontier node")
+    time, frontier_time = time.contiguous(), frontier_time.contiguous()
+    lib = _lib.load()
+    lo = torch.empty_like(frontier)
+    hi = torch.empty_like(frontier)
+    cnt = torch.empty_like(frontier)
+    check(lib.pygamd_sample_temporal_window(
+        _p(colptr), _p(row), _idx_dtype(colptr), _p(time), int(edge_level), _p(frontier),
+        _p(frontier_time), frontier.numel(), k, int(replace and k >= 0), int(last), _p(n_valid),
+        _p(lo), _p(hi), _p(cnt), _stream(colptr)), 'sample_temporal_window')
+    return lo, hi, cnt
+
+
+def sample_neighbors_temporal(row: Tensor, frontier: Tensor, lo: Tensor, hi: Tensor,
+                              offsets: Tensor, total: int, max_per_node: int, seed: int,
+                              zero_fill: bool = False, replace: bool = False,
+                              salt_position: bool = False, seed_dev: Optional[Tensor] = None):
+    """:func:`sample_neighbors` on the windows ``[lo, hi)`` of :func:`sample_temporal_window`
+    (``pygamd_sample_neighbors_temporal``): the same draws, so a window that is a node's whole
+    column gives the plain sampler's edges bit for bit."""
+    _require_device(row, frontier, lo, hi, offsets)
+    lib = _lib.load()
+    alloc = torch.zeros if zero_fill else torch.empty
+    src = alloc(total, dtype=row.dtype, device=row.device)
+    dstpos = alloc(total, dtype=row.dtype, device=row.device)
+    slot = alloc(total, dtype=row.dtype, device=row.device)
+    if total > 0:
+        check(lib.pygamd_sample_neighbors_temporal(
+            _p(row), _idx_dtype(row), _p(frontier), frontier.numel(), _p(lo), _p(hi), _p(offsets),
+            max_per_node, seed & 0xFFFFFFFFFFFFFFFF, int(replace) | (2 if salt_position else 0),
+            _p(seed_dev), _p(src), _p(dstpos), _p(slot), _stream(row)),
+            'sample_neighbors_temporal')
+    return src, dstpos, slot
+
+
 def relabel_new_nodes(src_global: Tensor, local_map: Tensor, base: int):
     """Assigns local ids base, base+1, ... to the sources not yet in `local_map` (order of first
     appearance) and returns (new_nodes, row_local).  One host sync (the number of new nodes)."""

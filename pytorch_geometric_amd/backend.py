@@ -869,7 +869,8 @@ _sampler_cls = None
 
 def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: bool = False,
                      disjoint: bool = False, subgraph_type='directional',
-                     weight_attr: Optional[str] = None):
+                     weight_attr: Optional[str] = None, time_attr: Optional[str] = None,
+                     temporal_strategy: str = 'uniform'):
     """A ``torch_geometric.sampler.BaseSampler`` (sampler/base.py:932-998) whose
     ``sample_from_nodes(NodeSamplerInput) -> SamplerOutput`` runs on the GPU
     (:class:`pytorch_geometric_amd.sampler.NeighborSampler`), so that the reference's
@@ -881,7 +882,11 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     (loader/neighbor_loader.py:209-233).  ``weight_attr``: the name of an ``[E]`` edge attribute
     of ``data`` holding non-negative sampling weights (loader/neighbor_loader.py:168-174:
     neighbours are more likely to get sampled the higher their edge weights); it needs the
-    ``Data`` form."""
+    ``Data`` form.  ``time_attr``: the name of a node-level (``data.is_node_attr``) or edge-level
+    (``data.is_edge_attr``) integer time attribute of ``data`` (sampler/neighbor_sampler.py:79-108)
+    with ``temporal_strategy`` (``'uniform'`` | ``'last'``): temporal sampling, always disjoint;
+    the reference's ``NodeLoader`` passes its ``input_time`` as ``NodeSamplerInput.time`` and reads
+    ``seed_time`` from ``metadata[1]``.  It needs the ``Data`` form too."""
     global _sampler_cls
     import torch_geometric.sampler as pyg_sampler
     from .sampler import NeighborSampler
@@ -890,13 +895,21 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
         class MI355XNeighborSampler(pyg_sampler.BaseSampler):
             def __init__(self, edge_index, num_nodes, num_neighbors, seed=0, replace=False,
                          disjoint=False, subgraph_type='directional', edge_weight=None,
-                         weight_attr=None):
+                         weight_attr=None, node_time=None, edge_time=None, time_attr=None,
+                         temporal_strategy='uniform'):
                 self.impl = NeighborSampler(edge_index, num_nodes, num_neighbors, seed=seed,
                                             output_cls=pyg_sampler.SamplerOutput,
                                             replace=replace, disjoint=disjoint,
                                             subgraph_type=subgraph_type,
-                                            edge_weight=edge_weight)
+                                            edge_weight=edge_weight, node_time=node_time,
+                                            edge_time=edge_time,
+                                            temporal_strategy=temporal_strategy)
                 self.weight_attr = weight_attr
+                # the reference's NeighborSampler attributes (sampler/neighbor_sampler.py:79-108,
+                # 386-395); the impl keeps its own int64 copies in CSC order
+                self.time_attr, self.temporal_strategy = time_attr, temporal_strategy
+                self.node_time, self.edge_time = node_time, edge_time
+                self.is_temporal = node_time is not None or edge_time is not None
                 self.edge_weight = self.impl.edge_weight  # fp32, CSC order
                 self.num_neighbors = list(num_neighbors)
                 self.replace, self.disjoint = self.impl.replace, self.impl.disjoint
@@ -913,21 +926,31 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
                 return None  # `edge` already indexes the caller's edge_index
 
         _sampler_cls = MI355XNeighborSampler
-    edge_weight = None
+    edge_weight = node_time = edge_time = None
     if isinstance(data, (tuple, list)):
-        if weight_attr is not None:
-            raise ValueError("'weight_attr' names an edge attribute of a 'Data' object; the "
-                             "(edge_index, num_nodes) form has none")
+        if weight_attr is not None or time_attr is not None:
+            raise ValueError("'weight_attr' and 'time_attr' name attributes of a 'Data' object; "
+                             "the (edge_index, num_nodes) form has none")
         edge_index, num_nodes = data
     else:
         edge_index, num_nodes = data.edge_index, data.num_nodes
         if weight_attr is not None:
             edge_weight = data[weight_attr]
+        if time_attr is not None:
+            if data.is_node_attr(time_attr):
+                node_time = data[time_attr]
+            elif data.is_edge_attr(time_attr):
+                edge_time = data[time_attr]
+            else:  # (the reference's wording, sampler/neighbor_sampler.py:95-99)
+                raise ValueError(f"The time attribute '{time_attr}' is neither a node-level or "
+                                 f"edge-level attribute")
     if not (isinstance(edge_index, Tensor) and edge_index.is_cuda):
         raise ValueError("the sampler needs 'edge_index' on the HIP device (there is no CPU "
                          "fallback): move the data with `.to('cuda')` first")
     return _sampler_cls(edge_index, int(num_nodes), num_neighbors, seed, replace, disjoint,
-                        subgraph_type, edge_weight=edge_weight, weight_attr=weight_attr)
+                        subgraph_type, edge_weight=edge_weight, weight_attr=weight_attr,
+                        node_time=node_time, edge_time=edge_time, time_attr=time_attr,
+                        temporal_strategy=temporal_strategy)
 
 
 def _wrap_linear_forward(cls):

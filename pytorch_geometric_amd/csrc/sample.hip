@@ -51,25 +51,17 @@ __device__ __forceinline__ uint64_t node_key(uint64_t seed, const uint64_t* __re
   return mix64(seed ^ mix64(static_cast<uint64_t>(v)) ^ salt);
 }
 
+// The uniform draw of one frontier node over the slot range [s, s + deg): cnt = offsets[f + 1] -
+// offsets[f] > 0 edges written from position o.  Shared by the plain kernel (the node's whole
+// column) and the temporal one (its eligible window), so the same (key, s, deg, cnt) gives the
+// same edges bit for bit.
 template <typename IdxT>
-__global__ void __launch_bounds__(kBlock)
-    sample_neighbors_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
-                            const IdxT* __restrict__ frontier, int64_t n_frontier,
-                            const IdxT* __restrict__ offsets, uint64_t seed, int flags,
-                            const uint64_t* __restrict__ seed_dev,
-                            IdxT* __restrict__ src_out, IdxT* __restrict__ dstpos_out,
-                            IdxT* __restrict__ slot_out) {
+__device__ __forceinline__ void draw_uniform(const IdxT* __restrict__ row, int64_t s, int64_t deg,
+                                             int64_t o, int64_t cnt, int64_t f, uint64_t key,
+                                             bool replace, IdxT* __restrict__ src_out,
+                                             IdxT* __restrict__ dstpos_out,
+                                             IdxT* __restrict__ slot_out) {
   const int lane = lane_id();
-  const int64_t f = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
-  if (f >= n_frontier) return;
-  const int64_t v = frontier[f];
-  const int64_t s = colptr[v];
-  const int64_t deg = static_cast<int64_t>(colptr[v + 1]) - s;
-  const int64_t o = offsets[f];
-  const int64_t cnt = static_cast<int64_t>(offsets[f + 1]) - o;
-  if (cnt <= 0) return;
-  const bool replace = (flags & 1) != 0;
-  const uint64_t key = node_key(seed, seed_dev, v, f, flags);
   if (replace) {  // cnt = k independent draws from the deg in-neighbours (deg > 0 here)
     if (lane < cnt) {
       const uint64_t r = mix64(key + static_cast<uint64_t>(lane));
@@ -105,6 +97,127 @@ __global__ void __launch_bounds__(kBlock)
     dstpos_out[o + lane] = static_cast<IdxT>(f);
     slot_out[o + lane] = static_cast<IdxT>(s + mine);
   }
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    sample_neighbors_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
+                            const IdxT* __restrict__ frontier, int64_t n_frontier,
+                            const IdxT* __restrict__ offsets, uint64_t seed, int flags,
+                            const uint64_t* __restrict__ seed_dev,
+                            IdxT* __restrict__ src_out, IdxT* __restrict__ dstpos_out,
+                            IdxT* __restrict__ slot_out) {
+  const int64_t f = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+  if (f >= n_frontier) return;
+  const int64_t v = frontier[f];
+  const int64_t s = colptr[v];
+  const int64_t deg = static_cast<int64_t>(colptr[v + 1]) - s;
+  const int64_t o = offsets[f];
+  const int64_t cnt = static_cast<int64_t>(offsets[f + 1]) - o;
+  if (cnt <= 0) return;
+  const uint64_t key = node_key(seed, seed_dev, v, f, flags);
+  draw_uniform(row, s, deg, o, cnt, f, key, (flags & 1) != 0, src_out, dstpos_out, slot_out);
+}
+
+// ---- temporal draws (the reference's NeighborLoader(..., time_attr=..., temporal_strategy=...)
+// -> torch.ops.pyg.neighbor_sample(..., node_time, edge_time, seed_time, ..., temporal_strategy),
+// sampler/neighbor_sampler.py:550-571).  The caller's CSC is sorted like the reference's sort_csc
+// (sampler/utils.py:24-42): inside every column the slots ascend in time (the source node's time
+// or the edge's), ties in edge_index order.  The in-edges of frontier node v (in tree t) that are
+// eligible, time <= seed_time[t], are then a PREFIX [s, hi) of its column.
+//
+// Window kernel: one wave per frontier node.  hi is found by a wave-cooperative search: the
+// candidate range [a, b] (key(a - 1) <= t < key(b), with key(s - 1) = -inf, key(end) = +inf) is
+// cut into 64 chunks of `step` slots, lane l probes the last slot of chunk l, one ballot gives the
+// first chunk whose probe is past t and the range shrinks to that chunk: ceil(log64(deg)) steps
+// (deg <= 64: one load per lane and one ballot).  'last' then narrows the window to its last k
+// slots, lo = max(s, hi - k) (k >= 0); 'uniform' keeps lo = s.  cnt is pygamd_sample_counts'
+// rule applied to the window hi - lo.
+template <typename IdxT>
+__device__ __forceinline__ int64_t slot_time_of(const IdxT* __restrict__ row,
+                                                const int64_t* __restrict__ time, int level,
+                                                int64_t j) {
+  return level == 0 ? time[static_cast<int64_t>(row[j])] : time[j];
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    sample_temporal_window_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
+                                  const int64_t* __restrict__ time, int level,
+                                  const IdxT* __restrict__ frontier,
+                                  const int64_t* __restrict__ frontier_time, int64_t n_frontier,
+                                  int64_t k, int replace, int last,
+                                  const int64_t* __restrict__ n_valid, IdxT* __restrict__ lo_out,
+                                  IdxT* __restrict__ hi_out, IdxT* __restrict__ cnt_out) {
+  const int lane = lane_id();
+  const int64_t f = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+  if (f >= n_frontier) return;
+  if (n_valid && f >= *n_valid) {  // padding of a fixed-capacity frontier
+    if (lane == 0) {
+      lo_out[f] = static_cast<IdxT>(0);
+      hi_out[f] = static_cast<IdxT>(0);
+      cnt_out[f] = static_cast<IdxT>(0);
+    }
+    return;
+  }
+  const int64_t v = frontier[f];
+  const int64_t s = colptr[v];
+  const int64_t end = colptr[v + 1];
+  const int64_t t = frontier_time[f];
+  int64_t a = s, b = end;  // the answer lies in [a, b]
+  while (a < b) {
+    const int64_t len = b - a;
+    const int64_t step = (len + kWave - 1) / kWave;
+    const int64_t q = a + (lane + 1) * step - 1;  // the last slot of chunk `lane`
+    const bool past = q >= b || slot_time_of(row, time, level, q) > t;
+    const uint64_t m = __ballot(past);
+    if (m == 0) {  // every probe is eligible: the last one is b - 1
+      a = b;
+      break;
+    }
+    const int p = __ffsll(static_cast<unsigned long long>(m)) - 1;
+    const int64_t qp = a + (static_cast<int64_t>(p) + 1) * step - 1;
+    a = a + static_cast<int64_t>(p) * step;
+    b = qp < b ? qp : b;
+  }
+  const int64_t hi = a;
+  const int64_t lo = (last && k >= 0 && hi - k > s) ? hi - k : s;
+  const int64_t w = hi - lo;
+  int64_t c;
+  if (replace && k >= 0) {
+    c = w > 0 ? k : 0;
+  } else {
+    c = (k >= 0 && w > k) ? k : w;
+  }
+  if (lane == 0) {
+    lo_out[f] = static_cast<IdxT>(lo);
+    hi_out[f] = static_cast<IdxT>(hi);
+    cnt_out[f] = static_cast<IdxT>(c);
+  }
+}
+
+// The draws of one hop over the windows [lo[f], hi[f]): draw_uniform on the window, with the hash
+// stream of the plain kernel, so a window that is the whole column draws what the plain kernel
+// draws.
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    sample_neighbors_temporal_kernel(const IdxT* __restrict__ row,
+                                     const IdxT* __restrict__ frontier, int64_t n_frontier,
+                                     const IdxT* __restrict__ lo, const IdxT* __restrict__ hi,
+                                     const IdxT* __restrict__ offsets, uint64_t seed, int flags,
+                                     const uint64_t* __restrict__ seed_dev,
+                                     IdxT* __restrict__ src_out, IdxT* __restrict__ dstpos_out,
+                                     IdxT* __restrict__ slot_out) {
+  const int64_t f = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+  if (f >= n_frontier) return;
+  const int64_t o = offsets[f];
+  const int64_t cnt = static_cast<int64_t>(offsets[f + 1]) - o;
+  if (cnt <= 0) return;
+  const int64_t v = frontier[f];
+  const int64_t s = lo[f];
+  const int64_t deg = static_cast<int64_t>(hi[f]) - s;
+  const uint64_t key = node_key(seed, seed_dev, v, f, flags);
+  draw_uniform(row, s, deg, o, cnt, f, key, (flags & 1) != 0, src_out, dstpos_out, slot_out);
 }
 
 // ---- weighted draws (the reference's weight_attr -> NeighborSampler.edge_weight,
@@ -452,6 +565,57 @@ int pygamd_sample_neighbors_weighted(const void* colptr, const void* row, int id
                        as_stream(stream), static_cast<const IdxT*>(colptr),
                        static_cast<const IdxT*>(row), weight_csc,
                        static_cast<const IdxT*>(frontier), n_frontier,
+                       static_cast<const IdxT*>(offsets), seed, flags, seed_dev,
+                       static_cast<IdxT*>(src_out), static_cast<IdxT*>(dstpos_out),
+                       static_cast<IdxT*>(slot_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_sample_temporal_window(const void* colptr, const void* row, int idx_dtype,
+                                  const int64_t* time, int level, const void* frontier,
+                                  const int64_t* frontier_time, int64_t n_frontier, int64_t k,
+                                  int replace, int strategy, const int64_t* n_valid,
+                                  void* lo_out, void* hi_out, void* cnt_out, void* stream) {
+  if (n_frontier < 0 || !time || !frontier_time) return PYGAMD_ERR_INVALID_ARG;
+  if ((level != 0 && level != 1) || (strategy != 0 && strategy != 1))
+    return PYGAMD_ERR_INVALID_ARG;
+  if (k > kMaxFanout) return PYGAMD_ERR_UNSUPPORTED;
+  if (replace && k < 0) return PYGAMD_ERR_INVALID_ARG;  // "all": no replacement
+  if (n_frontier == 0) return PYGAMD_OK;
+  if (!colptr || !row || !frontier || !lo_out || !hi_out || !cnt_out)
+    return PYGAMD_ERR_INVALID_ARG;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid = static_cast<unsigned>(ceil_div(n_frontier, kWavesPerBlock));
+    hipLaunchKernelGGL((sample_temporal_window_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(colptr),
+                       static_cast<const IdxT*>(row), time, level,
+                       static_cast<const IdxT*>(frontier), frontier_time, n_frontier, k,
+                       replace ? 1 : 0, strategy, n_valid, static_cast<IdxT*>(lo_out),
+                       static_cast<IdxT*>(hi_out), static_cast<IdxT*>(cnt_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_sample_neighbors_temporal(const void* row, int idx_dtype, const void* frontier,
+                                     int64_t n_frontier, const void* lo, const void* hi,
+                                     const void* offsets, int64_t max_per_node, uint64_t seed,
+                                     int flags, const uint64_t* seed_dev, void* src_out,
+                                     void* dstpos_out, void* slot_out, void* stream) {
+  if (n_frontier < 0 || !lo || !hi) return PYGAMD_ERR_INVALID_ARG;
+  if (max_per_node > kMaxFanout) return PYGAMD_ERR_UNSUPPORTED;
+  if ((flags & 1) && max_per_node <= 0) return PYGAMD_ERR_INVALID_ARG;  // "all": no replacement
+  if (n_frontier == 0) return PYGAMD_OK;
+  if (!row || !frontier || !offsets || !src_out || !dstpos_out || !slot_out)
+    return PYGAMD_ERR_INVALID_ARG;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid = static_cast<unsigned>(ceil_div(n_frontier, kWavesPerBlock));
+    hipLaunchKernelGGL((sample_neighbors_temporal_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(row),
+                       static_cast<const IdxT*>(frontier), n_frontier,
+                       static_cast<const IdxT*>(lo), static_cast<const IdxT*>(hi),
                        static_cast<const IdxT*>(offsets), seed, flags, seed_dev,
                        static_cast<IdxT*>(src_out), static_cast<IdxT*>(dstpos_out),
                        static_cast<IdxT*>(slot_out));

@@ -38,10 +38,11 @@ class Batch:
     num_sampled_nodes: Optional[List[int]]
     num_sampled_edges: Optional[List[int]]
     batch: Optional[Tensor] = None  # disjoint sampling: the seed (tree) index of every node
+    seed_time: Optional[Tensor] = None  # temporal sampling: the int64 time of every seed
 
     def record_stream(self, stream) -> None:
         for t in (self.x, self.y, self.edge_index, self.n_id, self.e_id, self.input_id,
-                  self.batch):
+                  self.batch, self.seed_time):
             if isinstance(t, Tensor) and t.is_cuda:
                 t.record_stream(stream)
         self.graph.record_stream(stream)
@@ -84,6 +85,14 @@ class NeighborLoader:
             ``weight_attr`` names (loader/neighbor_loader.py:168-174; see
             :class:`~.sampler.NeighborSampler`).  The slot layout (:meth:`collate_slots`) stays
             uniform and refuses it.
+        node_time, edge_time, temporal_strategy: temporal sampling, the tensor the reference's
+            ``time_attr`` names (node-level ``[N]`` or edge-level ``[E]`` integer times) and its
+            ``temporal_strategy`` (loader/neighbor_loader.py:150-165; see
+            :class:`~.sampler.NeighborSampler`).  Forces ``disjoint``; :meth:`collate_padded` and
+            :meth:`collate_slots` refuse it.
+        input_time: the reference's ``input_time``: one integer seed time per entry of
+            ``input_nodes``, shuffled and batched with them (default: ``node_time`` of the seeds;
+            edge-level time needs it).  Every batch carries its seeds' times as ``seed_time``.
     """
 
     def __init__(self, x: Tensor, edge_index: Tensor, num_neighbors: List[int],
@@ -91,7 +100,13 @@ class NeighborLoader:
                  input_nodes: Optional[Tensor] = None, shuffle: bool = False,
                  drop_last: bool = False, seed: int = 0, prefetch: int = 0,
                  replace: bool = False, disjoint: bool = False,
-                 subgraph_type: str = 'directional', edge_weight: Optional[Tensor] = None):
+                 subgraph_type: str = 'directional', edge_weight: Optional[Tensor] = None,
+                 node_time: Optional[Tensor] = None, edge_time: Optional[Tensor] = None,
+                 input_time: Optional[Tensor] = None, temporal_strategy: str = 'uniform'):
+        if input_time is not None and node_time is None and edge_time is None:
+            # (the reference's wording, loader/neighbor_loader.py:223-226)
+            raise ValueError("Received conflicting 'input_time' and 'time_attr' arguments: "
+                             "'input_time' is set while 'time_attr' is not set.")
         self.prefetch = int(prefetch)
         self._side = None
         self._slots = None  # the static-shape sampler of `collate_slots`, built on first use
@@ -99,10 +114,21 @@ class NeighborLoader:
         self.num_nodes = x.size(0)
         self.sampler = NeighborSampler(edge_index, self.num_nodes, num_neighbors, seed=seed,
                                        replace=replace, disjoint=disjoint,
-                                       subgraph_type=subgraph_type, edge_weight=edge_weight)
+                                       subgraph_type=subgraph_type, edge_weight=edge_weight,
+                                       node_time=node_time, edge_time=edge_time,
+                                       temporal_strategy=temporal_strategy)
         if input_nodes is None:
             input_nodes = torch.arange(self.num_nodes, device=x.device)
         self.input_nodes = input_nodes.to(x.device)
+        self.input_time = None
+        if input_time is not None:
+            if not isinstance(input_time, Tensor) or input_time.dim() != 1 \
+                    or input_time.numel() != self.input_nodes.numel():
+                raise ValueError("'input_time' must be a 1-D tensor with one entry per input node")
+            self.input_time = self.sampler.seed_time(self.input_nodes, input_time)
+        elif edge_time is not None:
+            raise ValueError("temporal sampling with edge-level time ('edge_time') needs the seed "
+                             "times ('input_time')")
         self.batch_size, self.shuffle, self.drop_last = batch_size, shuffle, drop_last
         self._gen = torch.Generator().manual_seed(seed)
 
@@ -111,7 +137,13 @@ class NeighborLoader:
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
     def collate(self, seeds: Tensor, input_id: Optional[Tensor] = None) -> Batch:
-        out = self.sampler.sample_from_nodes(seeds)
+        smp = self.sampler
+        seed_time = None
+        if smp.is_temporal:  # input_id: positions in `input_nodes` (None: seeds given directly)
+            time = None if self.input_time is None or input_id is None \
+                else self.input_time[input_id]
+            seed_time = smp.seed_time(seeds, time)
+        out = smp.sample_from_nodes(seeds, time=seed_time)
         x = _native.gather_rows(self.x, out.node)  # filter_data: x[n_id]
         y = None if self.y is None else self.y[out.node]
         ei = torch.stack([out.row, out.col])
@@ -122,7 +154,8 @@ class NeighborLoader:
         return Batch(x=x, y=y, edge_index=ei, graph=graph, n_id=out.node,
                      e_id=out.edge, input_id=seeds if input_id is None else input_id,
                      batch_size=seeds.numel(), num_sampled_nodes=out.num_sampled_nodes,
-                     num_sampled_edges=out.num_sampled_edges, batch=out.batch)
+                     num_sampled_edges=out.num_sampled_edges, batch=out.batch,
+                     seed_time=seed_time)
 
     def collate_padded(self, seeds: Tensor, seed: int = 0,
                        seed_dev: Optional[Tensor] = None) -> PaddedBatch:
