@@ -672,6 +672,55 @@ PYGAMD_API int pygamd_relabel(int phase, const void* src, int idx_dtype, int64_t
                               const int64_t* m_dev, void* local_map, int64_t* flag_or_scan,
                               int64_t base, const int64_t* base_dev, void* out, void* stream);
 
+/* ---- link-level sampling: negatives and the seed block -----------------------------------------
+ * pygamd_sample_negatives replaces the reference's negative draws of LinkNeighborLoader /
+ * NeighborSampler.sample_from_edges: `neg_sample` (sampler/neighbor_sampler.py:1051-1096) and
+ * `NegativeSampling.sample` (sampler/base.py:906-929, `torch.randint(num_nodes, (n, ))` /
+ * `torch.multinomial(weight, n, replacement=True)`).  Writes n node ids into `out` (out_dtype
+ * PYGAMD_IDX_I32 / _I64), one thread per draw.  Round r of draw j uses the counter-based hash of
+ * (seed, j, r), with seed_dev (device uint64, may be NULL) mixed in as in
+ * pygamd_sample_neighbors, and a salt of its own (the hop draws never share the stream).
+ *   cdf == NULL: the candidate is uniform over [0, num_nodes): the high word of h * num_nodes for
+ *     64 hash bits h, so no id is off its share 1 / num_nodes by more than num_nodes / 2^64;
+ *   cdf != NULL (fp64 [num_nodes], the inclusive prefix sums of non-negative weights, cdf[N-1] > 0
+ *     and finite): the first i with cdf[i] > u, u uniform in [0, cdf[N-1]) from 53 hash bits
+ *     (binary search): node i with probability w_i / W; a node whose weight leaves the fp64 CDF
+ *     unchanged (w_i = 0) is never drawn.
+ *   node_time != NULL (int64 [num_nodes], node-level time; the reference has none for edge-level
+ *     time): draw j is bounded by t = bound[j % n_bound] (int64 [n_bound]) and a candidate c is
+ *     accepted iff node_time[c] <= t.  Up to 6 candidates (the reference's first draw and its 5
+ *     retries), then `fallback` (the caller's node_time.argmin(): the smallest id among the
+ *     earliest nodes, neighbor_sampler.py:1094), which may itself be later than t when no node is
+ *     eligible.  The reference's first round accepts `node_time <= seed_time` (its comment says
+ *     the same), but its retry rounds mark `node_time >= seed_time` as still invalid
+ *     (neighbor_sampler.py:1079, 1089), so a retry whose time equals the bound is rejected there;
+ *     every round here uses `<=`.
+ * Rejected before any launch (PYGAMD_ERR_INVALID_ARG): n < 0; an out_dtype other than I32 / I64,
+ * or I32 with num_nodes > INT32_MAX; bound without node_time; node_time with a NULL bound,
+ * n_bound <= 0 or fallback outside [0, num_nodes); and, when n > 0, num_nodes <= 0 or a NULL out.
+ * n == 0 otherwise returns PYGAMD_OK.
+ *
+ * pygamd_unique_inverse replaces `seed.unique(return_inverse=True)` of edge_sample
+ * (sampler/neighbor_sampler.py:1004-1008: the seed nodes of an edge batch, cat([src, dst])) on the
+ * output of pygamd_index_sort: keys_sorted (idx_dtype, ascending) and perm (int64, keys_sorted[i] =
+ * keys[perm[i]]).  Three steps: rank[i] = 1 at the head of every run of equal keys, the inclusive
+ * scan of rank (pygamd_cumsum in place, `workspace` of pygamd_cumsum_workspace_bytes(
+ * PYGAMD_IDX_I64, n) bytes), then uniq_out[rank[i] - 1] = keys_sorted[i] at the heads,
+ * inverse_out[perm[i]] = rank[i] - 1 and *n_unique = rank[n - 1] (device int64).  uniq_out has
+ * room for n keys; its first *n_unique are torch.unique's result bit for bit (sorted), and
+ * inverse_out (int64 [n]) its inverse.  rank is int64 [n] scratch.  n < 0, an unknown idx_dtype
+ * or (n > 0) a NULL pointer -> PYGAMD_ERR_INVALID_ARG, a short workspace -> PYGAMD_ERR_WORKSPACE,
+ * before any launch; n == 0 writes nothing.                                                     */
+PYGAMD_API int pygamd_sample_negatives(int64_t n, int64_t num_nodes, uint64_t seed,
+                                       const uint64_t* seed_dev, const double* cdf,
+                                       const int64_t* node_time, const int64_t* bound,
+                                       int64_t n_bound, int64_t fallback, int out_dtype,
+                                       void* out, void* stream);
+PYGAMD_API int pygamd_unique_inverse(const void* keys_sorted, const int64_t* perm, int idx_dtype,
+                                     int64_t n, int64_t* rank, void* workspace,
+                                     size_t workspace_bytes, void* uniq_out, int64_t* inverse_out,
+                                     int64_t* n_unique, void* stream);
+
 /* ---- a18: one-pass multi-reduce (FusedAggregation) ---------------------------------------------
  * nn/aggr/fused.py:191-336 shares the group count, the sum and the sum of squares between
  * sum / mean / var / std / min / max.  Here ONE read of the rows produces all requested statistics

@@ -163,6 +163,9 @@ SIGNATURES = {
     'pygamd_edge_unkey': (c_int, [_P, _P, _P, c_int64, c_int64, c_int, c_int, _P, _P, _P, _P]),
     'pygamd_sample_counts': (c_int, [_P, c_int, _P, c_int64, c_int64, c_int, _P, _P, _P]),
     'pygamd_relabel': (c_int, [c_int, _P, c_int, c_int64, _P, _P, _P, c_int64, _P, _P, _P]),
+    'pygamd_sample_negatives': (c_int, [c_int64, c_int64, c_uint64, _P, _P, _P, _P, c_int64,
+                                        c_int64, c_int, _P, _P]),
+    'pygamd_unique_inverse': (c_int, [_P, _P, c_int, c_int64, _P, _P, c_size_t, _P, _P, _P, _P]),
     'pygamd_gather_rows': (c_int, [_P, c_int64, c_int64, _P, c_int, c_int64, c_int64, _P,
                                    c_int64, _P, _P]),
     'pygamd_gather_scatter_add': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P, c_int64, _P,

@@ -1850,6 +1850,72 @@ def relabel_new_nodes_padded(src_global: Tensor, total: Tensor, local_map: Tenso
     return new_nodes, rows, scan[-1:]
 
 
+def sample_negatives(n: int, num_nodes: int, seed: int, device, dtype=torch.int64,
+                     cdf: Optional[Tensor] = None, node_time: Optional[Tensor] = None,
+                     bound: Optional[Tensor] = None, fallback: int = 0,
+                     seed_dev: Optional[Tensor] = None) -> Tensor:
+    """``n`` negative node ids (``pygamd_sample_negatives``): uniform over ``[0, num_nodes)``, or
+    in proportion to weight given their fp64 inclusive ``cdf`` ``[num_nodes]``; with ``node_time``
+    (int64 ``[num_nodes]``) draw ``j`` is accepted iff ``node_time[c] <= bound[j % len(bound)]``
+    (int64), up to 6 candidates, then ``fallback``."""
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"negatives are int32 or int64 node ids (got {dtype})")
+    if n < 0:
+        raise ValueError(f"the number of negatives must be non-negative (got {n})")
+    if n > 0 and num_nodes <= 0:
+        raise ValueError('negatives need a graph with at least one node')
+    if cdf is not None and (cdf.dtype != torch.float64 or cdf.dim() != 1
+                            or cdf.numel() != num_nodes):
+        raise ValueError(f"'cdf' must be a one-dimensional float64 tensor with {num_nodes} "
+                         f"entries")
+    if (node_time is None) != (bound is None):
+        raise ValueError("'node_time' and 'bound' go together")
+    if node_time is not None:
+        if node_time.dtype != torch.int64 or node_time.numel() != num_nodes:
+            raise ValueError(f"'node_time' must be int64 with {num_nodes} entries")
+        if bound.dtype != torch.int64 or bound.dim() != 1 or (n > 0 and bound.numel() == 0):
+            raise ValueError("'bound' must be a non-empty one-dimensional int64 tensor")
+        if not 0 <= fallback < num_nodes:
+            raise ValueError(f"'fallback' must be a node id in [0, {num_nodes})")
+        node_time, bound = node_time.contiguous(), bound.contiguous()
+    out = torch.empty(n, dtype=dtype, device=device)
+    _require_device(out, cdf, node_time, bound, seed_dev)
+    if n == 0:
+        return out
+    lib = _lib.load()
+    check(lib.pygamd_sample_negatives(
+        n, num_nodes, seed & 0xFFFFFFFFFFFFFFFF, _p(seed_dev), _p(cdf), _p(node_time), _p(bound),
+        0 if bound is None else bound.numel(), int(fallback), _idx_dtype(out), _p(out),
+        _stream(out)), 'sample_negatives')
+    return out
+
+
+def unique_inverse(keys: Tensor, max_value: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """``torch.unique(keys, return_inverse=True)`` of non-negative int32 / int64 ids (sorted; the
+    inverse is int64): :func:`index_sort` (``max_value`` bounds its passes), then
+    ``pygamd_unique_inverse``.  One host read, the number of distinct keys."""
+    _require_device(keys)
+    if keys.dim() != 1:
+        raise ValueError("'keys' must be one-dimensional")
+    _idx_dtype(keys)
+    n = keys.numel()
+    if n == 0:
+        return keys.new_empty(0), torch.empty(0, dtype=torch.int64, device=keys.device)
+    sorted_k, perm = index_sort(keys, max_value)
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    check(lib.pygamd_cumsum_workspace_bytes(_lib.IDX_I64, n, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=keys.device)
+    rank = torch.empty(n, dtype=torch.int64, device=keys.device)
+    uniq = torch.empty_like(sorted_k)
+    inverse = torch.empty(n, dtype=torch.int64, device=keys.device)
+    n_unique = torch.empty(1, dtype=torch.int64, device=keys.device)
+    check(lib.pygamd_unique_inverse(_p(sorted_k), _p(perm), _idx_dtype(keys), n, _p(rank), _p(ws),
+                                    nbytes.value, _p(uniq), _p(inverse), _p(n_unique),
+                                    _stream(keys)), 'unique_inverse')
+    return uniq[:int(n_unique)], inverse  # host read: sizes the seed block
+
+
 def edge_key(row: Tensor, col: Tensor, num_nodes: int, by_row: bool) -> Tensor:
     _require_device(row, col)
     lib = _lib.load()

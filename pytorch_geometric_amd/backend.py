@@ -886,7 +886,12 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     (``data.is_edge_attr``) integer time attribute of ``data`` (sampler/neighbor_sampler.py:79-108)
     with ``temporal_strategy`` (``'uniform'`` | ``'last'``): temporal sampling, always disjoint;
     the reference's ``NodeLoader`` passes its ``input_time`` as ``NodeSamplerInput.time`` and reads
-    ``seed_time`` from ``metadata[1]``.  It needs the ``Data`` form too."""
+    ``seed_time`` from ``metadata[1]``.  It needs the ``Data`` form too.
+    ``sample_from_edges(EdgeSamplerInput, neg_sampling)`` is link-level sampling
+    (:meth:`pytorch_geometric_amd.sampler.NeighborSampler.sample_from_edges`), so that the
+    reference's ``LinkLoader(data, link_sampler=...)`` (loader/link_loader.py) drives it too; its
+    ``NegativeSampling`` objects are taken as they are, and ``edge_label_time`` needs
+    ``time_attr``."""
     global _sampler_cls
     import torch_geometric.sampler as pyg_sampler
     from .sampler import NeighborSampler
@@ -919,7 +924,9 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
                 return self.impl.sample_from_nodes(index, **kwargs)
 
             def sample_from_edges(self, index, neg_sampling=None):
-                raise NotImplementedError('link-level sampling is out of scope (SURVEY.md §8)')
+                # the reference's LinkLoader passes an EdgeSamplerInput and its own
+                # NegativeSampling (cast by duck typing); metadata as its edge_sample fills it
+                return self.impl.sample_from_edges(index, neg_sampling)
 
             @property
             def edge_permutation(self):

@@ -514,6 +514,81 @@ __global__ void __launch_bounds__(kBlock)
   out[e] = (!m_dev || e < *m_dev) ? local[src[e]] : static_cast<IdxT>(0);
 }
 
+// ---- negative draws of link-level sampling (the reference's neg_sample / NegativeSampling.sample,
+// sampler/neighbor_sampler.py:1051-1096, sampler/base.py:906-929).  One thread per draw j; round r
+// of draw j hashes (seed, j, r).  The candidate is uniform over [0, N) (multiply-high of 64 hash
+// bits) or, with a CDF, the first i with cdf[i] > u, u uniform in [0, cdf[N-1]).  With node times a
+// candidate is accepted iff node_time[c] <= bound[j % n_bound]; kNegRounds candidates are tried in
+// registers (the reference's first draw and its 5 retries), then `fallback` is written.
+constexpr int kNegRounds = 6;
+constexpr uint64_t kNegSalt = 0x6E65676174697665ull;  // "negative": a stream of its own
+
+__device__ __forceinline__ int64_t negative_candidate(uint64_t h, int64_t num_nodes,
+                                                      const double* __restrict__ cdf,
+                                                      double total) {
+  if (!cdf) return static_cast<int64_t>(__umul64hi(h, static_cast<uint64_t>(num_nodes)));
+  // 53 hash bits -> [0, 1); a product that rounds up to `total` is pulled just below it, so the
+  // search always lands on a node whose weight moved the CDF
+  double u = static_cast<double>(h >> 11) * 0x1p-53 * total;
+  if (!(u < total)) u = nextafter(total, 0.0);
+  int64_t lo = 0, hi = num_nodes - 1;  // the first i with cdf[i] > u lies in [lo, hi]
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (cdf[mid] > u) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    sample_negatives_kernel(int64_t n, int64_t num_nodes, uint64_t seed,
+                            const uint64_t* __restrict__ seed_dev, const double* __restrict__ cdf,
+                            const int64_t* __restrict__ node_time,
+                            const int64_t* __restrict__ bound, int64_t n_bound, int64_t fallback,
+                            IdxT* __restrict__ out) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (j >= n) return;
+  if (seed_dev) seed = mix64(seed ^ mix64(*seed_dev * 0x9E3779B97F4A7C15ull));
+  const uint64_t key = mix64(seed ^ kNegSalt);
+  const double total = cdf ? cdf[num_nodes - 1] : 0.0;
+  const uint64_t base = static_cast<uint64_t>(j) * 8u;
+  int64_t c = negative_candidate(mix64(key + base), num_nodes, cdf, total);
+  if (node_time) {
+    const int64_t t = bound[j % n_bound];
+    bool ok = node_time[c] <= t;
+    for (int r = 1; r < kNegRounds && !ok; ++r) {
+      c = negative_candidate(mix64(key + base + static_cast<uint64_t>(r)), num_nodes, cdf, total);
+      ok = node_time[c] <= t;
+    }
+    if (!ok) c = fallback;
+  }
+  out[j] = static_cast<IdxT>(c);
+}
+
+// ---- torch.unique(keys, return_inverse=True) on the output of index_sort: rank[i] = 1 where a run
+// of equal sorted keys starts (then scanned inclusively by pygamd_cumsum), and the scatter
+// uniq[rank - 1] = key (run heads), inverse[perm[i]] = rank[i] - 1, *n_unique = rank[n - 1].
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    unique_heads_kernel(const IdxT* __restrict__ sorted, int64_t n, int64_t* __restrict__ rank) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  rank[i] = (i == 0 || sorted[i] != sorted[i - 1]) ? 1 : 0;
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    unique_scatter_kernel(const IdxT* __restrict__ sorted, const int64_t* __restrict__ perm,
+                          int64_t n, const int64_t* __restrict__ rank, IdxT* __restrict__ uniq,
+                          int64_t* __restrict__ inverse, int64_t* __restrict__ n_unique) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = rank[i] - 1;
+  if (i == 0 || rank[i - 1] != rank[i]) uniq[r] = sorted[i];
+  inverse[perm[i]] = r;
+  if (i == n - 1) n_unique[0] = r + 1;
+}
+
 }  // namespace pygamd
 
 using namespace pygamd;
@@ -671,6 +746,56 @@ int pygamd_relabel(int phase, const void* src, int idx_dtype, int64_t m, const i
         hipLaunchKernelGGL((relabel_lookup_kernel<IdxT>), grid, dim3(kBlock), 0, st, s, m, m_dev,
                            local, static_cast<IdxT*>(out));
     }
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_sample_negatives(int64_t n, int64_t num_nodes, uint64_t seed, const uint64_t* seed_dev,
+                            const double* cdf, const int64_t* node_time, const int64_t* bound,
+                            int64_t n_bound, int64_t fallback, int out_dtype, void* out,
+                            void* stream) {
+  if (n < 0) return PYGAMD_ERR_INVALID_ARG;
+  if (out_dtype != PYGAMD_IDX_I32 && out_dtype != PYGAMD_IDX_I64) return PYGAMD_ERR_INVALID_ARG;
+  if (out_dtype == PYGAMD_IDX_I32 && num_nodes > INT32_MAX) return PYGAMD_ERR_INVALID_ARG;
+  if (!node_time && bound) return PYGAMD_ERR_INVALID_ARG;  // a bound without times to test
+  if (node_time && (!bound || n_bound <= 0 || fallback < 0 || fallback >= num_nodes))
+    return PYGAMD_ERR_INVALID_ARG;
+  if (n == 0) return PYGAMD_OK;
+  if (num_nodes <= 0 || !out) return PYGAMD_ERR_INVALID_ARG;
+  return PYGAMD_DISPATCH_IDX(out_dtype, [&]() -> int {
+    hipLaunchKernelGGL((sample_negatives_kernel<IdxT>),
+                       dim3(static_cast<unsigned>(ceil_div(n, kBlock))), dim3(kBlock), 0,
+                       as_stream(stream), n, num_nodes, seed, seed_dev, cdf, node_time, bound,
+                       n_bound, fallback, static_cast<IdxT*>(out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_unique_inverse(const void* keys_sorted, const int64_t* perm, int idx_dtype, int64_t n,
+                          int64_t* rank, void* workspace, size_t workspace_bytes, void* uniq_out,
+                          int64_t* inverse_out, int64_t* n_unique, void* stream) {
+  if (n < 0) return PYGAMD_ERR_INVALID_ARG;
+  if (idx_dtype != PYGAMD_IDX_I32 && idx_dtype != PYGAMD_IDX_I64) return PYGAMD_ERR_INVALID_ARG;
+  if (n == 0) return PYGAMD_OK;
+  if (!keys_sorted || !perm || !rank || !workspace || !uniq_out || !inverse_out || !n_unique)
+    return PYGAMD_ERR_INVALID_ARG;
+  size_t need = 0;
+  int rc = pygamd_cumsum_workspace_bytes(PYGAMD_IDX_I64, n, &need);
+  if (rc != PYGAMD_OK) return rc;
+  if (workspace_bytes < need) return PYGAMD_ERR_WORKSPACE;
+  const dim3 grid(static_cast<unsigned>(ceil_div(n, kBlock)));
+  hipStream_t st = as_stream(stream);
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const IdxT* keys = static_cast<const IdxT*>(keys_sorted);
+    hipLaunchKernelGGL((unique_heads_kernel<IdxT>), grid, dim3(kBlock), 0, st, keys, n, rank);
+    PYGAMD_LAUNCH_CHECK();
+    const int scan_rc = pygamd_cumsum(rank, PYGAMD_IDX_I64, n, rank, workspace, workspace_bytes,
+                                      stream);
+    if (scan_rc != PYGAMD_OK) return scan_rc;
+    hipLaunchKernelGGL((unique_scatter_kernel<IdxT>), grid, dim3(kBlock), 0, st, keys, perm, n,
+                       rank, static_cast<IdxT*>(uniq_out), inverse_out, n_unique);
     PYGAMD_LAUNCH_CHECK();
     return PYGAMD_OK;
   });

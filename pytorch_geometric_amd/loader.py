@@ -2,10 +2,13 @@
 (torch_geometric/loader/neighbor_loader.py, node_loader.py:90-207, loader/utils.py:32-83,159) for
 BASELINE config 4 — seeds are drawn per batch, the k-hop neighbourhood is sampled ON THE GPU
 (:mod:`.sampler`), features are gathered with the HIP gather kernel (``filter_data``'s
-``x[n_id]``) and the batch never touches the host."""
+``x[n_id]``) and the batch never touches the host.  :class:`LinkNeighborLoader` is the
+``LinkNeighborLoader`` role (loader/link_neighbor_loader.py, link_loader.py): batches of seed
+links with negatives drawn on the device."""
 import queue
 import threading
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Iterator, List, Optional
 
 import torch
@@ -15,7 +18,7 @@ import os
 
 from . import _native
 from .edge_index import EdgeIndex
-from .sampler import NeighborSampler
+from .sampler import NegativeSampling, NeighborSampler
 
 # collate_slots: layer 0 of the slot stack gathers its neighbours' rows straight from the feature
 # matrix (only the destination rows of a batch are copied) — slots.SlotSampler.gather(direct=True).
@@ -49,6 +52,29 @@ class Batch:
 
 
 @dataclass
+class LinkBatch(Batch):
+    """A link-level mini-batch (:class:`LinkNeighborLoader`): :class:`Batch`'s fields plus the
+    reference's link fields (loader/link_loader.py:264-279).  Without negatives or with binary
+    ones: ``edge_label_index`` ``[2, B + num_neg]`` (local ids into ``n_id``), ``edge_label`` and
+    ``edge_label_time``; with triplet ones: ``src_index``, ``dst_pos_index``, ``dst_neg_index``
+    (``[B]`` or ``[B, amount]``) and ``seed_time``.  ``batch_size`` is the number of positive
+    edges ``B``."""
+    edge_label_index: Optional[Tensor] = None
+    edge_label: Optional[Tensor] = None
+    edge_label_time: Optional[Tensor] = None
+    src_index: Optional[Tensor] = None
+    dst_pos_index: Optional[Tensor] = None
+    dst_neg_index: Optional[Tensor] = None
+
+    def record_stream(self, stream) -> None:
+        super().record_stream(stream)
+        for t in (self.edge_label_index, self.edge_label, self.edge_label_time, self.src_index,
+                  self.dst_pos_index, self.dst_neg_index):
+            if isinstance(t, Tensor) and t.is_cuda:
+                t.record_stream(stream)
+
+
+@dataclass
 class PaddedBatch:
     """A mini-batch at STATIC shapes (``NeighborLoader.collate_padded``): ``hops`` is the
     sampler's padded-id output (block positions as node ids, per-hop CSR pointers, device-side
@@ -63,7 +89,73 @@ class PaddedBatch:
     batch_size: int
 
 
-class NeighborLoader:
+class _Prefetching:
+    """``__iter__`` of the loaders: batches from ``self._plan()`` through ``self.collate``, sampled
+    inline (``prefetch <= 0``) or ahead of the consumer by a producer thread on its own stream."""
+
+    def __iter__(self) -> Iterator:
+        if self.prefetch <= 0:
+            for seeds, sel in self._plan():
+                yield self.collate(seeds, sel)
+            return
+        yield from self._prefetching_iter()
+
+    def _prefetching_iter(self) -> Iterator:
+        dev = self.x.device
+        if self._side is None:
+            self._side = torch.cuda.Stream(dev)
+        side = self._side
+        plan = self._plan()
+        first = next(plan, None)   # the seed tensors are made on the consumer's stream ...
+        side.wait_stream(torch.cuda.current_stream(dev))  # ... before the producer reads them
+        ready: 'queue.Queue' = queue.Queue(maxsize=self.prefetch)
+        stop = threading.Event()
+
+        def put(item) -> bool:
+            while not stop.is_set():
+                try:
+                    ready.put(item, timeout=0.05)
+                    return True
+                except queue.Full:
+                    continue
+            return False
+
+        def produce():
+            try:
+                torch.cuda.set_device(dev)
+                item = first
+                with torch.cuda.stream(side):
+                    while item is not None and not stop.is_set():
+                        batch = self.collate(*item)
+                        done = torch.cuda.Event()
+                        done.record(side)
+                        if not put((batch, done)):
+                            return
+                        item = next(plan, None)
+                put(None)
+            except BaseException as exc:  # surfaced in the consumer
+                put(exc)
+
+        worker = threading.Thread(target=produce, name='pyg-amd-sampler', daemon=True)
+        worker.start()
+        try:
+            while True:
+                item = ready.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                batch, done = item
+                cur = torch.cuda.current_stream(dev)
+                cur.wait_event(done)
+                batch.record_stream(cur)
+                yield batch
+        finally:
+            stop.set()
+            worker.join(timeout=10.0)
+
+
+class NeighborLoader(_Prefetching):
     r"""Iterates over mini-batches of ``batch_size`` seed nodes with their sampled ``k``-hop
     neighbourhoods.
 
@@ -203,63 +295,128 @@ class NeighborLoader:
             lo, hi = b * self.batch_size, (b + 1) * self.batch_size
             yield nodes[lo:hi], order[lo:hi]
 
-    def __iter__(self) -> Iterator[Batch]:
-        if self.prefetch <= 0:
-            for seeds, sel in self._plan():
-                yield self.collate(seeds, sel)
-            return
-        yield from self._prefetching_iter()
 
-    def _prefetching_iter(self) -> Iterator[Batch]:
-        dev = self.x.device
-        if self._side is None:
-            self._side = torch.cuda.Stream(dev)
-        side = self._side
-        plan = self._plan()
-        first = next(plan, None)   # the seed tensors are made on the consumer's stream ...
-        side.wait_stream(torch.cuda.current_stream(dev))  # ... before the producer reads them
-        ready: 'queue.Queue' = queue.Queue(maxsize=self.prefetch)
-        stop = threading.Event()
+class LinkNeighborLoader(_Prefetching):
+    r"""Iterates over mini-batches of ``batch_size`` seed LINKS with their sampled ``k``-hop
+    neighbourhoods: the reference's ``LinkNeighborLoader`` (loader/link_neighbor_loader.py ->
+    loader/link_loader.py) for one node type, sampled on the GPU
+    (:meth:`~.sampler.NeighborSampler.sample_from_edges`).
 
-        def put(item) -> bool:
-            while not stop.is_set():
-                try:
-                    ready.put(item, timeout=0.05)
-                    return True
-                except queue.Full:
-                    continue
-            return False
+    Args:
+        x, y, edge_index, num_neighbors, batch_size, shuffle, drop_last, seed, prefetch, replace,
+            disjoint, subgraph_type, edge_weight, node_time, edge_time, temporal_strategy: as
+            for :class:`NeighborLoader`.
+        edge_label_index: ``[2, L]`` the positive links to iterate over (default:
+            ``edge_index``).
+        edge_label: optional ``[L, ...]`` labels of the links.  With binary negatives, labels
+            whose minimum is 0 are shifted by +1 so that 0 denotes "negative"; triplet negatives
+            refuse labels.
+        edge_label_time: optional ``[L]`` integer times of the links, the seed times of a temporal
+            sampler (which needs them; a non-temporal one refuses them).
+        neg_sampling: :class:`~.sampler.NegativeSampling`, the reference's object, a ``dict`` of
+            its arguments or a mode string.
+        neg_sampling_ratio: shorthand for ``NegativeSampling('binary', ratio)`` (it takes
+            precedence when set and non-zero).
 
-        def produce():
-            try:
-                torch.cuda.set_device(dev)
-                item = first
-                with torch.cuda.stream(side):
-                    while item is not None and not stop.is_set():
-                        batch = self.collate(*item)
-                        done = torch.cuda.Event()
-                        done.record(side)
-                        if not put((batch, done)):
-                            return
-                        item = next(plan, None)
-                put(None)
-            except BaseException as exc:  # surfaced in the consumer
-                put(exc)
+    Yields :class:`LinkBatch`.
+    """
 
-        worker = threading.Thread(target=produce, name='pyg-amd-sampler', daemon=True)
-        worker.start()
-        try:
-            while True:
-                item = ready.get()
-                if item is None:
-                    break
-                if isinstance(item, BaseException):
-                    raise item
-                batch, done = item
-                cur = torch.cuda.current_stream(dev)
-                cur.wait_event(done)
-                batch.record_stream(cur)
-                yield batch
-        finally:
-            stop.set()
-            worker.join(timeout=10.0)
+    def __init__(self, x: Tensor, edge_index: Tensor, num_neighbors: List[int],
+                 edge_label_index: Optional[Tensor] = None, edge_label: Optional[Tensor] = None,
+                 edge_label_time: Optional[Tensor] = None, neg_sampling=None,
+                 neg_sampling_ratio: Optional[float] = None, batch_size: int = 1024,
+                 y: Optional[Tensor] = None, shuffle: bool = False, drop_last: bool = False,
+                 seed: int = 0, prefetch: int = 0, replace: bool = False,
+                 disjoint: bool = False, subgraph_type: str = 'directional',
+                 edge_weight: Optional[Tensor] = None, node_time: Optional[Tensor] = None,
+                 edge_time: Optional[Tensor] = None, temporal_strategy: str = 'uniform'):
+        temporal = node_time is not None or edge_time is not None
+        if (edge_label_time is not None) != temporal:
+            # (the reference's wording, loader/link_neighbor_loader.py:242-249; 'time_attr' is
+            # node_time / edge_time here)
+            raise ValueError(
+                f"Received conflicting 'edge_label_time' and 'time_attr' arguments: "
+                f"'edge_label_time' is {'set' if edge_label_time is not None else 'not set'} "
+                f"while 'time_attr' is {'set' if temporal else 'not set'}. Both arguments must "
+                f"be provided for temporal sampling.")
+        if neg_sampling_ratio is not None and neg_sampling_ratio != 0.0:
+            neg_sampling = NegativeSampling('binary', neg_sampling_ratio)
+        self.neg_sampling = NegativeSampling.cast(neg_sampling)
+        self.num_nodes = x.size(0)
+        if self.neg_sampling is not None:
+            self.neg_sampling.check(self.num_nodes)
+        if self.neg_sampling is not None and self.neg_sampling.is_triplet() \
+                and edge_label is not None:
+            # (the reference's wording, loader/link_loader.py:177-183)
+            raise ValueError("'edge_label' needs to be undefined for 'triplet'-based negative "
+                             "sampling. Please use `src_index`, `dst_pos_index` and "
+                             "`neg_pos_index` of the returned mini-batch instead to "
+                             "differentiate between positive and negative samples.")
+        if edge_label_index is None:
+            edge_label_index = edge_index
+        if edge_label_index.dim() != 2 or edge_label_index.size(0) != 2:
+            raise ValueError(f"'edge_label_index' must be a [2, L] tensor (got "
+                             f"{list(edge_label_index.shape)})")
+        L = edge_label_index.size(1)
+        for name, t in (('edge_label', edge_label), ('edge_label_time', edge_label_time)):
+            if t is not None and (t.dim() < 1 or t.size(0) != L):
+                raise ValueError(f"'{name}' needs one entry per link of 'edge_label_index' ({L})")
+        self.prefetch = int(prefetch)
+        self._side = None
+        self.x, self.y = x, y
+        self.sampler = NeighborSampler(edge_index, self.num_nodes, num_neighbors, seed=seed,
+                                       replace=replace, disjoint=disjoint,
+                                       subgraph_type=subgraph_type, edge_weight=edge_weight,
+                                       node_time=node_time, edge_time=edge_time,
+                                       temporal_strategy=temporal_strategy)
+        dev = x.device
+        self.edge_label_index = edge_label_index.to(dev)
+        if edge_label is not None:
+            edge_label = edge_label.to(dev)
+            if self.neg_sampling is not None and self.neg_sampling.is_binary() \
+                    and L > 0 and edge_label.min() == 0:
+                edge_label = edge_label + 1  # zero now denotes "negative"
+        self.edge_label = edge_label
+        self.edge_label_time = None if edge_label_time is None else \
+            self.sampler.seed_time(self.edge_label_index[0], edge_label_time)
+        self.batch_size, self.shuffle, self.drop_last = batch_size, shuffle, drop_last
+        self._gen = torch.Generator().manual_seed(seed)
+
+    def __len__(self) -> int:
+        n = self.edge_label_index.size(1)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _plan(self):
+        n = self.edge_label_index.size(1)
+        dev = self.edge_label_index.device
+        order = (torch.randperm(n, generator=self._gen).to(dev) if self.shuffle
+                 else torch.arange(n, device=dev))
+        for b in range(len(self)):
+            sel = order[b * self.batch_size:(b + 1) * self.batch_size]
+            yield self.edge_label_index[:, sel], sel
+
+    def collate(self, edges: Tensor, input_id: Tensor) -> LinkBatch:
+        """One batch from the positive links ``edges`` ``[2, B]`` (``input_id``: their positions
+        in ``edge_label_index``)."""
+        inp = SimpleNamespace(
+            row=edges[0], col=edges[1], input_id=input_id, input_type=None,
+            label=None if self.edge_label is None else self.edge_label[input_id],
+            time=None if self.edge_label_time is None else self.edge_label_time[input_id])
+        out = self.sampler.sample_from_edges(inp, self.neg_sampling)
+        x = _native.gather_rows(self.x, out.node)  # filter_data: x[n_id]
+        y = None if self.y is None else self.y[out.node]
+        ei = torch.stack([out.row, out.col])
+        fan = self.sampler.num_neighbors
+        bounded = min(fan, default=0) >= 0 and self.sampler.subgraph_type == 'directional'
+        graph = EdgeIndex.from_sorted_batch(
+            ei, out.node.numel(), max_in_degree=max(fan) if bounded and fan else None)
+        b = LinkBatch(x=x, y=y, edge_index=ei, graph=graph, n_id=out.node, e_id=out.edge,
+                      input_id=input_id, batch_size=edges.size(1),
+                      num_sampled_nodes=out.num_sampled_nodes,
+                      num_sampled_edges=out.num_sampled_edges, batch=out.batch)
+        md = out.metadata
+        if self.neg_sampling is None or self.neg_sampling.is_binary():
+            b.edge_label_index, b.edge_label, b.edge_label_time = md[1], md[2], md[3]
+        else:
+            b.src_index, b.dst_pos_index, b.dst_neg_index, b.seed_time = md[1:5]
+        return b

@@ -46,6 +46,16 @@ sampler's conventions; ``metadata = (input_id, time)``.
 (sampler/neighbor_sampler.py:333-356), so that ``torch_geometric.loader.NodeLoader`` can drive it
 (``backend.neighbor_sampler`` wraps it in a ``BaseSampler`` subclass).
 
+``sample_from_edges`` is link-level sampling, the homogeneous branch of the reference's
+``edge_sample`` / ``neg_sample`` (sampler/neighbor_sampler.py:821-1096): ``ceil(B * amount)``
+negatives per endpoint drawn on the device (``pygamd_sample_negatives``: uniform, in proportion to
+the :class:`NegativeSampling` weights, or bounded by the links' times under node-level time), the
+seeds ``cat([src, dst])`` deduplicated into their sorted unique (``pygamd_unique_inverse``) unless
+``disjoint``, then the hops of ``sample_from_nodes`` on that seed vector, so the subgraph is the
+one ``sample_from_nodes`` gives for the same seeds and ``seed``.  The reference's retry rounds for
+temporal negatives test ``node_time >= seed_time`` (neighbor_sampler.py:1089) where its first round
+and its comment test ``<=``; every round here uses ``<=``.
+
 Host synchronisation.  With bounded fan-outs every hop is sized by the STATIC bound
 ``frontier capacity x fan-out`` and all counts stay on the device (``pygamd_sample_counts`` /
 ``pygamd_relabel`` read them from device memory): a batch costs ONE host read at the very end
@@ -69,6 +79,7 @@ proportional draws with replacement (tests/test_gpu_sampler_weighted.py).  The t
 the rules above exactly; bounded ``'uniform'`` draws keep the contract on the window and equal the
 disjoint sampler bit for bit when every edge is eligible (tests/test_gpu_sampler_temporal.py).
 """
+import math
 from dataclasses import dataclass
 from typing import Any, List, Optional
 
@@ -112,6 +123,71 @@ class PaddedSamplerOutput:
     # (len = hops + 2).  A batch then has the same tensor shapes AND the same row ranges every time
     # (what a captured training step needs); rows past a block's valid count are padding.
     bases: Optional[List[int]] = None
+
+
+@dataclass(init=False)
+class NegativeSampling:
+    r"""The negative sampling configuration of :meth:`NeighborSampler.sample_from_edges`: the
+    reference's ``NegativeSampling`` (sampler/base.py:848-904) with its validation and wording.
+
+    Args:
+        mode: ``'binary'`` (random negative pairs of nodes) or ``'triplet'`` (random negative
+            destinations for every positive source).
+        amount: the ratio of negative to positive edges (an integer for ``'triplet'``).
+        src_weight, dst_weight: optional node-level ``[num_nodes]`` weights of the source /
+            destination draws (need not sum to one); uniform when not given.
+    """
+    mode: str
+    amount: float = 1
+    src_weight: Optional[Tensor] = None
+    dst_weight: Optional[Tensor] = None
+
+    def __init__(self, mode, amount=1, src_weight: Optional[Tensor] = None,
+                 dst_weight: Optional[Tensor] = None):
+        mode = getattr(mode, 'value', mode)  # the reference's NegativeSamplingMode
+        if mode not in ('binary', 'triplet'):
+            raise ValueError(f"'{mode}' is not a valid NegativeSamplingMode (expected 'binary' or "
+                             f"'triplet')")
+        self.mode, self.amount = mode, amount
+        self.src_weight, self.dst_weight = src_weight, dst_weight
+        if self.amount <= 0:
+            raise ValueError(f"The attribute 'amount' needs to be positive for "
+                             f"'{self.__class__.__name__}' (got {self.amount})")
+        if self.is_triplet():
+            if self.amount != math.ceil(self.amount):
+                raise ValueError(f"The attribute 'amount' needs to be an integer for "
+                                 f"'{self.__class__.__name__}' with 'triplet' negative sampling "
+                                 f"(got {self.amount}).")
+            self.amount = math.ceil(self.amount)
+
+    def is_binary(self) -> bool:
+        return self.mode == 'binary'
+
+    def is_triplet(self) -> bool:
+        return self.mode == 'triplet'
+
+    def check(self, num_nodes: int) -> None:
+        """The reference's weight check of ``NegativeSampling.sample`` (sampler/base.py:924-928)."""
+        for w in (self.src_weight, self.dst_weight):
+            if w is not None and w.numel() != num_nodes:
+                raise ValueError(f"The 'weight' attribute in '{self.__class__.__name__}' needs "
+                                 f"to match the number of nodes {num_nodes} (got {w.numel()})")
+
+    @classmethod
+    def cast(cls, value) -> Optional['NegativeSampling']:
+        """``None``, this class, the reference's object (duck-typed: ``mode`` or ``mode.value``,
+        ``amount``, ``src_weight``, ``dst_weight``), a ``dict`` of its arguments or a mode
+        string."""
+        if value is None or isinstance(value, cls):
+            return value
+        if isinstance(value, dict):
+            return cls(**value)
+        if isinstance(value, str):
+            return cls(value)
+        if hasattr(value, 'mode'):
+            return cls(value.mode, getattr(value, 'amount', 1), getattr(value, 'src_weight', None),
+                       getattr(value, 'dst_weight', None))
+        raise ValueError(f"cannot interpret {type(value).__name__} as 'NegativeSampling'")
 
 
 def _check_time(t, name: str, n: int) -> None:
@@ -204,6 +280,10 @@ class NeighborSampler:
         self.seed = seed
         self.output_cls = output_cls
         self._calls = 0
+        # link-level sampling: the fp64 CDFs of negative-sampling weights (per tensor) and the
+        # temporal fallback node, both built on first use
+        self._neg_cdf = {}
+        self._neg_fallback = None
         # global -> local id map; the dtype's minimum = not in the current batch (it must sort
         # below every claim value of pygamd_relabel); reset after every batch
         self._unset = torch.iinfo(self.colptr.dtype).min
@@ -300,6 +380,12 @@ class NeighborSampler:
         seed_time = self.seed_time(seeds, time) if self.is_temporal else None
         rng = self.seed + self._calls if seed is None else seed
         self._calls += 1
+        out = self._sample_seeds(seeds, rng, seed_time)
+        out.metadata = (input_id if input_id is not None else None, time)
+        return out
+
+    def _sample_seeds(self, seeds: Tensor, rng: int, seed_time: Optional[Tensor]):
+        """The hops from a seed vector (device, graph dtype) and the ``subgraph_type`` step."""
         if self.disjoint:
             out = self._hops_disjoint(seeds, rng, seed_time)
         elif all(k >= 0 for k in self.num_neighbors):
@@ -310,8 +396,146 @@ class NeighborSampler:
             out = self._to_bidirectional(out)
         elif self.subgraph_type == 'induced':
             out = self._to_induced(out)
-        out.metadata = (input_id if input_id is not None else None, time)
         return out
+
+    @torch.no_grad()
+    def sample_from_edges(self, index, neg_sampling=None, seed: Optional[int] = None):
+        """Link-level sampling, the reference's ``edge_sample`` (sampler/neighbor_sampler.py:
+        821-1048, homogeneous branch): ``index`` is a ``[2, B]`` tensor of positive edges or an
+        ``EdgeSamplerInput``-like object (``row``, ``col``, ``label``, ``time``, ``input_id``).
+        ``neg_sampling``: :class:`NegativeSampling` or anything its ``cast`` takes.
+
+        ``num_neg = ceil(B * amount)`` negatives are drawn on the device
+        (``pygamd_sample_negatives``): binary draws source and destination negatives, triplet
+        destination negatives only.  The seeds are ``cat([src, dst])``, deduplicated into their
+        sorted unique (``pygamd_unique_inverse``, the reference's ``unique(return_inverse=True)``)
+        unless ``disjoint``; the hops are :meth:`sample_from_nodes`' on that seed vector.
+        ``metadata`` is ``(input_id, edge_label_index, edge_label, src_time)`` without negatives or
+        with binary ones, ``(input_id, src_index, dst_pos_index, dst_neg_index, src_time)`` with
+        triplet ones.  ``seed`` fixes the RNG like in :meth:`sample_from_nodes`; the negatives
+        draw from a stream of their own."""
+        input_id = label = time = None
+        if isinstance(index, Tensor):
+            if index.dim() != 2 or index.size(0) != 2:
+                raise ValueError(f"the positive edges must be a [2, B] tensor (got "
+                                 f"{list(index.shape)})")
+            src, dst = index[0], index[1]
+        else:
+            if getattr(index, 'input_type', None) is not None:
+                raise NotImplementedError('heterogeneous sampling is out of scope (SURVEY.md §8)')
+            src, dst = index.row, index.col
+            input_id = getattr(index, 'input_id', None)
+            label, time = getattr(index, 'label', None), getattr(index, 'time', None)
+        neg = NegativeSampling.cast(neg_sampling)
+        B = src.numel()
+        if dst.numel() != B or src.dim() != 1 or dst.dim() != 1:
+            raise ValueError('the source and destination of the positive edges must be 1-D '
+                             'tensors of one length')
+        if B == 0:
+            raise ValueError("'sample_from_edges' needs at least one positive edge")
+        if time is not None and not self.is_temporal:
+            raise ValueError("'edge_label_time' is given but the sampler is not temporal (no "
+                             "'node_time' / 'edge_time')")
+        if time is None and self.is_temporal:
+            raise ValueError("a temporal sampler needs the seed-link times ('edge_label_time')")
+        if neg is not None:
+            neg.check(self.num_nodes)
+            if neg.is_triplet() and label is not None:
+                raise ValueError("'edge_label' needs to be undefined for 'triplet'-based negative "
+                                 "sampling")
+        if label is not None and label.size(0) != B:
+            raise ValueError(f"'edge_label' needs one entry per positive edge ({B})")
+        dev, dt = self.colptr.device, self.colptr.dtype
+        src = src.to(device=dev, dtype=dt)
+        dst = dst.to(device=dev, dtype=dt)
+        if time is not None:
+            time = self.seed_time(src, time)       # int64 [B] on the device
+        if label is not None:
+            label = label.to(dev)
+        rng = self.seed + self._calls if seed is None else seed
+        self._calls += 1
+        src_time = dst_time = time
+        num_neg = 0
+        if neg is not None:
+            num_neg = math.ceil(B * neg.amount)
+            if neg.is_binary():
+                src = torch.cat([src, self._negatives(num_neg, neg, 0, rng, src_time)])
+                dst = torch.cat([dst, self._negatives(num_neg, neg, 1, rng, dst_time)])
+                if label is None:
+                    label = torch.ones(B, device=dev)
+                label = torch.cat([label, label.new_zeros((num_neg, ) + label.shape[1:])])
+                if time is not None:
+                    src_time = dst_time = time.repeat(1 + math.ceil(neg.amount))[:B + num_neg]
+            else:
+                dst = torch.cat([dst, self._negatives(num_neg, neg, 1, rng, dst_time)])
+                if time is not None:
+                    dst_time = time.repeat(1 + neg.amount)
+        seeds = torch.cat([src, dst])
+        if not self.disjoint:
+            seeds, inverse = _native.unique_inverse(seeds, max_value=max(self.num_nodes - 1, 0))
+        seed_time = torch.cat([src_time, dst_time]) if time is not None else None
+        out = self._sample_seeds(seeds, rng, seed_time)
+        if self.disjoint:
+            out.batch = out.batch % B
+            order = torch.arange(seeds.numel(), device=dev)
+        if neg is None or neg.is_binary():
+            eli = order.view(2, -1) if self.disjoint else inverse.view(2, -1)
+            out.metadata = (input_id, eli, label, src_time)
+        else:
+            if self.disjoint:
+                src_index, dst_pos_index = order[:B], order[B:2 * B]
+                dst_neg_index = order[2 * B:].view(-1, B).t()
+            else:
+                src_index, dst_pos_index = inverse[:B], inverse[B:2 * B]
+                dst_neg_index = inverse[2 * B:]
+            dst_neg_index = dst_neg_index.reshape(B, -1).squeeze(-1)
+            out.metadata = (input_id, src_index, dst_pos_index, dst_neg_index, src_time)
+        return out
+
+    def _negatives(self, n: int, neg: NegativeSampling, endpoint: int, rng: int,
+                   bound: Optional[Tensor]) -> Tensor:
+        """``n`` negatives of one endpoint (0: source, 1: destination) in the graph's dtype: the
+        reference's ``neg_sample`` (sampler/neighbor_sampler.py:1051-1096).  With node-level time
+        draw ``j`` is bounded by ``bound[j % B]``; edge-level time draws without a bound, as the
+        reference does (its ``node_time`` is ``None`` then)."""
+        dev, dt = self.colptr.device, self.colptr.dtype
+        weight = neg.src_weight if endpoint == 0 else neg.dst_weight
+        cdf = None if weight is None else self._negative_cdf(weight)
+        node_time = fallback = None
+        if self.is_temporal and not self.edge_level:
+            node_time = self.time
+            if self._neg_fallback is None:  # the reference's node_time.argmin(), once
+                self._neg_fallback = int(torch.argmin(node_time))
+            fallback = self._neg_fallback
+        else:
+            bound = None
+        return _native.sample_negatives(n, self.num_nodes, (rng * 2 + endpoint), dev, dt, cdf=cdf,
+                                        node_time=node_time, bound=bound,
+                                        fallback=fallback or 0)
+
+    def _negative_cdf(self, weight: Tensor) -> Tensor:
+        """The fp64 inclusive CDF of a node weight vector, built once per tensor (and version) and
+        cached: setup work, the per-batch draw is the kernel.  One host read validates it like
+        ``torch.multinomial`` does (non-negative, finite, positive sum)."""
+        key = id(weight)
+        hit = self._neg_cdf.get(key)
+        if hit is not None and hit[0] is weight and hit[1] == weight._version:
+            return hit[2]
+        if not isinstance(weight, Tensor) or weight.dim() != 1 or weight.numel() != self.num_nodes:
+            raise ValueError(f"The 'weight' attribute in 'NegativeSampling' needs to match the "
+                             f"number of nodes {self.num_nodes}")
+        if not weight.is_floating_point():
+            raise ValueError(f"negative-sampling weights must be floating (got {weight.dtype})")
+        w = weight.to(device=self.colptr.device, dtype=torch.float64)
+        cdf = torch.cumsum(w, 0)
+        lo, total = (float(v) for v in torch.stack([w.min(), cdf[-1]]).tolist())
+        if not (lo >= 0 and math.isfinite(total) and total > 0):
+            raise ValueError("negative-sampling weights must be finite and non-negative with a "
+                             "positive sum")
+        if len(self._neg_cdf) >= 8:  # (a caller that makes a new weight tensor per batch)
+            self._neg_cdf.clear()
+        self._neg_cdf[key] = (weight, weight._version, cdf)
+        return cdf
 
     @torch.no_grad()
     def sample_padded(self, seeds: Tensor, seed: Optional[int] = None, padded_ids: bool = False,
