@@ -721,6 +721,67 @@ PYGAMD_API int pygamd_unique_inverse(const void* keys_sorted, const int64_t* per
                                      size_t workspace_bytes, void* uniq_out, int64_t* inverse_out,
                                      int64_t* n_unique, void* stream);
 
+/* ---- heterogeneous neighbour sampling: the typed layer -----------------------------------------
+ * Device-side counterpart of torch.ops.pyg.hetero_neighbor_sample(..., csc=True, ...) as the
+ * reference's NeighborSampler._sample calls it for a HeteroData (sampler/neighbor_sampler.py:
+ * 438-548): pyg-lib's sequential loop, hop by hop and, inside a hop, edge type by edge type.
+ * Every edge type shares ONE stacked CSC (colptr, row, perm in idx_dtype): node i of node type t
+ * has the global id node_base[t] + i, edge type et owns the columns [col_base[et], col_base[et] +
+ * N_dst(et)), row holds global source ids and perm each slot's position in its own type's
+ * edge_index.  A hop's work list is the concatenation, in edge-type order, of the frontier block of
+ * every edge type's destination type: item i belongs to the edge type et with item_begin[et] <= i
+ * < item_begin[et + 1] (item_begin: host int64 [n_et + 1], item_begin[0] = 0) and sits at
+ * p = i - item_begin[et] of its block.  et_table is host int64 [n_et][4]: frontier_off (where the
+ * block starts in `frontier`, the type-major buffer of global ids), col_off (col_base[et] -
+ * node_base[dst(et)]: the item's column is frontier[frontier_off + p] + col_off), dst_local (the
+ * typed local id of the block's first node) and k (the hop's fan-out, -1 = all, at most
+ * pygamd_sample_max_fanout()).  The tables travel in the kernel arguments (n_et <= 64), so ONE
+ * launch of each entry point serves a hop whatever the number of edge types.
+ * pygamd_hetero_sample_counts: cnt[i] = pygamd_sample_counts' rule on item i's column with its
+ *   edge type's k (replace != 0: k wherever deg > 0, for bounded k only).
+ * pygamd_hetero_sample_neighbors: offsets = the exclusive scan of cnt ([n + 1]); one wave per item
+ *   draws like pygamd_sample_neighbors (same flags: bit 0 replacement, applied only where the
+ *   item's k >= 0, bit 1 the item's position salts the draws), keyed by the stacked column id and
+ *   the item position, so one node type and one edge type (col_base = 0) draw bit for bit what
+ *   pygamd_sample_neighbors draws for the same seed.  Writes per sampled edge the global source
+ *   (src_out), the typed local destination dst_local + p (col_out), perm[slot] (edge_out) and,
+ *   when fpos_out is not NULL, the destination's position in `frontier`.
+ * pygamd_hetero_split: the hop's new nodes (global ids, the first *n_new of new_nodes[m] in order
+ *   of first appearance; n_new on the device) partitioned by node type (node_base: host int64
+ *   [n_t + 1], the last entry the total, n_t <= 64), stably.  Phase 0 writes the one-hot
+ *   flag_or_scan[t * m + j] = (type(new_nodes[j]) == t) (int64 [n_t * m]), which the caller scans
+ *   inclusively (pygamd_cumsum) as one vector.  Phase 1 reads that scan: node j of type t gets the
+ *   type-major position r = scan[t * m + j] - 1 and the typed local id count_prev[t] (host int64
+ *   [n_t]: nodes of type t in the batch before this hop) + its rank among the hop's nodes of type t;
+ *   it writes local_map[g] (may be NULL) and typed_out[j] (may be NULL) = that id,
+ *   sorted_global[r] = g, sorted_local[r] = g - node_base[t], aux_out[r] = aux_in[j] (int64 payload,
+ *   may be NULL), and stats (int64 [n_t + n_et + 1]): the new nodes per type, then
+ *   offsets[item_begin[e]] for e = 0 .. n_et (the hop's edge boundaries per edge type, 0 when
+ *   offsets is NULL and n_et = 0) — what the caller reads back, once per hop.
+ * Rejected before any launch: a bad phase, m < 0, n_t outside [1, 64], n_et outside [0, 64] (1 ..
+ * 64 for the sampling entry points), decreasing item_begin, k < -1, negative table entries or a
+ * NULL pointer the call needs -> PYGAMD_ERR_INVALID_ARG; k > pygamd_sample_max_fanout() ->
+ * PYGAMD_ERR_UNSUPPORTED; an unknown idx_dtype -> PYGAMD_ERR_INVALID_ARG.  An empty work list or
+ * m == 0 launches nothing.                                                                      */
+PYGAMD_API int pygamd_hetero_sample_counts(const void* colptr, int idx_dtype,
+                                           const void* frontier, const int64_t* item_begin,
+                                           const int64_t* et_table, int n_et, int replace,
+                                           void* cnt_out, void* stream);
+PYGAMD_API int pygamd_hetero_sample_neighbors(const void* colptr, const void* row,
+                                              const void* perm, int idx_dtype,
+                                              const void* frontier, const void* offsets,
+                                              const int64_t* item_begin,
+                                              const int64_t* et_table, int n_et, uint64_t seed,
+                                              int flags, void* src_out, void* col_out,
+                                              void* edge_out, void* fpos_out, void* stream);
+PYGAMD_API int pygamd_hetero_split(int phase, const void* new_nodes, int idx_dtype, int64_t m,
+                                   const int64_t* n_new, const int64_t* node_base,
+                                   const int64_t* count_prev, int n_t, int64_t* flag_or_scan,
+                                   const void* offsets, const int64_t* item_begin, int n_et,
+                                   const int64_t* aux_in, void* local_map, void* typed_out,
+                                   void* sorted_global, void* sorted_local, int64_t* aux_out,
+                                   int64_t* stats, void* stream);
+
 /* ---- a18: one-pass multi-reduce (FusedAggregation) ---------------------------------------------
  * nn/aggr/fused.py:191-336 shares the group count, the sum and the sum of squares between
  * sum / mean / var / std / min / max.  Here ONE read of the rows produces all requested statistics

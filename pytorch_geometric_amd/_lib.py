@@ -166,6 +166,11 @@ SIGNATURES = {
     'pygamd_sample_negatives': (c_int, [c_int64, c_int64, c_uint64, _P, _P, _P, _P, c_int64,
                                         c_int64, c_int, _P, _P]),
     'pygamd_unique_inverse': (c_int, [_P, _P, c_int, c_int64, _P, _P, c_size_t, _P, _P, _P, _P]),
+    'pygamd_hetero_sample_counts': (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
+    'pygamd_hetero_sample_neighbors': (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_uint64,
+                                               c_int, _P, _P, _P, _P, _P]),
+    'pygamd_hetero_split': (c_int, [c_int, _P, c_int, c_int64, _P, _P, _P, c_int, _P, _P, _P,
+                                    c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     'pygamd_gather_rows': (c_int, [_P, c_int64, c_int64, _P, c_int, c_int64, c_int64, _P,
                                    c_int64, _P, _P]),
     'pygamd_gather_scatter_add': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P, c_int64, _P,

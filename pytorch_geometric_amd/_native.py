@@ -1916,6 +1916,125 @@ def unique_inverse(keys: Tensor, max_value: Optional[int] = None) -> Tuple[Tenso
     return uniq[:int(n_unique)], inverse  # host read: sizes the seed block
 
 
+# ---- heterogeneous sampling: the typed layer over one stacked CSC -----------------------------------
+def _i64_host(values):
+    """A host int64 array for the small per-type tables of the hetero entry points."""
+    arr = (ctypes.c_int64 * max(len(values), 1))(*values)
+    return arr
+
+
+def hetero_sample_counts(colptr: Tensor, frontier: Tensor, item_begin, et_table,
+                         replace: bool = False) -> Tensor:
+    """``pygamd_hetero_sample_counts``: per work item of a hop, ``min(deg, k)`` with the ``k`` of
+    the item's edge type (see ``include/pyg_amd.h``).  ``item_begin``: host ints ``[n_et + 1]``;
+    ``et_table``: rows ``(frontier_off, col_off, dst_local, k)`` per edge type."""
+    _require_device(colptr, frontier)
+    if frontier.dtype != colptr.dtype:
+        raise ValueError("'frontier' must have the graph's index dtype")
+    lib = _lib.load()
+    n = int(item_begin[-1])
+    cnt = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
+    flat = [int(v) for row in et_table for v in row]
+    check(lib.pygamd_hetero_sample_counts(_p(colptr), _idx_dtype(colptr), _p(frontier),
+                                          _i64_host(item_begin), _i64_host(flat), len(et_table),
+                                          int(replace), _p(cnt), _stream(colptr)),
+          'hetero_sample_counts')
+    return cnt
+
+
+def hetero_sample_neighbors(colptr: Tensor, row: Tensor, perm: Tensor, frontier: Tensor,
+                            offsets: Tensor, capacity: int, item_begin, et_table, seed: int,
+                            replace: bool = False, salt_position: bool = False,
+                            want_fpos: bool = False):
+    """``pygamd_hetero_sample_neighbors``: ``(src_global, col_local, edge, fpos)`` of one hop at the
+    static ``capacity`` (entries past ``offsets[-1]`` are not written, except ``fpos``, which is
+    zero-filled; ``None`` unless ``want_fpos``)."""
+    _require_device(colptr, row, perm, frontier, offsets)
+    lib = _lib.load()
+    dt, dev = colptr.dtype, colptr.device
+    src = torch.empty(capacity, dtype=dt, device=dev)
+    col = torch.empty(capacity, dtype=dt, device=dev)
+    edge = torch.empty(capacity, dtype=dt, device=dev)
+    fpos = torch.zeros(capacity, dtype=dt, device=dev) if want_fpos else None
+    flat = [int(v) for r in et_table for v in r]
+    if capacity > 0 and int(item_begin[-1]) > 0:
+        check(lib.pygamd_hetero_sample_neighbors(
+            _p(colptr), _p(row), _p(perm), _idx_dtype(colptr), _p(frontier), _p(offsets),
+            _i64_host(item_begin), _i64_host(flat), len(et_table), seed & 0xFFFFFFFFFFFFFFFF,
+            int(replace) | (2 if salt_position else 0), _p(src), _p(col), _p(edge), _p(fpos),
+            _stream(colptr)), 'hetero_sample_neighbors')
+    return src, col, edge, fpos
+
+
+def hetero_split(new_nodes: Tensor, n_new: Tensor, node_base, count_prev, offsets: Optional[Tensor],
+                 item_begin, local_map: Optional[Tensor] = None, want_typed: bool = False,
+                 aux: Optional[Tensor] = None):
+    """``pygamd_hetero_split`` (both phases and the scan between them): the stable partition by
+    node type of the hop's new nodes (the first ``n_new`` (int64 [1], device) of ``new_nodes``).
+    Returns ``(sorted_global, sorted_local, typed, aux_sorted, stats)``: the type-major buffers,
+    the typed local id of every new node (``want_typed``; else ``None``), ``aux`` (int64) in
+    type-major order, and the int64 stats ``[n_t + n_et + 1]`` (new nodes per type, then the edge
+    boundaries ``offsets[item_begin[e]]``)."""
+    _require_device(new_nodes, n_new, offsets, local_map, aux)
+    lib = _lib.load()
+    m = new_nodes.numel()
+    dt, dev = new_nodes.dtype, new_nodes.device
+    n_t, n_et = len(node_base) - 1, len(item_begin) - 1
+    sorted_global = torch.empty(m, dtype=dt, device=dev)
+    sorted_local = torch.empty(m, dtype=dt, device=dev)
+    typed = torch.empty(m, dtype=dt, device=dev) if want_typed else None
+    aux_sorted = torch.empty(m, dtype=torch.int64, device=dev) if aux is not None else None
+    stats = torch.zeros(n_t + n_et + 1, dtype=torch.int64, device=dev)
+    if m == 0:
+        return sorted_global, sorted_local, typed, aux_sorted, stats
+    nb, cp, ib = _i64_host(node_base), _i64_host(count_prev), _i64_host(item_begin)
+    flag = torch.empty(n_t * m, dtype=torch.int64, device=dev)
+    st = _stream(new_nodes)
+    check(lib.pygamd_hetero_split(0, _p(new_nodes), _idx_dtype(new_nodes), m, _p(n_new), nb, cp,
+                                  n_t, _p(flag), None, ib, n_et, None, None, None, None, None,
+                                  None, None, st), 'hetero_split')
+    cumsum(flag, out=flag)
+    check(lib.pygamd_hetero_split(1, _p(new_nodes), _idx_dtype(new_nodes), m, _p(n_new), nb, cp,
+                                  n_t, _p(flag), _p(offsets), ib, n_et, _p(aux), _p(local_map),
+                                  _p(typed), _p(sorted_global), _p(sorted_local), _p(aux_sorted),
+                                  _p(stats), st), 'hetero_split')
+    return sorted_global, sorted_local, typed, aux_sorted, stats
+
+
+def relabel_claim_assign(src_global: Tensor, total: Tensor, local_map: Tensor):
+    """Phases 0-2 of ``pygamd_relabel`` at a static capacity (``total``: int64 [1] on the device):
+    ``(new_nodes [capacity], n_new int64 [1])``, the new sources in order of first appearance;
+    ``local_map`` holds their ranks afterwards.  No host read."""
+    _require_device(src_global, total, local_map)
+    lib = _lib.load()
+    m = src_global.numel()
+    dt, st, dev = _idx_dtype(src_global), _stream(src_global), src_global.device
+    new_nodes = torch.empty(m, dtype=src_global.dtype, device=dev)
+    if m == 0:
+        return new_nodes, torch.zeros(1, dtype=torch.int64, device=dev)
+    check(lib.pygamd_relabel(0, _p(src_global), dt, m, _p(total), _p(local_map), None, 0, None,
+                             None, st))
+    flag = torch.empty(m, dtype=torch.int64, device=dev)
+    check(lib.pygamd_relabel(1, _p(src_global), dt, m, _p(total), _p(local_map), _p(flag), 0,
+                             None, None, st))
+    scan = cumsum(flag, out=flag)
+    check(lib.pygamd_relabel(2, _p(src_global), dt, m, _p(total), _p(local_map), _p(scan), 0,
+                             None, _p(new_nodes), st))
+    return new_nodes, scan[-1:]
+
+
+def relabel_lookup(src_global: Tensor, total: Tensor, local_map: Tensor) -> Tensor:
+    """Phase 3 of ``pygamd_relabel``: ``local_map[src]`` for the first ``total`` entries, 0 after."""
+    _require_device(src_global, total, local_map)
+    lib = _lib.load()
+    out = torch.empty_like(src_global)
+    if src_global.numel() > 0:
+        check(lib.pygamd_relabel(3, _p(src_global), _idx_dtype(src_global), src_global.numel(),
+                                 _p(total), _p(local_map), None, 0, None, _p(out),
+                                 _stream(src_global)))
+    return out
+
+
 def edge_key(row: Tensor, col: Tensor, num_nodes: int, by_row: bool) -> Tensor:
     _require_device(row, col)
     lib = _lib.load()

@@ -887,6 +887,12 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     with ``temporal_strategy`` (``'uniform'`` | ``'last'``): temporal sampling, always disjoint;
     the reference's ``NodeLoader`` passes its ``input_time`` as ``NodeSamplerInput.time`` and reads
     ``seed_time`` from ``metadata[1]``.  It needs the ``Data`` form too.
+    A ``torch_geometric.data.HeteroData`` gives a heterogeneous sampler
+    (:class:`pytorch_geometric_amd.sampler.HeteroNeighborSampler` over ``data.metadata()``):
+    ``sample_from_nodes`` returns the reference's ``HeteroSamplerOutput`` with tuple keys, so
+    ``NodeLoader(hetero_data, node_sampler=..., input_nodes='paper')`` yields its own ``HeteroData``
+    batches through ``filter_hetero_data`` (loader/node_loader.py:209-257); ``num_neighbors`` is a
+    list or a dict keyed by edge type; ``weight_attr`` / ``time_attr`` are refused.
     ``sample_from_edges(EdgeSamplerInput, neg_sampling)`` is link-level sampling
     (:meth:`pytorch_geometric_amd.sampler.NeighborSampler.sample_from_edges`), so that the
     reference's ``LinkLoader(data, link_sampler=...)`` (loader/link_loader.py) drives it too; its
@@ -895,6 +901,9 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     global _sampler_cls
     import torch_geometric.sampler as pyg_sampler
     from .sampler import NeighborSampler
+    if hasattr(data, 'metadata') and hasattr(data, 'edge_index_dict'):  # a HeteroData
+        return _hetero_neighbor_sampler(data, num_neighbors, seed, replace, disjoint,
+                                        subgraph_type, weight_attr, time_attr)
     if _sampler_cls is None:
 
         class MI355XNeighborSampler(pyg_sampler.BaseSampler):
@@ -958,6 +967,56 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
                         subgraph_type, edge_weight=edge_weight, weight_attr=weight_attr,
                         node_time=node_time, edge_time=edge_time, time_attr=time_attr,
                         temporal_strategy=temporal_strategy)
+
+
+_hetero_sampler_cls = None
+
+
+def _hetero_neighbor_sampler(data, num_neighbors, seed, replace, disjoint, subgraph_type,
+                             weight_attr, time_attr):
+    """The ``HeteroData`` branch of :func:`neighbor_sampler`."""
+    global _hetero_sampler_cls
+    import torch_geometric.sampler as pyg_sampler
+    from .sampler import HeteroNeighborSampler
+    if weight_attr is not None or time_attr is not None:
+        raise ValueError("weighted or temporal heterogeneous sampling ('weight_attr' / "
+                         "'time_attr' with a 'HeteroData') is not supported")
+    if _hetero_sampler_cls is None:
+
+        class MI355XHeteroNeighborSampler(pyg_sampler.BaseSampler):
+            def __init__(self, edge_index_dict, num_nodes_dict, num_neighbors, seed=0,
+                         replace=False, disjoint=False, subgraph_type='directional'):
+                self.impl = HeteroNeighborSampler(
+                    edge_index_dict, num_nodes_dict, num_neighbors, seed=seed,
+                    replace=replace, disjoint=disjoint, subgraph_type=subgraph_type,
+                    output_cls=pyg_sampler.HeteroSamplerOutput)
+                # the reference's NeighborSampler attributes (sampler/neighbor_sampler.py:116-150)
+                self.node_types, self.edge_types = self.impl.node_types, self.impl.edge_types
+                self.num_nodes = dict(self.impl.num_nodes)
+                self.num_neighbors = dict(self.impl.num_neighbors)
+                self.replace, self.disjoint = self.impl.replace, self.impl.disjoint
+                self.subgraph_type = self.impl.subgraph_type
+
+            def sample_from_nodes(self, index, **kwargs):
+                return self.impl.sample_from_nodes(index, **kwargs)
+
+            def sample_from_edges(self, index, neg_sampling=None):
+                return self.impl.sample_from_edges(index, neg_sampling)
+
+            @property
+            def edge_permutation(self):
+                return None  # `edge` already indexes every type's own edge_index
+
+        _hetero_sampler_cls = MI355XHeteroNeighborSampler
+    node_types, edge_types = data.metadata()
+    num_nodes = {t: int(data[t].num_nodes or 0) for t in node_types}
+    edge_index_dict = {et: data[et].edge_index for et in edge_types}
+    for ei in edge_index_dict.values():
+        if not (isinstance(ei, Tensor) and ei.is_cuda):
+            raise ValueError("the sampler needs every 'edge_index' on the HIP device (there is "
+                             "no CPU fallback): move the data with `.to('cuda')` first")
+    return _hetero_sampler_cls(edge_index_dict, num_nodes, num_neighbors, seed, replace,
+                               disjoint, subgraph_type)
 
 
 def _wrap_linear_forward(cls):

@@ -25,16 +25,18 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
 }
 
 // deg(v) <= count: lanes copy the slot range [s, s + deg), coalesced, in slot order
+// (`perm`, the heterogeneous draw: slot_out receives perm[slot] in place of the slot)
 template <typename IdxT>
 __device__ __forceinline__ void copy_all_slots(const IdxT* __restrict__ row, int64_t s,
                                                int64_t deg, int64_t o, int64_t f,
                                                IdxT* __restrict__ src_out,
                                                IdxT* __restrict__ dstpos_out,
-                                               IdxT* __restrict__ slot_out) {
+                                               IdxT* __restrict__ slot_out,
+                                               const IdxT* __restrict__ perm = nullptr) {
   for (int64_t t = lane_id(); t < deg; t += kWave) {
     src_out[o + t] = row[s + t];
     dstpos_out[o + t] = static_cast<IdxT>(f);
-    slot_out[o + t] = static_cast<IdxT>(s + t);
+    slot_out[o + t] = perm ? perm[s + t] : static_cast<IdxT>(s + t);
   }
 }
 
@@ -60,7 +62,8 @@ __device__ __forceinline__ void draw_uniform(const IdxT* __restrict__ row, int64
                                              int64_t o, int64_t cnt, int64_t f, uint64_t key,
                                              bool replace, IdxT* __restrict__ src_out,
                                              IdxT* __restrict__ dstpos_out,
-                                             IdxT* __restrict__ slot_out) {
+                                             IdxT* __restrict__ slot_out,
+                                             const IdxT* __restrict__ perm = nullptr) {
   const int lane = lane_id();
   if (replace) {  // cnt = k independent draws from the deg in-neighbours (deg > 0 here)
     if (lane < cnt) {
@@ -68,12 +71,12 @@ __device__ __forceinline__ void draw_uniform(const IdxT* __restrict__ row, int64
       const int64_t t = static_cast<int64_t>(__umul64hi(r, static_cast<uint64_t>(deg)));
       src_out[o + lane] = row[s + t];
       dstpos_out[o + lane] = static_cast<IdxT>(f);
-      slot_out[o + lane] = static_cast<IdxT>(s + t);
+      slot_out[o + lane] = perm ? perm[s + t] : static_cast<IdxT>(s + t);
     }
     return;
   }
   if (deg <= cnt) {  // take every in-neighbour
-    copy_all_slots(row, s, deg, o, f, src_out, dstpos_out, slot_out);
+    copy_all_slots(row, s, deg, o, f, src_out, dstpos_out, slot_out, perm);
     return;
   }
   // Floyd: for j = deg-k .. deg-1: t = U{0..j}; insert t, or j if t is already chosen.  Lane c
@@ -95,7 +98,7 @@ __device__ __forceinline__ void draw_uniform(const IdxT* __restrict__ row, int64
   if (lane < k) {
     src_out[o + lane] = row[s + mine];
     dstpos_out[o + lane] = static_cast<IdxT>(f);
-    slot_out[o + lane] = static_cast<IdxT>(s + mine);
+    slot_out[o + lane] = perm ? perm[s + mine] : static_cast<IdxT>(s + mine);
   }
 }
 
@@ -589,6 +592,155 @@ __global__ void __launch_bounds__(kBlock)
   if (i == n - 1) n_unique[0] = r + 1;
 }
 
+// ---- heterogeneous hops (the reference's NeighborLoader(hetero_data, ...) ->
+// torch.ops.pyg.hetero_neighbor_sample(..., csc=True, ...), sampler/neighbor_sampler.py:438-548).
+// Every edge type lives in ONE stacked CSC: node i of type t is the global id node_base[t] + i, edge
+// type et owns the columns [col_base[et], col_base[et] + N_dst(et)), `row` holds global source ids
+// and `perm` each slot's position in its own type's edge_index.  A hop's work list is the
+// concatenation, in edge-type order, of the frontier block of every edge type's destination type:
+// item i belongs to the edge type et with item_begin[et] <= i < item_begin[et + 1] and sits at
+// p = i - item_begin[et] in that block, which starts at frontier_off[et] of the type-major frontier
+// buffer (global ids).  Its column is frontier[frontier_off[et] + p] + col_off[et] (col_off =
+// col_base - node_base[dst]).  The per-edge-type values travel in the kernel arguments, so ONE
+// launch serves every edge type of a hop.
+constexpr int kMaxEdgeTypes = 64;
+constexpr int kMaxNodeTypes = 64;
+
+struct HeteroHop {
+  int64_t item_begin[kMaxEdgeTypes + 1];
+  int64_t frontier_off[kMaxEdgeTypes];
+  int64_t col_off[kMaxEdgeTypes];
+  int64_t dst_local[kMaxEdgeTypes];  // typed local id of the block's first node (-> col)
+  int32_t k[kMaxEdgeTypes];          // fan-out of the hop, -1 = every in-neighbour
+  int32_t n_et;
+};
+
+// the edge type of work item i: the last et with item_begin[et] <= i (empty types skipped)
+__device__ __forceinline__ int hetero_edge_type(const HeteroHop& h, int64_t i) {
+  int lo = 0, hi = h.n_et - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (h.item_begin[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// cnt[i] = pygamd_sample_counts' rule with the k of item i's edge type
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    hetero_counts_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ frontier,
+                         const HeteroHop hop, int replace, IdxT* __restrict__ cnt) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= hop.item_begin[hop.n_et]) return;
+  const int et = hetero_edge_type(hop, i);
+  const int64_t c = static_cast<int64_t>(frontier[hop.frontier_off[et] + i - hop.item_begin[et]]) +
+                    hop.col_off[et];
+  const int64_t deg = static_cast<int64_t>(colptr[c + 1]) - static_cast<int64_t>(colptr[c]);
+  const int64_t k = hop.k[et];
+  if (replace && k >= 0) {
+    cnt[i] = static_cast<IdxT>(deg > 0 ? k : 0);
+  } else {
+    cnt[i] = static_cast<IdxT>((k >= 0 && deg > k) ? k : deg);
+  }
+}
+
+// One wave per work item: draw_uniform on the item's column, keyed by the stacked column id and
+// the item's position (a single type with col_base = 0 draws what sample_neighbors_kernel draws);
+// replacement only where the item's edge type has a bounded fan-out.  Writes the global source,
+// the typed local destination (dst_local + p), the edge id perm[slot] and, when fpos_out is given,
+// the destination's position in the frontier buffer.
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    hetero_sample_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
+                         const IdxT* __restrict__ perm, const IdxT* __restrict__ frontier,
+                         const IdxT* __restrict__ offsets, const HeteroHop hop, uint64_t seed,
+                         int flags, IdxT* __restrict__ src_out, IdxT* __restrict__ col_out,
+                         IdxT* __restrict__ edge_out, IdxT* __restrict__ fpos_out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+  if (i >= hop.item_begin[hop.n_et]) return;
+  const int64_t o = offsets[i];
+  const int64_t cnt = static_cast<int64_t>(offsets[i + 1]) - o;
+  if (cnt <= 0) return;
+  const int et = hetero_edge_type(hop, i);
+  const int64_t p = i - hop.item_begin[et];
+  const int64_t fp = hop.frontier_off[et] + p;
+  const int64_t c = static_cast<int64_t>(frontier[fp]) + hop.col_off[et];
+  const int64_t s = colptr[c];
+  const int64_t deg = static_cast<int64_t>(colptr[c + 1]) - s;
+  const uint64_t key = node_key(seed, nullptr, c, i, flags);
+  const bool rep = (flags & 1) != 0 && hop.k[et] >= 0;
+  draw_uniform(row, s, deg, o, cnt, hop.dst_local[et] + p, key, rep, src_out, col_out, edge_out,
+               perm);
+  if (fpos_out) {
+    for (int64_t t = lane_id(); t < cnt; t += kWave) fpos_out[o + t] = static_cast<IdxT>(fp);
+  }
+}
+
+// ---- the typed split of a hop's new nodes (global ids in order of first appearance, the first
+// *n_new of new_nodes[m]): a stable partition by node type.  Phase 0 writes the one-hot matrix
+// flag[t * m + j] = (type(new_nodes[j]) == t), which the caller scans inclusively as ONE vector of
+// n_t * m entries; then scan[t * m + j] - 1 is node j's position in the type-major order and
+// scan[t * m + j] - scan[t * m - 1] - 1 its rank among the new nodes of its type.  Phase 1 turns
+// that into the typed local id count_prev[t] + rank (into local[g] and / or typed_out[j]), writes
+// the type-major buffers (global id, id inside the type, aux payload) and the hop's stats: the new
+// nodes per type, then offsets[item_begin[et]] for et = 0 .. n_et (the edge boundaries).
+struct HeteroTypes {
+  int64_t node_base[kMaxNodeTypes + 1];
+  int64_t count_prev[kMaxNodeTypes];
+  int64_t item_begin[kMaxEdgeTypes + 1];
+  int32_t n_t;
+  int32_t n_et;
+};
+
+__device__ __forceinline__ int hetero_node_type(const HeteroTypes& h, int64_t g) {
+  int lo = 0, hi = h.n_t - 1;  // the last t with node_base[t] <= g
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (h.node_base[mid] <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    hetero_split_flag_kernel(const IdxT* __restrict__ new_nodes, int64_t m,
+                             const int64_t* __restrict__ n_new, const HeteroTypes types,
+                             int64_t* __restrict__ flag) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (j >= m) return;
+  const int t = j < *n_new ? hetero_node_type(types, new_nodes[j]) : -1;
+  for (int u = 0; u < types.n_t; ++u) flag[u * m + j] = (u == t) ? 1 : 0;
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    hetero_split_apply_kernel(const IdxT* __restrict__ new_nodes, int64_t m,
+                              const int64_t* __restrict__ n_new, const int64_t* __restrict__ scan,
+                              const HeteroTypes types, const IdxT* __restrict__ offsets,
+                              const int64_t* __restrict__ aux_in, IdxT* __restrict__ local,
+                              IdxT* __restrict__ typed_out, IdxT* __restrict__ sorted_global,
+                              IdxT* __restrict__ sorted_local, int64_t* __restrict__ aux_out,
+                              int64_t* __restrict__ stats) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (j < types.n_t) {
+    stats[j] = scan[(j + 1) * m - 1] - (j > 0 ? scan[j * m - 1] : 0);
+  }
+  if (j <= types.n_et) {
+    stats[types.n_t + j] = offsets ? static_cast<int64_t>(offsets[types.item_begin[j]]) : 0;
+  }
+  if (j >= m || j >= *n_new) return;
+  const int64_t g = new_nodes[j];
+  const int t = hetero_node_type(types, g);
+  const int64_t before = t > 0 ? scan[t * m - 1] : 0;
+  const int64_t r = scan[t * m + j] - 1;
+  const int64_t typed = types.count_prev[t] + (r - before);
+  if (local) local[g] = static_cast<IdxT>(typed);
+  if (typed_out) typed_out[j] = static_cast<IdxT>(typed);
+  sorted_global[r] = static_cast<IdxT>(g);
+  sorted_local[r] = static_cast<IdxT>(g - types.node_base[t]);
+  if (aux_in) aux_out[r] = aux_in[j];
+}
+
 }  // namespace pygamd
 
 using namespace pygamd;
@@ -796,6 +948,114 @@ int pygamd_unique_inverse(const void* keys_sorted, const int64_t* perm, int idx_
     if (scan_rc != PYGAMD_OK) return scan_rc;
     hipLaunchKernelGGL((unique_scatter_kernel<IdxT>), grid, dim3(kBlock), 0, st, keys, perm, n,
                        rank, static_cast<IdxT*>(uniq_out), inverse_out, n_unique);
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+// the kernel-argument table of a hop from the caller's host arrays (see pyg_amd.h)
+static int fill_hetero_hop(const int64_t* item_begin, const int64_t* et_table, int n_et,
+                           HeteroHop* hop) {
+  if (n_et <= 0 || n_et > kMaxEdgeTypes || !item_begin || !et_table) return PYGAMD_ERR_INVALID_ARG;
+  if (item_begin[0] != 0) return PYGAMD_ERR_INVALID_ARG;
+  hop->n_et = n_et;
+  for (int e = 0; e < n_et; ++e) {
+    if (item_begin[e + 1] < item_begin[e]) return PYGAMD_ERR_INVALID_ARG;
+    const int64_t k = et_table[4 * e + 3];
+    if (k > kMaxFanout) return PYGAMD_ERR_UNSUPPORTED;
+    if (k < -1 || et_table[4 * e] < 0 || et_table[4 * e + 2] < 0) return PYGAMD_ERR_INVALID_ARG;
+    hop->item_begin[e] = item_begin[e];
+    hop->frontier_off[e] = et_table[4 * e];
+    hop->col_off[e] = et_table[4 * e + 1];
+    hop->dst_local[e] = et_table[4 * e + 2];
+    hop->k[e] = static_cast<int32_t>(k);
+  }
+  hop->item_begin[n_et] = item_begin[n_et];
+  return PYGAMD_OK;
+}
+
+int pygamd_hetero_sample_counts(const void* colptr, int idx_dtype, const void* frontier,
+                                const int64_t* item_begin, const int64_t* et_table, int n_et,
+                                int replace, void* cnt_out, void* stream) {
+  HeteroHop hop;
+  const int rc = fill_hetero_hop(item_begin, et_table, n_et, &hop);
+  if (rc != PYGAMD_OK) return rc;
+  const int64_t n = hop.item_begin[n_et];
+  if (n == 0) return PYGAMD_OK;
+  if (!colptr || !frontier || !cnt_out) return PYGAMD_ERR_INVALID_ARG;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    hipLaunchKernelGGL((hetero_counts_kernel<IdxT>),
+                       dim3(static_cast<unsigned>(ceil_div(n, kBlock))), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(colptr),
+                       static_cast<const IdxT*>(frontier), hop, replace ? 1 : 0,
+                       static_cast<IdxT*>(cnt_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_hetero_sample_neighbors(const void* colptr, const void* row, const void* perm,
+                                   int idx_dtype, const void* frontier, const void* offsets,
+                                   const int64_t* item_begin, const int64_t* et_table, int n_et,
+                                   uint64_t seed, int flags, void* src_out, void* col_out,
+                                   void* edge_out, void* fpos_out, void* stream) {
+  HeteroHop hop;
+  const int rc = fill_hetero_hop(item_begin, et_table, n_et, &hop);
+  if (rc != PYGAMD_OK) return rc;
+  const int64_t n = hop.item_begin[n_et];
+  if (n == 0) return PYGAMD_OK;
+  if (!colptr || !row || !perm || !frontier || !offsets || !src_out || !col_out || !edge_out)
+    return PYGAMD_ERR_INVALID_ARG;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid = static_cast<unsigned>(ceil_div(n, kWavesPerBlock));
+    hipLaunchKernelGGL((hetero_sample_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(colptr),
+                       static_cast<const IdxT*>(row), static_cast<const IdxT*>(perm),
+                       static_cast<const IdxT*>(frontier), static_cast<const IdxT*>(offsets), hop,
+                       seed, flags, static_cast<IdxT*>(src_out), static_cast<IdxT*>(col_out),
+                       static_cast<IdxT*>(edge_out), static_cast<IdxT*>(fpos_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_hetero_split(int phase, const void* new_nodes, int idx_dtype, int64_t m,
+                        const int64_t* n_new, const int64_t* node_base, const int64_t* count_prev,
+                        int n_t, int64_t* flag_or_scan, const void* offsets,
+                        const int64_t* item_begin, int n_et, const int64_t* aux_in,
+                        void* local_map, void* typed_out, void* sorted_global,
+                        void* sorted_local, int64_t* aux_out, int64_t* stats, void* stream) {
+  if (phase < 0 || phase > 1 || m < 0) return PYGAMD_ERR_INVALID_ARG;
+  if (n_t <= 0 || n_t > kMaxNodeTypes || n_et < 0 || n_et > kMaxEdgeTypes || !node_base)
+    return PYGAMD_ERR_INVALID_ARG;
+  if (phase == 1 && (!count_prev || (n_et > 0 && !item_begin))) return PYGAMD_ERR_INVALID_ARG;
+  if (m == 0) return PYGAMD_OK;
+  if (!new_nodes || !n_new || !flag_or_scan) return PYGAMD_ERR_INVALID_ARG;
+  if (phase == 1 && (!sorted_global || !sorted_local || !stats || (aux_in && !aux_out) ||
+                     (n_et > 0 && !offsets)))
+    return PYGAMD_ERR_INVALID_ARG;
+  HeteroTypes types;
+  types.n_t = n_t;
+  types.n_et = n_et;
+  for (int t = 0; t <= n_t; ++t) types.node_base[t] = node_base[t];
+  for (int t = 0; t < n_t; ++t) types.count_prev[t] = phase == 1 ? count_prev[t] : 0;
+  for (int e = 0; e <= n_et; ++e) types.item_begin[e] = phase == 1 && item_begin ? item_begin[e] : 0;
+  hipStream_t st = as_stream(stream);
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const IdxT* nn = static_cast<const IdxT*>(new_nodes);
+    if (phase == 0) {
+      hipLaunchKernelGGL((hetero_split_flag_kernel<IdxT>),
+                         dim3(static_cast<unsigned>(ceil_div(m, kBlock))), dim3(kBlock), 0, st,
+                         nn, m, n_new, types, flag_or_scan);
+    } else {
+      const int64_t n = m > n_et + 1 ? m : n_et + 1;  // (n_t <= m: one flag row per type)
+      hipLaunchKernelGGL((hetero_split_apply_kernel<IdxT>),
+                         dim3(static_cast<unsigned>(ceil_div(n > n_t ? n : n_t, kBlock))),
+                         dim3(kBlock), 0, st, nn, m, n_new, flag_or_scan, types,
+                         static_cast<const IdxT*>(offsets), aux_in, static_cast<IdxT*>(local_map),
+                         static_cast<IdxT*>(typed_out), static_cast<IdxT*>(sorted_global),
+                         static_cast<IdxT*>(sorted_local), aux_out, stats);
+    }
     PYGAMD_LAUNCH_CHECK();
     return PYGAMD_OK;
   });

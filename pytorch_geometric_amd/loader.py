@@ -4,12 +4,13 @@ BASELINE config 4 — seeds are drawn per batch, the k-hop neighbourhood is samp
 (:mod:`.sampler`), features are gathered with the HIP gather kernel (``filter_data``'s
 ``x[n_id]``) and the batch never touches the host.  :class:`LinkNeighborLoader` is the
 ``LinkNeighborLoader`` role (loader/link_neighbor_loader.py, link_loader.py): batches of seed
-links with negatives drawn on the device."""
+links with negatives drawn on the device.  :class:`HeteroNeighborLoader` is ``NeighborLoader`` on
+a ``HeteroData`` (seeds of one node type, features per node type)."""
 import queue
 import threading
 from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Iterator, List, Optional
+from typing import Dict, Iterator, List, Optional
 
 import torch
 from torch import Tensor
@@ -18,7 +19,7 @@ import os
 
 from . import _native
 from .edge_index import EdgeIndex
-from .sampler import NegativeSampling, NeighborSampler
+from .sampler import HeteroNeighborSampler, NegativeSampling, NeighborSampler
 
 # collate_slots: layer 0 of the slot stack gathers its neighbours' rows straight from the feature
 # matrix (only the destination rows of a batch are copied) — slots.SlotSampler.gather(direct=True).
@@ -100,8 +101,11 @@ class _Prefetching:
             return
         yield from self._prefetching_iter()
 
+    def _stream_device(self):
+        return self.x.device
+
     def _prefetching_iter(self) -> Iterator:
-        dev = self.x.device
+        dev = self._stream_device()
         if self._side is None:
             self._side = torch.cuda.Stream(dev)
         side = self._side
@@ -420,3 +424,111 @@ class LinkNeighborLoader(_Prefetching):
         else:
             b.src_index, b.dst_pos_index, b.dst_neg_index, b.seed_time = md[1:5]
         return b
+
+
+@dataclass
+class HeteroBatch:
+    """A heterogeneous mini-batch (:class:`HeteroNeighborLoader`): per node type ``x_dict``,
+    ``n_id`` and (disjoint) ``batch``; per edge type ``edge_index_dict`` (local ``[row, col]``
+    into ``n_id[src]`` / ``n_id[dst]``) and ``e_id`` (positions in that type's ``edge_index``);
+    ``y`` the labels of the sampled ``input_type`` nodes (seeds first)."""
+    x_dict: Dict[str, Tensor]
+    edge_index_dict: Dict[tuple, Tensor]
+    n_id: Dict[str, Tensor]
+    e_id: Dict[tuple, Tensor]
+    input_type: str
+    input_id: Tensor
+    batch_size: int
+    num_sampled_nodes: Dict[str, List[int]]
+    num_sampled_edges: Dict[tuple, List[int]]
+    y: Optional[Tensor] = None
+    batch: Optional[Dict[str, Tensor]] = None
+
+    def record_stream(self, stream) -> None:
+        for d in (self.x_dict, self.edge_index_dict, self.n_id, self.e_id, self.batch or {}):
+            for t in d.values():
+                if isinstance(t, Tensor) and t.is_cuda:
+                    t.record_stream(stream)
+        for t in (self.input_id, self.y):
+            if isinstance(t, Tensor) and t.is_cuda:
+                t.record_stream(stream)
+
+
+class HeteroNeighborLoader(_Prefetching):
+    r"""Iterates over mini-batches of ``batch_size`` seed nodes of one node type with their sampled
+    heterogeneous ``k``-hop neighbourhoods: the reference's ``NeighborLoader(hetero_data,
+    input_nodes=...)`` (loader/neighbor_loader.py, node_loader.py:209-257), sampled on the GPU
+    (:class:`~.sampler.HeteroNeighborSampler`).
+
+    Args:
+        x_dict: node features per node type ``[N_t, F_t]`` (fp32, device); their row counts are the
+            numbers of nodes, their order the node types'.
+        edge_index_dict: ``[2, E]`` device tensors per edge type ``(src, rel, dst)``.
+        num_neighbors: one fan-out list for every edge type, or a dict keyed by edge type.
+        input_nodes: the seed type, or ``(type, nodes)`` with a tensor of node ids or a boolean
+            mask of that type.
+        y: optional labels of the input type ``[N_input]``; a batch carries those of its sampled
+            input-type nodes.
+        batch_size, shuffle, drop_last, seed, prefetch, replace, disjoint: as for
+            :class:`NeighborLoader`.
+
+    Yields :class:`HeteroBatch`.
+    """
+
+    def __init__(self, x_dict: Dict[str, Tensor], edge_index_dict, num_neighbors, input_nodes,
+                 batch_size: int = 1024, y: Optional[Tensor] = None, shuffle: bool = False,
+                 drop_last: bool = False, seed: int = 0, prefetch: int = 0,
+                 replace: bool = False, disjoint: bool = False):
+        if isinstance(input_nodes, str):
+            input_type, nodes = input_nodes, None
+        elif isinstance(input_nodes, (tuple, list)) and len(input_nodes) == 2:
+            input_type, nodes = input_nodes
+        else:
+            raise ValueError("'input_nodes' must be a node type or (node type, nodes)")
+        if input_type not in x_dict:
+            raise ValueError(f"the input type '{input_type}' has no entry in 'x_dict'")
+        self.prefetch = int(prefetch)
+        self._side = None
+        self.x_dict, self.y = dict(x_dict), y
+        self.sampler = HeteroNeighborSampler(
+            edge_index_dict, {t: x.size(0) for t, x in self.x_dict.items()}, num_neighbors,
+            seed=seed, replace=replace, disjoint=disjoint)
+        dev = self.sampler.colptr.device
+        self.input_type = input_type
+        if nodes is None:
+            nodes = torch.arange(self.x_dict[input_type].size(0), device=dev)
+        elif nodes.dtype == torch.bool:
+            nodes = nodes.nonzero().view(-1)
+        self.input_nodes = nodes.to(dev)
+        self.sampler.check_seeds(input_type, self.input_nodes)  # once: batches are slices of it
+        self.batch_size, self.shuffle, self.drop_last = batch_size, shuffle, drop_last
+        self._gen = torch.Generator().manual_seed(seed)
+
+    def _stream_device(self):
+        return self.sampler.colptr.device
+
+    def __len__(self) -> int:
+        n = self.input_nodes.numel()
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _plan(self):
+        n = self.input_nodes.numel()
+        dev = self.input_nodes.device
+        order = (torch.randperm(n, generator=self._gen).to(dev) if self.shuffle
+                 else torch.arange(n, device=dev))
+        nodes = self.input_nodes[order]
+        for b in range(len(self)):
+            lo, hi = b * self.batch_size, (b + 1) * self.batch_size
+            yield nodes[lo:hi], order[lo:hi]
+
+    def collate(self, seeds: Tensor, input_id: Optional[Tensor] = None) -> HeteroBatch:
+        out = self.sampler._sample(self.input_type, seeds)
+        # filter_hetero_data: x[t][n_id[t]] per node type, with the HIP gather kernel
+        x_dict = {t: _native.gather_rows(x, out.node[t]) for t, x in self.x_dict.items()}
+        ei = {et: torch.stack([out.row[et], out.col[et]]) for et in out.row}
+        y = None if self.y is None else self.y[out.node[self.input_type].long()]
+        return HeteroBatch(x_dict=x_dict, edge_index_dict=ei, n_id=out.node, e_id=out.edge,
+                           input_type=self.input_type,
+                           input_id=seeds if input_id is None else input_id,
+                           batch_size=seeds.numel(), num_sampled_nodes=out.num_sampled_nodes,
+                           num_sampled_edges=out.num_sampled_edges, y=y, batch=out.batch)

@@ -81,7 +81,7 @@ disjoint sampler bit for bit when every edge is eligible (tests/test_gpu_sampler
 """
 import math
 from dataclasses import dataclass
-from typing import Any, List, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -804,3 +804,459 @@ class NeighborSampler:
         out.row, out.col, out.edge = (key % n).to(dt), (key // n).to(dt), eid[perm][head]
         out.num_sampled_nodes = out.num_sampled_edges = None
         return out
+
+
+# ==== heterogeneous sampling ===========================================================================
+@dataclass
+class HeteroSamplerOutput:
+    """The reference's ``HeteroSamplerOutput`` (sampler/base.py:504-557): per node type ``node`` /
+    ``batch`` / ``num_sampled_nodes``, per edge type ``row`` / ``col`` / ``edge`` /
+    ``num_sampled_edges``."""
+    node: Dict[str, Tensor]
+    row: Dict[Tuple[str, str, str], Tensor]
+    col: Dict[Tuple[str, str, str], Tensor]
+    edge: Optional[Dict[Tuple[str, str, str], Tensor]]
+    batch: Optional[Dict[str, Tensor]] = None
+    num_sampled_nodes: Optional[Dict[str, List[int]]] = None
+    num_sampled_edges: Optional[Dict[Tuple[str, str, str], List[int]]] = None
+    orig_row: Optional[Dict[Tuple[str, str, str], Tensor]] = None
+    orig_col: Optional[Dict[Tuple[str, str, str], Tensor]] = None
+    metadata: Optional[Any] = None
+
+
+def _edge_type(key) -> Tuple[str, str, str]:
+    """An edge type as a ``(src, rel, dst)`` tuple: the reference's ``EdgeTypeStr`` rules
+    (typing.py:359-390): ``'src__rel__dst'`` strings are split, ``(src, dst)`` gets ``'to'``."""
+    if isinstance(key, str):
+        key = tuple(key.split('__'))
+    key = tuple(key)
+    if len(key) == 2:
+        key = (key[0], 'to', key[1])
+    if len(key) != 3 or not all(isinstance(k, str) for k in key):
+        raise ValueError(f"'{key}' is not an edge type (expected '(src, rel, dst)')")
+    return key
+
+
+def hetero_num_neighbors(num_neighbors, edge_types: List[Tuple[str, str, str]]
+                         ) -> Dict[Tuple[str, str, str], List[int]]:
+    """The fan-outs per edge type by the reference's ``NumNeighbors`` rules (sampler/base.py:
+    699-790) and wording: one list for every edge type, or a dict keyed by edge type (plus an
+    optional ``default`` list for the types it leaves out, given as ``(values, default)`` or as the
+    reference's ``NumNeighbors`` object); every list has the same number of hops."""
+    default = None
+    if hasattr(num_neighbors, 'values') and not isinstance(num_neighbors, dict):
+        num_neighbors, default = num_neighbors.values, getattr(num_neighbors, 'default', None)
+    elif isinstance(num_neighbors, tuple) and len(num_neighbors) == 2 \
+            and isinstance(num_neighbors[0], dict):
+        num_neighbors, default = num_neighbors
+    if isinstance(num_neighbors, (tuple, list)):
+        if default is not None:
+            raise ValueError(f"'default' must be set to 'None' in case a single list is given as "
+                             f"the number of neighbors (got '{type(default)})'")
+        out = {et: list(num_neighbors) for et in edge_types}
+    elif isinstance(num_neighbors, dict):
+        values = {_edge_type(k): list(v) for k, v in num_neighbors.items()}
+        if set(values) - set(edge_types):
+            raise ValueError("Not all edge types specified in 'num_neighbors' exist in the graph")
+        out = {}
+        for et in edge_types:
+            if et in values:
+                out[et] = values[et]
+            elif default is None:
+                raise ValueError(f"Missing number of neighbors for edge type '{et}'")
+            else:
+                out[et] = list(default)
+    else:
+        raise ValueError(f"'num_neighbors' must be a list or a dict keyed by edge type (got "
+                         f"{type(num_neighbors).__name__})")
+    num_hops = {len(v) for v in out.values()}
+    if len(num_hops) > 1:
+        raise ValueError(f"Number of hops must be the same across all edge types (got "
+                         f"{len(num_hops)} different number of hops)")
+    for et, ks in out.items():
+        for k in ks:
+            if int(k) != k or k < -1:
+                raise ValueError(f"fan-outs are integers >= -1 (got {k} for edge type '{et}')")
+    return out
+
+
+class HeteroNeighborSampler:
+    r"""Heterogeneous k-hop neighbour sampler on the GPU: the reference's ``NeighborSampler`` on a
+    ``HeteroData`` (sampler/neighbor_sampler.py:438-548 -> ``pyg-lib``'s
+    ``hetero_neighbor_sample(..., csc=True)``), uniform draws.
+
+    Node types and edge types keep the order of ``num_nodes_dict`` / ``edge_index_dict``.  An edge
+    type ``(src, rel, dst)`` samples in-edges of ``dst`` nodes and discovers ``src`` nodes.  Hop
+    ``h`` goes through the edge types in order and draws ``k = num_neighbors[et][h]`` in-neighbours
+    (``min(deg, k)`` without replacement, ``k`` with replacement where ``deg > 0``, all for ``-1``)
+    for every ``dst`` node ADDED in hop ``h - 1`` (the seeds, of the input type, count as hop -1).
+    A newly seen ``src`` node is appended to its type's list in order of first appearance in that
+    iteration; a node found in hop ``h`` is never a destination in hop ``h``.  The edges of a type
+    are ordered hop by hop, then by destination, then by draw; ``row`` / ``col`` are local indices
+    into ``node[src]`` / ``node[dst]`` and ``edge`` the positions in that type's own
+    ``edge_index``.  ``num_sampled_nodes[t]`` has ``hops + 1`` entries for every node type,
+    ``num_sampled_edges[et]`` ``hops`` for every edge type.  ``disjoint``: nodes are (tree, node)
+    pairs and ``batch[t]`` the seed index of every node.
+
+    Device layout: ONE stacked CSC over every edge type, built at construction with one stable
+    radix sort keyed by ``col_base[et] + dst`` (node ``i`` of type ``t`` is the global id
+    ``node_base[t] + i``; ``row`` holds global ids, ``perm`` positions in each type's
+    ``edge_index``).  A hop is one set of launches whatever the number of edge types
+    (``pygamd_hetero_sample_counts``, ``pygamd_cumsum``, ``pygamd_hetero_sample_neighbors``, the
+    relabelling over the global id map (disjoint: the pair-key sort) and ``pygamd_hetero_split``)
+    and ONE host read: the hop's edge boundaries per edge type and new nodes per node type.  The
+    draws are sized by a static bound (``k`` per item); a hop with a ``-1`` fan-out is sized by
+    its exact total instead, read after the counts (a second host read), so its buffers follow
+    the edges it really draws and not destinations x the largest in-degree.  Seeds are checked
+    against their type's node count (host seeds on the host, device seeds with one read).  With one
+    node type and one edge type the batch is :class:`NeighborSampler`'s for the same ``seed`` bit
+    for bit.
+
+    Out of scope, refused: edge weights and time (``edge_weight``, ``node_time`` / ``edge_time``,
+    seed times), ``subgraph_type`` ``'bidirectional'`` / ``'induced'``, link-level sampling and the
+    static-shape paths."""
+
+    def __init__(self, edge_index_dict, num_nodes_dict, num_neighbors, seed: int = 0,
+                 replace: bool = False, disjoint: bool = False,
+                 subgraph_type: str = 'directional', output_cls=HeteroSamplerOutput,
+                 edge_weight=None, node_time=None, edge_time=None):
+        subgraph_type = getattr(subgraph_type, 'value', subgraph_type)
+        if subgraph_type in ('bidirectional', 'induced'):
+            raise ValueError(f"heterogeneous sampling supports subgraph_type='directional' only "
+                             f"(got '{subgraph_type}')")
+        if subgraph_type != 'directional':
+            raise ValueError(f"unknown subgraph_type '{subgraph_type}'")
+        if edge_weight is not None:
+            raise ValueError("weighted heterogeneous sampling ('edge_weight') is not supported")
+        if node_time is not None or edge_time is not None:
+            raise ValueError("temporal heterogeneous sampling ('node_time' / 'edge_time') is not "
+                             "supported")
+        self.node_types = list(num_nodes_dict.keys())
+        self.num_nodes = {t: int(n) for t, n in num_nodes_dict.items()}
+        if len(self.node_types) == 0:
+            raise ValueError("heterogeneous sampling needs at least one node type")
+        if len(self.node_types) > 64 or len(edge_index_dict) > 64:
+            raise ValueError("heterogeneous sampling supports up to 64 node types and 64 edge "
+                             "types")
+        if any(n < 0 for n in self.num_nodes.values()):
+            raise ValueError("the number of nodes of a type must be non-negative")
+        self.edge_types = [_edge_type(k) for k in edge_index_dict.keys()]
+        if len(set(self.edge_types)) != len(self.edge_types):
+            raise ValueError("an edge type is given twice")
+        eis = list(edge_index_dict.values())
+        for et, ei in zip(self.edge_types, eis):
+            if et[0] not in self.num_nodes or et[2] not in self.num_nodes:
+                raise ValueError(f"edge type '{et}' names a node type missing from "
+                                 f"'num_nodes_dict'")
+            if not isinstance(ei, Tensor) or ei.dim() != 2 or ei.size(0) != 2:
+                raise ValueError(f"the edge_index of '{et}' must be a [2, E] tensor")
+        dtypes = {ei.dtype for ei in eis}
+        if len(dtypes) > 1:
+            raise ValueError(f"every edge_index must have one index dtype (got "
+                             f"{sorted(str(d) for d in dtypes)})")
+        dt = dtypes.pop() if dtypes else torch.int64
+        if dt not in (torch.int32, torch.int64):
+            raise ValueError(f"edge_index must be int32 or int64 (got {dt})")
+        self.num_neighbors = hetero_num_neighbors(num_neighbors, self.edge_types)
+        self.num_hops = len(next(iter(self.num_neighbors.values()))) if self.edge_types else 0
+        if any(k > _native._lib.load().pygamd_sample_max_fanout()
+               for ks in self.num_neighbors.values() for k in ks):
+            raise ValueError('bounded fan-outs above 64 are not supported (use -1 for all)')
+        # the global id spaces: node_base[t] (nodes), col_base[et] (stacked columns)
+        nb = [0]
+        for t in self.node_types:
+            nb.append(nb[-1] + self.num_nodes[t])
+        self.node_base = nb
+        self._type_index = {t: i for i, t in enumerate(self.node_types)}
+        cb = [0]
+        for et in self.edge_types:
+            cb.append(cb[-1] + self.num_nodes[et[2]])
+        self.col_base = cb
+        self.num_edges = [int(ei.size(1)) for ei in eis]
+        if dt == torch.int32 and max(nb[-1], cb[-1], sum(self.num_edges)) >= 2 ** 31:
+            raise ValueError("int32 edge_index: the total number of nodes, of stacked columns or "
+                             "of edges does not fit in int32 (use int64)")
+        devs = {ei.device for ei in eis}
+        if len(devs) > 1:
+            raise ValueError("every edge_index must be on one device")
+        dev = devs.pop() if devs else torch.device('cuda', torch.cuda.current_device())
+        if dev.type != 'cuda':
+            raise ValueError("the sampler needs every 'edge_index' on the HIP device (there is no "
+                             "CPU fallback)")
+        self.seed, self.replace, self.disjoint = seed, bool(replace), bool(disjoint)
+        self.subgraph_type = subgraph_type
+        self.output_cls = output_cls
+        self._calls = 0
+        self._build_csc(eis, dt, dev)
+        self._unset = torch.iinfo(dt).min
+        self._local = torch.full((max(nb[-1], 1), ), self._unset, dtype=dt, device=dev)
+        self._unset_t = torch.full((1, ), self._unset, dtype=dt, device=dev)
+
+    def _build_csc(self, eis, dt, dev) -> None:
+        """The stacked CSC: one stable radix sort of every edge keyed by ``col_base[et] + dst``
+        (slots of a column stay in ``edge_index`` order).  Two host reads at construction: one
+        validates the indices (before any of them is used as an address), one gives every edge
+        type's largest in-degree (the static bound of ``-1`` hops)."""
+        ET = len(self.edge_types)
+        C = self.col_base[-1]
+        eis = [ei.to(dev) for ei in eis]
+        live = [e for e in range(ET) if eis[e].size(1) > 0]
+        if live:
+            host = torch.stack([torch.stack([eis[e].min().long(), eis[e][0].max().long(),
+                                             eis[e][1].max().long()]) for e in live]).tolist()
+            for e, (lo, hi_src, hi_dst) in zip(live, host):
+                et = self.edge_types[e]
+                if lo < 0 or hi_src >= self.num_nodes[et[0]] or hi_dst >= self.num_nodes[et[2]]:
+                    raise ValueError(f"the edge_index of '{et}' holds node indices outside "
+                                     f"[0, num_nodes) of its source / destination type")
+        if live:
+            keys = torch.cat([eis[e][1].long() + self.col_base[e] for e in live]).to(dt)
+            srcs = torch.cat([eis[e][0].long() + self.node_base[self._type_index[
+                self.edge_types[e][0]]] for e in live])
+            pos = torch.cat([torch.arange(eis[e].size(1), device=dev) for e in live])
+            skeys, p = _native.index_sort(keys, max_value=max(C - 1, 0))
+            self.colptr = _native.index2ptr(skeys, C)
+            self.row = srcs[p].to(dt).contiguous()
+            self.perm = pos[p].to(dt).contiguous()
+        else:
+            self.colptr = torch.zeros(C + 1, dtype=dt, device=dev)
+            self.row = torch.empty(0, dtype=dt, device=dev)
+            self.perm = torch.empty(0, dtype=dt, device=dev)
+        deg = self.colptr[1:] - self.colptr[:-1]
+        maxdeg = [deg[self.col_base[e]:self.col_base[e + 1]].max().long()
+                  if self.num_edges[e] > 0 else torch.zeros((), dtype=torch.int64, device=dev)
+                  for e in range(ET)]
+        self.max_in_degree = [int(v) for v in torch.stack(maxdeg).tolist()] if ET else []
+
+    # -- entry points --------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample_from_nodes(self, index, seed: Optional[int] = None, **kwargs):
+        """``index``: ``(input_type, seeds)`` or a ``NodeSamplerInput``-like object (``.node``,
+        ``.input_id``, ``.input_type``; a seed ``.time`` is refused).  ``metadata = (input_id,
+        None)``."""
+        input_id = None
+        if isinstance(index, (tuple, list)):
+            if len(index) != 2:
+                raise ValueError("'index' must be (input_type, seeds)")
+            input_type, seeds = index
+        else:
+            seeds, input_id = index.node, getattr(index, 'input_id', None)
+            input_type = getattr(index, 'input_type', None)
+            if getattr(index, 'time', None) is not None:
+                raise ValueError("temporal heterogeneous sampling (seed times) is not supported")
+        if kwargs.get('time') is not None:
+            raise ValueError("temporal heterogeneous sampling (seed times) is not supported")
+        if input_type not in self._type_index:
+            raise ValueError(f"the input type '{input_type}' is not a node type of the graph "
+                             f"({self.node_types})")
+        self.check_seeds(input_type, seeds)
+        out = self._sample(input_type, seeds, seed)
+        out.metadata = (input_id, None)
+        return out
+
+    def check_seeds(self, input_type: str, seeds) -> None:
+        """Seeds must be a 1-D integer tensor of ids in ``[0, num_nodes[input_type])``: an id past
+        its type would name a node of the next type in the stacked id space.  Host seeds are
+        checked on the host; device seeds cost one host read (``pygamd_index_minmax``)."""
+        if not isinstance(seeds, Tensor) or seeds.dim() != 1:
+            raise ValueError("the seed nodes must be a 1-D tensor")
+        if seeds.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"the seed nodes must be int32 or int64 (got {seeds.dtype})")
+        if seeds.numel() == 0:
+            return
+        if seeds.is_cuda:
+            lo, hi = _native.index_minmax(seeds)
+        else:
+            lo, hi = int(seeds.min()), int(seeds.max())
+        n = self.num_nodes[input_type]
+        if lo < 0 or hi >= n:
+            raise ValueError(f"seed node ids must lie in [0, {n}) for node type '{input_type}' "
+                             f"(got {lo} .. {hi})")
+
+    def _sample(self, input_type: str, seeds: Tensor, seed: Optional[int] = None):
+        """The batch of already checked seeds."""
+        seeds = seeds.to(device=self.colptr.device, dtype=self.colptr.dtype).contiguous()
+        rng = self.seed + self._calls if seed is None else seed
+        self._calls += 1
+        return self._hops(input_type, seeds, rng)
+
+    def sample_from_edges(self, *args, **kwargs):
+        raise NotImplementedError("heterogeneous link-level sampling is not supported")
+
+    def sample_padded(self, *args, **kwargs):
+        raise NotImplementedError("the static-shape paths (sample_padded, collate_padded, "
+                                  "collate_slots, hipGraph capture) do not cover heterogeneous "
+                                  "sampling")
+
+    # -- the hop loop --------------------------------------------------------------------------------
+    def _capacity(self, e: int, k: int, n_items: int, distinct: bool) -> int:
+        """Static bound on the edges edge type ``e`` can draw for ``n_items`` destinations
+        (``distinct``: no destination repeats, so ``-1`` takes at most every edge once).  For
+        ``-1`` it only decides whether the hop draws anything: such a hop is sized by its exact
+        total (see :meth:`_hops`)."""
+        d = self.max_in_degree[e]
+        if k < 0:
+            cap = n_items * d
+            return min(cap, self.num_edges[e]) if distinct else cap
+        if self.replace:
+            return n_items * k if d > 0 else 0
+        return n_items * min(k, d)
+
+    def _hops(self, input_type: str, seeds: Tensor, rng: int):
+        dev, dt = self.colptr.device, self.colptr.dtype
+        T, ET = len(self.node_types), len(self.edge_types)
+        tin = self._type_index[input_type]
+        B = seeds.numel()
+        S = self.node_base[-1]
+        g_seeds = seeds + self.node_base[tin]
+        count = [0] * T               # nodes of every type in the batch so far
+        count[tin] = B
+        block_off, block_n = [0] * T, [0] * T  # the frontier's type-major blocks
+        block_n[tin] = B
+        prev = [0] * T                # typed local id of every frontier block's first node
+        nodes = [[] for _ in range(T)]
+        nodes[tin].append(seeds)
+        trees = [[] for _ in range(T)]
+        rows, cols, edges = ([[] for _ in range(ET)] for _ in range(3))
+        n_nodes = [[B if t == tin else 0] for t in range(T)]
+        n_edges = [[] for _ in range(ET)]
+        frontier = g_seeds
+        if self.disjoint:
+            if B * max(S, 1) >= 2 ** 62:
+                raise ValueError('disjoint sampling: batch size x num_nodes overflows the pair key')
+            trees[tin].append(torch.arange(B, device=dev))
+            keys_all = torch.arange(B, device=dev) * S + g_seeds.long()
+            pos2typed = torch.arange(B, dtype=dt, device=dev)
+            ftree = torch.arange(B, device=dev)
+        else:
+            local = self._local
+            local[g_seeds] = torch.arange(B, dtype=dt, device=dev)
+            touched = [g_seeds]
+        for hop in range(self.num_hops):
+            item_begin, table, cap, unbounded = [0], [], 0, False
+            for e, et in enumerate(self.edge_types):
+                d = self._type_index[et[2]]
+                k = int(self.num_neighbors[et][hop])
+                table.append((block_off[d], self.col_base[e] - self.node_base[d], prev[d], k))
+                item_begin.append(item_begin[-1] + block_n[d])
+                c = self._capacity(e, k, block_n[d], hop > 0 and not self.disjoint)
+                cap += c
+                unbounded |= k < 0 and c > 0
+            if cap > 0:
+                cnt = _native.hetero_sample_counts(self.colptr, frontier, item_begin, table,
+                                                   replace=self.replace)
+                offsets = torch.zeros(item_begin[-1] + 1, dtype=dt, device=dev)
+                if unbounded and dt == torch.int32 and cap >= 2 ** 31:
+                    # the int32 scan could wrap: take the exact total from an int64 scan first
+                    if int(_native.cumsum(cnt.to(torch.int64))[-1]) >= 2 ** 31:
+                        raise ValueError('int32 graph: a hop draws more than 2^31 - 1 edges (use '
+                                         'int64)')
+                _native.cumsum(cnt, out=offsets[1:])
+                if unbounded:
+                    # a -1 fan-out has no useful static bound (destinations x largest in-degree
+                    # is orders of magnitude above a hop with one hub): size the hop by its
+                    # exact total, a second host read, as NeighborSampler's -1 hops do
+                    cap = int(offsets[-1])
+                elif dt == torch.int32 and cap >= 2 ** 31:
+                    raise ValueError('int32 graph: a hop can draw more than 2^31 - 1 edges (use '
+                                     'int64)')
+            if cap == 0:  # nothing to draw (no destinations, k = 0 or no in-edges)
+                for t in range(T):
+                    n_nodes[t].append(0)
+                for e in range(ET):
+                    n_edges[e].append(0)
+                prev, block_n = list(count), [0] * T
+                continue
+            hop_seed = (rng * 1_000_003 + hop) & 0x7FFFFFFFFFFFFFFF
+            total = offsets[-1:].to(torch.int64)
+            src, col, edge, fpos = _native.hetero_sample_neighbors(
+                self.colptr, self.row, self.perm, frontier, offsets, cap, item_begin, table,
+                hop_seed, replace=self.replace, salt_position=self.disjoint,
+                want_fpos=self.disjoint)
+            if self.disjoint:
+                row, sg, sl, tree_sorted, new_keys, typed, stats = self._relabel_disjoint(
+                    keys_all, ftree, fpos, src, total, pos2typed, cap, count, offsets,
+                    item_begin, B, S)
+            else:
+                new, n_new = _native.relabel_claim_assign(src, total, local)
+                sg, sl, _, _, stats = _native.hetero_split(new, n_new, self.node_base, count,
+                                                           offsets, item_begin, local_map=local)
+                row = _native.relabel_lookup(src, total, local)
+            host = stats.tolist()  # the hop's ONE host read: new nodes per type, edge bounds
+            new_t, bounds = host[:T], host[T:]
+            for e in range(ET):
+                a, b = bounds[e], bounds[e + 1]
+                rows[e].append(row[a:b])
+                cols[e].append(col[a:b])
+                edges[e].append(edge[a:b])
+                n_edges[e].append(b - a)
+            off = 0
+            for t in range(T):
+                block_off[t], block_n[t] = off, new_t[t]
+                nodes[t].append(sl[off:off + new_t[t]])
+                if self.disjoint:
+                    trees[t].append(tree_sorted[off:off + new_t[t]])
+                n_nodes[t].append(new_t[t])
+                off += new_t[t]
+            if self.disjoint:
+                keys_all = torch.cat([keys_all, new_keys[:off]])
+                pos2typed = torch.cat([pos2typed, typed[:off]])
+                ftree = tree_sorted
+            else:
+                touched.append(sg[:off])
+            prev = list(count)
+            count = [c + n for c, n in zip(count, new_t)]
+            frontier = sg
+        if not self.disjoint:
+            local[torch.cat(touched)] = self._unset_t  # leave the map clean for the next batch
+
+        def cat(xs):
+            return torch.cat(xs) if len(xs) > 1 else (xs[0] if xs else
+                                                     torch.empty(0, dtype=dt, device=dev))
+        nt, ets = self.node_types, self.edge_types
+        out = self.output_cls(
+            node={t: cat(nodes[i]) for i, t in enumerate(nt)},
+            row={et: cat(rows[e]) for e, et in enumerate(ets)},
+            col={et: cat(cols[e]) for e, et in enumerate(ets)},
+            edge={et: cat(edges[e]) for e, et in enumerate(ets)},
+            batch=({t: cat(trees[i]).to(dt) for i, t in enumerate(nt)} if self.disjoint
+                   else None),
+            num_sampled_nodes={t: n_nodes[i] for i, t in enumerate(nt)},
+            num_sampled_edges={et: n_edges[e] for e, et in enumerate(ets)})
+        return out
+
+    def _relabel_disjoint(self, keys_all, ftree, fpos, src, total, pos2typed, cap, count,
+                          offsets, item_begin, B, S):
+        """The pair-key relabelling of :meth:`NeighborSampler._hops_disjoint` (pair ``tree * S +
+        global id``, one stable sort; first appearance = smallest position of a run) at the hop's
+        static capacity, without a host read, then the typed split of the new pairs."""
+        dev, dt = src.device, src.dtype
+        P = keys_all.numel()
+        n_all = P + cap
+        ar = torch.arange(cap, device=dev)
+        keys = ftree[fpos.long()] * S + src.long()
+        keys = torch.where(ar < total, keys, B * S)       # the unused capacity sorts last
+        allk = torch.cat([keys_all, keys])
+        sorted_k, perm = _native.index_sort(allk, max_value=B * S)
+        head = torch.ones_like(sorted_k, dtype=torch.bool)
+        head[1:] = sorted_k[1:] != sorted_k[:-1]
+        gid = _native.cumsum(head.to(torch.int64)) - 1
+        headpos = torch.empty(n_all + 1, dtype=torch.int64, device=dev)
+        headpos.scatter_(0, torch.where(head, gid, n_all), perm)   # first position of every pair
+        first_of = torch.empty(n_all, dtype=torch.int64, device=dev)
+        first_of.scatter_(0, perm, headpos[gid])
+        idx = torch.arange(n_all, device=dev)
+        mark = (first_of == idx) & (idx >= P) & (idx < P + total)  # pairs new in this hop
+        rank = _native.cumsum(mark.to(torch.int64)) - 1
+        n_new = rank[-1:] + 1
+        new_keys = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+        new_keys.scatter_(0, torch.where(mark[P:], rank[P:], cap), allk[P:])
+        new_keys = new_keys[:cap]
+        new_g = (new_keys % S).to(dt) if S > 0 else new_keys.to(dt)
+        sg, sl, typed, tree_sorted, stats = _native.hetero_split(
+            new_g, n_new, self.node_base, count, offsets, item_begin, want_typed=True,
+            aux=new_keys // max(S, 1))
+        f = first_of[P:]
+        row = torch.where(f < P, pos2typed[f.clamp(max=max(P - 1, 0))],
+                          typed[rank[f].clamp(min=0)])
+        return row, sg, sl, tree_sorted, new_keys, typed, stats
