@@ -782,6 +782,47 @@ PYGAMD_API int pygamd_hetero_split(int phase, const void* new_nodes, int idx_dty
                                    void* sorted_global, void* sorted_local, int64_t* aux_out,
                                    int64_t* stats, void* stream);
 
+/* ---- temporal heterogeneous hops: the typed window and the typed draw on a window -------------
+ * The reference's NeighborLoader(hetero_data, time_attr=..., temporal_strategy=...) ->
+ * hetero_neighbor_sample(..., node_time, edge_time, seed_time, ..., temporal_strategy)
+ * (sampler/neighbor_sampler.py:438-471).  Same stacked CSC, work list, item_begin and et_table as
+ * above.  Bit et of timed_mask marks edge type et as TIMED: inside each of its columns the slots
+ * ascend in time (ties in edge_index order, the reference's sort_csc); the other edge types keep
+ * edge_index order.  time is int64: level 0 (node level) one entry per GLOBAL node id, read through
+ * row[slot]; level 1 (edge level) one entry per slot.  frontier_time is int64 and aligned with
+ * `frontier`: entry fp holds the seed time of the tree of the destination at position fp.
+ * pygamd_hetero_sample_temporal_window: one wave per work item.  A timed item's window is the
+ *   prefix [s, hi) of its column with time <= frontier_time[fp] (the 64-probe / one-ballot search
+ *   of pygamd_sample_temporal_window); strategy 1 ('last') narrows it to its last k slots for
+ *   k >= 0, strategy 0 ('uniform') keeps lo = s.  An untimed item's window is its whole column,
+ *   whatever the strategy.  cnt is pygamd_hetero_sample_counts' rule on hi - lo.  It takes the
+ *   place of the counts launch of a temporal hop.  lo_out, hi_out, cnt_out: [n] in idx_dtype.
+ * pygamd_hetero_sample_neighbors_temporal: pygamd_hetero_sample_neighbors on [lo[i], hi[i]) in
+ *   place of item i's column: the same key, flags and outputs, so a window that is the whole column
+ *   gives the non-temporal draw, and one node type with one edge type gives
+ *   pygamd_sample_neighbors_temporal's draw, bit for bit.
+ * Rejected before any launch, like the entry points above, plus: level or strategy outside
+ * {0, 1}, a timed_mask bit at or above n_et, NULL time / frontier_time / lo / hi ->
+ * PYGAMD_ERR_INVALID_ARG.                                                                        */
+PYGAMD_API int pygamd_hetero_sample_temporal_window(const void* colptr, const void* row,
+                                                    int idx_dtype, const int64_t* time, int level,
+                                                    const void* frontier,
+                                                    const int64_t* frontier_time,
+                                                    const int64_t* item_begin,
+                                                    const int64_t* et_table, int n_et,
+                                                    uint64_t timed_mask, int replace,
+                                                    int strategy, void* lo_out, void* hi_out,
+                                                    void* cnt_out, void* stream);
+PYGAMD_API int pygamd_hetero_sample_neighbors_temporal(const void* row, const void* perm,
+                                                       int idx_dtype, const void* frontier,
+                                                       const void* lo, const void* hi,
+                                                       const void* offsets,
+                                                       const int64_t* item_begin,
+                                                       const int64_t* et_table, int n_et,
+                                                       uint64_t seed, int flags, void* src_out,
+                                                       void* col_out, void* edge_out,
+                                                       void* fpos_out, void* stream);
+
 /* ---- a18: one-pass multi-reduce (FusedAggregation) ---------------------------------------------
  * nn/aggr/fused.py:191-336 shares the group count, the sum and the sum of squares between
  * sum / mean / var / std / min / max.  Here ONE read of the rows produces all requested statistics

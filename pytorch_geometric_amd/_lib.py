@@ -171,6 +171,12 @@ SIGNATURES = {
                                                c_int, _P, _P, _P, _P, _P]),
     'pygamd_hetero_split': (c_int, [c_int, _P, c_int, c_int64, _P, _P, _P, c_int, _P, _P, _P,
                                     c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'pygamd_hetero_sample_temporal_window': (c_int, [_P, _P, c_int, _P, c_int, _P, _P, _P, _P,
+                                                     c_int, c_uint64, c_int, c_int, _P, _P, _P,
+                                                     _P]),
+    'pygamd_hetero_sample_neighbors_temporal': (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P,
+                                                        c_int, c_uint64, c_int, _P, _P, _P, _P,
+                                                        _P]),
     'pygamd_gather_rows': (c_int, [_P, c_int64, c_int64, _P, c_int, c_int64, c_int64, _P,
                                    c_int64, _P, _P]),
     'pygamd_gather_scatter_add': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P, c_int64, _P,

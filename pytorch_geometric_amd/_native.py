@@ -1966,6 +1966,60 @@ def hetero_sample_neighbors(colptr: Tensor, row: Tensor, perm: Tensor, frontier:
     return src, col, edge, fpos
 
 
+def hetero_sample_temporal_window(colptr: Tensor, row: Tensor, time: Tensor, frontier: Tensor,
+                                  frontier_time: Tensor, item_begin, et_table, timed_mask: int,
+                                  edge_level: bool = False, replace: bool = False,
+                                  last: bool = False):
+    """``pygamd_hetero_sample_temporal_window``: ``(lo, hi, cnt)`` per work item of a temporal hop.
+    A timed edge type (its bit of ``timed_mask``) gets the prefix of the item's time-sorted column
+    with time <= ``frontier_time`` (int64, aligned with ``frontier``), narrowed to its last ``k``
+    slots for ``last``; an untimed one its whole column.  ``cnt`` follows
+    :func:`hetero_sample_counts`' rule on the window.  ``time``: int64 over the global node ids,
+    or over the slots with ``edge_level``."""
+    _require_device(colptr, row, time, frontier, frontier_time)
+    if frontier.dtype != colptr.dtype:
+        raise ValueError("'frontier' must have the graph's index dtype")
+    if time.dtype != torch.int64 or frontier_time.dtype != torch.int64:
+        raise ValueError("'time' and 'frontier_time' must be int64")
+    time, frontier_time = time.contiguous(), frontier_time.contiguous()
+    lib = _lib.load()
+    n = int(item_begin[-1])
+    lo = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
+    hi = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
+    cnt = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
+    flat = [int(v) for r in et_table for v in r]
+    check(lib.pygamd_hetero_sample_temporal_window(
+        _p(colptr), _p(row), _idx_dtype(colptr), _p(time), int(edge_level), _p(frontier),
+        _p(frontier_time), _i64_host(item_begin), _i64_host(flat), len(et_table),
+        int(timed_mask), int(replace), int(last), _p(lo), _p(hi), _p(cnt), _stream(colptr)),
+        'hetero_sample_temporal_window')
+    return lo, hi, cnt
+
+
+def hetero_sample_neighbors_temporal(row: Tensor, perm: Tensor, frontier: Tensor, lo: Tensor,
+                                     hi: Tensor, offsets: Tensor, capacity: int, item_begin,
+                                     et_table, seed: int, replace: bool = False,
+                                     salt_position: bool = False, want_fpos: bool = False):
+    """:func:`hetero_sample_neighbors` on the windows ``[lo, hi)`` of
+    :func:`hetero_sample_temporal_window` (``pygamd_hetero_sample_neighbors_temporal``): the same
+    draws and outputs."""
+    _require_device(row, perm, frontier, lo, hi, offsets)
+    lib = _lib.load()
+    dt, dev = row.dtype, row.device
+    src = torch.empty(capacity, dtype=dt, device=dev)
+    col = torch.empty(capacity, dtype=dt, device=dev)
+    edge = torch.empty(capacity, dtype=dt, device=dev)
+    fpos = torch.zeros(capacity, dtype=dt, device=dev) if want_fpos else None
+    flat = [int(v) for r in et_table for v in r]
+    if capacity > 0 and int(item_begin[-1]) > 0:
+        check(lib.pygamd_hetero_sample_neighbors_temporal(
+            _p(row), _p(perm), _idx_dtype(row), _p(frontier), _p(lo), _p(hi), _p(offsets),
+            _i64_host(item_begin), _i64_host(flat), len(et_table), seed & 0xFFFFFFFFFFFFFFFF,
+            int(replace) | (2 if salt_position else 0), _p(src), _p(col), _p(edge), _p(fpos),
+            _stream(row)), 'hetero_sample_neighbors_temporal')
+    return src, col, edge, fpos
+
+
 def hetero_split(new_nodes: Tensor, n_new: Tensor, node_base, count_prev, offsets: Optional[Tensor],
                  item_begin, local_map: Optional[Tensor] = None, want_typed: bool = False,
                  aux: Optional[Tensor] = None):

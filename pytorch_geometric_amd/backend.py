@@ -892,7 +892,10 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     ``sample_from_nodes`` returns the reference's ``HeteroSamplerOutput`` with tuple keys, so
     ``NodeLoader(hetero_data, node_sampler=..., input_nodes='paper')`` yields its own ``HeteroData``
     batches through ``filter_hetero_data`` (loader/node_loader.py:209-257); ``num_neighbors`` is a
-    list or a dict keyed by edge type; ``weight_attr`` / ``time_attr`` are refused.
+    list or a dict keyed by edge type.  ``time_attr`` is collected from the node stores or from the
+    edge stores that hold it (sampler/neighbor_sampler.py:135-158; stores without it are untimed),
+    ``NodeSamplerInput.time`` is forwarded and ``metadata = (input_id, time)``; ``weight_attr`` is
+    refused on a ``HeteroData``.
     ``sample_from_edges(EdgeSamplerInput, neg_sampling)`` is link-level sampling
     (:meth:`pytorch_geometric_amd.sampler.NeighborSampler.sample_from_edges`), so that the
     reference's ``LinkLoader(data, link_sampler=...)`` (loader/link_loader.py) drives it too; its
@@ -903,7 +906,8 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     from .sampler import NeighborSampler
     if hasattr(data, 'metadata') and hasattr(data, 'edge_index_dict'):  # a HeteroData
         return _hetero_neighbor_sampler(data, num_neighbors, seed, replace, disjoint,
-                                        subgraph_type, weight_attr, time_attr)
+                                        subgraph_type, weight_attr, time_attr,
+                                        temporal_strategy)
     if _sampler_cls is None:
 
         class MI355XNeighborSampler(pyg_sampler.BaseSampler):
@@ -973,23 +977,29 @@ _hetero_sampler_cls = None
 
 
 def _hetero_neighbor_sampler(data, num_neighbors, seed, replace, disjoint, subgraph_type,
-                             weight_attr, time_attr):
+                             weight_attr, time_attr, temporal_strategy='uniform'):
     """The ``HeteroData`` branch of :func:`neighbor_sampler`."""
     global _hetero_sampler_cls
     import torch_geometric.sampler as pyg_sampler
     from .sampler import HeteroNeighborSampler
-    if weight_attr is not None or time_attr is not None:
-        raise ValueError("weighted or temporal heterogeneous sampling ('weight_attr' / "
-                         "'time_attr' with a 'HeteroData') is not supported")
+    if weight_attr is not None:
+        raise ValueError("weighted heterogeneous sampling ('weight_attr' with a 'HeteroData') is "
+                         "not supported")
     if _hetero_sampler_cls is None:
 
         class MI355XHeteroNeighborSampler(pyg_sampler.BaseSampler):
             def __init__(self, edge_index_dict, num_nodes_dict, num_neighbors, seed=0,
-                         replace=False, disjoint=False, subgraph_type='directional'):
+                         replace=False, disjoint=False, subgraph_type='directional',
+                         node_time=None, edge_time=None, time_attr=None,
+                         temporal_strategy='uniform'):
                 self.impl = HeteroNeighborSampler(
                     edge_index_dict, num_nodes_dict, num_neighbors, seed=seed,
                     replace=replace, disjoint=disjoint, subgraph_type=subgraph_type,
-                    output_cls=pyg_sampler.HeteroSamplerOutput)
+                    output_cls=pyg_sampler.HeteroSamplerOutput, node_time=node_time,
+                    edge_time=edge_time, temporal_strategy=temporal_strategy)
+                self.time_attr, self.temporal_strategy = time_attr, temporal_strategy
+                self.node_time, self.edge_time = node_time, edge_time
+                self.is_temporal = self.impl.is_temporal
                 # the reference's NeighborSampler attributes (sampler/neighbor_sampler.py:116-150)
                 self.node_types, self.edge_types = self.impl.node_types, self.impl.edge_types
                 self.num_nodes = dict(self.impl.num_nodes)
@@ -1011,12 +1021,24 @@ def _hetero_neighbor_sampler(data, num_neighbors, seed, replace, disjoint, subgr
     node_types, edge_types = data.metadata()
     num_nodes = {t: int(data[t].num_nodes or 0) for t in node_types}
     edge_index_dict = {et: data[et].edge_index for et in edge_types}
+    node_time = edge_time = None
+    if time_attr is not None:  # (the reference's rules and wording, neighbor_sampler.py:135-158)
+        in_nodes = {t: data[t][time_attr] for t in node_types if time_attr in data[t]}
+        in_edges = {et: data[et][time_attr] for et in edge_types if time_attr in data[et]}
+        if in_nodes and in_edges:
+            raise ValueError(f"The time attribute '{time_attr}' holds both node-level and "
+                             f"edge-level information")
+        if not in_nodes and not in_edges:
+            raise ValueError(f"The time attribute '{time_attr}' is neither a node-level or "
+                             f"edge-level attribute of the heterogeneous graph")
+        node_time, edge_time = in_nodes or None, in_edges or None
     for ei in edge_index_dict.values():
         if not (isinstance(ei, Tensor) and ei.is_cuda):
             raise ValueError("the sampler needs every 'edge_index' on the HIP device (there is "
                              "no CPU fallback): move the data with `.to('cuda')` first")
     return _hetero_sampler_cls(edge_index_dict, num_nodes, num_neighbors, seed, replace,
-                               disjoint, subgraph_type)
+                               disjoint, subgraph_type, node_time=node_time, edge_time=edge_time,
+                               time_attr=time_attr, temporal_strategy=temporal_strategy)
 
 
 def _wrap_linear_forward(cls):

@@ -143,6 +143,46 @@ __device__ __forceinline__ int64_t slot_time_of(const IdxT* __restrict__ row,
   return level == 0 ? time[static_cast<int64_t>(row[j])] : time[j];
 }
 
+// The search itself, shared by the plain and the typed window kernels: the first slot of [s, end)
+// whose time is past t (= end when every slot is eligible).  Wave-uniform arguments and result.
+template <typename IdxT>
+__device__ __forceinline__ int64_t temporal_window_end(const IdxT* __restrict__ row,
+                                                       const int64_t* __restrict__ time, int level,
+                                                       int64_t s, int64_t end, int64_t t) {
+  const int lane = lane_id();
+  int64_t a = s, b = end;  // the answer lies in [a, b]
+  while (a < b) {
+    const int64_t len = b - a;
+    const int64_t step = (len + kWave - 1) / kWave;
+    const int64_t q = a + (lane + 1) * step - 1;  // the last slot of chunk `lane`
+    const bool past = q >= b || slot_time_of(row, time, level, q) > t;
+    const uint64_t m = __ballot(past);
+    if (m == 0) {  // every probe is eligible: the last one is b - 1
+      a = b;
+      break;
+    }
+    const int p = __ffsll(static_cast<unsigned long long>(m)) - 1;
+    const int64_t qp = a + (static_cast<int64_t>(p) + 1) * step - 1;
+    a = a + static_cast<int64_t>(p) * step;
+    b = qp < b ? qp : b;
+  }
+  return a;
+}
+
+// lo and cnt of a window that ends at hi: 'last' keeps its last k slots (k >= 0), cnt is
+// pygamd_sample_counts' rule on hi - lo
+__device__ __forceinline__ void temporal_window_count(int64_t s, int64_t hi, int64_t k,
+                                                      bool replace, bool last, int64_t* lo,
+                                                      int64_t* cnt) {
+  *lo = (last && k >= 0 && hi - k > s) ? hi - k : s;
+  const int64_t w = hi - *lo;
+  if (replace && k >= 0) {
+    *cnt = w > 0 ? k : 0;
+  } else {
+    *cnt = (k >= 0 && w > k) ? k : w;
+  }
+}
+
 template <typename IdxT>
 __global__ void __launch_bounds__(kBlock)
     sample_temporal_window_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
@@ -166,32 +206,9 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t v = frontier[f];
   const int64_t s = colptr[v];
   const int64_t end = colptr[v + 1];
-  const int64_t t = frontier_time[f];
-  int64_t a = s, b = end;  // the answer lies in [a, b]
-  while (a < b) {
-    const int64_t len = b - a;
-    const int64_t step = (len + kWave - 1) / kWave;
-    const int64_t q = a + (lane + 1) * step - 1;  // the last slot of chunk `lane`
-    const bool past = q >= b || slot_time_of(row, time, level, q) > t;
-    const uint64_t m = __ballot(past);
-    if (m == 0) {  // every probe is eligible: the last one is b - 1
-      a = b;
-      break;
-    }
-    const int p = __ffsll(static_cast<unsigned long long>(m)) - 1;
-    const int64_t qp = a + (static_cast<int64_t>(p) + 1) * step - 1;
-    a = a + static_cast<int64_t>(p) * step;
-    b = qp < b ? qp : b;
-  }
-  const int64_t hi = a;
-  const int64_t lo = (last && k >= 0 && hi - k > s) ? hi - k : s;
-  const int64_t w = hi - lo;
-  int64_t c;
-  if (replace && k >= 0) {
-    c = w > 0 ? k : 0;
-  } else {
-    c = (k >= 0 && w > k) ? k : w;
-  }
+  const int64_t hi = temporal_window_end(row, time, level, s, end, frontier_time[f]);
+  int64_t lo, c;
+  temporal_window_count(s, hi, k, replace != 0, last != 0, &lo, &c);
   if (lane == 0) {
     lo_out[f] = static_cast<IdxT>(lo);
     hi_out[f] = static_cast<IdxT>(hi);
@@ -676,6 +693,75 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// ---- temporal heterogeneous hops (the reference's NeighborLoader(hetero_data, time_attr=...) ->
+// hetero_neighbor_sample(..., node_time, edge_time, seed_time, ..., temporal_strategy)).  The
+// stacked CSC keeps the slots of every column of a TIMED edge type ascending in time (bit et of
+// `timed`: the source type has node times, or the edge type edge times); `time` is int64 over the
+// global node ids (level 0) or over the slots (level 1).  One wave per work item: the window of a
+// timed item is the prefix of its column with time <= frontier_time[fp] (the seed time of the tree
+// of the destination at frontier position fp), found by temporal_window_end and narrowed by
+// 'last'; an untimed item's window is its whole column.  cnt is hetero_counts_kernel's rule on the
+// window, so this launch takes the place of the counts launch.
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    hetero_temporal_window_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
+                                  const int64_t* __restrict__ time, int level,
+                                  const IdxT* __restrict__ frontier,
+                                  const int64_t* __restrict__ frontier_time, const HeteroHop hop,
+                                  uint64_t timed, int replace, int last,
+                                  IdxT* __restrict__ lo_out, IdxT* __restrict__ hi_out,
+                                  IdxT* __restrict__ cnt_out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+  if (i >= hop.item_begin[hop.n_et]) return;
+  const int et = hetero_edge_type(hop, i);
+  const int64_t fp = hop.frontier_off[et] + i - hop.item_begin[et];
+  const int64_t c = static_cast<int64_t>(frontier[fp]) + hop.col_off[et];
+  const int64_t s = colptr[c];
+  const int64_t end = colptr[c + 1];
+  const bool is_timed = ((timed >> et) & 1ull) != 0;
+  const int64_t hi =
+      is_timed ? temporal_window_end(row, time, level, s, end, frontier_time[fp]) : end;
+  int64_t lo, cnt;
+  temporal_window_count(s, hi, hop.k[et], replace != 0, last != 0 && is_timed, &lo, &cnt);
+  if (lane_id() == 0) {
+    lo_out[i] = static_cast<IdxT>(lo);
+    hi_out[i] = static_cast<IdxT>(hi);
+    cnt_out[i] = static_cast<IdxT>(cnt);
+  }
+}
+
+// hetero_sample_kernel on the windows [lo[i], hi[i]): the same key (stacked column id, item
+// position), flags and outputs, so a window that is the whole column draws what
+// hetero_sample_kernel draws, and one node type with one edge type what
+// sample_neighbors_temporal_kernel draws.
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    hetero_sample_temporal_kernel(const IdxT* __restrict__ row, const IdxT* __restrict__ perm,
+                                  const IdxT* __restrict__ frontier, const IdxT* __restrict__ lo,
+                                  const IdxT* __restrict__ hi, const IdxT* __restrict__ offsets,
+                                  const HeteroHop hop, uint64_t seed, int flags,
+                                  IdxT* __restrict__ src_out, IdxT* __restrict__ col_out,
+                                  IdxT* __restrict__ edge_out, IdxT* __restrict__ fpos_out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+  if (i >= hop.item_begin[hop.n_et]) return;
+  const int64_t o = offsets[i];
+  const int64_t cnt = static_cast<int64_t>(offsets[i + 1]) - o;
+  if (cnt <= 0) return;
+  const int et = hetero_edge_type(hop, i);
+  const int64_t p = i - hop.item_begin[et];
+  const int64_t fp = hop.frontier_off[et] + p;
+  const int64_t c = static_cast<int64_t>(frontier[fp]) + hop.col_off[et];
+  const int64_t s = lo[i];
+  const int64_t deg = static_cast<int64_t>(hi[i]) - s;
+  const uint64_t key = node_key(seed, nullptr, c, i, flags);
+  const bool rep = (flags & 1) != 0 && hop.k[et] >= 0;
+  draw_uniform(row, s, deg, o, cnt, hop.dst_local[et] + p, key, rep, src_out, col_out, edge_out,
+               perm);
+  if (fpos_out) {
+    for (int64_t t = lane_id(); t < cnt; t += kWave) fpos_out[o + t] = static_cast<IdxT>(fp);
+  }
+}
+
 // ---- the typed split of a hop's new nodes (global ids in order of first appearance, the first
 // *n_new of new_nodes[m]): a stable partition by node type.  Phase 0 writes the one-hot matrix
 // flag[t * m + j] = (type(new_nodes[j]) == t), which the caller scans inclusively as ONE vector of
@@ -1013,6 +1099,64 @@ int pygamd_hetero_sample_neighbors(const void* colptr, const void* row, const vo
                        static_cast<const IdxT*>(row), static_cast<const IdxT*>(perm),
                        static_cast<const IdxT*>(frontier), static_cast<const IdxT*>(offsets), hop,
                        seed, flags, static_cast<IdxT*>(src_out), static_cast<IdxT*>(col_out),
+                       static_cast<IdxT*>(edge_out), static_cast<IdxT*>(fpos_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_hetero_sample_temporal_window(const void* colptr, const void* row, int idx_dtype,
+                                         const int64_t* time, int level, const void* frontier,
+                                         const int64_t* frontier_time, const int64_t* item_begin,
+                                         const int64_t* et_table, int n_et, uint64_t timed_mask,
+                                         int replace, int strategy, void* lo_out, void* hi_out,
+                                         void* cnt_out, void* stream) {
+  if ((level != 0 && level != 1) || (strategy != 0 && strategy != 1))
+    return PYGAMD_ERR_INVALID_ARG;
+  HeteroHop hop;
+  const int rc = fill_hetero_hop(item_begin, et_table, n_et, &hop);
+  if (rc != PYGAMD_OK) return rc;
+  if (n_et < kMaxEdgeTypes && (timed_mask >> n_et) != 0) return PYGAMD_ERR_INVALID_ARG;
+  if (!time || !frontier_time) return PYGAMD_ERR_INVALID_ARG;
+  const int64_t n = hop.item_begin[n_et];
+  if (n == 0) return PYGAMD_OK;
+  if (!colptr || !row || !frontier || !lo_out || !hi_out || !cnt_out)
+    return PYGAMD_ERR_INVALID_ARG;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid = static_cast<unsigned>(ceil_div(n, kWavesPerBlock));
+    hipLaunchKernelGGL((hetero_temporal_window_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(colptr),
+                       static_cast<const IdxT*>(row), time, level,
+                       static_cast<const IdxT*>(frontier), frontier_time, hop, timed_mask,
+                       replace ? 1 : 0, strategy, static_cast<IdxT*>(lo_out),
+                       static_cast<IdxT*>(hi_out), static_cast<IdxT*>(cnt_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_hetero_sample_neighbors_temporal(const void* row, const void* perm, int idx_dtype,
+                                            const void* frontier, const void* lo, const void* hi,
+                                            const void* offsets, const int64_t* item_begin,
+                                            const int64_t* et_table, int n_et, uint64_t seed,
+                                            int flags, void* src_out, void* col_out,
+                                            void* edge_out, void* fpos_out, void* stream) {
+  HeteroHop hop;
+  const int rc = fill_hetero_hop(item_begin, et_table, n_et, &hop);
+  if (rc != PYGAMD_OK) return rc;
+  if (!lo || !hi) return PYGAMD_ERR_INVALID_ARG;
+  const int64_t n = hop.item_begin[n_et];
+  if (n == 0) return PYGAMD_OK;
+  if (!row || !perm || !frontier || !offsets || !src_out || !col_out || !edge_out)
+    return PYGAMD_ERR_INVALID_ARG;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid = static_cast<unsigned>(ceil_div(n, kWavesPerBlock));
+    hipLaunchKernelGGL((hetero_sample_temporal_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(row),
+                       static_cast<const IdxT*>(perm), static_cast<const IdxT*>(frontier),
+                       static_cast<const IdxT*>(lo), static_cast<const IdxT*>(hi),
+                       static_cast<const IdxT*>(offsets), hop, seed, flags,
+                       static_cast<IdxT*>(src_out), static_cast<IdxT*>(col_out),
                        static_cast<IdxT*>(edge_out), static_cast<IdxT*>(fpos_out));
     PYGAMD_LAUNCH_CHECK();
     return PYGAMD_OK;

@@ -431,7 +431,8 @@ class HeteroBatch:
     """A heterogeneous mini-batch (:class:`HeteroNeighborLoader`): per node type ``x_dict``,
     ``n_id`` and (disjoint) ``batch``; per edge type ``edge_index_dict`` (local ``[row, col]``
     into ``n_id[src]`` / ``n_id[dst]``) and ``e_id`` (positions in that type's ``edge_index``);
-    ``y`` the labels of the sampled ``input_type`` nodes (seeds first)."""
+    ``y`` the labels of the sampled ``input_type`` nodes (seeds first); ``seed_time`` the int64
+    time of every seed of a temporal batch."""
     x_dict: Dict[str, Tensor]
     edge_index_dict: Dict[tuple, Tensor]
     n_id: Dict[str, Tensor]
@@ -443,13 +444,14 @@ class HeteroBatch:
     num_sampled_edges: Dict[tuple, List[int]]
     y: Optional[Tensor] = None
     batch: Optional[Dict[str, Tensor]] = None
+    seed_time: Optional[Tensor] = None
 
     def record_stream(self, stream) -> None:
         for d in (self.x_dict, self.edge_index_dict, self.n_id, self.e_id, self.batch or {}):
             for t in d.values():
                 if isinstance(t, Tensor) and t.is_cuda:
                     t.record_stream(stream)
-        for t in (self.input_id, self.y):
+        for t in (self.input_id, self.y, self.seed_time):
             if isinstance(t, Tensor) and t.is_cuda:
                 t.record_stream(stream)
 
@@ -471,6 +473,14 @@ class HeteroNeighborLoader(_Prefetching):
             input-type nodes.
         batch_size, shuffle, drop_last, seed, prefetch, replace, disjoint: as for
             :class:`NeighborLoader`.
+        node_time, edge_time, temporal_strategy: temporal sampling, the tensors the reference's
+            ``time_attr`` names: a dict from node type to integer times ``[N_t]`` or from edge type
+            to integer times ``[E_et]``, types may be missing (see
+            :class:`~.sampler.HeteroNeighborSampler`).  Forces ``disjoint``.
+        input_time: the reference's ``input_time``: one integer seed time per entry of the input
+            nodes, shuffled and batched with them (default: ``node_time[input_type]`` of the seeds;
+            edge-level time, or an input type without node times, needs it).  Every batch carries
+            its seeds' times as ``seed_time``.
 
     Yields :class:`HeteroBatch`.
     """
@@ -478,7 +488,12 @@ class HeteroNeighborLoader(_Prefetching):
     def __init__(self, x_dict: Dict[str, Tensor], edge_index_dict, num_neighbors, input_nodes,
                  batch_size: int = 1024, y: Optional[Tensor] = None, shuffle: bool = False,
                  drop_last: bool = False, seed: int = 0, prefetch: int = 0,
-                 replace: bool = False, disjoint: bool = False):
+                 replace: bool = False, disjoint: bool = False, node_time=None, edge_time=None,
+                 input_time: Optional[Tensor] = None, temporal_strategy: str = 'uniform'):
+        if input_time is not None and node_time is None and edge_time is None:
+            # (the reference's wording, loader/neighbor_loader.py:223-226)
+            raise ValueError("Received conflicting 'input_time' and 'time_attr' arguments: "
+                             "'input_time' is set while 'time_attr' is not set.")
         if isinstance(input_nodes, str):
             input_type, nodes = input_nodes, None
         elif isinstance(input_nodes, (tuple, list)) and len(input_nodes) == 2:
@@ -492,7 +507,8 @@ class HeteroNeighborLoader(_Prefetching):
         self.x_dict, self.y = dict(x_dict), y
         self.sampler = HeteroNeighborSampler(
             edge_index_dict, {t: x.size(0) for t, x in self.x_dict.items()}, num_neighbors,
-            seed=seed, replace=replace, disjoint=disjoint)
+            seed=seed, replace=replace, disjoint=disjoint, node_time=node_time,
+            edge_time=edge_time, temporal_strategy=temporal_strategy)
         dev = self.sampler.colptr.device
         self.input_type = input_type
         if nodes is None:
@@ -501,6 +517,14 @@ class HeteroNeighborLoader(_Prefetching):
             nodes = nodes.nonzero().view(-1)
         self.input_nodes = nodes.to(dev)
         self.sampler.check_seeds(input_type, self.input_nodes)  # once: batches are slices of it
+        self.input_time = None
+        if input_time is not None:
+            if not isinstance(input_time, Tensor) or input_time.dim() != 1 \
+                    or input_time.numel() != self.input_nodes.numel():
+                raise ValueError("'input_time' must be a 1-D tensor with one entry per input node")
+            self.input_time = self.sampler.seed_time(input_type, self.input_nodes, input_time)
+        elif self.sampler.is_temporal:
+            self.sampler.seed_time(input_type, self.input_nodes[:0])  # refuses a missing default
         self.batch_size, self.shuffle, self.drop_last = batch_size, shuffle, drop_last
         self._gen = torch.Generator().manual_seed(seed)
 
@@ -522,7 +546,13 @@ class HeteroNeighborLoader(_Prefetching):
             yield nodes[lo:hi], order[lo:hi]
 
     def collate(self, seeds: Tensor, input_id: Optional[Tensor] = None) -> HeteroBatch:
-        out = self.sampler._sample(self.input_type, seeds)
+        smp = self.sampler
+        seed_time = None
+        if smp.is_temporal:  # input_id: positions in `input_nodes` (None: seeds given directly)
+            time = None if self.input_time is None or input_id is None \
+                else self.input_time[input_id]
+            seed_time = smp.seed_time(self.input_type, seeds, time)
+        out = smp._sample(self.input_type, seeds, seed_time=seed_time)
         # filter_hetero_data: x[t][n_id[t]] per node type, with the HIP gather kernel
         x_dict = {t: _native.gather_rows(x, out.node[t]) for t, x in self.x_dict.items()}
         ei = {et: torch.stack([out.row[et], out.col[et]]) for et in out.row}
@@ -531,4 +561,5 @@ class HeteroNeighborLoader(_Prefetching):
                            input_type=self.input_type,
                            input_id=seeds if input_id is None else input_id,
                            batch_size=seeds.numel(), num_sampled_nodes=out.num_sampled_nodes,
-                           num_sampled_edges=out.num_sampled_edges, y=y, batch=out.batch)
+                           num_sampled_edges=out.num_sampled_edges, y=y, batch=out.batch,
+                           seed_time=seed_time)

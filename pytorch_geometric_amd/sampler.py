@@ -883,7 +883,7 @@ def hetero_num_neighbors(num_neighbors, edge_types: List[Tuple[str, str, str]]
 class HeteroNeighborSampler:
     r"""Heterogeneous k-hop neighbour sampler on the GPU: the reference's ``NeighborSampler`` on a
     ``HeteroData`` (sampler/neighbor_sampler.py:438-548 -> ``pyg-lib``'s
-    ``hetero_neighbor_sample(..., csc=True)``), uniform draws.
+    ``hetero_neighbor_sample(..., csc=True)``), uniform draws, optionally temporal.
 
     Node types and edge types keep the order of ``num_nodes_dict`` / ``edge_index_dict``.  An edge
     type ``(src, rel, dst)`` samples in-edges of ``dst`` nodes and discovers ``src`` nodes.  Hop
@@ -912,14 +912,54 @@ class HeteroNeighborSampler:
     node type and one edge type the batch is :class:`NeighborSampler`'s for the same ``seed`` bit
     for bit.
 
-    Out of scope, refused: edge weights and time (``edge_weight``, ``node_time`` / ``edge_time``,
-    seed times), ``subgraph_type`` ``'bidirectional'`` / ``'induced'``, link-level sampling and the
-    static-shape paths."""
+    Temporal sampling (the reference's ``time_attr`` on a ``HeteroData``, sampler/utils.py:114-137,
+    neighbor_sampler.py:438-471):
+
+    1. ``node_time`` is a dict from node type to an integer tensor ``[N_t]``, ``edge_time`` a dict
+       from edge type (keys normalised like those of ``num_neighbors``) to an integer tensor
+       ``[E_et]`` in that type's ``edge_index`` order.  Only one of the two may be given; types may
+       be missing.  Unknown keys, wrong lengths and floating, bool or complex tensors are refused
+       before any device work.
+    2. An edge type ``(src, rel, dst)`` is *timed* iff ``src`` has an entry in ``node_time`` or the
+       edge type one in ``edge_time``.  A timed edge type keeps the slots of every column ascending
+       in time, ties in ``edge_index`` order (the reference's ``sort_csc``); an untimed one keeps
+       ``edge_index`` order and all of its in-edges are eligible, whatever the strategy.
+    3. A temporal sampler is always ``disjoint``.
+    4. An in-edge of a timed type is eligible iff its time (the source node's, or the edge's) is
+       ``<=`` the seed time of the TREE its destination belongs to: the bound is the root's time,
+       not the destination's.
+    5. Per work item (edge type, destination), with that edge type's ``k`` of the hop:
+       ``'uniform'`` draws from the eligible prefix of the column, ``'last'`` from its last ``k``
+       slots (``k >= 0``).  The count is ``min(window, k)`` (``k`` wherever the window is not empty
+       with ``replace``, for bounded ``k`` only), and ``-1`` takes the whole window.
+    6. Seed times are one int64 per seed: ``sample_from_nodes((type, seeds), time=...)``,
+       ``NodeSamplerInput.time`` or the loader's ``input_time``; the default is
+       ``node_time[input_type][seeds]``.  Without a default (edge-level time, or an input type
+       without an entry in ``node_time``) they must be given.  A non-temporal sampler refuses
+       seed times.
+    7. Everything else is as above: node and edge ordering, ``num_sampled_*``, ``batch``, both
+       index dtypes, the limits, one host read per hop (two for a ``-1`` hop).
+
+    A temporal CSC is built as ``lexsort([time key, stacked column])`` with two stable radix sorts
+    (the time key biased by the smallest time, 0 for untimed edge types), and keeps ONE int64
+    ``time`` vector: over the global node ids (node level) or over the slots (edge level).  A
+    temporal hop replaces the counts launch by ``pygamd_hetero_sample_temporal_window`` (one wave
+    per item: the 64-probe search of the homogeneous sampler, bounded by ``seed_time[tree]``
+    gathered once per hop) and draws with ``pygamd_hetero_sample_neighbors_temporal``.  A sampler
+    without times takes none of this.  With one node type and one edge type the temporal batch is
+    :class:`NeighborSampler`'s ``node_time`` / ``edge_time`` batch bit for bit.
+
+    Out of scope, refused: edge weights (``edge_weight``, alone or with time), floating-point
+    times, ``subgraph_type`` ``'bidirectional'`` / ``'induced'``, link-level sampling, the
+    static-shape and hipGraph paths, ``sample_direction='backward'`` and ``(FeatureStore,
+    GraphStore)`` inputs."""
+
 
     def __init__(self, edge_index_dict, num_nodes_dict, num_neighbors, seed: int = 0,
                  replace: bool = False, disjoint: bool = False,
                  subgraph_type: str = 'directional', output_cls=HeteroSamplerOutput,
-                 edge_weight=None, node_time=None, edge_time=None):
+                 edge_weight=None, node_time=None, edge_time=None,
+                 temporal_strategy: str = 'uniform'):
         subgraph_type = getattr(subgraph_type, 'value', subgraph_type)
         if subgraph_type in ('bidirectional', 'induced'):
             raise ValueError(f"heterogeneous sampling supports subgraph_type='directional' only "
@@ -928,9 +968,19 @@ class HeteroNeighborSampler:
             raise ValueError(f"unknown subgraph_type '{subgraph_type}'")
         if edge_weight is not None:
             raise ValueError("weighted heterogeneous sampling ('edge_weight') is not supported")
-        if node_time is not None or edge_time is not None:
-            raise ValueError("temporal heterogeneous sampling ('node_time' / 'edge_time') is not "
-                             "supported")
+        if temporal_strategy not in ('uniform', 'last'):
+            raise ValueError(f"unknown temporal_strategy '{temporal_strategy}' (expected "
+                             f"'uniform' or 'last')")
+        for name, t in (('node_time', node_time), ('edge_time', edge_time)):
+            if t is not None and not isinstance(t, dict):
+                raise ValueError(f"temporal heterogeneous sampling takes '{name}' as a dict keyed "
+                                 f"by {name[:4]} type (got {type(t).__name__})")
+        if node_time is not None and edge_time is not None:
+            raise ValueError("temporal sampling takes either 'node_time' or 'edge_time', not "
+                             "both")
+        self.temporal_strategy = temporal_strategy
+        self.is_temporal = node_time is not None or edge_time is not None
+        self.edge_level = edge_time is not None
         self.node_types = list(num_nodes_dict.keys())
         self.num_nodes = {t: int(n) for t, n in num_nodes_dict.items()}
         if len(self.node_types) == 0:
@@ -973,6 +1023,7 @@ class HeteroNeighborSampler:
             cb.append(cb[-1] + self.num_nodes[et[2]])
         self.col_base = cb
         self.num_edges = [int(ei.size(1)) for ei in eis]
+        node_time, edge_time = self._check_times(node_time, edge_time)
         if dt == torch.int32 and max(nb[-1], cb[-1], sum(self.num_edges)) >= 2 ** 31:
             raise ValueError("int32 edge_index: the total number of nodes, of stacked columns or "
                              "of edges does not fit in int32 (use int64)")
@@ -983,20 +1034,92 @@ class HeteroNeighborSampler:
         if dev.type != 'cuda':
             raise ValueError("the sampler needs every 'edge_index' on the HIP device (there is no "
                              "CPU fallback)")
-        self.seed, self.replace, self.disjoint = seed, bool(replace), bool(disjoint)
+        # (the reference: disjoint = _disjoint or is_temporal)
+        self.seed, self.replace = seed, bool(replace)
+        self.disjoint = bool(disjoint) or self.is_temporal
         self.subgraph_type = subgraph_type
         self.output_cls = output_cls
         self._calls = 0
-        self._build_csc(eis, dt, dev)
+        self.time = None
+        self._build_csc(eis, dt, dev, node_time, edge_time)
         self._unset = torch.iinfo(dt).min
         self._local = torch.full((max(nb[-1], 1), ), self._unset, dtype=dt, device=dev)
         self._unset_t = torch.full((1, ), self._unset, dtype=dt, device=dev)
 
-    def _build_csc(self, eis, dt, dev) -> None:
+    def _check_times(self, node_time, edge_time):
+        """Rules 1 and 2 on host-side facts only: the dicts with normalised keys, and
+        ``timed_mask`` (bit ``e``: edge type ``e`` is timed) / ``timed_node_types``."""
+        self.timed_mask, self.timed_node_types = 0, set()
+        if node_time is not None:
+            node_time = dict(node_time)
+            for t, v in node_time.items():
+                if t not in self.num_nodes:
+                    raise ValueError(f"'node_time' names the node type '{t}', which is not a "
+                                     f"node type of the graph ({self.node_types})")
+                _check_time(v, f"node_time['{t}']", self.num_nodes[t])
+            self.timed_node_types = set(node_time)
+            for e, et in enumerate(self.edge_types):
+                if et[0] in node_time:
+                    self.timed_mask |= 1 << e
+        if edge_time is not None:
+            edge_time = {_edge_type(k): v for k, v in edge_time.items()}
+            for et, v in edge_time.items():
+                if et not in self.edge_types:
+                    raise ValueError(f"'edge_time' names the edge type '{et}', which is not an "
+                                     f"edge type of the graph")
+                _check_time(v, f"edge_time[{et}]", self.num_edges[self.edge_types.index(et)])
+            for e, et in enumerate(self.edge_types):
+                if et in edge_time:
+                    self.timed_mask |= 1 << e
+        return node_time, edge_time
+
+    def _time_keys(self, eis, live, dev, node_time, edge_time):
+        """The per-edge time keys of a temporal CSC, in the order of the stacked edge list: the
+        edge's time (its source node's, or its own) minus the smallest time of all, 0 for an untimed
+        edge type.  Also fills ``self.time`` (node level: int64 over the global node ids; edge
+        level: the per-edge times, permuted into slot order by the caller).  One host read."""
+        times = node_time if node_time is not None else edge_time
+        vals = {k: v.to(device=dev, dtype=torch.int64).contiguous() for k, v in times.items()}
+        full = [v for v in vals.values() if v.numel() > 0]
+        lo_t, hi_t = 0, 0
+        if full:
+            lo_t, hi_t = (int(x) for x in torch.stack(
+                [torch.stack([v.min() for v in full]).min(),
+                 torch.stack([v.max() for v in full]).max()]).tolist())
+        span = hi_t - lo_t
+        if span >= 2 ** 63:
+            raise ValueError('the times span more than the int64 range')
+        kdt = torch.int32 if span < 2 ** 31 else torch.int64
+        keys = []
+        if node_time is not None:
+            self.time = torch.zeros(max(self.node_base[-1], 1), dtype=torch.int64, device=dev)
+            for t, v in vals.items():
+                b = self.node_base[self._type_index[t]]
+                self.time[b:b + v.numel()] = v
+            for e in live:
+                s_t = self.edge_types[e][0]
+                keys.append((vals[s_t] - lo_t).to(kdt).index_select(0, eis[e][0].long())
+                            if s_t in vals else
+                            torch.zeros(eis[e].size(1), dtype=kdt, device=dev))
+        else:
+            per_edge = []
+            for e in live:
+                v = vals.get(self.edge_types[e])
+                per_edge.append(v if v is not None else
+                                torch.zeros(eis[e].size(1), dtype=torch.int64, device=dev))
+                keys.append((v - lo_t).to(kdt) if v is not None else
+                            torch.zeros(eis[e].size(1), dtype=kdt, device=dev))
+            self.time = torch.cat(per_edge) if per_edge else \
+                torch.zeros(1, dtype=torch.int64, device=dev)
+        return (torch.cat(keys) if keys else None), span
+
+    def _build_csc(self, eis, dt, dev, node_time=None, edge_time=None) -> None:
         """The stacked CSC: one stable radix sort of every edge keyed by ``col_base[et] + dst``
         (slots of a column stay in ``edge_index`` order).  Two host reads at construction: one
         validates the indices (before any of them is used as an address), one gives every edge
-        type's largest in-degree (the static bound of ``-1`` hops)."""
+        type's largest in-degree (the static bound of ``-1`` hops).  A temporal sampler sorts
+        ``lexsort([time key, stacked column])`` instead, as two stable sorts (the reference's
+        ``sort_csc`` per timed edge type), with one more host read for the span of the times."""
         ET = len(self.edge_types)
         C = self.col_base[-1]
         eis = [ei.to(dev) for ei in eis]
@@ -1014,7 +1137,17 @@ class HeteroNeighborSampler:
             srcs = torch.cat([eis[e][0].long() + self.node_base[self._type_index[
                 self.edge_types[e][0]]] for e in live])
             pos = torch.cat([torch.arange(eis[e].size(1), device=dev) for e in live])
-            skeys, p = _native.index_sort(keys, max_value=max(C - 1, 0))
+            if self.is_temporal:
+                tkey, span = self._time_keys(eis, live, dev, node_time, edge_time)
+                p1 = _native.index_sort(tkey, max_value=span)[1]
+                del tkey
+                skeys, p2 = _native.index_sort(keys[p1], max_value=max(C - 1, 0))
+                p = p1[p2]
+                del p1, p2
+                if self.edge_level:
+                    self.time = self.time[p].contiguous()
+            else:
+                skeys, p = _native.index_sort(keys, max_value=max(C - 1, 0))
             self.colptr = _native.index2ptr(skeys, C)
             self.row = srcs[p].to(dt).contiguous()
             self.perm = pos[p].to(dt).contiguous()
@@ -1022,6 +1155,8 @@ class HeteroNeighborSampler:
             self.colptr = torch.zeros(C + 1, dtype=dt, device=dev)
             self.row = torch.empty(0, dtype=dt, device=dev)
             self.perm = torch.empty(0, dtype=dt, device=dev)
+            if self.is_temporal:
+                self._time_keys(eis, live, dev, node_time, edge_time)
         deg = self.colptr[1:] - self.colptr[:-1]
         maxdeg = [deg[self.col_base[e]:self.col_base[e + 1]].max().long()
                   if self.num_edges[e] > 0 else torch.zeros((), dtype=torch.int64, device=dev)
@@ -1030,10 +1165,12 @@ class HeteroNeighborSampler:
 
     # -- entry points --------------------------------------------------------------------------------
     @torch.no_grad()
-    def sample_from_nodes(self, index, seed: Optional[int] = None, **kwargs):
+    def sample_from_nodes(self, index, seed: Optional[int] = None,
+                          time: Optional[Tensor] = None, **kwargs):
         """``index``: ``(input_type, seeds)`` or a ``NodeSamplerInput``-like object (``.node``,
-        ``.input_id``, ``.input_type``; a seed ``.time`` is refused).  ``metadata = (input_id,
-        None)``."""
+        ``.input_id``, ``.input_type``, ``.time``).  ``time``: the seed times of a temporal sampler
+        (``index.time`` takes their place when given; a non-temporal sampler refuses them).
+        ``metadata = (input_id, time)``."""
         input_id = None
         if isinstance(index, (tuple, list)):
             if len(index) != 2:
@@ -1043,16 +1180,42 @@ class HeteroNeighborSampler:
             seeds, input_id = index.node, getattr(index, 'input_id', None)
             input_type = getattr(index, 'input_type', None)
             if getattr(index, 'time', None) is not None:
-                raise ValueError("temporal heterogeneous sampling (seed times) is not supported")
-        if kwargs.get('time') is not None:
-            raise ValueError("temporal heterogeneous sampling (seed times) is not supported")
+                time = index.time
+        if time is not None and not self.is_temporal:
+            raise ValueError("seed times belong to a temporal sampler ('node_time' / "
+                             "'edge_time'): this heterogeneous sampler has none")
         if input_type not in self._type_index:
             raise ValueError(f"the input type '{input_type}' is not a node type of the graph "
                              f"({self.node_types})")
         self.check_seeds(input_type, seeds)
-        out = self._sample(input_type, seeds, seed)
-        out.metadata = (input_id, None)
+        seed_time = self.seed_time(input_type, seeds, time) if self.is_temporal else None
+        out = self._sample(input_type, seeds, seed, seed_time)
+        out.metadata = (input_id, time)
         return out
+
+    def seed_time(self, input_type: str, seeds: Tensor, time: Optional[Tensor] = None) -> Tensor:
+        """The int64 seed time of every seed of a temporal batch: ``time`` if given (integer, one
+        per seed), else ``node_time[input_type][seeds]``; edge-level time, or an input type without
+        node times, needs ``time``."""
+        if not self.is_temporal:
+            raise ValueError('seed times belong to a temporal sampler (node_time / edge_time)')
+        if time is None:
+            if self.edge_level:
+                raise ValueError("temporal sampling with edge-level time ('edge_time') needs the "
+                                 "seed times (NodeSamplerInput.time / the loader's 'input_time')")
+            if input_type not in self.timed_node_types:
+                raise ValueError(f"temporal sampling from the input type '{input_type}', which "
+                                 f"has no entry in 'node_time', needs the seed times "
+                                 f"(NodeSamplerInput.time / the loader's 'input_time')")
+            idx = seeds.to(device=self.time.device).long() + \
+                self.node_base[self._type_index[input_type]]
+            return self.time[idx]
+        if not isinstance(time, Tensor) or time.dim() != 1 or time.numel() != seeds.numel():
+            raise ValueError(f"the seed times must be a 1-D tensor with one entry per seed "
+                             f"({seeds.numel()})")
+        if time.is_floating_point() or time.is_complex() or time.dtype == torch.bool:
+            raise ValueError(f"the seed times must be an integer tensor (got {time.dtype})")
+        return time.to(device=self.row.device, dtype=torch.int64).contiguous()
 
     def check_seeds(self, input_type: str, seeds) -> None:
         """Seeds must be a 1-D integer tensor of ids in ``[0, num_nodes[input_type])``: an id past
@@ -1073,12 +1236,13 @@ class HeteroNeighborSampler:
             raise ValueError(f"seed node ids must lie in [0, {n}) for node type '{input_type}' "
                              f"(got {lo} .. {hi})")
 
-    def _sample(self, input_type: str, seeds: Tensor, seed: Optional[int] = None):
-        """The batch of already checked seeds."""
+    def _sample(self, input_type: str, seeds: Tensor, seed: Optional[int] = None,
+                seed_time: Optional[Tensor] = None):
+        """The batch of already checked seeds (``seed_time``: :meth:`seed_time`'s, temporal)."""
         seeds = seeds.to(device=self.colptr.device, dtype=self.colptr.dtype).contiguous()
         rng = self.seed + self._calls if seed is None else seed
         self._calls += 1
-        return self._hops(input_type, seeds, rng)
+        return self._hops(input_type, seeds, rng, seed_time)
 
     def sample_from_edges(self, *args, **kwargs):
         raise NotImplementedError("heterogeneous link-level sampling is not supported")
@@ -1102,7 +1266,11 @@ class HeteroNeighborSampler:
             return n_items * k if d > 0 else 0
         return n_items * min(k, d)
 
-    def _hops(self, input_type: str, seeds: Tensor, rng: int):
+    def _hops(self, input_type: str, seeds: Tensor, rng: int,
+              seed_time: Optional[Tensor] = None):
+        """The hop loop.  ``seed_time`` (int64 [B], a temporal sampler): the counts launch becomes
+        the typed window, bounded by the seed time of every frontier node's tree, and the draw runs
+        on the windows."""
         dev, dt = self.colptr.device, self.colptr.dtype
         T, ET = len(self.node_types), len(self.edge_types)
         tin = self._type_index[input_type]
@@ -1127,7 +1295,7 @@ class HeteroNeighborSampler:
             trees[tin].append(torch.arange(B, device=dev))
             keys_all = torch.arange(B, device=dev) * S + g_seeds.long()
             pos2typed = torch.arange(B, dtype=dt, device=dev)
-            ftree = torch.arange(B, device=dev)
+            ftree, n_front = torch.arange(B, device=dev), B
         else:
             local = self._local
             local[g_seeds] = torch.arange(B, dtype=dt, device=dev)
@@ -1143,8 +1311,17 @@ class HeteroNeighborSampler:
                 cap += c
                 unbounded |= k < 0 and c > 0
             if cap > 0:
-                cnt = _native.hetero_sample_counts(self.colptr, frontier, item_begin, table,
-                                                   replace=self.replace)
+                if seed_time is not None:
+                    # the hop's ONE gather of seed times (the work items name the first n_front
+                    # entries of the frontier buffers only; the rest is unwritten capacity)
+                    ftime = seed_time[ftree[:n_front]]
+                    lo, hi, cnt = _native.hetero_sample_temporal_window(
+                        self.colptr, self.row, self.time, frontier, ftime, item_begin, table,
+                        self.timed_mask, edge_level=self.edge_level, replace=self.replace,
+                        last=self.temporal_strategy == 'last')
+                else:
+                    cnt = _native.hetero_sample_counts(self.colptr, frontier, item_begin, table,
+                                                       replace=self.replace)
                 offsets = torch.zeros(item_begin[-1] + 1, dtype=dt, device=dev)
                 if unbounded and dt == torch.int32 and cap >= 2 ** 31:
                     # the int32 scan could wrap: take the exact total from an int64 scan first
@@ -1169,10 +1346,15 @@ class HeteroNeighborSampler:
                 continue
             hop_seed = (rng * 1_000_003 + hop) & 0x7FFFFFFFFFFFFFFF
             total = offsets[-1:].to(torch.int64)
-            src, col, edge, fpos = _native.hetero_sample_neighbors(
-                self.colptr, self.row, self.perm, frontier, offsets, cap, item_begin, table,
-                hop_seed, replace=self.replace, salt_position=self.disjoint,
-                want_fpos=self.disjoint)
+            if seed_time is not None:
+                src, col, edge, fpos = _native.hetero_sample_neighbors_temporal(
+                    self.row, self.perm, frontier, lo, hi, offsets, cap, item_begin, table,
+                    hop_seed, replace=self.replace, salt_position=True, want_fpos=True)
+            else:
+                src, col, edge, fpos = _native.hetero_sample_neighbors(
+                    self.colptr, self.row, self.perm, frontier, offsets, cap, item_begin, table,
+                    hop_seed, replace=self.replace, salt_position=self.disjoint,
+                    want_fpos=self.disjoint)
             if self.disjoint:
                 row, sg, sl, tree_sorted, new_keys, typed, stats = self._relabel_disjoint(
                     keys_all, ftree, fpos, src, total, pos2typed, cap, count, offsets,
@@ -1201,7 +1383,7 @@ class HeteroNeighborSampler:
             if self.disjoint:
                 keys_all = torch.cat([keys_all, new_keys[:off]])
                 pos2typed = torch.cat([pos2typed, typed[:off]])
-                ftree = tree_sorted
+                ftree, n_front = tree_sorted, off
             else:
                 touched.append(sg[:off])
             prev = list(count)
