@@ -782,6 +782,45 @@ PYGAMD_API int pygamd_hetero_split(int phase, const void* new_nodes, int idx_dty
                                    void* sorted_global, void* sorted_local, int64_t* aux_out,
                                    int64_t* stats, void* stream);
 
+/* ---- heterogeneous link-level sampling: the typed seed block of an edge batch -------------------
+ * pygamd_hetero_link_seeds replaces the head of the reference's edge_sample for a HeteroData
+ * (sampler/neighbor_sampler.py:852-937, `input_type is not None`): the two neg_sample calls, the
+ * `torch.cat([src, src_neg])` / `torch.cat([dst, dst_neg])`, the `edge_label_time.repeat(...)` of
+ * the seed times, and the shift of both endpoints into the stacked global id space of the typed
+ * layer above.  For n_pos seed links of edge type (S, rel, D) with typed local endpoints src / dst
+ * (idx_dtype [n_pos]) it writes, one thread per slot and in ONE launch,
+ *   seeds_out (idx_dtype [n_src + n_dst]): the source block, then the destination block, as global
+ *     ids (local id + node_base of the endpoint's type).  Slot j < n_pos of a block is the positive
+ *     j; slot n_pos + j is a negative.  n_src = n_pos + num_neg for PYGAMD_LINK_NEG_BINARY and
+ *     n_pos otherwise; n_dst = n_pos + num_neg for _BINARY and _TRIPLET and n_pos for _NONE;
+ *   seed_time_out (int64 [n_src + n_dst], only when link_time is given): slot j of an endpoint
+ *     carries link_time[j % n_pos] (int64 [n_pos]): the reference's `repeat` rule.
+ * The negative in slot n_pos + j of endpoint e (0 source, 1 destination) is exactly
+ * pygamd_sample_negatives' draw j for the seed `seed * 2 + e` (no seed_dev), that endpoint's
+ * num_nodes, cdf (src_cdf / dst_cdf, fp64 [num_nodes] or NULL), node_time (src_node_time /
+ * dst_node_time, int64 [num_nodes]: the type's own slice of the node-level time vector, or NULL
+ * when the type has no times or time is edge-level: the draw is then unbounded,
+ * `node_time.get(type)` in the reference), fallback, and the bound link_time[j % n_pos].
+ * ep_table is host int64 [2][3]: num_nodes, node_base and fallback of the source, then of the
+ * destination endpoint; it travels in the kernel arguments.
+ * Rejected before any launch (PYGAMD_ERR_INVALID_ARG): a mode outside the three below; n_pos < 0
+ * or num_neg < 0; num_neg != 0 with _NONE or with n_pos == 0; a NULL ep_table; negative num_nodes
+ * or node_base; an unknown idx_dtype, or I32 with node_base + num_nodes > INT32_MAX; a node_time
+ * without link_time, or with a fallback outside [0, num_nodes); link_time without seed_time_out;
+ * an endpoint that draws from a type without nodes; and, when n_pos > 0, a NULL src, dst or
+ * seeds_out.  n_pos == 0 otherwise returns PYGAMD_OK and launches nothing.                      */
+#define PYGAMD_LINK_NEG_NONE 0
+#define PYGAMD_LINK_NEG_BINARY 1
+#define PYGAMD_LINK_NEG_TRIPLET 2
+PYGAMD_API int pygamd_hetero_link_seeds(const void* src, const void* dst, int idx_dtype,
+                                        int64_t n_pos, int64_t num_neg, int mode,
+                                        const int64_t* link_time,
+                                        const int64_t* ep_table /*[host]*/,
+                                        const double* src_cdf, const double* dst_cdf,
+                                        const int64_t* src_node_time,
+                                        const int64_t* dst_node_time, uint64_t seed,
+                                        void* seeds_out, int64_t* seed_time_out, void* stream);
+
 /* ---- temporal heterogeneous hops: the typed window and the typed draw on a window -------------
  * The reference's NeighborLoader(hetero_data, time_attr=..., temporal_strategy=...) ->
  * hetero_neighbor_sample(..., node_time, edge_time, seed_time, ..., temporal_strategy)

@@ -177,6 +177,8 @@ SIGNATURES = {
     'pygamd_hetero_sample_neighbors_temporal': (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P,
                                                         c_int, c_uint64, c_int, _P, _P, _P, _P,
                                                         _P]),
+    'pygamd_hetero_link_seeds': (c_int, [_P, _P, c_int, c_int64, c_int64, c_int, _P, _P, _P, _P,
+                                         _P, _P, c_uint64, _P, _P, _P]),
     'pygamd_gather_rows': (c_int, [_P, c_int64, c_int64, _P, c_int, c_int64, c_int64, _P,
                                    c_int64, _P, _P]),
     'pygamd_gather_scatter_add': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P, c_int64, _P,

@@ -1890,17 +1890,22 @@ def sample_negatives(n: int, num_nodes: int, seed: int, device, dtype=torch.int6
     return out
 
 
-def unique_inverse(keys: Tensor, max_value: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+def unique_inverse(keys: Tensor, max_value: Optional[int] = None, count_on_device: bool = False):
     """``torch.unique(keys, return_inverse=True)`` of non-negative int32 / int64 ids (sorted; the
     inverse is int64): :func:`index_sort` (``max_value`` bounds its passes), then
-    ``pygamd_unique_inverse``.  One host read, the number of distinct keys."""
+    ``pygamd_unique_inverse``.  One host read, the number of distinct keys.
+    ``count_on_device``: no host read; returns ``(uniq, inverse, n_unique)`` with ``uniq`` at its
+    capacity ``len(keys)`` (entries past the count are unwritten) and ``n_unique`` int64 ``[1]`` on
+    the device, for a caller that reads the count together with other values."""
     _require_device(keys)
     if keys.dim() != 1:
         raise ValueError("'keys' must be one-dimensional")
     _idx_dtype(keys)
     n = keys.numel()
     if n == 0:
-        return keys.new_empty(0), torch.empty(0, dtype=torch.int64, device=keys.device)
+        empty = (keys.new_empty(0), torch.empty(0, dtype=torch.int64, device=keys.device))
+        return empty + (torch.zeros(1, dtype=torch.int64, device=keys.device), ) \
+            if count_on_device else empty
     sorted_k, perm = index_sort(keys, max_value)
     lib = _lib.load()
     nbytes = ctypes.c_size_t(0)
@@ -1913,6 +1918,8 @@ def unique_inverse(keys: Tensor, max_value: Optional[int] = None) -> Tuple[Tenso
     check(lib.pygamd_unique_inverse(_p(sorted_k), _p(perm), _idx_dtype(keys), n, _p(rank), _p(ws),
                                     nbytes.value, _p(uniq), _p(inverse), _p(n_unique),
                                     _stream(keys)), 'unique_inverse')
+    if count_on_device:
+        return uniq, inverse, n_unique
     return uniq[:int(n_unique)], inverse  # host read: sizes the seed block
 
 
@@ -1921,6 +1928,80 @@ def _i64_host(values):
     """A host int64 array for the small per-type tables of the hetero entry points."""
     arr = (ctypes.c_int64 * max(len(values), 1))(*values)
     return arr
+
+
+LINK_NEG_MODES = {None: 0, 'none': 0, 'binary': 1, 'triplet': 2}
+
+
+def hetero_link_seeds(src: Tensor, dst: Tensor, num_neg: int, mode, seed: int, endpoints,
+                      link_time: Optional[Tensor] = None
+                      ) -> Tuple[Tensor, Optional[Tensor]]:
+    """``pygamd_hetero_link_seeds``: the typed seed block of a heterogeneous edge batch in one
+    launch.  ``src`` / ``dst``: the typed local endpoints ``[P]`` of the positive links (device,
+    one index dtype); ``mode``: ``None`` / ``'binary'`` / ``'triplet'``; ``endpoints``: two dicts
+    (source, destination) with ``num_nodes``, ``node_base`` and optionally ``cdf`` (fp64
+    ``[num_nodes]``), ``node_time`` (int64 ``[num_nodes]``, that type's slice) and ``fallback``.
+    Returns ``(seeds, seed_time)``: the global ids ``[n_src + n_dst]`` (source block first,
+    positives then negatives; the negative in slot ``P + j`` of endpoint ``e`` is
+    :func:`sample_negatives`' draw ``j`` for the seed ``seed * 2 + e``), and, with ``link_time``
+    (int64 ``[P]``), the int64 time ``link_time[j % P]`` of every slot (else ``None``)."""
+    if mode not in LINK_NEG_MODES:
+        raise ValueError(f"'mode' must be None, 'binary' or 'triplet' (got {mode!r})")
+    m = LINK_NEG_MODES[mode]
+    if src.dim() != 1 or dst.dim() != 1 or src.numel() != dst.numel() or src.dtype != dst.dtype:
+        raise ValueError("'src' and 'dst' must be one-dimensional, of one length and one dtype")
+    dt = _idx_dtype(src)
+    P = src.numel()
+    if num_neg < 0 or (num_neg > 0 and (m == 0 or P == 0)):
+        raise ValueError(f"'num_neg' must be non-negative, and zero without a negative-sampling "
+                         f"mode or without positive links (got {num_neg})")
+    if len(endpoints) != 2:
+        raise ValueError("'endpoints' describes the source and the destination endpoint")
+    if link_time is not None and (link_time.dtype != torch.int64 or link_time.dim() != 1
+                                  or link_time.numel() != P):
+        raise ValueError(f"'link_time' must be a one-dimensional int64 tensor with {P} entries")
+    table, cdfs, times = [], [], []
+    for e, ep in enumerate(endpoints):
+        n, base = int(ep['num_nodes']), int(ep['node_base'])
+        cdf, node_time = ep.get('cdf'), ep.get('node_time')
+        fallback = int(ep.get('fallback') or 0)
+        draws = num_neg > 0 and (m == 1 or (m == 2 and e == 1))
+        if n < 0 or base < 0:
+            raise ValueError("'num_nodes' and 'node_base' must be non-negative")
+        if draws and n <= 0:
+            raise ValueError('negatives need a node type with at least one node')
+        if src.dtype == torch.int32 and base + n > 2 ** 31 - 1:
+            raise ValueError('int32 seeds: the global ids of the endpoint type do not fit')
+        if cdf is not None and (cdf.dtype != torch.float64 or cdf.dim() != 1
+                                or cdf.numel() != n):
+            raise ValueError(f"'cdf' must be a one-dimensional float64 tensor with {n} entries")
+        if node_time is not None:
+            if link_time is None:
+                raise ValueError("'node_time' bounds the negatives by 'link_time', which is "
+                                 "missing")
+            if node_time.dtype != torch.int64 or node_time.dim() != 1 or node_time.numel() != n \
+                    or not node_time.is_contiguous():
+                raise ValueError(f"'node_time' must be contiguous int64 with {n} entries")
+            if not 0 <= fallback < n:
+                raise ValueError(f"'fallback' must be a node id in [0, {n})")
+        table += [n, base, fallback]
+        cdfs.append(None if cdf is None else cdf.contiguous())
+        times.append(node_time)
+    _require_device(src, dst, link_time, *cdfs, *times)
+    n_src = P + (num_neg if m == 1 else 0)
+    n_dst = P + (num_neg if m >= 1 else 0)
+    seeds = torch.empty(n_src + n_dst, dtype=src.dtype, device=src.device)
+    seed_time = None if link_time is None else \
+        torch.empty(n_src + n_dst, dtype=torch.int64, device=src.device)
+    if P == 0:
+        return seeds, seed_time
+    src, dst = src.contiguous(), dst.contiguous()
+    link_time = None if link_time is None else link_time.contiguous()
+    check(_lib.load().pygamd_hetero_link_seeds(
+        _p(src), _p(dst), dt, P, int(num_neg), m, _p(link_time), _i64_host(table), _p(cdfs[0]),
+        _p(cdfs[1]), _p(times[0]), _p(times[1]), seed & 0xFFFFFFFFFFFFFFFF, _p(seeds),
+        _p(seed_time), _stream(seeds)), 'hetero_link_seeds')
+    return seeds, seed_time
 
 
 def hetero_sample_counts(colptr: Tensor, frontier: Tensor, item_begin, et_table,

@@ -900,7 +900,13 @@ def neighbor_sampler(data, num_neighbors: List[int], seed: int = 0, replace: boo
     (:meth:`pytorch_geometric_amd.sampler.NeighborSampler.sample_from_edges`), so that the
     reference's ``LinkLoader(data, link_sampler=...)`` (loader/link_loader.py) drives it too; its
     ``NegativeSampling`` objects are taken as they are, and ``edge_label_time`` needs
-    ``time_attr``."""
+    ``time_attr``.  On a ``HeteroData`` it is
+    :meth:`pytorch_geometric_amd.sampler.HeteroNeighborSampler.sample_from_edges`: the
+    ``EdgeSamplerInput`` carries the edge type of the seed links as ``input_type``
+    (``LinkLoader(hetero_data, link_sampler=..., edge_label_index=(edge_type, eli))``), and the
+    batches come out of the reference's ``filter_hetero_data`` with ``edge_label_index`` /
+    ``edge_label`` / ``edge_label_time`` on that edge type's store, or ``src_index`` /
+    ``dst_pos_index`` / ``dst_neg_index`` / ``seed_time`` on its endpoint types' stores."""
     global _sampler_cls
     import torch_geometric.sampler as pyg_sampler
     from .sampler import NeighborSampler
@@ -1011,6 +1017,8 @@ def _hetero_neighbor_sampler(data, num_neighbors, seed, replace, disjoint, subgr
                 return self.impl.sample_from_nodes(index, **kwargs)
 
             def sample_from_edges(self, index, neg_sampling=None):
+                # the reference's LinkLoader: an EdgeSamplerInput whose input_type is the edge
+                # type of the seed links, and its own NegativeSampling (cast by duck typing)
                 return self.impl.sample_from_edges(index, neg_sampling)
 
             @property

@@ -559,6 +559,25 @@ __device__ __forceinline__ int64_t negative_candidate(uint64_t h, int64_t num_no
   return lo;
 }
 
+// draw j of the stream `key` (= mix64(seed ^ kNegSalt)): the candidate rounds and the `<=` rule
+__device__ __forceinline__ int64_t negative_draw(uint64_t key, int64_t j, int64_t num_nodes,
+                                                 const double* __restrict__ cdf,
+                                                 const int64_t* __restrict__ node_time, int64_t t,
+                                                 int64_t fallback) {
+  const double total = cdf ? cdf[num_nodes - 1] : 0.0;
+  const uint64_t base = static_cast<uint64_t>(j) * 8u;
+  int64_t c = negative_candidate(mix64(key + base), num_nodes, cdf, total);
+  if (node_time) {
+    bool ok = node_time[c] <= t;
+    for (int r = 1; r < kNegRounds && !ok; ++r) {
+      c = negative_candidate(mix64(key + base + static_cast<uint64_t>(r)), num_nodes, cdf, total);
+      ok = node_time[c] <= t;
+    }
+    if (!ok) c = fallback;
+  }
+  return c;
+}
+
 template <typename IdxT>
 __global__ void __launch_bounds__(kBlock)
     sample_negatives_kernel(int64_t n, int64_t num_nodes, uint64_t seed,
@@ -570,19 +589,51 @@ __global__ void __launch_bounds__(kBlock)
   if (j >= n) return;
   if (seed_dev) seed = mix64(seed ^ mix64(*seed_dev * 0x9E3779B97F4A7C15ull));
   const uint64_t key = mix64(seed ^ kNegSalt);
-  const double total = cdf ? cdf[num_nodes - 1] : 0.0;
-  const uint64_t base = static_cast<uint64_t>(j) * 8u;
-  int64_t c = negative_candidate(mix64(key + base), num_nodes, cdf, total);
-  if (node_time) {
-    const int64_t t = bound[j % n_bound];
-    bool ok = node_time[c] <= t;
-    for (int r = 1; r < kNegRounds && !ok; ++r) {
-      c = negative_candidate(mix64(key + base + static_cast<uint64_t>(r)), num_nodes, cdf, total);
-      ok = node_time[c] <= t;
-    }
-    if (!ok) c = fallback;
+  const int64_t t = node_time ? bound[j % n_bound] : 0;
+  out[j] = static_cast<IdxT>(negative_draw(key, j, num_nodes, cdf, node_time, t, fallback));
+}
+
+// ---- the typed seed block of a heterogeneous edge batch (the reference's edge_sample, heterogeneous
+// branch, sampler/neighbor_sampler.py:852-937): seeds = [source block | destination block] as global
+// ids of the stacked id space, one thread per slot.  Slot j of an endpoint is the positive j for
+// j < n_pos and otherwise draw j - n_pos of pygamd_sample_negatives' stream seed * 2 + endpoint with
+// that endpoint's num_nodes / cdf / node_time / fallback and the bound link_time[j % n_pos];
+// seed_time[slot] = link_time[j % n_pos] (the reference's `repeat`).  The two endpoints' values
+// travel in the kernel arguments, like the hop table of the typed layer below.
+struct LinkEndpoint {
+  int64_t n;          // slots of this endpoint: n_pos, or n_pos + num_neg
+  int64_t num_nodes;
+  int64_t node_base;
+  int64_t fallback;
+  const double* cdf;          // fp64 [num_nodes] or NULL (uniform)
+  const int64_t* node_time;   // int64 [num_nodes] or NULL (untimed type / edge-level time)
+};
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    hetero_link_seeds_kernel(const IdxT* __restrict__ src, const IdxT* __restrict__ dst,
+                             int64_t n_pos, const LinkEndpoint e_src, const LinkEndpoint e_dst,
+                             uint64_t seed, const int64_t* __restrict__ link_time,
+                             IdxT* __restrict__ seeds, int64_t* __restrict__ seed_time) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= e_src.n + e_dst.n) return;
+  const bool is_dst = i >= e_src.n;
+  const int64_t j = is_dst ? i - e_src.n : i;
+  // (selected field by field: indexing a two-entry argument array would spill it to scratch)
+  const int64_t num_nodes = is_dst ? e_dst.num_nodes : e_src.num_nodes;
+  const int64_t node_base = is_dst ? e_dst.node_base : e_src.node_base;
+  const int64_t t = link_time ? link_time[j % n_pos] : 0;
+  int64_t c;
+  if (j < n_pos) {
+    c = static_cast<int64_t>((is_dst ? dst : src)[j]);
+  } else {
+    const uint64_t key = mix64((seed * 2u + (is_dst ? 1u : 0u)) ^ kNegSalt);
+    c = negative_draw(key, j - n_pos, num_nodes, is_dst ? e_dst.cdf : e_src.cdf,
+                      is_dst ? e_dst.node_time : e_src.node_time, t,
+                      is_dst ? e_dst.fallback : e_src.fallback);
   }
-  out[j] = static_cast<IdxT>(c);
+  seeds[i] = static_cast<IdxT>(c + node_base);
+  if (seed_time) seed_time[i] = t;
 }
 
 // ---- torch.unique(keys, return_inverse=True) on the output of index_sort: rank[i] = 1 where a run
@@ -1034,6 +1085,48 @@ int pygamd_unique_inverse(const void* keys_sorted, const int64_t* perm, int idx_
     if (scan_rc != PYGAMD_OK) return scan_rc;
     hipLaunchKernelGGL((unique_scatter_kernel<IdxT>), grid, dim3(kBlock), 0, st, keys, perm, n,
                        rank, static_cast<IdxT*>(uniq_out), inverse_out, n_unique);
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_hetero_link_seeds(const void* src, const void* dst, int idx_dtype, int64_t n_pos,
+                             int64_t num_neg, int mode, const int64_t* link_time,
+                             const int64_t* ep_table, const double* src_cdf, const double* dst_cdf,
+                             const int64_t* src_node_time, const int64_t* dst_node_time,
+                             uint64_t seed, void* seeds_out, int64_t* seed_time_out,
+                             void* stream) {
+  if (mode < PYGAMD_LINK_NEG_NONE || mode > PYGAMD_LINK_NEG_TRIPLET) return PYGAMD_ERR_INVALID_ARG;
+  if (n_pos < 0 || num_neg < 0 || !ep_table) return PYGAMD_ERR_INVALID_ARG;
+  if (mode == PYGAMD_LINK_NEG_NONE && num_neg != 0) return PYGAMD_ERR_INVALID_ARG;
+  if (idx_dtype != PYGAMD_IDX_I32 && idx_dtype != PYGAMD_IDX_I64) return PYGAMD_ERR_INVALID_ARG;
+  LinkEndpoint ep[2];
+  for (int e = 0; e < 2; ++e) {
+    ep[e].num_nodes = ep_table[3 * e];
+    ep[e].node_base = ep_table[3 * e + 1];
+    ep[e].fallback = ep_table[3 * e + 2];
+    ep[e].cdf = e ? dst_cdf : src_cdf;
+    ep[e].node_time = e ? dst_node_time : src_node_time;
+    const bool draws = mode == PYGAMD_LINK_NEG_BINARY || (e == 1 && mode == PYGAMD_LINK_NEG_TRIPLET);
+    ep[e].n = n_pos + (draws ? num_neg : 0);
+    if (ep[e].num_nodes < 0 || ep[e].node_base < 0) return PYGAMD_ERR_INVALID_ARG;
+    if (idx_dtype == PYGAMD_IDX_I32 && ep[e].node_base + ep[e].num_nodes > INT32_MAX)
+      return PYGAMD_ERR_INVALID_ARG;
+    if (ep[e].node_time && !link_time) return PYGAMD_ERR_INVALID_ARG;  // times without a bound
+    if (ep[e].node_time && (ep[e].fallback < 0 || ep[e].fallback >= ep[e].num_nodes))
+      return PYGAMD_ERR_INVALID_ARG;
+    if (draws && num_neg > 0 && n_pos > 0 && ep[e].num_nodes <= 0) return PYGAMD_ERR_INVALID_ARG;
+  }
+  if (link_time && !seed_time_out) return PYGAMD_ERR_INVALID_ARG;
+  if (n_pos == 0) return num_neg == 0 ? PYGAMD_OK : PYGAMD_ERR_INVALID_ARG;  // no link to bound by
+  if (!src || !dst || !seeds_out) return PYGAMD_ERR_INVALID_ARG;
+  const int64_t n = ep[0].n + ep[1].n;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    hipLaunchKernelGGL((hetero_link_seeds_kernel<IdxT>),
+                       dim3(static_cast<unsigned>(ceil_div(n, kBlock))), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(src),
+                       static_cast<const IdxT*>(dst), n_pos, ep[0], ep[1], seed, link_time,
+                       static_cast<IdxT*>(seeds_out), link_time ? seed_time_out : nullptr);
     PYGAMD_LAUNCH_CHECK();
     return PYGAMD_OK;
   });

@@ -5,7 +5,9 @@ BASELINE config 4 — seeds are drawn per batch, the k-hop neighbourhood is samp
 ``x[n_id]``) and the batch never touches the host.  :class:`LinkNeighborLoader` is the
 ``LinkNeighborLoader`` role (loader/link_neighbor_loader.py, link_loader.py): batches of seed
 links with negatives drawn on the device.  :class:`HeteroNeighborLoader` is ``NeighborLoader`` on
-a ``HeteroData`` (seeds of one node type, features per node type)."""
+a ``HeteroData`` (seeds of one node type, features per node type) and
+:class:`HeteroLinkNeighborLoader` ``LinkNeighborLoader`` on a ``HeteroData`` (seed links of one edge
+type)."""
 import queue
 import threading
 from dataclasses import dataclass
@@ -19,7 +21,7 @@ import os
 
 from . import _native
 from .edge_index import EdgeIndex
-from .sampler import HeteroNeighborSampler, NegativeSampling, NeighborSampler
+from .sampler import HeteroNeighborSampler, NegativeSampling, NeighborSampler, _edge_type
 
 # collate_slots: layer 0 of the slot stack gathers its neighbours' rows straight from the feature
 # matrix (only the destination rows of a batch are copied) — slots.SlotSampler.gather(direct=True).
@@ -563,3 +565,169 @@ class HeteroNeighborLoader(_Prefetching):
                            batch_size=seeds.numel(), num_sampled_nodes=out.num_sampled_nodes,
                            num_sampled_edges=out.num_sampled_edges, y=y, batch=out.batch,
                            seed_time=seed_time)
+
+
+@dataclass
+class HeteroLinkBatch(HeteroBatch):
+    """A heterogeneous link-level mini-batch (:class:`HeteroLinkNeighborLoader`):
+    :class:`HeteroBatch`'s fields (``input_type`` is the edge type ``(S, rel, D)`` of the seed
+    links, ``batch_size`` the number of positive links ``B``) plus the reference's link fields
+    (loader/link_loader.py:281-303).  Without negatives or with binary ones: ``edge_label_index``
+    ``[2, B + num_neg]`` (row 0 local ids into ``n_id[S]``, row 1 into ``n_id[D]``),
+    ``edge_label`` and ``edge_label_time``; with triplet ones: ``src_index`` (into ``n_id[S]``),
+    ``dst_pos_index`` / ``dst_neg_index`` (into ``n_id[D]``; ``[B]`` or ``[B, amount]``) and
+    ``seed_time``."""
+    edge_label_index: Optional[Tensor] = None
+    edge_label: Optional[Tensor] = None
+    edge_label_time: Optional[Tensor] = None
+    src_index: Optional[Tensor] = None
+    dst_pos_index: Optional[Tensor] = None
+    dst_neg_index: Optional[Tensor] = None
+
+    def record_stream(self, stream) -> None:
+        super().record_stream(stream)
+        for t in (self.edge_label_index, self.edge_label, self.edge_label_time, self.src_index,
+                  self.dst_pos_index, self.dst_neg_index):
+            if isinstance(t, Tensor) and t.is_cuda:
+                t.record_stream(stream)
+
+
+class HeteroLinkNeighborLoader(_Prefetching):
+    r"""Iterates over mini-batches of ``batch_size`` seed LINKS of one edge type with their sampled
+    heterogeneous ``k``-hop neighbourhoods: the reference's ``LinkNeighborLoader(hetero_data,
+    edge_label_index=(edge_type, edge_label_index))`` (loader/link_neighbor_loader.py ->
+    loader/link_loader.py), sampled on the GPU
+    (:meth:`~.sampler.HeteroNeighborSampler.sample_from_edges`).
+
+    Args:
+        x_dict, edge_index_dict, num_neighbors, batch_size, shuffle, drop_last, seed, prefetch,
+            replace, disjoint, node_time, edge_time, temporal_strategy: as for
+            :class:`HeteroNeighborLoader`.
+        edge_label_index: ``(edge_type, tensor)``: the edge type ``(S, rel, D)`` of the seed links
+            and the ``[2, L]`` positive links to iterate over (typed local ids; ``None``: that
+            edge type's own ``edge_index``).
+        edge_label, edge_label_time, neg_sampling, neg_sampling_ratio: as for
+            :class:`LinkNeighborLoader`; the weights of ``neg_sampling`` are per endpoint type
+            (``src_weight`` ``[N_S]``, ``dst_weight`` ``[N_D]``).
+
+    Yields :class:`HeteroLinkBatch`.
+    """
+
+    def __init__(self, x_dict: Dict[str, Tensor], edge_index_dict, num_neighbors,
+                 edge_label_index, edge_label: Optional[Tensor] = None,
+                 edge_label_time: Optional[Tensor] = None, neg_sampling=None,
+                 neg_sampling_ratio: Optional[float] = None, batch_size: int = 1024,
+                 shuffle: bool = False, drop_last: bool = False, seed: int = 0,
+                 prefetch: int = 0, replace: bool = False, disjoint: bool = False,
+                 node_time=None, edge_time=None, temporal_strategy: str = 'uniform'):
+        temporal = node_time is not None or edge_time is not None
+        if (edge_label_time is not None) != temporal:
+            # (the reference's wording, loader/link_neighbor_loader.py:242-249; 'time_attr' is
+            # node_time / edge_time here)
+            raise ValueError(
+                f"Received conflicting 'edge_label_time' and 'time_attr' arguments: "
+                f"'edge_label_time' is {'set' if edge_label_time is not None else 'not set'} "
+                f"while 'time_attr' is {'set' if temporal else 'not set'}. Both arguments must "
+                f"be provided for temporal sampling.")
+        if neg_sampling_ratio is not None and neg_sampling_ratio != 0.0:
+            neg_sampling = NegativeSampling('binary', neg_sampling_ratio)
+        self.neg_sampling = NegativeSampling.cast(neg_sampling)
+        if self.neg_sampling is not None and self.neg_sampling.is_triplet() \
+                and edge_label is not None:
+            # (the reference's wording, loader/link_loader.py:177-183)
+            raise ValueError("'edge_label' needs to be undefined for 'triplet'-based negative "
+                             "sampling. Please use `src_index`, `dst_pos_index` and "
+                             "`neg_pos_index` of the returned mini-batch instead to "
+                             "differentiate between positive and negative samples.")
+        if not isinstance(edge_label_index, (tuple, list)) or len(edge_label_index) != 2 \
+                or isinstance(edge_label_index[0], Tensor):
+            raise ValueError("'edge_label_index' must be (edge_type, [2, L] tensor or None): "
+                             "heterogeneous link-level sampling needs the edge type of the seed "
+                             "links")
+        input_type, links = edge_label_index
+        input_type = _edge_type(input_type)
+        edge_types = [_edge_type(k) for k in edge_index_dict.keys()]
+        if input_type not in edge_types:
+            raise ValueError(f"the input type '{input_type}' is not an edge type of the graph "
+                             f"({edge_types})")
+        for t in (input_type[0], input_type[2]):
+            if t not in x_dict:
+                raise ValueError(f"the node type '{t}' of the seed links has no entry in "
+                                 f"'x_dict'")
+        if links is None:
+            links = list(edge_index_dict.values())[edge_types.index(input_type)]
+        if not isinstance(links, Tensor) or links.dim() != 2 or links.size(0) != 2:
+            raise ValueError(f"'edge_label_index' must be a [2, L] tensor (got "
+                             f"{list(links.shape) if isinstance(links, Tensor) else type(links)})")
+        L = links.size(1)
+        for name, t in (('edge_label', edge_label), ('edge_label_time', edge_label_time)):
+            if t is not None and (t.dim() < 1 or t.size(0) != L):
+                raise ValueError(f"'{name}' needs one entry per link of 'edge_label_index' ({L})")
+        if self.neg_sampling is not None:
+            for w, t in ((self.neg_sampling.src_weight, input_type[0]),
+                         (self.neg_sampling.dst_weight, input_type[2])):
+                if w is not None and w.numel() != x_dict[t].size(0):
+                    raise ValueError(f"The 'weight' attribute in 'NegativeSampling' needs to "
+                                     f"match the number of nodes {x_dict[t].size(0)} of node "
+                                     f"type '{t}' (got {w.numel()})")
+        self.prefetch = int(prefetch)
+        self._side = None
+        self.x_dict = dict(x_dict)
+        self.sampler = HeteroNeighborSampler(
+            edge_index_dict, {t: x.size(0) for t, x in self.x_dict.items()}, num_neighbors,
+            seed=seed, replace=replace, disjoint=disjoint, node_time=node_time,
+            edge_time=edge_time, temporal_strategy=temporal_strategy)
+        dev = self.sampler.colptr.device
+        self.input_type = input_type
+        self.edge_label_index = links.to(dev)
+        # once: batches are column selections of it
+        self.sampler.check_seeds(input_type[0], self.edge_label_index[0])
+        self.sampler.check_seeds(input_type[2], self.edge_label_index[1])
+        if edge_label is not None:
+            edge_label = edge_label.to(dev)
+            if self.neg_sampling is not None and self.neg_sampling.is_binary() \
+                    and L > 0 and edge_label.min() == 0:
+                edge_label = edge_label + 1  # zero now denotes "negative"
+        self.edge_label = edge_label
+        self.edge_label_time = None if edge_label_time is None else \
+            self.sampler.seed_time(input_type[0], self.edge_label_index[0], edge_label_time)
+        self.batch_size, self.shuffle, self.drop_last = batch_size, shuffle, drop_last
+        self._gen = torch.Generator().manual_seed(seed)
+
+    def _stream_device(self):
+        return self.sampler.colptr.device
+
+    def __len__(self) -> int:
+        n = self.edge_label_index.size(1)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _plan(self):
+        n = self.edge_label_index.size(1)
+        dev = self.edge_label_index.device
+        order = (torch.randperm(n, generator=self._gen).to(dev) if self.shuffle
+                 else torch.arange(n, device=dev))
+        for b in range(len(self)):
+            sel = order[b * self.batch_size:(b + 1) * self.batch_size]
+            yield self.edge_label_index[:, sel], sel
+
+    def collate(self, edges: Tensor, input_id: Tensor) -> HeteroLinkBatch:
+        """One batch from the positive links ``edges`` ``[2, B]`` (``input_id``: their positions
+        in ``edge_label_index``)."""
+        inp = SimpleNamespace(
+            row=edges[0], col=edges[1], input_id=input_id, input_type=self.input_type,
+            label=None if self.edge_label is None else self.edge_label[input_id],
+            time=None if self.edge_label_time is None else self.edge_label_time[input_id])
+        out = self.sampler.sample_from_edges(inp, self.neg_sampling)
+        # filter_hetero_data: x[t][n_id[t]] per node type, with the HIP gather kernel
+        x_dict = {t: _native.gather_rows(x, out.node[t]) for t, x in self.x_dict.items()}
+        ei = {et: torch.stack([out.row[et], out.col[et]]) for et in out.row}
+        b = HeteroLinkBatch(x_dict=x_dict, edge_index_dict=ei, n_id=out.node, e_id=out.edge,
+                            input_type=self.input_type, input_id=input_id,
+                            batch_size=edges.size(1), num_sampled_nodes=out.num_sampled_nodes,
+                            num_sampled_edges=out.num_sampled_edges, batch=out.batch)
+        md = out.metadata
+        if self.neg_sampling is None or self.neg_sampling.is_binary():
+            b.edge_label_index, b.edge_label, b.edge_label_time = md[1], md[2], md[3]
+        else:
+            b.src_index, b.dst_pos_index, b.dst_neg_index, b.seed_time = md[1:5]
+        return b

@@ -198,6 +198,31 @@ def _check_time(t, name: str, n: int) -> None:
                          f"takes int64 times")
 
 
+def _cached_cdf(cache: dict, weight: Tensor, num_nodes: int, device) -> Tensor:
+    """The fp64 inclusive CDF of a node weight vector, built once per tensor (and version) and
+    kept in ``cache``: setup work, the per-batch draw is the kernel.  One host read validates it
+    like ``torch.multinomial`` does (non-negative, finite, positive sum)."""
+    key = id(weight)
+    hit = cache.get(key)
+    if hit is not None and hit[0] is weight and hit[1] == weight._version:
+        return hit[2]
+    if not isinstance(weight, Tensor) or weight.dim() != 1 or weight.numel() != num_nodes:
+        raise ValueError(f"The 'weight' attribute in 'NegativeSampling' needs to match the "
+                         f"number of nodes {num_nodes}")
+    if not weight.is_floating_point():
+        raise ValueError(f"negative-sampling weights must be floating (got {weight.dtype})")
+    w = weight.to(device=device, dtype=torch.float64)
+    cdf = torch.cumsum(w, 0)
+    lo, total = (float(v) for v in torch.stack([w.min(), cdf[-1]]).tolist())
+    if not (lo >= 0 and math.isfinite(total) and total > 0):
+        raise ValueError("negative-sampling weights must be finite and non-negative with a "
+                         "positive sum")
+    if len(cache) >= 8:  # (a caller that makes a new weight tensor per batch)
+        cache.clear()
+    cache[key] = (weight, weight._version, cdf)
+    return cdf
+
+
 class NeighborSampler:
     r"""k-hop neighbour sampler on the GPU (uniform, biased by ``edge_weight``, or temporal).
 
@@ -514,28 +539,8 @@ class NeighborSampler:
                                         fallback=fallback or 0)
 
     def _negative_cdf(self, weight: Tensor) -> Tensor:
-        """The fp64 inclusive CDF of a node weight vector, built once per tensor (and version) and
-        cached: setup work, the per-batch draw is the kernel.  One host read validates it like
-        ``torch.multinomial`` does (non-negative, finite, positive sum)."""
-        key = id(weight)
-        hit = self._neg_cdf.get(key)
-        if hit is not None and hit[0] is weight and hit[1] == weight._version:
-            return hit[2]
-        if not isinstance(weight, Tensor) or weight.dim() != 1 or weight.numel() != self.num_nodes:
-            raise ValueError(f"The 'weight' attribute in 'NegativeSampling' needs to match the "
-                             f"number of nodes {self.num_nodes}")
-        if not weight.is_floating_point():
-            raise ValueError(f"negative-sampling weights must be floating (got {weight.dtype})")
-        w = weight.to(device=self.colptr.device, dtype=torch.float64)
-        cdf = torch.cumsum(w, 0)
-        lo, total = (float(v) for v in torch.stack([w.min(), cdf[-1]]).tolist())
-        if not (lo >= 0 and math.isfinite(total) and total > 0):
-            raise ValueError("negative-sampling weights must be finite and non-negative with a "
-                             "positive sum")
-        if len(self._neg_cdf) >= 8:  # (a caller that makes a new weight tensor per batch)
-            self._neg_cdf.clear()
-        self._neg_cdf[key] = (weight, weight._version, cdf)
-        return cdf
+        """The fp64 inclusive CDF of a node weight vector (:func:`_cached_cdf`)."""
+        return _cached_cdf(self._neg_cdf, weight, self.num_nodes, self.colptr.device)
 
     @torch.no_grad()
     def sample_padded(self, seeds: Tensor, seed: Optional[int] = None, padded_ids: bool = False,
@@ -949,10 +954,45 @@ class HeteroNeighborSampler:
     without times takes none of this.  With one node type and one edge type the temporal batch is
     :class:`NeighborSampler`'s ``node_time`` / ``edge_time`` batch bit for bit.
 
+    Link-level sampling (:meth:`sample_from_edges`; the reference's ``LinkNeighborLoader(
+    hetero_data, edge_label_index=((S, rel, D), eli))`` -> ``edge_sample``, heterogeneous branch,
+    sampler/neighbor_sampler.py:852-998).  For ``P`` seed links of the edge type ``(S, rel, D)``:
+
+    1. Negatives: ``num_neg = ceil(P * amount)``.  Binary draws ``num_neg`` sources in
+       ``[0, N_S)`` and ``num_neg`` destinations in ``[0, N_D)``, triplet destinations only; the
+       :class:`NegativeSampling` weights are per endpoint type (``src_weight`` ``[N_S]``,
+       ``dst_weight`` ``[N_D]``).  Under node-level time the draws of an endpoint are bounded by
+       the link's time (draw ``j`` by ``time[j % P]``) iff that endpoint's node type has an entry
+       in ``node_time`` (fallback: that type's earliest node); edge-level time never bounds them.
+    2. ``pygamd_hetero_link_seeds`` writes the whole seed block ``[src | src negatives | dst | dst
+       negatives]`` as global ids, and the seed time of every slot, in ONE launch; its negatives
+       are ``pygamd_sample_negatives``' for the seed ``rng * 2 + endpoint``.
+    3. ``S != D``: the seed dict is ``{S: src, D: dst}``.  Not disjoint: each made unique on its
+       own (``node[S]`` / ``node[D]`` start with the sorted unique seeds of their type) by ONE
+       ``pygamd_unique_inverse`` over the global ids, which are type-major; ONE host read gives
+       the number of distinct seeds and the split point between the two types.  Disjoint (no host
+       read for the seeds): the TREES ARE NUMBERED CONSECUTIVELY THROUGH THE SEED DICT IN ITS
+       ORDER: source seed ``j`` is tree ``j``, destination seed ``j`` tree ``n_src + j`` (``n_src
+       = P``, or ``P + num_neg`` for binary), and the seed time of a tree is the entry of
+       ``cat([src_time, dst_time])`` at that number.  ``S == D``: one merged seed vector
+       ``cat([src, dst])`` of that type, unique unless disjoint, as in :class:`NeighborSampler`.
+    4. The hops start from both blocks; ``batch[t] %= P`` for every node type (disjoint).  As in
+       the reference, the folded id names the tree's positive link only when ``n_src`` is a
+       multiple of ``P`` (triplet, or binary with an integer ``amount``); the time bound uses
+       the unfolded tree id and holds for every ``amount``.
+    5. ``metadata``: ``(input_id, edge_label_index, edge_label, src_time)`` without negatives or
+       with binary ones, ``(input_id, src_index, dst_pos_index, dst_neg_index, src_time)`` with
+       triplet ones (``dst_neg_index`` ``[P]`` for ``amount == 1``, else ``[P, amount]``).  Row 0
+       / ``src_index`` are local ids into ``node[S]``, row 1 / ``dst_*_index`` into ``node[D]``
+       (int64, device).  Disjoint with ``S != D``: both rows are ``arange(P + num_neg)``,
+       ``dst_pos_index = arange(P)`` and ``dst_neg_index`` starts at ``P``.
+    6. With one node type and one edge type the output is
+       :meth:`NeighborSampler.sample_from_edges`' for the same ``seed`` bit for bit.
+
     Out of scope, refused: edge weights (``edge_weight``, alone or with time), floating-point
-    times, ``subgraph_type`` ``'bidirectional'`` / ``'induced'``, link-level sampling, the
-    static-shape and hipGraph paths, ``sample_direction='backward'`` and ``(FeatureStore,
-    GraphStore)`` inputs."""
+    times, ``subgraph_type`` ``'bidirectional'`` / ``'induced'``, seed links without their edge
+    type, the static-shape and hipGraph paths, ``sample_direction='backward'`` and
+    ``(FeatureStore, GraphStore)`` inputs."""
 
 
     def __init__(self, edge_index_dict, num_nodes_dict, num_neighbors, seed: int = 0,
@@ -1041,6 +1081,9 @@ class HeteroNeighborSampler:
         self.output_cls = output_cls
         self._calls = 0
         self.time = None
+        # link-level sampling: the fp64 CDFs of negative-sampling weights (per tensor) and the
+        # temporal fallback node of every node type, both built on first use
+        self._neg_cdf, self._neg_fallback = {}, {}
         self._build_csc(eis, dt, dev, node_time, edge_time)
         self._unset = torch.iinfo(dt).min
         self._local = torch.full((max(nb[-1], 1), ), self._unset, dtype=dt, device=dev)
@@ -1242,10 +1285,164 @@ class HeteroNeighborSampler:
         seeds = seeds.to(device=self.colptr.device, dtype=self.colptr.dtype).contiguous()
         rng = self.seed + self._calls if seed is None else seed
         self._calls += 1
-        return self._hops(input_type, seeds, rng, seed_time)
+        return self._hops([(input_type, seeds)], rng, seed_time)
 
-    def sample_from_edges(self, *args, **kwargs):
-        raise NotImplementedError("heterogeneous link-level sampling is not supported")
+    @torch.no_grad()
+    def sample_from_edges(self, index, neg_sampling=None, seed: Optional[int] = None):
+        """Link-level sampling from seed links of ONE edge type, the heterogeneous branch of the
+        reference's ``edge_sample`` (sampler/neighbor_sampler.py:852-998).  ``index``:
+        ``(edge_type, [2, B] tensor)`` or an ``EdgeSamplerInput``-like object (``row``, ``col``,
+        ``label``, ``time``, ``input_id``, ``input_type`` = the edge type).  ``neg_sampling``:
+        :class:`NegativeSampling` or anything its ``cast`` takes; its weights are per endpoint
+        type.  See the class docstring for the seed blocks, the tree numbering and ``metadata``.
+        ``seed`` fixes the RNG like in :meth:`sample_from_nodes`; the negatives draw from a stream
+        of their own."""
+        if isinstance(index, Tensor):
+            raise NotImplementedError(
+                "heterogeneous link-level sampling needs the edge type of the seed links: pass "
+                "(edge_type, [2, B] tensor) or an EdgeSamplerInput with 'input_type'")
+        input_id = label = time = None
+        if isinstance(index, (tuple, list)):
+            if len(index) != 2:
+                raise ValueError("'index' must be (edge_type, [2, B] tensor)")
+            input_type, ei = index
+            if not isinstance(ei, Tensor) or ei.dim() != 2 or ei.size(0) != 2:
+                raise ValueError(f"the positive edges must be a [2, B] tensor (got "
+                                 f"{list(ei.shape) if isinstance(ei, Tensor) else type(ei)})")
+            src, dst = ei[0], ei[1]
+        else:
+            input_type = getattr(index, 'input_type', None)
+            if input_type is None:
+                raise NotImplementedError(
+                    "heterogeneous link-level sampling needs the edge type of the seed links "
+                    "('input_type' of the EdgeSamplerInput)")
+            src, dst = index.row, index.col
+            input_id = getattr(index, 'input_id', None)
+            label, time = getattr(index, 'label', None), getattr(index, 'time', None)
+        et = _edge_type(input_type)
+        if et not in self.edge_types:
+            raise ValueError(f"the input type '{et}' is not an edge type of the graph "
+                             f"({self.edge_types})")
+        s_t, d_t = et[0], et[2]
+        neg = NegativeSampling.cast(neg_sampling)
+        B = src.numel()
+        if dst.numel() != B or src.dim() != 1 or dst.dim() != 1:
+            raise ValueError('the source and destination of the positive edges must be 1-D '
+                             'tensors of one length')
+        if B == 0:
+            raise ValueError("'sample_from_edges' needs at least one positive edge")
+        if time is not None and not self.is_temporal:
+            raise ValueError("'edge_label_time' is given but the sampler is not temporal (no "
+                             "'node_time' / 'edge_time')")
+        if time is None and self.is_temporal:
+            raise ValueError("a temporal sampler needs the seed-link times ('edge_label_time')")
+        if neg is not None:
+            for w, t in ((neg.src_weight, s_t), (neg.dst_weight, d_t)):
+                if w is not None and w.numel() != self.num_nodes[t]:
+                    raise ValueError(f"The 'weight' attribute in 'NegativeSampling' needs to "
+                                     f"match the number of nodes {self.num_nodes[t]} of node "
+                                     f"type '{t}' (got {w.numel()})")
+            if neg.is_triplet() and label is not None:
+                raise ValueError("'edge_label' needs to be undefined for 'triplet'-based negative "
+                                 "sampling")
+        if label is not None and label.size(0) != B:
+            raise ValueError(f"'edge_label' needs one entry per positive edge ({B})")
+        self.check_seeds(s_t, src)
+        self.check_seeds(d_t, dst)
+        dev, dt = self.colptr.device, self.colptr.dtype
+        src = src.to(device=dev, dtype=dt)
+        dst = dst.to(device=dev, dtype=dt)
+        if time is not None:
+            time = self.seed_time(s_t, src, time)  # int64 [B] on the device
+        if label is not None:
+            label = label.to(dev)
+        rng = self.seed + self._calls if seed is None else seed
+        self._calls += 1
+        # the seed block, ONE launch: [src | src negatives | dst | dst negatives] as global ids,
+        # and the seed time of every slot
+        mode, num_neg = None, 0
+        if neg is not None:
+            mode, num_neg = neg.mode, math.ceil(B * neg.amount)
+        binary = mode == 'binary'
+        ends = [self._link_endpoint(s_t, neg.src_weight if binary else None, binary),
+                self._link_endpoint(d_t, neg.dst_weight if neg is not None else None,
+                                    neg is not None)]
+        g_seeds, seed_time = _native.hetero_link_seeds(src, dst, num_neg, mode, rng, ends,
+                                                       link_time=time)
+        n_src = B + (num_neg if binary else 0)
+        src_time = None if time is None else seed_time[:n_src]
+        if binary:
+            if label is None:
+                label = torch.ones(B, device=dev)
+            label = torch.cat([label, label.new_zeros((num_neg, ) + label.shape[1:])])
+        si, di = self._type_index[s_t], self._type_index[d_t]
+        inv_src = inv_dst = None
+        if si == di:    # one node type: the merged seed vector cat([src, dst])
+            seeds = g_seeds - self.node_base[si] if self.node_base[si] else g_seeds
+            if not self.disjoint:
+                seeds, inverse = _native.unique_inverse(
+                    seeds, max_value=max(self.num_nodes[s_t] - 1, 0))
+                inv_src, inv_dst = inverse[:n_src], inverse[n_src:]
+            blocks = [(s_t, seeds)]
+        elif self.disjoint:
+            blocks = [(s_t, g_seeds[:n_src] - self.node_base[si]),
+                      (d_t, g_seeds[n_src:] - self.node_base[di])]
+        else:
+            # ONE unique over the global ids: they are type-major, so the sorted unique holds the
+            # sorted unique seeds of the type with the lower index, then the other type's; ONE
+            # host read gives the number of distinct seeds and the split point between the two
+            lo_i, hi_i = min(si, di), max(si, di)
+            uniq, inverse, n_u = _native.unique_inverse(
+                g_seeds, max_value=max(self.node_base[-1] - 1, 0), count_on_device=True)
+            pos = torch.arange(uniq.numel(), device=dev)
+            n_lo = ((uniq < self.node_base[hi_i]) & (pos < n_u)).sum().view(1)
+            n_uniq, n_first = torch.cat([n_u, n_lo]).tolist()
+            first = uniq[:n_first] - self.node_base[lo_i]
+            second = uniq[n_first:n_uniq] - self.node_base[hi_i]
+            inv_src, inv_dst = inverse[:n_src], inverse[n_src:]
+            if si < di:
+                inv_dst = inv_dst - n_first
+                blocks = [(s_t, first), (d_t, second)]
+            else:
+                inv_src = inv_src - n_first
+                blocks = [(s_t, second), (d_t, first)]
+        out = self._hops(blocks, rng, seed_time)
+        n_dst = g_seeds.numel() - n_src
+        if self.disjoint:
+            out.batch = {t: b % B for t, b in out.batch.items()}
+            # local ids are seed positions: of node[S] / node[D] for two node types, of the
+            # merged vector (destinations after the n_src sources) for one
+            inv_src = torch.arange(n_src, device=dev)
+            inv_dst = torch.arange(n_dst, device=dev) + (n_src if si == di else 0)
+        if neg is None or binary:
+            out.metadata = (input_id, torch.stack([inv_src, inv_dst]), label, src_time)
+        else:
+            dst_neg_index = inv_dst[B:]
+            if self.disjoint:
+                dst_neg_index = dst_neg_index.view(-1, B).t()
+            dst_neg_index = dst_neg_index.reshape(B, -1).squeeze(-1)
+            out.metadata = (input_id, inv_src, inv_dst[:B], dst_neg_index, src_time)
+        return out
+
+    def _link_endpoint(self, node_type: str, weight: Optional[Tensor], draws: bool) -> dict:
+        """The per-endpoint table of ``pygamd_hetero_link_seeds``.  For an endpoint that draws
+        negatives: the cached fp64 CDF of its weights, and, under node-level time, the type's
+        slice of the time vector with its fallback ``node_time[t].argmin()`` (one host read per
+        node type, once) iff the type has an entry in ``node_time``."""
+        ti = self._type_index[node_type]
+        n, base = self.num_nodes[node_type], self.node_base[ti]
+        ep = {'num_nodes': n, 'node_base': base}
+        if not draws:
+            return ep
+        if weight is not None:
+            ep['cdf'] = _cached_cdf(self._neg_cdf, weight, n, self.colptr.device)
+        if self.is_temporal and not self.edge_level and node_type in self.timed_node_types \
+                and n > 0:
+            ep['node_time'] = self.time[base:base + n]
+            if node_type not in self._neg_fallback:
+                self._neg_fallback[node_type] = int(torch.argmin(ep['node_time']))
+            ep['fallback'] = self._neg_fallback[node_type]
+        return ep
 
     def sample_padded(self, *args, **kwargs):
         raise NotImplementedError("the static-shape paths (sample_padded, collate_padded, "
@@ -1266,40 +1463,64 @@ class HeteroNeighborSampler:
             return n_items * k if d > 0 else 0
         return n_items * min(k, d)
 
-    def _hops(self, input_type: str, seeds: Tensor, rng: int,
-              seed_time: Optional[Tensor] = None):
-        """The hop loop.  ``seed_time`` (int64 [B], a temporal sampler): the counts launch becomes
-        the typed window, bounded by the seed time of every frontier node's tree, and the draw runs
-        on the windows."""
+    def _hops(self, blocks, rng: int, seed_time: Optional[Tensor] = None):
+        """The hop loop from typed seed blocks.  ``blocks``: ``[(node type, seeds)]`` (typed local
+        ids, device, graph dtype) of distinct node types in seed-dict order: one block for
+        :meth:`sample_from_nodes`, the source and the destination block for seed links between
+        two node types.  ``node[t]`` starts with type ``t``'s block.  The frontier buffer is
+        type-major by node-type index whatever the order of the blocks; ``disjoint``: the trees
+        are numbered consecutively through the blocks in THEIR order (seed ``j`` of the second
+        block is tree ``len(first block) + j``).  ``seed_time`` (int64, one per tree, a temporal
+        sampler): the counts launch becomes the typed window, bounded by the seed time of every
+        frontier node's tree, and the draw runs on the windows."""
         dev, dt = self.colptr.device, self.colptr.dtype
         T, ET = len(self.node_types), len(self.edge_types)
-        tin = self._type_index[input_type]
-        B = seeds.numel()
+        tis = [self._type_index[t] for t, _ in blocks]
+        assert len(set(tis)) == len(tis), 'one seed block per node type'
+        B = sum(sd.numel() for _, sd in blocks)     # seeds = trees of a disjoint batch
         S = self.node_base[-1]
-        g_seeds = seeds + self.node_base[tin]
         count = [0] * T               # nodes of every type in the batch so far
-        count[tin] = B
         block_off, block_n = [0] * T, [0] * T  # the frontier's type-major blocks
-        block_n[tin] = B
         prev = [0] * T                # typed local id of every frontier block's first node
         nodes = [[] for _ in range(T)]
-        nodes[tin].append(seeds)
         trees = [[] for _ in range(T)]
         rows, cols, edges = ([[] for _ in range(ET)] for _ in range(3))
-        n_nodes = [[B if t == tin else 0] for t in range(T)]
+        n_nodes = [[0] for _ in range(T)]
         n_edges = [[] for _ in range(ET)]
-        frontier = g_seeds
+        if self.disjoint and B * max(S, 1) >= 2 ** 62:
+            raise ValueError('disjoint sampling: batch size x num_nodes overflows the pair key')
+        tree0, acc = [], 0            # first tree id of every block
+        for _, sd in blocks:
+            tree0.append(acc)
+            acc += sd.numel()
+        front, ftrees, typed0, off = [], [], [], 0
+        for b in sorted(range(len(blocks)), key=lambda b: tis[b]):
+            tin, sd = tis[b], blocks[b][1]
+            n = sd.numel()
+            count[tin] = block_n[tin] = n_nodes[tin][0] = n
+            block_off[tin] = off
+            off += n
+            nodes[tin].append(sd)
+            front.append(sd + self.node_base[tin])
+            if self.disjoint:
+                tree = torch.arange(tree0[b], tree0[b] + n, device=dev)
+                trees[tin].append(tree)
+                ftrees.append(tree)
+                typed0.append(torch.arange(n, dtype=dt, device=dev))
+            else:
+                self._local[front[-1]] = torch.arange(n, dtype=dt, device=dev)
+
+        def cat(xs):
+            return torch.cat(xs) if len(xs) > 1 else (xs[0] if xs else
+                                                     torch.empty(0, dtype=dt, device=dev))
+        frontier = cat(front)
         if self.disjoint:
-            if B * max(S, 1) >= 2 ** 62:
-                raise ValueError('disjoint sampling: batch size x num_nodes overflows the pair key')
-            trees[tin].append(torch.arange(B, device=dev))
-            keys_all = torch.arange(B, device=dev) * S + g_seeds.long()
-            pos2typed = torch.arange(B, dtype=dt, device=dev)
-            ftree, n_front = torch.arange(B, device=dev), B
+            ftree, n_front = cat(ftrees), B
+            keys_all = ftree * S + frontier.long()
+            pos2typed = cat(typed0)
         else:
             local = self._local
-            local[g_seeds] = torch.arange(B, dtype=dt, device=dev)
-            touched = [g_seeds]
+            touched = [frontier]
         for hop in range(self.num_hops):
             item_begin, table, cap, unbounded = [0], [], 0, False
             for e, et in enumerate(self.edge_types):
@@ -1392,9 +1613,6 @@ class HeteroNeighborSampler:
         if not self.disjoint:
             local[torch.cat(touched)] = self._unset_t  # leave the map clean for the next batch
 
-        def cat(xs):
-            return torch.cat(xs) if len(xs) > 1 else (xs[0] if xs else
-                                                     torch.empty(0, dtype=dt, device=dev))
         nt, ets = self.node_types, self.edge_types
         out = self.output_cls(
             node={t: cat(nodes[i]) for i, t in enumerate(nt)},
