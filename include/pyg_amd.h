@@ -862,6 +862,48 @@ PYGAMD_API int pygamd_hetero_sample_neighbors_temporal(const void* row, const vo
                                                        void* col_out, void* edge_out,
                                                        void* fpos_out, void* stream);
 
+/* ---- heterogeneous layers: every edge type of a HeteroConv in one aggregation --------------------
+ * Replaces the aggregation half of the reference's per-edge-type loop, nn/conv/hetero_conv.py:
+ * 117-167 calling nn/conv/sage_conv.py:118-152 once per edge type (one propagate each, and one
+ * more each in the backward): csrc/hetero_conv.hip.
+ * All edge types share ONE stacked CSR in idx_dtype: row row_begin[et] + i is the neighbourhood of
+ * destination i under edge type et (row_begin: host int64 [n_et + 1], row_begin[0] = 0; rows are
+ * dense, an empty neighbourhood is an empty row), rowptr is [row_begin[n_et] + 1] and col holds the
+ * typed local source id of every slot.  The per-edge-type operands travel in the kernel arguments
+ * (n_et <= 64), so ONE launch serves a layer whatever the number of edge types.
+ * pygamd_hetero_spmm: out[et][i, :F] = sum (or mean: the sum / max(deg, 1)) over the row's slots of
+ *   x[et][col[slot], :F].  x / out: host arrays [n_et] of device pointers (the source matrix of the
+ *   edge type's source node type; row 0 of the edge type's output block, which may be a column
+ *   block of a wider matrix); et_table: host int64 [n_et][4] = ldx, n_src, mean (0 / 1), ldo.  The
+ *   lane shape is the one pygamd_spmm_csr picks for (F, the least aligned operand of the table),
+ *   slot order and mean epilogue are that kernel's: equal shapes give equal bits.  A source id
+ *   outside [0, n_src) sets *err_flag (device int32, optional) to 1 and reads row 0 (nothing when
+ *   n_src = 0).  Rows of any degree are walked by one wave (no two-stage hub path).
+ * pygamd_hetero_spmm_backward: the gradient of every source matrix in one launch, one wave per
+ *   stacked source node and no atomics.  Node j of source node type t is the stacked node
+ *   src_begin[t] + j (src_begin: host int64 [n_nt + 1], n_nt <= 64); rowptr_t [src_begin[n_nt] + 1]
+ *   / col_t are the transposed structure: the slots of a stacked node name stacked (et, i) rows, in
+ *   the order their contributions are added.  grad_x[t][j, :F] = sum over the slots r of
+ *   grad[et(r)][r - row_begin[et(r)], :F] (for a mean edge type divided by max(deg(r), 1), deg from
+ *   the forward rowptr); nodes without slots get zeros.  grad / grad_x: host arrays of device
+ *   pointers ([n_et] / [n_nt]); et_table: host int64 [n_et][2] = ldg, mean; ld_grad_x: host int64
+ *   [n_nt].
+ * Rejected before any launch: n_et or n_nt above 64 -> PYGAMD_ERR_UNSUPPORTED; n_et / n_nt <= 0, a
+ * block table that does not start at 0 or decreases, F < 0, a leading dimension below F or above
+ * INT32_MAX, n_src < 0, a mean flag other than 0 / 1, an unknown idx_dtype or a NULL pointer the
+ * call needs -> PYGAMD_ERR_INVALID_ARG.  No rows or F = 0 launches nothing.                      */
+PYGAMD_API int pygamd_hetero_spmm(const void* rowptr, const void* col, int idx_dtype,
+                                  const int64_t* row_begin, const float* const* x,
+                                  float* const* out, const int64_t* et_table, int n_et, int64_t F,
+                                  int32_t* err_flag, void* stream);
+PYGAMD_API int pygamd_hetero_spmm_backward(const void* rowptr_t, const void* col_t,
+                                           const void* rowptr, int idx_dtype,
+                                           const int64_t* row_begin, const float* const* grad,
+                                           const int64_t* et_table, int n_et,
+                                           const int64_t* src_begin, float* const* grad_x,
+                                           const int64_t* ld_grad_x, int n_nt, int64_t F,
+                                           void* stream);
+
 /* ---- a18: one-pass multi-reduce (FusedAggregation) ---------------------------------------------
  * nn/aggr/fused.py:191-336 shares the group count, the sum and the sum of squares between
  * sum / mean / var / std / min / max.  Here ONE read of the rows produces all requested statistics

@@ -171,6 +171,9 @@ SIGNATURES = {
                                                c_int, _P, _P, _P, _P, _P]),
     'pygamd_hetero_split': (c_int, [c_int, _P, c_int, c_int64, _P, _P, _P, c_int, _P, _P, _P,
                                     c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'pygamd_hetero_spmm': (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P, _P]),
+    'pygamd_hetero_spmm_backward': (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, _P,
+                                            c_int, c_int64, _P]),
     'pygamd_hetero_sample_temporal_window': (c_int, [_P, _P, c_int, _P, c_int, _P, _P, _P, _P,
                                                      c_int, c_uint64, c_int, c_int, _P, _P, _P,
                                                      _P]),

@@ -727,18 +727,20 @@ class _FlagRing:
             self.poll()
         return slot
 
-    def publish(self, slot: int, what: str, size: int, index: Tensor, on_flag=None):
+    def publish(self, slot: int, what: str, size: int, index: Tensor, on_flag=None, report=None):
         """``on_flag``: called (before the error is raised) when this launch turns out flagged —
         lets the owner of a CACHED object built from ``index`` (a sorted-scatter plan) remember
-        it, so that later uses of the cache report the same indices again."""
+        it, so that later uses of the cache report the same indices again.  ``report``: raises
+        the error of a flagged launch in place of the ``[0, size)`` report over ``index`` (a
+        launch whose indices have no single bound: :func:`hetero_spmm`)."""
         self.host[slot:slot + 1].copy_(self.dev[slot:slot + 1], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.dev.device))
-        self.pending.append((slot, ev, what, size, index, _error_style.value, on_flag))
+        self.pending.append((slot, ev, what, size, index, _error_style.value, on_flag, report))
 
     def poll(self, wait: bool = False):
         while self.pending:
-            slot, ev, what, size, index, style, on_flag = self.pending[0]
+            slot, ev, what, size, index, style, on_flag, report = self.pending[0]
             if wait:
                 ev.synchronize()
             elif not ev.query():
@@ -749,6 +751,8 @@ class _FlagRing:
                 self.dev[slot:slot + 1].zero_()
                 if on_flag is not None:
                     on_flag()
+                if report is not None:
+                    report()
                 _raise_out_of_range(index, size, what, style)
 
 
@@ -2205,3 +2209,122 @@ def run_flags(key_sorted: Tensor) -> Tensor:
     check(lib.pygamd_run_flags(_p(key_sorted), key_sorted.numel(), _p(flag),
                                _stream(key_sorted)), 'run_flags')
     return flag
+
+
+# ---- heterogeneous layers: every edge type of a HeteroConv in one aggregation ------------------------
+MAX_HETERO_TYPES = 64
+
+
+def _ptr_host(tensors):
+    """A host array of device pointers (NULL for None / empty tensors)."""
+    vals = [None if (t is None or t.numel() == 0) else t.data_ptr() for t in tensors]
+    return (ctypes.c_void_p * max(len(vals), 1))(*vals)
+
+
+def _hetero_block(t: Tensor, name: str, F: int) -> Tensor:
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.size(1) == F
+            and (F <= 1 or t.stride(1) == 1) and (t.size(0) <= 1 or t.stride(0) >= F)):
+        raise ValueError(f"'{name}' must hold float32 HIP row blocks [n, {F}] with unit inner "
+                         f"stride")
+    return t
+
+
+def hetero_spmm(rowptr: Tensor, col: Tensor, row_begin, xs, outs, means,
+                check_bounds: bool = False) -> None:
+    """``pygamd_hetero_spmm``: ``outs[et][i] = sum | mean`` of ``xs[et][col[slot]]`` over the slots
+    of the stacked row ``row_begin[et] + i`` — every edge type in one launch.  ``row_begin``: host
+    ints ``[n_et + 1]``; ``xs[et]``: the ``[n_src, F]`` float32 source matrix of edge type ``et``
+    (row-strided views are fine); ``outs[et]``: its ``[rows, F]`` output block, written in place
+    (e.g. a column block of a wider matrix); ``means[et]``: mean instead of sum.
+    ``check_bounds``: report a source id outside its matrix as ``INDEX_CHECK`` says (the kernel
+    reads row 0 for it in every mode); callers that range-checked ``col`` leave it off."""
+    _require_device(rowptr, col, *xs, *outs)
+    n_et = len(xs)
+    if not (len(outs) == len(means) == n_et and len(row_begin) == n_et + 1):
+        raise ValueError("'row_begin', 'xs', 'outs' and 'means' disagree about the edge types")
+    if n_et > MAX_HETERO_TYPES:
+        raise PygAmdError(f'hetero_spmm failed: at most {MAX_HETERO_TYPES} edge types per launch '
+                          f'(got {n_et})')
+    if col.dtype != rowptr.dtype or rowptr.dim() != 1 or col.dim() != 1:
+        raise ValueError("'rowptr' and 'col' must be one-dimensional and of one index dtype")
+    if n_et == 0:
+        return
+    F = xs[0].size(1) if xs[0].dim() == 2 else -1
+    n_rows = int(row_begin[-1])
+    if rowptr.numel() != n_rows + 1:
+        raise ValueError(f"'rowptr' must have {n_rows + 1} entries (got {rowptr.numel()})")
+    table = []
+    for et in range(n_et):
+        x, o = _hetero_block(xs[et], 'xs', F), _hetero_block(outs[et], 'outs', F)
+        rows = int(row_begin[et + 1]) - int(row_begin[et])
+        if o.size(0) != rows:
+            raise ValueError(f"'outs[{et}]' must have {rows} rows (got {o.size(0)})")
+        table += [_ld(x), x.size(0), int(bool(means[et])), _ld(o)]
+    rowptr, col = rowptr.contiguous(), col.contiguous()
+    active = check_bounds and n_rows > 0 and F > 0 and col.numel() > 0
+    ring, slot, err = _index_flag(rowptr.device, active)
+    check(_lib.load().pygamd_hetero_spmm(
+        _p(rowptr), _p(col), _idx_dtype(rowptr), _i64_host([int(v) for v in row_begin]),
+        _ptr_host(xs), _ptr_host(outs), _i64_host(table), n_et, F, _p(err), _stream(rowptr)),
+        'hetero_spmm')
+    if active:
+        _hetero_flag_done(ring, slot, err)
+
+
+def _raise_hetero_out_of_range():
+    raise IndexOutOfRange("hetero_spmm: 'col' holds a source id outside [0, n_src) of its edge "
+                          "type's source matrix (the kernel read row 0 for it)")
+
+
+def _hetero_flag_done(ring, slot, err):
+    """:func:`_index_flag_done` for :func:`hetero_spmm`: same delivery (async ring / blocking
+    read), its own report."""
+    if ring is not None:
+        ring.publish(slot, 'hetero_spmm', 0, None, report=_raise_hetero_out_of_range)
+    elif err is not None and INDEX_CHECK == 'sync' \
+            and not torch.cuda.is_current_stream_capturing() and int(err.item()) != 0:
+        _raise_hetero_out_of_range()
+
+
+def hetero_spmm_backward(rowptr_t: Tensor, col_t: Tensor, rowptr: Tensor, row_begin, grads,
+                         means, src_begin, grad_xs) -> None:
+    """``pygamd_hetero_spmm_backward``: the input gradients of :func:`hetero_spmm` for every source
+    node type in one launch, without atomics.  ``rowptr_t`` / ``col_t``: the transposed structure
+    over the stacked source nodes (``src_begin``: host ints ``[n_nt + 1]``), whose slots name
+    stacked rows; ``grads[et]``: the ``[rows, F]`` gradient of edge type ``et``'s output block;
+    ``grad_xs[t]``: the ``[n, F]`` gradient of source node type ``t``, overwritten."""
+    _require_device(rowptr_t, col_t, rowptr, *grads, *grad_xs)
+    n_et, n_nt = len(grads), len(grad_xs)
+    if not (len(means) == n_et and len(row_begin) == n_et + 1 and len(src_begin) == n_nt + 1):
+        raise ValueError("'row_begin', 'grads', 'means', 'src_begin' and 'grad_xs' disagree about "
+                         "the types")
+    if n_et > MAX_HETERO_TYPES or n_nt > MAX_HETERO_TYPES:
+        raise PygAmdError(f'hetero_spmm_backward failed: at most {MAX_HETERO_TYPES} edge types and '
+                          f'node types per launch (got {n_et}, {n_nt})')
+    if not (rowptr_t.dtype == col_t.dtype == rowptr.dtype):
+        raise ValueError('the index tensors must share one dtype')
+    if n_et == 0 or n_nt == 0:
+        return
+    F = grads[0].size(1) if grads[0].dim() == 2 else -1
+    n_rows, n_src = int(row_begin[-1]), int(src_begin[-1])
+    if rowptr.numel() != n_rows + 1 or rowptr_t.numel() != n_src + 1:
+        raise ValueError(f"'rowptr' / 'rowptr_t' must have {n_rows + 1} / {n_src + 1} entries")
+    table = []
+    for et in range(n_et):
+        g = _hetero_block(grads[et], 'grads', F)
+        rows = int(row_begin[et + 1]) - int(row_begin[et])
+        if g.size(0) != rows:
+            raise ValueError(f"'grads[{et}]' must have {rows} rows (got {g.size(0)})")
+        table += [_ld(g), int(bool(means[et]))]
+    lds = []
+    for t in range(n_nt):
+        gx = _hetero_block(grad_xs[t], 'grad_xs', F)
+        rows = int(src_begin[t + 1]) - int(src_begin[t])
+        if gx.size(0) != rows:
+            raise ValueError(f"'grad_xs[{t}]' must have {rows} rows (got {gx.size(0)})")
+        lds.append(_ld(gx))
+    check(_lib.load().pygamd_hetero_spmm_backward(
+        _p(rowptr_t.contiguous()), _p(col_t.contiguous()), _p(rowptr.contiguous()),
+        _idx_dtype(rowptr), _i64_host([int(v) for v in row_begin]), _ptr_host(grads),
+        _i64_host(table), n_et, _i64_host([int(v) for v in src_begin]), _ptr_host(grad_xs),
+        _i64_host(lds), n_nt, F, _stream(rowptr)), 'hetero_spmm_backward')

@@ -1289,27 +1289,13 @@ static SpmmDev<IdxT> make_dev(const pygamd_spmm_args* p) {
   return a;
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-struct Shape {
-  int vw, lpr, ch;
-  unsigned tiles;
-};
-
+// (Shape, spmm_shape and aligned16: spmm_device.h, shared with hetero_conv.hip)
 static Shape pick_shape(const pygamd_spmm_args* p) {
-  Shape s;
   const bool v4 = (p->F % 4 == 0) && (p->ldx % 4 == 0) && (p->ldo % 4 == 0) &&
                   aligned16(p->x) && aligned16(p->out) &&
                   (!p->relu_mask || (p->ld_mask % 4 == 0 && aligned16(p->relu_mask))) &&
                   (p->w_heads <= 1 || p->head_dim % 4 == 0);
-  s.vw = v4 ? 4 : 1;
-  const int64_t units = ceil_div(p->F, s.vw);  // lanes needed to cover a row once
-  int lpr = 4;
-  while (lpr < 64 && lpr < units) lpr <<= 1;
-  s.lpr = lpr;
-  s.ch = (lpr == 64 && units > 64) ? 2 : 1;
-  s.tiles = static_cast<unsigned>(ceil_div(units, static_cast<int64_t>(s.lpr) * s.ch));
-  return s;
+  return spmm_shape(p->F, v4);
 }
 
 template <typename IdxT, int VW, int LPR, int CH, int WMODE, bool IDENT>

@@ -214,11 +214,14 @@ __device__ __forceinline__ void spmm_batch_zrows(const SpmmDev<IdxT>& a, int j, 
 
 // UF > 0 overrides the number of row loads in flight per lane (a kernel with few resident waves
 // needs more memory-level parallelism per wave)
-template <typename IdxT, int VW, int LPR, int CH, int WMODE, bool IDENT, int UF = 0>
+// GUARD: a column id outside [0, a.n_src) reads row 0 instead and sets *bad (a per-lane flag of
+// the caller; the convention of pygamd_gather_rows) — for callers whose ids nobody vouches for.
+template <typename IdxT, int VW, int LPR, int CH, int WMODE, bool IDENT, int UF = 0,
+          bool GUARD = false>
 __device__ __forceinline__ void spmm_accumulate(const SpmmDev<IdxT>& a, IdxT start, IdxT end,
                                                 int lane, const int (&fo)[CH],
                                                 const bool (&fv)[CH], const int (&head)[CH],
-                                                float (&acc)[CH][VW]) {
+                                                float (&acc)[CH][VW], bool* bad = nullptr) {
   constexpr int EPI = kWave / LPR;
   constexpr int U = UF > 0 ? UF : spmm_unroll<LPR, CH>();
   constexpr int STEP = EPI * U;
@@ -238,6 +241,12 @@ __device__ __forceinline__ void spmm_accumulate(const SpmmDev<IdxT>& a, IdxT sta
         myc = k;
       } else {
         myc = __builtin_nontemporal_load(&a.col[k]);  // streamed once: keep L2 for feature rows
+      }
+      if constexpr (GUARD) {
+        if (myc < 0 || static_cast<int64_t>(myc) >= a.n_src) {
+          myc = 0;
+          *bad = true;
+        }
       }
       if constexpr (WMODE == 1 || WMODE == 2) {
         mye = a.eid ? a.eid[k] : k;
@@ -277,6 +286,27 @@ __device__ __forceinline__ void spmm_accumulate(const SpmmDev<IdxT>& a, IdxT sta
     }
   }
 }
+
+// The lane shape of a row kernel: LPR lanes x CH chunks of VW floats cover a row of F floats
+// (`tiles` times over when F > 512 floats); v4 = every row start is 16-byte aligned and F % 4 == 0.
+struct Shape {
+  int vw, lpr, ch;
+  unsigned tiles;
+};
+
+inline Shape spmm_shape(int64_t F, bool v4) {
+  Shape s;
+  s.vw = v4 ? 4 : 1;
+  const int64_t units = ceil_div(F, s.vw);  // lanes needed to cover a row once
+  int lpr = 4;
+  while (lpr < 64 && lpr < units) lpr <<= 1;
+  s.lpr = lpr;
+  s.ch = (lpr == 64 && units > 64) ? 2 : 1;
+  s.tiles = static_cast<unsigned>(ceil_div(units, static_cast<int64_t>(s.lpr) * s.ch));
+  return s;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <int VW, int LPR, int CH>
 __device__ __forceinline__ void feature_slots(int lane, int64_t F, int head_dim, int (&fo)[CH],

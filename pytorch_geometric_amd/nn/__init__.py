@@ -1,9 +1,9 @@
 from .aggr import (Aggregation, FusedAggregation, MaxAggregation, MeanAggregation,
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
-from .conv import (FastRGCNConv, GATConv, GCNConv, GraphConv, MessagePassing, RGCNConv, SAGEConv,
-                   gcn_norm)
-from .dense import HeteroLinear, Linear
+from .conv import (FastRGCNConv, GATConv, GCNConv, GraphConv, HeteroConv, MessagePassing,
+                   RGCNConv, SAGEConv, gcn_norm, group)
+from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, GraphSAGE
 from . import functional  # noqa: F401
 
@@ -11,5 +11,6 @@ __all__ = [
     'Aggregation', 'SumAggregation', 'MeanAggregation', 'MaxAggregation', 'MinAggregation',
     'MulAggregation', 'VarAggregation', 'StdAggregation', 'FusedAggregation',
     'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
+    'HeteroDictLinear', 'HeteroConv', 'group',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

@@ -4,6 +4,7 @@ from .gcn_conv import GCNConv, gcn_norm
 from .gat_conv import GATConv
 from .rgcn_conv import FastRGCNConv, RGCNConv
 from .graph_conv import GraphConv
+from .hetero_conv import HeteroConv, group
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'RGCNConv', 'FastRGCNConv',
-           'GraphConv']
+           'GraphConv', 'HeteroConv', 'group']

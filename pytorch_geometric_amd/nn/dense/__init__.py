@@ -1,1 +1,1 @@
-from .linear import HeteroLinear, Linear
+from .linear import HeteroDictLinear, HeteroLinear, Linear

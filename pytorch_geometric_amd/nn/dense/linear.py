@@ -1,5 +1,5 @@
 import math
-from typing import Optional
+from typing import Any, Dict, Optional, Union
 
 import torch
 import torch.nn.functional as F
@@ -151,3 +151,47 @@ class HeteroLinear(torch.nn.Module):
     def __repr__(self) -> str:
         return (f'{self.__class__.__name__}({self.in_channels}, {self.out_channels}, '
                 f'num_types={self.num_types}, bias={self.bias is not None})')
+
+
+class HeteroDictLinear(torch.nn.Module):
+    r"""One :class:`Linear` per key of the input dictionary: ``out[k] = x[k] @ W_k.T + b_k`` —
+    the interface and the parameter names (``lins.<type>.weight`` / ``lins.<type>.bias``) of
+    ``torch_geometric.nn.HeteroDictLinear`` (torch_geometric/nn/dense/linear.py:347-470), with
+    explicit input sizes only.  It is what brings raw per-type feature widths to the one hidden
+    width that the typed layers (:class:`~pytorch_geometric_amd.nn.HeteroConv`) aggregate in one
+    launch.  ``in_channels``: one width for all ``types``, or ``{type: width}``; ``**kwargs`` go to
+    every :class:`Linear`.  Type names may contain dots (``..module_dict.ModuleDict``)."""
+
+    def __init__(self, in_channels: Union[int, Dict[Any, int]], out_channels: int,
+                 types: Optional[Any] = None, **kwargs):
+        super().__init__()
+        from ..module_dict import ModuleDict
+        if isinstance(in_channels, dict):
+            widths = dict(in_channels)
+            if types is not None and set(types) != set(widths):
+                raise ValueError(f"'types' {sorted(map(str, types))} are not the keys of "
+                                 f"'in_channels' {sorted(map(str, widths))}")
+        elif types is None:
+            raise ValueError("an integer 'in_channels' needs the list of 'types' it holds for")
+        else:
+            widths = {t: in_channels for t in types}
+        lazy = [t for t, width in widths.items() if width <= 0]
+        if lazy:
+            raise ValueError(f"lazy initialisation (in_channels=-1) is not supported "
+                             f"(types {lazy})")
+        self.types = list(widths)
+        self.in_channels, self.out_channels, self.kwargs = widths, out_channels, kwargs
+        self.lins = ModuleDict({t: Linear(width, out_channels, **kwargs)
+                                for t, width in widths.items()})
+
+    def reset_parameters(self):
+        for lin in self.lins.values():
+            lin.reset_parameters()
+
+    def forward(self, x_dict: Dict[Any, Tensor]) -> Dict[Any, Tensor]:
+        """The transformed entries of ``x_dict``, over the types present in it."""
+        return {t: lin(x_dict[t]) for t, lin in self.lins.items() if t in x_dict}
+
+    def __repr__(self) -> str:
+        return (f'{type(self).__name__}(in_channels={self.in_channels}, '
+                f'out_channels={self.out_channels}, bias={self.kwargs.get("bias", True)})')
