@@ -1624,7 +1624,8 @@ def segment_matmul_wgrad(x: Tensor, g: Tensor, plan, n_seg: int, blocks: int = 1
 def sample_neighbors(colptr: Tensor, row: Tensor, frontier: Tensor, offsets: Tensor, total: int,
                      max_per_node: int, seed: int, zero_fill: bool = False,
                      replace: bool = False, salt_position: bool = False,
-                     seed_dev: Optional[Tensor] = None, weight: Optional[Tensor] = None):
+                     seed_dev: Optional[Tensor] = None, weight: Optional[Tensor] = None,
+                     window: Optional[Tuple[Tensor, Tensor]] = None):
     """(src_global, dst_pos_in_frontier, csc_slot) for the sampled in-edges of `frontier`.
     ``total`` sizes the outputs; ``zero_fill`` for a static capacity larger than what the hop
     really samples (the tail then holds 0 = a valid node / slot id).  ``replace``: draws with
@@ -1633,30 +1634,36 @@ def sample_neighbors(colptr: Tensor, row: Tensor, frontier: Tensor, offsets: Ten
     node in two trees draws independently).  ``seed_dev`` (int64 [1] on the device) is added to
     ``seed`` on the device (a captured graph bumps it between replays).  ``weight`` (fp32 [E] in
     CSC slot order, finite, >= 0): draws in proportion to edge weight
-    (``pygamd_sample_neighbors_weighted``)."""
-    _require_device(colptr, row, frontier, offsets, weight)
+    (``pygamd_sample_neighbors_weighted``).  ``window``: the ``(lo, hi)`` of
+    :func:`sample_temporal_window`; the same draws on the slots ``[lo, hi)`` in place of the
+    node's column (``pygamd_sample_neighbors_temporal``), so a window that is the whole column
+    gives the column's edges bit for bit."""
+    _require_device(colptr, row, frontier, offsets, weight, *(window or ()))
     if weight is not None and (weight.dtype != torch.float32 or not weight.is_contiguous()
                                or weight.numel() != row.numel()):
         raise ValueError("'weight' must be a contiguous float32 tensor with one entry per edge")
+    if weight is not None and window is not None:
+        raise ValueError("weighted draws on a window are not supported")
     lib = _lib.load()
     alloc = torch.zeros if zero_fill else torch.empty
     src = alloc(total, dtype=colptr.dtype, device=colptr.device)
     dstpos = alloc(total, dtype=colptr.dtype, device=colptr.device)
     slot = alloc(total, dtype=colptr.dtype, device=colptr.device)
+    # the arguments every draw entry point ends with
+    tail = (_p(offsets), max_per_node, seed & 0xFFFFFFFFFFFFFFFF,
+            int(replace) | (2 if salt_position else 0), _p(seed_dev), _p(src), _p(dstpos),
+            _p(slot), _stream(colptr))
     if total > 0 and weight is not None:
         check(lib.pygamd_sample_neighbors_weighted(
             _p(colptr), _p(row), _idx_dtype(colptr), _p(weight), _p(frontier), frontier.numel(),
-            _p(offsets), max_per_node, seed & 0xFFFFFFFFFFFFFFFF,
-            int(replace) | (2 if salt_position else 0), _p(seed_dev), _p(src), _p(dstpos),
-            _p(slot), _stream(colptr)), 'sample_neighbors_weighted')
+            *tail), 'sample_neighbors_weighted')
+    elif total > 0 and window is not None:
+        check(lib.pygamd_sample_neighbors_temporal(
+            _p(row), _idx_dtype(row), _p(frontier), frontier.numel(), _p(window[0]),
+            _p(window[1]), *tail), 'sample_neighbors_temporal')
     elif total > 0:
         check(lib.pygamd_sample_neighbors(_p(colptr), _p(row), _idx_dtype(colptr), _p(frontier),
-                                          frontier.numel(), _p(offsets), max_per_node,
-                                          seed & 0xFFFFFFFFFFFFFFFF,
-                                          int(replace) | (2 if salt_position else 0),
-                                          _p(seed_dev), _p(src),
-                                          _p(dstpos),
-                                          _p(slot), _stream(colptr)), 'sample_neighbors')
+                                          frontier.numel(), *tail), 'sample_neighbors')
     return src, dstpos, slot
 
 
@@ -1778,52 +1785,41 @@ def sample_temporal_window(colptr: Tensor, row: Tensor, time: Tensor, frontier: 
     return lo, hi, cnt
 
 
-def sample_neighbors_temporal(row: Tensor, frontier: Tensor, lo: Tensor, hi: Tensor,
-                              offsets: Tensor, total: int, max_per_node: int, seed: int,
-                              zero_fill: bool = False, replace: bool = False,
-                              salt_position: bool = False, seed_dev: Optional[Tensor] = None):
-    """:func:`sample_neighbors` on the windows ``[lo, hi)`` of :func:`sample_temporal_window`
-    (``pygamd_sample_neighbors_temporal``): the same draws, so a window that is a node's whole
-    column gives the plain sampler's edges bit for bit."""
-    _require_device(row, frontier, lo, hi, offsets)
+def _relabel_assign(src_global: Tensor, local_map: Tensor, total: Optional[Tensor] = None,
+                    base=0, zero_fill: bool = False):
+    """Phases 0-2 of ``pygamd_relabel`` and the scan between them: the sources not yet in
+    ``local_map`` get the local ids ``base``, ``base + 1``, ... in order of first appearance.
+    ``total`` (int64 [1], device): only that many entries of ``src_global`` are real (a static
+    capacity); ``base``: a host int, or int64 [1] on the device.  Returns ``(new_nodes, n_new)`` at
+    the capacity ``len(src_global)`` (entries past the count are unwritten, 0 with ``zero_fill``)
+    with ``n_new`` int64 [1] on the device.  No host read."""
     lib = _lib.load()
-    alloc = torch.zeros if zero_fill else torch.empty
-    src = alloc(total, dtype=row.dtype, device=row.device)
-    dstpos = alloc(total, dtype=row.dtype, device=row.device)
-    slot = alloc(total, dtype=row.dtype, device=row.device)
-    if total > 0:
-        check(lib.pygamd_sample_neighbors_temporal(
-            _p(row), _idx_dtype(row), _p(frontier), frontier.numel(), _p(lo), _p(hi), _p(offsets),
-            max_per_node, seed & 0xFFFFFFFFFFFFFFFF, int(replace) | (2 if salt_position else 0),
-            _p(seed_dev), _p(src), _p(dstpos), _p(slot), _stream(row)),
-            'sample_neighbors_temporal')
-    return src, dstpos, slot
+    m = src_global.numel()
+    dt, st, dev = _idx_dtype(src_global), _stream(src_global), src_global.device
+    new_nodes = (torch.zeros if zero_fill else torch.empty)(m, dtype=src_global.dtype, device=dev)
+    if m == 0:
+        return new_nodes, torch.zeros(1, dtype=torch.int64, device=dev)
+    base_dev = base if isinstance(base, Tensor) else None
+    check(lib.pygamd_relabel(0, _p(src_global), dt, m, _p(total), _p(local_map), None, 0, None,
+                             None, st))
+    flag = torch.empty(m, dtype=torch.int64, device=dev)
+    check(lib.pygamd_relabel(1, _p(src_global), dt, m, _p(total), _p(local_map), _p(flag), 0,
+                             None, None, st))
+    scan = cumsum(flag, out=flag)
+    check(lib.pygamd_relabel(2, _p(src_global), dt, m, _p(total), _p(local_map), _p(scan),
+                             0 if base_dev is not None else base, _p(base_dev), _p(new_nodes), st))
+    return new_nodes, scan[-1:]
 
 
 def relabel_new_nodes(src_global: Tensor, local_map: Tensor, base: int):
     """Assigns local ids base, base+1, ... to the sources not yet in `local_map` (order of first
     appearance) and returns (new_nodes, row_local).  One host sync (the number of new nodes)."""
     _require_device(src_global, local_map)
-    lib = _lib.load()
-    m = src_global.numel()
-    dt = _idx_dtype(src_global)
-    st = _stream(src_global)
-    if m == 0:
+    if src_global.numel() == 0:
         return src_global.new_empty(0), src_global.new_empty(0)
-    check(lib.pygamd_relabel(0, _p(src_global), dt, m, None, _p(local_map), None, 0, None, None,
-                             st))
-    flag = torch.empty(m, dtype=torch.int64, device=src_global.device)
-    check(lib.pygamd_relabel(1, _p(src_global), dt, m, None, _p(local_map), _p(flag), 0, None,
-                             None, st))
-    scan = cumsum(flag)
-    n_new = int(scan[-1])  # host sync: sizes the next hop (the frontier)
-    new_nodes = torch.empty(n_new, dtype=src_global.dtype, device=src_global.device)
-    check(lib.pygamd_relabel(2, _p(src_global), dt, m, None, _p(local_map), _p(scan), base, None,
-                             _p(new_nodes) if n_new > 0 else _p(flag), st))
-    rows = torch.empty_like(src_global)
-    check(lib.pygamd_relabel(3, _p(src_global), dt, m, None, _p(local_map), None, 0, None,
-                             _p(rows), st))
-    return new_nodes, rows
+    new_nodes, n_new = _relabel_assign(src_global, local_map, None, base)
+    rows = relabel_lookup(src_global, None, local_map)
+    return new_nodes[:int(n_new)], rows  # host sync: sizes the next hop (the frontier)
 
 
 def relabel_new_nodes_padded(src_global: Tensor, total: Tensor, local_map: Tensor, base: Tensor):
@@ -1832,26 +1828,8 @@ def relabel_new_nodes_padded(src_global: Tensor, total: Tensor, local_map: Tenso
     far.  Returns (new_nodes [capacity] zero-padded, row_local [capacity] zero-padded, n_new int64
     [1] on the device)."""
     _require_device(src_global, total, local_map, base)
-    lib = _lib.load()
-    m = src_global.numel()
-    dt = _idx_dtype(src_global)
-    st = _stream(src_global)
-    dev = src_global.device
-    new_nodes = torch.zeros(m, dtype=src_global.dtype, device=dev)
-    rows = torch.empty_like(src_global)
-    if m == 0:
-        return new_nodes, rows, torch.zeros(1, dtype=torch.int64, device=dev)
-    check(lib.pygamd_relabel(0, _p(src_global), dt, m, _p(total), _p(local_map), None, 0, None,
-                             None, st))
-    flag = torch.empty(m, dtype=torch.int64, device=dev)
-    check(lib.pygamd_relabel(1, _p(src_global), dt, m, _p(total), _p(local_map), _p(flag), 0,
-                             None, None, st))
-    scan = cumsum(flag)
-    check(lib.pygamd_relabel(2, _p(src_global), dt, m, _p(total), _p(local_map), _p(scan), 0,
-                             _p(base), _p(new_nodes), st))
-    check(lib.pygamd_relabel(3, _p(src_global), dt, m, _p(total), _p(local_map), None, 0, None,
-                             _p(rows), st))
-    return new_nodes, rows, scan[-1:]
+    new_nodes, n_new = _relabel_assign(src_global, local_map, total, base, zero_fill=True)
+    return new_nodes, relabel_lookup(src_global, total, local_map), n_new
 
 
 def sample_negatives(n: int, num_nodes: int, seed: int, device, dtype=torch.int64,
@@ -2008,6 +1986,13 @@ def hetero_link_seeds(src: Tensor, dst: Tensor, num_neg: int, mode, seed: int, e
     return seeds, seed_time
 
 
+def _hop_tables(item_begin, et_table):
+    """The ``item_begin, et_table, n_et`` arguments of the typed hop entry points as host arrays
+    (``et_table``: rows ``(frontier_off, col_off, dst_local, k)`` per edge type)."""
+    return (_i64_host(item_begin), _i64_host([int(v) for r in et_table for v in r]),
+            len(et_table))
+
+
 def hetero_sample_counts(colptr: Tensor, frontier: Tensor, item_begin, et_table,
                          replace: bool = False) -> Tensor:
     """``pygamd_hetero_sample_counts``: per work item of a hop, ``min(deg, k)`` with the ``k`` of
@@ -2019,35 +2004,41 @@ def hetero_sample_counts(colptr: Tensor, frontier: Tensor, item_begin, et_table,
     lib = _lib.load()
     n = int(item_begin[-1])
     cnt = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
-    flat = [int(v) for row in et_table for v in row]
     check(lib.pygamd_hetero_sample_counts(_p(colptr), _idx_dtype(colptr), _p(frontier),
-                                          _i64_host(item_begin), _i64_host(flat), len(et_table),
-                                          int(replace), _p(cnt), _stream(colptr)),
-          'hetero_sample_counts')
+                                          *_hop_tables(item_begin, et_table), int(replace),
+                                          _p(cnt), _stream(colptr)), 'hetero_sample_counts')
     return cnt
 
 
 def hetero_sample_neighbors(colptr: Tensor, row: Tensor, perm: Tensor, frontier: Tensor,
                             offsets: Tensor, capacity: int, item_begin, et_table, seed: int,
                             replace: bool = False, salt_position: bool = False,
-                            want_fpos: bool = False):
+                            want_fpos: bool = False,
+                            window: Optional[Tuple[Tensor, Tensor]] = None):
     """``pygamd_hetero_sample_neighbors``: ``(src_global, col_local, edge, fpos)`` of one hop at the
     static ``capacity`` (entries past ``offsets[-1]`` are not written, except ``fpos``, which is
-    zero-filled; ``None`` unless ``want_fpos``)."""
-    _require_device(colptr, row, perm, frontier, offsets)
+    zero-filled; ``None`` unless ``want_fpos``).  ``window``: the ``(lo, hi)`` of
+    :func:`hetero_sample_temporal_window`; the same draws and outputs on the slots ``[lo, hi)`` of
+    every item (``pygamd_hetero_sample_neighbors_temporal``)."""
+    _require_device(colptr, row, perm, frontier, offsets, *(window or ()))
     lib = _lib.load()
     dt, dev = colptr.dtype, colptr.device
     src = torch.empty(capacity, dtype=dt, device=dev)
     col = torch.empty(capacity, dtype=dt, device=dev)
     edge = torch.empty(capacity, dtype=dt, device=dev)
     fpos = torch.zeros(capacity, dtype=dt, device=dev) if want_fpos else None
-    flat = [int(v) for r in et_table for v in r]
-    if capacity > 0 and int(item_begin[-1]) > 0:
-        check(lib.pygamd_hetero_sample_neighbors(
-            _p(colptr), _p(row), _p(perm), _idx_dtype(colptr), _p(frontier), _p(offsets),
-            _i64_host(item_begin), _i64_host(flat), len(et_table), seed & 0xFFFFFFFFFFFFFFFF,
+    # the arguments both draw entry points end with
+    tail = (_p(offsets), *_hop_tables(item_begin, et_table), seed & 0xFFFFFFFFFFFFFFFF,
             int(replace) | (2 if salt_position else 0), _p(src), _p(col), _p(edge), _p(fpos),
-            _stream(colptr)), 'hetero_sample_neighbors')
+            _stream(colptr))
+    if capacity > 0 and int(item_begin[-1]) > 0 and window is not None:
+        check(lib.pygamd_hetero_sample_neighbors_temporal(
+            _p(row), _p(perm), _idx_dtype(row), _p(frontier), _p(window[0]), _p(window[1]),
+            *tail), 'hetero_sample_neighbors_temporal')
+    elif capacity > 0 and int(item_begin[-1]) > 0:
+        check(lib.pygamd_hetero_sample_neighbors(
+            _p(colptr), _p(row), _p(perm), _idx_dtype(colptr), _p(frontier), *tail),
+            'hetero_sample_neighbors')
     return src, col, edge, fpos
 
 
@@ -2072,37 +2063,12 @@ def hetero_sample_temporal_window(colptr: Tensor, row: Tensor, time: Tensor, fro
     lo = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
     hi = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
     cnt = torch.empty(n, dtype=colptr.dtype, device=colptr.device)
-    flat = [int(v) for r in et_table for v in r]
     check(lib.pygamd_hetero_sample_temporal_window(
         _p(colptr), _p(row), _idx_dtype(colptr), _p(time), int(edge_level), _p(frontier),
-        _p(frontier_time), _i64_host(item_begin), _i64_host(flat), len(et_table),
+        _p(frontier_time), *_hop_tables(item_begin, et_table),
         int(timed_mask), int(replace), int(last), _p(lo), _p(hi), _p(cnt), _stream(colptr)),
         'hetero_sample_temporal_window')
     return lo, hi, cnt
-
-
-def hetero_sample_neighbors_temporal(row: Tensor, perm: Tensor, frontier: Tensor, lo: Tensor,
-                                     hi: Tensor, offsets: Tensor, capacity: int, item_begin,
-                                     et_table, seed: int, replace: bool = False,
-                                     salt_position: bool = False, want_fpos: bool = False):
-    """:func:`hetero_sample_neighbors` on the windows ``[lo, hi)`` of
-    :func:`hetero_sample_temporal_window` (``pygamd_hetero_sample_neighbors_temporal``): the same
-    draws and outputs."""
-    _require_device(row, perm, frontier, lo, hi, offsets)
-    lib = _lib.load()
-    dt, dev = row.dtype, row.device
-    src = torch.empty(capacity, dtype=dt, device=dev)
-    col = torch.empty(capacity, dtype=dt, device=dev)
-    edge = torch.empty(capacity, dtype=dt, device=dev)
-    fpos = torch.zeros(capacity, dtype=dt, device=dev) if want_fpos else None
-    flat = [int(v) for r in et_table for v in r]
-    if capacity > 0 and int(item_begin[-1]) > 0:
-        check(lib.pygamd_hetero_sample_neighbors_temporal(
-            _p(row), _p(perm), _idx_dtype(row), _p(frontier), _p(lo), _p(hi), _p(offsets),
-            _i64_host(item_begin), _i64_host(flat), len(et_table), seed & 0xFFFFFFFFFFFFFFFF,
-            int(replace) | (2 if salt_position else 0), _p(src), _p(col), _p(edge), _p(fpos),
-            _stream(row)), 'hetero_sample_neighbors_temporal')
-    return src, col, edge, fpos
 
 
 def hetero_split(new_nodes: Tensor, n_new: Tensor, node_base, count_prev, offsets: Optional[Tensor],
@@ -2145,25 +2111,12 @@ def relabel_claim_assign(src_global: Tensor, total: Tensor, local_map: Tensor):
     ``(new_nodes [capacity], n_new int64 [1])``, the new sources in order of first appearance;
     ``local_map`` holds their ranks afterwards.  No host read."""
     _require_device(src_global, total, local_map)
-    lib = _lib.load()
-    m = src_global.numel()
-    dt, st, dev = _idx_dtype(src_global), _stream(src_global), src_global.device
-    new_nodes = torch.empty(m, dtype=src_global.dtype, device=dev)
-    if m == 0:
-        return new_nodes, torch.zeros(1, dtype=torch.int64, device=dev)
-    check(lib.pygamd_relabel(0, _p(src_global), dt, m, _p(total), _p(local_map), None, 0, None,
-                             None, st))
-    flag = torch.empty(m, dtype=torch.int64, device=dev)
-    check(lib.pygamd_relabel(1, _p(src_global), dt, m, _p(total), _p(local_map), _p(flag), 0,
-                             None, None, st))
-    scan = cumsum(flag, out=flag)
-    check(lib.pygamd_relabel(2, _p(src_global), dt, m, _p(total), _p(local_map), _p(scan), 0,
-                             None, _p(new_nodes), st))
-    return new_nodes, scan[-1:]
+    return _relabel_assign(src_global, local_map, total)
 
 
-def relabel_lookup(src_global: Tensor, total: Tensor, local_map: Tensor) -> Tensor:
-    """Phase 3 of ``pygamd_relabel``: ``local_map[src]`` for the first ``total`` entries, 0 after."""
+def relabel_lookup(src_global: Tensor, total: Optional[Tensor], local_map: Tensor) -> Tensor:
+    """Phase 3 of ``pygamd_relabel``: ``local_map[src]`` for the first ``total`` entries (all of
+    them for ``None``), 0 after."""
     _require_device(src_global, total, local_map)
     lib = _lib.load()
     out = torch.empty_like(src_global)

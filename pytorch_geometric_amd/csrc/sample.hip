@@ -54,9 +54,8 @@ __device__ __forceinline__ uint64_t node_key(uint64_t seed, const uint64_t* __re
 }
 
 // The uniform draw of one frontier node over the slot range [s, s + deg): cnt = offsets[f + 1] -
-// offsets[f] > 0 edges written from position o.  Shared by the plain kernel (the node's whole
-// column) and the temporal one (its eligible window), so the same (key, s, deg, cnt) gives the
-// same edges bit for bit.
+// offsets[f] > 0 edges written from position o.  The range is the node's whole column or its
+// eligible window (temporal draws): the same (key, s, deg, cnt) gives the same edges bit for bit.
 template <typename IdxT>
 __device__ __forceinline__ void draw_uniform(const IdxT* __restrict__ row, int64_t s, int64_t deg,
                                              int64_t o, int64_t cnt, int64_t f, uint64_t key,
@@ -102,10 +101,21 @@ __device__ __forceinline__ void draw_uniform(const IdxT* __restrict__ row, int64
   }
 }
 
+// The edges drawn from a window of w slots under (k, replace): min(w, k) (k < 0: all of it; with
+// replacement and k >= 0: k wherever the window is not empty).  THE count rule of every sampler:
+// the plain and the typed counts apply it to a column, the window kernels to the eligible window.
+__device__ __forceinline__ int64_t window_count(int64_t w, int64_t k, bool replace) {
+  if (replace && k >= 0) return w > 0 ? k : 0;
+  return (k >= 0 && w > k) ? k : w;
+}
+
+// lo / hi NULL: the slot range of frontier node f is its column, read from colptr.  Given (the
+// temporal draws, see below): it is the window [lo[f], hi[f]) and colptr is not read.
 template <typename IdxT>
 __global__ void __launch_bounds__(kBlock)
     sample_neighbors_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
                             const IdxT* __restrict__ frontier, int64_t n_frontier,
+                            const IdxT* __restrict__ lo, const IdxT* __restrict__ hi,
                             const IdxT* __restrict__ offsets, uint64_t seed, int flags,
                             const uint64_t* __restrict__ seed_dev,
                             IdxT* __restrict__ src_out, IdxT* __restrict__ dstpos_out,
@@ -113,8 +123,8 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t f = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
   if (f >= n_frontier) return;
   const int64_t v = frontier[f];
-  const int64_t s = colptr[v];
-  const int64_t deg = static_cast<int64_t>(colptr[v + 1]) - s;
+  const int64_t s = lo ? lo[f] : colptr[v];
+  const int64_t deg = static_cast<int64_t>(lo ? hi[f] : colptr[v + 1]) - s;
   const int64_t o = offsets[f];
   const int64_t cnt = static_cast<int64_t>(offsets[f + 1]) - o;
   if (cnt <= 0) return;
@@ -134,8 +144,9 @@ __global__ void __launch_bounds__(kBlock)
 // cut into 64 chunks of `step` slots, lane l probes the last slot of chunk l, one ballot gives the
 // first chunk whose probe is past t and the range shrinks to that chunk: ceil(log64(deg)) steps
 // (deg <= 64: one load per lane and one ballot).  'last' then narrows the window to its last k
-// slots, lo = max(s, hi - k) (k >= 0); 'uniform' keeps lo = s.  cnt is pygamd_sample_counts'
-// rule applied to the window hi - lo.
+// slots, lo = max(s, hi - k) (k >= 0); 'uniform' keeps lo = s.  cnt is window_count on hi - lo.
+// The draws of the hop are sample_neighbors_kernel's on the windows [lo[f], hi[f]): draw_uniform
+// with the same hash stream, so a window that is the whole column draws what the column draws.
 template <typename IdxT>
 __device__ __forceinline__ int64_t slot_time_of(const IdxT* __restrict__ row,
                                                 const int64_t* __restrict__ time, int level,
@@ -169,18 +180,10 @@ __device__ __forceinline__ int64_t temporal_window_end(const IdxT* __restrict__ 
   return a;
 }
 
-// lo and cnt of a window that ends at hi: 'last' keeps its last k slots (k >= 0), cnt is
-// pygamd_sample_counts' rule on hi - lo
-__device__ __forceinline__ void temporal_window_count(int64_t s, int64_t hi, int64_t k,
-                                                      bool replace, bool last, int64_t* lo,
-                                                      int64_t* cnt) {
-  *lo = (last && k >= 0 && hi - k > s) ? hi - k : s;
-  const int64_t w = hi - *lo;
-  if (replace && k >= 0) {
-    *cnt = w > 0 ? k : 0;
-  } else {
-    *cnt = (k >= 0 && w > k) ? k : w;
-  }
+// lo of a window [s, hi): 'last' keeps its last k slots (k >= 0)
+__device__ __forceinline__ int64_t temporal_window_lo(int64_t s, int64_t hi, int64_t k,
+                                                      bool last) {
+  return (last && k >= 0 && hi - k > s) ? hi - k : s;
 }
 
 template <typename IdxT>
@@ -207,37 +210,12 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t s = colptr[v];
   const int64_t end = colptr[v + 1];
   const int64_t hi = temporal_window_end(row, time, level, s, end, frontier_time[f]);
-  int64_t lo, c;
-  temporal_window_count(s, hi, k, replace != 0, last != 0, &lo, &c);
+  const int64_t lo = temporal_window_lo(s, hi, k, last != 0);
   if (lane == 0) {
     lo_out[f] = static_cast<IdxT>(lo);
     hi_out[f] = static_cast<IdxT>(hi);
-    cnt_out[f] = static_cast<IdxT>(c);
+    cnt_out[f] = static_cast<IdxT>(window_count(hi - lo, k, replace != 0));
   }
-}
-
-// The draws of one hop over the windows [lo[f], hi[f]): draw_uniform on the window, with the hash
-// stream of the plain kernel, so a window that is the whole column draws what the plain kernel
-// draws.
-template <typename IdxT>
-__global__ void __launch_bounds__(kBlock)
-    sample_neighbors_temporal_kernel(const IdxT* __restrict__ row,
-                                     const IdxT* __restrict__ frontier, int64_t n_frontier,
-                                     const IdxT* __restrict__ lo, const IdxT* __restrict__ hi,
-                                     const IdxT* __restrict__ offsets, uint64_t seed, int flags,
-                                     const uint64_t* __restrict__ seed_dev,
-                                     IdxT* __restrict__ src_out, IdxT* __restrict__ dstpos_out,
-                                     IdxT* __restrict__ slot_out) {
-  const int64_t f = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
-  if (f >= n_frontier) return;
-  const int64_t o = offsets[f];
-  const int64_t cnt = static_cast<int64_t>(offsets[f + 1]) - o;
-  if (cnt <= 0) return;
-  const int64_t v = frontier[f];
-  const int64_t s = lo[f];
-  const int64_t deg = static_cast<int64_t>(hi[f]) - s;
-  const uint64_t key = node_key(seed, seed_dev, v, f, flags);
-  draw_uniform(row, s, deg, o, cnt, f, key, (flags & 1) != 0, src_out, dstpos_out, slot_out);
 }
 
 // ---- weighted draws (the reference's weight_attr -> NeighborSampler.edge_weight,
@@ -460,11 +438,7 @@ __global__ void __launch_bounds__(kBlock)
   }
   const int64_t v = frontier[f];
   const int64_t deg = static_cast<int64_t>(colptr[v + 1]) - static_cast<int64_t>(colptr[v]);
-  if (replace && k >= 0) {
-    cnt[f] = static_cast<IdxT>(deg > 0 ? k : 0);
-  } else {
-    cnt[f] = static_cast<IdxT>((k >= 0 && deg > k) ? k : deg);
-  }
+  cnt[f] = static_cast<IdxT>(window_count(deg, k, replace != 0));
 }
 
 // ---- relabelling: global ids of the sampled sources -> local ids, new nodes in order of first
@@ -693,27 +667,40 @@ __device__ __forceinline__ int hetero_edge_type(const HeteroHop& h, int64_t i) {
   return lo;
 }
 
-// cnt[i] = pygamd_sample_counts' rule with the k of item i's edge type
+// work item i decoded: its edge type, its position p in that type's frontier block, its position
+// fp in the frontier buffer and its stacked column
+struct HeteroItem {
+  int et;
+  int64_t p, fp, col;
+};
+
+template <typename IdxT>
+__device__ __forceinline__ HeteroItem hetero_item(const HeteroHop& h,
+                                                  const IdxT* __restrict__ frontier, int64_t i) {
+  HeteroItem it;
+  it.et = hetero_edge_type(h, i);
+  it.p = i - h.item_begin[it.et];
+  it.fp = h.frontier_off[it.et] + it.p;
+  it.col = static_cast<int64_t>(frontier[it.fp]) + h.col_off[it.et];
+  return it;
+}
+
+// cnt[i] = window_count on item i's column with the k of its edge type
 template <typename IdxT>
 __global__ void __launch_bounds__(kBlock)
     hetero_counts_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ frontier,
                          const HeteroHop hop, int replace, IdxT* __restrict__ cnt) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i >= hop.item_begin[hop.n_et]) return;
-  const int et = hetero_edge_type(hop, i);
-  const int64_t c = static_cast<int64_t>(frontier[hop.frontier_off[et] + i - hop.item_begin[et]]) +
-                    hop.col_off[et];
-  const int64_t deg = static_cast<int64_t>(colptr[c + 1]) - static_cast<int64_t>(colptr[c]);
-  const int64_t k = hop.k[et];
-  if (replace && k >= 0) {
-    cnt[i] = static_cast<IdxT>(deg > 0 ? k : 0);
-  } else {
-    cnt[i] = static_cast<IdxT>((k >= 0 && deg > k) ? k : deg);
-  }
+  const HeteroItem it = hetero_item(hop, frontier, i);
+  const int64_t deg =
+      static_cast<int64_t>(colptr[it.col + 1]) - static_cast<int64_t>(colptr[it.col]);
+  cnt[i] = static_cast<IdxT>(window_count(deg, hop.k[it.et], replace != 0));
 }
 
-// One wave per work item: draw_uniform on the item's column, keyed by the stacked column id and
-// the item's position (a single type with col_base = 0 draws what sample_neighbors_kernel draws);
+// One wave per work item: draw_uniform on the item's column, or on its window [lo[i], hi[i]) when
+// lo / hi are given (colptr is not read then), keyed by the stacked column id and the item's
+// position (a single type with col_base = 0 draws what sample_neighbors_kernel draws);
 // replacement only where the item's edge type has a bounded fan-out.  Writes the global source,
 // the typed local destination (dst_local + p), the edge id perm[slot] and, when fpos_out is given,
 // the destination's position in the frontier buffer.
@@ -721,6 +708,7 @@ template <typename IdxT>
 __global__ void __launch_bounds__(kBlock)
     hetero_sample_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
                          const IdxT* __restrict__ perm, const IdxT* __restrict__ frontier,
+                         const IdxT* __restrict__ lo, const IdxT* __restrict__ hi,
                          const IdxT* __restrict__ offsets, const HeteroHop hop, uint64_t seed,
                          int flags, IdxT* __restrict__ src_out, IdxT* __restrict__ col_out,
                          IdxT* __restrict__ edge_out, IdxT* __restrict__ fpos_out) {
@@ -729,18 +717,15 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t o = offsets[i];
   const int64_t cnt = static_cast<int64_t>(offsets[i + 1]) - o;
   if (cnt <= 0) return;
-  const int et = hetero_edge_type(hop, i);
-  const int64_t p = i - hop.item_begin[et];
-  const int64_t fp = hop.frontier_off[et] + p;
-  const int64_t c = static_cast<int64_t>(frontier[fp]) + hop.col_off[et];
-  const int64_t s = colptr[c];
-  const int64_t deg = static_cast<int64_t>(colptr[c + 1]) - s;
-  const uint64_t key = node_key(seed, nullptr, c, i, flags);
-  const bool rep = (flags & 1) != 0 && hop.k[et] >= 0;
-  draw_uniform(row, s, deg, o, cnt, hop.dst_local[et] + p, key, rep, src_out, col_out, edge_out,
-               perm);
+  const HeteroItem it = hetero_item(hop, frontier, i);
+  const int64_t s = lo ? lo[i] : colptr[it.col];
+  const int64_t deg = static_cast<int64_t>(lo ? hi[i] : colptr[it.col + 1]) - s;
+  const uint64_t key = node_key(seed, nullptr, it.col, i, flags);
+  const bool rep = (flags & 1) != 0 && hop.k[it.et] >= 0;
+  draw_uniform(row, s, deg, o, cnt, hop.dst_local[it.et] + it.p, key, rep, src_out, col_out,
+               edge_out, perm);
   if (fpos_out) {
-    for (int64_t t = lane_id(); t < cnt; t += kWave) fpos_out[o + t] = static_cast<IdxT>(fp);
+    for (int64_t t = lane_id(); t < cnt; t += kWave) fpos_out[o + t] = static_cast<IdxT>(it.fp);
   }
 }
 
@@ -751,8 +736,9 @@ __global__ void __launch_bounds__(kBlock)
 // global node ids (level 0) or over the slots (level 1).  One wave per work item: the window of a
 // timed item is the prefix of its column with time <= frontier_time[fp] (the seed time of the tree
 // of the destination at frontier position fp), found by temporal_window_end and narrowed by
-// 'last'; an untimed item's window is its whole column.  cnt is hetero_counts_kernel's rule on the
-// window, so this launch takes the place of the counts launch.
+// 'last'; an untimed item's window is its whole column.  cnt is window_count on the window, so
+// this launch takes the place of the counts launch; hetero_sample_kernel then draws on the windows
+// (one node type with one edge type: what sample_neighbors_kernel draws on them).
 template <typename IdxT>
 __global__ void __launch_bounds__(kBlock)
     hetero_temporal_window_kernel(const IdxT* __restrict__ colptr, const IdxT* __restrict__ row,
@@ -764,52 +750,18 @@ __global__ void __launch_bounds__(kBlock)
                                   IdxT* __restrict__ cnt_out) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
   if (i >= hop.item_begin[hop.n_et]) return;
-  const int et = hetero_edge_type(hop, i);
-  const int64_t fp = hop.frontier_off[et] + i - hop.item_begin[et];
-  const int64_t c = static_cast<int64_t>(frontier[fp]) + hop.col_off[et];
-  const int64_t s = colptr[c];
-  const int64_t end = colptr[c + 1];
-  const bool is_timed = ((timed >> et) & 1ull) != 0;
+  const HeteroItem it = hetero_item(hop, frontier, i);
+  const int64_t s = colptr[it.col];
+  const int64_t end = colptr[it.col + 1];
+  const bool is_timed = ((timed >> it.et) & 1ull) != 0;
   const int64_t hi =
-      is_timed ? temporal_window_end(row, time, level, s, end, frontier_time[fp]) : end;
-  int64_t lo, cnt;
-  temporal_window_count(s, hi, hop.k[et], replace != 0, last != 0 && is_timed, &lo, &cnt);
+      is_timed ? temporal_window_end(row, time, level, s, end, frontier_time[it.fp]) : end;
+  const int64_t k = hop.k[it.et];
+  const int64_t lo = temporal_window_lo(s, hi, k, last != 0 && is_timed);
   if (lane_id() == 0) {
     lo_out[i] = static_cast<IdxT>(lo);
     hi_out[i] = static_cast<IdxT>(hi);
-    cnt_out[i] = static_cast<IdxT>(cnt);
-  }
-}
-
-// hetero_sample_kernel on the windows [lo[i], hi[i]): the same key (stacked column id, item
-// position), flags and outputs, so a window that is the whole column draws what
-// hetero_sample_kernel draws, and one node type with one edge type what
-// sample_neighbors_temporal_kernel draws.
-template <typename IdxT>
-__global__ void __launch_bounds__(kBlock)
-    hetero_sample_temporal_kernel(const IdxT* __restrict__ row, const IdxT* __restrict__ perm,
-                                  const IdxT* __restrict__ frontier, const IdxT* __restrict__ lo,
-                                  const IdxT* __restrict__ hi, const IdxT* __restrict__ offsets,
-                                  const HeteroHop hop, uint64_t seed, int flags,
-                                  IdxT* __restrict__ src_out, IdxT* __restrict__ col_out,
-                                  IdxT* __restrict__ edge_out, IdxT* __restrict__ fpos_out) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
-  if (i >= hop.item_begin[hop.n_et]) return;
-  const int64_t o = offsets[i];
-  const int64_t cnt = static_cast<int64_t>(offsets[i + 1]) - o;
-  if (cnt <= 0) return;
-  const int et = hetero_edge_type(hop, i);
-  const int64_t p = i - hop.item_begin[et];
-  const int64_t fp = hop.frontier_off[et] + p;
-  const int64_t c = static_cast<int64_t>(frontier[fp]) + hop.col_off[et];
-  const int64_t s = lo[i];
-  const int64_t deg = static_cast<int64_t>(hi[i]) - s;
-  const uint64_t key = node_key(seed, nullptr, c, i, flags);
-  const bool rep = (flags & 1) != 0 && hop.k[et] >= 0;
-  draw_uniform(row, s, deg, o, cnt, hop.dst_local[et] + p, key, rep, src_out, col_out, edge_out,
-               perm);
-  if (fpos_out) {
-    for (int64_t t = lane_id(); t < cnt; t += kWave) fpos_out[o + t] = static_cast<IdxT>(fp);
+    cnt_out[i] = static_cast<IdxT>(window_count(hi - lo, k, replace != 0));
   }
 }
 
@@ -886,6 +838,26 @@ extern "C" {
 
 int pygamd_sample_max_fanout(void) { return kMaxFanout; }
 
+// the launch of sample_neighbors_kernel behind both of its entry points (lo / hi NULL: the columns)
+static int launch_sample_neighbors(const void* colptr, const void* row, int idx_dtype,
+                                   const void* frontier, int64_t n_frontier, const void* lo,
+                                   const void* hi, const void* offsets, uint64_t seed, int flags,
+                                   const uint64_t* seed_dev, void* src_out, void* dstpos_out,
+                                   void* slot_out, void* stream) {
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid = static_cast<unsigned>(ceil_div(n_frontier, kWavesPerBlock));
+    hipLaunchKernelGGL((sample_neighbors_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(colptr),
+                       static_cast<const IdxT*>(row), static_cast<const IdxT*>(frontier),
+                       n_frontier, static_cast<const IdxT*>(lo), static_cast<const IdxT*>(hi),
+                       static_cast<const IdxT*>(offsets), seed, flags, seed_dev,
+                       static_cast<IdxT*>(src_out), static_cast<IdxT*>(dstpos_out),
+                       static_cast<IdxT*>(slot_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
 int pygamd_sample_neighbors(const void* colptr, const void* row, int idx_dtype,
                             const void* frontier, int64_t n_frontier, const void* offsets,
                             int64_t max_per_node, uint64_t seed, int flags,
@@ -898,17 +870,9 @@ int pygamd_sample_neighbors(const void* colptr, const void* row, int idx_dtype,
   // a bounded fan-out larger than the LDS draw table is not supported (k < 0 = "all" is)
   if (max_per_node > kMaxFanout) return PYGAMD_ERR_UNSUPPORTED;
   if ((flags & 1) && max_per_node <= 0) return PYGAMD_ERR_INVALID_ARG;  // "all": no replacement
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    const unsigned grid = static_cast<unsigned>(ceil_div(n_frontier, kWavesPerBlock));
-    hipLaunchKernelGGL((sample_neighbors_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
-                       as_stream(stream), static_cast<const IdxT*>(colptr),
-                       static_cast<const IdxT*>(row), static_cast<const IdxT*>(frontier),
-                       n_frontier, static_cast<const IdxT*>(offsets), seed, flags, seed_dev,
-                       static_cast<IdxT*>(src_out), static_cast<IdxT*>(dstpos_out),
-                       static_cast<IdxT*>(slot_out));
-    PYGAMD_LAUNCH_CHECK();
-    return PYGAMD_OK;
-  });
+  return launch_sample_neighbors(colptr, row, idx_dtype, frontier, n_frontier, nullptr, nullptr,
+                                 offsets, seed, flags, seed_dev, src_out, dstpos_out, slot_out,
+                                 stream);
 }
 
 int pygamd_sample_neighbors_weighted(const void* colptr, const void* row, int idx_dtype,
@@ -974,18 +938,8 @@ int pygamd_sample_neighbors_temporal(const void* row, int idx_dtype, const void*
   if (n_frontier == 0) return PYGAMD_OK;
   if (!row || !frontier || !offsets || !src_out || !dstpos_out || !slot_out)
     return PYGAMD_ERR_INVALID_ARG;
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    const unsigned grid = static_cast<unsigned>(ceil_div(n_frontier, kWavesPerBlock));
-    hipLaunchKernelGGL((sample_neighbors_temporal_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
-                       as_stream(stream), static_cast<const IdxT*>(row),
-                       static_cast<const IdxT*>(frontier), n_frontier,
-                       static_cast<const IdxT*>(lo), static_cast<const IdxT*>(hi),
-                       static_cast<const IdxT*>(offsets), seed, flags, seed_dev,
-                       static_cast<IdxT*>(src_out), static_cast<IdxT*>(dstpos_out),
-                       static_cast<IdxT*>(slot_out));
-    PYGAMD_LAUNCH_CHECK();
-    return PYGAMD_OK;
-  });
+  return launch_sample_neighbors(nullptr, row, idx_dtype, frontier, n_frontier, lo, hi, offsets,
+                                 seed, flags, seed_dev, src_out, dstpos_out, slot_out, stream);
 }
 
 int pygamd_sample_counts(const void* colptr, int idx_dtype, const void* frontier, int64_t n,
@@ -1173,6 +1127,27 @@ int pygamd_hetero_sample_counts(const void* colptr, int idx_dtype, const void* f
   });
 }
 
+// the launch of hetero_sample_kernel behind both of its entry points (lo / hi NULL: the columns)
+static int launch_hetero_sample(const void* colptr, const void* row, const void* perm,
+                                int idx_dtype, const void* frontier, const void* lo,
+                                const void* hi, const void* offsets, const HeteroHop& hop,
+                                uint64_t seed, int flags, void* src_out, void* col_out,
+                                void* edge_out, void* fpos_out, void* stream) {
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    const unsigned grid =
+        static_cast<unsigned>(ceil_div(hop.item_begin[hop.n_et], kWavesPerBlock));
+    hipLaunchKernelGGL((hetero_sample_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
+                       as_stream(stream), static_cast<const IdxT*>(colptr),
+                       static_cast<const IdxT*>(row), static_cast<const IdxT*>(perm),
+                       static_cast<const IdxT*>(frontier), static_cast<const IdxT*>(lo),
+                       static_cast<const IdxT*>(hi), static_cast<const IdxT*>(offsets), hop, seed,
+                       flags, static_cast<IdxT*>(src_out), static_cast<IdxT*>(col_out),
+                       static_cast<IdxT*>(edge_out), static_cast<IdxT*>(fpos_out));
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
 int pygamd_hetero_sample_neighbors(const void* colptr, const void* row, const void* perm,
                                    int idx_dtype, const void* frontier, const void* offsets,
                                    const int64_t* item_begin, const int64_t* et_table, int n_et,
@@ -1181,21 +1156,11 @@ int pygamd_hetero_sample_neighbors(const void* colptr, const void* row, const vo
   HeteroHop hop;
   const int rc = fill_hetero_hop(item_begin, et_table, n_et, &hop);
   if (rc != PYGAMD_OK) return rc;
-  const int64_t n = hop.item_begin[n_et];
-  if (n == 0) return PYGAMD_OK;
+  if (hop.item_begin[n_et] == 0) return PYGAMD_OK;
   if (!colptr || !row || !perm || !frontier || !offsets || !src_out || !col_out || !edge_out)
     return PYGAMD_ERR_INVALID_ARG;
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    const unsigned grid = static_cast<unsigned>(ceil_div(n, kWavesPerBlock));
-    hipLaunchKernelGGL((hetero_sample_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
-                       as_stream(stream), static_cast<const IdxT*>(colptr),
-                       static_cast<const IdxT*>(row), static_cast<const IdxT*>(perm),
-                       static_cast<const IdxT*>(frontier), static_cast<const IdxT*>(offsets), hop,
-                       seed, flags, static_cast<IdxT*>(src_out), static_cast<IdxT*>(col_out),
-                       static_cast<IdxT*>(edge_out), static_cast<IdxT*>(fpos_out));
-    PYGAMD_LAUNCH_CHECK();
-    return PYGAMD_OK;
-  });
+  return launch_hetero_sample(colptr, row, perm, idx_dtype, frontier, nullptr, nullptr, offsets,
+                              hop, seed, flags, src_out, col_out, edge_out, fpos_out, stream);
 }
 
 int pygamd_hetero_sample_temporal_window(const void* colptr, const void* row, int idx_dtype,
@@ -1238,22 +1203,11 @@ int pygamd_hetero_sample_neighbors_temporal(const void* row, const void* perm, i
   const int rc = fill_hetero_hop(item_begin, et_table, n_et, &hop);
   if (rc != PYGAMD_OK) return rc;
   if (!lo || !hi) return PYGAMD_ERR_INVALID_ARG;
-  const int64_t n = hop.item_begin[n_et];
-  if (n == 0) return PYGAMD_OK;
+  if (hop.item_begin[n_et] == 0) return PYGAMD_OK;
   if (!row || !perm || !frontier || !offsets || !src_out || !col_out || !edge_out)
     return PYGAMD_ERR_INVALID_ARG;
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    const unsigned grid = static_cast<unsigned>(ceil_div(n, kWavesPerBlock));
-    hipLaunchKernelGGL((hetero_sample_temporal_kernel<IdxT>), dim3(grid), dim3(kBlock), 0,
-                       as_stream(stream), static_cast<const IdxT*>(row),
-                       static_cast<const IdxT*>(perm), static_cast<const IdxT*>(frontier),
-                       static_cast<const IdxT*>(lo), static_cast<const IdxT*>(hi),
-                       static_cast<const IdxT*>(offsets), hop, seed, flags,
-                       static_cast<IdxT*>(src_out), static_cast<IdxT*>(col_out),
-                       static_cast<IdxT*>(edge_out), static_cast<IdxT*>(fpos_out));
-    PYGAMD_LAUNCH_CHECK();
-    return PYGAMD_OK;
-  });
+  return launch_hetero_sample(nullptr, row, perm, idx_dtype, frontier, lo, hi, offsets, hop, seed,
+                              flags, src_out, col_out, edge_out, fpos_out, stream);
 }
 
 int pygamd_hetero_split(int phase, const void* new_nodes, int idx_dtype, int64_t m,

@@ -223,6 +223,140 @@ def _cached_cdf(cache: dict, weight: Tensor, num_nodes: int, device) -> Tensor:
     return cdf
 
 
+# ---- what NeighborSampler and HeteroNeighborSampler share ---------------------------------------------
+def _subgraph_type(subgraph_type) -> str:
+    subgraph_type = getattr(subgraph_type, 'value', subgraph_type)  # the reference's enum
+    if subgraph_type not in ('directional', 'bidirectional', 'induced'):
+        raise ValueError(f"unknown subgraph_type '{subgraph_type}'")
+    return subgraph_type
+
+
+def _check_temporal_strategy(temporal_strategy) -> None:
+    if temporal_strategy not in ('uniform', 'last'):
+        raise ValueError(f"unknown temporal_strategy '{temporal_strategy}' (expected "
+                         f"'uniform' or 'last')")
+
+
+def _check_seed_time(time, n: int) -> None:
+    """Caller-supplied seed times: an integer tensor with one entry per seed."""
+    if not isinstance(time, Tensor) or time.dim() != 1 or time.numel() != n:
+        raise ValueError(f"the seed times must be a 1-D tensor with one entry per seed "
+                         f"({n})")
+    if time.is_floating_point() or time.is_complex() or time.dtype == torch.bool:
+        raise ValueError(f"the seed times must be an integer tensor (got {time.dtype})")
+
+
+def _link_input(index, neg_sampling, is_temporal: bool):
+    """The input of ``sample_from_edges``, a ``[2, B]`` tensor of positive edges or an
+    ``EdgeSamplerInput``-like object, as ``(src, dst, input_id, label, time, neg, B)``, with the
+    checks on shapes and on times against the kind of sampler."""
+    input_id = label = time = None
+    if isinstance(index, Tensor):
+        if index.dim() != 2 or index.size(0) != 2:
+            raise ValueError(f"the positive edges must be a [2, B] tensor (got "
+                             f"{list(index.shape)})")
+        src, dst = index[0], index[1]
+    else:
+        src, dst = index.row, index.col
+        input_id = getattr(index, 'input_id', None)
+        label, time = getattr(index, 'label', None), getattr(index, 'time', None)
+    neg = NegativeSampling.cast(neg_sampling)
+    B = src.numel()
+    if dst.numel() != B or src.dim() != 1 or dst.dim() != 1:
+        raise ValueError('the source and destination of the positive edges must be 1-D '
+                         'tensors of one length')
+    if B == 0:
+        raise ValueError("'sample_from_edges' needs at least one positive edge")
+    if time is not None and not is_temporal:
+        raise ValueError("'edge_label_time' is given but the sampler is not temporal (no "
+                         "'node_time' / 'edge_time')")
+    if time is None and is_temporal:
+        raise ValueError("a temporal sampler needs the seed-link times ('edge_label_time')")
+    return src, dst, input_id, label, time, neg, B
+
+
+def _check_link_label(neg, label, B: int) -> None:
+    if neg is not None and neg.is_triplet() and label is not None:
+        raise ValueError("'edge_label' needs to be undefined for 'triplet'-based negative "
+                         "sampling")
+    if label is not None and label.size(0) != B:
+        raise ValueError(f"'edge_label' needs one entry per positive edge ({B})")
+
+
+def _binary_label(label, B: int, num_neg: int, device) -> Tensor:
+    """The labels of binary negative sampling: the positives' (1 by default), then 0."""
+    if label is None:
+        label = torch.ones(B, device=device)
+    return torch.cat([label, label.new_zeros((num_neg, ) + label.shape[1:])])
+
+
+def _link_metadata(input_id, index, label, src_time, neg, B: int, disjoint: bool):
+    """``metadata`` of a link batch from ``index``, the local id of every seed slot (int64, the
+    source slots, then the destination slots: positives, then negatives)."""
+    if neg is None or neg.is_binary():  # as many source as destination slots
+        return (input_id, index.view(2, -1), label, src_time)
+    dst_neg_index = index[2 * B:]
+    if disjoint:
+        dst_neg_index = dst_neg_index.view(-1, B).t()
+    dst_neg_index = dst_neg_index.reshape(B, -1).squeeze(-1)
+    return (input_id, index[:B], index[B:2 * B], dst_neg_index, src_time)
+
+
+def _time_sorted_perm(times, edge_key, col_keys: Tensor, max_col: int):
+    """The reference's ``sort_csc`` (sampler/utils.py:24-42): ``lexsort([time, column])`` as two
+    stable radix sorts, first on the time key (biased to be non-negative), then on the column.
+    ``times``: the int64 time vectors; one host read gives their span, which picks the key dtype.
+    ``edge_key(narrow, key_dtype)`` builds the per-edge time key, where ``narrow(t)`` is ``t``
+    minus the smallest time in the key dtype (applied to a vector at its own length: node times
+    are narrowed at ``[N]`` and only then gathered by source, so there is no ``[E]`` int64 copy).
+    Returns the permutation and the sorted column keys."""
+    full = [t for t in times if t.numel() > 0]
+    lo_t, hi_t = 0, 0
+    if full:
+        lo_t, hi_t = (int(x) for x in torch.stack(
+            [torch.stack([t.min() for t in full]).min(),
+             torch.stack([t.max() for t in full]).max()]).tolist())
+    span = hi_t - lo_t
+    if span >= 2 ** 63:
+        raise ValueError('the times span more than the int64 range')
+    kdt = torch.int32 if span < 2 ** 31 else torch.int64
+    key = edge_key(lambda t: (t - lo_t).to(kdt), kdt)
+    perm1 = _native.index_sort(key, max_value=span)[1]
+    del key
+    sorted_cols, perm2 = _native.index_sort(col_keys[perm1], max_value=max_col)
+    return perm1[perm2], sorted_cols
+
+
+def _relabel_pairs(keys_all: Tensor, keys: Tensor, total, cap: int, max_key: int):
+    """The relabelling of disjoint trees.  A batch node is a pair, one int64 key; ``keys_all``
+    ``[P]`` are the pairs of the batch so far, ``keys`` ``[cap]`` the pairs a hop sampled, the
+    first ``total`` (a host int, or int64 [1] on the device) real and the rest ``max_key``, which
+    sorts last.  One stable sort: the first appearance of a pair is the smallest position of its
+    run.  Returns, over the positions of ``cat([keys_all, keys])``, ``first_of`` (the first
+    position of the entry's pair) and ``rank`` (at the first position of a pair new in this hop:
+    its rank among those, in order of first appearance), then ``new_keys`` ``[cap]`` (the new
+    pairs in that order; unwritten past their count) and ``n_new`` (int64 [1]).  No host read."""
+    dev = keys.device
+    P = keys_all.numel()
+    n_all = P + cap
+    allk = torch.cat([keys_all, keys])
+    sorted_k, perm = _native.index_sort(allk, max_value=max_key)
+    head = torch.ones_like(sorted_k, dtype=torch.bool)
+    head[1:] = sorted_k[1:] != sorted_k[:-1]
+    gid = _native.cumsum(head.to(torch.int64)) - 1
+    headpos = torch.empty(n_all + 1, dtype=torch.int64, device=dev)
+    headpos.scatter_(0, torch.where(head, gid, n_all), perm)   # first position of every pair
+    first_of = torch.empty(n_all, dtype=torch.int64, device=dev)
+    first_of.scatter_(0, perm, headpos[gid])
+    idx = torch.arange(n_all, device=dev)
+    mark = (first_of == idx) & (idx >= P) & (idx < P + total)  # pairs new in this hop
+    rank = _native.cumsum(mark.to(torch.int64)) - 1
+    n_new = rank[-1:] + 1
+    new_keys = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+    new_keys.scatter_(0, torch.where(mark[P:], rank[P:], cap), allk[P:])
+    return first_of, rank, new_keys[:cap], n_new
+
+
 class NeighborSampler:
     r"""k-hop neighbour sampler on the GPU (uniform, biased by ``edge_weight``, or temporal).
 
@@ -263,12 +397,8 @@ class NeighborSampler:
                  subgraph_type: str = 'directional', edge_weight: Optional[Tensor] = None,
                  node_time: Optional[Tensor] = None, edge_time: Optional[Tensor] = None,
                  temporal_strategy: str = 'uniform'):
-        subgraph_type = getattr(subgraph_type, 'value', subgraph_type)  # the reference's enum
-        if subgraph_type not in ('directional', 'bidirectional', 'induced'):
-            raise ValueError(f"unknown subgraph_type '{subgraph_type}'")
-        if temporal_strategy not in ('uniform', 'last'):
-            raise ValueError(f"unknown temporal_strategy '{temporal_strategy}' (expected "
-                             f"'uniform' or 'last')")
+        subgraph_type = _subgraph_type(subgraph_type)
+        _check_temporal_strategy(temporal_strategy)
         self.temporal_strategy = temporal_strategy
         self.is_temporal = node_time is not None or edge_time is not None
         if self.is_temporal:
@@ -333,31 +463,20 @@ class NeighborSampler:
         return w32[self.perm].contiguous()
 
     def _sort_by_time(self, graph, node_time, edge_time) -> None:
-        """The reference's ``sort_csc`` (sampler/utils.py:24-42): ``lexsort([time, col])`` as two
-        stable radix sorts, first on the time key (biased to be non-negative), then on the
-        destination.  ``colptr`` is unchanged; ``row`` / ``perm`` are replaced by the time-sorted
-        ones, and ``time`` keeps ``node_time`` ``[N]`` or ``edge_time`` in slot order."""
+        """:func:`_time_sorted_perm` by (time, destination).  ``colptr`` is unchanged; ``row`` /
+        ``perm`` are replaced by the time-sorted ones, and ``time`` keeps ``node_time`` ``[N]`` or
+        ``edge_time`` in slot order."""
         dev, dt = self.row.device, self.row.dtype
-        E, N = self.row.numel(), self.num_nodes
         self.time = (node_time if node_time is not None else edge_time).to(
             device=dev, dtype=torch.int64).contiguous()
-        if E == 0:
+        if self.row.numel() == 0:
             return
         src, dst = graph[0], graph[1]
-        t = self.time
-        lo_t, hi_t = (int(v) for v in torch.stack([t.min(), t.max()]).tolist()) \
-            if t.numel() else (0, 0)
-        span = hi_t - lo_t
-        if span >= 2 ** 63:
-            raise ValueError('the times span more than the int64 range')
-        kdt = torch.int32 if span < 2 ** 31 else torch.int64
-        biased = (t - lo_t).to(kdt)             # [N] or [E]; node-level: no [E] int64 copy
-        key = biased.index_select(0, src) if node_time is not None else biased
-        perm1 = _native.index_sort(key, max_value=span)[1]
-        del key, biased
-        perm2 = _native.index_sort(dst[perm1], max_value=max(N - 1, 0))[1]
-        perm = perm1[perm2]
-        del perm1, perm2
+        perm, _ = _time_sorted_perm(
+            [self.time],
+            lambda narrow, _: (narrow(self.time).index_select(0, src) if node_time is not None
+                               else narrow(self.time)),
+            dst, max(self.num_nodes - 1, 0))
         self.row = src[perm].contiguous()
         self.perm = perm.to(dt)
         if edge_time is not None:
@@ -373,11 +492,7 @@ class NeighborSampler:
                 raise ValueError("temporal sampling with edge-level time ('edge_time') needs the "
                                  "seed times (NodeSamplerInput.time / the loader's 'input_time')")
             return self.time[seeds.to(device=self.time.device).long()]
-        if not isinstance(time, Tensor) or time.dim() != 1 or time.numel() != seeds.numel():
-            raise ValueError(f"the seed times must be a 1-D tensor with one entry per seed "
-                             f"({seeds.numel()})")
-        if time.is_floating_point() or time.is_complex() or time.dtype == torch.bool:
-            raise ValueError(f"the seed times must be an integer tensor (got {time.dtype})")
+        _check_seed_time(time, seeds.numel())
         return time.to(device=self.row.device, dtype=torch.int64).contiguous()
 
     def _weight(self, k: int) -> Optional[Tensor]:
@@ -439,37 +554,13 @@ class NeighborSampler:
         with binary ones, ``(input_id, src_index, dst_pos_index, dst_neg_index, src_time)`` with
         triplet ones.  ``seed`` fixes the RNG like in :meth:`sample_from_nodes`; the negatives
         draw from a stream of their own."""
-        input_id = label = time = None
-        if isinstance(index, Tensor):
-            if index.dim() != 2 or index.size(0) != 2:
-                raise ValueError(f"the positive edges must be a [2, B] tensor (got "
-                                 f"{list(index.shape)})")
-            src, dst = index[0], index[1]
-        else:
-            if getattr(index, 'input_type', None) is not None:
-                raise NotImplementedError('heterogeneous sampling is out of scope (SURVEY.md §8)')
-            src, dst = index.row, index.col
-            input_id = getattr(index, 'input_id', None)
-            label, time = getattr(index, 'label', None), getattr(index, 'time', None)
-        neg = NegativeSampling.cast(neg_sampling)
-        B = src.numel()
-        if dst.numel() != B or src.dim() != 1 or dst.dim() != 1:
-            raise ValueError('the source and destination of the positive edges must be 1-D '
-                             'tensors of one length')
-        if B == 0:
-            raise ValueError("'sample_from_edges' needs at least one positive edge")
-        if time is not None and not self.is_temporal:
-            raise ValueError("'edge_label_time' is given but the sampler is not temporal (no "
-                             "'node_time' / 'edge_time')")
-        if time is None and self.is_temporal:
-            raise ValueError("a temporal sampler needs the seed-link times ('edge_label_time')")
+        if not isinstance(index, Tensor) and getattr(index, 'input_type', None) is not None:
+            raise NotImplementedError('heterogeneous sampling is out of scope (SURVEY.md §8)')
+        src, dst, input_id, label, time, neg, B = _link_input(index, neg_sampling,
+                                                              self.is_temporal)
         if neg is not None:
             neg.check(self.num_nodes)
-            if neg.is_triplet() and label is not None:
-                raise ValueError("'edge_label' needs to be undefined for 'triplet'-based negative "
-                                 "sampling")
-        if label is not None and label.size(0) != B:
-            raise ValueError(f"'edge_label' needs one entry per positive edge ({B})")
+        _check_link_label(neg, label, B)
         dev, dt = self.colptr.device, self.colptr.dtype
         src = src.to(device=dev, dtype=dt)
         dst = dst.to(device=dev, dtype=dt)
@@ -486,9 +577,7 @@ class NeighborSampler:
             if neg.is_binary():
                 src = torch.cat([src, self._negatives(num_neg, neg, 0, rng, src_time)])
                 dst = torch.cat([dst, self._negatives(num_neg, neg, 1, rng, dst_time)])
-                if label is None:
-                    label = torch.ones(B, device=dev)
-                label = torch.cat([label, label.new_zeros((num_neg, ) + label.shape[1:])])
+                label = _binary_label(label, B, num_neg, dev)
                 if time is not None:
                     src_time = dst_time = time.repeat(1 + math.ceil(neg.amount))[:B + num_neg]
             else:
@@ -500,21 +589,10 @@ class NeighborSampler:
             seeds, inverse = _native.unique_inverse(seeds, max_value=max(self.num_nodes - 1, 0))
         seed_time = torch.cat([src_time, dst_time]) if time is not None else None
         out = self._sample_seeds(seeds, rng, seed_time)
-        if self.disjoint:
+        if self.disjoint:   # local ids are seed positions
             out.batch = out.batch % B
-            order = torch.arange(seeds.numel(), device=dev)
-        if neg is None or neg.is_binary():
-            eli = order.view(2, -1) if self.disjoint else inverse.view(2, -1)
-            out.metadata = (input_id, eli, label, src_time)
-        else:
-            if self.disjoint:
-                src_index, dst_pos_index = order[:B], order[B:2 * B]
-                dst_neg_index = order[2 * B:].view(-1, B).t()
-            else:
-                src_index, dst_pos_index = inverse[:B], inverse[B:2 * B]
-                dst_neg_index = inverse[2 * B:]
-            dst_neg_index = dst_neg_index.reshape(B, -1).squeeze(-1)
-            out.metadata = (input_id, src_index, dst_pos_index, dst_neg_index, src_time)
+            inverse = torch.arange(seeds.numel(), device=dev)
+        out.metadata = _link_metadata(input_id, inverse, label, src_time, neg, B, self.disjoint)
         return out
 
     def _negatives(self, n: int, neg: NegativeSampling, endpoint: int, rng: int,
@@ -680,7 +758,8 @@ class NeighborSampler:
         the ``-1`` path.  The draws of a node depend on its position in the frontier as well, so
         the same graph node in two trees samples independently.  ``seed_time`` (int64 [B], a
         temporal sampler): every frontier node draws from its eligible window, bounded by the seed
-        time of its tree (``pygamd_sample_temporal_window`` -> ``pygamd_sample_neighbors_temporal``)."""
+        time of its tree (``pygamd_sample_temporal_window`` -> ``pygamd_sample_neighbors_temporal``).
+        The relabelling is :func:`_relabel_pairs` at the hop's exact size."""
         dev, dt = self.colptr.device, self.colptr.dtype
         N = self.num_nodes
         B = seeds.numel()
@@ -697,8 +776,9 @@ class NeighborSampler:
                 continue
             rep = self.replace and k >= 0
             hop_seed = (rng * 1_000_003 + hop) & 0x7FFFFFFFFFFFFFFF
+            window = None
             if seed_time is not None:
-                lo, hi, cnt = _native.sample_temporal_window(
+                *window, cnt = _native.sample_temporal_window(
                     self.colptr, self.row, self.time, frontier, seed_time[frontier_tree], k,
                     edge_level=self.edge_level, replace=rep,
                     last=self.temporal_strategy == 'last')
@@ -707,14 +787,9 @@ class NeighborSampler:
             offsets = torch.zeros(frontier.numel() + 1, dtype=dt, device=dev)
             _native.cumsum(cnt, out=offsets[1:])
             total = int(offsets[-1])
-            if seed_time is not None:
-                src_g, dstpos, slot = _native.sample_neighbors_temporal(
-                    self.row, frontier, lo, hi, offsets, total, max(k, 0), hop_seed,
-                    replace=rep, salt_position=True)
-            else:
-                src_g, dstpos, slot = _native.sample_neighbors(
-                    self.colptr, self.row, frontier, offsets, total, max(k, 0), hop_seed,
-                    replace=rep, salt_position=True, weight=self._weight(k))
+            src_g, dstpos, slot = _native.sample_neighbors(
+                self.colptr, self.row, frontier, offsets, total, max(k, 0), hop_seed,
+                replace=rep, salt_position=True, weight=self._weight(k), window=window)
             P = keys_all.numel()
             if total == 0:
                 num_nodes_hop.append(0)
@@ -723,20 +798,9 @@ class NeighborSampler:
                 continue
             tree_e = frontier_tree[dstpos.long()]
             keys = tree_e * N + src_g.to(torch.int64)
-            allk = torch.cat([keys_all, keys])
-            sorted_k, perm = _native.index_sort(allk, max_value=B * N)
-            head = torch.ones_like(sorted_k, dtype=torch.bool)
-            head[1:] = sorted_k[1:] != sorted_k[:-1]
-            gid_sorted = _native.cumsum(head.to(torch.int64)) - 1
-            first = perm[head]                        # first position of every distinct pair
-            gid = torch.empty_like(gid_sorted)
-            gid[perm] = gid_sorted
-            first_of = first[gid[P:]]                 # per sampled edge: first position of its pair
-            mark = torch.zeros(P + total, dtype=torch.int64, device=dev)
-            mark[first[first >= P]] = 1               # pairs that enter the batch in this hop
-            rank = _native.cumsum(mark) - 1
-            new_pos = mark.nonzero().squeeze(1)       # ascending = order of first appearance
-            new_keys = allk[new_pos]
+            first_of, rank, new_keys, n_new = _relabel_pairs(keys_all, keys, total, total, B * N)
+            new_keys = new_keys[:int(n_new)]  # host sync: sizes the next hop (the frontier)
+            first_of = first_of[P:]           # per sampled edge: first position of its pair
             rows.append(torch.where(first_of < P, first_of, P + rank[first_of]).to(dt))
             cols.append((dstpos + frontier_base).to(dt))
             edges.append(self.perm[slot])
@@ -1000,17 +1064,13 @@ class HeteroNeighborSampler:
                  subgraph_type: str = 'directional', output_cls=HeteroSamplerOutput,
                  edge_weight=None, node_time=None, edge_time=None,
                  temporal_strategy: str = 'uniform'):
-        subgraph_type = getattr(subgraph_type, 'value', subgraph_type)
-        if subgraph_type in ('bidirectional', 'induced'):
+        subgraph_type = _subgraph_type(subgraph_type)
+        if subgraph_type != 'directional':
             raise ValueError(f"heterogeneous sampling supports subgraph_type='directional' only "
                              f"(got '{subgraph_type}')")
-        if subgraph_type != 'directional':
-            raise ValueError(f"unknown subgraph_type '{subgraph_type}'")
         if edge_weight is not None:
             raise ValueError("weighted heterogeneous sampling ('edge_weight') is not supported")
-        if temporal_strategy not in ('uniform', 'last'):
-            raise ValueError(f"unknown temporal_strategy '{temporal_strategy}' (expected "
-                             f"'uniform' or 'last')")
+        _check_temporal_strategy(temporal_strategy)
         for name, t in (('node_time', node_time), ('edge_time', edge_time)):
             if t is not None and not isinstance(t, dict):
                 raise ValueError(f"temporal heterogeneous sampling takes '{name}' as a dict keyed "
@@ -1117,44 +1177,31 @@ class HeteroNeighborSampler:
         return node_time, edge_time
 
     def _time_keys(self, eis, live, dev, node_time, edge_time):
-        """The per-edge time keys of a temporal CSC, in the order of the stacked edge list: the
-        edge's time (its source node's, or its own) minus the smallest time of all, 0 for an untimed
-        edge type.  Also fills ``self.time`` (node level: int64 over the global node ids; edge
-        level: the per-edge times, permuted into slot order by the caller).  One host read."""
+        """Fills ``self.time`` (node level: int64 over the global node ids; edge level: the
+        per-edge times in the order of the stacked edge list, permuted into slot order by the
+        caller) and returns the ``times`` and ``edge_key`` of :func:`_time_sorted_perm`: the
+        key of an edge is its time (its source node's, or its own), 0 for an untimed edge type."""
         times = node_time if node_time is not None else edge_time
         vals = {k: v.to(device=dev, dtype=torch.int64).contiguous() for k, v in times.items()}
-        full = [v for v in vals.values() if v.numel() > 0]
-        lo_t, hi_t = 0, 0
-        if full:
-            lo_t, hi_t = (int(x) for x in torch.stack(
-                [torch.stack([v.min() for v in full]).min(),
-                 torch.stack([v.max() for v in full]).max()]).tolist())
-        span = hi_t - lo_t
-        if span >= 2 ** 63:
-            raise ValueError('the times span more than the int64 range')
-        kdt = torch.int32 if span < 2 ** 31 else torch.int64
-        keys = []
+        zeros = (lambda e, dtype: torch.zeros(eis[e].size(1), dtype=dtype, device=dev))
         if node_time is not None:
             self.time = torch.zeros(max(self.node_base[-1], 1), dtype=torch.int64, device=dev)
             for t, v in vals.items():
                 b = self.node_base[self._type_index[t]]
                 self.time[b:b + v.numel()] = v
-            for e in live:
-                s_t = self.edge_types[e][0]
-                keys.append((vals[s_t] - lo_t).to(kdt).index_select(0, eis[e][0].long())
-                            if s_t in vals else
-                            torch.zeros(eis[e].size(1), dtype=kdt, device=dev))
+            of = (lambda e: vals.get(self.edge_types[e][0]))
+            key = (lambda e, narrow: narrow(of(e)).index_select(0, eis[e][0].long()))
         else:
-            per_edge = []
-            for e in live:
-                v = vals.get(self.edge_types[e])
-                per_edge.append(v if v is not None else
-                                torch.zeros(eis[e].size(1), dtype=torch.int64, device=dev))
-                keys.append((v - lo_t).to(kdt) if v is not None else
-                            torch.zeros(eis[e].size(1), dtype=kdt, device=dev))
-            self.time = torch.cat(per_edge) if per_edge else \
+            of = (lambda e: vals.get(self.edge_types[e]))
+            key = (lambda e, narrow: narrow(of(e)))
+            self.time = torch.cat([of(e) if of(e) is not None else zeros(e, torch.int64)
+                                   for e in live]) if live else \
                 torch.zeros(1, dtype=torch.int64, device=dev)
-        return (torch.cat(keys) if keys else None), span
+
+        def edge_key(narrow, kdt):
+            return torch.cat([key(e, narrow) if of(e) is not None else zeros(e, kdt)
+                              for e in live])
+        return list(vals.values()), edge_key
 
     def _build_csc(self, eis, dt, dev, node_time=None, edge_time=None) -> None:
         """The stacked CSC: one stable radix sort of every edge keyed by ``col_base[et] + dst``
@@ -1181,12 +1228,8 @@ class HeteroNeighborSampler:
                 self.edge_types[e][0]]] for e in live])
             pos = torch.cat([torch.arange(eis[e].size(1), device=dev) for e in live])
             if self.is_temporal:
-                tkey, span = self._time_keys(eis, live, dev, node_time, edge_time)
-                p1 = _native.index_sort(tkey, max_value=span)[1]
-                del tkey
-                skeys, p2 = _native.index_sort(keys[p1], max_value=max(C - 1, 0))
-                p = p1[p2]
-                del p1, p2
+                p, skeys = _time_sorted_perm(
+                    *self._time_keys(eis, live, dev, node_time, edge_time), keys, max(C - 1, 0))
                 if self.edge_level:
                     self.time = self.time[p].contiguous()
             else:
@@ -1253,11 +1296,7 @@ class HeteroNeighborSampler:
             idx = seeds.to(device=self.time.device).long() + \
                 self.node_base[self._type_index[input_type]]
             return self.time[idx]
-        if not isinstance(time, Tensor) or time.dim() != 1 or time.numel() != seeds.numel():
-            raise ValueError(f"the seed times must be a 1-D tensor with one entry per seed "
-                             f"({seeds.numel()})")
-        if time.is_floating_point() or time.is_complex() or time.dtype == torch.bool:
-            raise ValueError(f"the seed times must be an integer tensor (got {time.dtype})")
+        _check_seed_time(time, seeds.numel())
         return time.to(device=self.row.device, dtype=torch.int64).contiguous()
 
     def check_seeds(self, input_type: str, seeds) -> None:
@@ -1301,52 +1340,33 @@ class HeteroNeighborSampler:
             raise NotImplementedError(
                 "heterogeneous link-level sampling needs the edge type of the seed links: pass "
                 "(edge_type, [2, B] tensor) or an EdgeSamplerInput with 'input_type'")
-        input_id = label = time = None
         if isinstance(index, (tuple, list)):
             if len(index) != 2:
                 raise ValueError("'index' must be (edge_type, [2, B] tensor)")
-            input_type, ei = index
-            if not isinstance(ei, Tensor) or ei.dim() != 2 or ei.size(0) != 2:
+            input_type, index = index
+            if not isinstance(index, Tensor):
                 raise ValueError(f"the positive edges must be a [2, B] tensor (got "
-                                 f"{list(ei.shape) if isinstance(ei, Tensor) else type(ei)})")
-            src, dst = ei[0], ei[1]
+                                 f"{type(index)})")
         else:
             input_type = getattr(index, 'input_type', None)
             if input_type is None:
                 raise NotImplementedError(
                     "heterogeneous link-level sampling needs the edge type of the seed links "
                     "('input_type' of the EdgeSamplerInput)")
-            src, dst = index.row, index.col
-            input_id = getattr(index, 'input_id', None)
-            label, time = getattr(index, 'label', None), getattr(index, 'time', None)
         et = _edge_type(input_type)
         if et not in self.edge_types:
             raise ValueError(f"the input type '{et}' is not an edge type of the graph "
                              f"({self.edge_types})")
         s_t, d_t = et[0], et[2]
-        neg = NegativeSampling.cast(neg_sampling)
-        B = src.numel()
-        if dst.numel() != B or src.dim() != 1 or dst.dim() != 1:
-            raise ValueError('the source and destination of the positive edges must be 1-D '
-                             'tensors of one length')
-        if B == 0:
-            raise ValueError("'sample_from_edges' needs at least one positive edge")
-        if time is not None and not self.is_temporal:
-            raise ValueError("'edge_label_time' is given but the sampler is not temporal (no "
-                             "'node_time' / 'edge_time')")
-        if time is None and self.is_temporal:
-            raise ValueError("a temporal sampler needs the seed-link times ('edge_label_time')")
+        src, dst, input_id, label, time, neg, B = _link_input(index, neg_sampling,
+                                                              self.is_temporal)
         if neg is not None:
             for w, t in ((neg.src_weight, s_t), (neg.dst_weight, d_t)):
                 if w is not None and w.numel() != self.num_nodes[t]:
                     raise ValueError(f"The 'weight' attribute in 'NegativeSampling' needs to "
                                      f"match the number of nodes {self.num_nodes[t]} of node "
                                      f"type '{t}' (got {w.numel()})")
-            if neg.is_triplet() and label is not None:
-                raise ValueError("'edge_label' needs to be undefined for 'triplet'-based negative "
-                                 "sampling")
-        if label is not None and label.size(0) != B:
-            raise ValueError(f"'edge_label' needs one entry per positive edge ({B})")
+        _check_link_label(neg, label, B)
         self.check_seeds(s_t, src)
         self.check_seeds(d_t, dst)
         dev, dt = self.colptr.device, self.colptr.dtype
@@ -1372,17 +1392,14 @@ class HeteroNeighborSampler:
         n_src = B + (num_neg if binary else 0)
         src_time = None if time is None else seed_time[:n_src]
         if binary:
-            if label is None:
-                label = torch.ones(B, device=dev)
-            label = torch.cat([label, label.new_zeros((num_neg, ) + label.shape[1:])])
+            label = _binary_label(label, B, num_neg, dev)
         si, di = self._type_index[s_t], self._type_index[d_t]
-        inv_src = inv_dst = None
+        inverse = None  # the local id of every seed slot: sources, then destinations
         if si == di:    # one node type: the merged seed vector cat([src, dst])
             seeds = g_seeds - self.node_base[si] if self.node_base[si] else g_seeds
             if not self.disjoint:
                 seeds, inverse = _native.unique_inverse(
                     seeds, max_value=max(self.num_nodes[s_t] - 1, 0))
-                inv_src, inv_dst = inverse[:n_src], inverse[n_src:]
             blocks = [(s_t, seeds)]
         elif self.disjoint:
             blocks = [(s_t, g_seeds[:n_src] - self.node_base[si]),
@@ -1399,29 +1416,21 @@ class HeteroNeighborSampler:
             n_uniq, n_first = torch.cat([n_u, n_lo]).tolist()
             first = uniq[:n_first] - self.node_base[lo_i]
             second = uniq[n_first:n_uniq] - self.node_base[hi_i]
-            inv_src, inv_dst = inverse[:n_src], inverse[n_src:]
-            if si < di:
-                inv_dst = inv_dst - n_first
+            if si < di:     # the ids of the second type count from its own first seed
+                inverse[n_src:] -= n_first
                 blocks = [(s_t, first), (d_t, second)]
             else:
-                inv_src = inv_src - n_first
+                inverse[:n_src] -= n_first
                 blocks = [(s_t, second), (d_t, first)]
         out = self._hops(blocks, rng, seed_time)
-        n_dst = g_seeds.numel() - n_src
         if self.disjoint:
             out.batch = {t: b % B for t, b in out.batch.items()}
             # local ids are seed positions: of node[S] / node[D] for two node types, of the
             # merged vector (destinations after the n_src sources) for one
-            inv_src = torch.arange(n_src, device=dev)
-            inv_dst = torch.arange(n_dst, device=dev) + (n_src if si == di else 0)
-        if neg is None or binary:
-            out.metadata = (input_id, torch.stack([inv_src, inv_dst]), label, src_time)
-        else:
-            dst_neg_index = inv_dst[B:]
-            if self.disjoint:
-                dst_neg_index = dst_neg_index.view(-1, B).t()
-            dst_neg_index = dst_neg_index.reshape(B, -1).squeeze(-1)
-            out.metadata = (input_id, inv_src, inv_dst[:B], dst_neg_index, src_time)
+            inverse = torch.arange(g_seeds.numel(), device=dev)
+            if si != di:
+                inverse[n_src:] -= n_src
+        out.metadata = _link_metadata(input_id, inverse, label, src_time, neg, B, self.disjoint)
         return out
 
     def _link_endpoint(self, node_type: str, weight: Optional[Tensor], draws: bool) -> dict:
@@ -1523,6 +1532,7 @@ class HeteroNeighborSampler:
             touched = [frontier]
         for hop in range(self.num_hops):
             item_begin, table, cap, unbounded = [0], [], 0, False
+            window = None
             for e, et in enumerate(self.edge_types):
                 d = self._type_index[et[2]]
                 k = int(self.num_neighbors[et][hop])
@@ -1536,7 +1546,7 @@ class HeteroNeighborSampler:
                     # the hop's ONE gather of seed times (the work items name the first n_front
                     # entries of the frontier buffers only; the rest is unwritten capacity)
                     ftime = seed_time[ftree[:n_front]]
-                    lo, hi, cnt = _native.hetero_sample_temporal_window(
+                    *window, cnt = _native.hetero_sample_temporal_window(
                         self.colptr, self.row, self.time, frontier, ftime, item_begin, table,
                         self.timed_mask, edge_level=self.edge_level, replace=self.replace,
                         last=self.temporal_strategy == 'last')
@@ -1567,15 +1577,11 @@ class HeteroNeighborSampler:
                 continue
             hop_seed = (rng * 1_000_003 + hop) & 0x7FFFFFFFFFFFFFFF
             total = offsets[-1:].to(torch.int64)
-            if seed_time is not None:
-                src, col, edge, fpos = _native.hetero_sample_neighbors_temporal(
-                    self.row, self.perm, frontier, lo, hi, offsets, cap, item_begin, table,
-                    hop_seed, replace=self.replace, salt_position=True, want_fpos=True)
-            else:
-                src, col, edge, fpos = _native.hetero_sample_neighbors(
-                    self.colptr, self.row, self.perm, frontier, offsets, cap, item_begin, table,
-                    hop_seed, replace=self.replace, salt_position=self.disjoint,
-                    want_fpos=self.disjoint)
+            # (a temporal sampler is disjoint: salted, with the frontier positions)
+            src, col, edge, fpos = _native.hetero_sample_neighbors(
+                self.colptr, self.row, self.perm, frontier, offsets, cap, item_begin, table,
+                hop_seed, replace=self.replace, salt_position=self.disjoint,
+                want_fpos=self.disjoint, window=window)
             if self.disjoint:
                 row, sg, sl, tree_sorted, new_keys, typed, stats = self._relabel_disjoint(
                     keys_all, ftree, fpos, src, total, pos2typed, cap, count, offsets,
@@ -1627,31 +1633,14 @@ class HeteroNeighborSampler:
 
     def _relabel_disjoint(self, keys_all, ftree, fpos, src, total, pos2typed, cap, count,
                           offsets, item_begin, B, S):
-        """The pair-key relabelling of :meth:`NeighborSampler._hops_disjoint` (pair ``tree * S +
-        global id``, one stable sort; first appearance = smallest position of a run) at the hop's
-        static capacity, without a host read, then the typed split of the new pairs."""
+        """:func:`_relabel_pairs` (pair ``tree * S + global id``) at the hop's static capacity,
+        without a host read, then the typed split of the new pairs."""
         dev, dt = src.device, src.dtype
         P = keys_all.numel()
-        n_all = P + cap
         ar = torch.arange(cap, device=dev)
         keys = ftree[fpos.long()] * S + src.long()
         keys = torch.where(ar < total, keys, B * S)       # the unused capacity sorts last
-        allk = torch.cat([keys_all, keys])
-        sorted_k, perm = _native.index_sort(allk, max_value=B * S)
-        head = torch.ones_like(sorted_k, dtype=torch.bool)
-        head[1:] = sorted_k[1:] != sorted_k[:-1]
-        gid = _native.cumsum(head.to(torch.int64)) - 1
-        headpos = torch.empty(n_all + 1, dtype=torch.int64, device=dev)
-        headpos.scatter_(0, torch.where(head, gid, n_all), perm)   # first position of every pair
-        first_of = torch.empty(n_all, dtype=torch.int64, device=dev)
-        first_of.scatter_(0, perm, headpos[gid])
-        idx = torch.arange(n_all, device=dev)
-        mark = (first_of == idx) & (idx >= P) & (idx < P + total)  # pairs new in this hop
-        rank = _native.cumsum(mark.to(torch.int64)) - 1
-        n_new = rank[-1:] + 1
-        new_keys = torch.empty(cap + 1, dtype=torch.int64, device=dev)
-        new_keys.scatter_(0, torch.where(mark[P:], rank[P:], cap), allk[P:])
-        new_keys = new_keys[:cap]
+        first_of, rank, new_keys, n_new = _relabel_pairs(keys_all, keys, total, cap, B * S)
         new_g = (new_keys % S).to(dt) if S > 0 else new_keys.to(dt)
         sg, sl, typed, tree_sorted, stats = _native.hetero_split(
             new_g, n_new, self.node_base, count, offsets, item_begin, want_typed=True,
