@@ -366,7 +366,11 @@ class MultiReduceFunction(Function):
 
 
 class SegmentFunction(Function):
-    """``segment(src, ptr, reduce)`` over contiguous row ranges (utils/_segment.py:11-50)."""
+    """``segment(src, ptr, reduce)`` over contiguous row ranges (utils/_segment.py:11-50).  For
+    min / max the reference replaces an INFINITE extremum by 0 (``torch.where(out.isinf(), 0,
+    out)``, utils/_segment.py:48-49): a segment of -inf masks, or one holding +inf, gives 0 and
+    takes no gradient.  ``_native.spmm_csr`` itself keeps the plain extremum (``scatter`` and the
+    graph aggregations return it as is)."""
 
     @staticmethod
     def forward(ctx, src: Tensor, ptr: Tensor, reduce: str):
@@ -374,12 +378,13 @@ class SegmentFunction(Function):
         n_seg = ptr.numel() - 1
         out = _native.spmm_csr(ptr, None, s2, reduce, n_rows=n_seg)
         ctx.reduce, ctx.src_shape = reduce, src.shape
-        res = _shaped(out, (n_seg, *src.shape[1:]))
         if reduce in ('min', 'max'):
-            ctx.save_for_backward(ptr, s2, res)
-        else:
-            ctx.save_for_backward(ptr)
-        return res
+            # the plain extremum is what the backward compares against; the caller sees 0 where
+            # it is infinite
+            ctx.save_for_backward(ptr, s2, out)
+            return _shaped(torch.where(out.isinf(), 0., out), (n_seg, *src.shape[1:]))
+        ctx.save_for_backward(ptr)
+        return _shaped(out, (n_seg, *src.shape[1:]))
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
@@ -388,17 +393,24 @@ class SegmentFunction(Function):
         n = ctx.src_shape[0]
         if reduce in ('min', 'max'):
             ptr, s2, out = ctx.saved_tensors
-            out = _rows(out)
+            # (a replaced extremum is a constant: nothing of that segment takes a gradient)
+            g2 = torch.where(out.isinf(), 0., g2)
+            # ATen's _segment_reduce backward (the reference's CPU path, utils/_segment.py:48)
+            # counts as "attaining the extremum" every element equal to it AND every NaN
+            # (SegmentReduce.cpp: `at::_isnan(value) || value == output`): a NaN extremum sends
+            # its gradient to the NaN elements.
+            nan = s2.isnan()
             ntie = _native.spmm_tie_count(ptr, None, s2, out, count_self=False)
+            ntie = ntie + _native.spmm_csr(ptr, None, nan.to(s2.dtype), 'sum',
+                                           n_rows=out.size(0))
             index = _native.ptr2index(ptr, n)
             # each row belongs to exactly one segment: grad = [src == out[seg]] * g[seg] / ntie[seg]
             o_e = _native.gather_rows(out, index)
-            # ATen's _segment_reduce backward (the reference's CPU path, utils/_segment.py:48)
-            # averages over the tied extrema ONLY where the incoming gradient is positive
-            # (SegmentReduce.cpp: `if (grad_input > 0) grad_input /= counter`); a negative
-            # gradient reaches every tied element undivided.  Matched as is.
+            # It averages over the tied extrema ONLY where the incoming gradient is positive
+            # (`if (grad_input > 0) grad_input /= counter`); a negative gradient reaches every
+            # tied element undivided.  Matched as is.
             g_e = _native.gather_rows(torch.where(g2 > 0, g2 / ntie.clamp(min=1), g2), index)
-            grad = torch.where(s2 == o_e, g_e, torch.zeros_like(g_e))
+            grad = torch.where((s2 == o_e) | nan, g_e, torch.zeros_like(g_e))
         else:
             (ptr,) = ctx.saved_tensors
             index = _native.ptr2index(ptr, n)

@@ -141,7 +141,10 @@ __global__ void __launch_bounds__(kBlock)
       continue;
     }
     const int64_t o = g * ldo + f;
-    grad_src[e * ldg + f] = (src[e * lds + f] == out[o]) ? grad_out[o] / ntie[o] : 0.f;
+    // (a product, as ATen's scatter_reduce backward forms it: a NaN extremum equals no element,
+    // ntie is 0 and the whole group gets 0 * (g / 0) = NaN, not a silent 0)
+    const float w = grad_out[o] / ntie[o];
+    grad_src[e * ldg + f] = (src[e * lds + f] == out[o]) ? w : 0.f * w;
   }
 }
 

@@ -23,10 +23,16 @@ __device__ __forceinline__ float column_reduce(float v, int H) {
 }
 
 // Generic "values of segment `seg`" accessor: Plain reads src[k*H+h]; Gat builds the logit.
+// `shift(m)`: what is subtracted for a column maximum m.  The reference's pointer branch takes
+// the maximum from segment(..., 'max'), which replaces an INFINITE extremum by 0
+// (utils/_segment.py:48-49): an all -inf segment gives 0 / 1e-16 = 0 there, [1, +inf] gives
+// [0, NaN].  Its index branch, which GATConv calls, subtracts the plain maximum (NaN for an all
+// -inf group).  One select per segment and column.
 template <typename IdxT>
 struct PlainLoader {
   const float* __restrict__ src;
   __device__ __forceinline__ void begin(int64_t) const {}
+  __device__ __forceinline__ float shift(float m) const { return fabsf(m) == INFINITY ? 0.f : m; }
   __device__ __forceinline__ float at(int64_t k, int h, int64_t H) const {
     return src[k * H + h];
   }
@@ -40,6 +46,7 @@ struct GatLoader {
   float slope;
   int64_t row;
   __device__ __forceinline__ void begin(int64_t r) { row = r; }
+  __device__ __forceinline__ float shift(float m) const { return m; }
   __device__ __forceinline__ float pre(int64_t k, int h, int64_t H) const {
     return alpha_src[static_cast<int64_t>(col[k]) * H + h] + alpha_dst[row * H + h];
   }
@@ -97,7 +104,7 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
       for (int i = 0; i < kSegKeep; ++i) m = fmaxf(m, v[q][i]);
       for (int64_t k = kt; k < e; k += kstep) m = fmaxf(m, lq.at(k, h, H));
-      m = column_reduce<true>(m, static_cast<int>(H));
+      m = lq.shift(column_reduce<true>(m, static_cast<int>(H)));
       float sum = 0.f;
 #pragma unroll
       for (int i = 0; i < kSegKeep; ++i)
@@ -125,7 +132,7 @@ __global__ void __launch_bounds__(kBlock)
     const int64_t kstep = kWave / H;
     float m = -INFINITY;
     for (int64_t k = k0; k < e; k += kstep) m = fmaxf(m, ld.at(k, h, H));
-    m = column_reduce<true>(m, static_cast<int>(H));
+    m = ld.shift(column_reduce<true>(m, static_cast<int>(H)));
     float sum = 0.f;
     for (int64_t k = k0; k < e; k += kstep) sum += expf(ld.at(k, h, H) - m);
     sum = column_reduce<false>(sum, static_cast<int>(H)) + 1e-16f;
@@ -134,6 +141,7 @@ __global__ void __launch_bounds__(kBlock)
     for (int64_t h = lane; h < H; h += kWave) {
       float m = -INFINITY;
       for (int64_t k = s; k < e; ++k) m = fmaxf(m, ld.at(k, static_cast<int>(h), H));
+      m = ld.shift(m);
       float sum = 0.f;
       for (int64_t k = s; k < e; ++k) sum += expf(ld.at(k, static_cast<int>(h), H) - m);
       sum += 1e-16f;
@@ -147,7 +155,13 @@ __global__ void __launch_bounds__(kBlock)
 // out[seg, h] = log(sum_{k in seg} exp(src[k, h] - m)) + m with m = the segment maximum (0 for an
 // empty segment, whose result is 0: log(0) = -inf is mapped to 0 by the reference's
 // nan_to_num(neginf=0)).  Same lane mapping as the softmax: for narrow power-of-two H the wave
-// covers 64 / H rows per pass.  BWD: grad_src[k, h] = exp(src[k, h] - out[seg, h]) * g[seg, h].
+// covers 64 / H rows per pass.  BWD: grad_src[k, h] = softmax_seg(src)[k, h] * g[seg, h].
+// Non-finite segments, as the reference has them: all -inf -> -inf, one holding +inf -> +inf
+// (its nan_to_num also maps the NaN of inf - inf to 0, leaving the maximum), one holding a NaN ->
+// NaN (its amax propagates it; fmaxf drops it).  For an INFINITE maximum the exponentials are
+// shifted by 0 instead: the sum is then 0 (all -inf), +inf, or NaN exactly when an element is NaN
+// — and for a finite maximum the largest term is 1, so the sum is NaN only for a NaN element.
+// One select per segment and column; no element is tested.
 template <typename IdxT, bool BWD>
 __global__ void __launch_bounds__(kBlock)
     segment_logsumexp_kernel(const float* __restrict__ src, const IdxT* __restrict__ ptr,
@@ -164,17 +178,28 @@ __global__ void __launch_bounds__(kBlock)
   const int64_t koff = narrow ? lane / H : 0;
   for (int64_t h = narrow ? lane % H : lane; h < H; h += hstep) {
     if (BWD) {
-      const float lse = out[seg * H + h];
-      const float g = grad_out[seg * H + h];
+      // The in-segment softmax from the maximum and the sum again (the segment is L2-resident),
+      // not exp(src - out): out = m + log(sum) is rounded at the magnitude of m, and half an ulp
+      // of 1e4 was 2e-4 in every gradient of a segment of 1e4-sized logits.  Same shift as the
+      // forward, so a segment whose result is not finite gets a gradient that is not finite.
+      float m = -INFINITY;
+      for (int64_t k = s + koff; k < e; k += kstep) m = fmaxf(m, src[k * H + h]);
+      if (narrow) m = column_reduce<true>(m, static_cast<int>(H));
+      const float shift = fabsf(m) == INFINITY ? 0.f : m;
+      float sum = 0.f;
+      for (int64_t k = s + koff; k < e; k += kstep) sum += expf(src[k * H + h] - shift);
+      if (narrow) sum = column_reduce<false>(sum, static_cast<int>(H));
+      const float scale = e > s ? grad_out[seg * H + h] / sum : 0.f;
       for (int64_t k = s + koff; k < e; k += kstep)
-        grad_src[k * H + h] = expf(src[k * H + h] - lse) * g;
+        grad_src[k * H + h] = expf(src[k * H + h] - shift) * scale;
     } else {
       float m = -INFINITY;
       for (int64_t k = s + koff; k < e; k += kstep) m = fmaxf(m, src[k * H + h]);
       if (narrow) m = column_reduce<true>(m, static_cast<int>(H));
       if (e <= s) m = 0.f;
+      const float shift = fabsf(m) == INFINITY ? 0.f : m;
       float sum = 0.f;
-      for (int64_t k = s + koff; k < e; k += kstep) sum += expf(src[k * H + h] - m);
+      for (int64_t k = s + koff; k < e; k += kstep) sum += expf(src[k * H + h] - shift);
       if (narrow) sum = column_reduce<false>(sum, static_cast<int>(H));
       const float l = logf(sum);
       if (koff == 0) out[seg * H + h] = (l == -INFINITY ? 0.f : l) + m;

@@ -23,6 +23,30 @@ namespace pygamd {
 constexpr int kCeRpw = 4;                                   // rows per wave (<= 256 classes)
 constexpr int kCeRowsPerBlock = kWavesPerBlock * kCeRpw;
 
+// How a row with maximum mx and se = sum exp(v - mx) forms p = softmax(v) = exp(v - sub) * mul and
+// its loss.  Up to |mx| < 16 the log-sum-exp itself is subtracted, lse = mx + log(se): it stays
+// below 32, so its rounding is at most 2^-20 relative in p, and a row costs no division.  Beyond
+// that (and for a maximum that is not finite) lse would be rounded at the magnitude of mx — half
+// an ulp of 1e4 is 5e-4 in every p of a row of 1e4-sized logits — so the maximum alone is
+// subtracted: p = exp(v - mx) / se, loss = log(se) - (v[label] - mx).  One select per row.
+constexpr float kCeLseMax = 16.f;
+struct CeShift {
+  float sub, mul, mx, lg;
+  bool wide;
+  __device__ __forceinline__ float loss(float v_label) const {
+    return wide ? lg - (v_label - mx) : sub - v_label;
+  }
+};
+__device__ __forceinline__ CeShift ce_shift(float mx, float se) {
+  CeShift cs;
+  cs.wide = !(fabsf(mx) < kCeLseMax);
+  cs.mx = mx;
+  cs.lg = logf(se);
+  cs.sub = cs.wide ? mx : mx + cs.lg;
+  cs.mul = cs.wide ? 1.f / se : 1.f;
+  return cs;
+}
+
 // One wave per row: max, sum of exp, the row's loss, the row's gradient.  Labels:
 // y[label_idx[r]] (label_idx NULL: y[r]); a label outside [0, C) contributes no loss and a zero
 // gradient row and raises *err_flag (the reference's device assert), the mean still divides by B
@@ -84,18 +108,18 @@ __global__ void __launch_bounds__(kBlock)
         if (lane + u * kWave < C) se += expf(v[q][u] - mx);
 #pragma unroll
       for (int o = kWave / 2; o > 0; o >>= 1) se += __shfl_xor(se, o, kWave);
-      const float lse = mx + logf(se);
+      const CeShift cs = ce_shift(mx, se);
       float* __restrict__ grow = grad + (r0 + q) * ldg;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int c = lane + u * kWave;
         if (c < C) {
-          const float p = expf(v[q][u] - lse);
+          const float p = expf(v[q][u] - cs.sub) * cs.mul;
           grow[c] = lab_ok ? (p - (c == lab[q] ? 1.f : 0.f)) * inv_b : 0.f;
         }
       }
       if (lane == 0) {
-        row_loss[r0 + q] = lab_ok ? lse - logits[src[q] * ld + (lab_ok ? lab[q] : 0)] : 0.f;
+        row_loss[r0 + q] = lab_ok ? cs.loss(logits[src[q] * ld + (lab_ok ? lab[q] : 0)]) : 0.f;
         if (!lab_ok && err_flag) atomicOr(err_flag, 1);
       }
     }
@@ -113,14 +137,14 @@ __global__ void __launch_bounds__(kBlock)
     for (int c = lane; c < C; c += kWave) se += expf(row[c] - mx);
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) se += __shfl_xor(se, o, kWave);
-    const float lse = mx + logf(se);
+    const CeShift cs = ce_shift(mx, se);
     float* __restrict__ grow = grad + (r0 + q) * ldg;
     for (int c = lane; c < C; c += kWave) {
-      const float p = expf(row[c] - lse);
+      const float p = expf(row[c] - cs.sub) * cs.mul;
       grow[c] = lab_ok ? (p - (c == lab[q] ? 1.f : 0.f)) * inv_b : 0.f;
     }
     if (lane == 0) {
-      row_loss[r0 + q] = lab_ok ? lse - row[lab_ok ? lab[q] : 0] : 0.f;
+      row_loss[r0 + q] = lab_ok ? cs.loss(row[lab_ok ? lab[q] : 0]) : 0.f;
       if (!lab_ok && err_flag) atomicOr(err_flag, 1);
     }
   }

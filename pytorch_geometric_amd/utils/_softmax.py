@@ -13,7 +13,14 @@ def softmax(src: Tensor, index: Optional[Tensor] = None, ptr: Optional[Tensor] =
     r"""Sparsely evaluated softmax: groups the rows of :obj:`src` by :obj:`index` (or by the CSR
     pointer :obj:`ptr` for sorted inputs) and normalises within each group — drop-in for
     ``torch_geometric.utils.softmax`` (torch_geometric/utils/_softmax.py:12-92), including the
-    detached maximum and the ``1e-16`` added to the denominator."""
+    detached maximum and the ``1e-16`` added to the denominator.
+
+    ``-inf`` entries next to finite ones are masked out: weight and gradient exactly 0.  The
+    two forms differ on non-finite groups exactly as the reference's do: with ``ptr`` (and
+    ``dim=0``) the subtracted maximum comes from ``segment(..., 'max')``, which is 0 where the
+    maximum is infinite, so a group of ``-inf`` only gives 0 and ``[1, +inf]`` gives ``[0, NaN]``;
+    with ``index`` the plain maximum is subtracted and both groups are NaN throughout.  A NaN
+    makes its whole group NaN in either form."""
     _require_fp32(src, 'softmax')
     dim = dim + src.dim() if dim < 0 else dim
     if ptr is not None and ptr.dim() == 1 and dim == 0:

@@ -1,5 +1,6 @@
 """Pins oracle/pyg_oracle.py against the vectors the REAL reference produced
 (tests/golden/make_golden.py) and against the reference's own known-answer tests."""
+import pytest
 import torch
 
 from oracle import pyg_oracle as O
@@ -306,3 +307,107 @@ def test_softmax_and_powermean_aggregation(golden_aggr):
         close(grads[0], case['grad_x'], 1e-5)
         if param is not None:
             close(grads[1], case['grad_param'], 1e-4)
+
+
+# ---- non-finite inputs of the softmax / logsumexp / extremum calls ---------------------------------
+@pytest.fixture(scope='module')
+def golden_nonfinite():
+    from tests import _nonfinite_cases as NF
+    return NF.load()
+
+
+def close_nonfinite(a, b, what=''):
+    """NaN for NaN, same-signed infinities exactly, the module's tolerance on the finite rest."""
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    assert torch.equal(a.isnan(), b.isnan()), f'{what}: NaN pattern'
+    inf = b.isinf()
+    assert torch.equal(a.isinf(), inf) and torch.equal(a[inf], b[inf]), f'{what}: infinities'
+    fin = b.isfinite()
+    assert torch.allclose(a[fin], b[fin], atol=ATOL, rtol=1e-6), \
+        (what, (a[fin] - b[fin]).abs().max())
+
+
+def nonfinite_calls(I, L, to=lambda t: t):
+    """name -> (fn, input, grad_out) of every call of the fixture, on full-width inputs; ``L``
+    is the library (the oracle here, the HIP package in tests/test_gpu_nonfinite.py)."""
+    from tests import _nonfinite_cases as NF
+    H, cols, seed = I['H'], I['cols'], I['seed']
+    src = NF.full(I['src'], H, cols, seed)
+    g_row = NF.full(I['grad_row'], H, cols, seed + 1) / 3
+    g_seg = NF.full(I['grad_seg'], H, cols, seed + 2) / 3
+    g_row[:, cols], g_seg[:, cols] = I['grad_row'], I['grad_seg']
+    ptr, index, perm, S = to(I['ptr']), to(I['index']), I['perm'], len(I['kinds'])
+    index_u = to(I['index'][perm])
+    calls = {
+        'softmax_ptr': (lambda s: L.softmax(s, None, ptr), src, g_row),
+        'softmax_index': (lambda s: L.softmax(s, index, num_nodes=S), src, g_row),
+        'softmax_shuffled': (lambda s: L.softmax(s, index_u, num_nodes=S), src[perm], g_row[perm]),
+        'softmax_dim1': (lambda s: L.softmax(s.t(), index, num_nodes=S, dim=-1).t(), src, g_row),
+        'lse_dim0': (lambda s: L.segment_logsumexp(s, ptr, 0), src, g_seg),
+        'lse_dim1': (lambda s: L.segment_logsumexp(s.t(), ptr, 1).t(), src, g_seg),
+    }
+    for r in ('sum', 'mean', 'min', 'max'):
+        calls[f'segment_{r}'] = (lambda s, r=r: L.segment(s, ptr, r), src, g_seg)
+    for r in ('sum', 'mean', 'min', 'max', 'mul'):
+        calls[f'scatter_{r}'] = (lambda s, r=r: L.scatter(s, index_u, 0, S, r), src[perm], g_seg)
+    return calls
+
+
+def test_nonfinite_fixture_layout(golden_nonfinite):
+    from tests import _nonfinite_cases as NF
+    for H in NF.WIDTHS:
+        I = golden_nonfinite[f'H{H}']
+        NF.check_layout(H, I['kinds'], I['ptr'])
+        c, ptr = I['cols'].index(I['col']), I['ptr']
+        for i, kind in enumerate(I['kinds']):
+            if kind:  # the special values sit in the special column, bit for bit
+                want = torch.tensor(NF.special_values(kind, H))
+                got = I['src'][ptr[i]:ptr[i + 1], c]
+                assert torch.equal(got.view(torch.int32), want.view(torch.int32)), (H, kind)
+        others = [j for j in range(len(I['cols'])) if j != c]
+        assert bool(I['src'][:, others].isfinite().all()) and bool(I['clean_col'].isfinite().all())
+
+
+def test_oracle_reproduces_the_reference_on_nonfinite_inputs(golden_nonfinite):
+    from tests import _nonfinite_cases as NF
+    for H in NF.WIDTHS:
+        I = golden_nonfinite[f'H{H}']
+        calls = nonfinite_calls(I, O)
+        assert set(calls) == set(I['results'])
+        for name, (fn, src, go) in calls.items():
+            out, (grad, ) = grad_of(fn, [src], go)
+            ref = I['results'][name]
+            close_nonfinite(out[:, I['cols']], ref['out'], f'H={H} {name}')
+            close_nonfinite(grad[:, I['cols']], ref['grad'], f'H={H} {name} gradient')
+
+
+def test_nonfinite_table_of_the_reference(golden_nonfinite):
+    """The reference's answers the HIP path is held to (tests/test_gpu_nonfinite.py), as recorded
+    in the fixture AND as the oracle gives them."""
+    inf, nan = float('inf'), float('nan')
+    table = [  # (call, segment kind, expected values of the special column)
+        ('lse_dim0', 'neginf_2', [-inf]),
+        ('lse_dim0', 'neginf_1', [-inf]),
+        ('lse_dim0', 'posinf', [inf]),
+        ('lse_dim0', 'nan', [nan]),
+        ('softmax_ptr', 'neginf_2', [0., 0.]),
+        ('softmax_ptr', 'posinf', [0., nan]),
+        ('softmax_index', 'neginf_2', [nan, nan]),
+        ('segment_max', 'neginf_2', [0.]),
+        ('segment_max', 'posinf', [0.]),
+        ('segment_min', 'neginf_2', [0.]),
+        ('scatter_max', 'neginf_2', [-inf]),
+        ('scatter_max', 'posinf', [inf]),
+    ]
+    for H in (1, 8, 100):
+        I = golden_nonfinite[f'H{H}']
+        calls, ptr, c = nonfinite_calls(I, O), I['ptr'], I['cols'].index(I['col'])
+        for name, kind, want in table:
+            i = I['kinds'].index(kind)
+            per_row = name.startswith('softmax')
+            rows = slice(int(ptr[i]), int(ptr[i + 1])) if per_row else slice(i, i + 1)
+            fn, src, _ = calls[name]
+            want = torch.tensor(want)
+            for got in (I['results'][name]['out'][rows, c], fn(src)[rows, I['col']]):
+                assert torch.equal(got.nan_to_num(nan=12345.), want.nan_to_num(nan=12345.)), \
+                    (H, name, kind, got)
