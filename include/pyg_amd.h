@@ -1094,7 +1094,16 @@ PYGAMD_API int pygamd_adam_step(float* param, const float* grad, float* exp_avg,
  * pygamd_spmm_csr (reduce SUM or MEAN, no edge weights; x / ldx = the rows that are gathered;
  * out / ldo = the global agg buffer, always required: hub rows are aggregated there first by the
  * two-stage hub kernels, and with save_agg != 0 every row is stored there once for the weight
- * gradient).  Supported: F % 4 == 0, F <= 256, Fo <= 256, 16-byte aligned operands (query below);
+ * gradient).
+ * save_agg = PYGAMD_AGG_GIVEN ("rows given"): out / ldo ALREADY holds the aggregated row of every
+ * destination row, in the final (mean-scaled) form a save_agg = 1 launch on the same graph and
+ * gather source leaves there — the kernel reads those rows as a coalesced stream and does not
+ * gather: rowptr, col, x and the hub plan are not read (rowptr / col / x may be NULL), the hub
+ * pre-pass does not run and nothing is stored back.  y, relu_bits_out, y_scaled and
+ * compressed_out are bit for bit those of the save_agg = 1 launch that wrote the rows.  Needs
+ * out != NULL and ldo >= F (PYGAMD_ERR_INVALID_ARG); not with x_format = PYGAMD_X_COMPRESSED
+ * (PYGAMD_ERR_UNSUPPORTED).  The workspace query leaves the hub partials out in this mode.
+ * Supported: F % 4 == 0, F <= 256, Fo <= 256, 16-byte aligned operands (query below);
  * otherwise PYGAMD_ERR_UNSUPPORTED and the caller runs pygamd_spmm_csr + pygamd_linear_forward.
  * relu_bits_out (ceil(n_rows / 32) * ld_bits * 32 words or NULL; needs relu != 0): [y > 0] as
  * one bit per element in the tiled layout of pygamd_spmm_args.relu_bits — the form of the ReLU mask
@@ -1102,6 +1111,7 @@ PYGAMD_API int pygamd_adam_step(float* param, const float* grad, float* exp_avg,
  * (ld_bits >= ceil(Fo / 32)).
  * Workspace: pygamd_sage_layer_fused_workspace_bytes (pygamd_spmm_csr_workspace_bytes(graph)
  * suffices in PYGAMD_GEMM_FP32 mode).                                                              */
+#define PYGAMD_AGG_GIVEN 2 /* save_agg: read the aggregated rows from out / ldo, do not gather */
 PYGAMD_API int pygamd_sage_layer_forward_supported(int64_t F, int64_t Fo, int reduce);
 PYGAMD_API int pygamd_sage_layer_forward(const pygamd_spmm_args* graph, const float* x_root,
                                          int64_t ld_root, const float* w, int64_t ldw,
@@ -1111,7 +1121,7 @@ PYGAMD_API int pygamd_sage_layer_forward(const pygamd_spmm_args* graph, const fl
                                          size_t workspace_bytes, void* stream);
 
 /* The same kernel with every epilogue it has, as one argument block (zero-initialise, fill what is
- * needed).  Beyond pygamd_sage_layer_forward:
+ * needed; save_agg as for pygamd_sage_layer_forward, PYGAMD_AGG_GIVEN included).  Beyond it:
  *  - mask_bits: y = bit ? y : 0 from a one-bit-per-element ReLU mask in the tiled layout of
  *    pygamd_spmm_args.relu_bits.  With the transposed graph, x = the (degree-scaled) gradient rows
  *    and w = [W_l^T | W_r^T] this launch IS a SAGEConv layer's input gradient,
@@ -1135,7 +1145,7 @@ typedef struct pygamd_sage_fused_args {
   const float* bias;         /* [Fo] or NULL                            */
   int64_t Fo;
   int32_t relu;
-  int32_t save_agg;
+  int32_t save_agg;          /* 0, 1 (store the rows) or PYGAMD_AGG_GIVEN (read them back)     */
   float* y;                  /* [n_rows, Fo]                            */
   int64_t ldy;
   uint32_t* relu_bits_out;   /* NULL or [y > 0] as bits (needs relu)    */

@@ -15,6 +15,7 @@ from .edge_index import EdgeIndex, as_edge_index, clear_cache, set_cache_enabled
 from .index import index2ptr, ptr2index
 from . import utils
 from . import nn
+from .nn.models._fused_sage import clear_aggregation_cache
 
 __version__ = '0.1.0'
 
@@ -60,6 +61,7 @@ def binding_status() -> str:
     return _compiled.status()
 
 
-__all__ = ['EdgeIndex', 'as_edge_index', 'clear_cache', 'set_cache_enabled', 'index2ptr',
+__all__ = ['EdgeIndex', 'as_edge_index', 'clear_cache', 'clear_aggregation_cache',
+           'set_cache_enabled', 'index2ptr',
            'ptr2index', 'utils', 'nn', 'build', 'load_library', 'lib_path', 'PygAmdError',
            'set_gemm_mode', 'get_gemm_mode', 'check_index_errors', 'binding_status']

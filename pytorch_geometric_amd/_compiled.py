@@ -15,7 +15,7 @@ from . import _build, _lib
 _state = {'tried': False, 'ns': None, 'error': None}
 
 OPS = ('spmm_csr', 'linear_forward', 'linear_dgrad', 'linear_wgrad', 'sage_layer_fused',
-       'gather_scatter_add')                                   # write into caller-allocated tensors
+       'sage_layer_given', 'gather_scatter_add')                                  # write into caller-allocated tensors
 FUNCTIONAL_OPS = ('index2ptr', 'ptr2index', 'gather_rows', 'sddmm_csr', 'segment_softmax_forward',
                   'segment_softmax_backward')                  # return a fresh tensor
 

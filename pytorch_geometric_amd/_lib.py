@@ -12,6 +12,7 @@ from . import _build
 
 ABI_VERSION = 10
 X_DENSE, X_COMPRESSED = 0, 1  # pygamd_x_format  # PYGAMD_ABI_VERSION of include/pyg_amd.h
+AGG_GIVEN = 2  # PYGAMD_AGG_GIVEN: save_agg of the one-kernel SAGE layer, "rows given"
 IDX_I32, IDX_I64 = 0, 1
 SUM, MEAN, MIN, MAX, MUL, ANY = 0, 1, 2, 3, 4, 5
 REDUCE_IDS = {'sum': SUM, 'add': SUM, 'mean': MEAN, 'min': MIN, 'amin': MIN, 'max': MAX,

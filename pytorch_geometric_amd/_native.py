@@ -1185,11 +1185,13 @@ def sage_layer_forward_supported(F: int, Fo: int, reduce: str) -> bool:
 # A/B timing on the device
 SAGE_FUSED_VARIANT = int(os.environ.get('PYGAMD_FUSED_VARIANT', '0'))
 SAGE_FUSED_PROBE = 0  # scripts/fused_probe.py: skip the gather (1) / MFMA (2) loop of the kernel
+# `save_agg` of sage_layer_forward: `agg` already holds the aggregated rows (PYGAMD_AGG_GIVEN)
+AGG_GIVEN = _lib.AGG_GIVEN
 
 
 def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Tensor, w: Tensor,
                        bias: Optional[Tensor], reduce: str, relu: bool, agg: Tensor, out: Tensor,
-                       hub=None, save_agg: bool = True, hub_threshold: int = None,
+                       hub=None, save_agg=True, hub_threshold: int = None,
                        hub_chunk: int = None, relu_bits: Optional[Tensor] = None,
                        mask_bits: Optional[Tensor] = None, row_scale: Optional[Tensor] = None,
                        out_scaled: Optional[Tensor] = None, variant: Optional[int] = None,
@@ -1198,7 +1200,9 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
                        rowend: Optional[Tensor] = None) -> Tensor:
     """``out = act([aggr(x_gather) | x_root] @ w.T + bias)`` in ONE kernel (csrc/sage_fused.hip);
     ``agg`` ([n_rows, F] view, may be a half of a wider buffer) receives the aggregated rows when
-    ``save_agg`` (hub rows always).  ``relu_bits`` (from :func:`relu_bits_like`, needs
+    ``save_agg`` (hub rows always).  ``save_agg=AGG_GIVEN``: ``agg`` already holds them (left there
+    by a ``save_agg=True`` launch on the same graph and ``x_gather``) and is read instead of the
+    gather — same results bit for bit, no index or source row is touched.  ``relu_bits`` (from :func:`relu_bits_like`, needs
     ``relu``) receives ``out > 0`` as one bit per element (see :func:`relu_bits_like`).
     ``mask_bits`` (same layout): ``out`` is zeroed where its bit is clear — with the transposed
     graph, the degree-scaled gradient rows as ``x_gather``, the unscaled ones as ``x_root`` and
@@ -1210,6 +1214,13 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
     _require_device(rowptr, col, x_gather, x_root, w, bias, agg, out, relu_bits, mask_bits,
                     row_scale, out_scaled, compressed_out)
     variant = SAGE_FUSED_VARIANT if variant is None else variant
+    given = not isinstance(save_agg, bool) and int(save_agg) == AGG_GIVEN
+    save_agg = AGG_GIVEN if given else int(bool(save_agg))
+    if given:
+        if gather_width is not None:
+            raise ValueError("'save_agg=AGG_GIVEN' reads dense aggregated rows: not with a "
+                             "compressed 'x_gather'")
+        hub = None  # (no hub pre-pass: the rows of `agg` are final)
     lab = bool(variant or SAGE_FUSED_PROBE)  # a laboratory schedule / probe: libpyg_amd_lab.so
     C = None if lab else _compiled.ops()
     if (C is not None and gather_width is None and compressed_out is None and rowend is None
@@ -1225,18 +1236,23 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
             _check_bits(relu_bits, n_rows, Fo)
             _check_bits(mask_bits, n_rows, Fo)
             h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
-            with _timed({'n_rows': n_rows, 'n_src': x_gather.size(0), 'nnz': col.numel(), 'F': F,
+            with _timed({'n_rows': n_rows, 'n_src': x_gather.size(0),
+                         'nnz': 0 if given else col.numel(), 'F': F,
                          'reduce': reduce, 'idx_bytes': rowptr.element_size(), 'weighted': False,
                          'src_scale': False, 'accumulate': False, 'n_hub': n_hub,
                          'fused_gemm': {'Fo': Fo, 'K': 2 * F, 'save_agg': bool(save_agg),
                                         'backward': mask_bits is not None,
                                         'scaled_copy': out_scaled is not None}}, x_gather):
-                C.sage_layer_fused(
-                    rowptr, col, x_gather, x_root, w, bias, REDUCE_IDS[reduce], relu, agg, out,
-                    h_rows, h_cptr, n_hub, n_chunks,
-                    HUB_THRESHOLD if hub_threshold is None else hub_threshold,
-                    HUB_CHUNK if hub_chunk is None else hub_chunk, save_agg, relu_bits,
-                    mask_bits, row_scale, out_scaled)
+                if given:  # (its own operator: `agg` is an input there, see torch_binding.cpp)
+                    C.sage_layer_given(rowptr, x_root, w, bias, REDUCE_IDS[reduce], relu, agg,
+                                       out, relu_bits, mask_bits, row_scale, out_scaled)
+                else:
+                    C.sage_layer_fused(
+                        rowptr, col, x_gather, x_root, w, bias, REDUCE_IDS[reduce], relu, agg,
+                        out, h_rows, h_cptr, n_hub, n_chunks,
+                        HUB_THRESHOLD if hub_threshold is None else hub_threshold,
+                        HUB_CHUNK if hub_chunk is None else hub_chunk, save_agg, relu_bits,
+                        mask_bits, row_scale, out_scaled)
             return out
     lib = _lib.load_lab() if lab else _lib.load()
     xr, w2 = _f32_rows(x_root, 'x_root'), _f32_rows(w, 'weight')
@@ -1281,7 +1297,7 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
     f.x_root, f.ld_root = xr.data_ptr(), _ld(xr)
     f.w, f.ldw = w2.data_ptr(), _ld(w2)
     f.bias = 0 if bias is None else bias.data_ptr()
-    f.Fo, f.relu, f.save_agg = Fo, int(relu), int(save_agg)
+    f.Fo, f.relu, f.save_agg = Fo, int(relu), save_agg
     f.y, f.ldy = out.data_ptr(), _ld(out)
     if relu_bits is not None:
         f.relu_bits_out, f.ld_bits_out = relu_bits.data_ptr(), relu_bits.size(1)
@@ -1320,7 +1336,8 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
                                           _stream(xg)), 'sage_layer_forward')
     if sink is not None:
         ev1.record(torch.cuda.current_stream(xg.device))
-        sink.append(({'n_rows': n_rows, 'n_src': xg.size(0), 'nnz': col.numel(), 'F': F,
+        sink.append(({'n_rows': n_rows, 'n_src': xg.size(0),
+                      'nnz': 0 if given else col.numel(), 'F': F,
                       'reduce': reduce, 'idx_bytes': rowptr.element_size(), 'weighted': False,
                       'src_scale': False, 'accumulate': False, 'n_hub': a.n_hub,
                       'compressed_src': gather_width is not None,

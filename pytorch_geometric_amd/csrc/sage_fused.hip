@@ -52,11 +52,20 @@
 // F <= 128 both halves fit side by side and there is one pass.
 // Numerics: error against fp64 at or below the exact instruction's (tests/test_gpu_split_accept.py
 // holds the comparison at the headline shapes); not bitwise an fmaf chain; Inf operands give NaN.
+//
+// Rows given (save_agg = PYGAMD_AGG_GIVEN, both schedules): the aggregated rows of the tile are not
+// gathered but read back from the global agg buffer, where an earlier save_agg = 1 launch on the
+// same graph and gather source left them (the first layer of a full-batch model aggregates the
+// same constant input on every step).  A compile-time variant of each kernel (GIVEN): phase 1 is a
+// coalesced stream of 32 x F / 4 sixteen-byte pieces over the 512 threads next to the root rows'
+// — no row pointer, index or source row is read, no hub pre-pass runs, nothing is stored back.  The
+// tiles / planes receive the same fp32 values and phase 2 is the same code: the outputs are those
+// of the gathering launch bit for bit.
 #include "sage_fused_device.h"
 
 namespace pygamd {
 
-template <typename IdxT, int LPR, bool ZSRC = false>
+template <typename IdxT, int LPR, bool ZSRC = false, bool GIVEN = false>
 __global__ void __launch_bounds__(kFBlock, 4)
     sage_fused_fwd_kernel(SageFusedArgs<IdxT> a) {
   extern __shared__ __align__(16) float smem[];
@@ -72,15 +81,19 @@ __global__ void __launch_bounds__(kFBlock, 4)
   if (row0 >= a.g.n_rows) return;
 
   // ---- phase 1: the aggregated tile and the tile's own (root) rows -> LDS
-  if (threadIdx.x == 0) next_row = 0;
+  if (!GIVEN && threadIdx.x == 0) next_row = 0;
   fused_stage_root<IdxT>(a, smem, xr, agg_ld, row0);
-  __syncthreads();  // next_row armed
-  for (;;) {  // rows are handed out one by one: long and short rows balance over the 8 waves
-    int r = 0;
-    if (lane == 0) r = atomicAdd(&next_row, 1);
-    r = __builtin_amdgcn_readfirstlane(r);
-    if (r >= kFTile) break;
-    fused_gather_row<IdxT, 4, LPR, ZSRC>(a, row0 + r, agg + r * agg_ld, lane);
+  if constexpr (GIVEN) {  // the stored rows: one more coalesced stream
+    fused_stage_given<IdxT>(a, agg, agg_ld, row0);
+  } else {
+    __syncthreads();  // next_row armed
+    for (;;) {  // rows are handed out one by one: long and short rows balance over the 8 waves
+      int r = 0;
+      if (lane == 0) r = atomicAdd(&next_row, 1);
+      r = __builtin_amdgcn_readfirstlane(r);
+      if (r >= kFTile) break;
+      fused_gather_row<IdxT, 4, LPR, ZSRC>(a, row0 + r, agg + r * agg_ld, lane);
+    }
   }
   __syncthreads();  // phase 1 complete: both tiles visible to every wave
   fused_transform<IdxT, 1>(a, agg, xr, agg_ld, row0, wave, lane, a.zout ? zw : nullptr);
@@ -265,7 +278,10 @@ __device__ __forceinline__ void split_pass(const u32x4* __restrict__ wq,
 // One pass: 44.5 KB of planes at F = 100 -> three workgroups per CU if the kernel stays within 80
 // registers; two passes: 50.7 KB at F = 256, two workgroups per CU (the ring of depth 4 and two
 // accumulators take 124 registers).
-template <typename IdxT, int LPR, int NPASS, bool PROBE, bool OCC3 = (NPASS == 1)>
+// GIVEN: the aggregated rows come from the global agg buffer, spread over the threads like the root
+// rows and loaded with them before the first barrier (see the head of this file).
+template <typename IdxT, int LPR, int NPASS, bool PROBE, bool OCC3 = (NPASS == 1),
+          bool GIVEN = false>
 __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
     sage_fused_split_kernel(SageFusedArgs<IdxT> a) {
   constexpr int D = OCC3 ? 2 : 4;
@@ -298,6 +314,18 @@ __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
     if (t < kFTile * units)
       rr[i] = *reinterpret_cast<const f32x4*>(a.x_root + row * a.ld_root + 4 * u);
   }
+  f32x4 ga[GIVEN ? NU : 1];  // GIVEN: the same pieces of the stored aggregated rows
+  if constexpr (GIVEN) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      ga[i] = f32x4{0.f, 0.f, 0.f, 0.f};  // (tile rows past n_rows: zero, as the gather has them)
+      const int t = threadIdx.x + i * kFBlock;
+      const int r = t / units;
+      const int u = t - r * units;
+      if (t < kFTile * units && row0 + r < a.g.n_rows)
+        ga[i] = *reinterpret_cast<const f32x4*>(a.g.out + (row0 + r) * a.g.ldo + 4 * u);
+    }
+  }
   auto root_to_planes = [&](int col0) {
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
@@ -309,7 +337,7 @@ __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
                      rr[i][2], rr[i][3]);
     }
   };
-  if (threadIdx.x == 0) next_row = 0;
+  if (!GIVEN && threadIdx.x == 0) next_row = 0;
   if (fh > F) {  // padding columns [F, f_half) of each resident half: zero in all three planes
     const int pu = (fh - F) / 4;
     const int halves = NPASS == 1 ? 2 : 1;
@@ -325,15 +353,26 @@ __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
     }
   }
   if constexpr (NPASS == 1) root_to_planes(fh);
-  __syncthreads();  // next_row armed
+  if constexpr (GIVEN) {  // the aggregated half: same conversion, columns [0, F)
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      const int t = threadIdx.x + i * kFBlock;
+      const int r = t / units;
+      const int u = t - r * units;
+      if (t < kFTile * units)
+        split_store4(pl + r * row_dw + 2 * u, pstride, ga[i][0], ga[i][1], ga[i][2], ga[i][3]);
+    }
+  } else {
+    __syncthreads();  // next_row armed
 
-  // ---- gather phase: rows handed out one by one, finished rows -> term planes
-  for (; !(PROBE && (a.probe & 1));) {
-    int r = 0;
-    if (lane == 0) r = atomicAdd(&next_row, 1);
-    r = __builtin_amdgcn_readfirstlane(r);
-    if (r >= kFTile) break;
-    split_gather_row<IdxT, LPR>(a, row0 + r, pl + r * row_dw, pstride, lane);
+    // ---- gather phase: rows handed out one by one, finished rows -> term planes
+    for (; !(PROBE && (a.probe & 1));) {
+      int r = 0;
+      if (lane == 0) r = atomicAdd(&next_row, 1);
+      r = __builtin_amdgcn_readfirstlane(r);
+      if (r >= kFTile) break;
+      split_gather_row<IdxT, LPR>(a, row0 + r, pl + r * row_dw, pstride, lane);
+    }
   }
   __syncthreads();  // aggregated half (and, one pass: the root half) visible to every wave
 
@@ -371,6 +410,7 @@ static int launch_fused(const SageFusedArgs<IdxT>& a, hipStream_t st, bool zsrc)
   if constexpr (LPR == kWave) {
     if (zsrc) k = sage_fused_fwd_kernel<IdxT, LPR, true>;
   }
+  if (a.save_agg == PYGAMD_AGG_GIVEN) k = sage_fused_fwd_kernel<IdxT, LPR, false, true>;
   PYGAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds)));
@@ -390,6 +430,8 @@ static int launch_split(const SageFusedArgs<IdxT>& a, hipStream_t st) {
   if constexpr (NPASS == 2) {  // (probe bit 4: the two-pass kernel at three workgroups per CU)
     if (a.probe & 16) k = sage_fused_split_kernel<IdxT, LPR, NPASS, true, true>;
   }
+  if (a.save_agg == PYGAMD_AGG_GIVEN)  // (no gather to probe: the probe bits do not apply)
+    k = sage_fused_split_kernel<IdxT, LPR, NPASS, false, NPASS == 1, true>;
   PYGAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds)));
@@ -406,9 +448,10 @@ static bool split_eligible(const pygamd_spmm_args* graph, const pygamd_sage_fuse
          !f->compressed_out;
 }
 
-static size_t hub_bytes_aligned(const pygamd_spmm_args* graph) {
+// (rows given: no hub pre-pass, so no partials in front of the weight planes)
+static size_t hub_bytes_aligned(const pygamd_spmm_args* graph, const pygamd_sage_fused_args* f) {
   size_t hub = 0;
-  pygamd_spmm_csr_workspace_bytes(graph, &hub);
+  if (f->save_agg != PYGAMD_AGG_GIVEN) pygamd_spmm_csr_workspace_bytes(graph, &hub);
   return static_cast<size_t>(round_up(static_cast<int64_t>(hub), 256));
 }
 
@@ -426,13 +469,15 @@ int sage_layer_fused_run(const pygamd_spmm_args* graph, const pygamd_sage_fused_
   u32x4* wp = nullptr;
   if (split) {
     if (zsrc || f->compressed_out) return PYGAMD_ERR_UNSUPPORTED;
-    const size_t off = hub_bytes_aligned(graph);
+    const size_t off = hub_bytes_aligned(graph, f);
     if (!workspace || workspace_bytes < off + split_planes_bytes(F, Fo))
       return PYGAMD_ERR_WORKSPACE;
     wp = reinterpret_cast<u32x4*>(static_cast<char*>(workspace) + off);
   }
-  rc = sage_fused_hub_pass(graph, workspace, workspace_bytes, stream);
-  if (rc != PYGAMD_OK) return rc;
+  if (f->save_agg != PYGAMD_AGG_GIVEN) {
+    rc = sage_fused_hub_pass(graph, workspace, workspace_bytes, stream);
+    if (rc != PYGAMD_OK) return rc;
+  }
   const int fh = split_f_half(F);
   if (split) {
     const int threads = static_cast<int>(ceil_div(Fo, 32)) * (2 * fh / kPK) * kWave;
@@ -483,12 +528,12 @@ int pygamd_sage_layer_fused_workspace_bytes(const pygamd_spmm_args* graph,
                                             const pygamd_sage_fused_args* f, size_t* bytes) {
   if (!graph || !f || !bytes || graph->F < 0 || f->Fo < 0) return PYGAMD_ERR_INVALID_ARG;
   size_t hub = 0;
-  pygamd_spmm_csr_workspace_bytes(graph, &hub);
+  if (f->save_agg != PYGAMD_AGG_GIVEN) pygamd_spmm_csr_workspace_bytes(graph, &hub);
   // (sized for the split schedule whatever the current mode: the mode may change between the
   // query and the launch)
   const bool planes = graph->x_format == PYGAMD_X_DENSE && !f->compressed_out &&
                       pygamd_sage_layer_forward_supported(graph->F, f->Fo, graph->reduce);
-  *bytes = planes ? hub_bytes_aligned(graph) + split_planes_bytes(graph->F, f->Fo) : hub;
+  *bytes = planes ? hub_bytes_aligned(graph, f) + split_planes_bytes(graph->F, f->Fo) : hub;
   return PYGAMD_OK;
 }
 

@@ -29,7 +29,7 @@ struct SageFusedArgs {
   const float* __restrict__ bias;    // [Fo] or null
   float* __restrict__ y;             // [n_rows, Fo]
   int64_t ldy;
-  int Fo, relu, save_agg;
+  int Fo, relu, save_agg;            // save_agg: 0 / 1, or PYGAMD_AGG_GIVEN (rows-given kernels)
   int f_pad;                         // F rounded up to a multiple of 32
   uint32_t* __restrict__ bits;       // null or [y > 0], one bit per element, 32 x 32 tiles
   int64_t ld_bits;
@@ -323,6 +323,24 @@ __device__ __forceinline__ void fused_stage_root(const SageFusedArgs<IdxT>& a,
   }
 }
 
+// "rows given" (save_agg = PYGAMD_AGG_GIVEN): the aggregated tile comes straight from the global agg
+// buffer, as a coalesced stream over the whole workgroup like the root rows next to it (no row loop,
+// no indices); tile rows past n_rows are zero, as the gather leaves them
+template <typename IdxT>
+__device__ __forceinline__ void fused_stage_given(const SageFusedArgs<IdxT>& a,
+                                                  float* __restrict__ agg, int agg_ld,
+                                                  int64_t row0) {
+  const int units = static_cast<int>(a.g.F) / 4;  // 16-byte pieces per row
+  for (int t = threadIdx.x; t < kFTile * units; t += kFBlock) {
+    const int r = t / units;
+    const int u = t - r * units;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (row0 + r < a.g.n_rows)
+      v = *reinterpret_cast<const f32x4*>(a.g.out + (row0 + r) * a.g.ldo + 4 * u);
+    *reinterpret_cast<f32x4*>(agg + r * agg_ld + 4 * u) = v;
+  }
+}
+
 static inline bool aligned16f(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline int sage_fused_lpr(int64_t F) {
@@ -338,7 +356,9 @@ inline int sage_fused_validate(const pygamd_spmm_args* graph, const pygamd_sage_
   *run = false;
   if (!graph || !f) return PYGAMD_ERR_INVALID_ARG;
   const int64_t F = graph->F, Fo = f->Fo;
-  if (graph->n_rows < 0 || F < 0 || Fo < 0 || graph->ldx < F || graph->ldo < F ||
+  // rows given: the stored rows of `out` stand in for the graph and the gather source
+  const bool given = f->save_agg == PYGAMD_AGG_GIVEN;
+  if (graph->n_rows < 0 || F < 0 || Fo < 0 || (!given && graph->ldx < F) || graph->ldo < F ||
       f->ld_root < F || f->ldw < 2 * F || f->ldy < Fo)
     return PYGAMD_ERR_INVALID_ARG;
   // (col may be NULL only for a graph without edges: it is never dereferenced then)
@@ -352,19 +372,20 @@ inline int sage_fused_validate(const pygamd_spmm_args* graph, const pygamd_sage_
   if (f->y_scaled && (!f->row_scale || f->ldy_scaled < Fo)) return PYGAMD_ERR_INVALID_ARG;
   const bool zsrc = graph->x_format == PYGAMD_X_COMPRESSED;
   if (graph->x_format != PYGAMD_X_DENSE && !zsrc) return PYGAMD_ERR_INVALID_ARG;
+  if (given && zsrc) return PYGAMD_ERR_UNSUPPORTED;  // (the stored rows are dense)
   if (graph->rowend && (graph->n_hub > 0 || zsrc)) return PYGAMD_ERR_UNSUPPORTED;
   if (graph->accumulate_rows != 0) return PYGAMD_ERR_INVALID_ARG;
   if (zsrc && (graph->ldx < F + 12 || graph->src_bits)) return PYGAMD_ERR_INVALID_ARG;
   if (f->compressed_out && (Fo % 32 != 0 || f->ld_compressed < Fo + 12))
     return PYGAMD_ERR_INVALID_ARG;
   if (graph->n_rows == 0) return PYGAMD_OK;
-  if (!graph->rowptr || !graph->x || !graph->out || !f->x_root || !f->w || !f->y)
+  if ((!given && (!graph->rowptr || !graph->x)) || !graph->out || !f->x_root || !f->w || !f->y)
     return PYGAMD_ERR_INVALID_ARG;
   if (graph->idx_dtype != PYGAMD_IDX_I32 && graph->idx_dtype != PYGAMD_IDX_I64)
     return PYGAMD_ERR_INVALID_ARG;
   // 16-byte accesses everywhere
-  if ((graph->ldx % 4) || (graph->ldo % 4) || (f->ld_root % 4) || (f->ldw % 4) ||
-      !aligned16f(graph->x) || !aligned16f(graph->out) || !aligned16f(f->x_root) ||
+  if ((!given && ((graph->ldx % 4) || !aligned16f(graph->x))) || (graph->ldo % 4) ||
+      (f->ld_root % 4) || (f->ldw % 4) || !aligned16f(graph->out) || !aligned16f(f->x_root) ||
       !aligned16f(f->w))
     return PYGAMD_ERR_UNSUPPORTED;
   *run = true;
@@ -422,7 +443,7 @@ inline SageFusedArgs<IdxT> sage_fused_fill(const pygamd_spmm_args* graph,
   a.ldy = f->ldy;
   a.Fo = static_cast<int>(f->Fo);
   a.relu = f->relu ? 1 : 0;
-  a.save_agg = f->save_agg ? 1 : 0;
+  a.save_agg = f->save_agg == PYGAMD_AGG_GIVEN ? PYGAMD_AGG_GIVEN : (f->save_agg ? 1 : 0);
   a.f_pad = static_cast<int>(round_up(F, kFK));
   a.bits = f->relu_bits_out;
   a.ld_bits = f->ld_bits_out;
@@ -440,7 +461,8 @@ inline SageFusedArgs<IdxT> sage_fused_fill(const pygamd_spmm_args* graph,
   return a;
 }
 
-// sage_fused.hip: validation + hub pass + (split: weight pre-pass) + the production launch
+// sage_fused.hip: validation + hub pass (not with the rows given) + (split: weight pre-pass) + the
+// production launch
 int sage_layer_fused_run(const pygamd_spmm_args* graph, const pygamd_sage_fused_args* f,
                          bool split, int probe, void* workspace, size_t workspace_bytes,
                          void* stream);

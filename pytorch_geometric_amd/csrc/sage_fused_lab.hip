@@ -694,8 +694,9 @@ extern "C" int pygamd_lab_sage_layer_fused(const pygamd_spmm_args* graph,
   // mode, with the probe bits they honour (bit 0 = skip the gather, bit 1 = skip the matrix loop)
   if (variant == 5) return sage_layer_fused_run(graph, f, true, probe, workspace, workspace_bytes, stream);
   if (variant == 6) return sage_layer_fused_run(graph, f, false, 0, workspace, workspace_bytes, stream);
-  // compressed rows in / out: the production kernel only
-  if (graph->x_format != PYGAMD_X_DENSE || f->compressed_out) return PYGAMD_ERR_UNSUPPORTED;
+  // compressed rows in / out, rows given: the production kernels only
+  if (graph->x_format != PYGAMD_X_DENSE || f->compressed_out || f->save_agg == PYGAMD_AGG_GIVEN)
+    return PYGAMD_ERR_UNSUPPORTED;
   // (the streamed / producer-consumer schedules read rowptr[row + 1] themselves)
   if (graph->rowend && variant != 5 && variant != 6 && variant != 1) return PYGAMD_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);

@@ -254,7 +254,8 @@ void sage_layer_fused(const Tensor& rowptr, const OptTensor& col, const Tensor& 
                         const Tensor& x_root, const Tensor& w, const OptTensor& bias,
                         int64_t reduce, bool relu, Tensor agg, Tensor out,
                         const OptTensor& hub_rows, const OptTensor& hub_cptr, int64_t n_hub,
-                        int64_t n_chunks, int64_t hub_threshold, int64_t hub_chunk, bool save_agg,
+                        int64_t n_chunks, int64_t hub_threshold, int64_t hub_chunk,
+                        int64_t save_agg /* 0, 1 or PYGAMD_AGG_GIVEN (sage_layer_given) */,
                         const OptTensor& relu_bits, const OptTensor& mask_bits,
                         const OptTensor& row_scale, const OptTensor& out_scaled) {
   const c10::hip::HIPGuardMasqueradingAsCUDA device_guard(rowptr.device());
@@ -300,7 +301,7 @@ void sage_layer_fused(const Tensor& rowptr, const OptTensor& col, const Tensor& 
   f.bias = fptr(b);
   f.Fo = Fo;
   f.relu = relu ? 1 : 0;
-  f.save_agg = save_agg ? 1 : 0;
+  f.save_agg = save_agg == PYGAMD_AGG_GIVEN ? PYGAMD_AGG_GIVEN : (save_agg ? 1 : 0);
   f.y = static_cast<float*>(ptr(out));
   f.ldy = ld(out);
   if (has(relu_bits)) {
@@ -329,6 +330,21 @@ void sage_layer_fused(const Tensor& rowptr, const OptTensor& col, const Tensor& 
   if (ws_bytes > 0)
     ws = at::empty({static_cast<int64_t>(ws_bytes)}, xg.options().dtype(at::kByte));
   check(pygamd_sage_layer_fused(&a, &f, ptr(ws), ws_bytes, cur_stream(xg)), "sage_layer_forward");
+}
+
+// The same launch with the aggregated rows given (PYGAMD_AGG_GIVEN): `agg` is only read, and the
+// operator's schema says so.  The buffer is shared between the steps of a training loop (the
+// first-layer cache of nn/models/_fused_sage.py) and sits among the saved tensors of every forward
+// that used it: marked mutable, a later forward would trip the version check of an earlier graph.
+// Neither the graph's indices nor the gather source are read; `rowptr` gives the row count and the
+// index type only.
+void sage_layer_given(const Tensor& rowptr, const Tensor& x_root, const Tensor& w,
+                      const OptTensor& bias, int64_t reduce, bool relu, const Tensor& agg,
+                      Tensor out, const OptTensor& relu_bits, const OptTensor& mask_bits,
+                      const OptTensor& row_scale, const OptTensor& out_scaled) {
+  sage_layer_fused(rowptr, OptTensor(), x_root, x_root, w, bias, reduce, relu, agg, out,
+                   OptTensor(), OptTensor(), 0, 0, 0, 0, PYGAMD_AGG_GIVEN, relu_bits, mask_bits,
+                   row_scale, out_scaled);
 }
 
 // ---- index / gather side -------------------------------------------------------------------------------
@@ -618,8 +634,12 @@ TORCH_LIBRARY(pyg_amd_c, m) {
       "sage_layer_fused(Tensor rowptr, Tensor? col, Tensor x_gather, Tensor x_root, Tensor w, "
       "Tensor? bias, int reduce, bool relu, Tensor(a!) agg, Tensor(b!) out, Tensor? hub_rows, "
       "Tensor? hub_cptr, int n_hub, int n_chunks, int hub_threshold, int hub_chunk, "
-      "bool save_agg, Tensor(c!)? relu_bits, Tensor? mask_bits, Tensor? row_scale, "
+      "int save_agg, Tensor(c!)? relu_bits, Tensor? mask_bits, Tensor? row_scale, "
       "Tensor(d!)? out_scaled) -> ()");
+  m.def(
+      "sage_layer_given(Tensor rowptr, Tensor x_root, Tensor w, Tensor? bias, int reduce, "
+      "bool relu, Tensor agg, Tensor(a!) out, Tensor(b!)? relu_bits, Tensor? mask_bits, "
+      "Tensor? row_scale, Tensor(c!)? out_scaled) -> ()");
   m.def("index2ptr(Tensor index, int size) -> Tensor");
   m.def("ptr2index(Tensor ptr, int n) -> Tensor");
   m.def("gather_rows(Tensor x, Tensor index) -> Tensor");
@@ -648,6 +668,7 @@ TORCH_LIBRARY_IMPL(pyg_amd_c, CUDA, m) {
   m.impl("linear_dgrad", &linear_dgrad);
   m.impl("linear_wgrad", &linear_wgrad);
   m.impl("sage_layer_fused", &sage_layer_fused);
+  m.impl("sage_layer_given", &sage_layer_given);
   m.impl("index2ptr", &index2ptr);
   m.impl("ptr2index", &ptr2index);
   m.impl("gather_rows", &gather_rows);

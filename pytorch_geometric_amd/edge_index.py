@@ -33,6 +33,7 @@ class CSR:
         self.n_rows, self.n_cols = n_rows, n_cols
         self._hub = None
         self._inv_deg = None
+        self._agg0 = None  # nn/models/_fused_sage.py: the first SAGE layer's cached aggregation
 
     @property
     def hub(self):

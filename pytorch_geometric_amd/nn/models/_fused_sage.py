@@ -26,6 +26,8 @@ applies the mean's ``1/deg`` to the ``grad_agg`` half so that the transposed SpM
 per-edge scale gather, ``linear_wgrad`` as a deterministic split reduction).
 ``PYGAMD_GEMM=lib`` switches back to rocBLAS / hipBLASLt through ``torch.mm`` for comparison."""
 import os
+import threading
+import weakref
 from typing import List, Optional
 
 import torch
@@ -71,6 +73,58 @@ COMPRESS_ROWS = os.environ.get('PYGAMD_COMPRESS_ROWS', '0') != '0'
 # backward of a 'pre' layer: find the all-zero rows of the incoming gradient in the pass that lays
 # it out and skip them in the transposed aggregation (PYGAMD_SPARSE_GRAD=0: read every row)
 SPARSE_GRAD = os.environ.get('PYGAMD_SPARSE_GRAD', '1') != '0'
+# The aggregated rows of a FIRST layer that runs as one kernel on the model input itself depend on
+# the graph and the input features only — in full-batch training and inference the same tensors on
+# every step (the reference caches propagated quantities the same way: GCNConv / SGConv
+# `cached=True`).  The layer stores them anyway (`save_agg`, for the weight gradient); they are kept
+# on the by-destination handle and the next step's launch reads them back instead of gathering
+# (`_native.AGG_GIVEN`: same kernel, same values bit for bit, no index or source row read).  One
+# entry per handle, keyed like the handle cache of edge_index.py on the input tensor's identity,
+# version, address and layout, the reduction and the hub plan's settings; it dies with the graph
+# handle or with the input tensor, whichever goes first.  Never used for an input that takes a
+# gradient or has a history (a hidden activation), nor under stream capture.
+# PYGAMD_CACHE_AGG0=0 (read at every call) switches it off; `clear_aggregation_cache()` drops every
+# entry.  Limit: a write to the input through a raw pointer (the ctypes route of an `out=` entry
+# point) does not bump its version and is not seen — DESIGN.md section 7.
+_agg0_handles = weakref.WeakSet()
+_call = threading.local()  # .recording: autograd's mode at the latest FusedSageStack.apply
+
+
+def cache_agg0_enabled() -> bool:
+    return os.environ.get('PYGAMD_CACHE_AGG0', '1') != '0'
+
+
+def clear_aggregation_cache() -> None:
+    """Drop every cached first-layer aggregation (see ``PYGAMD_CACHE_AGG0``)."""
+    for handle in list(_agg0_handles):
+        handle._agg0 = None
+    _agg0_handles.clear()
+
+
+def _agg0_key(x: Tensor, aggr: str):
+    return (x._version, x.data_ptr(), tuple(x.shape), tuple(x.stride()), aggr,
+            _native.HUB_THRESHOLD, _native.HUB_CHUNK)
+
+
+def _agg0_lookup(handle, x: Tensor, aggr: str) -> Optional[Tensor]:
+    hit = getattr(handle, '_agg0', None)
+    if hit is not None and hit[0]() is x and hit[1] == _agg0_key(x, aggr):
+        return hit[2]
+    return None
+
+
+def _agg0_store(handle, x: Tensor, aggr: str, buf: Tensor) -> None:
+    href = weakref.ref(handle)
+
+    def _drop(ref):
+        h = href()
+        if h is not None and getattr(h, '_agg0', None) is not None and h._agg0[0] is ref:
+            h._agg0 = None
+
+    handle._agg0 = (weakref.ref(x, _drop), _agg0_key(x, aggr), buf)
+    _agg0_handles.add(handle)
+
+
 _side_streams = {}
 # below this many rows the library GEMM stays (cf. _functions.OWN_GEMM_MIN_ROWS: from 1 k rows up
 # the own kernels fill the chip with 64 x 64 tiles and a split over the reduction)
@@ -93,6 +147,13 @@ def _pad4(n: int) -> int:
 
 
 class FusedSageStack(Function):
+    @classmethod
+    def apply(cls, *args):
+        # (forward() itself always runs with autograd off: whether the CALL records decides if an
+        # input without a history may be a hidden activation, see `store0` below)
+        _call.recording = torch.is_grad_enabled()
+        return super().apply(*args)
+
     @staticmethod
     def forward(ctx, x: Tensor, graph: EdgeIndex, aggr: str, reorder: bool,
                 *params: Optional[Tensor]):
@@ -122,8 +183,20 @@ class FusedSageStack(Function):
         split0 = (modes[0] == 'post' and FUSE_LAYER and GEMM_BACKEND == 'own' and x.is_contiguous()
                   and dims[0][0] % 4 == 0 and x.data_ptr() % 16 == 0
                   and _native.sage_layer_forward_supported(dims[0][0], dims[0][1], aggr))
+        # ... and keeps them from step to step when `x` is a constant of the loop (see _agg0_*).
+        # A miss stores the rows only where `x` cannot be a hidden activation in disguise: the call
+        # records (an activation would carry a history), or the stack is a whole model.  A single
+        # layer under no_grad may sit anywhere in a network: it reads an entry, it never makes one.
+        cache0 = (split0 and cache_agg0_enabled() and not ctx.needs_input_grad[0]
+                  and not x.requires_grad and x.grad_fn is None
+                  and not (x.is_cuda and torch.cuda.is_current_stream_capturing()))
+        agg0 = _agg0_lookup(fwd, x, aggr) if cache0 else None
+        store0 = cache0 and agg0 is None and (L > 1 or getattr(_call, 'recording', False))
         if split0:
-            buf = torch.empty(N, dims[0][0], dtype=torch.float32, device=dev)  # agg only
+            # agg only; read-only from here on once it is shared between steps (the backward's
+            # weight gradient reads it, nothing writes it)
+            buf = (torch.empty(N, dims[0][0], dtype=torch.float32, device=dev) if agg0 is None
+                   else agg0)
             inp = x
         elif modes[0] == 'pre' and x.is_contiguous():
             buf, inp = x, x
@@ -177,11 +250,14 @@ class FusedSageStack(Function):
                                                inp if lone else buf[:, Fi:],
                                                wmat, b, aggr, not last,
                                                buf if lone else buf[:, :Fi], dst, hub=fwd.hub,
-                                               save_agg=True,
+                                               save_agg=(_native.AGG_GIVEN
+                                                         if lone and agg0 is not None else True),
                                                relu_bits=None if last else bits[layer + 1],
                                                gather_width=None if zsrc is None else Fi,
                                                compressed_out=znext)
                     relu_done = True
+                    if lone and store0:
+                        _agg0_store(fwd, x, aggr, buf)
                 else:
                     _native.spmm_csr(fwd.ptr, fwd.idx, src, aggr, n_rows=N, hub=fwd.hub,
                                      out=buf[:, :Fi])
