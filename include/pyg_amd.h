@@ -556,6 +556,60 @@ PYGAMD_API int pygamd_gat_edge_softmax_backward(const void* rowptr, const void* 
                                                 int64_t H, float slope, float* grad_alpha_src,
                                                 float* grad_alpha_dst, void* stream);
 
+/* ---- a16: GATv2 attention in one pass ---------------------------------------------------------
+ * nn/conv/gatv2_conv.py:358-378 (edge_update + message + the 'add' aggregation) on a dst-sorted
+ * handle.  For slot k of row i with j = col[k]:
+ *   s[k,h]   = sum_c att[h,c] * leaky_relu(x_l[j,h,c] + x_r[i,h,c], slope)
+ *   alpha    = softmax over the row (maximum subtracted, 1e-16 on the denominator)
+ *   out[i,h] = sum_k alpha[k,h] * x_l[j,h,:]
+ * x_l [n_src, H*C], x_r [>= n_rows, H*C], att [H*C], all contiguous fp32.  alpha is [nnz, H] in
+ * SLOT order and always written; out [n_rows, H*C] may be NULL ("score mode": alpha only).
+ * Supported: H*C <= 512 and H <= 64 (pygamd_gatv2_supported), otherwise status 2.  Rows of more
+ * than hub_threshold slots are walked as the chunks of the hub plan (pygamd_hub_plan with the same
+ * threshold and chunk) and merged in chunk order; the workspace (pygamd_gatv2_workspace_bytes of
+ * that plan's n_chunks) holds the partial results and, for backward_dst, the per-workgroup
+ * partials of the att gradient.  No float atomics: all results are bitwise reproducible.
+ *
+ * backward_dst: grad_s[k,h] = alpha * (d alpha - D), grad_x_r [n_rows, H*C], grad_att [H*C].
+ *   d alpha = <grad_out[i,h,:], x_l[j,h,:]> and D = <grad_out[i,h,:], out[i,h,:]> when grad_out /
+ *   out are given and grad_alpha is NULL; score mode passes grad_alpha [nnz, H] (slot order) and
+ *   NULL for grad_out / out.
+ * backward_src: on the src-sorted handle with slot_map = by-source slot -> by-destination slot,
+ *   grad_x_l[j] = sum_i alpha * grad_out[i] + grad_s * att * leaky_relu'(x_l[j] + x_r[i]); the
+ *   first term is left out when grad_out is NULL (score mode).                                  */
+PYGAMD_API int pygamd_gatv2_supported(int64_t H, int64_t C);
+PYGAMD_API int pygamd_gatv2_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C,
+                                            size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_gatv2_forward(const void* rowptr, const void* col, int idx_dtype,
+                                    const float* x_l, const float* x_r, const float* att,
+                                    int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
+                                    float slope, const void* hub_rows,
+                                    const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
+                                    int64_t hub_threshold, int64_t hub_chunk, float* alpha,
+                                    float* out, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+PYGAMD_API int pygamd_gatv2_backward_dst(const void* rowptr, const void* col, int idx_dtype,
+                                         const float* x_l, const float* x_r, const float* att,
+                                         const float* alpha, const float* grad_out,
+                                         const float* out, const float* grad_alpha,
+                                         int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
+                                         float slope, const void* hub_rows,
+                                         const void* hub_chunk_ptr, int64_t n_hub,
+                                         int64_t n_chunks, int64_t hub_threshold,
+                                         int64_t hub_chunk, float* grad_s, float* grad_x_r,
+                                         float* grad_att, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_gatv2_backward_src(const void* rowptr_t, const void* col_t,
+                                         const void* slot_map, int idx_dtype, const float* x_l,
+                                         const float* x_r, const float* att, const float* alpha,
+                                         const float* grad_s, const float* grad_out,
+                                         int64_t n_src, int64_t n_dst, int64_t H, int64_t C,
+                                         float slope, const void* hub_rows,
+                                         const void* hub_chunk_ptr, int64_t n_hub,
+                                         int64_t n_chunks, int64_t hub_threshold,
+                                         int64_t hub_chunk, float* grad_x_l, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

@@ -568,6 +568,91 @@ class GatAttendFunction(Function):
                 g_att_dst.view(att_dst.shape), None, None, None)
 
 
+def _gatv2_backward(ctx, H, C, x_l, x_r, att, alpha, grad_out2, out2, grad_alpha):
+    """The two launches both GATv2 nodes share: by destination (d s, grad_x_r, grad_att), then by
+    source (grad_x_l).  ``grad_alpha`` given = score mode."""
+    graph = ctx.graph
+    fwd = graph.by_dst()
+    grad_s, g_r, g_att = _native.gatv2_backward_dst(
+        fwd.ptr, fwd.idx, x_l, x_r, att, alpha, H, C, ctx.slope, grad_out=grad_out2, out=out2,
+        grad_alpha=grad_alpha, hub=fwd.hub)
+    g_l = None
+    if ctx.needs_input_grad[0]:
+        bwd = graph.by_src()
+        g_l = _native.gatv2_backward_src(bwd.ptr, bwd.idx, graph.src_slot_to_dst_slot(), x_l, x_r,
+                                         att, alpha, grad_s, H, C, ctx.slope, grad_out=grad_out2,
+                                         n_dst=fwd.n_rows, hub=bwd.hub)
+        g_l = g_l.view(-1, H, C)
+    return g_l, g_r.view(-1, H, C), g_att.view(ctx.att_shape)
+
+
+def _gatv2_check(x_l: Tensor, x_r: Tensor, graph: EdgeIndex, n_dst: int):
+    if x_l.size(0) != graph.num_src_nodes:
+        raise ValueError(f"'x_l' has {x_l.size(0)} rows but the graph has "
+                         f"{graph.num_src_nodes} source nodes")
+    if n_dst != graph.num_dst_nodes or x_r.size(0) < n_dst:
+        raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = {n_dst}, "
+                         f"'x_r' has {x_r.size(0)} rows")
+
+
+class Gatv2AttendFunction(Function):
+    """One GATv2 attention + aggregation step on projected features ``x_l [N_src, H, C]`` (sources)
+    and ``x_r [>= n_dst, H, C]`` (destinations, a prefix): score, softmax per destination and the
+    weighted sum of ``x_l`` (gatv2_conv.py:358-378) in ONE pass over the by-destination slots; the
+    backward is one pass by destination and one by source (csrc/gatv2.hip).  Saved: the inputs,
+    ``alpha [E, H]`` and ``out`` — nothing of size ``E x H*C``."""
+
+    @staticmethod
+    def forward(ctx, x_l: Tensor, x_r: Tensor, att: Tensor, graph: EdgeIndex, slope: float,
+                n_dst: int):
+        _, H, C = x_l.shape
+        _gatv2_check(x_l, x_r, graph, n_dst)
+        fwd = graph.by_dst()
+        xl2, xr2 = x_l.reshape(-1, H * C), x_r.reshape(-1, H * C)
+        alpha, out = _native.gatv2_forward(fwd.ptr, fwd.idx, xl2, xr2, att, H, C, slope,
+                                           hub=fwd.hub)
+        ctx.save_for_backward(xl2, xr2, att, alpha, out)
+        ctx.graph, ctx.slope, ctx.dims, ctx.att_shape = graph, slope, (H, C), att.shape
+        return out.view(fwd.n_rows, H, C)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        xl2, xr2, att, alpha, out = ctx.saved_tensors
+        H, C = ctx.dims
+        g_l, g_r, g_att = _gatv2_backward(ctx, H, C, xl2, xr2, att, alpha, _rows(grad_out), out,
+                                          None)
+        return g_l, g_r, g_att, None, None, None
+
+
+class Gatv2ScoreFunction(Function):
+    """The attention coefficients of :class:`Gatv2AttendFunction` alone: ``alpha [E, H]`` in
+    by-destination slot order, for layers that consume them themselves (dropout on the
+    coefficients, ``return_attention_weights``) and aggregate with ``SpmmFunction(..., 'slot')``."""
+
+    @staticmethod
+    def forward(ctx, x_l: Tensor, x_r: Tensor, att: Tensor, graph: EdgeIndex, slope: float,
+                n_dst: int):
+        _, H, C = x_l.shape
+        _gatv2_check(x_l, x_r, graph, n_dst)
+        fwd = graph.by_dst()
+        xl2, xr2 = x_l.reshape(-1, H * C), x_r.reshape(-1, H * C)
+        alpha, _ = _native.gatv2_forward(fwd.ptr, fwd.idx, xl2, xr2, att, H, C, slope,
+                                         hub=fwd.hub, aggregate=False)
+        ctx.save_for_backward(xl2, xr2, att, alpha)
+        ctx.graph, ctx.slope, ctx.dims, ctx.att_shape = graph, slope, (H, C), att.shape
+        return alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_alpha: Tensor):
+        xl2, xr2, att, alpha = ctx.saved_tensors
+        H, C = ctx.dims
+        g_l, g_r, g_att = _gatv2_backward(ctx, H, C, xl2, xr2, att, alpha, None, None,
+                                          grad_alpha.contiguous())
+        return g_l, g_r, g_att, None, None, None
+
+
 class HeadDotFunction(Function):
     """(a_src, a_dst) = ((x * att_src).sum(-1), (x * att_dst).sum(-1)) for x [N, H, C] and
     att_* [1, H, C] (nn/conv/gat_conv.py:330-332) — one pass over x, one fused backward."""

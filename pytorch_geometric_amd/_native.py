@@ -1096,6 +1096,120 @@ def gat_edge_softmax_backward(rowptr, col, alpha_src, alpha_dst, alpha, grad_alp
     return g_src, g_dst
 
 
+# ---- GATv2 attention (csrc/gatv2.hip) ------------------------------------------------------------
+def gatv2_supported(H: int, C: int) -> bool:
+    """The one-pass kernels serve this head layout (H * C <= 512, H <= 64)."""
+    return bool(_lib.load().pygamd_gatv2_supported(int(H), int(C)))
+
+
+def _gatv2_workspace(lib, n_chunks: int, H: int, C: int, device, needed: bool):
+    if not needed:
+        return None, 0
+    nbytes = ctypes.c_size_t(0)
+    check(lib.pygamd_gatv2_workspace_bytes(n_chunks, H, C, ctypes.byref(nbytes)))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
+
+
+def _gatv2_rows(t: Tensor, name: str, width: int) -> Tensor:
+    if t.dtype != torch.float32 or t.dim() != 2 or t.size(1) != width:
+        raise ValueError(f"'{name}' must be a float32 [n, {width}] tensor (got {t.dtype} "
+                         f"{tuple(t.shape)})")
+    return t.contiguous()
+
+
+def gatv2_forward(rowptr: Tensor, col: Tensor, x_l: Tensor, x_r: Tensor, att: Tensor, H: int,
+                  C: int, slope: float, *, hub=None, aggregate: bool = True):
+    """``(alpha [nnz, H] in slot order, out [n_rows, H * C] | None)`` of one GATv2 attention step
+    on a by-destination handle; ``aggregate=False`` is the score mode (alpha only)."""
+    _require_device(rowptr, col, x_l, x_r, att)
+    lib = _lib.load()
+    W = H * C
+    x_l, x_r = _gatv2_rows(x_l, 'x_l', W), _gatv2_rows(x_r, 'x_r', W)
+    att = att.reshape(-1).contiguous()
+    n_rows = rowptr.numel() - 1
+    if att.numel() != W or x_r.size(0) < n_rows:
+        raise ValueError(f"'att' needs {W} entries and 'x_r' at least {n_rows} rows")
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    alpha = torch.empty(col.numel(), H, dtype=torch.float32, device=x_l.device)
+    out = torch.empty(n_rows, W, dtype=torch.float32, device=x_l.device) if aggregate else None
+    if col.numel() == 0:  # no edges: every row is empty
+        return alpha, (out.zero_() if aggregate else None)
+    ws, ws_bytes = _gatv2_workspace(lib, n_chunks, H, C, x_l.device, n_chunks > 0)
+    with _timed({'kind': 'gatv2', 'op': 'forward' if aggregate else 'score', 'n_rows': n_rows,
+                 'E': col.numel(), 'H': H, 'C': C, 'n_hub': n_hub, 'n_chunks': n_chunks}, x_l):
+        check(lib.pygamd_gatv2_forward(_p(rowptr), _p(col), _idx_dtype(rowptr), _p(x_l), _p(x_r),
+                                       _p(att), n_rows, x_l.size(0), H, C, float(slope),
+                                       _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD,
+                                       HUB_CHUNK, _p(alpha), _p(out), _p(ws), ws_bytes,
+                                       _stream(x_l)), 'gatv2_forward')
+    return alpha, out
+
+
+def gatv2_backward_dst(rowptr: Tensor, col: Tensor, x_l: Tensor, x_r: Tensor, att: Tensor,
+                       alpha: Tensor, H: int, C: int, slope: float, *,
+                       grad_out: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                       grad_alpha: Optional[Tensor] = None, hub=None):
+    """``(grad_s [nnz, H], grad_x_r [rows of x_r, H * C], grad_att [H * C])``; ``grad_alpha``
+    given = score mode, otherwise ``grad_out`` and ``out``."""
+    _require_device(rowptr, col, x_l, x_r, att, alpha, grad_out, out, grad_alpha)
+    lib = _lib.load()
+    W = H * C
+    x_l, x_r = _gatv2_rows(x_l, 'x_l', W), _gatv2_rows(x_r, 'x_r', W)
+    att, alpha = att.reshape(-1).contiguous(), alpha.contiguous()
+    n_rows = rowptr.numel() - 1
+    if grad_alpha is None:
+        grad_out, out = _gatv2_rows(grad_out, 'grad_out', W), _gatv2_rows(out, 'out', W)
+    else:
+        grad_alpha = grad_alpha.contiguous()
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    grad_s = torch.empty_like(alpha)
+    # (destinations may be a prefix of the rows of x_r: the rest takes no gradient)
+    alloc = torch.empty if x_r.size(0) == n_rows else torch.zeros
+    grad_x_r = alloc(x_r.size(0), W, dtype=torch.float32, device=x_l.device)
+    grad_att = torch.empty(W, dtype=torch.float32, device=x_l.device)
+    if col.numel() == 0:
+        return grad_s, grad_x_r.zero_(), grad_att.zero_()
+    ws, ws_bytes = _gatv2_workspace(lib, n_chunks, H, C, x_l.device, True)
+    with _timed({'kind': 'gatv2', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(),
+                 'H': H, 'C': C, 'n_hub': n_hub, 'score': grad_alpha is not None}, x_l):
+        check(lib.pygamd_gatv2_backward_dst(
+            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(x_l), _p(x_r), _p(att), _p(alpha),
+            _p(grad_out), _p(out), _p(grad_alpha), n_rows, x_l.size(0), H, C, float(slope),
+            _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_s),
+            _p(grad_x_r), _p(grad_att), _p(ws), ws_bytes, _stream(x_l)), 'gatv2_backward_dst')
+    return grad_s, grad_x_r, grad_att
+
+
+def gatv2_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, x_l: Tensor,
+                       x_r: Tensor, att: Tensor, alpha: Tensor, grad_s: Tensor, H: int, C: int,
+                       slope: float, *, grad_out: Optional[Tensor] = None, n_dst: int,
+                       hub=None) -> Tensor:
+    """``grad_x_l [n_src, H * C]`` on the by-source handle; ``grad_out=None`` = score mode."""
+    _require_device(rowptr_t, col_t, slot_map, x_l, x_r, att, alpha, grad_s, grad_out)
+    lib = _lib.load()
+    W = H * C
+    x_l, x_r = _gatv2_rows(x_l, 'x_l', W), _gatv2_rows(x_r, 'x_r', W)
+    att, alpha, grad_s = att.reshape(-1).contiguous(), alpha.contiguous(), grad_s.contiguous()
+    if grad_out is not None:
+        grad_out = _gatv2_rows(grad_out, 'grad_out', W)
+    n_src = rowptr_t.numel() - 1
+    if x_l.size(0) != n_src or slot_map.dtype != rowptr_t.dtype:
+        raise ValueError("'x_l' must have one row per source and 'slot_map' the index dtype")
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    grad_x_l = torch.empty(n_src, W, dtype=torch.float32, device=x_l.device)
+    if col_t.numel() == 0:
+        return grad_x_l.zero_()
+    ws, ws_bytes = _gatv2_workspace(lib, n_chunks, H, C, x_l.device, n_chunks > 0)
+    with _timed({'kind': 'gatv2', 'op': 'backward_src', 'n_rows': n_src, 'E': col_t.numel(),
+                 'H': H, 'C': C, 'n_hub': n_hub, 'score': grad_out is None}, x_l):
+        check(lib.pygamd_gatv2_backward_src(
+            _p(rowptr_t), _p(col_t), _p(slot_map.contiguous()), _idx_dtype(rowptr_t), _p(x_l),
+            _p(x_r), _p(att), _p(alpha), _p(grad_s), _p(grad_out), n_src, n_dst, H, C,
+            float(slope), _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK,
+            _p(grad_x_l), _p(ws), ws_bytes, _stream(x_l)), 'gatv2_backward_src')
+    return grad_x_l
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

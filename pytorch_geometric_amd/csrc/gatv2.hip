@@ -1,0 +1,675 @@
+// gatv2.hip — GATv2 attention (nn/conv/gatv2_conv.py:358-378 of the reference) as row-gather
+// kernels on a sorted handle.  The score
+//     s[i<-j, h] = sum_c att[h,c] * leaky_relu(x_l[j,h,c] + x_r[i,h,c])
+// needs the full source row per edge, and so does the aggregation: ONE pass per destination keeps
+// x_r[i] in registers, gathers every x_l[j] once, runs an online softmax per head and (AGG)
+// accumulates the weighted row.  Nothing of size E x H*C is ever written.
+//
+// Lane layout (wave64, one wave per row or per chunk of a long row): `lph` lanes per head, a power
+// of two with H * lph <= 64; lane l serves head l / lph and the channels sub + lph * r (scalar) or
+// the float4 units sub + lph * q (VEC) of that head, EPL registers per row.  A head's dot product
+// is an xor-butterfly over its lph lanes, so heads that are narrower or wider than a lane's share,
+// odd C and H*C < 64 all take the same code.
+//
+// Long rows (more slots than the handle's hub threshold) are split into the hub plan's chunks: one
+// wave per chunk leaves a partial (m, l, acc) — or a partial gradient row — in the workspace and a
+// merge kernel combines the chunks of a row in chunk order.  No float atomics anywhere: every
+// result, the att gradient included, is bitwise reproducible.
+#include <math.h>
+
+#include "common.h"
+
+namespace pygamd {
+namespace {
+
+constexpr int kGv2MaxWidth = 512;
+constexpr int kGv2MaxHeads = 64;
+constexpr int kGv2MaxBlocks = 1024;  // persistent grid of the by-destination backward
+
+struct Lay {
+  int H, C, lph, h, sub;
+  bool head_ok;
+};
+
+__device__ __forceinline__ Lay make_lay(int H, int C, int lph) {
+  Lay L;
+  L.H = H;
+  L.C = C;
+  L.lph = lph;
+  L.h = lane_id() / lph;
+  L.sub = lane_id() % lph;
+  L.head_ok = L.h < H;
+  return L;
+}
+
+template <int EPL, bool VEC>
+__device__ __forceinline__ void load_row(const float* __restrict__ row, const Lay& L,
+                                         float (&v)[EPL]) {
+  if constexpr (VEC) {
+#pragma unroll
+    for (int q = 0; q < EPL / 4; ++q) {
+      const int c = (L.sub + L.lph * q) * 4;
+      if (L.head_ok && c < L.C) {
+        const Vec<4> t = load_vec<4>(row + L.h * L.C + c);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[4 * q + i] = t.v[i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[4 * q + i] = 0.f;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < EPL; ++r) {
+      const int c = L.sub + L.lph * r;
+      v[r] = (L.head_ok && c < L.C) ? row[L.h * L.C + c] : 0.f;
+    }
+  }
+}
+
+template <int EPL, bool VEC>
+__device__ __forceinline__ void store_row(float* __restrict__ row, const Lay& L,
+                                          const float (&v)[EPL]) {
+  if constexpr (VEC) {
+#pragma unroll
+    for (int q = 0; q < EPL / 4; ++q) {
+      const int c = (L.sub + L.lph * q) * 4;
+      if (L.head_ok && c < L.C) {
+        Vec<4> t;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t.v[i] = v[4 * q + i];
+        store_vec<4>(row + L.h * L.C + c, t);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < EPL; ++r) {
+      const int c = L.sub + L.lph * r;
+      if (L.head_ok && c < L.C) row[L.h * L.C + c] = v[r];
+    }
+  }
+}
+
+// sum over the lph lanes of a head; every lane of the group gets the total
+__device__ __forceinline__ float group_sum(float v, int lph) {
+  for (int o = lph >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
+// Work items of a launch: the chunks of the hub rows first (they are the long ones), then every
+// row; a hub row's own item does nothing.
+template <typename IdxT>
+struct Items {
+  const IdxT* rowptr;
+  const IdxT* hub_rows;
+  const IdxT* hub_cptr;
+  int64_t n_rows, n_hub, n_chunks, threshold, chunk;
+};
+
+struct Span {
+  int64_t row, k0, k1, row_start, row_end, chunk_id;  // chunk_id < 0: a whole row
+};
+
+template <typename IdxT>
+__device__ __forceinline__ bool decode(const Items<IdxT>& it, int64_t item, Span& s) {
+  if (item < it.n_chunks) {
+    int64_t lo = 0, hi = it.n_hub - 1;  // last hub row whose first chunk is <= item
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (static_cast<int64_t>(it.hub_cptr[mid]) <= item) lo = mid; else hi = mid - 1;
+    }
+    s.row = static_cast<int64_t>(it.hub_rows[lo]);
+    s.row_start = static_cast<int64_t>(it.rowptr[s.row]);
+    s.row_end = static_cast<int64_t>(it.rowptr[s.row + 1]);
+    s.k0 = s.row_start + (item - static_cast<int64_t>(it.hub_cptr[lo])) * it.chunk;
+    s.k1 = s.k0 + it.chunk < s.row_end ? s.k0 + it.chunk : s.row_end;
+    s.chunk_id = item;
+    return s.k0 < s.row_end;
+  }
+  s.row = item - it.n_chunks;
+  if (s.row >= it.n_rows) return false;
+  s.row_start = s.k0 = static_cast<int64_t>(it.rowptr[s.row]);
+  s.row_end = s.k1 = static_cast<int64_t>(it.rowptr[s.row + 1]);
+  s.chunk_id = -1;
+  return !(it.n_hub > 0 && s.row_end - s.row_start > it.threshold);
+}
+
+template <int EPL>
+struct InFlight {
+  static constexpr int fwd = EPL >= 16 ? 2 : 4;   // gathered rows in flight per wave
+  static constexpr int src = EPL >= 8 ? 2 : 4;    // (the by-source pass gathers two rows per slot)
+};
+
+// ---- forward ---------------------------------------------------------------------------------
+template <typename IdxT, int EPL, bool VEC, bool AGG>
+__global__ void __launch_bounds__(kBlock)
+    gatv2_fwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col, const float* __restrict__ xl,
+                     const float* __restrict__ xr, const float* __restrict__ att, int H, int C,
+                     int lph, float slope, float* __restrict__ alpha, float* __restrict__ out,
+                     float* __restrict__ part) {
+  constexpr int U = InFlight<EPL>::fwd;
+  const int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block();
+  Span s;
+  if (!decode(it, item, s)) return;
+  const Lay L = make_lay(H, C, lph);
+  const int64_t W = static_cast<int64_t>(H) * C;
+  float a[EPL], r[EPL], acc[EPL];
+  load_row<EPL, VEC>(att, L, a);
+  load_row<EPL, VEC>(xr + s.row * W, L, r);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+  float m = -INFINITY, l = 0.f;
+  for (int64_t k = s.k0; k < s.k1; k += U) {
+    float v[U][EPL];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (k + u < s.k1) {
+        const int64_t j = static_cast<int64_t>(col[k + u]);
+        load_row<EPL, VEC>(xl + j * W, L, v[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (k + u < s.k1) {
+        float p = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          const float t = v[u][e] + r[e];
+          p = fmaf(a[e], t > 0.f ? t : t * slope, p);
+        }
+        p = group_sum(p, lph);
+        // the raw score; the lane that writes it is the lane that rescales it below
+        if (L.head_ok && L.sub == static_cast<int>((k + u - s.row_start) & (lph - 1)))
+          alpha[(k + u) * H + L.h] = p;
+        const float mn = fmaxf(m, p);
+        const float sc = expf(m - mn), pe = expf(p - mn);
+        l = fmaf(l, sc, pe);
+        if constexpr (AGG) {
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) acc[e] = fmaf(acc[e], sc, pe * v[u][e]);
+        }
+        m = mn;
+      }
+    }
+  }
+  if (s.chunk_id >= 0) {  // partial (acc, m, l) of one chunk of a long row
+    float* p = part + s.chunk_id * (W + 2 * H);
+    if constexpr (AGG) store_row<EPL, VEC>(p, L, acc);
+    if (L.head_ok && L.sub == 0) {
+      p[W + L.h] = m;
+      p[W + H + L.h] = l;
+    }
+    return;
+  }
+  const float inv = 1.f / (l + 1e-16f);
+  if constexpr (AGG) {
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc[e] *= inv;
+    store_row<EPL, VEC>(out + s.row * W, L, acc);
+  }
+  if (L.head_ok) {
+    for (int64_t k = s.row_start + L.sub; k < s.row_end; k += lph)
+      alpha[k * H + L.h] = expf(alpha[k * H + L.h] - m) * inv;
+  }
+}
+
+// one 64-lane workgroup per hub row: final (m, l) per head, the output row, the row's alpha
+template <typename IdxT>
+__global__ void __launch_bounds__(kWave)
+    gatv2_fwd_merge_kernel(const IdxT* __restrict__ rowptr, const IdxT* __restrict__ hub_rows,
+                           const IdxT* __restrict__ hub_cptr, int H, int C,
+                           const float* __restrict__ part, float* __restrict__ alpha,
+                           float* __restrict__ out) {
+  __shared__ float sm[kGv2MaxHeads], sinv[kGv2MaxHeads];
+  const int64_t hr = blockIdx.x;
+  const int64_t row = static_cast<int64_t>(hub_rows[hr]);
+  const int64_t c0 = static_cast<int64_t>(hub_cptr[hr]), c1 = static_cast<int64_t>(hub_cptr[hr + 1]);
+  const int64_t W = static_cast<int64_t>(H) * C, S = W + 2 * H;
+  const int lane = threadIdx.x;
+  if (lane < H) {
+    float m = -INFINITY, l = 0.f;
+    for (int64_t c = c0; c < c1; ++c) {
+      const float mc = part[c * S + W + lane], lc = part[c * S + W + H + lane];
+      const float mn = fmaxf(m, mc);
+      l = l * expf(m - mn) + lc * expf(mc - mn);
+      m = mn;
+    }
+    sm[lane] = m;
+    sinv[lane] = 1.f / (l + 1e-16f);
+  }
+  __syncthreads();
+  if (out) {
+    for (int64_t t = lane; t < W; t += kWave) {
+      const int h = static_cast<int>(t / C);
+      float acc = 0.f;
+      for (int64_t c = c0; c < c1; ++c)
+        acc = fmaf(part[c * S + t], expf(part[c * S + W + h] - sm[h]), acc);
+      out[row * W + t] = acc * sinv[h];
+    }
+  }
+  const int64_t k0 = static_cast<int64_t>(rowptr[row]) * H;
+  const int64_t k1 = static_cast<int64_t>(rowptr[row + 1]) * H;
+  for (int64_t t = k0 + lane; t < k1; t += kWave) {
+    const int h = static_cast<int>(t % H);
+    alpha[t] = expf(alpha[t] - sm[h]) * sinv[h];
+  }
+}
+
+// partial rows of a hub row summed in chunk order
+template <typename IdxT>
+__global__ void __launch_bounds__(kWave)
+    gatv2_sum_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
+                           int64_t W, const float* __restrict__ part, float* __restrict__ dst) {
+  const int64_t hr = blockIdx.x;
+  const int64_t row = static_cast<int64_t>(hub_rows[hr]);
+  const int64_t c0 = static_cast<int64_t>(hub_cptr[hr]), c1 = static_cast<int64_t>(hub_cptr[hr + 1]);
+  for (int64_t t = threadIdx.x; t < W; t += kWave) {
+    float acc = 0.f;
+    for (int64_t c = c0; c < c1; ++c) acc += part[c * W + t];
+    dst[row * W + t] = acc;
+  }
+}
+
+// ---- backward, by destination -------------------------------------------------------------------
+// d s[k,h] = alpha * (d alpha - D);  grad_x_r[i] = sum_k d pre;  grad_att += sum_k d s * lrelu(pre).
+// SCORE: d alpha is given (the layer consumed alpha itself); otherwise d alpha = <grad_out, x_l[j]>
+// and D = <grad_out[i,h,:], out[i,h,:]>.
+template <typename IdxT, int EPL, bool VEC, bool SCORE>
+__global__ void __launch_bounds__(kBlock)
+    gatv2_bwd_dst_kernel(Items<IdxT> it, int64_t n_items, const IdxT* __restrict__ col,
+                         const float* __restrict__ xl, const float* __restrict__ xr,
+                         const float* __restrict__ att, const float* __restrict__ alpha,
+                         const float* __restrict__ gout, const float* __restrict__ outp,
+                         const float* __restrict__ galpha, int H, int C, int lph, float slope,
+                         float* __restrict__ ds, float* __restrict__ gxr,
+                         float* __restrict__ part, float* __restrict__ att_part) {
+  constexpr int U = InFlight<EPL>::src;
+  __shared__ __attribute__((aligned(16))) float sm[kWavesPerBlock][kGv2MaxWidth];
+  const Lay L = make_lay(H, C, lph);
+  const int64_t W = static_cast<int64_t>(H) * C;
+  float a[EPL], ga[EPL];
+  load_row<EPL, VEC>(att, L, a);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) ga[e] = 0.f;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+  for (int64_t item = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
+       item < n_items; item += stride) {
+    Span s;
+    if (!decode(it, item, s)) continue;
+    float r[EPL], g[EPL], gr[EPL];
+    load_row<EPL, VEC>(xr + s.row * W, L, r);
+    float D = 0.f;
+    if constexpr (SCORE) {
+      if (L.head_ok) {
+        for (int64_t k = s.row_start + L.sub; k < s.row_end; k += lph)
+          D = fmaf(alpha[k * H + L.h], galpha[k * H + L.h], D);
+      }
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) g[e] = 0.f;
+    } else {
+      float o[EPL];
+      load_row<EPL, VEC>(gout + s.row * W, L, g);
+      load_row<EPL, VEC>(outp + s.row * W, L, o);
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) D = fmaf(g[e], o[e], D);
+    }
+    D = group_sum(D, lph);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) gr[e] = 0.f;
+    for (int64_t k = s.k0; k < s.k1; k += U) {
+      float v[U][EPL];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (k + u < s.k1) {
+          const int64_t j = static_cast<int64_t>(col[k + u]);
+          load_row<EPL, VEC>(xl + j * W, L, v[u]);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (k + u < s.k1) {
+          float da = 0.f;
+          if constexpr (SCORE) {
+            da = L.head_ok ? galpha[(k + u) * H + L.h] : 0.f;
+          } else {
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) da = fmaf(g[e], v[u][e], da);
+            da = group_sum(da, lph);
+          }
+          const float al = L.head_ok ? alpha[(k + u) * H + L.h] : 0.f;
+          const float d = al * (da - D);
+          if (L.head_ok && L.sub == 0) ds[(k + u) * H + L.h] = d;
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) {
+            const float t = v[u][e] + r[e];
+            const bool pos = t > 0.f;
+            gr[e] = fmaf(d * a[e], pos ? 1.f : slope, gr[e]);
+            ga[e] = fmaf(d, pos ? t : t * slope, ga[e]);
+          }
+        }
+      }
+    }
+    store_row<EPL, VEC>(s.chunk_id >= 0 ? part + s.chunk_id * W : gxr + s.row * W, L, gr);
+  }
+  // att gradient: per wave -> per workgroup (fixed order) -> one row of the partials buffer
+  store_row<EPL, VEC>(sm[threadIdx.x >> 6], L, ga);
+  __syncthreads();
+  for (int t = threadIdx.x; t < W; t += kBlock) {
+    float acc = sm[0][t];
+#pragma unroll
+    for (int w = 1; w < kWavesPerBlock; ++w) acc += sm[w][t];
+    att_part[static_cast<int64_t>(blockIdx.x) * W + t] = acc;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+    gatv2_att_reduce_kernel(const float* __restrict__ att_part, int64_t n_part, int64_t W,
+                            float* __restrict__ gatt) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (t >= W) return;
+  float acc = 0.f;
+  for (int64_t b = 0; b < n_part; ++b) acc += att_part[b * W + t];
+  gatt[t] = acc;
+}
+
+// ---- backward, by source ---------------------------------------------------------------------
+// grad_x_l[j] = sum over the edges j -> i of alpha * grad_out[i] (not in SCORE mode) + d pre.
+template <typename IdxT, int EPL, bool VEC, bool SCORE>
+__global__ void __launch_bounds__(kBlock)
+    gatv2_bwd_src_kernel(Items<IdxT> it, const IdxT* __restrict__ col_t,
+                         const IdxT* __restrict__ slot_map, const float* __restrict__ xl,
+                         const float* __restrict__ xr, const float* __restrict__ att,
+                         const float* __restrict__ alpha, const float* __restrict__ ds,
+                         const float* __restrict__ gout, int H, int C, int lph, float slope,
+                         float* __restrict__ gxl, float* __restrict__ part) {
+  constexpr int U = InFlight<EPL>::src;
+  const int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block();
+  Span s;
+  if (!decode(it, item, s)) return;
+  const Lay L = make_lay(H, C, lph);
+  const int64_t W = static_cast<int64_t>(H) * C;
+  float a[EPL], v[EPL], acc[EPL];
+  load_row<EPL, VEC>(att, L, a);
+  load_row<EPL, VEC>(xl + s.row * W, L, v);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+  for (int64_t q = s.k0; q < s.k1; q += U) {
+    float r[U][EPL], g[SCORE ? 1 : U][EPL];
+    float al[U], d[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (q + u < s.k1) {
+        const int64_t i = static_cast<int64_t>(col_t[q + u]);
+        const int64_t kd = static_cast<int64_t>(slot_map[q + u]);
+        load_row<EPL, VEC>(xr + i * W, L, r[u]);
+        if constexpr (!SCORE) load_row<EPL, VEC>(gout + i * W, L, g[u]);
+        al[u] = (!SCORE && L.head_ok) ? alpha[kd * H + L.h] : 0.f;
+        d[u] = L.head_ok ? ds[kd * H + L.h] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (q + u < s.k1) {
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          const float t = v[e] + r[u][e];
+          acc[e] = fmaf(d[u] * a[e], t > 0.f ? 1.f : slope, acc[e]);
+          if constexpr (!SCORE) acc[e] = fmaf(al[u], g[u][e], acc[e]);
+        }
+      }
+    }
+  }
+  store_row<EPL, VEC>(s.chunk_id >= 0 ? part + s.chunk_id * W : gxl + s.row * W, L, acc);
+}
+
+// ---- host side -------------------------------------------------------------------------------
+struct Shape {
+  int lph, epl;
+  bool vec;
+};
+
+bool choose_shape(int64_t H, int64_t C, bool aligned, Shape* s) {
+  if (H < 1 || C < 1 || H * C > kGv2MaxWidth || H > kGv2MaxHeads) return false;
+  int cap = 1;
+  while (cap * 2 * H <= kWave) cap *= 2;
+  if (aligned && C % 4 == 0) {
+    const int units = static_cast<int>(C / 4);
+    int lph = cap;
+    while (lph > 1 && lph / 2 >= units) lph /= 2;
+    const int n = (units + lph - 1) / lph;
+    if (n <= 2) {
+      *s = Shape{lph, 4 * n, true};
+      return true;
+    }
+  }
+  int lph = cap;
+  while (lph > 1 && lph / 2 >= C) lph /= 2;
+  const int n = static_cast<int>((C + lph - 1) / lph);
+  int epl = 1;
+  while (epl < n) epl *= 2;
+  if (epl > 16) return false;
+  *s = Shape{lph, epl, false};
+  return true;
+}
+
+#define GV2_DISPATCH_SHAPE(shape, ...)                                  \
+  do {                                                                  \
+    if ((shape).vec) {                                                  \
+      if ((shape).epl == 4) { constexpr int EPL = 4; constexpr bool VEC = true; __VA_ARGS__ }   \
+      else { constexpr int EPL = 8; constexpr bool VEC = true; __VA_ARGS__ }                    \
+    } else {                                                            \
+      switch ((shape).epl) {                                            \
+        case 1: { constexpr int EPL = 1; constexpr bool VEC = false; __VA_ARGS__ } break;       \
+        case 2: { constexpr int EPL = 2; constexpr bool VEC = false; __VA_ARGS__ } break;       \
+        case 4: { constexpr int EPL = 4; constexpr bool VEC = false; __VA_ARGS__ } break;       \
+        case 8: { constexpr int EPL = 8; constexpr bool VEC = false; __VA_ARGS__ } break;       \
+        default: { constexpr int EPL = 16; constexpr bool VEC = false; __VA_ARGS__ } break;     \
+      }                                                                 \
+    }                                                                   \
+  } while (0)
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+size_t gv2_ws_bytes(int64_t n_chunks, int64_t H, int64_t C) {
+  const int64_t W = H * C;
+  return sizeof(float) * static_cast<size_t>(n_chunks * (W + 2 * H) + kGv2MaxBlocks * W);
+}
+
+// the checks every entry point shares; 0 = go on
+int gv2_check(int idx_dtype, int64_t n_rows, int64_t n_other, int64_t H, int64_t C,
+              const void* hub_rows, const void* hub_cptr, int64_t n_hub, int64_t n_chunks,
+              int64_t threshold, int64_t chunk) {
+  if (idx_dtype != PYGAMD_IDX_I64 && idx_dtype != PYGAMD_IDX_I32) return PYGAMD_ERR_INVALID_ARG;
+  if (n_rows < 0 || n_other < 0 || H < 1 || C < 1 || n_hub < 0 || n_chunks < 0)
+    return PYGAMD_ERR_INVALID_ARG;
+  if (n_hub > 0 && (!hub_rows || !hub_cptr || n_chunks < n_hub || threshold < 1 || chunk < 1))
+    return PYGAMD_ERR_INVALID_ARG;
+  if (n_hub == 0 && n_chunks != 0) return PYGAMD_ERR_INVALID_ARG;
+  if (H * C > kGv2MaxWidth || H > kGv2MaxHeads) return PYGAMD_ERR_UNSUPPORTED;
+  return PYGAMD_OK;
+}
+
+}  // namespace
+}  // namespace pygamd
+
+using namespace pygamd;
+
+extern "C" {
+
+int pygamd_gatv2_supported(int64_t H, int64_t C) {
+  Shape s;
+  return choose_shape(H, C, false, &s) ? 1 : 0;
+}
+
+int pygamd_gatv2_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C, size_t* bytes) {
+  if (!bytes || n_chunks < 0 || H < 1 || C < 1) return PYGAMD_ERR_INVALID_ARG;
+  if (H * C > kGv2MaxWidth || H > kGv2MaxHeads) return PYGAMD_ERR_UNSUPPORTED;
+  *bytes = gv2_ws_bytes(n_chunks, H, C);
+  return PYGAMD_OK;
+}
+
+int pygamd_gatv2_forward(const void* rowptr, const void* col, int idx_dtype, const float* x_l,
+                         const float* x_r, const float* att, int64_t n_rows, int64_t n_src,
+                         int64_t H, int64_t C, float slope, const void* hub_rows,
+                         const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
+                         int64_t hub_threshold, int64_t hub_chunk, float* alpha, float* out,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = gv2_check(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
+                           n_chunks, hub_threshold, hub_chunk);
+  if (rc != PYGAMD_OK) return rc;
+  if (n_rows == 0) return PYGAMD_OK;
+  if (!rowptr || !col || !x_l || !x_r || !att || !alpha) return PYGAMD_ERR_INVALID_ARG;
+  if (n_chunks > 0 && (!workspace || workspace_bytes < gv2_ws_bytes(n_chunks, H, C)))
+    return PYGAMD_ERR_WORKSPACE;
+  Shape sh;
+  const bool al = aligned16(x_l) && aligned16(x_r) && aligned16(att) && aligned16(workspace) &&
+                  (!out || aligned16(out)) && (H % 2 == 0 || n_chunks == 0);
+  if (!choose_shape(H, C, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+  float* part = static_cast<float*>(workspace);
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
+                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
+                   hub_threshold, hub_chunk};
+    const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
+    const IdxT* c = static_cast<const IdxT*>(col);
+    GV2_DISPATCH_SHAPE(sh, {
+      if (out) {
+        hipLaunchKernelGGL((gatv2_fwd_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it, c,
+                           x_l, x_r, att, static_cast<int>(H), static_cast<int>(C), sh.lph, slope,
+                           alpha, out, part);
+      } else {
+        hipLaunchKernelGGL((gatv2_fwd_kernel<IdxT, EPL, VEC, false>), grid, block, 0, st, it, c,
+                           x_l, x_r, att, static_cast<int>(H), static_cast<int>(C), sh.lph, slope,
+                           alpha, out, part);
+      }
+    });
+    PYGAMD_LAUNCH_CHECK();
+    if (n_hub > 0) {
+      hipLaunchKernelGGL((gatv2_fwd_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
+                         dim3(kWave), 0, st, it.rowptr, it.hub_rows, it.hub_cptr,
+                         static_cast<int>(H), static_cast<int>(C), part, alpha, out);
+      PYGAMD_LAUNCH_CHECK();
+    }
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_gatv2_backward_dst(const void* rowptr, const void* col, int idx_dtype,
+                              const float* x_l, const float* x_r, const float* att,
+                              const float* alpha, const float* grad_out, const float* out,
+                              const float* grad_alpha, int64_t n_rows, int64_t n_src, int64_t H,
+                              int64_t C, float slope, const void* hub_rows,
+                              const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
+                              int64_t hub_threshold, int64_t hub_chunk, float* grad_s,
+                              float* grad_x_r, float* grad_att, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  const int rc = gv2_check(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
+                           n_chunks, hub_threshold, hub_chunk);
+  if (rc != PYGAMD_OK) return rc;
+  if (!grad_att) return PYGAMD_ERR_INVALID_ARG;
+  // exactly one of (grad_out, out) and grad_alpha says where d alpha comes from
+  const bool score = grad_alpha != nullptr;
+  if (score ? (grad_out || out) : (!grad_out || !out)) return PYGAMD_ERR_INVALID_ARG;
+  hipStream_t st = as_stream(stream);
+  const int64_t W = H * C;
+  if (n_rows == 0) {
+    PYGAMD_HIP_CHECK(hipMemsetAsync(grad_att, 0, sizeof(float) * W, st));
+    return PYGAMD_OK;
+  }
+  if (!rowptr || !col || !x_l || !x_r || !att || !alpha || !grad_s || !grad_x_r)
+    return PYGAMD_ERR_INVALID_ARG;
+  if (!workspace || workspace_bytes < gv2_ws_bytes(n_chunks, H, C)) return PYGAMD_ERR_WORKSPACE;
+  Shape sh;
+  const bool al = aligned16(x_l) && aligned16(x_r) && aligned16(att) && aligned16(workspace) &&
+                  aligned16(grad_x_r) && (score || (aligned16(grad_out) && aligned16(out)));
+  if (!choose_shape(H, C, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
+  float* part = static_cast<float*>(workspace);
+  float* att_part = part + n_chunks * W;
+  const int64_t n_items = n_rows + n_chunks;
+  int64_t blocks = wave_grid(n_items);
+  if (blocks > kGv2MaxBlocks) blocks = kGv2MaxBlocks;
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
+                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
+                   hub_threshold, hub_chunk};
+    const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
+    const IdxT* c = static_cast<const IdxT*>(col);
+    GV2_DISPATCH_SHAPE(sh, {
+      if (score) {
+        hipLaunchKernelGGL((gatv2_bwd_dst_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it,
+                           n_items, c, x_l, x_r, att, alpha, grad_out, out, grad_alpha,
+                           static_cast<int>(H), static_cast<int>(C), sh.lph, slope, grad_s,
+                           grad_x_r, part, att_part);
+      } else {
+        hipLaunchKernelGGL((gatv2_bwd_dst_kernel<IdxT, EPL, VEC, false>), grid, block, 0, st, it,
+                           n_items, c, x_l, x_r, att, alpha, grad_out, out, grad_alpha,
+                           static_cast<int>(H), static_cast<int>(C), sh.lph, slope, grad_s,
+                           grad_x_r, part, att_part);
+      }
+    });
+    PYGAMD_LAUNCH_CHECK();
+    if (n_hub > 0) {
+      hipLaunchKernelGGL((gatv2_sum_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
+                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, W, part, grad_x_r);
+      PYGAMD_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(gatv2_att_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(W, kBlock))),
+                       block, 0, st, att_part, blocks, W, grad_att);
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_gatv2_backward_src(const void* rowptr_t, const void* col_t, const void* slot_map,
+                              int idx_dtype, const float* x_l, const float* x_r,
+                              const float* att, const float* alpha, const float* grad_s,
+                              const float* grad_out, int64_t n_src, int64_t n_dst, int64_t H,
+                              int64_t C, float slope, const void* hub_rows,
+                              const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
+                              int64_t hub_threshold, int64_t hub_chunk, float* grad_x_l,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = gv2_check(idx_dtype, n_src, n_dst, H, C, hub_rows, hub_chunk_ptr, n_hub,
+                           n_chunks, hub_threshold, hub_chunk);
+  if (rc != PYGAMD_OK) return rc;
+  if (n_src == 0) return PYGAMD_OK;
+  if (!rowptr_t || !col_t || !slot_map || !x_l || !x_r || !att || !alpha || !grad_s || !grad_x_l)
+    return PYGAMD_ERR_INVALID_ARG;
+  if (n_chunks > 0 && (!workspace || workspace_bytes < gv2_ws_bytes(n_chunks, H, C)))
+    return PYGAMD_ERR_WORKSPACE;
+  Shape sh;
+  const bool al = aligned16(x_l) && aligned16(x_r) && aligned16(att) && aligned16(workspace) &&
+                  aligned16(grad_x_l) && (!grad_out || aligned16(grad_out));
+  if (!choose_shape(H, C, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+  const int64_t W = H * C;
+  float* part = static_cast<float*>(workspace);
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    Items<IdxT> it{static_cast<const IdxT*>(rowptr_t), static_cast<const IdxT*>(hub_rows),
+                   static_cast<const IdxT*>(hub_chunk_ptr), n_src, n_hub, n_chunks,
+                   hub_threshold, hub_chunk};
+    const dim3 grid(wave_grid(n_src + n_chunks)), block(kBlock);
+    const IdxT* c = static_cast<const IdxT*>(col_t);
+    const IdxT* sm = static_cast<const IdxT*>(slot_map);
+    GV2_DISPATCH_SHAPE(sh, {
+      if (!grad_out) {
+        hipLaunchKernelGGL((gatv2_bwd_src_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it,
+                           c, sm, x_l, x_r, att, alpha, grad_s, grad_out, static_cast<int>(H),
+                           static_cast<int>(C), sh.lph, slope, grad_x_l, part);
+      } else {
+        hipLaunchKernelGGL((gatv2_bwd_src_kernel<IdxT, EPL, VEC, false>), grid, block, 0, st, it,
+                           c, sm, x_l, x_r, att, alpha, grad_s, grad_out, static_cast<int>(H),
+                           static_cast<int>(C), sh.lph, slope, grad_x_l, part);
+      }
+    });
+    PYGAMD_LAUNCH_CHECK();
+    if (n_hub > 0) {
+      hipLaunchKernelGGL((gatv2_sum_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
+                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, W, part, grad_x_l);
+      PYGAMD_LAUNCH_CHECK();
+    }
+    return PYGAMD_OK;
+  });
+}
+
+}  // extern "C"

@@ -2,9 +2,10 @@ from .message_passing import MessagePassing
 from .sage_conv import SAGEConv
 from .gcn_conv import GCNConv, gcn_norm
 from .gat_conv import GATConv
+from .gatv2_conv import GATv2Conv
 from .rgcn_conv import FastRGCNConv, RGCNConv
 from .graph_conv import GraphConv
 from .hetero_conv import HeteroConv, group
 
-__all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'RGCNConv', 'FastRGCNConv',
+__all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group']

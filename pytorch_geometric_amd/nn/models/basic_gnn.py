@@ -5,7 +5,7 @@ from torch import Tensor
 from torch.nn import ModuleList
 
 from ...utils import trim_to_layer
-from ..conv import GATConv, GCNConv, MessagePassing, SAGEConv
+from ..conv import GATConv, GATv2Conv, GCNConv, MessagePassing, SAGEConv
 from ..conv._act_request import has_forward_hooks, request_activation
 
 _ACTS = {'relu': torch.nn.ReLU, 'elu': torch.nn.ELU, 'leaky_relu': torch.nn.LeakyReLU,
@@ -89,7 +89,8 @@ class BasicGNN(torch.nn.Module):
                 else:
                     edge_attr = value
             fused = fuse_ok and i < self.num_layers - 1 and hasattr(conv, 'bias') \
-                and type(conv).__name__ in ('GCNConv', 'GATConv', 'RGCNConv', 'FastRGCNConv') \
+                and type(conv).__name__ in ('GCNConv', 'GATConv', 'GATv2Conv', 'RGCNConv',
+                                            'FastRGCNConv') \
                 and type(conv).__module__.startswith('pytorch_geometric_amd') \
                 and not has_forward_hooks(conv)
             with request_activation(conv, 'relu' if fused else None):
@@ -146,10 +147,12 @@ class GraphSAGE(BasicGNN):
 
 class GAT(BasicGNN):
     """:class:`GATConv` stack (basic_gnn.py:528-597): hidden layers concatenate ``heads`` of
-    width ``hidden // heads``; an explicit output layer averages its heads."""
+    width ``hidden // heads``; an explicit output layer averages its heads.  ``v2=True`` builds
+    :class:`GATv2Conv` layers instead."""
     supports_edge_attr = True
 
     def init_conv(self, in_channels, out_channels: int, **kwargs) -> MessagePassing:
+        v2 = kwargs.pop('v2', False)
         heads = kwargs.pop('heads', 1)
         concat = kwargs.pop('concat', True)
         # do not use concatenation in the last layer when out_channels was given explicitly
@@ -161,5 +164,6 @@ class GAT(BasicGNN):
                              f"(got '{heads}')")
         if concat:
             out_channels = out_channels // heads
-        return GATConv(in_channels, out_channels, heads=heads, concat=concat,
-                       dropout=self.dropout.p, **kwargs)
+        Conv = GATv2Conv if v2 else GATConv
+        return Conv(in_channels, out_channels, heads=heads, concat=concat,
+                    dropout=self.dropout.p, **kwargs)

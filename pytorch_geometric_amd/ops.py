@@ -27,6 +27,8 @@ Operators (all index tensors int32 / int64, features float32):
 ``softmax_csr``             ``(Tensor src, Tensor ptr) -> Tensor``
 ``spmm``                    ``(Tensor rowptr, Tensor col, Tensor? value, Tensor other, str reduce)``
 ``linear``                  ``(Tensor x, Tensor weight, Tensor? bias) -> Tensor``
+``gatv2_attend``            ``(Tensor x_l, Tensor x_r, Tensor att, Tensor rowptr, Tensor col,
+                            float negative_slope) -> (Tensor out, Tensor alpha)``
 ==========================  ===========================================================
 """
 import math
@@ -367,6 +369,70 @@ def _linear_bwd(ctx, grad):
 
 register_autograd('pyg_amd::linear', _linear_bwd, setup_context=_linear_setup)
 
+# ---- GATv2 attention on a CSR pair (rows = destinations) -----------------------------------------
+@custom_op('pyg_amd::gatv2_attend', mutates_args=(), device_types=_DEV)
+def gatv2_attend(x_l: Tensor, x_r: Tensor, att: Tensor, rowptr: Tensor, col: Tensor,
+                 negative_slope: float) -> Tuple[Tensor, Tensor]:
+    """``(out [n_dst, H, C], alpha [nnz, H])`` of one GATv2 attention step (gatv2_conv.py:358-378)
+    for ``x_l [n_src, H, C]``, ``x_r [>= n_dst, H, C]``, ``att`` with ``H * C`` entries; ``alpha``
+    follows the slots of ``col`` and is returned for inspection (gradients flow through ``out``)."""
+    _, H, C = x_l.shape
+    if not _native.gatv2_supported(H, C):
+        raise NotImplementedError(f'gatv2_attend serves H * C <= 512 and H <= 64 (got {H} x {C})')
+    alpha, out = _native.gatv2_forward(rowptr, col, _rows(x_l), _rows(x_r), att, H, C,
+                                       negative_slope, hub=_native.hub_plan(rowptr))
+    return out.reshape(rowptr.numel() - 1, H, C), alpha
+
+
+@gatv2_attend.register_fake
+def _(x_l, x_r, att, rowptr, col, negative_slope):
+    return (x_l.new_empty(rowptr.numel() - 1, *x_l.shape[1:]),
+            x_l.new_empty(col.numel(), x_l.shape[1]))
+
+
+@custom_op('pyg_amd::gatv2_attend_backward', mutates_args=(), device_types=_DEV)
+def gatv2_attend_backward(grad: Tensor, x_l: Tensor, x_r: Tensor, att: Tensor, alpha: Tensor,
+                          out: Tensor, rowptr: Tensor, col: Tensor,
+                          negative_slope: float) -> Tuple[Tensor, Tensor, Tensor]:
+    _, H, C = x_l.shape
+    n_dst = rowptr.numel() - 1
+    xl2, xr2 = _rows(x_l), _rows(x_r)
+    grad_s, g_r, g_att = _native.gatv2_backward_dst(
+        rowptr, col, xl2, xr2, att, alpha, H, C, negative_slope,
+        grad_out=_rows(grad).contiguous(), out=_rows(out), hub=_native.hub_plan(rowptr))
+    # the by-source form of the same slots: a stable sort of `col`; its permutation IS the map
+    # from by-source slots to the CSR's own (by-destination) slots
+    dst = _native.ptr2index(rowptr, col.numel())
+    src_sorted, perm = _native.index_sort(col, max_value=max(x_l.size(0) - 1, 0))
+    rowptr_t = _native.index2ptr(src_sorted, x_l.size(0))
+    col_t = _native.permute_index(dst, perm)
+    g_l = _native.gatv2_backward_src(rowptr_t, col_t, _native.cast_index(perm, col.dtype), xl2,
+                                     xr2, att, alpha, grad_s, H, C, negative_slope,
+                                     grad_out=_rows(grad).contiguous(), n_dst=n_dst,
+                                     hub=_native.hub_plan(rowptr_t))
+    return g_l.reshape(x_l.shape), g_r.reshape(x_r.shape), g_att.reshape(att.shape)
+
+
+@gatv2_attend_backward.register_fake
+def _(grad, x_l, x_r, att, alpha, out, rowptr, col, negative_slope):
+    return torch.empty_like(x_l), torch.empty_like(x_r), torch.empty_like(att)
+
+
+def _gatv2_setup(ctx, inputs, output):
+    x_l, x_r, att, rowptr, col, slope = inputs
+    ctx.slope = slope
+    ctx.save_for_backward(x_l, x_r, att, output[1], output[0], rowptr, col)
+
+
+def _gatv2_bwd(ctx, grad, _grad_alpha):
+    x_l, x_r, att, alpha, out, rowptr, col = ctx.saved_tensors
+    g_l, g_r, g_att = gatv2_attend_backward(grad.contiguous(), x_l, x_r, att, alpha, out, rowptr,
+                                            col, ctx.slope)
+    return g_l, g_r, g_att, None, None, None
+
+
+register_autograd('pyg_amd::gatv2_attend', _gatv2_bwd, setup_context=_gatv2_setup)
+
 OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_backward',
        'segment_csr', 'segment_csr_backward', 'softmax_csr', 'softmax_csr_backward', 'spmm',
-       'spmm_backward', 'linear', 'linear_backward')
+       'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward')

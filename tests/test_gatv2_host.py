@@ -1,0 +1,162 @@
+"""nn.GATv2Conv / nn.GAT(v2=True): everything that needs no device.  The class on host tensors and
+the plain-torch restatement (tests/_gatv2_ref.py) are pinned to the reference's recorded results
+(tests/golden/golden_gatv2_v1.pt); state dicts interchange with the reference; the argument checks
+of the new entry points."""
+import ctypes
+
+import pytest
+import torch
+
+import _gatv2_ref as R
+from _util import assert_close
+
+CASES = ['v2', 'v2_mean', 'v2_share', 'v2_noloops', 'v2_res_nobias', 'v2_c5', 'v2_pair', 'v2_edge',
+         'v2_attention']
+
+
+def test_golden_file_is_what_the_tests_expect():
+    G = R.load_golden()
+    assert list(G['cases']) == CASES and 'model' in G
+    assert G['x'].shape == (48, 16) and G['edge_index'].shape == (2, 400)
+    deg = torch.bincount(G['edge_index'][1], minlength=48)
+    assert int((deg == 0).sum()) > 0 and int(deg.max()) > 40           # empty rows, a long row
+    assert int((G['edge_index'][0] == G['edge_index'][1]).sum()) > 0   # self-loops
+    # every pre-activation was recorded off the kink of leaky_relu: no outlier allowance needed
+    for case in list(G['cases'].values()) + [G['model']]:
+        assert case['min_gap'] >= 1e-4
+
+
+@pytest.mark.parametrize('name', CASES)
+def test_class_on_host_tensors_matches_the_reference(name):
+    R.check_class_case(R.load_golden(), name, 'cpu')
+
+
+def test_model_on_host_tensors_matches_the_reference():
+    R.check_model_case(R.load_golden(), 'cpu')
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.float64])
+def test_restatement_reproduces_every_golden_case(dtype):
+    G = R.load_golden()
+    for name in CASES:
+        case = G['cases'][name]
+        xs, ei, ea = R.case_inputs(G, case)
+        xs = [t.to(dtype).requires_grad_(True) for t in xs]
+        tied = case['kwargs'].get('share_weights', False)    # lin_r is lin_l: one set of leaves
+        p = {k: v.to(dtype).requires_grad_(True) for k, v in case['state'].items()
+             if not (tied and k.startswith('lin_r.'))}
+        out, used, alpha = R.conv(tuple(xs) if case['pair'] else xs[0], ei, p,
+                                  edge_attr=None if ea is None else ea.to(dtype),
+                                  **{k: v for k, v in case['kwargs'].items() if k != 'in_channels'})
+        assert_close(out.float(), case['out'], what=f'{name} out')
+        names = list(case['grad_params'])
+        grads = torch.autograd.grad(out, xs + [p[n] for n in names], case['grad_out'].to(dtype))
+        for g, ref in zip(grads, case['grad_x']):
+            assert_close(g.float(), ref, what=f'{name} grad_x')
+        for n, g in zip(names, grads[len(xs):]):
+            assert_close(g.float(), case['grad_params'][n], atol=5e-5, rtol=5e-5,
+                         what=f'{name} grad {n}')
+        if 'attention' in case:
+            assert torch.equal(used, case['attention'][0])
+            assert_close(alpha.float(), case['attention'][1], what=f'{name} attention')
+    case = G['model']
+    x = G['x'].to(dtype).requires_grad_(True)
+    p = {k: v.to(dtype).requires_grad_(True) for k, v in case['state'].items()}
+    out = R.gat_model(x, G['edge_index'], p, **case['kwargs'])
+    assert_close(out.float(), case['out'], atol=2e-5, what='model out')
+    names = list(case['grad_params'])
+    grads = torch.autograd.grad(out, [x] + [p[n] for n in names], case['grad_out'].to(dtype))
+    assert_close(grads[0].float(), case['grad_x'][0], atol=2e-5, what='model grad_x')
+    for n, g in zip(names, grads[1:]):
+        assert_close(g.float(), case['grad_params'][n], atol=1e-4, rtol=1e-4,
+                     what=f'model grad {n}')
+
+
+def test_state_dict_and_structure():
+    from pytorch_geometric_amd.nn import GAT, GATConv, GATv2Conv, Linear
+    G = R.load_golden()
+    for name in CASES:
+        case = G['cases'][name]
+        kw = dict(case['kwargs'])
+        layer = GATv2Conv(kw.pop('in_channels'), **kw)
+        assert list(layer.state_dict()) == list(case['state']), name
+        for k, v in layer.state_dict().items():
+            assert v.shape == case['state'][k].shape, (name, k)
+    shared = GATv2Conv(8, 4, heads=2, share_weights=True)
+    assert shared.lin_r is shared.lin_l
+    assert sorted(shared.state_dict()) == ['att', 'bias', 'lin_l.bias', 'lin_l.weight',
+                                           'lin_r.bias', 'lin_r.weight']
+    assert len(list(shared.parameters())) == 4                     # the tied linear counts once
+    plain = GATv2Conv((8, 6), 4, heads=2, bias=False, residual=True, edge_dim=3)
+    assert plain.lin_r is not plain.lin_l and plain.lin_l.bias is None and plain.bias is None
+    assert plain.lin_l.weight.shape == (8, 8) and plain.lin_r.weight.shape == (8, 6)
+    assert isinstance(plain.lin_edge, Linear) and plain.lin_edge.bias is None
+    assert plain.res.weight.shape == (8, 6) and plain.att.shape == (1, 2, 4)
+    assert float(GATv2Conv(8, 4).bias.detach().abs().sum()) == 0.0          # zeros(bias), glorot elsewhere
+    assert repr(plain) == 'GATv2Conv((8, 6), 4, heads=2)' and plain.fuse
+    model = GAT(16, 32, num_layers=3, out_channels=5, heads=4, v2=True)
+    assert [type(c) for c in model.convs] == [GATv2Conv] * 3
+    assert model.convs[0].out_channels == 8 and model.convs[0].concat
+    assert model.convs[2].out_channels == 5 and not model.convs[2].concat
+    assert [type(c) for c in GAT(16, 32, num_layers=2, heads=4).convs] == [GATConv] * 2
+    assert list(model.state_dict()) == list(G['model']['state'])
+    with pytest.raises(ValueError, match='divisible by the number of heads'):
+        GAT(16, 30, num_layers=2, heads=4, v2=True)
+
+
+def test_entry_points_validate_without_gpu():
+    """pygamd_gatv2_* reject bad arguments with status 1 / 2 / 3 before any device work."""
+    from pytorch_geometric_amd import _build, _lib
+    if _build.is_stale() and _build.find_hipcc() is None:
+        pytest.skip('library not built and no hipcc here')
+    lib = _lib.load()
+    dev = ctypes.c_void_p(16)   # (never dereferenced: every call below is rejected or launches nothing)
+    nbytes = ctypes.c_size_t(0)
+    assert lib.pygamd_gatv2_supported(4, 128) == 1 and lib.pygamd_gatv2_supported(3, 5) == 1
+    assert lib.pygamd_gatv2_supported(1, 512) == 1 and lib.pygamd_gatv2_supported(64, 8) == 1
+    assert lib.pygamd_gatv2_supported(8, 128) == 0 and lib.pygamd_gatv2_supported(65, 1) == 0
+    assert lib.pygamd_gatv2_supported(0, 4) == 0
+    assert lib.pygamd_gatv2_workspace_bytes(3, 4, 8, ctypes.byref(nbytes)) == 0
+    assert nbytes.value >= 4 * 3 * (32 + 8)
+    assert lib.pygamd_gatv2_workspace_bytes(3, 4, 8, None) == 1
+    assert lib.pygamd_gatv2_workspace_bytes(-1, 4, 8, ctypes.byref(nbytes)) == 1
+    assert lib.pygamd_gatv2_workspace_bytes(0, 8, 128, ctypes.byref(nbytes)) == 2
+
+    def fwd(rowptr=dev, idx=1, x_l=dev, n_rows=5, H=4, C=8, hub_rows=None, n_hub=0, n_chunks=0,
+            alpha=dev, ws=None, ws_bytes=0):
+        return lib.pygamd_gatv2_forward(rowptr, dev, idx, x_l, dev, dev, n_rows, 9, H, C, 0.2,
+                                        hub_rows, hub_rows, n_hub, n_chunks, 1024, 256, alpha,
+                                        dev, ws, ws_bytes, None)
+
+    assert fwd(rowptr=None) == 1 and fwd(x_l=None) == 1 and fwd(alpha=None) == 1
+    assert fwd(idx=5) == 1 and fwd(n_rows=-1) == 1 and fwd(H=0) == 1 and fwd(C=0) == 1
+    assert fwd(H=8, C=128) == 2 and fwd(H=65, C=1) == 2
+    assert fwd(n_hub=2, n_chunks=8) == 1                        # a plan without its arrays
+    assert fwd(n_hub=0, n_chunks=3) == 1
+    assert fwd(hub_rows=dev, n_hub=2, n_chunks=1) == 1          # fewer chunks than hub rows
+    assert fwd(hub_rows=dev, n_hub=2, n_chunks=8) == 3          # no workspace for the partials
+    assert fwd(hub_rows=dev, n_hub=2, n_chunks=8, ws=dev, ws_bytes=64) == 3
+    assert fwd(n_rows=0) == 0                                   # no rows: nothing to launch
+
+    def bwd_dst(grad_out=dev, out=dev, grad_alpha=None, H=4, C=8, n_rows=5, grad_att=dev, ws=dev,
+                ws_bytes=1 << 30, grad_s=dev):
+        return lib.pygamd_gatv2_backward_dst(dev, dev, 1, dev, dev, dev, dev, grad_out, out,
+                                             grad_alpha, n_rows, 9, H, C, 0.2, None, None, 0, 0,
+                                             1024, 256, grad_s, dev, grad_att, ws, ws_bytes, None)
+
+    assert bwd_dst(grad_out=None) == 1 and bwd_dst(out=None) == 1
+    assert bwd_dst(grad_alpha=dev) == 1                         # both sources of d alpha given
+    assert bwd_dst(grad_out=None, out=None, grad_alpha=None) == 1
+    assert bwd_dst(grad_att=None) == 1 and bwd_dst(grad_s=None) == 1
+    assert bwd_dst(H=8, C=128) == 2 and bwd_dst(n_rows=-2) == 1
+    assert bwd_dst(ws=None, ws_bytes=0) == 3 and bwd_dst(ws_bytes=16) == 3
+
+    def bwd_src(slot_map=dev, idx=0, n_src=5, H=4, C=8, gx=dev, n_hub=0, n_chunks=0):
+        return lib.pygamd_gatv2_backward_src(dev, dev, slot_map, idx, dev, dev, dev, dev, dev,
+                                             None, n_src, 7, H, C, 0.2, None, None, n_hub,
+                                             n_chunks, 1024, 256, gx, None, 0, None)
+
+    assert bwd_src(slot_map=None) == 1 and bwd_src(gx=None) == 1 and bwd_src(idx=2) == 1
+    assert bwd_src(H=2, C=300) == 2 and bwd_src(n_src=-1) == 1
+    assert bwd_src(n_hub=1, n_chunks=4) == 1
+    assert bwd_src(n_src=0) == 0
