@@ -610,6 +610,63 @@ PYGAMD_API int pygamd_gatv2_backward_src(const void* rowptr_t, const void* col_t
                                          int64_t hub_chunk, float* grad_x_l, void* workspace,
                                          size_t workspace_bytes, void* stream);
 
+/* ---- a16b: TransformerConv's dot-product attention in one pass --------------------------------
+ * nn/conv/transformer_conv.py:263-283 (message: the scaled dot product, the softmax and the
+ * weighting of value_j) + the 'add' aggregation of propagate (transformer_conv.py:234-235) on a
+ * dst-sorted handle, without edge features.  For slot k of row i with j = col[k]:
+ *   s[k,h]   = scale * sum_c query[i,h,c] * key[j,h,c]          (scale = 1 / sqrt(C))
+ *   alpha    = softmax over the row (maximum subtracted, 1e-16 on the denominator; utils/_softmax.py)
+ *   out[i,h] = sum_k alpha[k,h] * value[j,h,:]
+ * query [>= n_rows, H*C] contiguous fp32; key and value are two pointers to rows of H*C floats with
+ * ONE row stride ld >= H*C (floats): separate contiguous tensors (ld = H*C) or the two halves of a
+ * [n_src, 2*H*C] projection (ld = 2*H*C, value = key + H*C).  alpha is [nnz, H] in SLOT order and
+ * always written; out [n_rows, H*C] may be NULL ("score mode": alpha only, value is not read).
+ * Supported head layouts, hub rows, chunk-order merges and reproducibility as for pygamd_gatv2_*
+ * (pygamd_transformer_supported; workspace of pygamd_transformer_workspace_bytes for the plan's
+ * n_chunks, 0 bytes without hub rows).  Status 1 / 2 / 3 before any device work.
+ *
+ * backward_dst (transformer_conv.py:273-282 differentiated): grad_s[k,h] = alpha * (d alpha - D),
+ *   grad_query[i] = scale * sum_k grad_s * key[j].  d alpha = <grad_out[i,h,:], value[j,h,:]> and
+ *   D = <grad_out[i,h,:], out[i,h,:]> when grad_out / out are given and grad_alpha is NULL; score
+ *   mode passes grad_alpha [nnz, H] (slot order), NULL for grad_out / out, and does not read value.
+ * backward_src: on the src-sorted handle with slot_map = by-source slot -> by-destination slot,
+ *   grad_key[j] = scale * sum_i grad_s * query[i] and grad_value[j] = sum_i alpha * grad_out[i],
+ *   both written at row stride ld (one [n_src, 2*H*C] gradient buffer feeds one dgrad GEMM);
+ *   grad_out NULL = score mode: grad_key only, grad_value may be NULL.                          */
+PYGAMD_API int pygamd_transformer_supported(int64_t H, int64_t C);
+PYGAMD_API int pygamd_transformer_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C,
+                                                  size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_transformer_forward(const void* rowptr, const void* col, int idx_dtype,
+                                          const float* query, const float* key,
+                                          const float* value, int64_t ld, int64_t n_rows,
+                                          int64_t n_src, int64_t H, int64_t C, float scale,
+                                          const void* hub_rows, const void* hub_chunk_ptr,
+                                          int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
+                                          int64_t hub_chunk, float* alpha, float* out,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_transformer_backward_dst(const void* rowptr, const void* col, int idx_dtype,
+                                               const float* key, const float* value, int64_t ld,
+                                               const float* alpha, const float* grad_out,
+                                               const float* out, const float* grad_alpha,
+                                               int64_t n_rows, int64_t n_src, int64_t H,
+                                               int64_t C, float scale, const void* hub_rows,
+                                               const void* hub_chunk_ptr, int64_t n_hub,
+                                               int64_t n_chunks, int64_t hub_threshold,
+                                               int64_t hub_chunk, float* grad_s,
+                                               float* grad_query, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_transformer_backward_src(const void* rowptr_t, const void* col_t,
+                                               const void* slot_map, int idx_dtype,
+                                               const float* query, const float* alpha,
+                                               const float* grad_s, const float* grad_out,
+                                               int64_t n_src, int64_t n_dst, int64_t H, int64_t C,
+                                               float scale, const void* hub_rows,
+                                               const void* hub_chunk_ptr, int64_t n_hub,
+                                               int64_t n_chunks, int64_t hub_threshold,
+                                               int64_t hub_chunk, float* grad_key,
+                                               float* grad_value, int64_t ld, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

@@ -653,6 +653,107 @@ class Gatv2ScoreFunction(Function):
         return g_l, g_r, g_att, None, None, None
 
 
+def _transformer_check(query: Tensor, key: Tensor, graph: EdgeIndex, n_dst: int):
+    if key.size(0) != graph.num_src_nodes:
+        raise ValueError(f"'key' has {key.size(0)} rows but the graph has "
+                         f"{graph.num_src_nodes} source nodes")
+    if n_dst != graph.num_dst_nodes or query.size(0) < n_dst:
+        raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = {n_dst}, "
+                         f"'query' has {query.size(0)} rows")
+
+
+def _transformer_backward(ctx, H, C, query, key, value, alpha, grad_out2, out2, grad_alpha,
+                          packed=False):
+    """The two launches both TransformerConv nodes share: by destination (d s, grad_query), then
+    by source (grad_key and, unless in score mode, grad_value).  ``grad_alpha`` given = score
+    mode."""
+    graph = ctx.graph
+    fwd = graph.by_dst()
+    grad_s, g_q = _native.transformer_backward_dst(
+        fwd.ptr, fwd.idx, query, key, value, alpha, H, C, ctx.scale, grad_out=grad_out2,
+        out=out2, grad_alpha=grad_alpha, hub=fwd.hub)
+    g_k = g_v = None
+    if ctx.needs_input_grad[1] or (grad_alpha is None and ctx.needs_input_grad[2]):
+        bwd = graph.by_src()
+        g_k, g_v = _native.transformer_backward_src(
+            bwd.ptr, bwd.idx, graph.src_slot_to_dst_slot(), query, alpha, grad_s, H, C,
+            ctx.scale, grad_out=grad_out2, n_dst=fwd.n_rows, hub=bwd.hub, packed=packed)
+    return g_q, g_k, g_v
+
+
+class TransformerAttendFunction(Function):
+    """One dot-product attention + aggregation step of TransformerConv on projected features
+    ``query [>= n_dst, H, C]`` (destinations, a prefix), ``key`` and ``value [N_src, H, C]``
+    (sources): scaled score, softmax per destination and the weighted sum of ``value``
+    (transformer_conv.py:263-283) in ONE pass over the by-destination slots; the backward is one
+    pass by destination and one by source (csrc/transformer.hip).  ``value=None``: ``key`` is the
+    packed projection ``[N_src, 2, H, C]`` (key, then value, of every source); both halves are
+    read in place and ONE packed gradient comes back.  Saved: the inputs, ``alpha [E, H]`` (slot
+    order) and ``out`` — nothing of size ``E x H*C``."""
+
+    @staticmethod
+    def forward(ctx, query: Tensor, key: Tensor, value: Optional[Tensor], graph: EdgeIndex,
+                scale: float, n_dst: int):
+        _, H, C = query.shape
+        W = H * C
+        _transformer_check(query, key, graph, n_dst)
+        fwd = graph.by_dst()
+        q2 = query.reshape(-1, W)
+        packed = value is None
+        if packed:
+            kv = key.reshape(-1, 2 * W)
+            k2, v2 = kv[:, :W], kv[:, W:]
+        else:
+            k2, v2 = key.reshape(-1, W), value.reshape(-1, W)
+        alpha, out = _native.transformer_forward(fwd.ptr, fwd.idx, q2, k2, v2, H, C, scale,
+                                                 hub=fwd.hub)
+        ctx.save_for_backward(q2, k2, v2, alpha, out)
+        ctx.graph, ctx.scale, ctx.dims, ctx.packed = graph, scale, (H, C), packed
+        ctx.key_shape = key.shape
+        return out.view(fwd.n_rows, H, C)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        q2, k2, v2, alpha, out = ctx.saved_tensors
+        H, C = ctx.dims
+        g_q, g_k, g_v = _transformer_backward(ctx, H, C, q2, k2, v2, alpha, _rows(grad_out), out,
+                                              None, packed=ctx.packed)
+        g_q = g_q.view(-1, H, C)
+        if ctx.packed:  # g_k is the one [N_src, 2 * H * C] buffer: grad_key | grad_value
+            return g_q, None if g_k is None else g_k.view(ctx.key_shape), None, None, None, None
+        return (g_q, None if g_k is None else g_k.view(ctx.key_shape),
+                None if g_v is None else g_v.view(ctx.key_shape), None, None, None)
+
+
+class TransformerScoreFunction(Function):
+    """The attention coefficients of :class:`TransformerAttendFunction` alone: ``alpha [E, H]`` in
+    by-destination slot order, for layers that consume them themselves (dropout on the
+    coefficients, ``return_attention_weights``) and aggregate with ``SpmmFunction(..., 'slot')``."""
+
+    @staticmethod
+    def forward(ctx, query: Tensor, key: Tensor, graph: EdgeIndex, scale: float, n_dst: int):
+        _, H, C = query.shape
+        _transformer_check(query, key, graph, n_dst)
+        fwd = graph.by_dst()
+        q2, k2 = query.reshape(-1, H * C), key.reshape(-1, H * C)
+        alpha, _ = _native.transformer_forward(fwd.ptr, fwd.idx, q2, k2, None, H, C, scale,
+                                               hub=fwd.hub, aggregate=False)
+        ctx.save_for_backward(q2, k2, alpha)
+        ctx.graph, ctx.scale, ctx.dims, ctx.key_shape = graph, scale, (H, C), key.shape
+        return alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_alpha: Tensor):
+        q2, k2, alpha = ctx.saved_tensors
+        H, C = ctx.dims
+        g_q, g_k, _ = _transformer_backward(ctx, H, C, q2, k2, None, alpha, None, None,
+                                            grad_alpha.contiguous())
+        return (g_q.view(-1, H, C), None if g_k is None else g_k.view(ctx.key_shape), None, None,
+                None)
+
+
 class HeadDotFunction(Function):
     """(a_src, a_dst) = ((x * att_src).sum(-1), (x * att_dst).sum(-1)) for x [N, H, C] and
     att_* [1, H, C] (nn/conv/gat_conv.py:330-332) — one pass over x, one fused backward."""

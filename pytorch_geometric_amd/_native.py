@@ -1210,6 +1210,161 @@ def gatv2_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, x_l: T
     return grad_x_l
 
 
+# ---- TransformerConv's dot-product attention (csrc/transformer.hip) ------------------------------
+def transformer_supported(H: int, C: int) -> bool:
+    """The one-pass kernels serve this head layout (H * C <= 512, H <= 64)."""
+    return bool(_lib.load().pygamd_transformer_supported(int(H), int(C)))
+
+
+def _transformer_workspace(lib, n_chunks: int, H: int, C: int, device):
+    nbytes = ctypes.c_size_t(0)
+    check(lib.pygamd_transformer_workspace_bytes(n_chunks, H, C, ctypes.byref(nbytes)))
+    if nbytes.value == 0:
+        return None, 0
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
+
+
+def _strided_rows(t: Tensor, name: str, width: int) -> Tensor:
+    """``[n, width]`` float32 rows with unit column stride: a contiguous tensor or a column block
+    of a wider one (the halves of a packed key | value projection) is taken in place."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.size(1) != width:
+        raise ValueError(f"'{name}' must be a float32 [n, {width}] tensor (got {t.dtype} "
+                         f"{tuple(t.shape)})")
+    return t.contiguous() if t.stride(1) != 1 or t.stride(0) < width else t
+
+
+def _key_value(key: Tensor, value: Optional[Tensor], W: int):
+    """``key`` and ``value`` with one shared row stride (copies made contiguous if they differ)."""
+    key = _strided_rows(key, 'key', W)
+    if value is None:
+        return key, None, key.stride(0)
+    value = _strided_rows(value, 'value', W)
+    if value.size(0) != key.size(0):
+        raise ValueError("'key' and 'value' need one row per source each")
+    if key.stride(0) != value.stride(0):
+        key, value = key.contiguous(), value.contiguous()
+    return key, value, key.stride(0)
+
+
+def transformer_forward(rowptr: Tensor, col: Tensor, query: Tensor, key: Tensor,
+                        value: Optional[Tensor], H: int, C: int, scale: float, *, hub=None,
+                        aggregate: bool = True):
+    """``(alpha [nnz, H] in slot order, out [n_rows, H * C] | None)`` of one dot-product attention
+    step on a by-destination handle; ``aggregate=False`` is the score mode (alpha only, ``value``
+    not read)."""
+    _require_device(rowptr, col, query, key, value)
+    lib = _lib.load()
+    W = H * C
+    query = _gatv2_rows(query, 'query', W)
+    key, value, ld = _key_value(key, value if aggregate else None, W)
+    n_rows = rowptr.numel() - 1
+    if query.size(0) < n_rows:
+        raise ValueError(f"'query' needs at least {n_rows} rows")
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    alpha = torch.empty(col.numel(), H, dtype=torch.float32, device=query.device)
+    out = torch.empty(n_rows, W, dtype=torch.float32, device=query.device) if aggregate else None
+    if col.numel() == 0:  # no edges: every row is empty
+        return alpha, (out.zero_() if aggregate else None)
+    ws, ws_bytes = (_transformer_workspace(lib, n_chunks, H, C, query.device) if n_chunks > 0
+                    else (None, 0))
+    with _timed({'kind': 'transformer', 'op': 'forward' if aggregate else 'score',
+                 'n_rows': n_rows, 'E': col.numel(), 'H': H, 'C': C, 'ld': ld, 'n_hub': n_hub,
+                 'n_chunks': n_chunks}, query):
+        check(lib.pygamd_transformer_forward(
+            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(query), _p(key), _p(value), ld, n_rows,
+            key.size(0), H, C, float(scale), _p(h_rows), _p(h_cptr), n_hub, n_chunks,
+            HUB_THRESHOLD, HUB_CHUNK, _p(alpha), _p(out), _p(ws), ws_bytes, _stream(query)),
+            'transformer_forward')
+    return alpha, out
+
+
+def transformer_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, key: Tensor,
+                             value: Optional[Tensor], alpha: Tensor, H: int, C: int,
+                             scale: float, *, grad_out: Optional[Tensor] = None,
+                             out: Optional[Tensor] = None, grad_alpha: Optional[Tensor] = None,
+                             hub=None):
+    """``(grad_s [nnz, H], grad_query [rows of query, H * C])``; ``grad_alpha`` given = score mode
+    (``value`` not read), otherwise ``grad_out`` and ``out``."""
+    _require_device(rowptr, col, query, key, value, alpha, grad_out, out, grad_alpha)
+    lib = _lib.load()
+    W = H * C
+    score = grad_alpha is not None
+    key, value, ld = _key_value(key, None if score else value, W)
+    alpha = alpha.contiguous()
+    n_rows = rowptr.numel() - 1
+    if score:
+        grad_alpha = grad_alpha.contiguous()
+    else:
+        grad_out, out = _gatv2_rows(grad_out, 'grad_out', W), _gatv2_rows(out, 'out', W)
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    grad_s = torch.empty_like(alpha)
+    # (destinations may be a prefix of the rows of query: the rest takes no gradient)
+    alloc = torch.empty if query.size(0) == n_rows else torch.zeros
+    grad_query = alloc(query.size(0), W, dtype=torch.float32, device=key.device)
+    if col.numel() == 0:
+        return grad_s, grad_query.zero_()
+    ws, ws_bytes = _transformer_workspace(lib, n_chunks, H, C, key.device)
+    with _timed({'kind': 'transformer', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(),
+                 'H': H, 'C': C, 'ld': ld, 'n_hub': n_hub, 'n_chunks': n_chunks,
+                 'score': score}, key):
+        check(lib.pygamd_transformer_backward_dst(
+            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(key), _p(value), ld, _p(alpha),
+            _p(grad_out), _p(out), _p(grad_alpha), n_rows, key.size(0), H, C, float(scale),
+            _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_s),
+            _p(grad_query), _p(ws), ws_bytes, _stream(key)), 'transformer_backward_dst')
+    return grad_s, grad_query
+
+
+def transformer_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, query: Tensor,
+                             alpha: Tensor, grad_s: Tensor, H: int, C: int, scale: float, *,
+                             grad_out: Optional[Tensor] = None, n_dst: int, hub=None,
+                             packed: bool = False):
+    """``(grad_key, grad_value | None)``, ``[n_src, H * C]`` each, on the by-source handle;
+    ``grad_out=None`` = score mode (``grad_key`` only).  ``packed``: the two are the halves of ONE
+    ``[n_src, 2 * H * C]`` buffer (row stride ``2 * H * C``), the gradient of a packed key | value
+    projection, and that buffer is returned in place of the pair's first entry (the second is
+    None)."""
+    _require_device(rowptr_t, col_t, slot_map, query, alpha, grad_s, grad_out)
+    lib = _lib.load()
+    W = H * C
+    query = _gatv2_rows(query, 'query', W)
+    alpha, grad_s = alpha.contiguous(), grad_s.contiguous()
+    score = grad_out is None
+    if not score:
+        grad_out = _gatv2_rows(grad_out, 'grad_out', W)
+    n_src = rowptr_t.numel() - 1
+    if slot_map.dtype != rowptr_t.dtype:
+        raise ValueError("'slot_map' must have the index dtype")
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    if packed and score:
+        raise ValueError('the score mode has no value gradient to pack')
+    if packed:
+        both = torch.empty(n_src, 2 * W, dtype=torch.float32, device=query.device)
+        grad_key, grad_value, ld = both[:, :W], both[:, W:], 2 * W
+        result = (both, None)
+    else:
+        grad_key = torch.empty(n_src, W, dtype=torch.float32, device=query.device)
+        grad_value = None if score else torch.empty_like(grad_key)
+        ld = W
+        result = (grad_key, grad_value)
+    if col_t.numel() == 0:
+        for t in result:
+            if t is not None:
+                t.zero_()
+        return result
+    ws, ws_bytes = (_transformer_workspace(lib, n_chunks, H, C, query.device) if n_chunks > 0
+                    else (None, 0))
+    with _timed({'kind': 'transformer', 'op': 'backward_src', 'n_rows': n_src,
+                 'E': col_t.numel(), 'H': H, 'C': C, 'ld': ld, 'n_hub': n_hub,
+                 'n_chunks': n_chunks, 'score': score}, query):
+        check(lib.pygamd_transformer_backward_src(
+            _p(rowptr_t), _p(col_t), _p(slot_map.contiguous()), _idx_dtype(rowptr_t), _p(query),
+            _p(alpha), _p(grad_s), _p(grad_out), n_src, n_dst, H, C, float(scale), _p(h_rows),
+            _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_key), _p(grad_value),
+            ld, _p(ws), ws_bytes, _stream(query)), 'transformer_backward_src')
+    return result
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

@@ -17,122 +17,17 @@
 // result, the att gradient included, is bitwise reproducible.
 #include <math.h>
 
+#include "attn_device.h"
 #include "common.h"
 
 namespace pygamd {
 namespace {
 
-constexpr int kGv2MaxWidth = 512;
-constexpr int kGv2MaxHeads = 64;
+using namespace attn;  // layout, work items and merges: attn_device.h
+
+constexpr int kGv2MaxWidth = kAttnMaxWidth;
+constexpr int kGv2MaxHeads = kAttnMaxHeads;
 constexpr int kGv2MaxBlocks = 1024;  // persistent grid of the by-destination backward
-
-struct Lay {
-  int H, C, lph, h, sub;
-  bool head_ok;
-};
-
-__device__ __forceinline__ Lay make_lay(int H, int C, int lph) {
-  Lay L;
-  L.H = H;
-  L.C = C;
-  L.lph = lph;
-  L.h = lane_id() / lph;
-  L.sub = lane_id() % lph;
-  L.head_ok = L.h < H;
-  return L;
-}
-
-template <int EPL, bool VEC>
-__device__ __forceinline__ void load_row(const float* __restrict__ row, const Lay& L,
-                                         float (&v)[EPL]) {
-  if constexpr (VEC) {
-#pragma unroll
-    for (int q = 0; q < EPL / 4; ++q) {
-      const int c = (L.sub + L.lph * q) * 4;
-      if (L.head_ok && c < L.C) {
-        const Vec<4> t = load_vec<4>(row + L.h * L.C + c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[4 * q + i] = t.v[i];
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[4 * q + i] = 0.f;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < EPL; ++r) {
-      const int c = L.sub + L.lph * r;
-      v[r] = (L.head_ok && c < L.C) ? row[L.h * L.C + c] : 0.f;
-    }
-  }
-}
-
-template <int EPL, bool VEC>
-__device__ __forceinline__ void store_row(float* __restrict__ row, const Lay& L,
-                                          const float (&v)[EPL]) {
-  if constexpr (VEC) {
-#pragma unroll
-    for (int q = 0; q < EPL / 4; ++q) {
-      const int c = (L.sub + L.lph * q) * 4;
-      if (L.head_ok && c < L.C) {
-        Vec<4> t;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) t.v[i] = v[4 * q + i];
-        store_vec<4>(row + L.h * L.C + c, t);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < EPL; ++r) {
-      const int c = L.sub + L.lph * r;
-      if (L.head_ok && c < L.C) row[L.h * L.C + c] = v[r];
-    }
-  }
-}
-
-// sum over the lph lanes of a head; every lane of the group gets the total
-__device__ __forceinline__ float group_sum(float v, int lph) {
-  for (int o = lph >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-
-// Work items of a launch: the chunks of the hub rows first (they are the long ones), then every
-// row; a hub row's own item does nothing.
-template <typename IdxT>
-struct Items {
-  const IdxT* rowptr;
-  const IdxT* hub_rows;
-  const IdxT* hub_cptr;
-  int64_t n_rows, n_hub, n_chunks, threshold, chunk;
-};
-
-struct Span {
-  int64_t row, k0, k1, row_start, row_end, chunk_id;  // chunk_id < 0: a whole row
-};
-
-template <typename IdxT>
-__device__ __forceinline__ bool decode(const Items<IdxT>& it, int64_t item, Span& s) {
-  if (item < it.n_chunks) {
-    int64_t lo = 0, hi = it.n_hub - 1;  // last hub row whose first chunk is <= item
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (static_cast<int64_t>(it.hub_cptr[mid]) <= item) lo = mid; else hi = mid - 1;
-    }
-    s.row = static_cast<int64_t>(it.hub_rows[lo]);
-    s.row_start = static_cast<int64_t>(it.rowptr[s.row]);
-    s.row_end = static_cast<int64_t>(it.rowptr[s.row + 1]);
-    s.k0 = s.row_start + (item - static_cast<int64_t>(it.hub_cptr[lo])) * it.chunk;
-    s.k1 = s.k0 + it.chunk < s.row_end ? s.k0 + it.chunk : s.row_end;
-    s.chunk_id = item;
-    return s.k0 < s.row_end;
-  }
-  s.row = item - it.n_chunks;
-  if (s.row >= it.n_rows) return false;
-  s.row_start = s.k0 = static_cast<int64_t>(it.rowptr[s.row]);
-  s.row_end = s.k1 = static_cast<int64_t>(it.rowptr[s.row + 1]);
-  s.chunk_id = -1;
-  return !(it.n_hub > 0 && s.row_end - s.row_start > it.threshold);
-}
 
 template <int EPL>
 struct InFlight {
@@ -221,38 +116,8 @@ __global__ void __launch_bounds__(kWave)
                            const float* __restrict__ part, float* __restrict__ alpha,
                            float* __restrict__ out) {
   __shared__ float sm[kGv2MaxHeads], sinv[kGv2MaxHeads];
-  const int64_t hr = blockIdx.x;
-  const int64_t row = static_cast<int64_t>(hub_rows[hr]);
-  const int64_t c0 = static_cast<int64_t>(hub_cptr[hr]), c1 = static_cast<int64_t>(hub_cptr[hr + 1]);
-  const int64_t W = static_cast<int64_t>(H) * C, S = W + 2 * H;
-  const int lane = threadIdx.x;
-  if (lane < H) {
-    float m = -INFINITY, l = 0.f;
-    for (int64_t c = c0; c < c1; ++c) {
-      const float mc = part[c * S + W + lane], lc = part[c * S + W + H + lane];
-      const float mn = fmaxf(m, mc);
-      l = l * expf(m - mn) + lc * expf(mc - mn);
-      m = mn;
-    }
-    sm[lane] = m;
-    sinv[lane] = 1.f / (l + 1e-16f);
-  }
-  __syncthreads();
-  if (out) {
-    for (int64_t t = lane; t < W; t += kWave) {
-      const int h = static_cast<int>(t / C);
-      float acc = 0.f;
-      for (int64_t c = c0; c < c1; ++c)
-        acc = fmaf(part[c * S + t], expf(part[c * S + W + h] - sm[h]), acc);
-      out[row * W + t] = acc * sinv[h];
-    }
-  }
-  const int64_t k0 = static_cast<int64_t>(rowptr[row]) * H;
-  const int64_t k1 = static_cast<int64_t>(rowptr[row + 1]) * H;
-  for (int64_t t = k0 + lane; t < k1; t += kWave) {
-    const int h = static_cast<int>(t % H);
-    alpha[t] = expf(alpha[t] - sm[h]) * sinv[h];
-  }
+  merge_softmax_row(rowptr, hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), H, C, part,
+                    alpha, out, sm, sinv, 0, static_cast<int64_t>(H) * C, true, nullptr);
 }
 
 // partial rows of a hub row summed in chunk order
@@ -260,14 +125,7 @@ template <typename IdxT>
 __global__ void __launch_bounds__(kWave)
     gatv2_sum_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
                            int64_t W, const float* __restrict__ part, float* __restrict__ dst) {
-  const int64_t hr = blockIdx.x;
-  const int64_t row = static_cast<int64_t>(hub_rows[hr]);
-  const int64_t c0 = static_cast<int64_t>(hub_cptr[hr]), c1 = static_cast<int64_t>(hub_cptr[hr + 1]);
-  for (int64_t t = threadIdx.x; t < W; t += kWave) {
-    float acc = 0.f;
-    for (int64_t c = c0; c < c1; ++c) acc += part[c * W + t];
-    dst[row * W + t] = acc;
-  }
+  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), W, part, W, dst, W);
 }
 
 // ---- backward, by destination -------------------------------------------------------------------
@@ -423,52 +281,7 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---- host side -------------------------------------------------------------------------------
-struct Shape {
-  int lph, epl;
-  bool vec;
-};
-
-bool choose_shape(int64_t H, int64_t C, bool aligned, Shape* s) {
-  if (H < 1 || C < 1 || H * C > kGv2MaxWidth || H > kGv2MaxHeads) return false;
-  int cap = 1;
-  while (cap * 2 * H <= kWave) cap *= 2;
-  if (aligned && C % 4 == 0) {
-    const int units = static_cast<int>(C / 4);
-    int lph = cap;
-    while (lph > 1 && lph / 2 >= units) lph /= 2;
-    const int n = (units + lph - 1) / lph;
-    if (n <= 2) {
-      *s = Shape{lph, 4 * n, true};
-      return true;
-    }
-  }
-  int lph = cap;
-  while (lph > 1 && lph / 2 >= C) lph /= 2;
-  const int n = static_cast<int>((C + lph - 1) / lph);
-  int epl = 1;
-  while (epl < n) epl *= 2;
-  if (epl > 16) return false;
-  *s = Shape{lph, epl, false};
-  return true;
-}
-
-#define GV2_DISPATCH_SHAPE(shape, ...)                                  \
-  do {                                                                  \
-    if ((shape).vec) {                                                  \
-      if ((shape).epl == 4) { constexpr int EPL = 4; constexpr bool VEC = true; __VA_ARGS__ }   \
-      else { constexpr int EPL = 8; constexpr bool VEC = true; __VA_ARGS__ }                    \
-    } else {                                                            \
-      switch ((shape).epl) {                                            \
-        case 1: { constexpr int EPL = 1; constexpr bool VEC = false; __VA_ARGS__ } break;       \
-        case 2: { constexpr int EPL = 2; constexpr bool VEC = false; __VA_ARGS__ } break;       \
-        case 4: { constexpr int EPL = 4; constexpr bool VEC = false; __VA_ARGS__ } break;       \
-        case 8: { constexpr int EPL = 8; constexpr bool VEC = false; __VA_ARGS__ } break;       \
-        default: { constexpr int EPL = 16; constexpr bool VEC = false; __VA_ARGS__ } break;     \
-      }                                                                 \
-    }                                                                   \
-  } while (0)
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+#define GV2_DISPATCH_SHAPE ATTN_DISPATCH_SHAPE
 
 size_t gv2_ws_bytes(int64_t n_chunks, int64_t H, int64_t C) {
   const int64_t W = H * C;
@@ -479,14 +292,8 @@ size_t gv2_ws_bytes(int64_t n_chunks, int64_t H, int64_t C) {
 int gv2_check(int idx_dtype, int64_t n_rows, int64_t n_other, int64_t H, int64_t C,
               const void* hub_rows, const void* hub_cptr, int64_t n_hub, int64_t n_chunks,
               int64_t threshold, int64_t chunk) {
-  if (idx_dtype != PYGAMD_IDX_I64 && idx_dtype != PYGAMD_IDX_I32) return PYGAMD_ERR_INVALID_ARG;
-  if (n_rows < 0 || n_other < 0 || H < 1 || C < 1 || n_hub < 0 || n_chunks < 0)
-    return PYGAMD_ERR_INVALID_ARG;
-  if (n_hub > 0 && (!hub_rows || !hub_cptr || n_chunks < n_hub || threshold < 1 || chunk < 1))
-    return PYGAMD_ERR_INVALID_ARG;
-  if (n_hub == 0 && n_chunks != 0) return PYGAMD_ERR_INVALID_ARG;
-  if (H * C > kGv2MaxWidth || H > kGv2MaxHeads) return PYGAMD_ERR_UNSUPPORTED;
-  return PYGAMD_OK;
+  return check_args(idx_dtype, n_rows, n_other, H, C, hub_rows, hub_cptr, n_hub, n_chunks,
+                    threshold, chunk);
 }
 
 }  // namespace

@@ -2,7 +2,7 @@ from .aggr import (Aggregation, FusedAggregation, MaxAggregation, MeanAggregatio
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
 from .conv import (FastRGCNConv, GATConv, GATv2Conv, GCNConv, GraphConv, HeteroConv, MessagePassing,
-                   RGCNConv, SAGEConv, gcn_norm, group)
+                   RGCNConv, SAGEConv, TransformerConv, gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, GraphSAGE
 from . import functional  # noqa: F401
@@ -10,7 +10,7 @@ from . import functional  # noqa: F401
 __all__ = [
     'Aggregation', 'SumAggregation', 'MeanAggregation', 'MaxAggregation', 'MinAggregation',
     'MulAggregation', 'VarAggregation', 'StdAggregation', 'FusedAggregation',
-    'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
+    'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
     'HeteroDictLinear', 'HeteroConv', 'group',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

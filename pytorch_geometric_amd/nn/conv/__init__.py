@@ -3,9 +3,10 @@ from .sage_conv import SAGEConv
 from .gcn_conv import GCNConv, gcn_norm
 from .gat_conv import GATConv
 from .gatv2_conv import GATv2Conv
+from .transformer_conv import TransformerConv
 from .rgcn_conv import FastRGCNConv, RGCNConv
 from .graph_conv import GraphConv
 from .hetero_conv import HeteroConv, group
 
-__all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'RGCNConv', 'FastRGCNConv',
+__all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group']

@@ -29,6 +29,8 @@ Operators (all index tensors int32 / int64, features float32):
 ``linear``                  ``(Tensor x, Tensor weight, Tensor? bias) -> Tensor``
 ``gatv2_attend``            ``(Tensor x_l, Tensor x_r, Tensor att, Tensor rowptr, Tensor col,
                             float negative_slope) -> (Tensor out, Tensor alpha)``
+``transformer_attend``      ``(Tensor query, Tensor key, Tensor value, Tensor rowptr, Tensor col,
+                            float scale) -> (Tensor out, Tensor alpha)``
 ==========================  ===========================================================
 """
 import math
@@ -433,6 +435,73 @@ def _gatv2_bwd(ctx, grad, _grad_alpha):
 
 register_autograd('pyg_amd::gatv2_attend', _gatv2_bwd, setup_context=_gatv2_setup)
 
+# ---- TransformerConv's dot-product attention on a CSR pair (rows = destinations) ------------------
+@custom_op('pyg_amd::transformer_attend', mutates_args=(), device_types=_DEV)
+def transformer_attend(query: Tensor, key: Tensor, value: Tensor, rowptr: Tensor, col: Tensor,
+                       scale: float) -> Tuple[Tensor, Tensor]:
+    """``(out [n_dst, H, C], alpha [nnz, H])`` of one dot-product attention step
+    (transformer_conv.py:263-283) for ``query [>= n_dst, H, C]`` and ``key``, ``value
+    [n_src, H, C]``; ``alpha`` follows the slots of ``col`` and is returned for inspection
+    (gradients flow through ``out``)."""
+    _, H, C = query.shape
+    if not _native.transformer_supported(H, C):
+        raise NotImplementedError(
+            f'transformer_attend serves H * C <= 512 and H <= 64 (got {H} x {C})')
+    alpha, out = _native.transformer_forward(rowptr, col, _rows(query), _rows(key), _rows(value),
+                                             H, C, scale, hub=_native.hub_plan(rowptr))
+    return out.reshape(rowptr.numel() - 1, H, C), alpha
+
+
+@transformer_attend.register_fake
+def _(query, key, value, rowptr, col, scale):
+    return (query.new_empty(rowptr.numel() - 1, *query.shape[1:]),
+            query.new_empty(col.numel(), query.shape[1]))
+
+
+@custom_op('pyg_amd::transformer_attend_backward', mutates_args=(), device_types=_DEV)
+def transformer_attend_backward(grad: Tensor, query: Tensor, key: Tensor, value: Tensor,
+                                alpha: Tensor, out: Tensor, rowptr: Tensor, col: Tensor,
+                                scale: float) -> Tuple[Tensor, Tensor, Tensor]:
+    _, H, C = query.shape
+    n_dst = rowptr.numel() - 1
+    q2, g2 = _rows(query), _rows(grad).contiguous()
+    grad_s, g_q = _native.transformer_backward_dst(
+        rowptr, col, q2, _rows(key), _rows(value), alpha, H, C, scale, grad_out=g2,
+        out=_rows(out), hub=_native.hub_plan(rowptr))
+    # the by-source form of the same slots: a stable sort of `col`; its permutation IS the map
+    # from by-source slots to the CSR's own (by-destination) slots
+    dst = _native.ptr2index(rowptr, col.numel())
+    src_sorted, perm = _native.index_sort(col, max_value=max(key.size(0) - 1, 0))
+    rowptr_t = _native.index2ptr(src_sorted, key.size(0))
+    col_t = _native.permute_index(dst, perm)
+    g_k, g_v = _native.transformer_backward_src(
+        rowptr_t, col_t, _native.cast_index(perm, col.dtype), q2, alpha, grad_s, H, C, scale,
+        grad_out=g2, n_dst=n_dst, hub=_native.hub_plan(rowptr_t))
+    return g_q.reshape(query.shape), g_k.reshape(key.shape), g_v.reshape(value.shape)
+
+
+@transformer_attend_backward.register_fake
+def _(grad, query, key, value, alpha, out, rowptr, col, scale):
+    return torch.empty_like(query), torch.empty_like(key), torch.empty_like(value)
+
+
+def _transformer_setup(ctx, inputs, output):
+    query, key, value, rowptr, col, scale = inputs
+    ctx.scale = scale
+    ctx.save_for_backward(query, key, value, output[1], output[0], rowptr, col)
+
+
+def _transformer_bwd(ctx, grad, _grad_alpha):
+    query, key, value, alpha, out, rowptr, col = ctx.saved_tensors
+    g_q, g_k, g_v = transformer_attend_backward(grad.contiguous(), query, key, value, alpha, out,
+                                                rowptr, col, ctx.scale)
+    return g_q, g_k, g_v, None, None, None
+
+
+register_autograd('pyg_amd::transformer_attend', _transformer_bwd,
+                  setup_context=_transformer_setup)
+
 OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_backward',
        'segment_csr', 'segment_csr_backward', 'softmax_csr', 'softmax_csr_backward', 'spmm',
-       'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward')
+       'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
+       'transformer_attend_backward')
