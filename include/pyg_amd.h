@@ -1015,6 +1015,52 @@ PYGAMD_API int pygamd_hetero_spmm_backward(const void* rowptr_t, const void* col
                                            const int64_t* ld_grad_x, int n_nt, int64_t F,
                                            void* stream);
 
+/* ---- HGTConv: the typed relation transform of every edge type in one launch ----------------------
+ * Replaces nn/conv/hgt_conv.py:118-154 (_construct_src_node_feat: for K and again for V a cat over
+ * the edge types, a transpose copy to [H * sum N, D], an int64 type vector, a grouped GEMM over
+ * H * T segments and a transpose back): csrc/hgt.hip.  For edge type e of the call with n_e source
+ * rows at stacked offset src_off[e] = sum of the n of the edge types before it:
+ *   kv[src_off[e] + j, 0, h, :] = k[e][j, h, :] @ wk[h * T + widx(e)]       (D x D)
+ *   kv[src_off[e] + j, 1, h, :] = v[e][j, h, :] @ wv[h * T + widx(e)]
+ * k / v: host arrays [n_et] of device pointers to rows of H * D floats with ONE row stride per edge
+ * type (the k and v column blocks of the [N, 3 H D] projection, or contiguous tensors); wk / wv are
+ * the parameters as they are, [H * T, D, D] with T the number of edge types of the metadata and
+ * widx(e) the metadata position of e; kv is [S, 2 H D] contiguous, the packed key | value table
+ * pygamd_transformer_* reads with ld = 2 H D.  et_table: host int64 [n_et][4] = ld, n_e, widx,
+ * position of the source node type in nt_table (read by the backward only).  Exact fp32 on
+ * v_mfma_f32_16x16x4_f32 (an fmaf chain per output, reduction order fixed), a D that is not a
+ * multiple of 16 is padded inside.
+ * pygamd_hgt_relation_backward (no floating-point atomics, bitwise reproducible):
+ *   grad_k[t][j, h, :] = sum over the edge types e of the call with source node type t, in call
+ *   order, of grad_kv[src_off[e] + j, 0, h, :] @ wk[h * T + widx(e)]^T, accumulated in registers
+ *   and written once at row stride nt_table[t][1] (likewise grad_v): nt_table is host int64
+ *   [n_nt][2] = rows, ld; a node type no edge type reads gets zeros.  n_nt = 0 skips these.
+ *   grad_wk[h * T + widx(e)] = sum_j k[e][j, h, :]^T . grad_kv[src_off[e] + j, 0, h, :] (likewise
+ *   grad_wv): per-workgroup partial matrices in the workspace (pygamd_hgt_workspace_bytes for the
+ *   same et_table), summed in chunk order; EVERY matrix of both [H * T, D, D] gradients is written,
+ *   zeros for edge types that are not in the call.  grad_wk = grad_wv = NULL skips these.
+ * Supported (pygamd_hgt_supported): H * D <= 512, H <= 64, D <= 128; otherwise, and for n_et or
+ * n_nt above 64, PYGAMD_ERR_UNSUPPORTED.  n_et <= 0, T < n_et, H * T > 65535, a widx outside
+ * [0, T) or named twice, negative rows, rows of an edge type that differ from its node type's, a
+ * row stride below H * D or above INT32_MAX, a NULL pointer the call needs ->
+ * PYGAMD_ERR_INVALID_ARG; a short workspace -> PYGAMD_ERR_WORKSPACE; all before any launch.  An
+ * edge type with n_e = 0 is legal; a call without rows launches nothing in the forward.         */
+PYGAMD_API int pygamd_hgt_supported(int64_t H, int64_t D);
+PYGAMD_API int pygamd_hgt_workspace_bytes(const int64_t* et_table, int n_et, int64_t H, int64_t D,
+                                          size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_hgt_relation_forward(const float* const* k, const float* const* v,
+                                           const int64_t* et_table, int n_et, const float* wk,
+                                           const float* wv, int64_t T, int64_t H, int64_t D,
+                                           float* kv, void* stream);
+PYGAMD_API int pygamd_hgt_relation_backward(const float* const* k, const float* const* v,
+                                            const int64_t* et_table, int n_et, const float* wk,
+                                            const float* wv, int64_t T, int64_t H, int64_t D,
+                                            const float* grad_kv, float* const* grad_k,
+                                            float* const* grad_v, const int64_t* nt_table,
+                                            int n_nt, float* grad_wk, float* grad_wv,
+                                            void* workspace, size_t workspace_bytes,
+                                            void* stream);
+
 /* ---- a18: one-pass multi-reduce (FusedAggregation) ---------------------------------------------
  * nn/aggr/fused.py:191-336 shares the group count, the sum and the sum of squares between
  * sum / mean / var / std / min / max.  Here ONE read of the rows produces all requested statistics

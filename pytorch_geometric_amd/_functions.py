@@ -754,6 +754,62 @@ class TransformerScoreFunction(Function):
                 None)
 
 
+class HgtRelationPlan:
+    """Static description of one relation-transform node: ``heads``; ``src_pos[e]``: the position
+    (among the tensor inputs) of the source node type of edge type ``e`` of the call; ``widx[e]``:
+    its position in the layer's metadata, i.e. its matrix ``h * T + widx[e]`` of the weights."""
+
+    def __init__(self, heads: int, src_pos, widx):
+        self.heads, self.src_pos, self.widx = int(heads), tuple(src_pos), tuple(widx)
+
+
+class HGTRelationFunction(Function):
+    """The typed relation transform of HGTConv (hgt_conv.py:118-154) for every edge type of a
+    layer call in ONE launch: ``kqvs[t] [N_t, 3 * F]`` (the key | query | value projection of
+    source node type ``t``, read in place) and the relation weights ``[H * T, D, D]`` as the
+    parameters hold them -> the packed ``kv [S, 2 * F]`` of the stacked source rows, the table
+    ``TransformerAttendFunction`` reads.  The backward is one launch too (csrc/hgt.hip): the key
+    and value gradients of a node type land in the k and v column blocks of one ``[N_t, 3 * F]``
+    buffer (its q block is cleared: the query gradient arrives through the caller's slice), the
+    weight gradients are reduced from per-workgroup partials in a fixed order — no atomics."""
+
+    @staticmethod
+    def forward(ctx, plan: HgtRelationPlan, wk: Tensor, wv: Tensor, *kqvs: Tensor):
+        H, D = plan.heads, wk.size(-1)
+        F = H * D
+        for x in kqvs:
+            if x.dim() != 2 or x.size(1) != 3 * F:
+                raise ValueError(f"every 'kqv' must be [N, {3 * F}] (got {tuple(x.shape)})")
+        kqvs = tuple(_native._f32_rows(x, 'kqv') for x in kqvs)
+        wk, wv = wk.contiguous(), wv.contiguous()
+        ks = [kqvs[p][:, :F] for p in plan.src_pos]
+        vs = [kqvs[p][:, 2 * F:] for p in plan.src_pos]
+        kv = _native.hgt_relation_forward(ks, vs, plan.widx, wk, wv, H, D)
+        ctx.save_for_backward(wk, wv, *kqvs)
+        ctx.plan = plan
+        return kv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_kv: Tensor):
+        wk, wv, *kqvs = ctx.saved_tensors
+        plan = ctx.plan
+        H, D = plan.heads, wk.size(-1)
+        F = H * D
+        ks = [kqvs[p][:, :F] for p in plan.src_pos]
+        vs = [kqvs[p][:, 2 * F:] for p in plan.src_pos]
+        bufs = []
+        if any(ctx.needs_input_grad[3:]):
+            bufs = [torch.empty_like(x, memory_format=torch.contiguous_format) for x in kqvs]
+            for b in bufs:
+                b[:, F:2 * F].zero_()
+        g_wk, g_wv = _native.hgt_relation_backward(
+            ks, vs, plan.widx, plan.src_pos, wk, wv, H, D, grad_kv,
+            [b[:, :F] for b in bufs], [b[:, 2 * F:] for b in bufs],
+            weight_grads=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        return (None, g_wk, g_wv) + (tuple(bufs) if bufs else (None, ) * len(kqvs))
+
+
 class HeadDotFunction(Function):
     """(a_src, a_dst) = ((x * att_src).sum(-1), (x * att_dst).sum(-1)) for x [N, H, C] and
     att_* [1, H, C] (nn/conv/gat_conv.py:330-332) — one pass over x, one fused backward."""

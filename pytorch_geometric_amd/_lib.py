@@ -175,6 +175,12 @@ SIGNATURES = {
     'pygamd_hetero_spmm': (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P, _P]),
     'pygamd_hetero_spmm_backward': (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, _P,
                                             c_int, c_int64, _P]),
+    'pygamd_hgt_supported': (c_int, [c_int64, c_int64]),
+    'pygamd_hgt_workspace_bytes': (c_int, [_P, c_int, c_int64, c_int64, POINTER(c_size_t)]),
+    'pygamd_hgt_relation_forward': (c_int, [_P, _P, _P, c_int, _P, _P, c_int64, c_int64, c_int64,
+                                            _P, _P]),
+    'pygamd_hgt_relation_backward': (c_int, [_P, _P, _P, c_int, _P, _P, c_int64, c_int64, c_int64,
+                                             _P, _P, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
     'pygamd_hetero_sample_temporal_window': (c_int, [_P, _P, c_int, _P, c_int, _P, _P, _P, _P,
                                                      c_int, c_uint64, c_int, c_int, _P, _P, _P,
                                                      _P]),

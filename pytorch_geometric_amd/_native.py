@@ -2567,3 +2567,106 @@ def hetero_spmm_backward(rowptr_t: Tensor, col_t: Tensor, rowptr: Tensor, row_be
         _idx_dtype(rowptr), _i64_host([int(v) for v in row_begin]), _ptr_host(grads),
         _i64_host(table), n_et, _i64_host([int(v) for v in src_begin]), _ptr_host(grad_xs),
         _i64_host(lds), n_nt, F, _stream(rowptr)), 'hetero_spmm_backward')
+
+
+# ---- HGTConv: the typed relation transform (csrc/hgt.hip) ----------------------------------------
+def hgt_supported(H: int, D: int) -> bool:
+    """The relation kernels serve this head layout (H * D <= 512, H <= 64, D <= 128)."""
+    return bool(_lib.load().pygamd_hgt_supported(int(H), int(D)))
+
+
+def _hgt_table(ks, vs, widx, src_type, F: int):
+    n_et = len(ks)
+    if not (len(vs) == len(widx) == len(src_type) == n_et):
+        raise ValueError("'ks', 'vs', 'widx' and 'src_type' disagree about the edge types")
+    if n_et > MAX_HETERO_TYPES:
+        raise PygAmdError(f'hgt_relation failed: at most {MAX_HETERO_TYPES} edge types per launch '
+                          f'(got {n_et})')
+    table = []
+    for e in range(n_et):
+        k, v = _hetero_block(ks[e], 'ks', F), _hetero_block(vs[e], 'vs', F)
+        if k.size(0) != v.size(0) or _ld(k) != _ld(v):
+            raise ValueError(f"'ks[{e}]' and 'vs[{e}]' need the same rows and row stride")
+        table += [_ld(k), k.size(0), int(widx[e]), int(src_type[e])]
+    return table
+
+
+def _hgt_weights(wk: Tensor, wv: Tensor, H: int, D: int) -> int:
+    for w in (wk, wv):
+        if not (w.is_cuda and w.dtype == torch.float32 and w.dim() == 3 and w.is_contiguous()
+                and w.size(1) == D and w.size(2) == D and w.size(0) % H == 0):
+            raise ValueError(f"the relation weights must be contiguous float32 [H * T, {D}, {D}] "
+                             f"HIP tensors (got {tuple(w.shape)})")
+    if wk.shape != wv.shape:
+        raise ValueError('the key and value relation weights must have one shape')
+    return wk.size(0) // H
+
+
+def hgt_relation_forward(ks, vs, widx, wk: Tensor, wv: Tensor, H: int, D: int) -> Tensor:
+    """``pygamd_hgt_relation_forward``: the packed ``kv [S, 2 * H * D]`` of the stacked source rows
+    of every edge type of a call in one launch: ``kv[off[e] + j, 0, h] = ks[e][j, h] @ wk[h * T +
+    widx[e]]``, and ``vs`` / ``wv`` in the second half.  ``ks[e]`` / ``vs[e]``: ``[n_e, H * D]``
+    float32 row blocks read in place (column blocks of a wider projection are fine)."""
+    _require_device(wk, wv, *ks, *vs)
+    F = H * D
+    T = _hgt_weights(wk, wv, H, D)
+    table = _hgt_table(ks, vs, widx, [0] * len(ks), F)
+    S = sum(k.size(0) for k in ks)
+    kv = torch.empty(S, 2 * F, dtype=torch.float32, device=wk.device)
+    if not ks:
+        return kv
+    with _timed({'kind': 'hgt', 'op': 'relation_forward', 'S': S, 'H': H, 'D': D,
+                 'n_et': len(ks)}, wk):
+        check(_lib.load().pygamd_hgt_relation_forward(
+            _ptr_host(ks), _ptr_host(vs), _i64_host(table), len(ks), _p(wk), _p(wv), T, H, D,
+            _p(kv), _stream(wk)), 'hgt_relation_forward')
+    return kv
+
+
+def hgt_relation_backward(ks, vs, widx, src_type, wk: Tensor, wv: Tensor, H: int, D: int,
+                          grad_kv: Tensor, grad_ks, grad_vs, weight_grads: bool = True):
+    """``pygamd_hgt_relation_backward``: ``grad_ks[t]`` / ``grad_vs[t]`` (``[N_t, H * D]`` row
+    blocks of source node type ``t``, e.g. column blocks of one ``[N_t, 3 * H * D]`` buffer) are
+    overwritten with the input gradients, summed over the edge types with ``src_type[e] == t`` in
+    call order; returns ``(grad_wk, grad_wv)`` (every matrix written) or ``(None, None)``.  No
+    atomics: bitwise reproducible."""
+    _require_device(wk, wv, grad_kv, *ks, *vs, *grad_ks, *grad_vs)
+    lib = _lib.load()
+    F = H * D
+    T = _hgt_weights(wk, wv, H, D)
+    table = _hgt_table(ks, vs, widx, src_type, F)
+    S = sum(k.size(0) for k in ks)
+    if not (grad_kv.dtype == torch.float32 and grad_kv.shape == (S, 2 * F)):
+        raise ValueError(f"'grad_kv' must be float32 [{S}, {2 * F}] (got {tuple(grad_kv.shape)})")
+    grad_kv = grad_kv.contiguous()
+    if len(grad_ks) != len(grad_vs) or len(grad_ks) > MAX_HETERO_TYPES:
+        raise PygAmdError(f'hgt_relation_backward failed: at most {MAX_HETERO_TYPES} node types, '
+                          f'one key and one value gradient block each')
+    nt_table = []
+    for t, (gk, gv) in enumerate(zip(grad_ks, grad_vs)):
+        gk, gv = _hetero_block(gk, 'grad_ks', F), _hetero_block(gv, 'grad_vs', F)
+        if gk.size(0) != gv.size(0) or _ld(gk) != _ld(gv):
+            raise ValueError(f"'grad_ks[{t}]' and 'grad_vs[{t}]' need the same rows and row stride")
+        nt_table += [gk.size(0), _ld(gk)]
+    grad_wk = grad_wv = ws = None
+    ws_bytes = 0
+    if not ks:
+        for g in list(grad_ks) + list(grad_vs):
+            g.zero_()
+        return (torch.zeros_like(wk), torch.zeros_like(wv)) if weight_grads else (None, None)
+    if weight_grads:
+        grad_wk, grad_wv = torch.empty_like(wk), torch.empty_like(wv)
+        nbytes = ctypes.c_size_t(0)
+        check(lib.pygamd_hgt_workspace_bytes(_i64_host(table), len(ks), H, D,
+                                             ctypes.byref(nbytes)), 'hgt_workspace_bytes')
+        ws_bytes = nbytes.value
+        if ws_bytes:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=wk.device)
+    with _timed({'kind': 'hgt', 'op': 'relation_backward', 'S': S, 'H': H, 'D': D,
+                 'n_et': len(ks)}, wk):
+        check(lib.pygamd_hgt_relation_backward(
+            _ptr_host(ks), _ptr_host(vs), _i64_host(table), len(ks), _p(wk), _p(wv), T, H, D,
+            _p(grad_kv), _ptr_host(grad_ks), _ptr_host(grad_vs), _i64_host(nt_table),
+            len(grad_ks), _p(grad_wk), _p(grad_wv), _p(ws), ws_bytes, _stream(wk)),
+            'hgt_relation_backward')
+    return grad_wk, grad_wv

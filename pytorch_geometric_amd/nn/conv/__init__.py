@@ -7,6 +7,7 @@ from .transformer_conv import TransformerConv
 from .rgcn_conv import FastRGCNConv, RGCNConv
 from .graph_conv import GraphConv
 from .hetero_conv import HeteroConv, group
+from .hgt_conv import HGTConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
-           'GraphConv', 'HeteroConv', 'group']
+           'GraphConv', 'HeteroConv', 'group', 'HGTConv']

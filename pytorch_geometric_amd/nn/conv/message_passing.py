@@ -51,6 +51,8 @@ class MessagePassing(torch.nn.Module):
         self._edge_params = _params(self.edge_update)
         self._propagate_forward_pre_hooks = {}
         self._propagate_forward_hooks = {}
+        self._message_forward_pre_hooks = {}
+        self._message_forward_hooks = {}
         self._hook_id = 0
         has_fused = type(self).message_and_aggregate is not MessagePassing.message_and_aggregate
         self._fused_params = _params(self.message_and_aggregate)[1:] if has_fused else None
@@ -179,6 +181,15 @@ class MessagePassing(torch.nn.Module):
         """``hook(module, (edge_index, size, kwargs), output)`` may return a replacement output."""
         return self._register(self._propagate_forward_hooks, hook)
 
+    def register_message_forward_pre_hook(self, hook):
+        """``hook(module, (message_kwargs, ))`` may return a replacement tuple; a layer with
+        message hooks materialises its messages (gather -> ``message`` -> aggregate)."""
+        return self._register(self._message_forward_pre_hooks, hook)
+
+    def register_message_forward_hook(self, hook):
+        """``hook(module, (message_kwargs, ), output)`` may return a replacement output."""
+        return self._register(self._message_forward_hooks, hook)
+
     # -- the hot path -----------------------------------------------------------------------------
     def propagate(self, edge_index, size: Optional[Tuple[int, int]] = None, **kwargs) -> Tensor:
         r"""Gather -> message -> aggregate -> update (message_passing.py:421-563)."""
@@ -195,7 +206,9 @@ class MessagePassing(torch.nn.Module):
 
     def _propagate(self, edge_index, size, kwargs) -> Tensor:
         size = self._check_input(edge_index, size)
-        if self.fuse and self._fused_params is not None and self._can_fuse(kwargs):
+        observed = self._message_forward_pre_hooks or self._message_forward_hooks
+        if (self.fuse and self._fused_params is not None and not observed
+                and self._can_fuse(kwargs)):
             coll = self._collect(self._msg_params, edge_index, size, kwargs, lift=False)
             i, j = self._ij()
             n_src = size[j] if size[j] is not None else size[i]
@@ -206,7 +219,16 @@ class MessagePassing(torch.nn.Module):
             out = self.message_and_aggregate(graph, **fused)
         else:
             coll = self._collect(self._msg_params, edge_index, size, kwargs)
-            msg = self.message(**self._select(self._msg_params, coll, 'message'))
+            msg_kwargs = self._select(self._msg_params, coll, 'message')
+            for hook in list(self._message_forward_pre_hooks.values()):
+                res = hook(self, (msg_kwargs, ))
+                if res is not None:
+                    msg_kwargs = res[0] if isinstance(res, tuple) else res
+            msg = self.message(**msg_kwargs)
+            for hook in list(self._message_forward_hooks.values()):
+                res = hook(self, (msg_kwargs, ), msg)
+                if res is not None:
+                    msg = res
             out = self.aggregate(msg, index=coll['index'], ptr=coll['ptr'],
                                  dim_size=coll['dim_size'])
         for n in self._upd_params:

@@ -31,10 +31,12 @@ Operators (all index tensors int32 / int64, features float32):
                             float negative_slope) -> (Tensor out, Tensor alpha)``
 ``transformer_attend``      ``(Tensor query, Tensor key, Tensor value, Tensor rowptr, Tensor col,
                             float scale) -> (Tensor out, Tensor alpha)``
+``hgt_relation``            ``(Tensor[] kqvs, Tensor k_weight, Tensor v_weight, int[] src_pos,
+                            int[] widx, int heads) -> Tensor``
 ==========================  ===========================================================
 """
 import math
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -501,7 +503,75 @@ def _transformer_bwd(ctx, grad, _grad_alpha):
 register_autograd('pyg_amd::transformer_attend', _transformer_bwd,
                   setup_context=_transformer_setup)
 
+
+# ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
+def _hgt_blocks(kqvs, src_pos, F):
+    return ([kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos])
+
+
+@custom_op('pyg_amd::hgt_relation', mutates_args=(), device_types=_DEV)
+def hgt_relation(kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor, src_pos: List[int],
+                 widx: List[int], heads: int) -> Tensor:
+    """The packed ``kv [S, 2 * F]`` of hgt_conv.py:118-154: for edge type ``e`` of the call, whose
+    source node type is ``kqvs[src_pos[e]] [N, 3 * F]`` (key | query | value), the rows ``k[:, h] @
+    k_weight[h * T + widx[e]]`` and ``v[:, h] @ v_weight[h * T + widx[e]]``, stacked in call order.
+    The weights are ``[heads * T, D, D]``."""
+    D = k_weight.size(-1)
+    if not _native.hgt_supported(heads, D):
+        raise NotImplementedError(
+            f'hgt_relation serves H * D <= 512, H <= 64 and D <= 128 (got {heads} x {D})')
+    kqvs = [_native._f32_rows(x, 'kqv') for x in kqvs]
+    ks, vs = _hgt_blocks(kqvs, src_pos, heads * D)
+    return _native.hgt_relation_forward(ks, vs, widx, k_weight.contiguous(),
+                                        v_weight.contiguous(), heads, D)
+
+
+@hgt_relation.register_fake
+def _(kqvs, k_weight, v_weight, src_pos, widx, heads):
+    S = sum(kqvs[p].shape[0] for p in src_pos)
+    return k_weight.new_empty(S, 2 * heads * k_weight.shape[-1])
+
+
+@custom_op('pyg_amd::hgt_relation_backward', mutates_args=(), device_types=_DEV)
+def hgt_relation_backward(grad: Tensor, kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor,
+                          src_pos: List[int], widx: List[int],
+                          heads: int) -> Tuple[List[Tensor], Tensor, Tensor]:
+    D = k_weight.size(-1)
+    F = heads * D
+    kqvs = [_native._f32_rows(x, 'kqv') for x in kqvs]
+    ks, vs = _hgt_blocks(kqvs, src_pos, F)
+    bufs = [torch.empty_like(x, memory_format=torch.contiguous_format) for x in kqvs]
+    for b in bufs:
+        b[:, F:2 * F].zero_()
+    g_wk, g_wv = _native.hgt_relation_backward(
+        ks, vs, widx, src_pos, k_weight.contiguous(), v_weight.contiguous(), heads, D,
+        grad.contiguous(), [b[:, :F] for b in bufs], [b[:, 2 * F:] for b in bufs])
+    return bufs, g_wk, g_wv
+
+
+@hgt_relation_backward.register_fake
+def _(grad, kqvs, k_weight, v_weight, src_pos, widx, heads):
+    return ([torch.empty_like(x, memory_format=torch.contiguous_format) for x in kqvs],
+            torch.empty_like(k_weight), torch.empty_like(v_weight))
+
+
+def _hgt_setup(ctx, inputs, output):
+    kqvs, k_weight, v_weight, src_pos, widx, heads = inputs
+    ctx.static = (list(src_pos), list(widx), heads)
+    ctx.n = len(kqvs)
+    ctx.save_for_backward(k_weight, v_weight, *kqvs)
+
+
+def _hgt_bwd(ctx, grad):
+    k_weight, v_weight, *kqvs = ctx.saved_tensors
+    g_x, g_wk, g_wv = hgt_relation_backward(grad.contiguous(), list(kqvs), k_weight, v_weight,
+                                            *ctx.static)
+    return list(g_x), g_wk, g_wv, None, None, None
+
+
+register_autograd('pyg_amd::hgt_relation', _hgt_bwd, setup_context=_hgt_setup)
+
 OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_backward',
        'segment_csr', 'segment_csr_backward', 'softmax_csr', 'softmax_csr_backward', 'spmm',
        'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
-       'transformer_attend_backward')
+       'transformer_attend_backward', 'hgt_relation', 'hgt_relation_backward')
