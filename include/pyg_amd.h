@@ -667,6 +667,55 @@ PYGAMD_API int pygamd_transformer_backward_src(const void* rowptr_t, const void*
                                                float* grad_value, int64_t ld, void* workspace,
                                                size_t workspace_bytes, void* stream);
 
+/* ---- a16c: TransformerConv's edge features (edge_dim) inside the one-pass kernels ---------------
+ * nn/conv/transformer_conv.py:263-283 with lin_edge: key_j + e and value_j + e, e = W_e a_k.  The
+ * edge term is linear, so the kernels never see it at width H*C.  With a_k [De] the raw features of
+ * slot k and, per destination, bias[i,h,:] = scale * (W_e^h)^T query[i,h,:]  ([>= n_rows, H*De]):
+ *   s[k,h]   = scale * <query[i,h,:], key[j,h,:]> + <bias[i,h,:], a_k>
+ *   alpha    = softmax over the row, as pygamd_transformer_forward
+ *   out[i,h] = sum_k alpha[k,h] * value[j,h,:]          (WITHOUT the edge term)
+ *   z[i,h]   = sum_k alpha[k,h] * a_k                   ([n_rows, H*De])
+ * and the caller adds W_e^h z[i,h] to out (transformer_conv.py:263-283: `out = value_j + edge_attr`).
+ * edge_attr is [nnz, De] contiguous fp32 in SLOT order.  out and z are both given, or both NULL
+ * ("score mode": alpha only).  Every other argument, the hub plan, the chunk-order merges and the
+ * reproducibility are those of pygamd_transformer_forward; the workspace is that of
+ * pygamd_transformer_edge_workspace_bytes.  pygamd_transformer_edge_supported (transformer_conv.py:
+ * 263-283): the head layout of pygamd_transformer_supported and De <= 4 * lph_max, lph_max the
+ * largest power of two with H * lph_max <= 64 (De <= 32 at H <= 8, De <= 4 at H = 64); otherwise
+ * status 2.  Status 1 / 2 / 3 before any device work; n_rows == 0 returns 0.
+ *
+ * edge_backward_dst (transformer_conv.py:263-283 differentiated), with g = grad_out, gz = grad_z:
+ *   d alpha[k,h] = <g[i,h,:], value[j,h,:]> + <gz[i,h,:], a_k>,  D = <g, out> + <gz, z> per (i, h)
+ *   grad_s = alpha * (d alpha - D);  grad_query[i] = scale * sum_k grad_s * key[j]
+ *   grad_bias[i,h,:] = sum_k grad_s[k,h] * a_k
+ *   grad_edge_attr[k,:] = sum_h (grad_s[k,h] * bias[i,h,:] + alpha[k,h] * gz[i,h,:])   (slot order;
+ *     NULL: not wanted, the work is skipped)
+ *   score mode passes grad_alpha [nnz, H] and NULL for grad_out / out / grad_z / z: d alpha is
+ *   given, D = sum_row alpha * d alpha, and grad_edge_attr holds the grad_s * bias part only.
+ * The by-source pass is pygamd_transformer_backward_src, unchanged.                              */
+PYGAMD_API int pygamd_transformer_edge_supported(int64_t H, int64_t C, int64_t De);
+PYGAMD_API int pygamd_transformer_edge_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C,
+                                                       int64_t De, size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_transformer_edge_forward(const void* rowptr, const void* col, int idx_dtype,
+                                               const float* query, const float* key,
+                                               const float* value, int64_t ld,
+                                               const float* edge_attr, const float* bias,
+                                               int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
+                                               int64_t De, float scale, const void* hub_rows,
+                                               const void* hub_chunk_ptr, int64_t n_hub,
+                                               int64_t n_chunks, int64_t hub_threshold,
+                                               int64_t hub_chunk, float* alpha, float* out,
+                                               float* z, void* workspace, size_t workspace_bytes,
+                                               void* stream);
+PYGAMD_API int pygamd_transformer_edge_backward_dst(
+    const void* rowptr, const void* col, int idx_dtype, const float* key, const float* value,
+    int64_t ld, const float* edge_attr, const float* bias, const float* alpha,
+    const float* grad_out, const float* out, const float* grad_z, const float* z,
+    const float* grad_alpha, int64_t n_rows, int64_t n_src, int64_t H, int64_t C, int64_t De,
+    float scale, const void* hub_rows, const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
+    int64_t hub_threshold, int64_t hub_chunk, float* grad_s, float* grad_query, float* grad_bias,
+    float* grad_edge_attr, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

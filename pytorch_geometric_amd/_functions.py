@@ -754,6 +754,132 @@ class TransformerScoreFunction(Function):
                 None)
 
 
+def _edge_slots(edge_attr: Tensor, graph: EdgeIndex) -> Tensor:
+    """``edge_attr [E, De]`` (the caller's edge order) in by-destination slot order, contiguous:
+    the one permuted copy the edge kernels stream through."""
+    if edge_attr.dim() != 2 or edge_attr.size(0) != graph.by_dst().idx.numel():
+        raise ValueError(f"'edge_attr' must be [E, De] with one row per edge (got "
+                         f"{tuple(edge_attr.shape)})")
+    return edge_attr.index_select(0, graph.by_dst().perm.long())
+
+
+def _edge_unslot(grad_slots: Optional[Tensor], graph: EdgeIndex) -> Optional[Tensor]:
+    """a gradient in slot order back in the caller's edge order (``perm`` is a permutation: every
+    row is written once)"""
+    if grad_slots is None:
+        return None
+    grad = torch.empty_like(grad_slots)
+    grad[graph.by_dst().perm.long()] = grad_slots
+    return grad
+
+
+def _transformer_edge_backward(ctx, H, C, query, key, value, ea, bias, alpha, grad_out2, out2,
+                               grad_z2, z2, grad_alpha, want_ga, packed=False):
+    """The two launches both edge nodes share: by destination (d s, grad_query, grad_bias and,
+    if wanted, the slot-ordered grad_edge_attr), then by source, the launch of the nodes without
+    edge features: d s and alpha are all it reads of the edge term."""
+    graph = ctx.graph
+    fwd = graph.by_dst()
+    grad_s, g_q, g_b, g_a = _native.transformer_edge_backward_dst(
+        fwd.ptr, fwd.idx, query, key, value, ea, bias, alpha, H, C, ctx.scale,
+        grad_out=grad_out2, out=out2, grad_z=grad_z2, z=z2, grad_alpha=grad_alpha,
+        want_grad_edge_attr=want_ga, hub=fwd.hub)
+    g_k = g_v = None
+    if ctx.needs_input_grad[1] or (grad_alpha is None and ctx.needs_input_grad[2]):
+        bwd = graph.by_src()
+        g_k, g_v = _native.transformer_backward_src(
+            bwd.ptr, bwd.idx, graph.src_slot_to_dst_slot(), query, alpha, grad_s, H, C,
+            ctx.scale, grad_out=grad_out2, n_dst=fwd.n_rows, hub=bwd.hub, packed=packed)
+    return g_q, g_k, g_v, g_b, _edge_unslot(g_a, graph)
+
+
+class TransformerEdgeAttendFunction(Function):
+    """:class:`TransformerAttendFunction` with edge features inside the kernel.  The edge term
+    ``W_e a_k`` of key and value (transformer_conv.py:263-283) is linear, so it enters as a
+    per-destination score bias and leaves as a per-destination sum of the RAW features:
+
+        s[k,h] = scale <q_i, key_j> + <bias[i,h], a_k>       bias = scale * W_e^T q  [>= n_dst, H, De]
+        out_nodes[i,h] = sum_k alpha value_j                 (without the edge term)
+        z[i,h]         = sum_k alpha[k,h] a_k                [n_dst, H, De]
+
+    and the caller adds ``W_e z`` to ``out_nodes``.  ``edge_attr [E, De]`` comes in the CALLER's
+    edge order and is permuted into slot order once per call; its gradient is produced in slot
+    order and scattered back, and skipped altogether when it is not required.  ``value=None``:
+    ``key`` is the packed ``[N_src, 2, H, C]`` projection.  Saved: the inputs, ``alpha [E, H]``,
+    ``out_nodes``, ``z`` and the slot-ordered ``edge_attr`` — nothing of size ``E x H*C``."""
+
+    @staticmethod
+    def forward(ctx, query: Tensor, key: Tensor, value: Optional[Tensor], edge_attr: Tensor,
+                bias: Tensor, graph: EdgeIndex, scale: float, n_dst: int):
+        _, H, C = query.shape
+        W = H * C
+        _transformer_check(query, key, graph, n_dst)
+        fwd = graph.by_dst()
+        q2 = query.reshape(-1, W)
+        packed = value is None
+        if packed:
+            kv = key.reshape(-1, 2 * W)
+            k2, v2 = kv[:, :W], kv[:, W:]
+        else:
+            k2, v2 = key.reshape(-1, W), value.reshape(-1, W)
+        ea = _edge_slots(edge_attr, graph)
+        De = ea.size(1)
+        b2 = bias.reshape(-1, H * De)
+        alpha, out, z = _native.transformer_edge_forward(fwd.ptr, fwd.idx, q2, k2, v2, ea, b2, H,
+                                                         C, scale, hub=fwd.hub)
+        ctx.save_for_backward(q2, k2, v2, ea, b2, alpha, out, z)
+        ctx.graph, ctx.scale, ctx.dims, ctx.packed = graph, scale, (H, C, De), packed
+        ctx.key_shape, ctx.bias_shape = key.shape, bias.shape
+        return out.view(fwd.n_rows, H, C), z.view(fwd.n_rows, H, De)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor, grad_z: Tensor):
+        q2, k2, v2, ea, b2, alpha, out, z = ctx.saved_tensors
+        H, C, De = ctx.dims
+        g_q, g_k, g_v, g_b, g_a = _transformer_edge_backward(
+            ctx, H, C, q2, k2, v2, ea, b2, alpha, _rows(grad_out), out, _rows(grad_z), z, None,
+            ctx.needs_input_grad[3], packed=ctx.packed)
+        g_k = None if g_k is None else g_k.view(ctx.key_shape)
+        g_v = None if g_v is None or ctx.packed else g_v.view(ctx.key_shape)
+        return (g_q.view(-1, H, C), g_k, g_v, g_a, g_b.view(ctx.bias_shape), None, None, None)
+
+
+class TransformerEdgeScoreFunction(Function):
+    """The attention coefficients of :class:`TransformerEdgeAttendFunction` alone (``alpha [E, H]``
+    in by-destination slot order), as :class:`TransformerScoreFunction` is to its node.  The
+    backward takes ``grad_alpha`` and additionally returns ``grad_bias`` and the ``d s * bias``
+    part of ``grad_edge_attr`` — all of it: ``z`` is formed by the caller from ``alpha``."""
+
+    @staticmethod
+    def forward(ctx, query: Tensor, key: Tensor, edge_attr: Tensor, bias: Tensor,
+                graph: EdgeIndex, scale: float, n_dst: int):
+        _, H, C = query.shape
+        _transformer_check(query, key, graph, n_dst)
+        fwd = graph.by_dst()
+        q2, k2 = query.reshape(-1, H * C), key.reshape(-1, H * C)
+        ea = _edge_slots(edge_attr, graph)
+        De = ea.size(1)
+        b2 = bias.reshape(-1, H * De)
+        alpha, _, _ = _native.transformer_edge_forward(fwd.ptr, fwd.idx, q2, k2, None, ea, b2, H,
+                                                       C, scale, hub=fwd.hub, aggregate=False)
+        ctx.save_for_backward(q2, k2, ea, b2, alpha)
+        ctx.graph, ctx.scale, ctx.dims = graph, scale, (H, C, De)
+        ctx.key_shape, ctx.bias_shape = key.shape, bias.shape
+        return alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_alpha: Tensor):
+        q2, k2, ea, b2, alpha = ctx.saved_tensors
+        H, C, De = ctx.dims
+        g_q, g_k, _, g_b, g_a = _transformer_edge_backward(
+            ctx, H, C, q2, k2, None, ea, b2, alpha, None, None, None, None,
+            grad_alpha.contiguous(), ctx.needs_input_grad[2])
+        return (g_q.view(-1, H, C), None if g_k is None else g_k.view(ctx.key_shape), g_a,
+                g_b.view(ctx.bias_shape), None, None, None)
+
+
 class HgtRelationPlan:
     """Static description of one relation-transform node: ``heads``; ``src_pos[e]``: the position
     (among the tensor inputs) of the source node type of edge type ``e`` of the call; ``widx[e]``:

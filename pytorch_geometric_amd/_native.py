@@ -1365,6 +1365,115 @@ def transformer_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, 
     return result
 
 
+# ---- ... with edge features inside the kernels (the edge variant of csrc/transformer.hip) --------
+def transformer_edge_supported(H: int, C: int, De: int) -> bool:
+    """The edge variant serves this layout: that of :func:`transformer_supported` and ``De <= 4 *
+    lph``, ``lph`` the largest power of two with ``H * lph <= 64``."""
+    return bool(_lib.load().pygamd_transformer_edge_supported(int(H), int(C), int(De)))
+
+
+def _transformer_edge_workspace(lib, n_chunks: int, H: int, C: int, De: int, device):
+    nbytes = ctypes.c_size_t(0)
+    check(lib.pygamd_transformer_edge_workspace_bytes(n_chunks, H, C, De, ctypes.byref(nbytes)))
+    if nbytes.value == 0:
+        return None, 0
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
+
+
+def transformer_edge_forward(rowptr: Tensor, col: Tensor, query: Tensor, key: Tensor,
+                             value: Optional[Tensor], edge_attr: Tensor, bias: Tensor, H: int,
+                             C: int, scale: float, *, hub=None, aggregate: bool = True):
+    """``(alpha [nnz, H] in slot order, out [n_rows, H * C] | None, z [n_rows, H * De] | None)``
+    of one attention step whose score carries ``<bias[i, h], edge_attr[k]>``; ``edge_attr [nnz,
+    De]`` in SLOT order, ``bias [>= n_rows, H * De]``.  ``out`` is the weighted sum of ``value``
+    alone, ``z`` that of the raw edge features; ``aggregate=False`` is the score mode (alpha
+    only)."""
+    _require_device(rowptr, col, query, key, value, edge_attr, bias)
+    lib = _lib.load()
+    W = H * C
+    query = _gatv2_rows(query, 'query', W)
+    key, value, ld = _key_value(key, value if aggregate else None, W)
+    n_rows = rowptr.numel() - 1
+    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 \
+            or edge_attr.size(0) != col.numel():
+        raise ValueError(f"'edge_attr' must be a float32 [{col.numel()}, De] tensor (got "
+                         f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
+    De = edge_attr.size(1)
+    edge_attr, bias = edge_attr.contiguous(), _gatv2_rows(bias, 'bias', H * De)
+    if query.size(0) < n_rows or bias.size(0) < n_rows:
+        raise ValueError(f"'query' and 'bias' need at least {n_rows} rows")
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    alpha = torch.empty(col.numel(), H, dtype=torch.float32, device=query.device)
+    out = torch.empty(n_rows, W, dtype=torch.float32, device=query.device) if aggregate else None
+    z = torch.empty(n_rows, H * De, dtype=torch.float32, device=query.device) \
+        if aggregate else None
+    if col.numel() == 0:  # no edges: every row is empty
+        return alpha, (out.zero_() if aggregate else None), (z.zero_() if aggregate else None)
+    ws, ws_bytes = (_transformer_edge_workspace(lib, n_chunks, H, C, De, query.device)
+                    if n_chunks > 0 else (None, 0))
+    with _timed({'kind': 'transformer', 'op': 'edge_forward' if aggregate else 'edge_score',
+                 'n_rows': n_rows, 'E': col.numel(), 'H': H, 'C': C, 'De': De, 'ld': ld,
+                 'n_hub': n_hub, 'n_chunks': n_chunks}, query):
+        check(lib.pygamd_transformer_edge_forward(
+            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(query), _p(key), _p(value), ld,
+            _p(edge_attr), _p(bias), n_rows, key.size(0), H, C, De, float(scale), _p(h_rows),
+            _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(alpha), _p(out), _p(z),
+            _p(ws), ws_bytes, _stream(query)), 'transformer_edge_forward')
+    return alpha, out, z
+
+
+def transformer_edge_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, key: Tensor,
+                                  value: Optional[Tensor], edge_attr: Tensor, bias: Tensor,
+                                  alpha: Tensor, H: int, C: int, scale: float, *,
+                                  grad_out: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                                  grad_z: Optional[Tensor] = None, z: Optional[Tensor] = None,
+                                  grad_alpha: Optional[Tensor] = None,
+                                  want_grad_edge_attr: bool = True, hub=None):
+    """``(grad_s [nnz, H], grad_query [rows of query, H * C], grad_bias [rows of bias, H * De],
+    grad_edge_attr [nnz, De] in slot order | None)``; ``grad_alpha`` given = score mode
+    (``value`` not read, ``grad_edge_attr`` holds its ``grad_s * bias`` part), otherwise
+    ``grad_out``, ``out``, ``grad_z`` and ``z``."""
+    _require_device(rowptr, col, query, key, value, edge_attr, bias, alpha, grad_out, out, grad_z,
+                    z, grad_alpha)
+    lib = _lib.load()
+    W = H * C
+    De = edge_attr.size(1)
+    Z = H * De
+    score = grad_alpha is not None
+    key, value, ld = _key_value(key, None if score else value, W)
+    alpha, edge_attr = alpha.contiguous(), edge_attr.contiguous()
+    bias = _gatv2_rows(bias, 'bias', Z)
+    n_rows = rowptr.numel() - 1
+    if score:
+        grad_alpha = grad_alpha.contiguous()
+    else:
+        grad_out, out = _gatv2_rows(grad_out, 'grad_out', W), _gatv2_rows(out, 'out', W)
+        grad_z, z = _gatv2_rows(grad_z, 'grad_z', Z), _gatv2_rows(z, 'z', Z)
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    grad_s = torch.empty_like(alpha)
+    # (destinations may be a prefix of the rows of query and bias: the rest takes no gradient)
+    dev = key.device
+    alloc = torch.empty if query.size(0) == n_rows else torch.zeros
+    grad_query = alloc(query.size(0), W, dtype=torch.float32, device=dev)
+    alloc = torch.empty if bias.size(0) == n_rows else torch.zeros
+    grad_bias = alloc(bias.size(0), Z, dtype=torch.float32, device=dev)
+    grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
+    if col.numel() == 0:
+        return grad_s, grad_query.zero_(), grad_bias.zero_(), grad_edge
+    ws, ws_bytes = _transformer_edge_workspace(lib, n_chunks, H, C, De, dev)
+    with _timed({'kind': 'transformer', 'op': 'edge_backward_dst', 'n_rows': n_rows,
+                 'E': col.numel(), 'H': H, 'C': C, 'De': De, 'ld': ld, 'n_hub': n_hub,
+                 'n_chunks': n_chunks, 'score': score,
+                 'grad_edge_attr': want_grad_edge_attr}, key):
+        check(lib.pygamd_transformer_edge_backward_dst(
+            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(key), _p(value), ld, _p(edge_attr),
+            _p(bias), _p(alpha), _p(grad_out), _p(out), _p(grad_z), _p(z), _p(grad_alpha), n_rows,
+            key.size(0), H, C, De, float(scale), _p(h_rows), _p(h_cptr), n_hub, n_chunks,
+            HUB_THRESHOLD, HUB_CHUNK, _p(grad_s), _p(grad_query), _p(grad_bias), _p(grad_edge),
+            _p(ws), ws_bytes, _stream(key)), 'transformer_edge_backward_dst')
+    return grad_s, grad_query, grad_bias, grad_edge
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

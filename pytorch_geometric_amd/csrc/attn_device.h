@@ -88,6 +88,38 @@ __device__ __forceinline__ float group_sum(float v, int lph) {
   return v;
 }
 
+// ---- edge features (transformer.hip's edge variant) -----------------------------------------------
+// The lane that serves head h, sub-lane `sub` additionally owns the edge features d = sub + lph * r,
+// r < kEdgeRegs, of that head: a fixed register capacity with predication, so De <= kEdgeRegs * lph.
+constexpr int kEdgeRegs = 4;
+
+// `row` holds De floats: a slot's raw features (every head reads the same line) or one head's block
+// of a per-destination [H, De] row
+__device__ __forceinline__ void load_edge(const float* __restrict__ row, const Lay& L, int De,
+                                          float (&v)[kEdgeRegs]) {
+#pragma unroll
+  for (int r = 0; r < kEdgeRegs; ++r) {
+    const int d = L.sub + L.lph * r;
+    v[r] = (L.head_ok && d < De) ? row[d] : 0.f;
+  }
+}
+
+__device__ __forceinline__ void store_edge(float* __restrict__ row, const Lay& L, int De,
+                                           const float (&v)[kEdgeRegs]) {
+#pragma unroll
+  for (int r = 0; r < kEdgeRegs; ++r) {
+    const int d = L.sub + L.lph * r;
+    if (L.head_ok && d < De) row[d] = v[r];
+  }
+}
+
+// sum over the heads, i.e. across the lane groups of a wave: lanes with equal `sub` are combined by
+// an xor-butterfly over the lane offsets lph, 2 * lph, ...; every lane gets the total
+__device__ __forceinline__ float head_sum(float v, int lph) {
+  for (int o = lph; o < kWave; o <<= 1) v += __shfl_xor(v, o, kWave);
+  return v;
+}
+
 // Work items of a launch: the chunks of the hub rows first (they are the long ones), then every
 // row; a hub row's own item does nothing.
 template <typename IdxT>
@@ -225,6 +257,22 @@ inline bool choose_shape(int64_t H, int64_t C, bool aligned, Shape* s) {
   while (epl < n) epl *= 2;
   if (epl > 16) return false;
   *s = Shape{lph, epl, false};
+  return true;
+}
+
+// The lane shape of the edge variant: the shape of (H, C) with lph widened (idle lanes for the row)
+// until kEdgeRegs * lph >= De.  Whether one exists does not depend on `aligned`.
+inline bool choose_shape_edge(int64_t H, int64_t C, int64_t De, bool aligned, Shape* s) {
+  if (De < 1 || !choose_shape(H, C, aligned, s)) return false;
+  int lph = s->lph;
+  while (kEdgeRegs * lph < De && lph * 2 * H <= kWave) lph *= 2;
+  if (kEdgeRegs * lph < De) return false;
+  if (lph != s->lph) {
+    const int n = static_cast<int>(((s->vec ? C / 4 : C) + lph - 1) / lph);
+    int epl = 1;
+    while (epl < n) epl *= 2;
+    *s = Shape{lph, s->vec ? 4 * n : epl, s->vec};
+  }
   return true;
 }
 

@@ -1,4 +1,5 @@
 import math
+import os
 from typing import Optional, Tuple, Union
 
 import torch
@@ -6,12 +7,16 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from ... import _native
-from ..._functions import (SpmmFunction, TransformerAttendFunction, TransformerScoreFunction,
-                           linear)
+from ..._functions import (SegmentFunction, SpmmFunction, TransformerAttendFunction,
+                           TransformerEdgeAttendFunction, TransformerEdgeScoreFunction,
+                           TransformerScoreFunction, linear)
 from ...edge_index import EdgeIndex, as_edge_index
 from ...utils import softmax
 from ..dense.linear import Linear
 from .message_passing import MessagePassing
+
+# PYGAMD_FUSE_EDGE=1: layers with ``edge_dim`` start with ``fuse_edge = True`` (read at import)
+FUSE_EDGE = os.environ.get('PYGAMD_FUSE_EDGE', '0') not in ('', '0')
 
 
 class TransformerConv(MessagePassing):
@@ -37,13 +42,32 @@ class TransformerConv(MessagePassing):
       in the reference the coefficients are returned as they are BEFORE dropout
       (transformer_conv.py:274-276), whenever the argument is a ``bool``, in the caller's edge
       order;
-    * generic gather -> ``message`` -> scatter for ``edge_dim``, ``fuse = False``,
-      ``target_to_source`` and head layouts the kernels do not serve (``H * C > 512``, ``H > 64``);
-      host tensors compute in plain torch.
+    * fused with edge features (``edge_dim`` layers with ``fuse_edge = True`` and a 2-D float
+      device ``edge_attr [E, edge_dim]``, under the same other conditions, and
+      ``_native.transformer_edge_supported(H, C, edge_dim)``): the edge term is linear, so it
+      never exists per edge at width ``H * C``.  With ``W_e^h`` head ``h``'s block of
+      ``lin_edge.weight``, ``b = scale * (W_e^h)^T q_i^h`` is a per-destination score bias and
+      ``z_i^h = sum_k alpha a_k`` a per-destination sum of the RAW features; the same one-pass
+      kernel reads ``De`` floats per slot and accumulates ``z`` beside the output
+      (``TransformerEdgeAttendFunction``), and ``out = out_nodes + W_e z``.  The two products with
+      ``W_e`` are plain einsums over nodes, so autograd carries their gradients.  In score mode
+      the edge score node gives ``alpha``; after dropout the weighted SpMM aggregates ``value``
+      and ``z`` is formed in tensor code (``w[k,h] * a_k`` as ``[E, H * edge_dim]``, reduced by
+      the segment sum over the destination rows);
+    * generic gather -> ``message`` -> scatter for ``edge_dim`` layers with ``fuse_edge = False``,
+      ``fuse = False``, ``target_to_source`` and layouts the kernels do not serve (``H * C >
+      512``, ``H > 64``, ``edge_dim`` beyond the edge registers); host tensors compute in plain
+      torch.
 
-    Not offered: edge features inside the fused kernels, ``SparseTensor`` inputs, routing of the
-    reference's own class through ``backend.install()``, a ``BasicGNN`` model of this layer.  The
-    epilogue (head mean, ``lin_skip``, the ``lin_beta`` gate) is plain tensor code.
+    ``fuse_edge`` is a per-layer attribute initialised from the environment switch
+    ``PYGAMD_FUSE_EDGE``, which is read at import and defaults to ``0``: with default settings
+    ``edge_dim`` layers take the generic route, which ``test_routing_to_the_generic_route`` in
+    ``tests/test_gpu_transformer.py`` pins.  Flipping the default is a later change of its own,
+    once the timings of ``profiles/transformer_conv_edge.md`` exist.
+
+    Not offered: ``SparseTensor`` inputs, routing of the reference's own class through
+    ``backend.install()``, a ``BasicGNN`` model of this layer.  The epilogue (head mean,
+    ``lin_skip``, the ``lin_beta`` gate) is plain tensor code.
     """
 
     def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int,
@@ -56,6 +80,7 @@ class TransformerConv(MessagePassing):
         self.beta = beta and root_weight
         self.root_weight, self.concat, self.dropout = root_weight, concat, dropout
         self.edge_dim = edge_dim
+        self.fuse_edge = FUSE_EDGE
         self._alpha = None
         in_src, in_dst = (in_channels, in_channels) if isinstance(in_channels, int) \
             else in_channels
@@ -98,9 +123,15 @@ class TransformerConv(MessagePassing):
         # (transformer_conv.py:254)
         want_alpha = isinstance(return_attention_weights, bool)
         native = (x_src.is_cuda and x_src.dtype in (torch.float32, torch.float16, torch.bfloat16)
-                  and self.fuse and edge_attr is None and self.lin_edge is None
-                  and self.flow == 'source_to_target'
+                  and self.fuse and self.flow == 'source_to_target'
                   and _native.transformer_supported(H, C))
+        edge = False
+        if native and (edge_attr is not None or self.lin_edge is not None):
+            edge = native = (
+                self.fuse_edge and self.lin_edge is not None and isinstance(edge_attr, Tensor)
+                and edge_attr.is_cuda and edge_attr.dim() == 2
+                and edge_attr.size(1) == self.edge_dim and edge_attr.is_floating_point()
+                and _native.transformer_edge_supported(H, C, self.edge_dim))
         scale = 1.0 / math.sqrt(C)
         alpha = None
         low = None
@@ -124,7 +155,11 @@ class TransformerConv(MessagePassing):
             n_src, n_dst = x_src.size(0), x_dst.size(0)
             graph = as_edge_index(edge_index, n_src, n_dst)
             query = query.view(-1, H, C)
-            if score_mode:
+            if edge:
+                out, alpha = self._attend_edge(query, key if score_mode else kv,
+                                               value if score_mode else None, edge_attr, graph,
+                                               scale, n_dst, score_mode, want_alpha)
+            elif score_mode:
                 # the coefficients are observable (dropout acts on them, or the caller asked):
                 # score kernel -> dropout -> multi-head weighted SpMM over value
                 alpha_slot = TransformerScoreFunction.apply(query, key.view(-1, H, C), graph,
@@ -172,6 +207,38 @@ class TransformerConv(MessagePassing):
         assert alpha is not None
         coo = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
         return out, (coo, alpha)
+
+    def _attend_edge(self, query: Tensor, key: Tensor, value: Optional[Tensor], edge_attr: Tensor,
+                     graph, scale: float, n_dst: int, score_mode: bool, want_alpha: bool):
+        """The fused route with edge features: ``(out [n_dst, H, C], alpha | None)``.  ``value``
+        None: ``key`` is the packed key | value projection."""
+        H, C, De = self.heads, self.out_channels, self.edge_dim
+        W = H * C
+        ea = edge_attr.float()
+        w_e = self.lin_edge.weight.float().view(H, C, De)
+        bias = scale * torch.einsum('nhc,hcd->nhd', query, w_e)
+        alpha = None
+        if not score_mode:
+            out, z = TransformerEdgeAttendFunction.apply(query, key.view(-1, 2, H, C), None, ea,
+                                                         bias, graph, scale, n_dst)
+        else:
+            n_src = key.size(0)
+            alpha_slot = TransformerEdgeScoreFunction.apply(query, key.view(-1, H, C), ea, bias,
+                                                            graph, scale, n_dst)
+            weights = F.dropout(alpha_slot, p=self.dropout, training=self.training)
+            out = SpmmFunction.apply(value.reshape(n_src, W), weights, graph, 'sum', 'slot')
+            out = out.view(-1, H, C)
+            # z = sum over the row of w[k,h] * a_k, in tensor code: [E, H * De], then the segment
+            # sum over the destination rows
+            fwd = graph.by_dst()
+            ea_slot = ea.index_select(0, fwd.perm.long())
+            z = SegmentFunction.apply(
+                (weights.unsqueeze(-1) * ea_slot.unsqueeze(1)).reshape(-1, H * De), fwd.ptr,
+                'sum').view(-1, H, De)
+            if want_alpha:
+                alpha = torch.empty_like(alpha_slot)
+                alpha[fwd.perm.long()] = alpha_slot
+        return out + torch.einsum('nhd,hcd->nhc', z, w_e), alpha
 
     def _project_key_value(self, x_src: Tensor) -> Tensor:
         """``[lin_key(x) | lin_value(x)]`` as one ``[N_src, 2 * H * C]`` product."""

@@ -31,6 +31,9 @@ Operators (all index tensors int32 / int64, features float32):
                             float negative_slope) -> (Tensor out, Tensor alpha)``
 ``transformer_attend``      ``(Tensor query, Tensor key, Tensor value, Tensor rowptr, Tensor col,
                             float scale) -> (Tensor out, Tensor alpha)``
+``transformer_edge_attend`` ``(Tensor query, Tensor key, Tensor value, Tensor edge_attr,
+                            Tensor bias, Tensor rowptr, Tensor col, float scale)
+                            -> (Tensor out, Tensor z, Tensor alpha)``
 ``hgt_relation``            ``(Tensor[] kqvs, Tensor k_weight, Tensor v_weight, int[] src_pos,
                             int[] widx, int heads) -> Tensor``
 ==========================  ===========================================================
@@ -504,6 +507,86 @@ register_autograd('pyg_amd::transformer_attend', _transformer_bwd,
                   setup_context=_transformer_setup)
 
 
+# ---- ... with edge features inside the kernel (rows = destinations, edge_attr follows `col`) -----
+@custom_op('pyg_amd::transformer_edge_attend', mutates_args=(), device_types=_DEV)
+def transformer_edge_attend(query: Tensor, key: Tensor, value: Tensor, edge_attr: Tensor,
+                            bias: Tensor, rowptr: Tensor, col: Tensor,
+                            scale: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(out [n_dst, H, C], z [n_dst, H, De], alpha [nnz, H])`` of one dot-product attention step
+    with edge features (transformer_conv.py:263-283): ``s = scale <q, key_j> + <bias[i, h], a_k>``
+    for ``edge_attr [nnz, De]`` in the order of ``col`` and ``bias [>= n_dst, H, De]``; ``out`` is
+    the weighted sum of ``value`` alone and ``z`` that of the raw edge features."""
+    _, H, C = query.shape
+    De = edge_attr.size(1)
+    if not _native.transformer_edge_supported(H, C, De):
+        raise NotImplementedError(
+            f'transformer_edge_attend serves H * C <= 512, H <= 64 and De <= 4 * (64 // H rounded '
+            f'down to a power of two) (got {H} x {C}, De = {De})')
+    alpha, out, z = _native.transformer_edge_forward(
+        rowptr, col, _rows(query), _rows(key), _rows(value), edge_attr, _rows(bias), H, C, scale,
+        hub=_native.hub_plan(rowptr))
+    n = rowptr.numel() - 1
+    return out.reshape(n, H, C), z.reshape(n, H, De), alpha
+
+
+@transformer_edge_attend.register_fake
+def _(query, key, value, edge_attr, bias, rowptr, col, scale):
+    n = rowptr.numel() - 1
+    return (query.new_empty(n, *query.shape[1:]),
+            query.new_empty(n, query.shape[1], edge_attr.shape[1]),
+            query.new_empty(col.numel(), query.shape[1]))
+
+
+@custom_op('pyg_amd::transformer_edge_attend_backward', mutates_args=(), device_types=_DEV)
+def transformer_edge_attend_backward(grad: Tensor, grad_z: Tensor, query: Tensor, key: Tensor,
+                                     value: Tensor, edge_attr: Tensor, bias: Tensor,
+                                     alpha: Tensor, out: Tensor, z: Tensor, rowptr: Tensor,
+                                     col: Tensor, scale: float
+                                     ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    _, H, C = query.shape
+    n_dst = rowptr.numel() - 1
+    q2, g2 = _rows(query), _rows(grad).contiguous()
+    grad_s, g_q, g_b, g_a = _native.transformer_edge_backward_dst(
+        rowptr, col, q2, _rows(key), _rows(value), edge_attr, _rows(bias), alpha, H, C, scale,
+        grad_out=g2, out=_rows(out), grad_z=_rows(grad_z).contiguous(), z=_rows(z),
+        hub=_native.hub_plan(rowptr))
+    # the by-source form of the same slots, as transformer_attend_backward builds it
+    dst = _native.ptr2index(rowptr, col.numel())
+    src_sorted, perm = _native.index_sort(col, max_value=max(key.size(0) - 1, 0))
+    rowptr_t = _native.index2ptr(src_sorted, key.size(0))
+    col_t = _native.permute_index(dst, perm)
+    g_k, g_v = _native.transformer_backward_src(
+        rowptr_t, col_t, _native.cast_index(perm, col.dtype), q2, alpha, grad_s, H, C, scale,
+        grad_out=g2, n_dst=n_dst, hub=_native.hub_plan(rowptr_t))
+    return (g_q.reshape(query.shape), g_k.reshape(key.shape), g_v.reshape(value.shape), g_a,
+            g_b.reshape(bias.shape))
+
+
+@transformer_edge_attend_backward.register_fake
+def _(grad, grad_z, query, key, value, edge_attr, bias, alpha, out, z, rowptr, col, scale):
+    return (torch.empty_like(query), torch.empty_like(key), torch.empty_like(value),
+            torch.empty_like(edge_attr), torch.empty_like(bias))
+
+
+def _transformer_edge_setup(ctx, inputs, output):
+    query, key, value, edge_attr, bias, rowptr, col, scale = inputs
+    ctx.scale = scale
+    ctx.save_for_backward(query, key, value, edge_attr, bias, output[2], output[0], output[1],
+                          rowptr, col)
+
+
+def _transformer_edge_bwd(ctx, grad, grad_z, _grad_alpha):
+    query, key, value, edge_attr, bias, alpha, out, z, rowptr, col = ctx.saved_tensors
+    g_q, g_k, g_v, g_a, g_b = transformer_edge_attend_backward(
+        grad.contiguous(), grad_z.contiguous(), query, key, value, edge_attr, bias, alpha, out, z,
+        rowptr, col, ctx.scale)
+    return g_q, g_k, g_v, g_a, g_b, None, None, None
+
+
+register_autograd('pyg_amd::transformer_edge_attend', _transformer_edge_bwd,
+                  setup_context=_transformer_edge_setup)
+
+
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
 def _hgt_blocks(kqvs, src_pos, F):
     return ([kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos])
@@ -574,4 +657,5 @@ register_autograd('pyg_amd::hgt_relation', _hgt_bwd, setup_context=_hgt_setup)
 OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_backward',
        'segment_csr', 'segment_csr_backward', 'softmax_csr', 'softmax_csr_backward', 'spmm',
        'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
-       'transformer_attend_backward', 'hgt_relation', 'hgt_relation_backward')
+       'transformer_attend_backward', 'transformer_edge_attend',
+       'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward')

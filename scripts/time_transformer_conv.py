@@ -11,7 +11,12 @@ Warm-up, HIP events around every repetition, medians.  Also times the fused forw
 and sets its algorithmic bytes ``E (8 HC + b + 4 H) + N (3 * 4 HC)`` (b = index bytes) against the
 row-gather rate measured in the same run (``gather_rows`` of ``[N, 2 HC]`` rows by the same
 sources), and the per-step ``cat`` of the key and value weights.
-``python scripts/time_transformer_conv.py [--reps 15] [--out profiles/transformer_conv.md]``."""
+``python scripts/time_transformer_conv.py [--reps 15] [--out profiles/transformer_conv.md]``.
+
+``--edge-dim D`` times the same layer with ``edge_dim = D`` and ``edge_attr [E, D]`` instead: with
+``fuse_edge = True`` (edge features inside the one-pass kernels), in score mode, and with
+``fuse_edge = False`` — the generic gather / ``message`` / scatter route such a layer takes by
+default, code unchanged: the yardstick.  All in one process, same graphs."""
 import argparse
 import math
 import os
@@ -54,7 +59,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=15)
     ap.add_argument('--out', default=None, help='also write the table to this file')
+    ap.add_argument('--edge-dim', type=int, default=None,
+                    help='time the layer with edge_dim = D: fuse_edge on, score mode, off')
     args = ap.parse_args()
+    if args.edge_dim is not None:
+        return main_edge(args)
     dev = torch.device('cuda:0')
     n, e, K, H, C = 169_343, 1_166_243, 256, 8, 32
     W = H * C
@@ -107,11 +116,50 @@ def main():
                      f'{alg / (t * 1e-3) / rate:.2f} of the row-gather rate measured here '
                      f'({rate / 1e12:.2f} TB/s, gather_rows of [N, {2 * W}] in {tg:.3f} ms) |  |  |')
         lines.append(f'|  | cat of the key and value weights, per step | {tc:.3f} | — |')
+    emit(lines, args.out)
+
+
+def main_edge(args):
+    dev = torch.device('cuda:0')
+    n, e, K, H, C, D = 169_343, 1_166_243, 256, 8, 32, args.edge_dim
+    x = torch.randn(n, K, generator=torch.Generator().manual_seed(1)).to(dev)
+    ea = torch.randn(e, D, generator=torch.Generator().manual_seed(2)).to(dev).requires_grad_(True)
+    lines = [f'TransformerConv({K}, {C}, heads={H}, edge_dim={D}) at N = {n}, E = {e}, '
+             f'{torch.cuda.get_device_name(0)}, medians of {args.reps}; edge_attr requires grad',
+             '', '| graph | route | forward ms | forward + backward ms |', '|---|---|---|---|']
+    for gname, ei in graphs(n, e, dev).items():
+        torch.manual_seed(0)
+        conv = TransformerConv(K, C, heads=H, edge_dim=D).to(dev).eval()
+        routes = {'fuse_edge = True': (True, {}),
+                  'fuse_edge = True, score mode': (True, {'return_attention_weights': True}),
+                  'fuse_edge = False': (False, {})}
+        for rname, (fuse_edge, kw) in routes.items():
+            conv.fuse_edge = fuse_edge
+
+            def out():
+                res = conv(x, ei, ea, **kw)
+                return res[0] if isinstance(res, tuple) else res
+
+            def fwd():
+                with torch.no_grad():
+                    out()
+
+            def both():
+                conv.zero_grad()
+                ea.grad = None
+                out().sum().backward()
+
+            f, fb = median_ms(fwd, args.reps), median_ms(both, args.reps)
+            lines.append(f'| {gname} | {rname} | {f:.3f} | {fb:.3f} |')
+    emit(lines, args.out)
+
+
+def emit(lines, path):
     text = '\n'.join(lines)
     print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'w') as f:
             f.write(text + '\n')
 
 
