@@ -88,6 +88,24 @@ __device__ __forceinline__ float group_sum(float v, int lph) {
   return v;
 }
 
+// ---- the online softmax -------------------------------------------------------------------------
+// A running (maximum m, sum l, weighted sum acc) takes in a score p, or a chunk's (m_c, l_c, acc_c),
+// as   mn = fmaxf(m, p);  l = l * exp(m - mn) + exp(p - mn)   (acc like l).
+// Both factors are exp(-inf - -inf) = NaN while nothing finite has been seen: a masked score
+// (p = -inf) ahead of the first finite one, or a fully masked first chunk, would poison the row.
+// A side that is -inf has weight exactly 0 — which is also what expf gives whenever the other side
+// is finite, so for finite scores nothing changes, bit for bit.  NaN and +inf scores still reach l
+// through the other factor and poison their own (row, head), as the reference's softmax does.
+__device__ __forceinline__ float softmax_weight(float x, float mn) {
+  return x == -INFINITY ? 0.f : expf(x - mn);
+}
+
+// 1 / (l + 1e-16) of a finished row; NaN for a row with slots whose every score is -inf (m is still
+// -inf: l and acc are 0), the reference's exp(-inf - -inf).  A row without slots keeps out = 0.
+__device__ __forceinline__ float softmax_inv(float m, float l, bool has_slots) {
+  return (has_slots && m == -INFINITY) ? NAN : 1.f / (l + 1e-16f);
+}
+
 // ---- edge features (transformer.hip's edge variant) -----------------------------------------------
 // The lane that serves head h, sub-lane `sub` additionally owns the edge features d = sub + lph * r,
 // r < kEdgeRegs, of that head: a fixed register capacity with predication, so De <= kEdgeRegs * lph.
@@ -184,11 +202,11 @@ __device__ __forceinline__ void merge_softmax_row(const IdxT* __restrict__ rowpt
     for (int64_t c = c0; c < c1; ++c) {
       const float mc = part[c * S + W + lane], lc = part[c * S + W + H + lane];
       const float mn = fmaxf(m, mc);
-      l = l * expf(m - mn) + lc * expf(mc - mn);
+      l = l * softmax_weight(m, mn) + lc * softmax_weight(mc, mn);
       m = mn;
     }
     sm[lane] = m;
-    sinv[lane] = 1.f / (l + 1e-16f);
+    sinv[lane] = softmax_inv(m, l, true);  // (a hub row has slots)
   }
   __syncthreads();
   if (out) {

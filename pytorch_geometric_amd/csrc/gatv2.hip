@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(kBlock)
         if (L.head_ok && L.sub == static_cast<int>((k + u - s.row_start) & (lph - 1)))
           alpha[(k + u) * H + L.h] = p;
         const float mn = fmaxf(m, p);
-        const float sc = expf(m - mn), pe = expf(p - mn);
+        const float sc = softmax_weight(m, mn), pe = softmax_weight(p, mn);
         l = fmaf(l, sc, pe);
         if constexpr (AGG) {
 #pragma unroll
@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(kBlock)
     }
     return;
   }
-  const float inv = 1.f / (l + 1e-16f);
+  const float inv = softmax_inv(m, l, s.k1 > s.k0);
   if constexpr (AGG) {
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] *= inv;

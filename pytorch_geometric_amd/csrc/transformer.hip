@@ -107,7 +107,7 @@ __device__ __forceinline__ void
         if (L.head_ok && L.sub == static_cast<int>((k + u - s.row_start) & (lph - 1)))
           alpha[(k + u) * H + L.h] = p;
         const float mn = fmaxf(m, p);
-        const float sc = expf(m - mn), pe = expf(p - mn);
+        const float sc = softmax_weight(m, mn), pe = softmax_weight(p, mn);
         l = fmaf(l, sc, pe);
         if constexpr (AGG) {
 #pragma unroll
@@ -132,7 +132,7 @@ __device__ __forceinline__ void
     }
     return;
   }
-  const float inv = 1.f / (l + 1e-16f);
+  const float inv = softmax_inv(m, l, s.k1 > s.k0);
   if constexpr (AGG) {
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] *= inv;
@@ -241,11 +241,11 @@ __global__ void __launch_bounds__(kWave)
     for (int64_t c = c0; c < c1; ++c) {
       const float mc = part[c * S + W + Z + lane], lc = part[c * S + W + Z + H + lane];
       const float mn = fmaxf(m, mc);
-      l = l * expf(m - mn) + lc * expf(mc - mn);
+      l = l * softmax_weight(m, mn) + lc * softmax_weight(mc, mn);
       m = mn;
     }
     sm[lane] = m;
-    sinv[lane] = 1.f / (l + 1e-16f);
+    sinv[lane] = softmax_inv(m, l, true);  // (a hub row has slots)
   }
   __syncthreads();
   const int64_t t = static_cast<int64_t>(blockIdx.y) * kWave + lane;
