@@ -716,6 +716,59 @@ PYGAMD_API int pygamd_transformer_edge_backward_dst(
     int64_t hub_threshold, int64_t hub_chunk, float* grad_s, float* grad_query, float* grad_bias,
     float* grad_edge_attr, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- GINEConv's edge message (gin_conv.py:19-207) -------------------------------------------------
+ * One destination row i of a CSR by destination (rows = destinations, col = the source of every
+ * slot), slot k with source j = col[k] and original edge edge_id[k] (NULL: slot order):
+ *   out[i,:] = (x_root ? (1 + *eps) * x_root[i,:] : 0) + sum_k max(x_src[j,:] + e_k, 0)
+ *   wide   (De == 0): e_k = edge_attr[edge_id[k], :],   edge_attr [E, F]
+ *   linear (De >= 1): e_k = W a_k + b, a_k = edge_attr[edge_id[k], :De], weight W [F, De] in
+ *                     torch.nn.Linear's layout, bias b [F] or NULL
+ * (gin_conv.py:185-207: message = (x_j + lin(edge_attr)).relu(), out = nn((1 + eps) * x_r + sum)).
+ * ONE launch, one 64-lane wave per row, lanes over the F columns; edge features are read in place
+ * through edge_id and, in linear mode, every lane keeps its columns' rows of W in registers: no
+ * [E, F] value is formed.  eps is a DEVICE pointer (it may be a parameter; no host read); x_root
+ * and eps may be NULL (the bipartite (x_src, None) case).  x_src and x_root have row strides
+ * ld_src / ld_root (floats), everything else is contiguous; fp32 data, int32 / int64 indices.
+ * Rows beyond hub_threshold slots go through the hub plan's chunks and their partial sums are
+ * added in chunk order.  No float atomics: bitwise reproducible.
+ *
+ * backward: ONE launch over the CSR by source (rowptr_t over sources, col_t = the destination of
+ * every out-slot, edge_id_t = that form's own slot -> original edge map, NULL: slot order), every
+ * edge visited once, m = (x_src[j,:] + e_k > 0) (strict, as relu's backward), g = grad_out[i,:]:
+ *   grad_x_src[j,:] = sum_t m * g                      (zeros for rows without out-slots)
+ *   wide:   grad_edge_attr[k,:] = m * g                (original edge order; NULL: not wanted)
+ *   linear: grad_edge_attr[k,d] = sum_f m_f g_f W[f,d] (NULL: not wanted, the wave sums are skipped)
+ *           grad_weight[f,d] = sum_k m_f g_f a_k[d],  grad_bias[f] = sum_k m_f g_f (NULL iff bias is)
+ * grad_weight / grad_bias accumulate in registers, leave one partial per workgroup in the
+ * workspace and are reduced in workgroup order by a second small kernel inside the call; the grid
+ * is a function of (n_src, n_chunks) only.  The self term (grad_x_root, grad_eps) is the caller's.
+ *
+ * pygamd_gine_supported(F, De) (De = 0: wide mode): F <= 512 and, in linear mode, De <= 32 and
+ * F * De <= 4096; otherwise status 2.  The workspace (pygamd_gine_workspace_bytes) holds the
+ * chunks' partial rows and, in linear mode, the backward's per-workgroup partials.  Status 1 / 2 /
+ * 3 before any device work; n_rows == 0 returns 0.                                               */
+PYGAMD_API int pygamd_gine_supported(int64_t F, int64_t De);
+PYGAMD_API int pygamd_gine_workspace_bytes(int64_t n_chunks, int64_t F, int64_t De,
+                                           size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_gine_forward(const void* rowptr, const void* col, const void* edge_id,
+                                   int idx_dtype, const float* x_src, int64_t ld_src,
+                                   const float* x_root, int64_t ld_root, const float* eps,
+                                   const float* edge_attr, const float* weight, const float* bias,
+                                   int64_t n_rows, int64_t n_src, int64_t F, int64_t De,
+                                   const void* hub_rows, const void* hub_chunk_ptr, int64_t n_hub,
+                                   int64_t n_chunks, int64_t hub_threshold, int64_t hub_chunk,
+                                   float* out, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+PYGAMD_API int pygamd_gine_backward(const void* rowptr_t, const void* col_t, const void* edge_id_t,
+                                    int idx_dtype, const float* x_src, int64_t ld_src,
+                                    const float* edge_attr, const float* weight, const float* bias,
+                                    const float* grad_out, int64_t n_src, int64_t n_dst, int64_t F,
+                                    int64_t De, const void* hub_rows, const void* hub_chunk_ptr,
+                                    int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
+                                    int64_t hub_chunk, float* grad_x_src, float* grad_edge_attr,
+                                    float* grad_weight, float* grad_bias, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

@@ -880,6 +880,67 @@ class TransformerEdgeScoreFunction(Function):
                 g_b.view(ctx.bias_shape), None, None, None)
 
 
+class GineAggregateFunction(Function):
+    """The aggregation of GINEConv (gin_conv.py:185-207) in ONE pass over the by-destination slots:
+
+        out[i] = (1 + eps) * x_root[i] + sum_{k of i} relu(x_src[j_k] + e_k)
+
+    with ``e_k = edge_attr[k]`` (``weight=None``, the wide mode) or ``weight @ edge_attr[k] + bias``
+    (the linear mode, ``edge_dim``), rebuilt per slot in registers (csrc/gine.hip).  ``edge_attr``
+    stays in the caller's edge order and is read through the handle's permutations.  ``x_root``
+    (destinations, a prefix of its rows), ``eps`` (one element), ``weight`` and ``bias`` may be
+    ``None``.  The backward is one pass over the by-source slots, which rebuilds the ReLU mask:
+    only the inputs are saved, nothing per edge; ``grad_edge_attr`` is not computed when it is
+    not required."""
+
+    @staticmethod
+    def forward(ctx, x_src: Tensor, x_root: Optional[Tensor], eps: Optional[Tensor],
+                edge_attr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                graph: EdgeIndex, n_dst: int):
+        if x_src.size(0) != graph.num_src_nodes:
+            raise ValueError(f"'x_src' has {x_src.size(0)} rows but the graph has "
+                             f"{graph.num_src_nodes} source nodes")
+        if n_dst != graph.num_dst_nodes or (x_root is not None and x_root.size(0) < n_dst):
+            raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = "
+                             f"{n_dst}, 'x_root' has "
+                             f"{None if x_root is None else x_root.size(0)} rows")
+        fwd = graph.by_dst()
+        eps1 = None if eps is None or x_root is None else eps.reshape(1)
+        out = _native.gine_forward(fwd.ptr, fwd.idx, fwd.perm, x_src, x_root, eps1, edge_attr,
+                                   weight, bias, hub=fwd.hub)
+        ctx.save_for_backward(x_src, x_root, eps, edge_attr, weight, bias)
+        ctx.graph, ctx.n_dst = graph, n_dst
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        x_src, x_root, eps, edge_attr, weight, bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grad_out = grad_out.contiguous()
+        g_x = g_a = g_w = g_b = g_root = g_eps = None
+        if need[0] or need[3] or need[4] or need[5]:
+            bwd = ctx.graph.by_src()
+            g_x, g_a, g_w, g_b = _native.gine_backward(
+                bwd.ptr, bwd.idx, bwd.perm, x_src, edge_attr, weight, bias, grad_out,
+                want_grad_edge_attr=need[3], hub=bwd.hub)
+        if x_root is not None:
+            n = ctx.n_dst
+            if need[1]:
+                scale = 1.0 if eps is None else 1.0 + eps.reshape(())
+                g_root = grad_out * scale
+                if x_root.size(0) != n:  # destinations are a prefix: the rest takes no gradient
+                    full = grad_out.new_zeros(x_root.shape)
+                    full[:n] = g_root
+                    g_root = full
+            if eps is not None and need[2]:
+                # row sums in fp32, their total in fp64: one rounding of the whole inner product
+                g_eps = ((grad_out * x_root[:n]).sum(dim=1).double().sum().to(eps.dtype)
+                         .reshape(eps.shape))
+        return (g_x if need[0] else None, g_root, g_eps, g_a if need[3] else None,
+                g_w if need[4] else None, g_b if need[5] else None, None, None)
+
+
 class HgtRelationPlan:
     """Static description of one relation-transform node: ``heads``; ``src_pos[e]``: the position
     (among the tensor inputs) of the source node type of edge type ``e`` of the call; ``widx[e]``:

@@ -260,6 +260,14 @@ SIGNATURES = {
                                                      c_int64, c_int64, c_int64, c_float, _P, _P,
                                                      c_int64, c_int64, c_int64, c_int64, _P, _P,
                                                      _P, _P, _P, c_size_t, _P]),
+    'pygamd_gine_supported': (c_int, [c_int64, c_int64]),
+    'pygamd_gine_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    'pygamd_gine_forward': (c_int, [_P, _P, _P, c_int, _P, c_int64, _P, c_int64, _P, _P, _P, _P,
+                                    c_int64, c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64,
+                                    c_int64, c_int64, _P, _P, c_size_t, _P]),
+    'pygamd_gine_backward': (c_int, [_P, _P, _P, c_int, _P, c_int64, _P, _P, _P, _P, c_int64,
+                                     c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64,
+                                     c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 # include/pyg_amd_lab.h: schedules measured and not adopted + timing probes (NOT the boundary;

@@ -1474,6 +1474,142 @@ def transformer_edge_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, ke
     return grad_s, grad_query, grad_bias, grad_edge
 
 
+# ---- GINEConv's edge message (csrc/gine.hip) -------------------------------------------------------
+def gine_supported(F: int, De: int = 0) -> bool:
+    """The kernel pair serves ``F <= 512`` and, in linear mode (``De >= 1``), ``De <= 32`` and
+    ``F * De <= 4096``; ``De = 0`` is the wide mode."""
+    return bool(_lib.load().pygamd_gine_supported(int(F), int(De)))
+
+
+def _gine_workspace(lib, n_chunks: int, F: int, De: int, device):
+    nbytes = ctypes.c_size_t(0)
+    check(lib.pygamd_gine_workspace_bytes(n_chunks, F, De, ctypes.byref(nbytes)))
+    if nbytes.value == 0:
+        return None, 0
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
+
+
+def _gine_edge(edge_attr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], F: int,
+               E: int):
+    """(edge_attr, weight, bias, De) checked: wide mode without ``weight`` (``De = 0``)."""
+    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != E:
+        raise ValueError(f"'edge_attr' must be a float32 [{E}, width] tensor (got "
+                         f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
+    if weight is None:
+        if bias is not None:
+            raise ValueError("'bias' needs 'weight'")
+        if edge_attr.size(1) != F:
+            raise ValueError(f"without 'weight' the edge features need width {F} (got "
+                             f"{edge_attr.size(1)})")
+        return edge_attr.contiguous(), None, None, 0
+    De = edge_attr.size(1)
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (F, De) or De < 1:
+        raise ValueError(f"'weight' must be float32 [{F}, {De}] (got {weight.dtype} "
+                         f"{tuple(weight.shape)})")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (F,)):
+        raise ValueError(f"'bias' must be float32 [{F}]")
+    return (edge_attr.contiguous(), weight.contiguous(),
+            None if bias is None else bias.contiguous(), De)
+
+
+def _gine_no_edges(rowptr: Tensor, x: Tensor):
+    """(col, edge_id, edge_attr) of a graph without edges: valid one-element buffers, never read"""
+    return rowptr.new_zeros(1), None, x.new_zeros(1, 1)
+
+
+def gine_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], x_src: Tensor,
+                 x_root: Optional[Tensor], eps: Optional[Tensor], edge_attr: Tensor,
+                 weight: Optional[Tensor] = None, bias: Optional[Tensor] = None, *, hub=None):
+    """``out [n_rows, F] = (1 + eps) * x_root[:n_rows] + sum_k relu(x_src[col[k]] + e_k)`` on a
+    by-destination handle; ``e_k = edge_attr[edge_id[k]]`` (wide) or ``weight @ edge_attr[edge_id[k]]
+    + bias`` (linear).  ``edge_attr`` stays in the caller's edge order (``edge_id=None``: it is in
+    slot order); ``eps`` is a one-element device tensor; ``x_root`` and ``eps`` may be None.
+    ``x_src`` and ``x_root`` may be column blocks of wider tensors (their row stride is passed)."""
+    _require_device(rowptr, col, edge_id, x_src, x_root, eps, edge_attr, weight, bias)
+    lib = _lib.load()
+    if x_src.dim() != 2:
+        raise ValueError("'x_src' must be two-dimensional")
+    F = x_src.size(1)
+    x_src = _strided_rows(x_src, 'x_src', F)
+    n_rows = rowptr.numel() - 1
+    if x_root is not None:
+        x_root = _strided_rows(x_root, 'x_root', F)
+        if x_root.size(0) < n_rows:
+            raise ValueError(f"'x_root' needs at least {n_rows} rows")
+        if eps is not None and (eps.dtype != torch.float32 or eps.numel() != 1):
+            raise ValueError("'eps' must be one float32")
+    else:
+        eps = None
+    edge_attr, weight, bias, De = _gine_edge(edge_attr, weight, bias, F, col.numel())
+    if edge_id is not None:
+        if edge_id.dtype != rowptr.dtype or edge_id.numel() != col.numel():
+            raise ValueError("'edge_id' must have the index dtype and one entry per slot")
+        edge_id = edge_id.contiguous()
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    out = torch.empty(n_rows, F, dtype=torch.float32, device=x_src.device)
+    if n_rows == 0:
+        return out
+    if col.numel() == 0:  # no edges: every row is its self term; the launch reads no slot
+        col, edge_id, edge_attr = _gine_no_edges(rowptr, x_src)
+    ws, ws_bytes = (_gine_workspace(lib, n_chunks, F, De, x_src.device) if n_chunks > 0
+                    else (None, 0))
+    with _timed({'kind': 'gine', 'op': 'forward', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'De': De, 'ld': _ld(x_src), 'n_hub': n_hub, 'n_chunks': n_chunks,
+                 'grad_edge_attr': False}, x_src):
+        check(lib.pygamd_gine_forward(
+            _p(rowptr), _p(col), _p(edge_id), _idx_dtype(rowptr), _p(x_src), _ld(x_src),
+            _p(x_root), 0 if x_root is None else _ld(x_root), _p(eps), _p(edge_attr), _p(weight),
+            _p(bias), n_rows, x_src.size(0), F, De, _p(h_rows), _p(h_cptr), n_hub, n_chunks,
+            HUB_THRESHOLD, HUB_CHUNK, _p(out), _p(ws), ws_bytes, _stream(x_src)), 'gine_forward')
+    return out
+
+
+def gine_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], x_src: Tensor,
+                  edge_attr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                  grad_out: Tensor, *, want_grad_edge_attr: bool = True, hub=None):
+    """``(grad_x_src [n_src, F], grad_edge_attr | None, grad_weight | None, grad_bias | None)`` on
+    the by-SOURCE handle (``col_t`` = the destination of every out-slot, ``edge_id_t`` = that
+    form's slot -> edge map); ``grad_edge_attr`` comes in the caller's edge order."""
+    _require_device(rowptr_t, col_t, edge_id_t, x_src, edge_attr, weight, bias, grad_out)
+    lib = _lib.load()
+    F = x_src.size(1)
+    x_src = _strided_rows(x_src, 'x_src', F)
+    grad_out = _gatv2_rows(grad_out, 'grad_out', F)
+    n_src = rowptr_t.numel() - 1
+    if x_src.size(0) != n_src:
+        raise ValueError(f"'x_src' needs {n_src} rows")
+    edge_attr, weight, bias, De = _gine_edge(edge_attr, weight, bias, F, col_t.numel())
+    if edge_id_t is not None:
+        if edge_id_t.dtype != rowptr_t.dtype or edge_id_t.numel() != col_t.numel():
+            raise ValueError("'edge_id_t' must have the index dtype and one entry per slot")
+        edge_id_t = edge_id_t.contiguous()
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    dev = x_src.device
+    grad_x = torch.empty(n_src, F, dtype=torch.float32, device=dev)
+    grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
+    grad_w = torch.empty_like(weight) if weight is not None else None
+    grad_b = torch.empty_like(bias) if bias is not None else None
+    if n_src == 0:
+        for t in (grad_w, grad_b):
+            if t is not None:
+                t.zero_()
+        return grad_x, grad_edge, grad_w, grad_b
+    if col_t.numel() == 0:
+        col_t, edge_id_t, edge_attr = _gine_no_edges(rowptr_t, x_src)
+    ws, ws_bytes = (_gine_workspace(lib, n_chunks, F, De, dev) if n_chunks > 0 or De > 0
+                    else (None, 0))
+    with _timed({'kind': 'gine', 'op': 'backward', 'n_rows': n_src, 'E': col_t.numel(), 'F': F,
+                 'De': De, 'ld': _ld(x_src), 'n_hub': n_hub, 'n_chunks': n_chunks,
+                 'grad_edge_attr': bool(want_grad_edge_attr)}, x_src):
+        check(lib.pygamd_gine_backward(
+            _p(rowptr_t), _p(col_t), _p(edge_id_t), _idx_dtype(rowptr_t), _p(x_src), _ld(x_src),
+            _p(edge_attr), _p(weight), _p(bias), _p(grad_out), n_src, grad_out.size(0), F, De,
+            _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_x),
+            _p(grad_edge), _p(grad_w), _p(grad_b), _p(ws), ws_bytes, _stream(x_src)),
+            'gine_backward')
+    return grad_x, grad_edge, grad_w, grad_b
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

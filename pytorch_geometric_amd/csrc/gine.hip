@@ -1,0 +1,510 @@
+// gine.hip — the edge message of GINEConv (nn/conv/gin_conv.py:19-207 of the reference) as a pair
+// of row-gather kernels on a sorted handle.  For destination i and the source j of slot k:
+//     e_k      = edge_attr[k, :]                      (wide,   edge_dim = None)
+//              = W a_k + b,  a_k = edge_attr[k, :De]   (linear, edge_dim = De; W [F, De], b [F])
+//     out[i,:] = (1 + eps) * x_root[i,:] + sum_k max(x_src[j,:] + e_k, 0)
+// The ReLU sits between the edge term and the sum, so nothing factors out per destination (as the
+// linear edge term of transformer.hip does): the kernels rebuild e_k per slot, in registers.  In
+// linear mode every lane keeps the rows of W of ITS columns in registers for the whole launch and
+// a slot's raw features reach the lanes by v_readlane: no [E, F] value exists anywhere.
+//
+// Lanes run over the F columns (attn_device.h's layout with one head): scalar registers for any
+// F, float4 units where F % 4 == 0 and every row is 16-byte aligned.  Work items, the hub plan's
+// chunks and the in-order merge of a long row's partials: attn_device.h.  The forward walks the
+// CSR by destination, the backward the CSR by source and visits every edge exactly once.  No float
+// atomics anywhere: every result is bitwise reproducible.
+#include <math.h>
+
+#include "attn_device.h"
+#include "common.h"
+
+namespace pygamd {
+namespace {
+
+using namespace attn;
+
+constexpr int kGineMaxWidth = 512;
+constexpr int kGineMaxDe = 32;
+constexpr int kGineMaxWeight = 4096;  // F * De: 64 registers per lane at 64 busy lanes
+// Linear mode: a wave loads its 64 * EPL * De weights once and then walks items at the stride of
+// the grid, so the grid is capped; the caps depend on nothing but these constants, and the number
+// of workgroups of a launch on the problem's sizes only (grad_W is reduced in workgroup order).
+constexpr unsigned kGineFwdBlocks = 1024;
+constexpr unsigned kGineBwdBlocks = 512;
+
+// the column of register e of this lane
+template <bool VEC>
+__device__ __forceinline__ int lane_col(const Lay& L, int e) {
+  if constexpr (VEC) return (L.sub + L.lph * (e >> 2)) * 4 + (e & 3);
+  return L.sub + L.lph * e;
+}
+
+// rows of W [F, De] (torch.nn.Linear's layout) and entries of b [F] (or NULL) of the lane's columns
+template <int EPL, bool VEC, int DE>
+__device__ __forceinline__ void load_weight(const float* __restrict__ weight,
+                                            const float* __restrict__ bias, const Lay& L, int De,
+                                            float (&w)[EPL][DE], float (&b)[EPL]) {
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    const int c = lane_col<VEC>(L, e);
+    const bool ok = L.head_ok && c < L.C;
+#pragma unroll
+    for (int d = 0; d < DE; ++d)
+      w[e][d] = (ok && d < De) ? weight[static_cast<int64_t>(c) * De + d] : 0.f;
+    b[e] = (ok && bias) ? bias[c] : 0.f;
+  }
+}
+
+// e = b + W a for this lane's columns; lane d of the wave holds a[d] in `av` (0 beyond De)
+template <int EPL, int DE>
+__device__ __forceinline__ void edge_term(const float (&w)[EPL][DE], const float (&b)[EPL],
+                                          float av, float (&ev)[EPL]) {
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) ev[e] = b[e];
+#pragma unroll
+  for (int d = 0; d < DE; ++d) {
+    const float a = bcast_uniform(av, d);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) ev[e] = fmaf(w[e][d], a, ev[e]);
+  }
+}
+
+template <int EPL, int DE>
+struct GineSlots {  // slots in flight per wave
+  static constexpr int n = (EPL >= 8 || DE > 0) ? 2 : 4;
+};
+
+struct GineEdge {
+  const float* edge_attr;  // [E, F] (wide) or [E, De] (linear), original edge order
+  const float* weight;     // [F, De] or NULL (wide)
+  const float* bias;       // [F] or NULL
+  int De;
+};
+
+// ---- forward ---------------------------------------------------------------------------------
+template <typename IdxT, int EPL, bool VEC, int DE>
+__global__ void __launch_bounds__(kBlock)
+    gine_fwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col,
+                    const IdxT* __restrict__ edge_id, const float* __restrict__ x_src, int64_t ld,
+                    const float* __restrict__ x_root, int64_t ld_root,
+                    const float* __restrict__ eps, GineEdge ed, int F, int lph,
+                    float* __restrict__ out, float* __restrict__ part) {
+  constexpr int U = GineSlots<EPL, DE>::n;
+  constexpr bool LIN = DE > 0;
+  const Lay L = make_lay(1, F, lph);
+  float w[LIN ? EPL : 1][LIN ? DE : 1], b[EPL];
+  if constexpr (LIN) load_weight<EPL, VEC, DE>(ed.weight, ed.bias, L, ed.De, w, b);
+  const int lane = lane_id();
+  const int64_t n_items = it.n_chunks + it.n_rows;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
+       item += stride) {
+    Span s;
+    if (!decode(it, item, s)) continue;
+    float acc[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+    for (int64_t k = s.k0; k < s.k1; k += U) {
+      float xx[U][EPL], ee[U][EPL], av[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (k + u < s.k1) {
+          const int64_t j = static_cast<int64_t>(col[k + u]);
+          const int64_t id = edge_id ? static_cast<int64_t>(edge_id[k + u]) : k + u;
+          load_row<EPL, VEC>(x_src + j * ld, L, xx[u]);
+          if constexpr (LIN) {
+            av[u] = lane < ed.De ? ed.edge_attr[id * ed.De + lane] : 0.f;
+          } else {
+            load_row<EPL, VEC>(ed.edge_attr + id * F, L, ee[u]);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (k + u < s.k1) {
+          if constexpr (LIN) edge_term<EPL, DE>(w, b, av[u], ee[u]);
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) acc[e] += fmaxf(xx[u][e] + ee[u][e], 0.f);
+        }
+      }
+    }
+    if (s.chunk_id >= 0) {  // partial sum of one chunk of a long row
+      store_row<EPL, VEC>(part + s.chunk_id * F, L, acc);
+      continue;
+    }
+    if (x_root) {
+      const float sc = 1.f + (eps ? *eps : 0.f);
+      float r[EPL];
+      load_row<EPL, VEC>(x_root + s.row * ld_root, L, r);
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) acc[e] = fmaf(sc, r[e], acc[e]);
+    }
+    store_row<EPL, VEC>(out + s.row * F, L, acc);
+  }
+}
+
+// hub rows, forward: the chunks' partial sums in chunk order, then the self term
+template <typename IdxT>
+__global__ void __launch_bounds__(kWave)
+    gine_fwd_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
+                          int64_t F, const float* __restrict__ part,
+                          const float* __restrict__ x_root, int64_t ld_root,
+                          const float* __restrict__ eps, float* __restrict__ out) {
+  const int64_t hr = blockIdx.x;
+  merge_sum_row(hub_rows, hub_cptr, hr, F, part, F, out, F);
+  if (!x_root) return;
+  const int64_t row = static_cast<int64_t>(hub_rows[hr]);
+  const float sc = 1.f + (eps ? *eps : 0.f);
+  // (thread t wrote the columns t, t + 64, ... above: it reads its own stores)
+  for (int64_t t = threadIdx.x; t < F; t += kWave)
+    out[row * F + t] = fmaf(sc, x_root[row * ld_root + t], out[row * F + t]);
+}
+
+// ---- backward, by source ------------------------------------------------------------------------
+// A wave owns source row j (or a chunk of its out-slots) and keeps x_src[j] in registers; slot t
+// has destination i = col_t[t] and edge k = edge_id_t[t].  m = (x_src[j] + e_k > 0), g =
+// grad_out[i]:  grad_x_src[j] = sum_t m g;  wide: grad_edge_attr[k] = m g;  linear:
+// grad_edge_attr[k,d] = sum_f m g W[f,d] (a wave sum per d), and grad_W[f,d] = sum_k m g a_k[d],
+// grad_b[f] = sum_k m g accumulate in the lane's registers over all items of the wave; the waves
+// of a workgroup add theirs in wave order in LDS and the workgroup leaves ONE partial.
+template <typename IdxT, int EPL, bool VEC, int DE>
+__global__ void __launch_bounds__(kBlock)
+    gine_bwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col_t,
+                    const IdxT* __restrict__ edge_id_t, const float* __restrict__ x_src,
+                    int64_t ld, GineEdge ed, const float* __restrict__ grad_out, int F, int lph,
+                    float* __restrict__ grad_x, float* __restrict__ grad_edge,
+                    float* __restrict__ part, float* __restrict__ wpart) {
+  constexpr int U = GineSlots<EPL, DE>::n;
+  constexpr bool LIN = DE > 0;
+  const Lay L = make_lay(1, F, lph);
+  float w[LIN ? EPL : 1][LIN ? DE : 1], b[EPL];
+  float gw[LIN ? EPL : 1][LIN ? DE : 1], gb[EPL];
+  if constexpr (LIN) {
+    load_weight<EPL, VEC, DE>(ed.weight, ed.bias, L, ed.De, w, b);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+      gb[e] = 0.f;
+#pragma unroll
+      for (int d = 0; d < DE; ++d) gw[e][d] = 0.f;
+    }
+  }
+  const int lane = lane_id();
+  const int64_t n_items = it.n_chunks + it.n_rows;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
+       item += stride) {
+    Span s;
+    if (!decode(it, item, s)) continue;
+    float x[EPL], gx[EPL];
+    load_row<EPL, VEC>(x_src + s.row * ld, L, x);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) gx[e] = 0.f;
+    for (int64_t t = s.k0; t < s.k1; t += U) {
+      float gg[U][EPL], ee[U][EPL], av[U];
+      int64_t id[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (t + u < s.k1) {
+          const int64_t i = static_cast<int64_t>(col_t[t + u]);
+          id[u] = edge_id_t ? static_cast<int64_t>(edge_id_t[t + u]) : t + u;
+          load_row<EPL, VEC>(grad_out + i * F, L, gg[u]);
+          if constexpr (LIN) {
+            av[u] = lane < ed.De ? ed.edge_attr[id[u] * ed.De + lane] : 0.f;
+          } else {
+            load_row<EPL, VEC>(ed.edge_attr + id[u] * F, L, ee[u]);
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (t + u < s.k1) {
+          if constexpr (LIN) edge_term<EPL, DE>(w, b, av[u], ee[u]);
+          float mg[EPL];
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) {
+            mg[e] = (x[e] + ee[u][e] > 0.f) ? gg[u][e] : 0.f;
+            gx[e] += mg[e];
+          }
+          if constexpr (LIN) {
+#pragma unroll
+            for (int d = 0; d < DE; ++d) {
+              const float a = bcast_uniform(av[u], d);
+#pragma unroll
+              for (int e = 0; e < EPL; ++e) gw[e][d] = fmaf(mg[e], a, gw[e][d]);
+            }
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) gb[e] += mg[e];
+            if (grad_edge) {  // (wave-uniform)
+              float mine = 0.f;
+#pragma unroll
+              for (int d = 0; d < DE; ++d) {
+                if (d < ed.De) {
+                  float p = 0.f;
+#pragma unroll
+                  for (int e = 0; e < EPL; ++e) p = fmaf(mg[e], w[e][d], p);
+                  p = group_sum(p, kWave);
+                  if (lane == d) mine = p;
+                }
+              }
+              if (lane < ed.De) grad_edge[id[u] * ed.De + lane] = mine;
+            }
+          } else {
+            if (grad_edge) store_row<EPL, VEC>(grad_edge + id[u] * F, L, mg);
+          }
+        }
+      }
+    }
+    if (s.chunk_id >= 0) {
+      store_row<EPL, VEC>(part + s.chunk_id * F, L, gx);
+    } else {
+      store_row<EPL, VEC>(grad_x + s.row * F, L, gx);
+    }
+  }
+  if constexpr (LIN) {
+    __shared__ float red[kGineMaxWeight + kGineMaxWidth];
+    const int De = ed.De;
+    const int FD = F * De;
+    for (int wv = 0; wv < kWavesPerBlock; ++wv) {
+      if (wave_in_block() == wv) {
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          const int c = lane_col<VEC>(L, e);
+          if (L.head_ok && c < F) {
+#pragma unroll
+            for (int d = 0; d < DE; ++d) {
+              if (d < De) red[c * De + d] = (wv == 0 ? 0.f : red[c * De + d]) + gw[e][d];
+            }
+            red[FD + c] = (wv == 0 ? 0.f : red[FD + c]) + gb[e];
+          }
+        }
+      }
+      __syncthreads();
+    }
+    float* dst = wpart + static_cast<int64_t>(blockIdx.x) * (FD + F);
+    for (int t = threadIdx.x; t < FD + F; t += kBlock) dst[t] = red[t];
+  }
+}
+
+template <typename IdxT>
+__global__ void __launch_bounds__(kWave)
+    gine_bwd_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
+                          int64_t F, const float* __restrict__ part, float* __restrict__ grad_x) {
+  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), F, part, F, grad_x, F);
+}
+
+// the workgroups' partials (grad_W [F * De], then grad_b [F]) summed in workgroup order
+__global__ void __launch_bounds__(kBlock)
+    gine_param_reduce_kernel(const float* __restrict__ wpart, int n_blocks, int FD, int F,
+                             float* __restrict__ grad_weight, float* __restrict__ grad_bias) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  const int S = FD + F;
+  if (t >= S) return;
+  float acc = 0.f;
+  for (int g = 0; g < n_blocks; ++g) acc += wpart[static_cast<int64_t>(g) * S + t];
+  if (t < FD) {
+    grad_weight[t] = acc;
+  } else if (grad_bias) {
+    grad_bias[t - FD] = acc;
+  }
+}
+
+// ---- host side -------------------------------------------------------------------------------
+struct GineShape {
+  int lph, epl, de;  // de: the register capacity for De (0: wide mode)
+  bool vec;
+};
+
+bool gine_envelope(int64_t F, int64_t De) {
+  if (F < 1 || F > kGineMaxWidth || De < 0) return false;
+  return De == 0 || (De <= kGineMaxDe && F * De <= kGineMaxWeight);
+}
+
+bool gine_shape(int64_t F, int64_t De, bool aligned, GineShape* g) {
+  if (!gine_envelope(F, De)) return false;
+  if (De == 0) {
+    Shape s;
+    if (!choose_shape(1, F, aligned, &s)) return false;
+    *g = GineShape{s.lph, s.epl, 0, s.vec};
+    return true;
+  }
+  // linear mode: all 64 lanes share the columns, so that a lane's rows of W stay few
+  const int de = De <= 4 ? 4 : De <= 8 ? 8 : De <= 16 ? 16 : 32;
+  if (aligned && F % 4 == 0 && F > 128) {
+    *g = GineShape{kWave, F <= 256 ? 4 : 8, de, true};
+  } else {
+    const int n = static_cast<int>((F + kWave - 1) / kWave);
+    int epl = 1;
+    while (epl < n) epl *= 2;
+    *g = GineShape{kWave, epl, de, false};
+  }
+  return g->epl * g->de <= 128;  // (holds inside the envelope)
+}
+
+unsigned gine_grid(int64_t n_items, bool linear, unsigned cap) {
+  const unsigned full = wave_grid(n_items);
+  return linear && full > cap ? cap : full;
+}
+
+size_t gine_ws_bytes(int64_t n_chunks, int64_t F, int64_t De) {
+  // a chunk's partial row; in linear mode the backward's partials of (grad_W, grad_b) follow
+  const int64_t wpart = De > 0 ? static_cast<int64_t>(kGineBwdBlocks) * (F * De + F) : 0;
+  return sizeof(float) * static_cast<size_t>(n_chunks * F + wpart);
+}
+
+// `...` sees IdxT-independent constants EPL, VEC, DE of the shape
+#define GINE_CASE(epl_, vec_, de_, ...)                                              \
+  if (sh.epl == epl_ && sh.vec == vec_ && sh.de == de_) {                            \
+    constexpr int EPL = epl_; constexpr bool VEC = vec_; constexpr int DE = de_;     \
+    __VA_ARGS__                                                                      \
+  } else
+
+#define GINE_CASES_DE(de_, ...)                                                      \
+  GINE_CASE(1, false, de_, __VA_ARGS__) GINE_CASE(2, false, de_, __VA_ARGS__)        \
+  GINE_CASE(4, false, de_, __VA_ARGS__) GINE_CASE(4, true, de_, __VA_ARGS__)
+
+#define GINE_DISPATCH(...)                                                           \
+  do {                                                                               \
+    GINE_CASES_DE(0, __VA_ARGS__) GINE_CASES_DE(4, __VA_ARGS__)                      \
+    GINE_CASES_DE(8, __VA_ARGS__) GINE_CASES_DE(16, __VA_ARGS__)                     \
+    GINE_CASES_DE(32, __VA_ARGS__)                                                   \
+    GINE_CASE(8, false, 0, __VA_ARGS__) GINE_CASE(8, true, 0, __VA_ARGS__)           \
+    GINE_CASE(8, false, 4, __VA_ARGS__) GINE_CASE(8, true, 4, __VA_ARGS__)           \
+    GINE_CASE(8, false, 8, __VA_ARGS__) GINE_CASE(8, true, 8, __VA_ARGS__)           \
+    GINE_CASE(8, false, 16, __VA_ARGS__) GINE_CASE(8, true, 16, __VA_ARGS__)         \
+    { return PYGAMD_ERR_UNSUPPORTED; }                                               \
+  } while (0)
+
+int gine_check(int idx_dtype, int64_t n_rows, int64_t n_other, int64_t F, int64_t De,
+               const void* hub_rows, const void* hub_cptr, int64_t n_hub, int64_t n_chunks,
+               int64_t threshold, int64_t chunk) {
+  if (De < 0) return PYGAMD_ERR_INVALID_ARG;
+  const int rc = check_args(idx_dtype, n_rows, n_other, 1, F < 1 ? F : 1, hub_rows, hub_cptr,
+                            n_hub, n_chunks, threshold, chunk);
+  if (rc != PYGAMD_OK) return rc;
+  return gine_envelope(F, De) ? PYGAMD_OK : PYGAMD_ERR_UNSUPPORTED;
+}
+
+}  // namespace
+}  // namespace pygamd
+
+using namespace pygamd;
+
+extern "C" {
+
+int pygamd_gine_supported(int64_t F, int64_t De) { return gine_envelope(F, De) ? 1 : 0; }
+
+int pygamd_gine_workspace_bytes(int64_t n_chunks, int64_t F, int64_t De, size_t* bytes) {
+  if (!bytes || n_chunks < 0 || F < 1 || De < 0) return PYGAMD_ERR_INVALID_ARG;
+  if (!gine_envelope(F, De)) return PYGAMD_ERR_UNSUPPORTED;
+  *bytes = gine_ws_bytes(n_chunks, F, De);
+  return PYGAMD_OK;
+}
+
+int pygamd_gine_forward(const void* rowptr, const void* col, const void* edge_id, int idx_dtype,
+                        const float* x_src, int64_t ld_src, const float* x_root, int64_t ld_root,
+                        const float* eps, const float* edge_attr, const float* weight,
+                        const float* bias, int64_t n_rows, int64_t n_src, int64_t F, int64_t De,
+                        const void* hub_rows, const void* hub_chunk_ptr, int64_t n_hub,
+                        int64_t n_chunks, int64_t hub_threshold, int64_t hub_chunk, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = gine_check(idx_dtype, n_rows, n_src, F, De, hub_rows, hub_chunk_ptr, n_hub,
+                            n_chunks, hub_threshold, hub_chunk);
+  if (rc != PYGAMD_OK) return rc;
+  if (ld_src < F || (x_root && ld_root < F)) return PYGAMD_ERR_INVALID_ARG;
+  if (n_rows == 0) return PYGAMD_OK;
+  if (!rowptr || !col || !x_src || !edge_attr || !out || (De > 0 && !weight) ||
+      (De == 0 && (weight || bias)))
+    return PYGAMD_ERR_INVALID_ARG;
+  if (n_chunks > 0 && (!workspace || workspace_bytes < sizeof(float) * n_chunks * F))
+    return PYGAMD_ERR_WORKSPACE;
+  const bool al = aligned16(x_src) && ld_src % 4 == 0 && aligned16(out) &&
+                  (De > 0 || aligned16(edge_attr)) &&
+                  (!x_root || (aligned16(x_root) && ld_root % 4 == 0)) &&
+                  (n_chunks == 0 || aligned16(workspace));
+  GineShape sh;
+  if (!gine_shape(F, De, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+  float* part = static_cast<float*>(workspace);
+  const GineEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
+                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
+                   hub_threshold, hub_chunk};
+    const dim3 grid(gine_grid(n_rows + n_chunks, De > 0, kGineFwdBlocks)), block(kBlock);
+    GINE_DISPATCH({
+      hipLaunchKernelGGL((gine_fwd_kernel<IdxT, EPL, VEC, DE>), grid, block, 0, st, it,
+                         static_cast<const IdxT*>(col), static_cast<const IdxT*>(edge_id), x_src,
+                         ld_src, x_root, ld_root, eps, ed, static_cast<int>(F), sh.lph, out, part);
+    });
+    PYGAMD_LAUNCH_CHECK();
+    if (n_hub > 0) {
+      hipLaunchKernelGGL((gine_fwd_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
+                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, F, part, x_root, ld_root,
+                         eps, out);
+      PYGAMD_LAUNCH_CHECK();
+    }
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_gine_backward(const void* rowptr_t, const void* col_t, const void* edge_id_t,
+                         int idx_dtype, const float* x_src, int64_t ld_src,
+                         const float* edge_attr, const float* weight, const float* bias,
+                         const float* grad_out, int64_t n_src, int64_t n_dst, int64_t F,
+                         int64_t De, const void* hub_rows, const void* hub_chunk_ptr,
+                         int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
+                         int64_t hub_chunk, float* grad_x_src, float* grad_edge_attr,
+                         float* grad_weight, float* grad_bias, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  const int rc = gine_check(idx_dtype, n_src, n_dst, F, De, hub_rows, hub_chunk_ptr, n_hub,
+                            n_chunks, hub_threshold, hub_chunk);
+  if (rc != PYGAMD_OK) return rc;
+  if (ld_src < F) return PYGAMD_ERR_INVALID_ARG;
+  if (n_src == 0) return PYGAMD_OK;
+  if (!rowptr_t || !col_t || !x_src || !edge_attr || !grad_out || !grad_x_src ||
+      (De > 0 && (!weight || !grad_weight)) ||
+      (De == 0 && (weight || bias || grad_weight || grad_bias)) || (grad_bias && !bias))
+    return PYGAMD_ERR_INVALID_ARG;
+  if ((n_chunks > 0 || De > 0) &&
+      (!workspace || workspace_bytes < gine_ws_bytes(n_chunks, F, De)))
+    return PYGAMD_ERR_WORKSPACE;
+  const bool al = aligned16(x_src) && ld_src % 4 == 0 && aligned16(grad_out) &&
+                  aligned16(grad_x_src) &&
+                  (De > 0 || (aligned16(edge_attr) && aligned16(grad_edge_attr))) &&
+                  (n_chunks == 0 || aligned16(workspace));
+  GineShape sh;
+  if (!gine_shape(F, De, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
+  hipStream_t st = as_stream(stream);
+  float* part = static_cast<float*>(workspace);
+  float* wpart = part + n_chunks * F;
+  const GineEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    Items<IdxT> it{static_cast<const IdxT*>(rowptr_t), static_cast<const IdxT*>(hub_rows),
+                   static_cast<const IdxT*>(hub_chunk_ptr), n_src, n_hub, n_chunks,
+                   hub_threshold, hub_chunk};
+    const unsigned n_blocks = gine_grid(n_src + n_chunks, De > 0, kGineBwdBlocks);
+    const dim3 grid(n_blocks), block(kBlock);
+    GINE_DISPATCH({
+      hipLaunchKernelGGL((gine_bwd_kernel<IdxT, EPL, VEC, DE>), grid, block, 0, st, it,
+                         static_cast<const IdxT*>(col_t), static_cast<const IdxT*>(edge_id_t),
+                         x_src, ld_src, ed, grad_out, static_cast<int>(F), sh.lph, grad_x_src,
+                         grad_edge_attr, part, wpart);
+    });
+    PYGAMD_LAUNCH_CHECK();
+    if (n_hub > 0) {
+      hipLaunchKernelGGL((gine_bwd_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
+                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, F, part, grad_x_src);
+      PYGAMD_LAUNCH_CHECK();
+    }
+    if (De > 0) {
+      const int S = static_cast<int>(F * De + F);
+      hipLaunchKernelGGL(gine_param_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(S, kBlock))),
+                         block, 0, st, wpart, static_cast<int>(n_blocks),
+                         static_cast<int>(F * De), static_cast<int>(F), grad_weight, grad_bias);
+      PYGAMD_LAUNCH_CHECK();
+    }
+    return PYGAMD_OK;
+  });
+}
+
+}  // extern "C"

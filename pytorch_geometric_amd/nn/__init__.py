@@ -1,7 +1,7 @@
 from .aggr import (Aggregation, FusedAggregation, MaxAggregation, MeanAggregation,
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
-from .conv import (FastRGCNConv, GATConv, GATv2Conv, GCNConv, GraphConv, HeteroConv, HGTConv,
+from .conv import (FastRGCNConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HeteroConv, HGTConv,
                    MessagePassing, RGCNConv, SAGEConv, TransformerConv, gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, GraphSAGE
@@ -11,6 +11,6 @@ __all__ = [
     'Aggregation', 'SumAggregation', 'MeanAggregation', 'MaxAggregation', 'MinAggregation',
     'MulAggregation', 'VarAggregation', 'StdAggregation', 'FusedAggregation',
     'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
-    'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv',
+    'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

@@ -8,6 +8,7 @@ from .rgcn_conv import FastRGCNConv, RGCNConv
 from .graph_conv import GraphConv
 from .hetero_conv import HeteroConv, group
 from .hgt_conv import HGTConv
+from .gin_conv import GINConv, GINEConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
-           'GraphConv', 'HeteroConv', 'group', 'HGTConv']
+           'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv']

@@ -2,7 +2,7 @@
 kaiming-uniform, glorot, constants), applied to plain tensors / parameters; ``None`` is ignored so
 optional parameters can be passed unconditionally."""
 import math
-from typing import Optional
+from typing import Any, Optional
 
 from torch import Tensor
 
@@ -40,3 +40,13 @@ def zeros(value: Optional[Tensor]) -> None:
 
 def ones(value: Optional[Tensor]) -> None:
     constant(value, 1.0)
+
+
+def reset(value: Any) -> None:
+    """``reset_parameters()`` of a module, or of every module below one that has none of its
+    own (a ``Sequential``); anything else is left alone (inits.py:63-70)."""
+    if hasattr(value, 'reset_parameters'):
+        value.reset_parameters()
+    else:
+        for child in (value.children() if hasattr(value, 'children') else ()):
+            reset(child)

@@ -36,6 +36,9 @@ Operators (all index tensors int32 / int64, features float32):
                             -> (Tensor out, Tensor z, Tensor alpha)``
 ``hgt_relation``            ``(Tensor[] kqvs, Tensor k_weight, Tensor v_weight, int[] src_pos,
                             int[] widx, int heads) -> Tensor``
+``gine_aggregate``          ``(Tensor x_src, Tensor? x_root, Tensor? eps, Tensor edge_attr,
+                            Tensor? weight, Tensor? bias, Tensor rowptr, Tensor col,
+                            Tensor? edge_id) -> Tensor``
 ==========================  ===========================================================
 """
 import math
@@ -587,6 +590,91 @@ register_autograd('pyg_amd::transformer_edge_attend', _transformer_edge_bwd,
                   setup_context=_transformer_edge_setup)
 
 
+# ---- GINEConv's aggregation on a CSR pair (rows = destinations) ------------------------------------
+@custom_op('pyg_amd::gine_aggregate', mutates_args=(), device_types=_DEV)
+def gine_aggregate(x_src: Tensor, x_root: Optional[Tensor], eps: Optional[Tensor],
+                   edge_attr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                   rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor]) -> Tensor:
+    """``out [n_dst, F] = (1 + eps) * x_root[:n_dst] + sum_k relu(x_src[col[k]] + e_k)``
+    (gin_conv.py:185-207) with ``e_k = edge_attr[edge_id[k]]`` for ``edge_attr [E, F]``, or
+    ``weight @ edge_attr[edge_id[k]] + bias`` for ``edge_attr [E, De]`` and ``weight [F, De]``.
+    ``edge_id=None``: ``edge_attr`` follows the slots of ``col``.  The by-source form the backward
+    walks is built from ``(rowptr, col)`` there, as the attention operators do."""
+    F = x_src.size(1)
+    De = 0 if weight is None else edge_attr.size(1)
+    if not _native.gine_supported(F, De):
+        raise NotImplementedError(
+            f'gine_aggregate serves F <= 512 and, with a weight, De <= 32 and F * De <= 4096 '
+            f'(got F = {F}, De = {De})')
+    return _native.gine_forward(rowptr, col, edge_id, x_src, x_root,
+                                None if eps is None else eps.reshape(1), edge_attr, weight, bias,
+                                hub=_native.hub_plan(rowptr))
+
+
+@gine_aggregate.register_fake
+def _(x_src, x_root, eps, edge_attr, weight, bias, rowptr, col, edge_id):
+    return x_src.new_empty(rowptr.numel() - 1, x_src.shape[1])
+
+
+@custom_op('pyg_amd::gine_aggregate_backward', mutates_args=(), device_types=_DEV)
+def gine_aggregate_backward(grad: Tensor, x_src: Tensor, x_root: Optional[Tensor],
+                            eps: Optional[Tensor], edge_attr: Tensor, weight: Optional[Tensor],
+                            bias: Optional[Tensor], rowptr: Tensor, col: Tensor,
+                            edge_id: Optional[Tensor]
+                            ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The gradients of ``(x_src, x_root, eps, edge_attr, weight, bias)``; an input that was not
+    given gets an empty tensor."""
+    n_dst, n_src = rowptr.numel() - 1, x_src.size(0)
+    # the by-source form of the same slots: a stable sort of `col`; its permutation maps the
+    # by-source slots to the CSR's own slots, and through edge_id to the caller's edges
+    dst = _native.ptr2index(rowptr, col.numel())
+    src_sorted, perm = _native.index_sort(col, max_value=max(n_src - 1, 0))
+    rowptr_t = _native.index2ptr(src_sorted, n_src)
+    col_t = _native.permute_index(dst, perm)
+    edge_id_t = (_native.cast_index(perm, col.dtype) if edge_id is None
+                 else _native.permute_index(edge_id, perm))
+    g_x, g_a, g_w, g_b = _native.gine_backward(rowptr_t, col_t, edge_id_t, x_src, edge_attr,
+                                               weight, bias, grad,
+                                               hub=_native.hub_plan(rowptr_t))
+    none = grad.new_empty(0)
+    g_root = g_eps = none
+    if x_root is not None:
+        g_root = grad.new_zeros(x_root.shape)
+        g_root[:n_dst] = grad if eps is None else grad * (1.0 + eps.reshape(()))
+        if eps is not None:
+            g_eps = ((grad * x_root[:n_dst]).sum(dim=1).double().sum().to(eps.dtype)
+                     .reshape(eps.shape))
+    return (g_x, g_root, g_eps, g_a, none if g_w is None else g_w, none if g_b is None else g_b)
+
+
+@gine_aggregate_backward.register_fake
+def _(grad, x_src, x_root, eps, edge_attr, weight, bias, rowptr, col, edge_id):
+    none = grad.new_empty(0)
+    return (torch.empty_like(x_src), none if x_root is None else torch.empty_like(x_root),
+            none if eps is None or x_root is None else torch.empty_like(eps),
+            torch.empty_like(edge_attr), none if weight is None else torch.empty_like(weight),
+            none if bias is None else torch.empty_like(bias))
+
+
+def _gine_setup(ctx, inputs, output):
+    x_src, x_root, eps, edge_attr, weight, bias, rowptr, col, edge_id = inputs
+    ctx.given = (x_root is not None, eps is not None and x_root is not None, weight is not None,
+                 bias is not None)
+    ctx.save_for_backward(x_src, x_root, eps, edge_attr, weight, bias, rowptr, col, edge_id)
+
+
+def _gine_bwd(ctx, grad):
+    x_src, x_root, eps, edge_attr, weight, bias, rowptr, col, edge_id = ctx.saved_tensors
+    g_x, g_root, g_eps, g_a, g_w, g_b = gine_aggregate_backward(
+        grad.contiguous(), x_src, x_root, eps, edge_attr, weight, bias, rowptr, col, edge_id)
+    has_root, has_eps, has_w, has_b = ctx.given
+    return (g_x, g_root if has_root else None, g_eps if has_eps else None, g_a,
+            g_w if has_w else None, g_b if has_b else None, None, None, None)
+
+
+register_autograd('pyg_amd::gine_aggregate', _gine_bwd, setup_context=_gine_setup)
+
+
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
 def _hgt_blocks(kqvs, src_pos, F):
     return ([kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos])
@@ -658,4 +746,5 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'segment_csr', 'segment_csr_backward', 'softmax_csr', 'softmax_csr_backward', 'spmm',
        'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
        'transformer_attend_backward', 'transformer_edge_attend',
-       'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward')
+       'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward',
+       'gine_aggregate', 'gine_aggregate_backward')
