@@ -30,7 +30,7 @@ extern "C" {
 
 #define PYGAMD_API __attribute__((visibility("default")))
 
-#define PYGAMD_ABI_VERSION 10
+#define PYGAMD_ABI_VERSION 11
 
 typedef enum {
   PYGAMD_OK = 0,
@@ -144,6 +144,28 @@ PYGAMD_API int pygamd_hub_plan(const void* rowptr, int idx_dtype, int64_t n_rows
                                void* hub_chunk_ptr, int64_t cap, int64_t* n_hub_out /*[host]*/,
                                int64_t* n_chunks_out /*[host]*/, void* workspace,
                                size_t workspace_bytes, void* stream);
+
+/* A CSR handle with its hub plan: what the one-pass kernels (pygamd_gatv2_*, pygamd_transformer_*,
+ * pygamd_gine_*) walk, one wave per row.  Row r owns the slots [rowptr[r], rowptr[r + 1]) and
+ * col[k] is the row of the OTHER side that slot k reads; a by-destination handle has the
+ * destinations as rows, a by-source handle (the `_src` / GINE backward passes) the sources.
+ * Rows of more than hub_threshold slots are walked as the plan's chunks of hub_chunk slots and
+ * their partial results merged in chunk order; n_hub == 0 means that no row is split (the hub
+ * pointers are then ignored and n_chunks must be 0).  The plan must come from pygamd_hub_plan on
+ * this rowptr with the same threshold and chunk.  All index arrays share idx_dtype.            */
+typedef struct pygamd_csr {
+  const void* rowptr;        /* [n_rows + 1]                         */
+  const void* col;           /* [nnz]                                */
+  int32_t idx_dtype;         /* PYGAMD_IDX_I32 | PYGAMD_IDX_I64      */
+  int32_t reserved0;         /* 0 */
+  int64_t n_rows;
+  const void* hub_rows;      /* [n_hub] or NULL                      */
+  const void* hub_chunk_ptr; /* [n_hub + 1] or NULL                  */
+  int64_t n_hub;
+  int64_t n_chunks;
+  int64_t hub_threshold;
+  int64_t hub_chunk;
+} pygamd_csr;
 
 /* ---- a9/a13/a14: CSR SpMM (fused gather -> message -> segmented reduce) ---------------------
  * Replaces torch.ops.torch_sparse.spmm_{sum,mean,min,max}
@@ -564,50 +586,39 @@ PYGAMD_API int pygamd_gat_edge_softmax_backward(const void* rowptr, const void* 
  *   out[i,h] = sum_k alpha[k,h] * x_l[j,h,:]
  * x_l [n_src, H*C], x_r [>= n_rows, H*C], att [H*C], all contiguous fp32.  alpha is [nnz, H] in
  * SLOT order and always written; out [n_rows, H*C] may be NULL ("score mode": alpha only).
- * Supported: H*C <= 512 and H <= 64 (pygamd_gatv2_supported), otherwise status 2.  Rows of more
- * than hub_threshold slots are walked as the chunks of the hub plan (pygamd_hub_plan with the same
- * threshold and chunk) and merged in chunk order; the workspace (pygamd_gatv2_workspace_bytes of
- * that plan's n_chunks) holds the partial results and, for backward_dst, the per-workgroup
- * partials of the att gradient.  No float atomics: all results are bitwise reproducible.
+ * Supported: H*C <= 512 and H <= 64 (pygamd_gatv2_supported), otherwise status 2.  `g` is the
+ * handle (pygamd_csr; NULL: status 1) and n_src the row count of x_l; the workspace
+ * (pygamd_gatv2_workspace_bytes of g's n_chunks) holds the chunks' partial results and, for
+ * backward_dst, the per-workgroup partials of the att gradient.  No float atomics: all results are
+ * bitwise reproducible.
  *
  * backward_dst: grad_s[k,h] = alpha * (d alpha - D), grad_x_r [n_rows, H*C], grad_att [H*C].
  *   d alpha = <grad_out[i,h,:], x_l[j,h,:]> and D = <grad_out[i,h,:], out[i,h,:]> when grad_out /
  *   out are given and grad_alpha is NULL; score mode passes grad_alpha [nnz, H] (slot order) and
  *   NULL for grad_out / out.
- * backward_src: on the src-sorted handle with slot_map = by-source slot -> by-destination slot,
+ * backward_src: g is the src-sorted handle (n_dst the row count of the by-destination one), with
+ *   slot_map = by-source slot -> by-destination slot,
  *   grad_x_l[j] = sum_i alpha * grad_out[i] + grad_s * att * leaky_relu'(x_l[j] + x_r[i]); the
  *   first term is left out when grad_out is NULL (score mode).                                  */
 PYGAMD_API int pygamd_gatv2_supported(int64_t H, int64_t C);
 PYGAMD_API int pygamd_gatv2_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C,
                                             size_t* bytes /*[host]*/);
-PYGAMD_API int pygamd_gatv2_forward(const void* rowptr, const void* col, int idx_dtype,
-                                    const float* x_l, const float* x_r, const float* att,
-                                    int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
-                                    float slope, const void* hub_rows,
-                                    const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
-                                    int64_t hub_threshold, int64_t hub_chunk, float* alpha,
-                                    float* out, void* workspace, size_t workspace_bytes,
-                                    void* stream);
-PYGAMD_API int pygamd_gatv2_backward_dst(const void* rowptr, const void* col, int idx_dtype,
+PYGAMD_API int pygamd_gatv2_forward(const pygamd_csr* g, const float* x_l, const float* x_r,
+                                    const float* att, int64_t n_src, int64_t H, int64_t C,
+                                    float slope, float* alpha, float* out, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_gatv2_backward_dst(const pygamd_csr* g, const float* x_l, const float* x_r,
+                                         const float* att, const float* alpha,
+                                         const float* grad_out, const float* out,
+                                         const float* grad_alpha, int64_t n_src, int64_t H,
+                                         int64_t C, float slope, float* grad_s, float* grad_x_r,
+                                         float* grad_att, void* workspace, size_t workspace_bytes,
+                                         void* stream);
+PYGAMD_API int pygamd_gatv2_backward_src(const pygamd_csr* g, const void* slot_map,
                                          const float* x_l, const float* x_r, const float* att,
-                                         const float* alpha, const float* grad_out,
-                                         const float* out, const float* grad_alpha,
-                                         int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
-                                         float slope, const void* hub_rows,
-                                         const void* hub_chunk_ptr, int64_t n_hub,
-                                         int64_t n_chunks, int64_t hub_threshold,
-                                         int64_t hub_chunk, float* grad_s, float* grad_x_r,
-                                         float* grad_att, void* workspace,
-                                         size_t workspace_bytes, void* stream);
-PYGAMD_API int pygamd_gatv2_backward_src(const void* rowptr_t, const void* col_t,
-                                         const void* slot_map, int idx_dtype, const float* x_l,
-                                         const float* x_r, const float* att, const float* alpha,
-                                         const float* grad_s, const float* grad_out,
-                                         int64_t n_src, int64_t n_dst, int64_t H, int64_t C,
-                                         float slope, const void* hub_rows,
-                                         const void* hub_chunk_ptr, int64_t n_hub,
-                                         int64_t n_chunks, int64_t hub_threshold,
-                                         int64_t hub_chunk, float* grad_x_l, void* workspace,
+                                         const float* alpha, const float* grad_s,
+                                         const float* grad_out, int64_t n_dst, int64_t H, int64_t C,
+                                         float slope, float* grad_x_l, void* workspace,
                                          size_t workspace_bytes, void* stream);
 
 /* ---- a16b: TransformerConv's dot-product attention in one pass --------------------------------
@@ -621,51 +632,39 @@ PYGAMD_API int pygamd_gatv2_backward_src(const void* rowptr_t, const void* col_t
  * ONE row stride ld >= H*C (floats): separate contiguous tensors (ld = H*C) or the two halves of a
  * [n_src, 2*H*C] projection (ld = 2*H*C, value = key + H*C).  alpha is [nnz, H] in SLOT order and
  * always written; out [n_rows, H*C] may be NULL ("score mode": alpha only, value is not read).
- * Supported head layouts, hub rows, chunk-order merges and reproducibility as for pygamd_gatv2_*
- * (pygamd_transformer_supported; workspace of pygamd_transformer_workspace_bytes for the plan's
+ * Supported head layouts, the handle g and reproducibility as for pygamd_gatv2_*
+ * (pygamd_transformer_supported; workspace of pygamd_transformer_workspace_bytes for g's
  * n_chunks, 0 bytes without hub rows).  Status 1 / 2 / 3 before any device work.
  *
  * backward_dst (transformer_conv.py:273-282 differentiated): grad_s[k,h] = alpha * (d alpha - D),
  *   grad_query[i] = scale * sum_k grad_s * key[j].  d alpha = <grad_out[i,h,:], value[j,h,:]> and
  *   D = <grad_out[i,h,:], out[i,h,:]> when grad_out / out are given and grad_alpha is NULL; score
  *   mode passes grad_alpha [nnz, H] (slot order), NULL for grad_out / out, and does not read value.
- * backward_src: on the src-sorted handle with slot_map = by-source slot -> by-destination slot,
+ * backward_src: g is the src-sorted handle, slot_map = by-source slot -> by-destination slot,
  *   grad_key[j] = scale * sum_i grad_s * query[i] and grad_value[j] = sum_i alpha * grad_out[i],
  *   both written at row stride ld (one [n_src, 2*H*C] gradient buffer feeds one dgrad GEMM);
  *   grad_out NULL = score mode: grad_key only, grad_value may be NULL.                          */
 PYGAMD_API int pygamd_transformer_supported(int64_t H, int64_t C);
 PYGAMD_API int pygamd_transformer_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C,
                                                   size_t* bytes /*[host]*/);
-PYGAMD_API int pygamd_transformer_forward(const void* rowptr, const void* col, int idx_dtype,
-                                          const float* query, const float* key,
-                                          const float* value, int64_t ld, int64_t n_rows,
-                                          int64_t n_src, int64_t H, int64_t C, float scale,
-                                          const void* hub_rows, const void* hub_chunk_ptr,
-                                          int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
-                                          int64_t hub_chunk, float* alpha, float* out,
+PYGAMD_API int pygamd_transformer_forward(const pygamd_csr* g, const float* query, const float* key,
+                                          const float* value, int64_t ld, int64_t n_src, int64_t H,
+                                          int64_t C, float scale, float* alpha, float* out,
                                           void* workspace, size_t workspace_bytes, void* stream);
-PYGAMD_API int pygamd_transformer_backward_dst(const void* rowptr, const void* col, int idx_dtype,
-                                               const float* key, const float* value, int64_t ld,
-                                               const float* alpha, const float* grad_out,
-                                               const float* out, const float* grad_alpha,
-                                               int64_t n_rows, int64_t n_src, int64_t H,
-                                               int64_t C, float scale, const void* hub_rows,
-                                               const void* hub_chunk_ptr, int64_t n_hub,
-                                               int64_t n_chunks, int64_t hub_threshold,
-                                               int64_t hub_chunk, float* grad_s,
+PYGAMD_API int pygamd_transformer_backward_dst(const pygamd_csr* g, const float* key,
+                                               const float* value, int64_t ld, const float* alpha,
+                                               const float* grad_out, const float* out,
+                                               const float* grad_alpha, int64_t n_src, int64_t H,
+                                               int64_t C, float scale, float* grad_s,
                                                float* grad_query, void* workspace,
                                                size_t workspace_bytes, void* stream);
-PYGAMD_API int pygamd_transformer_backward_src(const void* rowptr_t, const void* col_t,
-                                               const void* slot_map, int idx_dtype,
+PYGAMD_API int pygamd_transformer_backward_src(const pygamd_csr* g, const void* slot_map,
                                                const float* query, const float* alpha,
                                                const float* grad_s, const float* grad_out,
-                                               int64_t n_src, int64_t n_dst, int64_t H, int64_t C,
-                                               float scale, const void* hub_rows,
-                                               const void* hub_chunk_ptr, int64_t n_hub,
-                                               int64_t n_chunks, int64_t hub_threshold,
-                                               int64_t hub_chunk, float* grad_key,
-                                               float* grad_value, int64_t ld, void* workspace,
-                                               size_t workspace_bytes, void* stream);
+                                               int64_t n_dst, int64_t H, int64_t C, float scale,
+                                               float* grad_key, float* grad_value, int64_t ld,
+                                               void* workspace, size_t workspace_bytes,
+                                               void* stream);
 
 /* ---- a16c: TransformerConv's edge features (edge_dim) inside the one-pass kernels ---------------
  * nn/conv/transformer_conv.py:263-283 with lin_edge: key_j + e and value_j + e, e = W_e a_k.  The
@@ -677,7 +676,7 @@ PYGAMD_API int pygamd_transformer_backward_src(const void* rowptr_t, const void*
  *   z[i,h]   = sum_k alpha[k,h] * a_k                   ([n_rows, H*De])
  * and the caller adds W_e^h z[i,h] to out (transformer_conv.py:263-283: `out = value_j + edge_attr`).
  * edge_attr is [nnz, De] contiguous fp32 in SLOT order.  out and z are both given, or both NULL
- * ("score mode": alpha only).  Every other argument, the hub plan, the chunk-order merges and the
+ * ("score mode": alpha only).  Every other argument, the handle g and the
  * reproducibility are those of pygamd_transformer_forward; the workspace is that of
  * pygamd_transformer_edge_workspace_bytes.  pygamd_transformer_edge_supported (transformer_conv.py:
  * 263-283): the head layout of pygamd_transformer_supported and De <= 4 * lph_max, lph_max the
@@ -696,29 +695,24 @@ PYGAMD_API int pygamd_transformer_backward_src(const void* rowptr_t, const void*
 PYGAMD_API int pygamd_transformer_edge_supported(int64_t H, int64_t C, int64_t De);
 PYGAMD_API int pygamd_transformer_edge_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C,
                                                        int64_t De, size_t* bytes /*[host]*/);
-PYGAMD_API int pygamd_transformer_edge_forward(const void* rowptr, const void* col, int idx_dtype,
-                                               const float* query, const float* key,
-                                               const float* value, int64_t ld,
+PYGAMD_API int pygamd_transformer_edge_forward(const pygamd_csr* g, const float* query,
+                                               const float* key, const float* value, int64_t ld,
                                                const float* edge_attr, const float* bias,
-                                               int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
-                                               int64_t De, float scale, const void* hub_rows,
-                                               const void* hub_chunk_ptr, int64_t n_hub,
-                                               int64_t n_chunks, int64_t hub_threshold,
-                                               int64_t hub_chunk, float* alpha, float* out,
-                                               float* z, void* workspace, size_t workspace_bytes,
+                                               int64_t n_src, int64_t H, int64_t C, int64_t De,
+                                               float scale, float* alpha, float* out, float* z,
+                                               void* workspace, size_t workspace_bytes,
                                                void* stream);
 PYGAMD_API int pygamd_transformer_edge_backward_dst(
-    const void* rowptr, const void* col, int idx_dtype, const float* key, const float* value,
-    int64_t ld, const float* edge_attr, const float* bias, const float* alpha,
-    const float* grad_out, const float* out, const float* grad_z, const float* z,
-    const float* grad_alpha, int64_t n_rows, int64_t n_src, int64_t H, int64_t C, int64_t De,
-    float scale, const void* hub_rows, const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
-    int64_t hub_threshold, int64_t hub_chunk, float* grad_s, float* grad_query, float* grad_bias,
-    float* grad_edge_attr, void* workspace, size_t workspace_bytes, void* stream);
+    const pygamd_csr* g, const float* key, const float* value, int64_t ld,
+    const float* edge_attr, const float* bias, const float* alpha, const float* grad_out,
+    const float* out, const float* grad_z, const float* z, const float* grad_alpha,
+    int64_t n_src, int64_t H, int64_t C, int64_t De, float scale, float* grad_s,
+    float* grad_query, float* grad_bias, float* grad_edge_attr, void* workspace,
+    size_t workspace_bytes, void* stream);
 
 /* ---- GINEConv's edge message (gin_conv.py:19-207) -------------------------------------------------
- * One destination row i of a CSR by destination (rows = destinations, col = the source of every
- * slot), slot k with source j = col[k] and original edge edge_id[k] (NULL: slot order):
+ * One destination row i of the by-destination handle g (pygamd_csr; NULL: status 1), slot k with
+ * source j = col[k] and original edge edge_id[k] (NULL: slot order):
  *   out[i,:] = (x_root ? (1 + *eps) * x_root[i,:] : 0) + sum_k max(x_src[j,:] + e_k, 0)
  *   wide   (De == 0): e_k = edge_attr[edge_id[k], :],   edge_attr [E, F]
  *   linear (De >= 1): e_k = W a_k + b, a_k = edge_attr[edge_id[k], :De], weight W [F, De] in
@@ -729,11 +723,10 @@ PYGAMD_API int pygamd_transformer_edge_backward_dst(
  * [E, F] value is formed.  eps is a DEVICE pointer (it may be a parameter; no host read); x_root
  * and eps may be NULL (the bipartite (x_src, None) case).  x_src and x_root have row strides
  * ld_src / ld_root (floats), everything else is contiguous; fp32 data, int32 / int64 indices.
- * Rows beyond hub_threshold slots go through the hub plan's chunks and their partial sums are
- * added in chunk order.  No float atomics: bitwise reproducible.
+ * A split row's partial sums are added in chunk order.  No float atomics: bitwise reproducible.
  *
- * backward: ONE launch over the CSR by source (rowptr_t over sources, col_t = the destination of
- * every out-slot, edge_id_t = that form's own slot -> original edge map, NULL: slot order), every
+ * backward: ONE launch over the by-source handle g (col = the destination of every out-slot,
+ * edge_id_t = that form's own slot -> original edge map, NULL: slot order), every
  * edge visited once, m = (x_src[j,:] + e_k > 0) (strict, as relu's backward), g = grad_out[i,:]:
  *   grad_x_src[j,:] = sum_t m * g                      (zeros for rows without out-slots)
  *   wide:   grad_edge_attr[k,:] = m * g                (original edge order; NULL: not wanted)
@@ -750,22 +743,16 @@ PYGAMD_API int pygamd_transformer_edge_backward_dst(
 PYGAMD_API int pygamd_gine_supported(int64_t F, int64_t De);
 PYGAMD_API int pygamd_gine_workspace_bytes(int64_t n_chunks, int64_t F, int64_t De,
                                            size_t* bytes /*[host]*/);
-PYGAMD_API int pygamd_gine_forward(const void* rowptr, const void* col, const void* edge_id,
-                                   int idx_dtype, const float* x_src, int64_t ld_src,
-                                   const float* x_root, int64_t ld_root, const float* eps,
-                                   const float* edge_attr, const float* weight, const float* bias,
-                                   int64_t n_rows, int64_t n_src, int64_t F, int64_t De,
-                                   const void* hub_rows, const void* hub_chunk_ptr, int64_t n_hub,
-                                   int64_t n_chunks, int64_t hub_threshold, int64_t hub_chunk,
+PYGAMD_API int pygamd_gine_forward(const pygamd_csr* g, const void* edge_id, const float* x_src,
+                                   int64_t ld_src, const float* x_root, int64_t ld_root,
+                                   const float* eps, const float* edge_attr, const float* weight,
+                                   const float* bias, int64_t n_src, int64_t F, int64_t De,
                                    float* out, void* workspace, size_t workspace_bytes,
                                    void* stream);
-PYGAMD_API int pygamd_gine_backward(const void* rowptr_t, const void* col_t, const void* edge_id_t,
-                                    int idx_dtype, const float* x_src, int64_t ld_src,
-                                    const float* edge_attr, const float* weight, const float* bias,
-                                    const float* grad_out, int64_t n_src, int64_t n_dst, int64_t F,
-                                    int64_t De, const void* hub_rows, const void* hub_chunk_ptr,
-                                    int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
-                                    int64_t hub_chunk, float* grad_x_src, float* grad_edge_attr,
+PYGAMD_API int pygamd_gine_backward(const pygamd_csr* g, const void* edge_id_t, const float* x_src,
+                                    int64_t ld_src, const float* edge_attr, const float* weight,
+                                    const float* bias, const float* grad_out, int64_t n_dst,
+                                    int64_t F, int64_t De, float* grad_x_src, float* grad_edge_attr,
                                     float* grad_weight, float* grad_bias, void* workspace,
                                     size_t workspace_bytes, void* stream);
 

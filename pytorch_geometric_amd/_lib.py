@@ -10,7 +10,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_in
 
 from . import _build
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 X_DENSE, X_COMPRESSED = 0, 1  # pygamd_x_format  # PYGAMD_ABI_VERSION of include/pyg_amd.h
 AGG_GIVEN = 2  # PYGAMD_AGG_GIVEN: save_agg of the one-kernel SAGE layer, "rows given"
 IDX_I32, IDX_I64 = 0, 1
@@ -40,6 +40,16 @@ class SpmmArgs(Structure):
     ]
 
 
+class Csr(Structure):
+    """Mirror of ``pygamd_csr`` (include/pyg_amd.h): a CSR handle with its hub plan."""
+    _fields_ = [
+        ('rowptr', c_void_p), ('col', c_void_p), ('idx_dtype', c_int32), ('reserved0', c_int32),
+        ('n_rows', c_int64), ('hub_rows', c_void_p), ('hub_chunk_ptr', c_void_p),
+        ('n_hub', c_int64), ('n_chunks', c_int64), ('hub_threshold', c_int64),
+        ('hub_chunk', c_int64),
+    ]
+
+
 class SageFusedArgs(Structure):
     """Mirror of ``pygamd_sage_fused_args`` (include/pyg_amd.h)."""
     _fields_ = [
@@ -54,6 +64,7 @@ class SageFusedArgs(Structure):
 
 # name -> (restype, argtypes); must list every PYGAMD_API symbol of include/pyg_amd.h
 _P = c_void_p
+_G = POINTER(Csr)
 SIGNATURES = {
     'pygamd_abi_version': (c_int, []),
     'pygamd_status_string': (c_char_p, [c_int]),
@@ -224,50 +235,37 @@ SIGNATURES = {
                                                  c_int64, c_float, _P, _P, _P]),
     'pygamd_gatv2_supported': (c_int, [c_int64, c_int64]),
     'pygamd_gatv2_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_gatv2_forward': (c_int, [_P, _P, c_int, _P, _P, _P, c_int64, c_int64, c_int64,
-                                     c_int64, c_float, _P, _P, c_int64, c_int64, c_int64,
-                                     c_int64, _P, _P, _P, c_size_t, _P]),
-    'pygamd_gatv2_backward_dst': (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64,
-                                          c_int64, c_int64, c_int64, c_float, _P, _P, c_int64,
-                                          c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t,
-                                          _P]),
-    'pygamd_gatv2_backward_src': (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int64,
-                                          c_int64, c_int64, c_int64, c_float, _P, _P, c_int64,
-                                          c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
+    'pygamd_gatv2_forward': (c_int, [_G, _P, _P, _P, c_int64, c_int64, c_int64, c_float, _P, _P, _P,
+                                     c_size_t, _P]),
+    'pygamd_gatv2_backward_dst': (c_int, [_G, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
+                                          c_float, _P, _P, _P, _P, c_size_t, _P]),
+    'pygamd_gatv2_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
+                                          c_float, _P, _P, c_size_t, _P]),
     'pygamd_transformer_supported': (c_int, [c_int64, c_int64]),
     'pygamd_transformer_workspace_bytes': (c_int, [c_int64, c_int64, c_int64,
                                                    POINTER(c_size_t)]),
-    'pygamd_transformer_forward': (c_int, [_P, _P, c_int, _P, _P, _P, c_int64, c_int64, c_int64,
-                                           c_int64, c_int64, c_float, _P, _P, c_int64, c_int64,
-                                           c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
-    'pygamd_transformer_backward_dst': (c_int, [_P, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P,
-                                                c_int64, c_int64, c_int64, c_int64, c_float, _P,
-                                                _P, c_int64, c_int64, c_int64, c_int64, _P, _P,
-                                                _P, c_size_t, _P]),
-    'pygamd_transformer_backward_src': (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int64,
-                                                c_int64, c_int64, c_int64, c_float, _P, _P,
-                                                c_int64, c_int64, c_int64, c_int64, _P, _P,
-                                                c_int64, _P, c_size_t, _P]),
+    'pygamd_transformer_forward': (c_int, [_G, _P, _P, _P, c_int64, c_int64, c_int64, c_int64,
+                                           c_float, _P, _P, _P, c_size_t, _P]),
+    'pygamd_transformer_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, _P, _P, _P, c_int64,
+                                                c_int64, c_int64, c_float, _P, _P, _P, c_size_t,
+                                                _P]),
+    'pygamd_transformer_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
+                                                c_float, _P, _P, c_int64, _P, c_size_t, _P]),
     'pygamd_transformer_edge_supported': (c_int, [c_int64, c_int64, c_int64]),
     'pygamd_transformer_edge_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, c_int64,
                                                         POINTER(c_size_t)]),
-    'pygamd_transformer_edge_forward': (c_int, [_P, _P, c_int, _P, _P, _P, c_int64, _P, _P,
-                                                c_int64, c_int64, c_int64, c_int64, c_int64,
-                                                c_float, _P, _P, c_int64, c_int64, c_int64,
-                                                c_int64, _P, _P, _P, _P, c_size_t, _P]),
-    'pygamd_transformer_edge_backward_dst': (c_int, [_P, _P, c_int, _P, _P, c_int64, _P, _P, _P,
-                                                     _P, _P, _P, _P, _P, c_int64, c_int64,
-                                                     c_int64, c_int64, c_int64, c_float, _P, _P,
-                                                     c_int64, c_int64, c_int64, c_int64, _P, _P,
-                                                     _P, _P, _P, c_size_t, _P]),
+    'pygamd_transformer_edge_forward': (c_int, [_G, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64,
+                                                c_int64, c_int64, c_float, _P, _P, _P, _P, c_size_t,
+                                                _P]),
+    'pygamd_transformer_edge_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, _P, _P, _P, _P, _P,
+                                                     _P, _P, c_int64, c_int64, c_int64, c_int64,
+                                                     c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
     'pygamd_gine_supported': (c_int, [c_int64, c_int64]),
     'pygamd_gine_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_gine_forward': (c_int, [_P, _P, _P, c_int, _P, c_int64, _P, c_int64, _P, _P, _P, _P,
-                                    c_int64, c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64,
+    'pygamd_gine_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64,
                                     c_int64, c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_gine_backward': (c_int, [_P, _P, _P, c_int, _P, c_int64, _P, _P, _P, _P, c_int64,
-                                     c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64,
-                                     c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    'pygamd_gine_backward': (c_int, [_G, _P, _P, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_int64,
+                                     _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 # include/pyg_amd_lab.h: schedules measured and not adopted + timing probes (NOT the boundary;

@@ -14,7 +14,7 @@ import torch
 from torch import Tensor
 
 from . import _compiled, _lib
-from ._lib import REDUCE_IDS, PygAmdError, SpmmArgs, check
+from ._lib import REDUCE_IDS, Csr, PygAmdError, SpmmArgs, check
 
 # rows with more stored entries than this are split into chunks (see csrc/spmm.hip)
 HUB_THRESHOLD = 1024
@@ -78,6 +78,45 @@ def _hub4(hub):
     if hub is not None and hub[2] > 0:
         return hub
     return None, None, 0, 0
+
+
+def _csr(rowptr: Tensor, col: Tensor, n_rows: int, hub) -> Csr:
+    """``pygamd_csr`` of a handle and its hub plan (``hub``: what :func:`hub_plan` returned for
+    this ``rowptr``, or None), split at this module's ``HUB_THRESHOLD`` / ``HUB_CHUNK``.  The
+    struct holds raw addresses and keeps nothing alive: the caller keeps every tensor given here
+    (and the result of any ``.contiguous()`` it passes) bound to a local until the call that
+    takes the struct has returned."""
+    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    return Csr(rowptr=rowptr.data_ptr(), col=col.data_ptr(), idx_dtype=_idx_dtype(rowptr),
+               n_rows=n_rows, hub_rows=None if h_rows is None else h_rows.data_ptr(),
+               hub_chunk_ptr=None if h_cptr is None else h_cptr.data_ptr(), n_hub=n_hub,
+               n_chunks=n_chunks, hub_threshold=HUB_THRESHOLD, hub_chunk=HUB_CHUNK)
+
+
+def _workspace(size_fn, dims, device, needed: bool = True):
+    """``(buffer | None, bytes)`` for the ``pygamd_*_workspace_bytes`` query ``size_fn`` at
+    ``dims``; no query when the caller does not need one."""
+    if not needed:
+        return None, 0
+    nbytes = ctypes.c_size_t(0)
+    check(size_fn(*dims, ctypes.byref(nbytes)))
+    if nbytes.value == 0:
+        return None, 0
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
+
+
+def _strided_rows(t: Tensor, name: str, width: int) -> Tensor:
+    """``[n, width]`` float32 rows with unit column stride: a contiguous tensor or a column block
+    of a wider one (the halves of a packed key | value projection) is taken in place."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.size(1) != width:
+        raise ValueError(f"'{name}' must be a float32 [n, {width}] tensor (got {t.dtype} "
+                         f"{tuple(t.shape)})")
+    return t.contiguous() if t.stride(1) != 1 or t.stride(0) < width else t
+
+
+def _dense_rows(t: Tensor, name: str, width: int) -> Tensor:
+    """:func:`_strided_rows` for an operand that has no row stride: always contiguous."""
+    return _strided_rows(t, name, width).contiguous()
 
 
 # ---- integer side --------------------------------------------------------------------------------
@@ -1102,21 +1141,6 @@ def gatv2_supported(H: int, C: int) -> bool:
     return bool(_lib.load().pygamd_gatv2_supported(int(H), int(C)))
 
 
-def _gatv2_workspace(lib, n_chunks: int, H: int, C: int, device, needed: bool):
-    if not needed:
-        return None, 0
-    nbytes = ctypes.c_size_t(0)
-    check(lib.pygamd_gatv2_workspace_bytes(n_chunks, H, C, ctypes.byref(nbytes)))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
-
-
-def _gatv2_rows(t: Tensor, name: str, width: int) -> Tensor:
-    if t.dtype != torch.float32 or t.dim() != 2 or t.size(1) != width:
-        raise ValueError(f"'{name}' must be a float32 [n, {width}] tensor (got {t.dtype} "
-                         f"{tuple(t.shape)})")
-    return t.contiguous()
-
-
 def gatv2_forward(rowptr: Tensor, col: Tensor, x_l: Tensor, x_r: Tensor, att: Tensor, H: int,
                   C: int, slope: float, *, hub=None, aggregate: bool = True):
     """``(alpha [nnz, H] in slot order, out [n_rows, H * C] | None)`` of one GATv2 attention step
@@ -1124,23 +1148,22 @@ def gatv2_forward(rowptr: Tensor, col: Tensor, x_l: Tensor, x_r: Tensor, att: Te
     _require_device(rowptr, col, x_l, x_r, att)
     lib = _lib.load()
     W = H * C
-    x_l, x_r = _gatv2_rows(x_l, 'x_l', W), _gatv2_rows(x_r, 'x_r', W)
+    x_l, x_r = _dense_rows(x_l, 'x_l', W), _dense_rows(x_r, 'x_r', W)
     att = att.reshape(-1).contiguous()
     n_rows = rowptr.numel() - 1
     if att.numel() != W or x_r.size(0) < n_rows:
         raise ValueError(f"'att' needs {W} entries and 'x_r' at least {n_rows} rows")
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    g = _csr(rowptr, col, n_rows, hub)
     alpha = torch.empty(col.numel(), H, dtype=torch.float32, device=x_l.device)
     out = torch.empty(n_rows, W, dtype=torch.float32, device=x_l.device) if aggregate else None
     if col.numel() == 0:  # no edges: every row is empty
         return alpha, (out.zero_() if aggregate else None)
-    ws, ws_bytes = _gatv2_workspace(lib, n_chunks, H, C, x_l.device, n_chunks > 0)
+    ws, ws_bytes = _workspace(lib.pygamd_gatv2_workspace_bytes, (g.n_chunks, H, C), x_l.device,
+                              g.n_chunks > 0)
     with _timed({'kind': 'gatv2', 'op': 'forward' if aggregate else 'score', 'n_rows': n_rows,
-                 'E': col.numel(), 'H': H, 'C': C, 'n_hub': n_hub, 'n_chunks': n_chunks}, x_l):
-        check(lib.pygamd_gatv2_forward(_p(rowptr), _p(col), _idx_dtype(rowptr), _p(x_l), _p(x_r),
-                                       _p(att), n_rows, x_l.size(0), H, C, float(slope),
-                                       _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD,
-                                       HUB_CHUNK, _p(alpha), _p(out), _p(ws), ws_bytes,
+                 'E': col.numel(), 'H': H, 'C': C, 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x_l):
+        check(lib.pygamd_gatv2_forward(ctypes.byref(g), _p(x_l), _p(x_r), _p(att), x_l.size(0), H,
+                                       C, float(slope), _p(alpha), _p(out), _p(ws), ws_bytes,
                                        _stream(x_l)), 'gatv2_forward')
     return alpha, out
 
@@ -1154,14 +1177,14 @@ def gatv2_backward_dst(rowptr: Tensor, col: Tensor, x_l: Tensor, x_r: Tensor, at
     _require_device(rowptr, col, x_l, x_r, att, alpha, grad_out, out, grad_alpha)
     lib = _lib.load()
     W = H * C
-    x_l, x_r = _gatv2_rows(x_l, 'x_l', W), _gatv2_rows(x_r, 'x_r', W)
+    x_l, x_r = _dense_rows(x_l, 'x_l', W), _dense_rows(x_r, 'x_r', W)
     att, alpha = att.reshape(-1).contiguous(), alpha.contiguous()
     n_rows = rowptr.numel() - 1
     if grad_alpha is None:
-        grad_out, out = _gatv2_rows(grad_out, 'grad_out', W), _gatv2_rows(out, 'out', W)
+        grad_out, out = _dense_rows(grad_out, 'grad_out', W), _dense_rows(out, 'out', W)
     else:
         grad_alpha = grad_alpha.contiguous()
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    g = _csr(rowptr, col, n_rows, hub)
     grad_s = torch.empty_like(alpha)
     # (destinations may be a prefix of the rows of x_r: the rest takes no gradient)
     alloc = torch.empty if x_r.size(0) == n_rows else torch.zeros
@@ -1169,14 +1192,13 @@ def gatv2_backward_dst(rowptr: Tensor, col: Tensor, x_l: Tensor, x_r: Tensor, at
     grad_att = torch.empty(W, dtype=torch.float32, device=x_l.device)
     if col.numel() == 0:
         return grad_s, grad_x_r.zero_(), grad_att.zero_()
-    ws, ws_bytes = _gatv2_workspace(lib, n_chunks, H, C, x_l.device, True)
+    ws, ws_bytes = _workspace(lib.pygamd_gatv2_workspace_bytes, (g.n_chunks, H, C), x_l.device)
     with _timed({'kind': 'gatv2', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(),
-                 'H': H, 'C': C, 'n_hub': n_hub, 'score': grad_alpha is not None}, x_l):
+                 'H': H, 'C': C, 'n_hub': g.n_hub, 'score': grad_alpha is not None}, x_l):
         check(lib.pygamd_gatv2_backward_dst(
-            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(x_l), _p(x_r), _p(att), _p(alpha),
-            _p(grad_out), _p(out), _p(grad_alpha), n_rows, x_l.size(0), H, C, float(slope),
-            _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_s),
-            _p(grad_x_r), _p(grad_att), _p(ws), ws_bytes, _stream(x_l)), 'gatv2_backward_dst')
+            ctypes.byref(g), _p(x_l), _p(x_r), _p(att), _p(alpha), _p(grad_out), _p(out),
+            _p(grad_alpha), x_l.size(0), H, C, float(slope), _p(grad_s), _p(grad_x_r),
+            _p(grad_att), _p(ws), ws_bytes, _stream(x_l)), 'gatv2_backward_dst')
     return grad_s, grad_x_r, grad_att
 
 
@@ -1188,25 +1210,26 @@ def gatv2_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, x_l: T
     _require_device(rowptr_t, col_t, slot_map, x_l, x_r, att, alpha, grad_s, grad_out)
     lib = _lib.load()
     W = H * C
-    x_l, x_r = _gatv2_rows(x_l, 'x_l', W), _gatv2_rows(x_r, 'x_r', W)
+    x_l, x_r = _dense_rows(x_l, 'x_l', W), _dense_rows(x_r, 'x_r', W)
     att, alpha, grad_s = att.reshape(-1).contiguous(), alpha.contiguous(), grad_s.contiguous()
     if grad_out is not None:
-        grad_out = _gatv2_rows(grad_out, 'grad_out', W)
+        grad_out = _dense_rows(grad_out, 'grad_out', W)
     n_src = rowptr_t.numel() - 1
     if x_l.size(0) != n_src or slot_map.dtype != rowptr_t.dtype:
         raise ValueError("'x_l' must have one row per source and 'slot_map' the index dtype")
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    slot_map = slot_map.contiguous()
+    g = _csr(rowptr_t, col_t, n_src, hub)
     grad_x_l = torch.empty(n_src, W, dtype=torch.float32, device=x_l.device)
     if col_t.numel() == 0:
         return grad_x_l.zero_()
-    ws, ws_bytes = _gatv2_workspace(lib, n_chunks, H, C, x_l.device, n_chunks > 0)
+    ws, ws_bytes = _workspace(lib.pygamd_gatv2_workspace_bytes, (g.n_chunks, H, C), x_l.device,
+                              g.n_chunks > 0)
     with _timed({'kind': 'gatv2', 'op': 'backward_src', 'n_rows': n_src, 'E': col_t.numel(),
-                 'H': H, 'C': C, 'n_hub': n_hub, 'score': grad_out is None}, x_l):
+                 'H': H, 'C': C, 'n_hub': g.n_hub, 'score': grad_out is None}, x_l):
         check(lib.pygamd_gatv2_backward_src(
-            _p(rowptr_t), _p(col_t), _p(slot_map.contiguous()), _idx_dtype(rowptr_t), _p(x_l),
-            _p(x_r), _p(att), _p(alpha), _p(grad_s), _p(grad_out), n_src, n_dst, H, C,
-            float(slope), _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK,
-            _p(grad_x_l), _p(ws), ws_bytes, _stream(x_l)), 'gatv2_backward_src')
+            ctypes.byref(g), _p(slot_map), _p(x_l), _p(x_r), _p(att), _p(alpha), _p(grad_s),
+            _p(grad_out), n_dst, H, C, float(slope), _p(grad_x_l), _p(ws), ws_bytes,
+            _stream(x_l)), 'gatv2_backward_src')
     return grad_x_l
 
 
@@ -1214,23 +1237,6 @@ def gatv2_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, x_l: T
 def transformer_supported(H: int, C: int) -> bool:
     """The one-pass kernels serve this head layout (H * C <= 512, H <= 64)."""
     return bool(_lib.load().pygamd_transformer_supported(int(H), int(C)))
-
-
-def _transformer_workspace(lib, n_chunks: int, H: int, C: int, device):
-    nbytes = ctypes.c_size_t(0)
-    check(lib.pygamd_transformer_workspace_bytes(n_chunks, H, C, ctypes.byref(nbytes)))
-    if nbytes.value == 0:
-        return None, 0
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
-
-
-def _strided_rows(t: Tensor, name: str, width: int) -> Tensor:
-    """``[n, width]`` float32 rows with unit column stride: a contiguous tensor or a column block
-    of a wider one (the halves of a packed key | value projection) is taken in place."""
-    if t.dtype != torch.float32 or t.dim() != 2 or t.size(1) != width:
-        raise ValueError(f"'{name}' must be a float32 [n, {width}] tensor (got {t.dtype} "
-                         f"{tuple(t.shape)})")
-    return t.contiguous() if t.stride(1) != 1 or t.stride(0) < width else t
 
 
 def _key_value(key: Tensor, value: Optional[Tensor], W: int):
@@ -1255,26 +1261,24 @@ def transformer_forward(rowptr: Tensor, col: Tensor, query: Tensor, key: Tensor,
     _require_device(rowptr, col, query, key, value)
     lib = _lib.load()
     W = H * C
-    query = _gatv2_rows(query, 'query', W)
+    query = _dense_rows(query, 'query', W)
     key, value, ld = _key_value(key, value if aggregate else None, W)
     n_rows = rowptr.numel() - 1
     if query.size(0) < n_rows:
         raise ValueError(f"'query' needs at least {n_rows} rows")
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    g = _csr(rowptr, col, n_rows, hub)
     alpha = torch.empty(col.numel(), H, dtype=torch.float32, device=query.device)
     out = torch.empty(n_rows, W, dtype=torch.float32, device=query.device) if aggregate else None
     if col.numel() == 0:  # no edges: every row is empty
         return alpha, (out.zero_() if aggregate else None)
-    ws, ws_bytes = (_transformer_workspace(lib, n_chunks, H, C, query.device) if n_chunks > 0
-                    else (None, 0))
+    ws, ws_bytes = _workspace(lib.pygamd_transformer_workspace_bytes, (g.n_chunks, H, C),
+                              query.device, g.n_chunks > 0)
     with _timed({'kind': 'transformer', 'op': 'forward' if aggregate else 'score',
-                 'n_rows': n_rows, 'E': col.numel(), 'H': H, 'C': C, 'ld': ld, 'n_hub': n_hub,
-                 'n_chunks': n_chunks}, query):
+                 'n_rows': n_rows, 'E': col.numel(), 'H': H, 'C': C, 'ld': ld, 'n_hub': g.n_hub,
+                 'n_chunks': g.n_chunks}, query):
         check(lib.pygamd_transformer_forward(
-            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(query), _p(key), _p(value), ld, n_rows,
-            key.size(0), H, C, float(scale), _p(h_rows), _p(h_cptr), n_hub, n_chunks,
-            HUB_THRESHOLD, HUB_CHUNK, _p(alpha), _p(out), _p(ws), ws_bytes, _stream(query)),
-            'transformer_forward')
+            ctypes.byref(g), _p(query), _p(key), _p(value), ld, key.size(0), H, C, float(scale),
+            _p(alpha), _p(out), _p(ws), ws_bytes, _stream(query)), 'transformer_forward')
     return alpha, out
 
 
@@ -1295,23 +1299,23 @@ def transformer_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, key: Te
     if score:
         grad_alpha = grad_alpha.contiguous()
     else:
-        grad_out, out = _gatv2_rows(grad_out, 'grad_out', W), _gatv2_rows(out, 'out', W)
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+        grad_out, out = _dense_rows(grad_out, 'grad_out', W), _dense_rows(out, 'out', W)
+    g = _csr(rowptr, col, n_rows, hub)
     grad_s = torch.empty_like(alpha)
     # (destinations may be a prefix of the rows of query: the rest takes no gradient)
     alloc = torch.empty if query.size(0) == n_rows else torch.zeros
     grad_query = alloc(query.size(0), W, dtype=torch.float32, device=key.device)
     if col.numel() == 0:
         return grad_s, grad_query.zero_()
-    ws, ws_bytes = _transformer_workspace(lib, n_chunks, H, C, key.device)
+    ws, ws_bytes = _workspace(lib.pygamd_transformer_workspace_bytes, (g.n_chunks, H, C),
+                              key.device)
     with _timed({'kind': 'transformer', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(),
-                 'H': H, 'C': C, 'ld': ld, 'n_hub': n_hub, 'n_chunks': n_chunks,
+                 'H': H, 'C': C, 'ld': ld, 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
                  'score': score}, key):
         check(lib.pygamd_transformer_backward_dst(
-            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(key), _p(value), ld, _p(alpha),
-            _p(grad_out), _p(out), _p(grad_alpha), n_rows, key.size(0), H, C, float(scale),
-            _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_s),
-            _p(grad_query), _p(ws), ws_bytes, _stream(key)), 'transformer_backward_dst')
+            ctypes.byref(g), _p(key), _p(value), ld, _p(alpha), _p(grad_out), _p(out),
+            _p(grad_alpha), key.size(0), H, C, float(scale), _p(grad_s), _p(grad_query), _p(ws),
+            ws_bytes, _stream(key)), 'transformer_backward_dst')
     return grad_s, grad_query
 
 
@@ -1327,15 +1331,16 @@ def transformer_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, 
     _require_device(rowptr_t, col_t, slot_map, query, alpha, grad_s, grad_out)
     lib = _lib.load()
     W = H * C
-    query = _gatv2_rows(query, 'query', W)
+    query = _dense_rows(query, 'query', W)
     alpha, grad_s = alpha.contiguous(), grad_s.contiguous()
     score = grad_out is None
     if not score:
-        grad_out = _gatv2_rows(grad_out, 'grad_out', W)
+        grad_out = _dense_rows(grad_out, 'grad_out', W)
     n_src = rowptr_t.numel() - 1
     if slot_map.dtype != rowptr_t.dtype:
         raise ValueError("'slot_map' must have the index dtype")
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    slot_map = slot_map.contiguous()
+    g = _csr(rowptr_t, col_t, n_src, hub)
     if packed and score:
         raise ValueError('the score mode has no value gradient to pack')
     if packed:
@@ -1352,16 +1357,15 @@ def transformer_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, 
             if t is not None:
                 t.zero_()
         return result
-    ws, ws_bytes = (_transformer_workspace(lib, n_chunks, H, C, query.device) if n_chunks > 0
-                    else (None, 0))
+    ws, ws_bytes = _workspace(lib.pygamd_transformer_workspace_bytes, (g.n_chunks, H, C),
+                              query.device, g.n_chunks > 0)
     with _timed({'kind': 'transformer', 'op': 'backward_src', 'n_rows': n_src,
-                 'E': col_t.numel(), 'H': H, 'C': C, 'ld': ld, 'n_hub': n_hub,
-                 'n_chunks': n_chunks, 'score': score}, query):
+                 'E': col_t.numel(), 'H': H, 'C': C, 'ld': ld, 'n_hub': g.n_hub,
+                 'n_chunks': g.n_chunks, 'score': score}, query):
         check(lib.pygamd_transformer_backward_src(
-            _p(rowptr_t), _p(col_t), _p(slot_map.contiguous()), _idx_dtype(rowptr_t), _p(query),
-            _p(alpha), _p(grad_s), _p(grad_out), n_src, n_dst, H, C, float(scale), _p(h_rows),
-            _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_key), _p(grad_value),
-            ld, _p(ws), ws_bytes, _stream(query)), 'transformer_backward_src')
+            ctypes.byref(g), _p(slot_map), _p(query), _p(alpha), _p(grad_s), _p(grad_out), n_dst,
+            H, C, float(scale), _p(grad_key), _p(grad_value), ld, _p(ws), ws_bytes,
+            _stream(query)), 'transformer_backward_src')
     return result
 
 
@@ -1370,14 +1374,6 @@ def transformer_edge_supported(H: int, C: int, De: int) -> bool:
     """The edge variant serves this layout: that of :func:`transformer_supported` and ``De <= 4 *
     lph``, ``lph`` the largest power of two with ``H * lph <= 64``."""
     return bool(_lib.load().pygamd_transformer_edge_supported(int(H), int(C), int(De)))
-
-
-def _transformer_edge_workspace(lib, n_chunks: int, H: int, C: int, De: int, device):
-    nbytes = ctypes.c_size_t(0)
-    check(lib.pygamd_transformer_edge_workspace_bytes(n_chunks, H, C, De, ctypes.byref(nbytes)))
-    if nbytes.value == 0:
-        return None, 0
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
 
 
 def transformer_edge_forward(rowptr: Tensor, col: Tensor, query: Tensor, key: Tensor,
@@ -1391,7 +1387,7 @@ def transformer_edge_forward(rowptr: Tensor, col: Tensor, query: Tensor, key: Te
     _require_device(rowptr, col, query, key, value, edge_attr, bias)
     lib = _lib.load()
     W = H * C
-    query = _gatv2_rows(query, 'query', W)
+    query = _dense_rows(query, 'query', W)
     key, value, ld = _key_value(key, value if aggregate else None, W)
     n_rows = rowptr.numel() - 1
     if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 \
@@ -1399,26 +1395,25 @@ def transformer_edge_forward(rowptr: Tensor, col: Tensor, query: Tensor, key: Te
         raise ValueError(f"'edge_attr' must be a float32 [{col.numel()}, De] tensor (got "
                          f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
     De = edge_attr.size(1)
-    edge_attr, bias = edge_attr.contiguous(), _gatv2_rows(bias, 'bias', H * De)
+    edge_attr, bias = edge_attr.contiguous(), _dense_rows(bias, 'bias', H * De)
     if query.size(0) < n_rows or bias.size(0) < n_rows:
         raise ValueError(f"'query' and 'bias' need at least {n_rows} rows")
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+    g = _csr(rowptr, col, n_rows, hub)
     alpha = torch.empty(col.numel(), H, dtype=torch.float32, device=query.device)
     out = torch.empty(n_rows, W, dtype=torch.float32, device=query.device) if aggregate else None
     z = torch.empty(n_rows, H * De, dtype=torch.float32, device=query.device) \
         if aggregate else None
     if col.numel() == 0:  # no edges: every row is empty
         return alpha, (out.zero_() if aggregate else None), (z.zero_() if aggregate else None)
-    ws, ws_bytes = (_transformer_edge_workspace(lib, n_chunks, H, C, De, query.device)
-                    if n_chunks > 0 else (None, 0))
+    ws, ws_bytes = _workspace(lib.pygamd_transformer_edge_workspace_bytes,
+                              (g.n_chunks, H, C, De), query.device, g.n_chunks > 0)
     with _timed({'kind': 'transformer', 'op': 'edge_forward' if aggregate else 'edge_score',
                  'n_rows': n_rows, 'E': col.numel(), 'H': H, 'C': C, 'De': De, 'ld': ld,
-                 'n_hub': n_hub, 'n_chunks': n_chunks}, query):
+                 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, query):
         check(lib.pygamd_transformer_edge_forward(
-            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(query), _p(key), _p(value), ld,
-            _p(edge_attr), _p(bias), n_rows, key.size(0), H, C, De, float(scale), _p(h_rows),
-            _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(alpha), _p(out), _p(z),
-            _p(ws), ws_bytes, _stream(query)), 'transformer_edge_forward')
+            ctypes.byref(g), _p(query), _p(key), _p(value), ld, _p(edge_attr), _p(bias),
+            key.size(0), H, C, De, float(scale), _p(alpha), _p(out), _p(z), _p(ws), ws_bytes,
+            _stream(query)), 'transformer_edge_forward')
     return alpha, out, z
 
 
@@ -1442,14 +1437,14 @@ def transformer_edge_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, ke
     score = grad_alpha is not None
     key, value, ld = _key_value(key, None if score else value, W)
     alpha, edge_attr = alpha.contiguous(), edge_attr.contiguous()
-    bias = _gatv2_rows(bias, 'bias', Z)
+    bias = _dense_rows(bias, 'bias', Z)
     n_rows = rowptr.numel() - 1
     if score:
         grad_alpha = grad_alpha.contiguous()
     else:
-        grad_out, out = _gatv2_rows(grad_out, 'grad_out', W), _gatv2_rows(out, 'out', W)
-        grad_z, z = _gatv2_rows(grad_z, 'grad_z', Z), _gatv2_rows(z, 'z', Z)
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+        grad_out, out = _dense_rows(grad_out, 'grad_out', W), _dense_rows(out, 'out', W)
+        grad_z, z = _dense_rows(grad_z, 'grad_z', Z), _dense_rows(z, 'z', Z)
+    g = _csr(rowptr, col, n_rows, hub)
     grad_s = torch.empty_like(alpha)
     # (destinations may be a prefix of the rows of query and bias: the rest takes no gradient)
     dev = key.device
@@ -1460,17 +1455,17 @@ def transformer_edge_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, ke
     grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
     if col.numel() == 0:
         return grad_s, grad_query.zero_(), grad_bias.zero_(), grad_edge
-    ws, ws_bytes = _transformer_edge_workspace(lib, n_chunks, H, C, De, dev)
+    ws, ws_bytes = _workspace(lib.pygamd_transformer_edge_workspace_bytes,
+                              (g.n_chunks, H, C, De), dev)
     with _timed({'kind': 'transformer', 'op': 'edge_backward_dst', 'n_rows': n_rows,
-                 'E': col.numel(), 'H': H, 'C': C, 'De': De, 'ld': ld, 'n_hub': n_hub,
-                 'n_chunks': n_chunks, 'score': score,
+                 'E': col.numel(), 'H': H, 'C': C, 'De': De, 'ld': ld, 'n_hub': g.n_hub,
+                 'n_chunks': g.n_chunks, 'score': score,
                  'grad_edge_attr': want_grad_edge_attr}, key):
         check(lib.pygamd_transformer_edge_backward_dst(
-            _p(rowptr), _p(col), _idx_dtype(rowptr), _p(key), _p(value), ld, _p(edge_attr),
-            _p(bias), _p(alpha), _p(grad_out), _p(out), _p(grad_z), _p(z), _p(grad_alpha), n_rows,
-            key.size(0), H, C, De, float(scale), _p(h_rows), _p(h_cptr), n_hub, n_chunks,
-            HUB_THRESHOLD, HUB_CHUNK, _p(grad_s), _p(grad_query), _p(grad_bias), _p(grad_edge),
-            _p(ws), ws_bytes, _stream(key)), 'transformer_edge_backward_dst')
+            ctypes.byref(g), _p(key), _p(value), ld, _p(edge_attr), _p(bias), _p(alpha),
+            _p(grad_out), _p(out), _p(grad_z), _p(z), _p(grad_alpha), key.size(0), H, C, De,
+            float(scale), _p(grad_s), _p(grad_query), _p(grad_bias), _p(grad_edge), _p(ws),
+            ws_bytes, _stream(key)), 'transformer_edge_backward_dst')
     return grad_s, grad_query, grad_bias, grad_edge
 
 
@@ -1479,14 +1474,6 @@ def gine_supported(F: int, De: int = 0) -> bool:
     """The kernel pair serves ``F <= 512`` and, in linear mode (``De >= 1``), ``De <= 32`` and
     ``F * De <= 4096``; ``De = 0`` is the wide mode."""
     return bool(_lib.load().pygamd_gine_supported(int(F), int(De)))
-
-
-def _gine_workspace(lib, n_chunks: int, F: int, De: int, device):
-    nbytes = ctypes.c_size_t(0)
-    check(lib.pygamd_gine_workspace_bytes(n_chunks, F, De, ctypes.byref(nbytes)))
-    if nbytes.value == 0:
-        return None, 0
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
 
 
 def _gine_edge(edge_attr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], F: int,
@@ -1545,22 +1532,21 @@ def gine_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], x_src: 
         if edge_id.dtype != rowptr.dtype or edge_id.numel() != col.numel():
             raise ValueError("'edge_id' must have the index dtype and one entry per slot")
         edge_id = edge_id.contiguous()
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
     out = torch.empty(n_rows, F, dtype=torch.float32, device=x_src.device)
     if n_rows == 0:
         return out
     if col.numel() == 0:  # no edges: every row is its self term; the launch reads no slot
         col, edge_id, edge_attr = _gine_no_edges(rowptr, x_src)
-    ws, ws_bytes = (_gine_workspace(lib, n_chunks, F, De, x_src.device) if n_chunks > 0
-                    else (None, 0))
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_gine_workspace_bytes, (g.n_chunks, F, De), x_src.device,
+                              g.n_chunks > 0)
     with _timed({'kind': 'gine', 'op': 'forward', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
-                 'De': De, 'ld': _ld(x_src), 'n_hub': n_hub, 'n_chunks': n_chunks,
+                 'De': De, 'ld': _ld(x_src), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
                  'grad_edge_attr': False}, x_src):
         check(lib.pygamd_gine_forward(
-            _p(rowptr), _p(col), _p(edge_id), _idx_dtype(rowptr), _p(x_src), _ld(x_src),
-            _p(x_root), 0 if x_root is None else _ld(x_root), _p(eps), _p(edge_attr), _p(weight),
-            _p(bias), n_rows, x_src.size(0), F, De, _p(h_rows), _p(h_cptr), n_hub, n_chunks,
-            HUB_THRESHOLD, HUB_CHUNK, _p(out), _p(ws), ws_bytes, _stream(x_src)), 'gine_forward')
+            ctypes.byref(g), _p(edge_id), _p(x_src), _ld(x_src), _p(x_root),
+            0 if x_root is None else _ld(x_root), _p(eps), _p(edge_attr), _p(weight), _p(bias),
+            x_src.size(0), F, De, _p(out), _p(ws), ws_bytes, _stream(x_src)), 'gine_forward')
     return out
 
 
@@ -1574,7 +1560,7 @@ def gine_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], 
     lib = _lib.load()
     F = x_src.size(1)
     x_src = _strided_rows(x_src, 'x_src', F)
-    grad_out = _gatv2_rows(grad_out, 'grad_out', F)
+    grad_out = _dense_rows(grad_out, 'grad_out', F)
     n_src = rowptr_t.numel() - 1
     if x_src.size(0) != n_src:
         raise ValueError(f"'x_src' needs {n_src} rows")
@@ -1583,7 +1569,6 @@ def gine_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], 
         if edge_id_t.dtype != rowptr_t.dtype or edge_id_t.numel() != col_t.numel():
             raise ValueError("'edge_id_t' must have the index dtype and one entry per slot")
         edge_id_t = edge_id_t.contiguous()
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
     dev = x_src.device
     grad_x = torch.empty(n_src, F, dtype=torch.float32, device=dev)
     grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
@@ -1596,17 +1581,16 @@ def gine_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], 
         return grad_x, grad_edge, grad_w, grad_b
     if col_t.numel() == 0:
         col_t, edge_id_t, edge_attr = _gine_no_edges(rowptr_t, x_src)
-    ws, ws_bytes = (_gine_workspace(lib, n_chunks, F, De, dev) if n_chunks > 0 or De > 0
-                    else (None, 0))
+    g = _csr(rowptr_t, col_t, n_src, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_gine_workspace_bytes, (g.n_chunks, F, De), dev,
+                              g.n_chunks > 0 or De > 0)
     with _timed({'kind': 'gine', 'op': 'backward', 'n_rows': n_src, 'E': col_t.numel(), 'F': F,
-                 'De': De, 'ld': _ld(x_src), 'n_hub': n_hub, 'n_chunks': n_chunks,
+                 'De': De, 'ld': _ld(x_src), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
                  'grad_edge_attr': bool(want_grad_edge_attr)}, x_src):
         check(lib.pygamd_gine_backward(
-            _p(rowptr_t), _p(col_t), _p(edge_id_t), _idx_dtype(rowptr_t), _p(x_src), _ld(x_src),
-            _p(edge_attr), _p(weight), _p(bias), _p(grad_out), n_src, grad_out.size(0), F, De,
-            _p(h_rows), _p(h_cptr), n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, _p(grad_x),
-            _p(grad_edge), _p(grad_w), _p(grad_b), _p(ws), ws_bytes, _stream(x_src)),
-            'gine_backward')
+            ctypes.byref(g), _p(edge_id_t), _p(x_src), _ld(x_src), _p(edge_attr), _p(weight),
+            _p(bias), _p(grad_out), grad_out.size(0), F, De, _p(grad_x), _p(grad_edge), _p(grad_w),
+            _p(grad_b), _p(ws), ws_bytes, _stream(x_src)), 'gine_backward')
     return grad_x, grad_edge, grad_w, grad_b
 
 

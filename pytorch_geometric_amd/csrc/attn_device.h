@@ -1,6 +1,7 @@
 // attn_device.h — what the one-pass attention kernels share (gatv2.hip, transformer.hip): the
 // lanes-per-head layout, the work items of a launch with the hub plan's chunks, the in-order merges
-// of the chunks of a long row and the host-side choice of the lane shape.
+// of the chunks of a long row and, on the host, the choice of the lane shape and the checks and
+// typed view of the entry points' handle (pygamd_csr).  gine.hip uses the items and the host part.
 //
 // Lane layout (wave64, one wave per row or per chunk of a long row): `lph` lanes per head, a power
 // of two with H * lph <= 64; lane l serves head l / lph and the channels sub + lph * r (scalar) or
@@ -312,18 +313,33 @@ inline bool choose_shape_edge(int64_t H, int64_t C, int64_t De, bool aligned, Sh
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// the checks every entry point shares; 0 = go on
-inline int check_args(int idx_dtype, int64_t n_rows, int64_t n_other, int64_t H, int64_t C,
-                      const void* hub_rows, const void* hub_cptr, int64_t n_hub,
-                      int64_t n_chunks, int64_t threshold, int64_t chunk) {
-  if (idx_dtype != PYGAMD_IDX_I64 && idx_dtype != PYGAMD_IDX_I32) return PYGAMD_ERR_INVALID_ARG;
-  if (n_rows < 0 || n_other < 0 || H < 1 || C < 1 || n_hub < 0 || n_chunks < 0)
+// the checks every entry point shares on its handle `g`, the row count of the other side and the
+// head layout; 0 = go on
+inline int check_args(const pygamd_csr* g, int64_t n_other, int64_t H, int64_t C) {
+  if (!g) return PYGAMD_ERR_INVALID_ARG;
+  if (g->idx_dtype != PYGAMD_IDX_I64 && g->idx_dtype != PYGAMD_IDX_I32)
     return PYGAMD_ERR_INVALID_ARG;
-  if (n_hub > 0 && (!hub_rows || !hub_cptr || n_chunks < n_hub || threshold < 1 || chunk < 1))
+  if (g->n_rows < 0 || n_other < 0 || H < 1 || C < 1 || g->n_hub < 0 || g->n_chunks < 0)
     return PYGAMD_ERR_INVALID_ARG;
-  if (n_hub == 0 && n_chunks != 0) return PYGAMD_ERR_INVALID_ARG;
+  if (g->n_hub > 0 && (!g->hub_rows || !g->hub_chunk_ptr || g->n_chunks < g->n_hub ||
+                       g->hub_threshold < 1 || g->hub_chunk < 1))
+    return PYGAMD_ERR_INVALID_ARG;
+  if (g->n_hub == 0 && g->n_chunks != 0) return PYGAMD_ERR_INVALID_ARG;
   if (H * C > kAttnMaxWidth || H > kAttnMaxHeads) return PYGAMD_ERR_UNSUPPORTED;
   return PYGAMD_OK;
+}
+
+// the work items of a launch over the handle, and its column array, at the handle's index type
+template <typename IdxT>
+inline Items<IdxT> make_items(const pygamd_csr& g) {
+  return Items<IdxT>{static_cast<const IdxT*>(g.rowptr), static_cast<const IdxT*>(g.hub_rows),
+                     static_cast<const IdxT*>(g.hub_chunk_ptr), g.n_rows, g.n_hub, g.n_chunks,
+                     g.hub_threshold, g.hub_chunk};
+}
+
+template <typename IdxT>
+inline const IdxT* typed_col(const pygamd_csr& g) {
+  return static_cast<const IdxT*>(g.col);
 }
 
 }  // namespace attn

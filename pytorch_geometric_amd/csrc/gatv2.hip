@@ -288,14 +288,6 @@ size_t gv2_ws_bytes(int64_t n_chunks, int64_t H, int64_t C) {
   return sizeof(float) * static_cast<size_t>(n_chunks * (W + 2 * H) + kGv2MaxBlocks * W);
 }
 
-// the checks every entry point shares; 0 = go on
-int gv2_check(int idx_dtype, int64_t n_rows, int64_t n_other, int64_t H, int64_t C,
-              const void* hub_rows, const void* hub_cptr, int64_t n_hub, int64_t n_chunks,
-              int64_t threshold, int64_t chunk) {
-  return check_args(idx_dtype, n_rows, n_other, H, C, hub_rows, hub_cptr, n_hub, n_chunks,
-                    threshold, chunk);
-}
-
 }  // namespace
 }  // namespace pygamd
 
@@ -315,17 +307,14 @@ int pygamd_gatv2_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C, size_t*
   return PYGAMD_OK;
 }
 
-int pygamd_gatv2_forward(const void* rowptr, const void* col, int idx_dtype, const float* x_l,
-                         const float* x_r, const float* att, int64_t n_rows, int64_t n_src,
-                         int64_t H, int64_t C, float slope, const void* hub_rows,
-                         const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
-                         int64_t hub_threshold, int64_t hub_chunk, float* alpha, float* out,
+int pygamd_gatv2_forward(const pygamd_csr* g, const float* x_l, const float* x_r, const float* att,
+                         int64_t n_src, int64_t H, int64_t C, float slope, float* alpha, float* out,
                          void* workspace, size_t workspace_bytes, void* stream) {
-  const int rc = gv2_check(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                           n_chunks, hub_threshold, hub_chunk);
+  const int rc = check_args(g, n_src, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (n_rows == 0) return PYGAMD_OK;
-  if (!rowptr || !col || !x_l || !x_r || !att || !alpha) return PYGAMD_ERR_INVALID_ARG;
+  if (!g->rowptr || !g->col || !x_l || !x_r || !att || !alpha) return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < gv2_ws_bytes(n_chunks, H, C)))
     return PYGAMD_ERR_WORKSPACE;
   Shape sh;
@@ -334,12 +323,10 @@ int pygamd_gatv2_forward(const void* rowptr, const void* col, int idx_dtype, con
   if (!choose_shape(H, C, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col);
+    const IdxT* c = typed_col<IdxT>(*g);
     GV2_DISPATCH_SHAPE(sh, {
       if (out) {
         hipLaunchKernelGGL((gatv2_fwd_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it, c,
@@ -362,18 +349,15 @@ int pygamd_gatv2_forward(const void* rowptr, const void* col, int idx_dtype, con
   });
 }
 
-int pygamd_gatv2_backward_dst(const void* rowptr, const void* col, int idx_dtype,
-                              const float* x_l, const float* x_r, const float* att,
-                              const float* alpha, const float* grad_out, const float* out,
-                              const float* grad_alpha, int64_t n_rows, int64_t n_src, int64_t H,
-                              int64_t C, float slope, const void* hub_rows,
-                              const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
-                              int64_t hub_threshold, int64_t hub_chunk, float* grad_s,
-                              float* grad_x_r, float* grad_att, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-  const int rc = gv2_check(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                           n_chunks, hub_threshold, hub_chunk);
+int pygamd_gatv2_backward_dst(const pygamd_csr* g, const float* x_l, const float* x_r,
+                              const float* att, const float* alpha, const float* grad_out,
+                              const float* out, const float* grad_alpha, int64_t n_src, int64_t H,
+                              int64_t C, float slope, float* grad_s, float* grad_x_r,
+                              float* grad_att, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  const int rc = check_args(g, n_src, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (!grad_att) return PYGAMD_ERR_INVALID_ARG;
   // exactly one of (grad_out, out) and grad_alpha says where d alpha comes from
   const bool score = grad_alpha != nullptr;
@@ -384,7 +368,7 @@ int pygamd_gatv2_backward_dst(const void* rowptr, const void* col, int idx_dtype
     PYGAMD_HIP_CHECK(hipMemsetAsync(grad_att, 0, sizeof(float) * W, st));
     return PYGAMD_OK;
   }
-  if (!rowptr || !col || !x_l || !x_r || !att || !alpha || !grad_s || !grad_x_r)
+  if (!g->rowptr || !g->col || !x_l || !x_r || !att || !alpha || !grad_s || !grad_x_r)
     return PYGAMD_ERR_INVALID_ARG;
   if (!workspace || workspace_bytes < gv2_ws_bytes(n_chunks, H, C)) return PYGAMD_ERR_WORKSPACE;
   Shape sh;
@@ -396,12 +380,10 @@ int pygamd_gatv2_backward_dst(const void* rowptr, const void* col, int idx_dtype
   const int64_t n_items = n_rows + n_chunks;
   int64_t blocks = wave_grid(n_items);
   if (blocks > kGv2MaxBlocks) blocks = kGv2MaxBlocks;
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col);
+    const IdxT* c = typed_col<IdxT>(*g);
     GV2_DISPATCH_SHAPE(sh, {
       if (score) {
         hipLaunchKernelGGL((gatv2_bwd_dst_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it,
@@ -428,19 +410,16 @@ int pygamd_gatv2_backward_dst(const void* rowptr, const void* col, int idx_dtype
   });
 }
 
-int pygamd_gatv2_backward_src(const void* rowptr_t, const void* col_t, const void* slot_map,
-                              int idx_dtype, const float* x_l, const float* x_r,
-                              const float* att, const float* alpha, const float* grad_s,
-                              const float* grad_out, int64_t n_src, int64_t n_dst, int64_t H,
-                              int64_t C, float slope, const void* hub_rows,
-                              const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
-                              int64_t hub_threshold, int64_t hub_chunk, float* grad_x_l,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-  const int rc = gv2_check(idx_dtype, n_src, n_dst, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                           n_chunks, hub_threshold, hub_chunk);
+int pygamd_gatv2_backward_src(const pygamd_csr* g, const void* slot_map, const float* x_l,
+                              const float* x_r, const float* att, const float* alpha,
+                              const float* grad_s, const float* grad_out, int64_t n_dst, int64_t H,
+                              int64_t C, float slope, float* grad_x_l, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  const int rc = check_args(g, n_dst, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_src = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (n_src == 0) return PYGAMD_OK;
-  if (!rowptr_t || !col_t || !slot_map || !x_l || !x_r || !att || !alpha || !grad_s || !grad_x_l)
+  if (!g->rowptr || !g->col || !slot_map || !x_l || !x_r || !att || !alpha || !grad_s || !grad_x_l)
     return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < gv2_ws_bytes(n_chunks, H, C)))
     return PYGAMD_ERR_WORKSPACE;
@@ -451,12 +430,10 @@ int pygamd_gatv2_backward_src(const void* rowptr_t, const void* col_t, const voi
   hipStream_t st = as_stream(stream);
   const int64_t W = H * C;
   float* part = static_cast<float*>(workspace);
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr_t), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_src, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_src + n_chunks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col_t);
+    const IdxT* c = typed_col<IdxT>(*g);
     const IdxT* sm = static_cast<const IdxT*>(slot_map);
     GV2_DISPATCH_SHAPE(sh, {
       if (!grad_out) {

@@ -374,12 +374,9 @@ size_t gine_ws_bytes(int64_t n_chunks, int64_t F, int64_t De) {
     { return PYGAMD_ERR_UNSUPPORTED; }                                               \
   } while (0)
 
-int gine_check(int idx_dtype, int64_t n_rows, int64_t n_other, int64_t F, int64_t De,
-               const void* hub_rows, const void* hub_cptr, int64_t n_hub, int64_t n_chunks,
-               int64_t threshold, int64_t chunk) {
+int gine_check(const pygamd_csr* g, int64_t n_other, int64_t F, int64_t De) {
   if (De < 0) return PYGAMD_ERR_INVALID_ARG;
-  const int rc = check_args(idx_dtype, n_rows, n_other, 1, F < 1 ? F : 1, hub_rows, hub_cptr,
-                            n_hub, n_chunks, threshold, chunk);
+  const int rc = check_args(g, n_other, 1, F < 1 ? F : 1);
   if (rc != PYGAMD_OK) return rc;
   return gine_envelope(F, De) ? PYGAMD_OK : PYGAMD_ERR_UNSUPPORTED;
 }
@@ -400,19 +397,17 @@ int pygamd_gine_workspace_bytes(int64_t n_chunks, int64_t F, int64_t De, size_t*
   return PYGAMD_OK;
 }
 
-int pygamd_gine_forward(const void* rowptr, const void* col, const void* edge_id, int idx_dtype,
-                        const float* x_src, int64_t ld_src, const float* x_root, int64_t ld_root,
-                        const float* eps, const float* edge_attr, const float* weight,
-                        const float* bias, int64_t n_rows, int64_t n_src, int64_t F, int64_t De,
-                        const void* hub_rows, const void* hub_chunk_ptr, int64_t n_hub,
-                        int64_t n_chunks, int64_t hub_threshold, int64_t hub_chunk, float* out,
-                        void* workspace, size_t workspace_bytes, void* stream) {
-  const int rc = gine_check(idx_dtype, n_rows, n_src, F, De, hub_rows, hub_chunk_ptr, n_hub,
-                            n_chunks, hub_threshold, hub_chunk);
+int pygamd_gine_forward(const pygamd_csr* g, const void* edge_id, const float* x_src,
+                        int64_t ld_src, const float* x_root, int64_t ld_root, const float* eps,
+                        const float* edge_attr, const float* weight, const float* bias,
+                        int64_t n_src, int64_t F, int64_t De, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  const int rc = gine_check(g, n_src, F, De);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld_src < F || (x_root && ld_root < F)) return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
-  if (!rowptr || !col || !x_src || !edge_attr || !out || (De > 0 && !weight) ||
+  if (!g->rowptr || !g->col || !x_src || !edge_attr || !out || (De > 0 && !weight) ||
       (De == 0 && (weight || bias)))
     return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < sizeof(float) * n_chunks * F))
@@ -426,14 +421,12 @@ int pygamd_gine_forward(const void* rowptr, const void* col, const void* edge_id
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   const GineEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(gine_grid(n_rows + n_chunks, De > 0, kGineFwdBlocks)), block(kBlock);
     GINE_DISPATCH({
       hipLaunchKernelGGL((gine_fwd_kernel<IdxT, EPL, VEC, DE>), grid, block, 0, st, it,
-                         static_cast<const IdxT*>(col), static_cast<const IdxT*>(edge_id), x_src,
+                         typed_col<IdxT>(*g), static_cast<const IdxT*>(edge_id), x_src,
                          ld_src, x_root, ld_root, eps, ed, static_cast<int>(F), sh.lph, out, part);
     });
     PYGAMD_LAUNCH_CHECK();
@@ -447,21 +440,17 @@ int pygamd_gine_forward(const void* rowptr, const void* col, const void* edge_id
   });
 }
 
-int pygamd_gine_backward(const void* rowptr_t, const void* col_t, const void* edge_id_t,
-                         int idx_dtype, const float* x_src, int64_t ld_src,
-                         const float* edge_attr, const float* weight, const float* bias,
-                         const float* grad_out, int64_t n_src, int64_t n_dst, int64_t F,
-                         int64_t De, const void* hub_rows, const void* hub_chunk_ptr,
-                         int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
-                         int64_t hub_chunk, float* grad_x_src, float* grad_edge_attr,
-                         float* grad_weight, float* grad_bias, void* workspace,
-                         size_t workspace_bytes, void* stream) {
-  const int rc = gine_check(idx_dtype, n_src, n_dst, F, De, hub_rows, hub_chunk_ptr, n_hub,
-                            n_chunks, hub_threshold, hub_chunk);
+int pygamd_gine_backward(const pygamd_csr* g, const void* edge_id_t, const float* x_src,
+                         int64_t ld_src, const float* edge_attr, const float* weight,
+                         const float* bias, const float* grad_out, int64_t n_dst, int64_t F,
+                         int64_t De, float* grad_x_src, float* grad_edge_attr, float* grad_weight,
+                         float* grad_bias, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = gine_check(g, n_dst, F, De);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_src = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld_src < F) return PYGAMD_ERR_INVALID_ARG;
   if (n_src == 0) return PYGAMD_OK;
-  if (!rowptr_t || !col_t || !x_src || !edge_attr || !grad_out || !grad_x_src ||
+  if (!g->rowptr || !g->col || !x_src || !edge_attr || !grad_out || !grad_x_src ||
       (De > 0 && (!weight || !grad_weight)) ||
       (De == 0 && (weight || bias || grad_weight || grad_bias)) || (grad_bias && !bias))
     return PYGAMD_ERR_INVALID_ARG;
@@ -478,15 +467,13 @@ int pygamd_gine_backward(const void* rowptr_t, const void* col_t, const void* ed
   float* part = static_cast<float*>(workspace);
   float* wpart = part + n_chunks * F;
   const GineEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr_t), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_src, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const unsigned n_blocks = gine_grid(n_src + n_chunks, De > 0, kGineBwdBlocks);
     const dim3 grid(n_blocks), block(kBlock);
     GINE_DISPATCH({
       hipLaunchKernelGGL((gine_bwd_kernel<IdxT, EPL, VEC, DE>), grid, block, 0, st, it,
-                         static_cast<const IdxT*>(col_t), static_cast<const IdxT*>(edge_id_t),
+                         typed_col<IdxT>(*g), static_cast<const IdxT*>(edge_id_t),
                          x_src, ld_src, ed, grad_out, static_cast<int>(F), sh.lph, grad_x_src,
                          grad_edge_attr, part, wpart);
     });

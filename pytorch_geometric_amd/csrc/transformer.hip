@@ -545,19 +545,16 @@ int pygamd_transformer_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C, s
   return PYGAMD_OK;
 }
 
-int pygamd_transformer_forward(const void* rowptr, const void* col, int idx_dtype,
-                               const float* query, const float* key, const float* value,
-                               int64_t ld, int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
-                               float scale, const void* hub_rows, const void* hub_chunk_ptr,
-                               int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
-                               int64_t hub_chunk, float* alpha, float* out, void* workspace,
+int pygamd_transformer_forward(const pygamd_csr* g, const float* query, const float* key,
+                               const float* value, int64_t ld, int64_t n_src, int64_t H, int64_t C,
+                               float scale, float* alpha, float* out, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  const int rc = check_args(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                            n_chunks, hub_threshold, hub_chunk);
+  const int rc = check_args(g, n_src, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld < H * C) return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
-  if (!rowptr || !col || !query || !key || !alpha || (out && !value))
+  if (!g->rowptr || !g->col || !query || !key || !alpha || (out && !value))
     return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < tf_ws_bytes(n_chunks, H, C)))
     return PYGAMD_ERR_WORKSPACE;
@@ -568,12 +565,10 @@ int pygamd_transformer_forward(const void* rowptr, const void* col, int idx_dtyp
   if (!choose_shape(H, C, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col);
+    const IdxT* c = typed_col<IdxT>(*g);
     ATTN_DISPATCH_SHAPE(sh, {
       if (out) {
         hipLaunchKernelGGL((transformer_fwd_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it,
@@ -602,24 +597,21 @@ int pygamd_transformer_forward(const void* rowptr, const void* col, int idx_dtyp
   });
 }
 
-int pygamd_transformer_backward_dst(const void* rowptr, const void* col, int idx_dtype,
-                                    const float* key, const float* value, int64_t ld,
-                                    const float* alpha, const float* grad_out, const float* out,
-                                    const float* grad_alpha, int64_t n_rows, int64_t n_src,
-                                    int64_t H, int64_t C, float scale, const void* hub_rows,
-                                    const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
-                                    int64_t hub_threshold, int64_t hub_chunk, float* grad_s,
+int pygamd_transformer_backward_dst(const pygamd_csr* g, const float* key, const float* value,
+                                    int64_t ld, const float* alpha, const float* grad_out,
+                                    const float* out, const float* grad_alpha, int64_t n_src,
+                                    int64_t H, int64_t C, float scale, float* grad_s,
                                     float* grad_query, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-  const int rc = check_args(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                            n_chunks, hub_threshold, hub_chunk);
+  const int rc = check_args(g, n_src, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld < H * C) return PYGAMD_ERR_INVALID_ARG;
   // exactly one of (grad_out, out) and grad_alpha says where d alpha comes from
   const bool score = grad_alpha != nullptr;
   if (score ? (grad_out || out) : (!grad_out || !out)) return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
-  if (!rowptr || !col || !key || (!score && !value) || !alpha || !grad_s || !grad_query)
+  if (!g->rowptr || !g->col || !key || (!score && !value) || !alpha || !grad_s || !grad_query)
     return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < tf_ws_bytes(n_chunks, H, C)))
     return PYGAMD_ERR_WORKSPACE;
@@ -631,12 +623,10 @@ int pygamd_transformer_backward_dst(const void* rowptr, const void* col, int idx
   hipStream_t st = as_stream(stream);
   const int64_t W = H * C;
   float* part = static_cast<float*>(workspace);
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col);
+    const IdxT* c = typed_col<IdxT>(*g);
     float* dpart = part + n_chunks * W;
     if (score && n_chunks > 0) {
       hipLaunchKernelGGL((transformer_hub_d_kernel<IdxT>),
@@ -668,22 +658,18 @@ int pygamd_transformer_backward_dst(const void* rowptr, const void* col, int idx
   });
 }
 
-int pygamd_transformer_backward_src(const void* rowptr_t, const void* col_t, const void* slot_map,
-                                    int idx_dtype, const float* query, const float* alpha,
-                                    const float* grad_s, const float* grad_out, int64_t n_src,
+int pygamd_transformer_backward_src(const pygamd_csr* g, const void* slot_map, const float* query,
+                                    const float* alpha, const float* grad_s, const float* grad_out,
                                     int64_t n_dst, int64_t H, int64_t C, float scale,
-                                    const void* hub_rows, const void* hub_chunk_ptr,
-                                    int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
-                                    int64_t hub_chunk, float* grad_key, float* grad_value,
-                                    int64_t ld, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-  const int rc = check_args(idx_dtype, n_src, n_dst, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                            n_chunks, hub_threshold, hub_chunk);
+                                    float* grad_key, float* grad_value, int64_t ld, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  const int rc = check_args(g, n_dst, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_src = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld < H * C) return PYGAMD_ERR_INVALID_ARG;
   if (n_src == 0) return PYGAMD_OK;
   const bool score = grad_out == nullptr;
-  if (!rowptr_t || !col_t || !slot_map || !query || !alpha || !grad_s || !grad_key ||
+  if (!g->rowptr || !g->col || !slot_map || !query || !alpha || !grad_s || !grad_key ||
       (!score && !grad_value))
     return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < tf_ws_bytes(n_chunks, H, C)))
@@ -695,12 +681,10 @@ int pygamd_transformer_backward_src(const void* rowptr_t, const void* col_t, con
   hipStream_t st = as_stream(stream);
   const int64_t W = H * C;
   float* part = static_cast<float*>(workspace);
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr_t), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_src, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_src + n_chunks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col_t);
+    const IdxT* c = typed_col<IdxT>(*g);
     const IdxT* sm = static_cast<const IdxT*>(slot_map);
     ATTN_DISPATCH_SHAPE(sh, {
       if (score) {
@@ -738,23 +722,19 @@ int pygamd_transformer_edge_workspace_bytes(int64_t n_chunks, int64_t H, int64_t
   return PYGAMD_OK;
 }
 
-int pygamd_transformer_edge_forward(const void* rowptr, const void* col, int idx_dtype,
-                                    const float* query, const float* key, const float* value,
-                                    int64_t ld, const float* edge_attr, const float* bias,
-                                    int64_t n_rows, int64_t n_src, int64_t H, int64_t C,
-                                    int64_t De, float scale, const void* hub_rows,
-                                    const void* hub_chunk_ptr, int64_t n_hub, int64_t n_chunks,
-                                    int64_t hub_threshold, int64_t hub_chunk, float* alpha,
-                                    float* out, float* z, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  const int rc = check_args(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                            n_chunks, hub_threshold, hub_chunk);
+int pygamd_transformer_edge_forward(const pygamd_csr* g, const float* query, const float* key,
+                                    const float* value, int64_t ld, const float* edge_attr,
+                                    const float* bias, int64_t n_src, int64_t H, int64_t C,
+                                    int64_t De, float scale, float* alpha, float* out, float* z,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = check_args(g, n_src, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld < H * C || De < 1) return PYGAMD_ERR_INVALID_ARG;
   if (!pygamd_transformer_edge_supported(H, C, De)) return PYGAMD_ERR_UNSUPPORTED;
   if (n_rows == 0) return PYGAMD_OK;
   // out and z come together (aggregation) or not at all (score mode)
-  if (!rowptr || !col || !query || !key || !edge_attr || !bias || !alpha || (out && !value) ||
+  if (!g->rowptr || !g->col || !query || !key || !edge_attr || !bias || !alpha || (out && !value) ||
       (out != nullptr) != (z != nullptr))
     return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < tf_edge_ws_bytes(n_chunks, H, C, De)))
@@ -768,12 +748,10 @@ int pygamd_transformer_edge_forward(const void* rowptr, const void* col, int idx
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   const EdgeFwd ed{edge_attr, bias, z, static_cast<int>(De)};
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col);
+    const IdxT* c = typed_col<IdxT>(*g);
     ATTN_DISPATCH_SHAPE(sh, {
       if (out) {
         hipLaunchKernelGGL((transformer_edge_fwd_kernel<IdxT, EPL, VEC, true>), grid, block, 0,
@@ -802,21 +780,15 @@ int pygamd_transformer_edge_forward(const void* rowptr, const void* col, int idx
   });
 }
 
-int pygamd_transformer_edge_backward_dst(const void* rowptr, const void* col, int idx_dtype,
-                                         const float* key, const float* value, int64_t ld,
-                                         const float* edge_attr, const float* bias,
-                                         const float* alpha, const float* grad_out,
-                                         const float* out, const float* grad_z, const float* z,
-                                         const float* grad_alpha, int64_t n_rows, int64_t n_src,
-                                         int64_t H, int64_t C, int64_t De, float scale,
-                                         const void* hub_rows, const void* hub_chunk_ptr,
-                                         int64_t n_hub, int64_t n_chunks, int64_t hub_threshold,
-                                         int64_t hub_chunk, float* grad_s, float* grad_query,
-                                         float* grad_bias, float* grad_edge_attr, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
-  const int rc = check_args(idx_dtype, n_rows, n_src, H, C, hub_rows, hub_chunk_ptr, n_hub,
-                            n_chunks, hub_threshold, hub_chunk);
+int pygamd_transformer_edge_backward_dst(
+    const pygamd_csr* g, const float* key, const float* value, int64_t ld, const float* edge_attr,
+    const float* bias, const float* alpha, const float* grad_out, const float* out,
+    const float* grad_z, const float* z, const float* grad_alpha, int64_t n_src, int64_t H,
+    int64_t C, int64_t De, float scale, float* grad_s, float* grad_query, float* grad_bias,
+    float* grad_edge_attr, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = check_args(g, n_src, H, C);
   if (rc != PYGAMD_OK) return rc;
+  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld < H * C || De < 1) return PYGAMD_ERR_INVALID_ARG;
   if (!pygamd_transformer_edge_supported(H, C, De)) return PYGAMD_ERR_UNSUPPORTED;
   // exactly one of (grad_out, out, grad_z, z) and grad_alpha says where d alpha comes from
@@ -824,8 +796,8 @@ int pygamd_transformer_edge_backward_dst(const void* rowptr, const void* col, in
   if (score ? (grad_out || out || grad_z || z) : (!grad_out || !out || !grad_z || !z))
     return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
-  if (!rowptr || !col || !key || (!score && !value) || !edge_attr || !bias || !alpha || !grad_s ||
-      !grad_query || !grad_bias)
+  if (!g->rowptr || !g->col || !key || (!score && !value) || !edge_attr || !bias || !alpha ||
+      !grad_s || !grad_query || !grad_bias)
     return PYGAMD_ERR_INVALID_ARG;
   if (n_chunks > 0 && (!workspace || workspace_bytes < tf_edge_ws_bytes(n_chunks, H, C, De)))
     return PYGAMD_ERR_WORKSPACE;
@@ -838,12 +810,10 @@ int pygamd_transformer_edge_backward_dst(const void* rowptr, const void* col, in
   const int64_t W = H * C, Z = H * De;
   float* part = static_cast<float*>(workspace);
   const EdgeBwd ed{edge_attr, bias, grad_z, z, grad_bias, grad_edge_attr, static_cast<int>(De)};
-  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
-    Items<IdxT> it{static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(hub_rows),
-                   static_cast<const IdxT*>(hub_chunk_ptr), n_rows, n_hub, n_chunks,
-                   hub_threshold, hub_chunk};
+  return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
+    const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
-    const IdxT* c = static_cast<const IdxT*>(col);
+    const IdxT* c = typed_col<IdxT>(*g);
     float* dpart = part + n_chunks * (W + Z);
     if (score && n_chunks > 0) {
       hipLaunchKernelGGL((transformer_hub_d_kernel<IdxT>),

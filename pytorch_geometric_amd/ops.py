@@ -379,6 +379,20 @@ def _linear_bwd(ctx, grad):
 
 register_autograd('pyg_amd::linear', _linear_bwd, setup_context=_linear_setup)
 
+def _by_source(rowptr: Tensor, col: Tensor, n_src: int, edge_id: Optional[Tensor] = None):
+    """``(rowptr_t, col_t, slot_map, hub)``: the by-source form of the slots of a by-destination
+    CSR, which the backward passes over the sources walk.  A stable sort of ``col``; its
+    permutation IS the map from by-source slots to the CSR's own slots (``slot_map``), and
+    through ``edge_id``, where given, to the caller's edges."""
+    dst = _native.ptr2index(rowptr, col.numel())
+    src_sorted, perm = _native.index_sort(col, max_value=max(n_src - 1, 0))
+    rowptr_t = _native.index2ptr(src_sorted, n_src)
+    col_t = _native.permute_index(dst, perm)
+    slot_map = (_native.cast_index(perm, col.dtype) if edge_id is None
+                else _native.permute_index(edge_id, perm))
+    return rowptr_t, col_t, slot_map, _native.hub_plan(rowptr_t)
+
+
 # ---- GATv2 attention on a CSR pair (rows = destinations) -----------------------------------------
 @custom_op('pyg_amd::gatv2_attend', mutates_args=(), device_types=_DEV)
 def gatv2_attend(x_l: Tensor, x_r: Tensor, att: Tensor, rowptr: Tensor, col: Tensor,
@@ -410,16 +424,10 @@ def gatv2_attend_backward(grad: Tensor, x_l: Tensor, x_r: Tensor, att: Tensor, a
     grad_s, g_r, g_att = _native.gatv2_backward_dst(
         rowptr, col, xl2, xr2, att, alpha, H, C, negative_slope,
         grad_out=_rows(grad).contiguous(), out=_rows(out), hub=_native.hub_plan(rowptr))
-    # the by-source form of the same slots: a stable sort of `col`; its permutation IS the map
-    # from by-source slots to the CSR's own (by-destination) slots
-    dst = _native.ptr2index(rowptr, col.numel())
-    src_sorted, perm = _native.index_sort(col, max_value=max(x_l.size(0) - 1, 0))
-    rowptr_t = _native.index2ptr(src_sorted, x_l.size(0))
-    col_t = _native.permute_index(dst, perm)
-    g_l = _native.gatv2_backward_src(rowptr_t, col_t, _native.cast_index(perm, col.dtype), xl2,
-                                     xr2, att, alpha, grad_s, H, C, negative_slope,
-                                     grad_out=_rows(grad).contiguous(), n_dst=n_dst,
-                                     hub=_native.hub_plan(rowptr_t))
+    rowptr_t, col_t, slot_map, hub_t = _by_source(rowptr, col, x_l.size(0))
+    g_l = _native.gatv2_backward_src(rowptr_t, col_t, slot_map, xl2, xr2, att, alpha, grad_s, H, C,
+                                     negative_slope, grad_out=_rows(grad).contiguous(),
+                                     n_dst=n_dst, hub=hub_t)
     return g_l.reshape(x_l.shape), g_r.reshape(x_r.shape), g_att.reshape(att.shape)
 
 
@@ -476,15 +484,9 @@ def transformer_attend_backward(grad: Tensor, query: Tensor, key: Tensor, value:
     grad_s, g_q = _native.transformer_backward_dst(
         rowptr, col, q2, _rows(key), _rows(value), alpha, H, C, scale, grad_out=g2,
         out=_rows(out), hub=_native.hub_plan(rowptr))
-    # the by-source form of the same slots: a stable sort of `col`; its permutation IS the map
-    # from by-source slots to the CSR's own (by-destination) slots
-    dst = _native.ptr2index(rowptr, col.numel())
-    src_sorted, perm = _native.index_sort(col, max_value=max(key.size(0) - 1, 0))
-    rowptr_t = _native.index2ptr(src_sorted, key.size(0))
-    col_t = _native.permute_index(dst, perm)
-    g_k, g_v = _native.transformer_backward_src(
-        rowptr_t, col_t, _native.cast_index(perm, col.dtype), q2, alpha, grad_s, H, C, scale,
-        grad_out=g2, n_dst=n_dst, hub=_native.hub_plan(rowptr_t))
+    rowptr_t, col_t, slot_map, hub_t = _by_source(rowptr, col, key.size(0))
+    g_k, g_v = _native.transformer_backward_src(rowptr_t, col_t, slot_map, q2, alpha, grad_s, H, C,
+                                                scale, grad_out=g2, n_dst=n_dst, hub=hub_t)
     return g_q.reshape(query.shape), g_k.reshape(key.shape), g_v.reshape(value.shape)
 
 
@@ -553,14 +555,9 @@ def transformer_edge_attend_backward(grad: Tensor, grad_z: Tensor, query: Tensor
         rowptr, col, q2, _rows(key), _rows(value), edge_attr, _rows(bias), alpha, H, C, scale,
         grad_out=g2, out=_rows(out), grad_z=_rows(grad_z).contiguous(), z=_rows(z),
         hub=_native.hub_plan(rowptr))
-    # the by-source form of the same slots, as transformer_attend_backward builds it
-    dst = _native.ptr2index(rowptr, col.numel())
-    src_sorted, perm = _native.index_sort(col, max_value=max(key.size(0) - 1, 0))
-    rowptr_t = _native.index2ptr(src_sorted, key.size(0))
-    col_t = _native.permute_index(dst, perm)
-    g_k, g_v = _native.transformer_backward_src(
-        rowptr_t, col_t, _native.cast_index(perm, col.dtype), q2, alpha, grad_s, H, C, scale,
-        grad_out=g2, n_dst=n_dst, hub=_native.hub_plan(rowptr_t))
+    rowptr_t, col_t, slot_map, hub_t = _by_source(rowptr, col, key.size(0))
+    g_k, g_v = _native.transformer_backward_src(rowptr_t, col_t, slot_map, q2, alpha, grad_s, H, C,
+                                                scale, grad_out=g2, n_dst=n_dst, hub=hub_t)
     return (g_q.reshape(query.shape), g_k.reshape(key.shape), g_v.reshape(value.shape), g_a,
             g_b.reshape(bias.shape))
 
@@ -625,17 +622,9 @@ def gine_aggregate_backward(grad: Tensor, x_src: Tensor, x_root: Optional[Tensor
     """The gradients of ``(x_src, x_root, eps, edge_attr, weight, bias)``; an input that was not
     given gets an empty tensor."""
     n_dst, n_src = rowptr.numel() - 1, x_src.size(0)
-    # the by-source form of the same slots: a stable sort of `col`; its permutation maps the
-    # by-source slots to the CSR's own slots, and through edge_id to the caller's edges
-    dst = _native.ptr2index(rowptr, col.numel())
-    src_sorted, perm = _native.index_sort(col, max_value=max(n_src - 1, 0))
-    rowptr_t = _native.index2ptr(src_sorted, n_src)
-    col_t = _native.permute_index(dst, perm)
-    edge_id_t = (_native.cast_index(perm, col.dtype) if edge_id is None
-                 else _native.permute_index(edge_id, perm))
+    rowptr_t, col_t, edge_id_t, hub_t = _by_source(rowptr, col, n_src, edge_id)
     g_x, g_a, g_w, g_b = _native.gine_backward(rowptr_t, col_t, edge_id_t, x_src, edge_attr,
-                                               weight, bias, grad,
-                                               hub=_native.hub_plan(rowptr_t))
+                                               weight, bias, grad, hub=hub_t)
     none = grad.new_empty(0)
     g_root = g_eps = none
     if x_root is not None:

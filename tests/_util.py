@@ -26,6 +26,19 @@ def assert_close(got, ref, rtol=RTOL, atol=ATOL, what=''):
         assert torch.equal(got, ref), f'{what}: integer mismatch'
 
 
+def csr_arg(**fields):
+    """A ``pygamd_csr`` (``_lib.Csr``) filled by field name and passed by reference, for a direct
+    call of the C ABI; fields that are not named stay 0 / NULL."""
+    import ctypes
+    from pytorch_geometric_amd import _lib
+    g = _lib.Csr()
+    known = {name for name, _ in _lib.Csr._fields_}
+    for name, value in fields.items():
+        assert name in known, f'pygamd_csr has no field {name}'
+        setattr(g, name, value.value if isinstance(value, ctypes.c_void_p) else value)
+    return ctypes.byref(g)
+
+
 def gen(seed):
     return torch.Generator().manual_seed(seed)
 

@@ -28,7 +28,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     if _build.is_stale() and _build.find_hipcc() is None:
         pytest.skip('library not built and no hipcc here')
     lib = _lib.load()
-    assert lib.pygamd_abi_version() == _lib.ABI_VERSION == 10
+    assert lib.pygamd_abi_version() == _lib.ABI_VERSION == 11
     assert lib.pygamd_build_arch() == b'gfx950'
     assert lib.pygamd_status_string(0) == b'ok'
     assert lib.pygamd_status_string(3) == b'workspace too small'
@@ -216,8 +216,8 @@ def test_torch_binding_builds_loads_and_declares_its_operators():
 
 
 def test_struct_mirrors_match_the_header_field_for_field(tmp_path):
-    """`_lib.SpmmArgs` / `_lib.SageFusedArgs` are hand-written mirrors of the two argument structs of
-    include/pyg_amd.h.  Compile the header with gcc and compare size and every field offset: a field
+    """`_lib.SpmmArgs` / `_lib.SageFusedArgs` / `_lib.Csr` are hand-written mirrors of the argument
+    structs of include/pyg_amd.h.  Compile the header with gcc and compare size and every field offset: a field
     added on one side only would silently shift everything behind it."""
     import ctypes
     import re
@@ -238,9 +238,14 @@ def test_struct_mirrors_match_the_header_field_for_field(tmp_path):
     m1 = re.search(r'typedef struct \{(.*?)\} pygamd_spmm_args;', header, flags=re.S)
     m2 = re.search(r'typedef struct pygamd_sage_fused_args \{(.*?)\} pygamd_sage_fused_args;',
                    header, flags=re.S)
-    assert m1 and m2
+    m3 = re.search(r'typedef struct pygamd_csr \{(.*?)\} pygamd_csr;', header, flags=re.S)
+    assert m1 and m2 and m3
     structs = {'pygamd_spmm_args': (c_fields(m1.group(1)), _lib.SpmmArgs),
-               'pygamd_sage_fused_args': (c_fields(m2.group(1)), _lib.SageFusedArgs)}
+               'pygamd_sage_fused_args': (c_fields(m2.group(1)), _lib.SageFusedArgs),
+               'pygamd_csr': (c_fields(m3.group(1)), _lib.Csr)}
+    assert structs['pygamd_csr'][0] == ['rowptr', 'col', 'idx_dtype', 'reserved0', 'n_rows',
+                                        'hub_rows', 'hub_chunk_ptr', 'n_hub', 'n_chunks',
+                                        'hub_threshold', 'hub_chunk']
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "pyg_amd.h"', 'int main(void) {']
     for name, (fields, _) in structs.items():
         lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import _gatv2_ref as R
-from _util import assert_close
+from _util import assert_close, csr_arg
 
 CASES = ['v2', 'v2_mean', 'v2_share', 'v2_noloops', 'v2_res_nobias', 'v2_c5', 'v2_pair', 'v2_edge',
          'v2_attention']
@@ -124,10 +124,14 @@ def test_entry_points_validate_without_gpu():
 
     def fwd(rowptr=dev, idx=1, x_l=dev, n_rows=5, H=4, C=8, hub_rows=None, n_hub=0, n_chunks=0,
             alpha=dev, ws=None, ws_bytes=0):
-        return lib.pygamd_gatv2_forward(rowptr, dev, idx, x_l, dev, dev, n_rows, 9, H, C, 0.2,
-                                        hub_rows, hub_rows, n_hub, n_chunks, 1024, 256, alpha,
-                                        dev, ws, ws_bytes, None)
+        g = csr_arg(rowptr=rowptr, col=dev, idx_dtype=idx, n_rows=n_rows, hub_rows=hub_rows,
+                    hub_chunk_ptr=hub_rows, n_hub=n_hub, n_chunks=n_chunks, hub_threshold=1024,
+                    hub_chunk=256)
+        return lib.pygamd_gatv2_forward(g, x_l, dev, dev, 9, H, C, 0.2, alpha, dev, ws, ws_bytes,
+                                        None)
 
+    assert lib.pygamd_gatv2_forward(None, dev, dev, dev, 9, 4, 8, 0.2, dev, dev, None, 0,
+                                    None) == 1                   # no descriptor
     assert fwd(rowptr=None) == 1 and fwd(x_l=None) == 1 and fwd(alpha=None) == 1
     assert fwd(idx=5) == 1 and fwd(n_rows=-1) == 1 and fwd(H=0) == 1 and fwd(C=0) == 1
     assert fwd(H=8, C=128) == 2 and fwd(H=65, C=1) == 2
@@ -140,10 +144,13 @@ def test_entry_points_validate_without_gpu():
 
     def bwd_dst(grad_out=dev, out=dev, grad_alpha=None, H=4, C=8, n_rows=5, grad_att=dev, ws=dev,
                 ws_bytes=1 << 30, grad_s=dev):
-        return lib.pygamd_gatv2_backward_dst(dev, dev, 1, dev, dev, dev, dev, grad_out, out,
-                                             grad_alpha, n_rows, 9, H, C, 0.2, None, None, 0, 0,
-                                             1024, 256, grad_s, dev, grad_att, ws, ws_bytes, None)
+        g = csr_arg(rowptr=dev, col=dev, idx_dtype=1, n_rows=n_rows, hub_threshold=1024,
+                    hub_chunk=256)
+        return lib.pygamd_gatv2_backward_dst(g, dev, dev, dev, dev, grad_out, out, grad_alpha, 9,
+                                             H, C, 0.2, grad_s, dev, grad_att, ws, ws_bytes, None)
 
+    assert lib.pygamd_gatv2_backward_dst(None, dev, dev, dev, dev, dev, dev, None, 9, 4, 8, 0.2,
+                                         dev, dev, dev, dev, 1 << 30, None) == 1
     assert bwd_dst(grad_out=None) == 1 and bwd_dst(out=None) == 1
     assert bwd_dst(grad_alpha=dev) == 1                         # both sources of d alpha given
     assert bwd_dst(grad_out=None, out=None, grad_alpha=None) == 1
@@ -152,10 +159,13 @@ def test_entry_points_validate_without_gpu():
     assert bwd_dst(ws=None, ws_bytes=0) == 3 and bwd_dst(ws_bytes=16) == 3
 
     def bwd_src(slot_map=dev, idx=0, n_src=5, H=4, C=8, gx=dev, n_hub=0, n_chunks=0):
-        return lib.pygamd_gatv2_backward_src(dev, dev, slot_map, idx, dev, dev, dev, dev, dev,
-                                             None, n_src, 7, H, C, 0.2, None, None, n_hub,
-                                             n_chunks, 1024, 256, gx, None, 0, None)
+        g = csr_arg(rowptr=dev, col=dev, idx_dtype=idx, n_rows=n_src, n_hub=n_hub,
+                    n_chunks=n_chunks, hub_threshold=1024, hub_chunk=256)
+        return lib.pygamd_gatv2_backward_src(g, slot_map, dev, dev, dev, dev, dev, None, 7, H, C,
+                                             0.2, gx, None, 0, None)
 
+    assert lib.pygamd_gatv2_backward_src(None, dev, dev, dev, dev, dev, dev, None, 7, 4, 8, 0.2,
+                                         dev, None, 0, None) == 1
     assert bwd_src(slot_map=None) == 1 and bwd_src(gx=None) == 1 and bwd_src(idx=2) == 1
     assert bwd_src(H=2, C=300) == 2 and bwd_src(n_src=-1) == 1
     assert bwd_src(n_hub=1, n_chunks=4) == 1

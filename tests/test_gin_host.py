@@ -69,3 +69,30 @@ def test_reset_parameters_restores_eps_and_resets_nn():
         layer.reset_parameters()
         assert float(layer.eps.detach()) == pytest.approx(0.3)
         assert not torch.equal(layer.nn[0].weight, before)      # nn was re-initialised
+
+
+def test_entry_points_reject_a_missing_descriptor():
+    """pygamd_gine_* take the CSR handle and its hub plan as one ``pygamd_csr``: without it the
+    call is status 1 before any device work, and with it the first bad field still decides."""
+    import ctypes
+    from _util import csr_arg
+    from pytorch_geometric_amd import _build, _lib
+    if _build.is_stale() and _build.find_hipcc() is None:
+        pytest.skip('library not built and no hipcc here')
+    lib = _lib.load()
+    dev = ctypes.c_void_p(16)   # (never dereferenced: every call below is rejected or launches nothing)
+
+    def fwd(g, F=8, De=0):
+        return lib.pygamd_gine_forward(g, None, dev, 8, None, 0, None, dev, None, None, 9, F, De,
+                                       dev, None, 0, None)
+
+    def bwd(g, F=8, De=0):
+        return lib.pygamd_gine_backward(g, None, dev, 8, dev, None, None, dev, 7, F, De, dev, dev,
+                                        None, None, None, 0, None)
+
+    assert fwd(None) == 1 and bwd(None) == 1
+    empty = dict(rowptr=dev, col=dev, idx_dtype=1, n_rows=0, hub_threshold=1024, hub_chunk=256)
+    assert fwd(csr_arg(**empty)) == 0 and bwd(csr_arg(**empty)) == 0      # no rows: nothing to launch
+    assert fwd(csr_arg(**dict(empty, idx_dtype=5))) == 1
+    assert bwd(csr_arg(**dict(empty, n_hub=0, n_chunks=3))) == 1         # chunks without hub rows
+    assert fwd(csr_arg(**empty), F=513) == 2 and bwd(csr_arg(**empty), F=64, De=33) == 2

@@ -43,7 +43,7 @@ def test_hetero_entry_points_are_declared_exported_and_typed(sym, n_args):
     out = subprocess.run(['nm', '-D', '--defined-only', _lib.lib_path()], capture_output=True,
                          text=True).stdout
     assert re.search(r' T ' + sym + r'\b', out)
-    assert _lib.ABI_VERSION == 10
+    assert _lib.ABI_VERSION == 11
 
 
 def test_hetero_entry_points_validate_without_gpu():

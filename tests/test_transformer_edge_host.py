@@ -13,7 +13,7 @@ import torch
 
 import _transformer_edge_ref as RE
 import _transformer_ref as R
-from _util import assert_close
+from _util import assert_close, csr_arg
 
 
 def test_golden_file_is_what_the_tests_expect():
@@ -152,10 +152,15 @@ def test_entry_points_validate_without_gpu():
     def fwd(rowptr=dev, idx=1, query=dev, key=dev, value=dev, ld=32, ea=dev, bias=dev, n_rows=5,
             H=4, C=8, De=6, hub_rows=None, n_hub=0, n_chunks=0, alpha=dev, out=dev, z=dev,
             ws=None, ws_bytes=0):
+        g = csr_arg(rowptr=rowptr, col=dev, idx_dtype=idx, n_rows=n_rows, hub_rows=hub_rows,
+                    hub_chunk_ptr=hub_rows, n_hub=n_hub, n_chunks=n_chunks, hub_threshold=1024,
+                    hub_chunk=256)
         return lib.pygamd_transformer_edge_forward(
-            rowptr, dev, idx, query, key, value, ld, ea, bias, n_rows, 9, H, C, De, 0.35, hub_rows,
-            hub_rows, n_hub, n_chunks, 1024, 256, alpha, out, z, ws, ws_bytes, None)
+            g, query, key, value, ld, ea, bias, 9, H, C, De, 0.35, alpha, out, z, ws, ws_bytes,
+            None)
 
+    assert lib.pygamd_transformer_edge_forward(None, dev, dev, dev, 32, dev, dev, 9, 4, 8, 6, 0.35,
+                                               dev, dev, dev, None, 0, None) == 1   # no descriptor
     assert fwd(rowptr=None) == 1 and fwd(query=None) == 1 and fwd(key=None) == 1
     assert fwd(ea=None) == 1 and fwd(bias=None) == 1 and fwd(alpha=None) == 1
     assert fwd(value=None) == 1                                 # aggregation asked for, no values
@@ -173,11 +178,16 @@ def test_entry_points_validate_without_gpu():
     def bwd(key=dev, value=dev, ld=32, ea=dev, bias=dev, grad_out=dev, out=dev, grad_z=dev, z=dev,
             grad_alpha=None, H=4, C=8, De=6, n_rows=5, grad_s=dev, grad_query=dev, grad_bias=dev,
             grad_ea=dev, hub_rows=None, n_hub=0, n_chunks=0, ws=None, ws_bytes=0):
+        g = csr_arg(rowptr=dev, col=dev, idx_dtype=1, n_rows=n_rows, hub_rows=hub_rows,
+                    hub_chunk_ptr=hub_rows, n_hub=n_hub, n_chunks=n_chunks, hub_threshold=1024,
+                    hub_chunk=256)
         return lib.pygamd_transformer_edge_backward_dst(
-            dev, dev, 1, key, value, ld, ea, bias, dev, grad_out, out, grad_z, z, grad_alpha,
-            n_rows, 9, H, C, De, 0.35, hub_rows, hub_rows, n_hub, n_chunks, 1024, 256, grad_s,
-            grad_query, grad_bias, grad_ea, ws, ws_bytes, None)
+            g, key, value, ld, ea, bias, dev, grad_out, out, grad_z, z, grad_alpha, 9, H, C, De,
+            0.35, grad_s, grad_query, grad_bias, grad_ea, ws, ws_bytes, None)
 
+    assert lib.pygamd_transformer_edge_backward_dst(
+        None, dev, dev, 32, dev, dev, dev, dev, dev, dev, dev, None, 9, 4, 8, 6, 0.35, dev, dev,
+        dev, dev, None, 0, None) == 1
     assert bwd(grad_out=None) == 1 and bwd(out=None) == 1
     assert bwd(grad_z=None) == 1 and bwd(z=None) == 1
     assert bwd(grad_alpha=dev) == 1                             # both sources of d alpha given

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import _transformer_ref as R
-from _util import assert_close
+from _util import assert_close, csr_arg
 
 CASES = ['t', 't_mean', 't_beta', 't_beta_mean', 't_noroot', 't_nobias', 't_c5', 't_pair', 't_edge',
          't_attention']
@@ -135,10 +135,14 @@ def test_entry_points_validate_without_gpu():
 
     def fwd(rowptr=dev, idx=1, query=dev, key=dev, value=dev, ld=32, n_rows=5, H=4, C=8,
             hub_rows=None, n_hub=0, n_chunks=0, alpha=dev, out=dev, ws=None, ws_bytes=0):
-        return lib.pygamd_transformer_forward(rowptr, dev, idx, query, key, value, ld, n_rows, 9,
-                                              H, C, 0.35, hub_rows, hub_rows, n_hub, n_chunks,
-                                              1024, 256, alpha, out, ws, ws_bytes, None)
+        g = csr_arg(rowptr=rowptr, col=dev, idx_dtype=idx, n_rows=n_rows, hub_rows=hub_rows,
+                    hub_chunk_ptr=hub_rows, n_hub=n_hub, n_chunks=n_chunks, hub_threshold=1024,
+                    hub_chunk=256)
+        return lib.pygamd_transformer_forward(g, query, key, value, ld, 9, H, C, 0.35, alpha, out,
+                                              ws, ws_bytes, None)
 
+    assert lib.pygamd_transformer_forward(None, dev, dev, dev, 32, 9, 4, 8, 0.35, dev, dev, None,
+                                          0, None) == 1          # no descriptor
     assert fwd(rowptr=None) == 1 and fwd(query=None) == 1 and fwd(key=None) == 1
     assert fwd(alpha=None) == 1 and fwd(value=None) == 1    # aggregation asked for, no values
     assert fwd(ld=31) == 1                                  # rows narrower than H * C
@@ -154,10 +158,15 @@ def test_entry_points_validate_without_gpu():
     def bwd_dst(key=dev, value=dev, ld=32, grad_out=dev, out=dev, grad_alpha=None, H=4, C=8,
                 n_rows=5, grad_s=dev, grad_query=dev, hub_rows=None, n_hub=0, n_chunks=0,
                 ws=None, ws_bytes=0):
+        g = csr_arg(rowptr=dev, col=dev, idx_dtype=1, n_rows=n_rows, hub_rows=hub_rows,
+                    hub_chunk_ptr=hub_rows, n_hub=n_hub, n_chunks=n_chunks, hub_threshold=1024,
+                    hub_chunk=256)
         return lib.pygamd_transformer_backward_dst(
-            dev, dev, 1, key, value, ld, dev, grad_out, out, grad_alpha, n_rows, 9, H, C, 0.35,
-            hub_rows, hub_rows, n_hub, n_chunks, 1024, 256, grad_s, grad_query, ws, ws_bytes, None)
+            g, key, value, ld, dev, grad_out, out, grad_alpha, 9, H, C, 0.35, grad_s, grad_query,
+            ws, ws_bytes, None)
 
+    assert lib.pygamd_transformer_backward_dst(None, dev, dev, 32, dev, dev, dev, None, 9, 4, 8,
+                                               0.35, dev, dev, None, 0, None) == 1
     assert bwd_dst(grad_out=None) == 1 and bwd_dst(out=None) == 1
     assert bwd_dst(grad_alpha=dev) == 1                         # both sources of d alpha given
     assert bwd_dst(grad_out=None, out=None, grad_alpha=None) == 1
@@ -170,10 +179,15 @@ def test_entry_points_validate_without_gpu():
 
     def bwd_src(slot_map=dev, idx=0, n_src=5, H=4, C=8, grad_out=dev, grad_key=dev,
                 grad_value=dev, ld=64, hub_rows=None, n_hub=0, n_chunks=0):
+        g = csr_arg(rowptr=dev, col=dev, idx_dtype=idx, n_rows=n_src, hub_rows=hub_rows,
+                    hub_chunk_ptr=hub_rows, n_hub=n_hub, n_chunks=n_chunks, hub_threshold=1024,
+                    hub_chunk=256)
         return lib.pygamd_transformer_backward_src(
-            dev, dev, slot_map, idx, dev, dev, dev, grad_out, n_src, 7, H, C, 0.35, hub_rows,
-            hub_rows, n_hub, n_chunks, 1024, 256, grad_key, grad_value, ld, None, 0, None)
+            g, slot_map, dev, dev, dev, grad_out, 7, H, C, 0.35, grad_key, grad_value, ld, None, 0,
+            None)
 
+    assert lib.pygamd_transformer_backward_src(None, dev, dev, dev, dev, dev, 7, 4, 8, 0.35, dev,
+                                               dev, 64, None, 0, None) == 1
     assert bwd_src(slot_map=None) == 1 and bwd_src(grad_key=None) == 1 and bwd_src(idx=2) == 1
     assert bwd_src(grad_value=None) == 1                        # grad_out given: both gradients
     assert bwd_src(ld=16) == 1
