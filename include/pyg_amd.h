@@ -756,6 +756,52 @@ PYGAMD_API int pygamd_gine_backward(const pygamd_csr* g, const void* edge_id_t, 
                                     float* grad_weight, float* grad_bias, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* ---- PNAConv's multi-statistic aggregation (pna_conv.py:175-188, aggr/scaler.py:82) --------------
+ * For a linear message (pre_layers = 1) the message of slot k of destination i with source
+ * j = col[k] is m_k = p_dst[i,:] + u_k with u_k = p_src[j,:] + Wc a_k, a_k = edge_attr[edge_id[k],
+ * :De], Wc [W, De] (De == 0: u_k = p_src[j,:]; edge_attr and wc are NULL).  forward
+ * (pna_conv.py:175-188 is the message, aggr/scaler.py:82 the aggregation it feeds): ONE launch
+ * over the by-destination handle g, one 64-lane wave per row, lanes over the W columns, one
+ * gathered row per slot.  `stats` is a non-empty bit set (1 mean, 2 min, 4 max, 8 std); `out`
+ * holds the selected statistics as consecutive [n_rows, W] planes in that order:
+ *   mean = p_dst[i] + sum u / d,  min = p_dst[i] + min u,  max = p_dst[i] + max u,
+ *   std = sqrt(max(var u, 1e-5)), 0 where that is <= sqrt(1e-5)
+ * and exactly 0 for a row without slots.  The second moment is accumulated about the first u of
+ * the row (or chunk).  `saved` [6, n_rows, W] takes what the backward needs: mean u, min u, max u,
+ * std and the number of slots attaining the minimum / the maximum (as floats; 0, 0, 0, 0, 1, 1 for
+ * a row without slots).  A split row's partials (seven rows per chunk) are merged in chunk order:
+ * equal extrema add their counts, moments combine by the parallel-variance formula.
+ *
+ * backward (the gradient of pna_conv.py:175-188 under aggr/scaler.py:82): ONE launch over the
+ * by-source handle g (col = the destination of every out-slot, edge_id_t = that form's slot ->
+ * original edge map).  `coef` [n_dst, 6, W] is a packed row per destination: A, B, Gmin, Gmax,
+ * min u, max u.  The launch rebuilds u_k bit for bit and forms
+ *   grad_u = A + B u_k + Gmin [u_k == min u] + Gmax [u_k == max u]
+ * (rows of a statistic outside `stats` are not read), then
+ *   grad_p_src[j,:] = sum_t grad_u   (zeros for rows without out-slots)
+ *   grad_edge_attr[k,d] = sum_c grad_u[c] Wc[c,d]   (original edge order; NULL: not wanted)
+ *   grad_wc[c,d] = sum_k grad_u[c] a_k[d]   (per-workgroup partials reduced in workgroup order)
+ * The gradient of p_dst is elementwise and the caller's.
+ *
+ * pygamd_pna_supported(W, De): W <= 512 and, with edge features, De <= 32 and W * De <= 4096;
+ * otherwise status 2.  p_src / p_dst have row strides ld_src / ld_dst (floats); fp32 data, int32 /
+ * int64 indices.  No float atomics: bitwise reproducible.  Status 1 / 2 / 3 before any device
+ * work; n_rows == 0 returns 0.                                                                    */
+PYGAMD_API int pygamd_pna_supported(int64_t W, int64_t De);
+PYGAMD_API int pygamd_pna_workspace_bytes(int64_t n_chunks, int64_t W, int64_t De,
+                                          size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_pna_forward(const pygamd_csr* g, const void* edge_id, const float* p_src,
+                                  int64_t ld_src, const float* p_dst, int64_t ld_dst,
+                                  const float* edge_attr, const float* wc, int64_t n_src,
+                                  int64_t W, int64_t De, int stats, float* out, float* saved,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_pna_backward(const pygamd_csr* g, const void* edge_id_t, const float* p_src,
+                                   int64_t ld_src, const float* edge_attr, const float* wc,
+                                   const float* coef, int64_t n_dst, int64_t W, int64_t De,
+                                   int stats, float* grad_p_src, float* grad_edge_attr,
+                                   float* grad_wc, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

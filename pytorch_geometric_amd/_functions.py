@@ -941,6 +941,82 @@ class GineAggregateFunction(Function):
                 g_w if need[4] else None, g_b if need[5] else None, None, None)
 
 
+def pna_coefficients(saved: Tensor, deg: Tensor, stats, grads) -> Tensor:
+    """The packed coefficient rows ``[n_dst, 6, W]`` (A, B, Gmin, Gmax, min u, max u) the backward
+    kernel of csrc/pna.hip reads, from the forward's saved planes, the degrees ``deg [n_dst]`` and
+    the incoming gradients of ``stats`` (None: zero).  Per slot the kernel forms ``grad_u = A +
+    B u + Gmin [u == min u] + Gmax [u == max u]``: ``B = g_std / (d std)`` (0 where std was
+    masked), ``A = g_mean / d - B mean_u``, ``Gmin = g_min / cnt_min`` (an even split among
+    ties, as ``scatter_reduce``), ``Gmax`` alike; all 0 for ``d = 0``."""
+    mean_u, min_u, max_u, std, cnt_min, cnt_max = saved.unbind(0)
+    g = dict(zip(stats, grads))
+    d = deg.to(torch.float32).view(-1, 1)
+    has = d > 0
+    zero = torch.zeros_like(mean_u)
+    B = zero
+    if g.get('std') is not None:
+        B = torch.where(std > 0, g['std'] / (d * std), zero)
+    A = -B * mean_u
+    if g.get('mean') is not None:
+        A = A + torch.where(has, g['mean'] / d.clamp(min=1), zero)
+    Gmin = zero if g.get('min') is None else torch.where(has, g['min'] / cnt_min, zero)
+    Gmax = zero if g.get('max') is None else torch.where(has, g['max'] / cnt_max, zero)
+    return torch.stack([A, B, Gmin, Gmax, min_u, max_u], dim=1)
+
+
+class PnaAggregateFunction(Function):
+    """The aggregation of PNAConv with a linear message (pna_conv.py:175-188 under
+    aggr/scaler.py:82) in ONE pass over the by-destination slots.  The message of slot ``k`` of
+    destination ``i`` is ``p_dst[i] + u_k`` with ``u_k = p_src[j_k] + wc @ edge_attr[k]``
+    (``edge_attr`` and ``wc`` None: ``u_k = p_src[j_k]``); ``stats`` is a tuple out of ``'mean'``,
+    ``'min'``, ``'max'``, ``'std'`` and the result a tuple of ``[n_dst, W]`` tensors in its order,
+    exactly 0 for destinations without slots.  ``edge_attr`` stays in the caller's edge order.
+    Saved for the backward: the inputs and six ``[n_dst, W]`` planes, nothing per edge.  The
+    backward is an elementwise pre-pass (:func:`pna_coefficients`) and one pass over the by-source
+    slots; ``grad_edge_attr`` is not computed when it is not required."""
+
+    @staticmethod
+    def forward(ctx, p_src: Tensor, p_dst: Tensor, edge_attr: Optional[Tensor],
+                wc: Optional[Tensor], graph: EdgeIndex, n_dst: int, stats):
+        stats = tuple(stats)
+        if p_src.size(0) != graph.num_src_nodes:
+            raise ValueError(f"'p_src' has {p_src.size(0)} rows but the graph has "
+                             f"{graph.num_src_nodes} source nodes")
+        if n_dst != graph.num_dst_nodes or p_dst.size(0) < n_dst:
+            raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = "
+                             f"{n_dst}, 'p_dst' has {p_dst.size(0)} rows")
+        fwd = graph.by_dst()
+        out, saved = _native.pna_forward(fwd.ptr, fwd.idx, fwd.perm, p_src, p_dst, edge_attr, wc,
+                                         stats, hub=fwd.hub)
+        ctx.save_for_backward(p_src, edge_attr, wc, saved)
+        ctx.graph, ctx.n_dst, ctx.stats, ctx.dst_rows = graph, n_dst, stats, p_dst.size(0)
+        order = sorted(stats, key=_native.PNA_STATS.index)
+        return tuple(out[order.index(s)] for s in stats)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        p_src, edge_attr, wc, saved = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_src = g_dst = g_a = g_wc = None
+        ptr = ctx.graph.by_dst().ptr
+        deg = ptr[1:] - ptr[:-1]
+        if need[0] or need[2] or need[3]:
+            coef = pna_coefficients(saved, deg, ctx.stats, grads)
+            bwd = ctx.graph.by_src()
+            g_src, g_a, g_wc = _native.pna_backward(
+                bwd.ptr, bwd.idx, bwd.perm, p_src, edge_attr, wc, coef, ctx.stats,
+                want_grad_edge_attr=need[2], hub=bwd.hub)
+        if need[1]:
+            parts = [g for s, g in zip(ctx.stats, grads) if s != 'std' and g is not None]
+            g_dst = saved.new_zeros(ctx.dst_rows, saved.size(2))
+            if parts:  # (destinations may be a prefix of p_dst's rows: the rest takes no gradient)
+                total = parts[0] if len(parts) == 1 else torch.stack(parts).sum(0)
+                g_dst[:ctx.n_dst] = total * (deg > 0).view(-1, 1)
+        return (g_src if need[0] else None, g_dst, g_a if need[2] else None,
+                g_wc if need[3] else None, None, None, None)
+
+
 class HgtRelationPlan:
     """Static description of one relation-transform node: ``heads``; ``src_pos[e]``: the position
     (among the tensor inputs) of the source node type of edge type ``e`` of the call; ``widx[e]``:

@@ -1594,6 +1594,131 @@ def gine_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], 
     return grad_x, grad_edge, grad_w, grad_b
 
 
+# ---- PNAConv's multi-statistic aggregation (csrc/pna.hip) ------------------------------------------
+PNA_STATS = ('mean', 'min', 'max', 'std')      # the kernel's order: bit q selects PNA_STATS[q]
+
+
+def pna_supported(W: int, De: int = 0) -> bool:
+    """The kernel pair serves message widths ``W <= 512`` and, with edge features (``De >= 1``),
+    ``De <= 32`` and ``W * De <= 4096``."""
+    return bool(_lib.load().pygamd_pna_supported(int(W), int(De)))
+
+
+def _pna_mask(stats) -> int:
+    stats = tuple(stats)
+    if not stats or len(set(stats)) != len(stats) or any(s not in PNA_STATS for s in stats):
+        raise ValueError(f"'stats' must be a non-empty subset of {PNA_STATS} (got {stats})")
+    return sum(1 << PNA_STATS.index(s) for s in stats)
+
+
+def _pna_edge(edge_attr: Optional[Tensor], wc: Optional[Tensor], W: int, E: int):
+    """(edge_attr, wc, De) checked; both None without edge features (``De = 0``)."""
+    if (edge_attr is None) != (wc is None):
+        raise ValueError("'edge_attr' and 'wc' come together")
+    if wc is None:
+        return None, None, 0
+    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != E:
+        raise ValueError(f"'edge_attr' must be a float32 [{E}, De] tensor (got "
+                         f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
+    De = edge_attr.size(1)
+    if wc.dtype != torch.float32 or tuple(wc.shape) != (W, De) or De < 1:
+        raise ValueError(f"'wc' must be float32 [{W}, {De}] (got {wc.dtype} {tuple(wc.shape)})")
+    return edge_attr.contiguous(), wc.contiguous(), De
+
+
+def _pna_edge_id(edge_id: Optional[Tensor], rowptr: Tensor, col: Tensor):
+    if edge_id is None:
+        return None
+    if edge_id.dtype != rowptr.dtype or edge_id.numel() != col.numel():
+        raise ValueError("'edge_id' must have the index dtype and one entry per slot")
+    return edge_id.contiguous()
+
+
+def pna_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], p_src: Tensor,
+                p_dst: Tensor, edge_attr: Optional[Tensor], wc: Optional[Tensor], stats, *,
+                hub=None):
+    """The statistics ``stats`` (a subset of :data:`PNA_STATS`) of the messages ``p_dst[i] + u_k``,
+    ``u_k = p_src[col[k]] + wc @ edge_attr[edge_id[k]]``, over every row of a by-destination
+    handle: ``(out [n_stats, n_rows, W], saved [6, n_rows, W])`` with the planes of ``out`` in the
+    order of :data:`PNA_STATS` and ``saved`` = mean u, min u, max u, std, the numbers of slots
+    attaining the minimum / the maximum.  Rows without slots are exactly 0.  ``p_src`` and
+    ``p_dst`` may be column blocks of wider tensors (their row stride is passed)."""
+    _require_device(rowptr, col, edge_id, p_src, p_dst, edge_attr, wc)
+    lib = _lib.load()
+    if p_src.dim() != 2:
+        raise ValueError("'p_src' must be two-dimensional")
+    W = p_src.size(1)
+    mask = _pna_mask(stats)
+    p_src, p_dst = _strided_rows(p_src, 'p_src', W), _strided_rows(p_dst, 'p_dst', W)
+    n_rows = rowptr.numel() - 1
+    if p_dst.size(0) < n_rows:
+        raise ValueError(f"'p_dst' needs at least {n_rows} rows")
+    edge_attr, wc, De = _pna_edge(edge_attr, wc, W, col.numel())
+    edge_id = _pna_edge_id(edge_id, rowptr, col)
+    dev = p_src.device
+    n_sel = bin(mask).count('1')
+    if n_rows == 0 or col.numel() == 0:  # no slot anywhere: every statistic is 0, nothing to launch
+        saved = torch.zeros(6, n_rows, W, dtype=torch.float32, device=dev)
+        saved[4:] = 1.0
+        return torch.zeros(n_sel, n_rows, W, dtype=torch.float32, device=dev), saved
+    out = torch.empty(n_sel, n_rows, W, dtype=torch.float32, device=dev)
+    saved = torch.empty(6, n_rows, W, dtype=torch.float32, device=dev)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_pna_workspace_bytes, (g.n_chunks, W, 0), dev,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'pna', 'op': 'forward', 'n_rows': n_rows, 'E': col.numel(), 'W': W,
+                 'De': De, 'stats': mask, 'ld': _ld(p_src), 'n_hub': g.n_hub,
+                 'n_chunks': g.n_chunks, 'grad_edge_attr': False}, p_src):
+        check(lib.pygamd_pna_forward(
+            ctypes.byref(g), _p(edge_id), _p(p_src), _ld(p_src), _p(p_dst), _ld(p_dst),
+            _p(edge_attr), _p(wc), p_src.size(0), W, De, mask, _p(out), _p(saved), _p(ws),
+            ws_bytes, _stream(p_src)), 'pna_forward')
+    return out, saved
+
+
+def pna_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], p_src: Tensor,
+                 edge_attr: Optional[Tensor], wc: Optional[Tensor], coef: Tensor, stats, *,
+                 want_grad_edge_attr: bool = True, hub=None):
+    """``(grad_p_src [n_src, W], grad_edge_attr | None, grad_wc | None)`` on the by-SOURCE handle
+    (``col_t`` = the destination of every out-slot, ``edge_id_t`` = that form's slot -> edge map)
+    from the packed coefficient rows ``coef [n_dst, 6, W]`` = A, B, Gmin, Gmax, min u, max u:
+    ``grad_u = A + B u + Gmin [u == min u] + Gmax [u == max u]`` per slot."""
+    _require_device(rowptr_t, col_t, edge_id_t, p_src, edge_attr, wc, coef)
+    lib = _lib.load()
+    W = p_src.size(1)
+    mask = _pna_mask(stats)
+    p_src = _strided_rows(p_src, 'p_src', W)
+    n_src = rowptr_t.numel() - 1
+    if p_src.size(0) != n_src:
+        raise ValueError(f"'p_src' needs {n_src} rows")
+    if coef.dtype != torch.float32 or coef.dim() != 3 or tuple(coef.shape[1:]) != (6, W):
+        raise ValueError(f"'coef' must be a float32 [n_dst, 6, {W}] tensor (got {coef.dtype} "
+                         f"{tuple(coef.shape)})")
+    coef = coef.contiguous()
+    edge_attr, wc, De = _pna_edge(edge_attr, wc, W, col_t.numel())
+    edge_id_t = _pna_edge_id(edge_id_t, rowptr_t, col_t)
+    want_grad_edge_attr = bool(want_grad_edge_attr) and De > 0
+    dev = p_src.device
+    if n_src == 0 or col_t.numel() == 0:
+        return (torch.zeros(n_src, W, dtype=torch.float32, device=dev),
+                torch.zeros_like(edge_attr) if want_grad_edge_attr else None,
+                None if wc is None else torch.zeros_like(wc))
+    grad_p = torch.empty(n_src, W, dtype=torch.float32, device=dev)
+    grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
+    grad_wc = torch.empty_like(wc) if wc is not None else None
+    g = _csr(rowptr_t, col_t, n_src, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_pna_workspace_bytes, (g.n_chunks, W, De), dev,
+                              g.n_chunks > 0 or De > 0)
+    with _timed({'kind': 'pna', 'op': 'backward', 'n_rows': n_src, 'E': col_t.numel(), 'W': W,
+                 'De': De, 'stats': mask, 'ld': _ld(p_src), 'n_hub': g.n_hub,
+                 'n_chunks': g.n_chunks, 'grad_edge_attr': want_grad_edge_attr}, p_src):
+        check(lib.pygamd_pna_backward(
+            ctypes.byref(g), _p(edge_id_t), _p(p_src), _ld(p_src), _p(edge_attr), _p(wc),
+            _p(coef), coef.size(0), W, De, mask, _p(grad_p), _p(grad_edge), _p(grad_wc), _p(ws),
+            ws_bytes, _stream(p_src)), 'pna_backward')
+    return grad_p, grad_edge, grad_wc
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

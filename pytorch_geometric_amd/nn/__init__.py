@@ -1,8 +1,8 @@
-from .aggr import (Aggregation, FusedAggregation, MaxAggregation, MeanAggregation,
+from .aggr import (Aggregation, DegreeScalerAggregation, FusedAggregation, MaxAggregation, MeanAggregation,
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
 from .conv import (FastRGCNConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HeteroConv, HGTConv,
-                   MessagePassing, RGCNConv, SAGEConv, TransformerConv, gcn_norm, group)
+                   MessagePassing, PNAConv, RGCNConv, SAGEConv, TransformerConv, gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, GraphSAGE
 from . import functional  # noqa: F401
@@ -12,5 +12,6 @@ __all__ = [
     'MulAggregation', 'VarAggregation', 'StdAggregation', 'FusedAggregation',
     'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
     'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
+    'PNAConv', 'DegreeScalerAggregation',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

@@ -3,8 +3,10 @@ from .basic import (MaxAggregation, MeanAggregation, MinAggregation, MulAggregat
                     SumAggregation, aggregation_resolver)
 from .deeper import PowerMeanAggregation, SoftmaxAggregation
 from .fused import FusedAggregation, MultiAggregation, StdAggregation, VarAggregation
+from .scaler import DegreeScalerAggregation
 
 __all__ = ['Aggregation', 'SumAggregation', 'MeanAggregation', 'MaxAggregation',
            'MinAggregation', 'MulAggregation', 'VarAggregation', 'StdAggregation',
            'FusedAggregation', 'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation',
+           'DegreeScalerAggregation',
            'aggregation_resolver']

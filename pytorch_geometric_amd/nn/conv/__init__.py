@@ -9,6 +9,8 @@ from .graph_conv import GraphConv
 from .hetero_conv import HeteroConv, group
 from .hgt_conv import HGTConv
 from .gin_conv import GINConv, GINEConv
+from .pna_conv import PNAConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
-           'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv']
+           'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
+           'PNAConv']

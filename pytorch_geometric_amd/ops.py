@@ -39,6 +39,9 @@ Operators (all index tensors int32 / int64, features float32):
 ``gine_aggregate``          ``(Tensor x_src, Tensor? x_root, Tensor? eps, Tensor edge_attr,
                             Tensor? weight, Tensor? bias, Tensor rowptr, Tensor col,
                             Tensor? edge_id) -> Tensor``
+``pna_aggregate``           ``(Tensor p_src, Tensor p_dst, Tensor? edge_attr, Tensor? wc,
+                            Tensor rowptr, Tensor col, Tensor? edge_id, int stats)
+                            -> (Tensor out, Tensor saved)``
 ==========================  ===========================================================
 """
 import math
@@ -664,6 +667,89 @@ def _gine_bwd(ctx, grad):
 register_autograd('pyg_amd::gine_aggregate', _gine_bwd, setup_context=_gine_setup)
 
 
+# ---- PNAConv's multi-statistic aggregation on a CSR pair (rows = destinations) ---------------------
+def _pna_stats(stats: int):
+    if not 1 <= stats <= 15:
+        raise ValueError(f"'stats' is a non-empty bit set of 1 mean, 2 min, 4 max, 8 std (got {stats})")
+    return tuple(s for q, s in enumerate(_native.PNA_STATS) if stats >> q & 1)
+
+
+@custom_op('pyg_amd::pna_aggregate', mutates_args=(), device_types=_DEV)
+def pna_aggregate(p_src: Tensor, p_dst: Tensor, edge_attr: Optional[Tensor],
+                  wc: Optional[Tensor], rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor],
+                  stats: int) -> Tuple[Tensor, Tensor]:
+    """The statistics of PNAConv's linear message (pna_conv.py:175-188, aggr/scaler.py:82):
+    ``out [n_stats, n_dst, W]``, the planes selected by the bit set ``stats`` (1 mean, 2 min, 4
+    max, 8 std, in that order) of ``p_dst[i] + u_k`` with ``u_k = p_src[col[k]] + wc @
+    edge_attr[edge_id[k]]`` (``edge_attr`` and ``wc`` None: ``u_k = p_src[col[k]]``), exactly 0 for
+    rows without slots; and ``saved [6, n_dst, W]``, the planes the backward reads (no gradient
+    flows through them).  ``edge_id=None``: ``edge_attr`` follows the slots of ``col``."""
+    W = p_src.size(1)
+    De = 0 if wc is None else wc.size(1)
+    if not _native.pna_supported(W, De):
+        raise NotImplementedError(
+            f'pna_aggregate serves W <= 512 and, with edge features, De <= 32 and W * De <= 4096 '
+            f'(got W = {W}, De = {De})')
+    return _native.pna_forward(rowptr, col, edge_id, p_src, p_dst, edge_attr, wc,
+                               _pna_stats(stats), hub=_native.hub_plan(rowptr))
+
+
+@pna_aggregate.register_fake
+def _(p_src, p_dst, edge_attr, wc, rowptr, col, edge_id, stats):
+    n, W = rowptr.numel() - 1, p_src.shape[1]
+    return p_src.new_empty(bin(stats).count('1'), n, W), p_src.new_empty(6, n, W)
+
+
+@custom_op('pyg_amd::pna_aggregate_backward', mutates_args=(), device_types=_DEV)
+def pna_aggregate_backward(grad: Tensor, p_src: Tensor, p_dst: Tensor,
+                           edge_attr: Optional[Tensor], wc: Optional[Tensor], saved: Tensor,
+                           rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor],
+                           stats: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The gradients of ``(p_src, p_dst, edge_attr, wc)`` from ``grad [n_stats, n_dst, W]``; an
+    input that was not given gets an empty tensor."""
+    from ._functions import pna_coefficients
+    names = _pna_stats(stats)
+    n_dst, n_src = rowptr.numel() - 1, p_src.size(0)
+    deg = rowptr[1:] - rowptr[:-1]
+    coef = pna_coefficients(saved, deg, names, grad.unbind(0))
+    rowptr_t, col_t, edge_id_t, hub_t = _by_source(rowptr, col, n_src, edge_id)
+    g_src, g_a, g_wc = _native.pna_backward(rowptr_t, col_t, edge_id_t, p_src, edge_attr, wc, coef,
+                                            names, hub=hub_t)
+    g_dst = grad.new_zeros(p_dst.shape)
+    keep = [q for q, s in enumerate(names) if s != 'std']
+    if keep:
+        g_dst[:n_dst] = grad[keep].sum(0) * (deg > 0).view(-1, 1)
+    none = grad.new_empty(0)
+    return g_src, g_dst, none if g_a is None else g_a, none if g_wc is None else g_wc
+
+
+@pna_aggregate_backward.register_fake
+def _(grad, p_src, p_dst, edge_attr, wc, saved, rowptr, col, edge_id, stats):
+    none = grad.new_empty(0)
+    return (torch.empty_like(p_src, memory_format=torch.contiguous_format),
+            torch.empty_like(p_dst, memory_format=torch.contiguous_format),
+            none if edge_attr is None else torch.empty_like(edge_attr),
+            none if wc is None else torch.empty_like(wc))
+
+
+def _pna_setup(ctx, inputs, output):
+    p_src, p_dst, edge_attr, wc, rowptr, col, edge_id, stats = inputs
+    ctx.stats = stats
+    ctx.given = edge_attr is not None
+    ctx.save_for_backward(p_src, p_dst, edge_attr, wc, output[1], rowptr, col, edge_id)
+
+
+def _pna_bwd(ctx, grad, _grad_saved):
+    p_src, p_dst, edge_attr, wc, saved, rowptr, col, edge_id = ctx.saved_tensors
+    g_src, g_dst, g_a, g_wc = pna_aggregate_backward(
+        grad.contiguous(), p_src, p_dst, edge_attr, wc, saved, rowptr, col, edge_id, ctx.stats)
+    return (g_src, g_dst, g_a if ctx.given else None, g_wc if ctx.given else None, None, None,
+            None, None)
+
+
+register_autograd('pyg_amd::pna_aggregate', _pna_bwd, setup_context=_pna_setup)
+
+
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
 def _hgt_blocks(kqvs, src_pos, F):
     return ([kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos])
@@ -736,4 +822,4 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
        'transformer_attend_backward', 'transformer_edge_attend',
        'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward',
-       'gine_aggregate', 'gine_aggregate_backward')
+       'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward')
