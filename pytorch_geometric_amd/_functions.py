@@ -9,9 +9,8 @@ from torch import Tensor
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-import math
-
-from . import _native
+from . import _native, _onepass
+from ._onepass import Slots, _rows, pna_coefficients  # noqa: F401 (kept importable from here)
 from .edge_index import EdgeIndex
 
 
@@ -24,11 +23,6 @@ def _shaped(out2d: Tensor, shape) -> Tensor:
         return out2d
     assert out2d.is_contiguous() and out2d._base is None
     return out2d.new_empty(0).set_(out2d.untyped_storage(), out2d.storage_offset(), shape)
-
-
-def _rows(t: Tensor) -> Tensor:
-    """[n, ...] -> [n, prod(...)] (also for empty tensors, where reshape(n, -1) is ambiguous)."""
-    return t.reshape(t.size(0), math.prod(t.shape[1:]))
 
 
 class SpmmFunction(Function):
@@ -568,31 +562,38 @@ class GatAttendFunction(Function):
                 g_att_dst.view(att_dst.shape), None, None, None)
 
 
-def _gatv2_backward(ctx, H, C, x_l, x_r, att, alpha, grad_out2, out2, grad_alpha):
-    """The two launches both GATv2 nodes share: by destination (d s, grad_x_r, grad_att), then by
-    source (grad_x_l).  ``grad_alpha`` given = score mode."""
-    graph = ctx.graph
-    fwd = graph.by_dst()
-    grad_s, g_r, g_att = _native.gatv2_backward_dst(
-        fwd.ptr, fwd.idx, x_l, x_r, att, alpha, H, C, ctx.slope, grad_out=grad_out2, out=out2,
-        grad_alpha=grad_alpha, hub=fwd.hub)
-    g_l = None
-    if ctx.needs_input_grad[0]:
-        bwd = graph.by_src()
-        g_l = _native.gatv2_backward_src(bwd.ptr, bwd.idx, graph.src_slot_to_dst_slot(), x_l, x_r,
-                                         att, alpha, grad_s, H, C, ctx.slope, grad_out=grad_out2,
-                                         n_dst=fwd.n_rows, hub=bwd.hub)
-        g_l = g_l.view(-1, H, C)
-    return g_l, g_r.view(-1, H, C), g_att.view(ctx.att_shape)
-
-
-def _gatv2_check(x_l: Tensor, x_r: Tensor, graph: EdgeIndex, n_dst: int):
-    if x_l.size(0) != graph.num_src_nodes:
-        raise ValueError(f"'x_l' has {x_l.size(0)} rows but the graph has "
+def _check_rows(graph: EdgeIndex, n_dst: int, src_name: str, src: Tensor, dst_name: str,
+                dst: Optional[Tensor]):
+    """``src``: one row per source of the graph; ``dst`` (None: not given): >= ``n_dst`` rows"""
+    if src.size(0) != graph.num_src_nodes:
+        raise ValueError(f"'{src_name}' has {src.size(0)} rows but the graph has "
                          f"{graph.num_src_nodes} source nodes")
-    if n_dst != graph.num_dst_nodes or x_r.size(0) < n_dst:
+    if n_dst != graph.num_dst_nodes or (dst is not None and dst.size(0) < n_dst):
         raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = {n_dst}, "
-                         f"'x_r' has {x_r.size(0)} rows")
+                         f"'{dst_name}' has {None if dst is None else dst.size(0)} rows")
+
+
+def _gatv2_forward(ctx, x_l, x_r, att, graph, slope, n_dst, aggregate):
+    """The forward of both GATv2 nodes: ``out [n_dst, H, C]``, or ``alpha`` in the score mode."""
+    _, H, C = x_l.shape
+    _check_rows(graph, n_dst, 'x_l', x_l, 'x_r', x_r)
+    fwd = graph.by_dst()
+    xl2, xr2 = x_l.reshape(-1, H * C), x_r.reshape(-1, H * C)
+    alpha, out = _native.gatv2_forward(fwd.ptr, fwd.idx, xl2, xr2, att, H, C, slope, hub=fwd.hub,
+                                       aggregate=aggregate)
+    ctx.save_for_backward(xl2, xr2, att, alpha, *((out, ) if aggregate else ()))
+    ctx.graph, ctx.slope, ctx.dims, ctx.att_shape = graph, slope, (H, C), att.shape
+    return out.view(fwd.n_rows, H, C) if aggregate else alpha
+
+
+def _gatv2_backward(ctx, x_l, x_r, att, alpha, **grads):
+    """The return tuple of both GATv2 nodes from the flat gradients of the shared body."""
+    H, C = ctx.dims
+    g_l, g_r, g_att = _onepass.gatv2_backward(
+        Slots.of_graph(ctx.graph), x_l, x_r, att, alpha, H, C, ctx.slope,
+        want_x_l=ctx.needs_input_grad[0], **grads)
+    return (None if g_l is None else g_l.view(-1, H, C), g_r.view(-1, H, C),
+            g_att.view(ctx.att_shape), None, None, None)
 
 
 class Gatv2AttendFunction(Function):
@@ -605,24 +606,13 @@ class Gatv2AttendFunction(Function):
     @staticmethod
     def forward(ctx, x_l: Tensor, x_r: Tensor, att: Tensor, graph: EdgeIndex, slope: float,
                 n_dst: int):
-        _, H, C = x_l.shape
-        _gatv2_check(x_l, x_r, graph, n_dst)
-        fwd = graph.by_dst()
-        xl2, xr2 = x_l.reshape(-1, H * C), x_r.reshape(-1, H * C)
-        alpha, out = _native.gatv2_forward(fwd.ptr, fwd.idx, xl2, xr2, att, H, C, slope,
-                                           hub=fwd.hub)
-        ctx.save_for_backward(xl2, xr2, att, alpha, out)
-        ctx.graph, ctx.slope, ctx.dims, ctx.att_shape = graph, slope, (H, C), att.shape
-        return out.view(fwd.n_rows, H, C)
+        return _gatv2_forward(ctx, x_l, x_r, att, graph, slope, n_dst, True)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out: Tensor):
         xl2, xr2, att, alpha, out = ctx.saved_tensors
-        H, C = ctx.dims
-        g_l, g_r, g_att = _gatv2_backward(ctx, H, C, xl2, xr2, att, alpha, _rows(grad_out), out,
-                                          None)
-        return g_l, g_r, g_att, None, None, None
+        return _gatv2_backward(ctx, xl2, xr2, att, alpha, grad_out=_rows(grad_out), out=out)
 
 
 class Gatv2ScoreFunction(Function):
@@ -633,52 +623,33 @@ class Gatv2ScoreFunction(Function):
     @staticmethod
     def forward(ctx, x_l: Tensor, x_r: Tensor, att: Tensor, graph: EdgeIndex, slope: float,
                 n_dst: int):
-        _, H, C = x_l.shape
-        _gatv2_check(x_l, x_r, graph, n_dst)
-        fwd = graph.by_dst()
-        xl2, xr2 = x_l.reshape(-1, H * C), x_r.reshape(-1, H * C)
-        alpha, _ = _native.gatv2_forward(fwd.ptr, fwd.idx, xl2, xr2, att, H, C, slope,
-                                         hub=fwd.hub, aggregate=False)
-        ctx.save_for_backward(xl2, xr2, att, alpha)
-        ctx.graph, ctx.slope, ctx.dims, ctx.att_shape = graph, slope, (H, C), att.shape
-        return alpha
+        return _gatv2_forward(ctx, x_l, x_r, att, graph, slope, n_dst, False)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_alpha: Tensor):
         xl2, xr2, att, alpha = ctx.saved_tensors
-        H, C = ctx.dims
-        g_l, g_r, g_att = _gatv2_backward(ctx, H, C, xl2, xr2, att, alpha, None, None,
-                                          grad_alpha.contiguous())
-        return g_l, g_r, g_att, None, None, None
+        return _gatv2_backward(ctx, xl2, xr2, att, alpha, grad_alpha=grad_alpha.contiguous())
 
 
-def _transformer_check(query: Tensor, key: Tensor, graph: EdgeIndex, n_dst: int):
-    if key.size(0) != graph.num_src_nodes:
-        raise ValueError(f"'key' has {key.size(0)} rows but the graph has "
-                         f"{graph.num_src_nodes} source nodes")
-    if n_dst != graph.num_dst_nodes or query.size(0) < n_dst:
-        raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = {n_dst}, "
-                         f"'query' has {query.size(0)} rows")
+def _key_value(key: Tensor, value: Optional[Tensor], W: int):
+    """``(key, value, packed)`` as ``[N_src, W]`` rows; ``value=None``: the halves of ``key``"""
+    if value is None:
+        kv = key.reshape(-1, 2 * W)
+        return kv[:, :W], kv[:, W:], True
+    return key.reshape(-1, W), value.reshape(-1, W), False
 
 
-def _transformer_backward(ctx, H, C, query, key, value, alpha, grad_out2, out2, grad_alpha,
-                          packed=False):
-    """The two launches both TransformerConv nodes share: by destination (d s, grad_query), then
-    by source (grad_key and, unless in score mode, grad_value).  ``grad_alpha`` given = score
-    mode."""
-    graph = ctx.graph
-    fwd = graph.by_dst()
-    grad_s, g_q = _native.transformer_backward_dst(
-        fwd.ptr, fwd.idx, query, key, value, alpha, H, C, ctx.scale, grad_out=grad_out2,
-        out=out2, grad_alpha=grad_alpha, hub=fwd.hub)
-    g_k = g_v = None
-    if ctx.needs_input_grad[1] or (grad_alpha is None and ctx.needs_input_grad[2]):
-        bwd = graph.by_src()
-        g_k, g_v = _native.transformer_backward_src(
-            bwd.ptr, bwd.idx, graph.src_slot_to_dst_slot(), query, alpha, grad_s, H, C,
-            ctx.scale, grad_out=grad_out2, n_dst=fwd.n_rows, hub=bwd.hub, packed=packed)
-    return g_q, g_k, g_v
+def _transformer_backward(ctx, query, key, value, alpha, want_value=False, **kwargs):
+    """The shared body's five gradients under the public shapes of the four TransformerConv nodes
+    (packed: grad_key is the one ``[N_src, 2, H, C]`` gradient), grad_edge_attr in edge order."""
+    H, C = ctx.dims[:2]
+    g_q, g_k, g_v, g_b, g_a = _onepass.transformer_backward(
+        Slots.of_graph(ctx.graph), query, key, value, alpha, H, C, ctx.scale,
+        want_key=ctx.needs_input_grad[1], want_value=want_value, **kwargs)
+    return (g_q.view(-1, H, C), None if g_k is None else g_k.view(ctx.key_shape),
+            None if g_v is None else g_v.view(ctx.key_shape),
+            None if g_b is None else g_b.view(ctx.bias_shape), _edge_unslot(g_a, ctx.graph))
 
 
 class TransformerAttendFunction(Function):
@@ -695,16 +666,10 @@ class TransformerAttendFunction(Function):
     def forward(ctx, query: Tensor, key: Tensor, value: Optional[Tensor], graph: EdgeIndex,
                 scale: float, n_dst: int):
         _, H, C = query.shape
-        W = H * C
-        _transformer_check(query, key, graph, n_dst)
+        _check_rows(graph, n_dst, 'key', key, 'query', query)
         fwd = graph.by_dst()
-        q2 = query.reshape(-1, W)
-        packed = value is None
-        if packed:
-            kv = key.reshape(-1, 2 * W)
-            k2, v2 = kv[:, :W], kv[:, W:]
-        else:
-            k2, v2 = key.reshape(-1, W), value.reshape(-1, W)
+        q2 = query.reshape(-1, H * C)
+        k2, v2, packed = _key_value(key, value, H * C)
         alpha, out = _native.transformer_forward(fwd.ptr, fwd.idx, q2, k2, v2, H, C, scale,
                                                  hub=fwd.hub)
         ctx.save_for_backward(q2, k2, v2, alpha, out)
@@ -716,14 +681,10 @@ class TransformerAttendFunction(Function):
     @once_differentiable
     def backward(ctx, grad_out: Tensor):
         q2, k2, v2, alpha, out = ctx.saved_tensors
-        H, C = ctx.dims
-        g_q, g_k, g_v = _transformer_backward(ctx, H, C, q2, k2, v2, alpha, _rows(grad_out), out,
-                                              None, packed=ctx.packed)
-        g_q = g_q.view(-1, H, C)
-        if ctx.packed:  # g_k is the one [N_src, 2 * H * C] buffer: grad_key | grad_value
-            return g_q, None if g_k is None else g_k.view(ctx.key_shape), None, None, None, None
-        return (g_q, None if g_k is None else g_k.view(ctx.key_shape),
-                None if g_v is None else g_v.view(ctx.key_shape), None, None, None)
+        g_q, g_k, g_v, _, _ = _transformer_backward(
+            ctx, q2, k2, v2, alpha, ctx.needs_input_grad[2], grad_out=_rows(grad_out), out=out,
+            packed=ctx.packed)
+        return g_q, g_k, g_v, None, None, None
 
 
 class TransformerScoreFunction(Function):
@@ -734,7 +695,7 @@ class TransformerScoreFunction(Function):
     @staticmethod
     def forward(ctx, query: Tensor, key: Tensor, graph: EdgeIndex, scale: float, n_dst: int):
         _, H, C = query.shape
-        _transformer_check(query, key, graph, n_dst)
+        _check_rows(graph, n_dst, 'key', key, 'query', query)
         fwd = graph.by_dst()
         q2, k2 = query.reshape(-1, H * C), key.reshape(-1, H * C)
         alpha, _ = _native.transformer_forward(fwd.ptr, fwd.idx, q2, k2, None, H, C, scale,
@@ -747,11 +708,9 @@ class TransformerScoreFunction(Function):
     @once_differentiable
     def backward(ctx, grad_alpha: Tensor):
         q2, k2, alpha = ctx.saved_tensors
-        H, C = ctx.dims
-        g_q, g_k, _ = _transformer_backward(ctx, H, C, q2, k2, None, alpha, None, None,
-                                            grad_alpha.contiguous())
-        return (g_q.view(-1, H, C), None if g_k is None else g_k.view(ctx.key_shape), None, None,
-                None)
+        g_q, g_k, _, _, _ = _transformer_backward(ctx, q2, k2, None, alpha,
+                                                  grad_alpha=grad_alpha.contiguous())
+        return g_q, g_k, None, None, None
 
 
 def _edge_slots(edge_attr: Tensor, graph: EdgeIndex) -> Tensor:
@@ -773,26 +732,6 @@ def _edge_unslot(grad_slots: Optional[Tensor], graph: EdgeIndex) -> Optional[Ten
     return grad
 
 
-def _transformer_edge_backward(ctx, H, C, query, key, value, ea, bias, alpha, grad_out2, out2,
-                               grad_z2, z2, grad_alpha, want_ga, packed=False):
-    """The two launches both edge nodes share: by destination (d s, grad_query, grad_bias and,
-    if wanted, the slot-ordered grad_edge_attr), then by source, the launch of the nodes without
-    edge features: d s and alpha are all it reads of the edge term."""
-    graph = ctx.graph
-    fwd = graph.by_dst()
-    grad_s, g_q, g_b, g_a = _native.transformer_edge_backward_dst(
-        fwd.ptr, fwd.idx, query, key, value, ea, bias, alpha, H, C, ctx.scale,
-        grad_out=grad_out2, out=out2, grad_z=grad_z2, z=z2, grad_alpha=grad_alpha,
-        want_grad_edge_attr=want_ga, hub=fwd.hub)
-    g_k = g_v = None
-    if ctx.needs_input_grad[1] or (grad_alpha is None and ctx.needs_input_grad[2]):
-        bwd = graph.by_src()
-        g_k, g_v = _native.transformer_backward_src(
-            bwd.ptr, bwd.idx, graph.src_slot_to_dst_slot(), query, alpha, grad_s, H, C,
-            ctx.scale, grad_out=grad_out2, n_dst=fwd.n_rows, hub=bwd.hub, packed=packed)
-    return g_q, g_k, g_v, g_b, _edge_unslot(g_a, graph)
-
-
 class TransformerEdgeAttendFunction(Function):
     """:class:`TransformerAttendFunction` with edge features inside the kernel.  The edge term
     ``W_e a_k`` of key and value (transformer_conv.py:263-283) is linear, so it enters as a
@@ -812,16 +751,10 @@ class TransformerEdgeAttendFunction(Function):
     def forward(ctx, query: Tensor, key: Tensor, value: Optional[Tensor], edge_attr: Tensor,
                 bias: Tensor, graph: EdgeIndex, scale: float, n_dst: int):
         _, H, C = query.shape
-        W = H * C
-        _transformer_check(query, key, graph, n_dst)
+        _check_rows(graph, n_dst, 'key', key, 'query', query)
         fwd = graph.by_dst()
-        q2 = query.reshape(-1, W)
-        packed = value is None
-        if packed:
-            kv = key.reshape(-1, 2 * W)
-            k2, v2 = kv[:, :W], kv[:, W:]
-        else:
-            k2, v2 = key.reshape(-1, W), value.reshape(-1, W)
+        q2 = query.reshape(-1, H * C)
+        k2, v2, packed = _key_value(key, value, H * C)
         ea = _edge_slots(edge_attr, graph)
         De = ea.size(1)
         b2 = bias.reshape(-1, H * De)
@@ -836,13 +769,11 @@ class TransformerEdgeAttendFunction(Function):
     @once_differentiable
     def backward(ctx, grad_out: Tensor, grad_z: Tensor):
         q2, k2, v2, ea, b2, alpha, out, z = ctx.saved_tensors
-        H, C, De = ctx.dims
-        g_q, g_k, g_v, g_b, g_a = _transformer_edge_backward(
-            ctx, H, C, q2, k2, v2, ea, b2, alpha, _rows(grad_out), out, _rows(grad_z), z, None,
-            ctx.needs_input_grad[3], packed=ctx.packed)
-        g_k = None if g_k is None else g_k.view(ctx.key_shape)
-        g_v = None if g_v is None or ctx.packed else g_v.view(ctx.key_shape)
-        return (g_q.view(-1, H, C), g_k, g_v, g_a, g_b.view(ctx.bias_shape), None, None, None)
+        g_q, g_k, g_v, g_b, g_a = _transformer_backward(
+            ctx, q2, k2, v2, alpha, ctx.needs_input_grad[2], grad_out=_rows(grad_out), out=out,
+            edge_attr=ea, bias=b2, grad_z=_rows(grad_z), z=z,
+            want_edge_attr=ctx.needs_input_grad[3], packed=ctx.packed)
+        return g_q, g_k, g_v, g_a, g_b, None, None, None
 
 
 class TransformerEdgeScoreFunction(Function):
@@ -855,7 +786,7 @@ class TransformerEdgeScoreFunction(Function):
     def forward(ctx, query: Tensor, key: Tensor, edge_attr: Tensor, bias: Tensor,
                 graph: EdgeIndex, scale: float, n_dst: int):
         _, H, C = query.shape
-        _transformer_check(query, key, graph, n_dst)
+        _check_rows(graph, n_dst, 'key', key, 'query', query)
         fwd = graph.by_dst()
         q2, k2 = query.reshape(-1, H * C), key.reshape(-1, H * C)
         ea = _edge_slots(edge_attr, graph)
@@ -872,12 +803,10 @@ class TransformerEdgeScoreFunction(Function):
     @once_differentiable
     def backward(ctx, grad_alpha: Tensor):
         q2, k2, ea, b2, alpha = ctx.saved_tensors
-        H, C, De = ctx.dims
-        g_q, g_k, _, g_b, g_a = _transformer_edge_backward(
-            ctx, H, C, q2, k2, None, ea, b2, alpha, None, None, None, None,
-            grad_alpha.contiguous(), ctx.needs_input_grad[2])
-        return (g_q.view(-1, H, C), None if g_k is None else g_k.view(ctx.key_shape), g_a,
-                g_b.view(ctx.bias_shape), None, None, None)
+        g_q, g_k, _, g_b, g_a = _transformer_backward(
+            ctx, q2, k2, None, alpha, grad_alpha=grad_alpha.contiguous(), edge_attr=ea, bias=b2,
+            want_edge_attr=ctx.needs_input_grad[2])
+        return g_q, g_k, g_a, g_b, None, None, None
 
 
 class GineAggregateFunction(Function):
@@ -897,71 +826,23 @@ class GineAggregateFunction(Function):
     def forward(ctx, x_src: Tensor, x_root: Optional[Tensor], eps: Optional[Tensor],
                 edge_attr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
                 graph: EdgeIndex, n_dst: int):
-        if x_src.size(0) != graph.num_src_nodes:
-            raise ValueError(f"'x_src' has {x_src.size(0)} rows but the graph has "
-                             f"{graph.num_src_nodes} source nodes")
-        if n_dst != graph.num_dst_nodes or (x_root is not None and x_root.size(0) < n_dst):
-            raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = "
-                             f"{n_dst}, 'x_root' has "
-                             f"{None if x_root is None else x_root.size(0)} rows")
+        _check_rows(graph, n_dst, 'x_src', x_src, 'x_root', x_root)
         fwd = graph.by_dst()
         eps1 = None if eps is None or x_root is None else eps.reshape(1)
         out = _native.gine_forward(fwd.ptr, fwd.idx, fwd.perm, x_src, x_root, eps1, edge_attr,
                                    weight, bias, hub=fwd.hub)
         ctx.save_for_backward(x_src, x_root, eps, edge_attr, weight, bias)
-        ctx.graph, ctx.n_dst = graph, n_dst
+        ctx.graph = graph
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out: Tensor):
-        x_src, x_root, eps, edge_attr, weight, bias = ctx.saved_tensors
         need = ctx.needs_input_grad
-        grad_out = grad_out.contiguous()
-        g_x = g_a = g_w = g_b = g_root = g_eps = None
-        if need[0] or need[3] or need[4] or need[5]:
-            bwd = ctx.graph.by_src()
-            g_x, g_a, g_w, g_b = _native.gine_backward(
-                bwd.ptr, bwd.idx, bwd.perm, x_src, edge_attr, weight, bias, grad_out,
-                want_grad_edge_attr=need[3], hub=bwd.hub)
-        if x_root is not None:
-            n = ctx.n_dst
-            if need[1]:
-                scale = 1.0 if eps is None else 1.0 + eps.reshape(())
-                g_root = grad_out * scale
-                if x_root.size(0) != n:  # destinations are a prefix: the rest takes no gradient
-                    full = grad_out.new_zeros(x_root.shape)
-                    full[:n] = g_root
-                    g_root = full
-            if eps is not None and need[2]:
-                # row sums in fp32, their total in fp64: one rounding of the whole inner product
-                g_eps = ((grad_out * x_root[:n]).sum(dim=1).double().sum().to(eps.dtype)
-                         .reshape(eps.shape))
-        return (g_x if need[0] else None, g_root, g_eps, g_a if need[3] else None,
-                g_w if need[4] else None, g_b if need[5] else None, None, None)
-
-
-def pna_coefficients(saved: Tensor, deg: Tensor, stats, grads) -> Tensor:
-    """The packed coefficient rows ``[n_dst, 6, W]`` (A, B, Gmin, Gmax, min u, max u) the backward
-    kernel of csrc/pna.hip reads, from the forward's saved planes, the degrees ``deg [n_dst]`` and
-    the incoming gradients of ``stats`` (None: zero).  Per slot the kernel forms ``grad_u = A +
-    B u + Gmin [u == min u] + Gmax [u == max u]``: ``B = g_std / (d std)`` (0 where std was
-    masked), ``A = g_mean / d - B mean_u``, ``Gmin = g_min / cnt_min`` (an even split among
-    ties, as ``scatter_reduce``), ``Gmax`` alike; all 0 for ``d = 0``."""
-    mean_u, min_u, max_u, std, cnt_min, cnt_max = saved.unbind(0)
-    g = dict(zip(stats, grads))
-    d = deg.to(torch.float32).view(-1, 1)
-    has = d > 0
-    zero = torch.zeros_like(mean_u)
-    B = zero
-    if g.get('std') is not None:
-        B = torch.where(std > 0, g['std'] / (d * std), zero)
-    A = -B * mean_u
-    if g.get('mean') is not None:
-        A = A + torch.where(has, g['mean'] / d.clamp(min=1), zero)
-    Gmin = zero if g.get('min') is None else torch.where(has, g['min'] / cnt_min, zero)
-    Gmax = zero if g.get('max') is None else torch.where(has, g['max'] / cnt_max, zero)
-    return torch.stack([A, B, Gmin, Gmax, min_u, max_u], dim=1)
+        return _onepass.gine_backward(
+            Slots.of_graph(ctx.graph), *ctx.saved_tensors, grad_out.contiguous(),
+            want_x_src=need[0], want_root=need[1], want_eps=need[2], want_edge_attr=need[3],
+            want_weight=need[4], want_bias=need[5]) + (None, None)
 
 
 class PnaAggregateFunction(Function):
@@ -979,42 +860,23 @@ class PnaAggregateFunction(Function):
     def forward(ctx, p_src: Tensor, p_dst: Tensor, edge_attr: Optional[Tensor],
                 wc: Optional[Tensor], graph: EdgeIndex, n_dst: int, stats):
         stats = tuple(stats)
-        if p_src.size(0) != graph.num_src_nodes:
-            raise ValueError(f"'p_src' has {p_src.size(0)} rows but the graph has "
-                             f"{graph.num_src_nodes} source nodes")
-        if n_dst != graph.num_dst_nodes or p_dst.size(0) < n_dst:
-            raise ValueError(f"the graph has {graph.num_dst_nodes} destinations: 'n_dst' = "
-                             f"{n_dst}, 'p_dst' has {p_dst.size(0)} rows")
+        _check_rows(graph, n_dst, 'p_src', p_src, 'p_dst', p_dst)
         fwd = graph.by_dst()
         out, saved = _native.pna_forward(fwd.ptr, fwd.idx, fwd.perm, p_src, p_dst, edge_attr, wc,
                                          stats, hub=fwd.hub)
         ctx.save_for_backward(p_src, edge_attr, wc, saved)
-        ctx.graph, ctx.n_dst, ctx.stats, ctx.dst_rows = graph, n_dst, stats, p_dst.size(0)
+        ctx.graph, ctx.stats, ctx.dst_rows = graph, stats, p_dst.size(0)
         order = sorted(stats, key=_native.PNA_STATS.index)
         return tuple(out[order.index(s)] for s in stats)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        p_src, edge_attr, wc, saved = ctx.saved_tensors
         need = ctx.needs_input_grad
-        g_src = g_dst = g_a = g_wc = None
-        ptr = ctx.graph.by_dst().ptr
-        deg = ptr[1:] - ptr[:-1]
-        if need[0] or need[2] or need[3]:
-            coef = pna_coefficients(saved, deg, ctx.stats, grads)
-            bwd = ctx.graph.by_src()
-            g_src, g_a, g_wc = _native.pna_backward(
-                bwd.ptr, bwd.idx, bwd.perm, p_src, edge_attr, wc, coef, ctx.stats,
-                want_grad_edge_attr=need[2], hub=bwd.hub)
-        if need[1]:
-            parts = [g for s, g in zip(ctx.stats, grads) if s != 'std' and g is not None]
-            g_dst = saved.new_zeros(ctx.dst_rows, saved.size(2))
-            if parts:  # (destinations may be a prefix of p_dst's rows: the rest takes no gradient)
-                total = parts[0] if len(parts) == 1 else torch.stack(parts).sum(0)
-                g_dst[:ctx.n_dst] = total * (deg > 0).view(-1, 1)
-        return (g_src if need[0] else None, g_dst, g_a if need[2] else None,
-                g_wc if need[3] else None, None, None, None)
+        return _onepass.pna_backward(
+            Slots.of_graph(ctx.graph), *ctx.saved_tensors, ctx.stats, grads, ctx.dst_rows,
+            want_src=need[0], want_dst=need[1], want_edge_attr=need[2],
+            want_wc=need[3]) + (None, None, None)
 
 
 class HgtRelationPlan:
@@ -1045,8 +907,7 @@ class HGTRelationFunction(Function):
                 raise ValueError(f"every 'kqv' must be [N, {3 * F}] (got {tuple(x.shape)})")
         kqvs = tuple(_native._f32_rows(x, 'kqv') for x in kqvs)
         wk, wv = wk.contiguous(), wv.contiguous()
-        ks = [kqvs[p][:, :F] for p in plan.src_pos]
-        vs = [kqvs[p][:, 2 * F:] for p in plan.src_pos]
+        ks, vs = _onepass.hgt_blocks(kqvs, plan.src_pos, F)
         kv = _native.hgt_relation_forward(ks, vs, plan.widx, wk, wv, H, D)
         ctx.save_for_backward(wk, wv, *kqvs)
         ctx.plan = plan
@@ -1056,20 +917,10 @@ class HGTRelationFunction(Function):
     @once_differentiable
     def backward(ctx, grad_kv: Tensor):
         wk, wv, *kqvs = ctx.saved_tensors
-        plan = ctx.plan
-        H, D = plan.heads, wk.size(-1)
-        F = H * D
-        ks = [kqvs[p][:, :F] for p in plan.src_pos]
-        vs = [kqvs[p][:, 2 * F:] for p in plan.src_pos]
-        bufs = []
-        if any(ctx.needs_input_grad[3:]):
-            bufs = [torch.empty_like(x, memory_format=torch.contiguous_format) for x in kqvs]
-            for b in bufs:
-                b[:, F:2 * F].zero_()
-        g_wk, g_wv = _native.hgt_relation_backward(
-            ks, vs, plan.widx, plan.src_pos, wk, wv, H, D, grad_kv,
-            [b[:, :F] for b in bufs], [b[:, 2 * F:] for b in bufs],
-            weight_grads=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        plan, need = ctx.plan, ctx.needs_input_grad
+        bufs, g_wk, g_wv = _onepass.hgt_backward(
+            kqvs, wk, wv, plan.src_pos, plan.widx, plan.heads, grad_kv, want_kqvs=any(need[3:]),
+            want_weights=need[1] or need[2])
         return (None, g_wk, g_wv) + (tuple(bufs) if bufs else (None, ) * len(kqvs))
 
 

@@ -119,6 +119,30 @@ def _dense_rows(t: Tensor, name: str, width: int) -> Tensor:
     return _strided_rows(t, name, width).contiguous()
 
 
+def _grad_rows(rows: int, n_rows: int, width: int, device) -> Tensor:
+    """An uninitialised ``[rows, width]`` gradient whose first ``n_rows`` rows a kernel writes;
+    rows beyond them (destinations may be a prefix of the tensor's rows) take no gradient: 0."""
+    alloc = torch.empty if rows == n_rows else torch.zeros
+    return alloc(rows, width, dtype=torch.float32, device=device)
+
+
+def _edge_rows(edge_attr: Tensor, E: int, width: str = 'De') -> Tensor:
+    """``edge_attr`` checked to be a float32 ``[E, .]`` tensor, contiguous."""
+    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != E:
+        raise ValueError(f"'edge_attr' must be a float32 [{E}, {width}] tensor (got "
+                         f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
+    return edge_attr.contiguous()
+
+
+def _edge_id(edge_id: Optional[Tensor], rowptr: Tensor, col: Tensor, name: str = 'edge_id'):
+    """The slot -> edge map of a handle (None: the slots are the edges) checked, contiguous."""
+    if edge_id is None:
+        return None
+    if edge_id.dtype != rowptr.dtype or edge_id.numel() != col.numel():
+        raise ValueError(f"'{name}' must have the index dtype and one entry per slot")
+    return edge_id.contiguous()
+
+
 # ---- integer side --------------------------------------------------------------------------------
 def index_sort(keys: Tensor, max_value: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     _require_device(keys)
@@ -1186,9 +1210,7 @@ def gatv2_backward_dst(rowptr: Tensor, col: Tensor, x_l: Tensor, x_r: Tensor, at
         grad_alpha = grad_alpha.contiguous()
     g = _csr(rowptr, col, n_rows, hub)
     grad_s = torch.empty_like(alpha)
-    # (destinations may be a prefix of the rows of x_r: the rest takes no gradient)
-    alloc = torch.empty if x_r.size(0) == n_rows else torch.zeros
-    grad_x_r = alloc(x_r.size(0), W, dtype=torch.float32, device=x_l.device)
+    grad_x_r = _grad_rows(x_r.size(0), n_rows, W, x_l.device)
     grad_att = torch.empty(W, dtype=torch.float32, device=x_l.device)
     if col.numel() == 0:
         return grad_s, grad_x_r.zero_(), grad_att.zero_()
@@ -1302,9 +1324,7 @@ def transformer_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, key: Te
         grad_out, out = _dense_rows(grad_out, 'grad_out', W), _dense_rows(out, 'out', W)
     g = _csr(rowptr, col, n_rows, hub)
     grad_s = torch.empty_like(alpha)
-    # (destinations may be a prefix of the rows of query: the rest takes no gradient)
-    alloc = torch.empty if query.size(0) == n_rows else torch.zeros
-    grad_query = alloc(query.size(0), W, dtype=torch.float32, device=key.device)
+    grad_query = _grad_rows(query.size(0), n_rows, W, key.device)
     if col.numel() == 0:
         return grad_s, grad_query.zero_()
     ws, ws_bytes = _workspace(lib.pygamd_transformer_workspace_bytes, (g.n_chunks, H, C),
@@ -1390,12 +1410,9 @@ def transformer_edge_forward(rowptr: Tensor, col: Tensor, query: Tensor, key: Te
     query = _dense_rows(query, 'query', W)
     key, value, ld = _key_value(key, value if aggregate else None, W)
     n_rows = rowptr.numel() - 1
-    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 \
-            or edge_attr.size(0) != col.numel():
-        raise ValueError(f"'edge_attr' must be a float32 [{col.numel()}, De] tensor (got "
-                         f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
+    edge_attr = _edge_rows(edge_attr, col.numel())
     De = edge_attr.size(1)
-    edge_attr, bias = edge_attr.contiguous(), _dense_rows(bias, 'bias', H * De)
+    bias = _dense_rows(bias, 'bias', H * De)
     if query.size(0) < n_rows or bias.size(0) < n_rows:
         raise ValueError(f"'query' and 'bias' need at least {n_rows} rows")
     g = _csr(rowptr, col, n_rows, hub)
@@ -1446,12 +1463,9 @@ def transformer_edge_backward_dst(rowptr: Tensor, col: Tensor, query: Tensor, ke
         grad_z, z = _dense_rows(grad_z, 'grad_z', Z), _dense_rows(z, 'z', Z)
     g = _csr(rowptr, col, n_rows, hub)
     grad_s = torch.empty_like(alpha)
-    # (destinations may be a prefix of the rows of query and bias: the rest takes no gradient)
     dev = key.device
-    alloc = torch.empty if query.size(0) == n_rows else torch.zeros
-    grad_query = alloc(query.size(0), W, dtype=torch.float32, device=dev)
-    alloc = torch.empty if bias.size(0) == n_rows else torch.zeros
-    grad_bias = alloc(bias.size(0), Z, dtype=torch.float32, device=dev)
+    grad_query = _grad_rows(query.size(0), n_rows, W, dev)
+    grad_bias = _grad_rows(bias.size(0), n_rows, Z, dev)
     grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
     if col.numel() == 0:
         return grad_s, grad_query.zero_(), grad_bias.zero_(), grad_edge
@@ -1479,24 +1493,21 @@ def gine_supported(F: int, De: int = 0) -> bool:
 def _gine_edge(edge_attr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], F: int,
                E: int):
     """(edge_attr, weight, bias, De) checked: wide mode without ``weight`` (``De = 0``)."""
-    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != E:
-        raise ValueError(f"'edge_attr' must be a float32 [{E}, width] tensor (got "
-                         f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
+    edge_attr = _edge_rows(edge_attr, E, 'width')
     if weight is None:
         if bias is not None:
             raise ValueError("'bias' needs 'weight'")
         if edge_attr.size(1) != F:
             raise ValueError(f"without 'weight' the edge features need width {F} (got "
                              f"{edge_attr.size(1)})")
-        return edge_attr.contiguous(), None, None, 0
+        return edge_attr, None, None, 0
     De = edge_attr.size(1)
     if weight.dtype != torch.float32 or tuple(weight.shape) != (F, De) or De < 1:
         raise ValueError(f"'weight' must be float32 [{F}, {De}] (got {weight.dtype} "
                          f"{tuple(weight.shape)})")
     if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (F,)):
         raise ValueError(f"'bias' must be float32 [{F}]")
-    return (edge_attr.contiguous(), weight.contiguous(),
-            None if bias is None else bias.contiguous(), De)
+    return edge_attr, weight.contiguous(), None if bias is None else bias.contiguous(), De
 
 
 def _gine_no_edges(rowptr: Tensor, x: Tensor):
@@ -1528,10 +1539,7 @@ def gine_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], x_src: 
     else:
         eps = None
     edge_attr, weight, bias, De = _gine_edge(edge_attr, weight, bias, F, col.numel())
-    if edge_id is not None:
-        if edge_id.dtype != rowptr.dtype or edge_id.numel() != col.numel():
-            raise ValueError("'edge_id' must have the index dtype and one entry per slot")
-        edge_id = edge_id.contiguous()
+    edge_id = _edge_id(edge_id, rowptr, col)
     out = torch.empty(n_rows, F, dtype=torch.float32, device=x_src.device)
     if n_rows == 0:
         return out
@@ -1565,10 +1573,7 @@ def gine_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], 
     if x_src.size(0) != n_src:
         raise ValueError(f"'x_src' needs {n_src} rows")
     edge_attr, weight, bias, De = _gine_edge(edge_attr, weight, bias, F, col_t.numel())
-    if edge_id_t is not None:
-        if edge_id_t.dtype != rowptr_t.dtype or edge_id_t.numel() != col_t.numel():
-            raise ValueError("'edge_id_t' must have the index dtype and one entry per slot")
-        edge_id_t = edge_id_t.contiguous()
+    edge_id_t = _edge_id(edge_id_t, rowptr_t, col_t, 'edge_id_t')
     dev = x_src.device
     grad_x = torch.empty(n_src, F, dtype=torch.float32, device=dev)
     grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
@@ -1617,21 +1622,11 @@ def _pna_edge(edge_attr: Optional[Tensor], wc: Optional[Tensor], W: int, E: int)
         raise ValueError("'edge_attr' and 'wc' come together")
     if wc is None:
         return None, None, 0
-    if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.size(0) != E:
-        raise ValueError(f"'edge_attr' must be a float32 [{E}, De] tensor (got "
-                         f"{edge_attr.dtype} {tuple(edge_attr.shape)})")
+    edge_attr = _edge_rows(edge_attr, E)
     De = edge_attr.size(1)
     if wc.dtype != torch.float32 or tuple(wc.shape) != (W, De) or De < 1:
         raise ValueError(f"'wc' must be float32 [{W}, {De}] (got {wc.dtype} {tuple(wc.shape)})")
-    return edge_attr.contiguous(), wc.contiguous(), De
-
-
-def _pna_edge_id(edge_id: Optional[Tensor], rowptr: Tensor, col: Tensor):
-    if edge_id is None:
-        return None
-    if edge_id.dtype != rowptr.dtype or edge_id.numel() != col.numel():
-        raise ValueError("'edge_id' must have the index dtype and one entry per slot")
-    return edge_id.contiguous()
+    return edge_attr, wc.contiguous(), De
 
 
 def pna_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], p_src: Tensor,
@@ -1654,7 +1649,7 @@ def pna_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], p_src: T
     if p_dst.size(0) < n_rows:
         raise ValueError(f"'p_dst' needs at least {n_rows} rows")
     edge_attr, wc, De = _pna_edge(edge_attr, wc, W, col.numel())
-    edge_id = _pna_edge_id(edge_id, rowptr, col)
+    edge_id = _edge_id(edge_id, rowptr, col)
     dev = p_src.device
     n_sel = bin(mask).count('1')
     if n_rows == 0 or col.numel() == 0:  # no slot anywhere: every statistic is 0, nothing to launch
@@ -1696,7 +1691,7 @@ def pna_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], p
                          f"{tuple(coef.shape)})")
     coef = coef.contiguous()
     edge_attr, wc, De = _pna_edge(edge_attr, wc, W, col_t.numel())
-    edge_id_t = _pna_edge_id(edge_id_t, rowptr_t, col_t)
+    edge_id_t = _edge_id(edge_id_t, rowptr_t, col_t)
     want_grad_edge_attr = bool(want_grad_edge_attr) and De > 0
     dev = p_src.device
     if n_src == 0 or col_t.numel() == 0:

@@ -1,0 +1,213 @@
+"""The backward of every one-pass operator family, written once for its two autograd routes: the
+``torch.autograd.Function`` classes of ``_functions.py`` on the cached sorted forms of an
+``EdgeIndex`` and the ``torch.ops.pyg_amd.*_backward`` operators of ``ops.py`` on ``(rowptr, col[,
+edge_id])``.  A route hands over its :class:`Slots`, flat 2-D tensors and the gradients it wants."""
+import functools
+import math
+
+import torch
+
+from . import _native
+
+
+def _rows(t):
+    """[n, ...] -> [n, prod(...)] (also for empty tensors, where reshape(n, -1) is ambiguous)."""
+    return t.reshape(t.size(0), math.prod(t.shape[1:]))
+
+
+class _Form:
+    """One sorted form given as its tensors; the hub plan is made when it is first read."""
+
+    def __init__(self, ptr, idx, perm=None):
+        self.ptr, self.idx, self.perm, self.n_rows = ptr, idx, perm, ptr.numel() - 1
+
+    @functools.cached_property
+    def hub(self):
+        return _native.hub_plan(self.ptr)
+
+
+class Slots:
+    """The slots of a graph by destination (``fwd``: ``ptr``, ``idx``, ``hub``, ``n_rows``) and,
+    built when first asked for, by source.  Each route keeps ITS by-source form: for an edge list
+    not sorted by destination the two order the slots of a source differently (last-bit sums)."""
+
+    def __init__(self, fwd, graph=None, n_src=0, edge_id=None):
+        self.fwd, self._graph, self._n_src, self._edge_id = fwd, graph, n_src, edge_id
+
+    @classmethod
+    def of_graph(cls, graph):  # the cached sorted forms, hub plans and slot map of an EdgeIndex
+        return cls(graph.by_dst(), graph=graph)
+
+    @classmethod
+    def of_csr(cls, rowptr, col, n_src, edge_id=None):  # edge_id: slot -> edge (None: identity)
+        return cls(_Form(rowptr, col), n_src=n_src, edge_id=edge_id)
+
+    @functools.cached_property
+    def _sorted(self):
+        """The by-source form of a CSR pair: a stable sort of ``col``, whose permutation (``perm``,
+        int64) IS the map from by-source slots to the pair's own slots."""
+        ptr, col = self.fwd.ptr, self.fwd.idx
+        dst = _native.ptr2index(ptr, col.numel())
+        src_sorted, perm = _native.index_sort(col, max_value=max(self._n_src - 1, 0))
+        return _Form(_native.index2ptr(src_sorted, self._n_src), _native.permute_index(dst, perm),
+                     perm)
+
+    def by_src(self):
+        """``ptr``, ``idx`` and ``hub`` of the same slots sorted by source"""
+        return self._sorted if self._graph is None else self._graph.by_src()
+
+    def slot_map(self):
+        """by-source slot -> by-destination slot: where the attention kernels find ``alpha``"""
+        if self._graph is not None:
+            return self._graph.src_slot_to_dst_slot()
+        return _native.cast_index(self._sorted.perm, self.fwd.idx.dtype)
+
+    def edge_id_t(self):
+        """by-source slot -> the caller's edge"""
+        if self._graph is not None:
+            return self._graph.by_src().perm
+        if self._edge_id is None:
+            return self.slot_map()
+        return _native.permute_index(self._edge_id, self._sorted.perm)
+
+
+def gatv2_backward(slots, x_l, x_r, att, alpha, H, C, slope, *, grad_out=None, out=None,
+                   grad_alpha=None, want_x_l=True):
+    """``(grad_x_l | None, grad_x_r, grad_att)``, flat: one launch by destination, then one by
+    source (grad_x_l).  ``grad_alpha`` given = score mode, otherwise ``grad_out`` and ``out``."""
+    fwd = slots.fwd
+    grad_s, g_r, g_att = _native.gatv2_backward_dst(
+        fwd.ptr, fwd.idx, x_l, x_r, att, alpha, H, C, slope, grad_out=grad_out, out=out,
+        grad_alpha=grad_alpha, hub=fwd.hub)
+    g_l = None
+    if want_x_l:
+        bwd = slots.by_src()
+        g_l = _native.gatv2_backward_src(bwd.ptr, bwd.idx, slots.slot_map(), x_l, x_r, att, alpha,
+                                         grad_s, H, C, slope, grad_out=grad_out,
+                                         n_dst=fwd.n_rows, hub=bwd.hub)
+    return g_l, g_r, g_att
+
+
+def transformer_backward(slots, query, key, value, alpha, H, C, scale, *, grad_out=None, out=None,
+                         grad_alpha=None, edge_attr=None, bias=None, grad_z=None, z=None,
+                         want_key=True, want_value=True, want_edge_attr=True, packed=False):
+    """``(grad_query, grad_key, grad_value, grad_bias, grad_edge_attr)``, flat, None where not
+    computed: one launch by destination, then one by source (grad_key and, unless in score mode,
+    grad_value; ``packed``: both in one buffer).  ``grad_alpha`` given = score mode.  ``edge_attr``
+    (slot order) given = the edge variant: its by-destination launch also returns grad_bias and, if
+    wanted, grad_edge_attr in slot order; the by-source launch reads d s and alpha alone."""
+    fwd = slots.fwd
+    g_b = g_a = None
+    if edge_attr is None:
+        grad_s, g_q = _native.transformer_backward_dst(
+            fwd.ptr, fwd.idx, query, key, value, alpha, H, C, scale, grad_out=grad_out, out=out,
+            grad_alpha=grad_alpha, hub=fwd.hub)
+    else:
+        grad_s, g_q, g_b, g_a = _native.transformer_edge_backward_dst(
+            fwd.ptr, fwd.idx, query, key, value, edge_attr, bias, alpha, H, C, scale,
+            grad_out=grad_out, out=out, grad_z=grad_z, z=z, grad_alpha=grad_alpha,
+            want_grad_edge_attr=want_edge_attr, hub=fwd.hub)
+    g_k = g_v = None
+    if want_key or (grad_alpha is None and want_value):
+        bwd = slots.by_src()
+        g_k, g_v = _native.transformer_backward_src(
+            bwd.ptr, bwd.idx, slots.slot_map(), query, alpha, grad_s, H, C, scale,
+            grad_out=grad_out, n_dst=fwd.n_rows, hub=bwd.hub, packed=packed)
+    return g_q, g_k, g_v, g_b, g_a
+
+
+def gine_backward(slots, x_src, x_root, eps, edge_attr, weight, bias, grad_out, *, want_x_src=True,
+                  want_root=True, want_eps=True, want_edge_attr=True, want_weight=True,
+                  want_bias=True):
+    """``(grad_x_src, grad_x_root, grad_eps, grad_edge_attr, grad_weight, grad_bias)``, None where
+    not wanted or not given: one launch by source and the self term elementwise."""
+    g_x = g_a = g_w = g_b = g_root = g_eps = None
+    if want_x_src or want_edge_attr or want_weight or want_bias:
+        bwd = slots.by_src()
+        g_x, g_a, g_w, g_b = _native.gine_backward(
+            bwd.ptr, bwd.idx, slots.edge_id_t(), x_src, edge_attr, weight, bias, grad_out,
+            want_grad_edge_attr=want_edge_attr, hub=bwd.hub)
+    if x_root is not None:
+        n = slots.fwd.n_rows
+        if want_root:
+            g_root = grad_out * (1.0 if eps is None else 1.0 + eps.reshape(()))
+            if x_root.size(0) != n:  # destinations are a prefix: the rest takes no gradient
+                full = grad_out.new_zeros(x_root.shape)
+                full[:n] = g_root
+                g_root = full
+        if eps is not None and want_eps:
+            # row sums in fp32, their total in fp64: one rounding of the whole inner product
+            g_eps = ((grad_out * x_root[:n]).sum(dim=1).double().sum().to(eps.dtype)
+                     .reshape(eps.shape))
+    return (g_x if want_x_src else None, g_root, g_eps, g_a if want_edge_attr else None,
+            g_w if want_weight else None, g_b if want_bias else None)
+
+
+def pna_coefficients(saved, deg, stats, grads):
+    """The packed coefficient rows ``[n_dst, 6, W]`` (A, B, Gmin, Gmax, min u, max u) the backward
+    kernel of csrc/pna.hip reads, from the forward's saved planes, the degrees ``deg [n_dst]`` and
+    the incoming gradients of ``stats`` (None: zero).  Per slot the kernel forms ``grad_u = A +
+    B u + Gmin [u == min u] + Gmax [u == max u]``: ``B = g_std / (d std)`` (0 where std was
+    masked), ``A = g_mean / d - B mean_u``, ``Gmin = g_min / cnt_min`` (an even split among
+    ties, as ``scatter_reduce``), ``Gmax`` alike; all 0 for ``d = 0``."""
+    mean_u, min_u, max_u, std, cnt_min, cnt_max = saved.unbind(0)
+    g = dict(zip(stats, grads))
+    d = deg.to(torch.float32).view(-1, 1)
+    has = d > 0
+    zero = torch.zeros_like(mean_u)
+    B = zero
+    if g.get('std') is not None:
+        B = torch.where(std > 0, g['std'] / (d * std), zero)
+    A = -B * mean_u
+    if g.get('mean') is not None:
+        A = A + torch.where(has, g['mean'] / d.clamp(min=1), zero)
+    Gmin = zero if g.get('min') is None else torch.where(has, g['min'] / cnt_min, zero)
+    Gmax = zero if g.get('max') is None else torch.where(has, g['max'] / cnt_max, zero)
+    return torch.stack([A, B, Gmin, Gmax, min_u, max_u], dim=1)
+
+
+def pna_backward(slots, p_src, edge_attr, wc, saved, stats, grads, dst_rows, *, want_src=True,
+                 want_dst=True, want_edge_attr=True, want_wc=True):
+    """``(grad_p_src, grad_p_dst [dst_rows, W], grad_edge_attr, grad_wc)``, None where not wanted
+    or not given: :func:`pna_coefficients` of ``grads`` (one per statistic of ``stats``) and one
+    launch by source.  ``p_dst`` takes the gradients of every statistic but std, added in the order
+    of ``stats``: the caller's on the handle route, the kernel's on the operator route, as ever."""
+    ptr = slots.fwd.ptr
+    deg = ptr[1:] - ptr[:-1]
+    g_src = g_dst = g_a = g_wc = None
+    if want_src or want_edge_attr or want_wc:
+        coef = pna_coefficients(saved, deg, stats, grads)
+        bwd = slots.by_src()
+        g_src, g_a, g_wc = _native.pna_backward(
+            bwd.ptr, bwd.idx, slots.edge_id_t(), p_src, edge_attr, wc, coef, stats,
+            want_grad_edge_attr=want_edge_attr, hub=bwd.hub)
+    if want_dst:
+        g_dst = saved.new_zeros(dst_rows, saved.size(2))
+        parts = [g for s, g in zip(stats, grads) if s != 'std' and g is not None]
+        if parts:  # (destinations may be a prefix of p_dst's rows: the rest takes no gradient)
+            total = parts[0] if len(parts) == 1 else torch.stack(parts).sum(0)
+            g_dst[:slots.fwd.n_rows] = total * (deg > 0).view(-1, 1)
+    return (g_src if want_src else None, g_dst, g_a if want_edge_attr else None,
+            g_wc if want_wc else None)
+
+
+def hgt_blocks(kqvs, src_pos, F):
+    """``(ks, vs)`` per edge type: the key and value column blocks of its ``[N, 3 * F]`` source"""
+    return [kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos]
+
+
+def hgt_backward(kqvs, wk, wv, src_pos, widx, H, grad_kv, *, want_kqvs=True, want_weights=True):
+    """``(grad_kqvs | [], grad_wk, grad_wv)`` in one launch: one ``[N_t, 3 * F]`` buffer per node
+    type takes the k and v gradients; its q block is cleared."""
+    D = wk.size(-1)
+    F = H * D
+    ks, vs = hgt_blocks(kqvs, src_pos, F)
+    bufs = []
+    if want_kqvs:
+        bufs = [torch.empty_like(x, memory_format=torch.contiguous_format) for x in kqvs]
+        for b in bufs:
+            b[:, F:2 * F].zero_()
+    g_wk, g_wv = _native.hgt_relation_backward(
+        ks, vs, widx, src_pos, wk, wv, H, D, grad_kv, [b[:, :F] for b in bufs],
+        [b[:, 2 * F:] for b in bufs], weight_grads=want_weights)
+    return bufs, g_wk, g_wv

@@ -44,22 +44,17 @@ Operators (all index tensors int32 / int64, features float32):
                             -> (Tensor out, Tensor saved)``
 ==========================  ===========================================================
 """
-import math
 from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
 from torch.library import custom_op, register_autograd
 
-from . import _native
+from . import _native, _onepass
+from ._onepass import Slots, _rows
 
 _DEV = 'cuda'
 _REDUCES = ('sum', 'mean', 'min', 'max', 'mul')
-
-
-def _rows(t: Tensor) -> Tensor:
-    """[n, ...] -> [n, prod(...)] (well defined for empty tensors too)."""
-    return t.reshape(t.size(0), math.prod(t.shape[1:]))
 
 
 # ---- integer side (no gradients) ---------------------------------------------------------------
@@ -382,20 +377,6 @@ def _linear_bwd(ctx, grad):
 
 register_autograd('pyg_amd::linear', _linear_bwd, setup_context=_linear_setup)
 
-def _by_source(rowptr: Tensor, col: Tensor, n_src: int, edge_id: Optional[Tensor] = None):
-    """``(rowptr_t, col_t, slot_map, hub)``: the by-source form of the slots of a by-destination
-    CSR, which the backward passes over the sources walk.  A stable sort of ``col``; its
-    permutation IS the map from by-source slots to the CSR's own slots (``slot_map``), and
-    through ``edge_id``, where given, to the caller's edges."""
-    dst = _native.ptr2index(rowptr, col.numel())
-    src_sorted, perm = _native.index_sort(col, max_value=max(n_src - 1, 0))
-    rowptr_t = _native.index2ptr(src_sorted, n_src)
-    col_t = _native.permute_index(dst, perm)
-    slot_map = (_native.cast_index(perm, col.dtype) if edge_id is None
-                else _native.permute_index(edge_id, perm))
-    return rowptr_t, col_t, slot_map, _native.hub_plan(rowptr_t)
-
-
 # ---- GATv2 attention on a CSR pair (rows = destinations) -----------------------------------------
 @custom_op('pyg_amd::gatv2_attend', mutates_args=(), device_types=_DEV)
 def gatv2_attend(x_l: Tensor, x_r: Tensor, att: Tensor, rowptr: Tensor, col: Tensor,
@@ -422,15 +403,9 @@ def gatv2_attend_backward(grad: Tensor, x_l: Tensor, x_r: Tensor, att: Tensor, a
                           out: Tensor, rowptr: Tensor, col: Tensor,
                           negative_slope: float) -> Tuple[Tensor, Tensor, Tensor]:
     _, H, C = x_l.shape
-    n_dst = rowptr.numel() - 1
-    xl2, xr2 = _rows(x_l), _rows(x_r)
-    grad_s, g_r, g_att = _native.gatv2_backward_dst(
-        rowptr, col, xl2, xr2, att, alpha, H, C, negative_slope,
-        grad_out=_rows(grad).contiguous(), out=_rows(out), hub=_native.hub_plan(rowptr))
-    rowptr_t, col_t, slot_map, hub_t = _by_source(rowptr, col, x_l.size(0))
-    g_l = _native.gatv2_backward_src(rowptr_t, col_t, slot_map, xl2, xr2, att, alpha, grad_s, H, C,
-                                     negative_slope, grad_out=_rows(grad).contiguous(),
-                                     n_dst=n_dst, hub=hub_t)
+    g_l, g_r, g_att = _onepass.gatv2_backward(
+        Slots.of_csr(rowptr, col, x_l.size(0)), _rows(x_l), _rows(x_r), att, alpha, H, C,
+        negative_slope, grad_out=_rows(grad).contiguous(), out=_rows(out))
     return g_l.reshape(x_l.shape), g_r.reshape(x_r.shape), g_att.reshape(att.shape)
 
 
@@ -482,14 +457,9 @@ def transformer_attend_backward(grad: Tensor, query: Tensor, key: Tensor, value:
                                 alpha: Tensor, out: Tensor, rowptr: Tensor, col: Tensor,
                                 scale: float) -> Tuple[Tensor, Tensor, Tensor]:
     _, H, C = query.shape
-    n_dst = rowptr.numel() - 1
-    q2, g2 = _rows(query), _rows(grad).contiguous()
-    grad_s, g_q = _native.transformer_backward_dst(
-        rowptr, col, q2, _rows(key), _rows(value), alpha, H, C, scale, grad_out=g2,
-        out=_rows(out), hub=_native.hub_plan(rowptr))
-    rowptr_t, col_t, slot_map, hub_t = _by_source(rowptr, col, key.size(0))
-    g_k, g_v = _native.transformer_backward_src(rowptr_t, col_t, slot_map, q2, alpha, grad_s, H, C,
-                                                scale, grad_out=g2, n_dst=n_dst, hub=hub_t)
+    g_q, g_k, g_v, _, _ = _onepass.transformer_backward(
+        Slots.of_csr(rowptr, col, key.size(0)), _rows(query), _rows(key), _rows(value), alpha, H,
+        C, scale, grad_out=_rows(grad).contiguous(), out=_rows(out))
     return g_q.reshape(query.shape), g_k.reshape(key.shape), g_v.reshape(value.shape)
 
 
@@ -552,15 +522,10 @@ def transformer_edge_attend_backward(grad: Tensor, grad_z: Tensor, query: Tensor
                                      col: Tensor, scale: float
                                      ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     _, H, C = query.shape
-    n_dst = rowptr.numel() - 1
-    q2, g2 = _rows(query), _rows(grad).contiguous()
-    grad_s, g_q, g_b, g_a = _native.transformer_edge_backward_dst(
-        rowptr, col, q2, _rows(key), _rows(value), edge_attr, _rows(bias), alpha, H, C, scale,
-        grad_out=g2, out=_rows(out), grad_z=_rows(grad_z).contiguous(), z=_rows(z),
-        hub=_native.hub_plan(rowptr))
-    rowptr_t, col_t, slot_map, hub_t = _by_source(rowptr, col, key.size(0))
-    g_k, g_v = _native.transformer_backward_src(rowptr_t, col_t, slot_map, q2, alpha, grad_s, H, C,
-                                                scale, grad_out=g2, n_dst=n_dst, hub=hub_t)
+    g_q, g_k, g_v, g_b, g_a = _onepass.transformer_backward(
+        Slots.of_csr(rowptr, col, key.size(0)), _rows(query), _rows(key), _rows(value), alpha, H,
+        C, scale, grad_out=_rows(grad).contiguous(), out=_rows(out), edge_attr=edge_attr,
+        bias=_rows(bias), grad_z=_rows(grad_z).contiguous(), z=_rows(z))
     return (g_q.reshape(query.shape), g_k.reshape(key.shape), g_v.reshape(value.shape), g_a,
             g_b.reshape(bias.shape))
 
@@ -624,19 +589,10 @@ def gine_aggregate_backward(grad: Tensor, x_src: Tensor, x_root: Optional[Tensor
                             ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
     """The gradients of ``(x_src, x_root, eps, edge_attr, weight, bias)``; an input that was not
     given gets an empty tensor."""
-    n_dst, n_src = rowptr.numel() - 1, x_src.size(0)
-    rowptr_t, col_t, edge_id_t, hub_t = _by_source(rowptr, col, n_src, edge_id)
-    g_x, g_a, g_w, g_b = _native.gine_backward(rowptr_t, col_t, edge_id_t, x_src, edge_attr,
-                                               weight, bias, grad, hub=hub_t)
-    none = grad.new_empty(0)
-    g_root = g_eps = none
-    if x_root is not None:
-        g_root = grad.new_zeros(x_root.shape)
-        g_root[:n_dst] = grad if eps is None else grad * (1.0 + eps.reshape(()))
-        if eps is not None:
-            g_eps = ((grad * x_root[:n_dst]).sum(dim=1).double().sum().to(eps.dtype)
-                     .reshape(eps.shape))
-    return (g_x, g_root, g_eps, g_a, none if g_w is None else g_w, none if g_b is None else g_b)
+    grads = _onepass.gine_backward(Slots.of_csr(rowptr, col, x_src.size(0), edge_id), x_src,
+                                   x_root, eps, edge_attr, weight, bias, grad)
+    # (one empty tensor EACH: an operator's outputs must not alias one another)
+    return tuple(grad.new_empty(0) if g is None else g for g in grads)
 
 
 @gine_aggregate_backward.register_fake
@@ -707,20 +663,11 @@ def pna_aggregate_backward(grad: Tensor, p_src: Tensor, p_dst: Tensor,
                            stats: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """The gradients of ``(p_src, p_dst, edge_attr, wc)`` from ``grad [n_stats, n_dst, W]``; an
     input that was not given gets an empty tensor."""
-    from ._functions import pna_coefficients
-    names = _pna_stats(stats)
-    n_dst, n_src = rowptr.numel() - 1, p_src.size(0)
-    deg = rowptr[1:] - rowptr[:-1]
-    coef = pna_coefficients(saved, deg, names, grad.unbind(0))
-    rowptr_t, col_t, edge_id_t, hub_t = _by_source(rowptr, col, n_src, edge_id)
-    g_src, g_a, g_wc = _native.pna_backward(rowptr_t, col_t, edge_id_t, p_src, edge_attr, wc, coef,
-                                            names, hub=hub_t)
-    g_dst = grad.new_zeros(p_dst.shape)
-    keep = [q for q, s in enumerate(names) if s != 'std']
-    if keep:
-        g_dst[:n_dst] = grad[keep].sum(0) * (deg > 0).view(-1, 1)
-    none = grad.new_empty(0)
-    return g_src, g_dst, none if g_a is None else g_a, none if g_wc is None else g_wc
+    grads = _onepass.pna_backward(Slots.of_csr(rowptr, col, p_src.size(0), edge_id), p_src,
+                                  edge_attr, wc, saved, _pna_stats(stats), grad.unbind(0),
+                                  p_dst.size(0))
+    # (one empty tensor EACH: an operator's outputs must not alias one another)
+    return tuple(grad.new_empty(0) if g is None else g for g in grads)
 
 
 @pna_aggregate_backward.register_fake
@@ -751,10 +698,6 @@ register_autograd('pyg_amd::pna_aggregate', _pna_bwd, setup_context=_pna_setup)
 
 
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
-def _hgt_blocks(kqvs, src_pos, F):
-    return ([kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos])
-
-
 @custom_op('pyg_amd::hgt_relation', mutates_args=(), device_types=_DEV)
 def hgt_relation(kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor, src_pos: List[int],
                  widx: List[int], heads: int) -> Tensor:
@@ -767,7 +710,7 @@ def hgt_relation(kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor, src_pos
         raise NotImplementedError(
             f'hgt_relation serves H * D <= 512, H <= 64 and D <= 128 (got {heads} x {D})')
     kqvs = [_native._f32_rows(x, 'kqv') for x in kqvs]
-    ks, vs = _hgt_blocks(kqvs, src_pos, heads * D)
+    ks, vs = _onepass.hgt_blocks(kqvs, src_pos, heads * D)
     return _native.hgt_relation_forward(ks, vs, widx, k_weight.contiguous(),
                                         v_weight.contiguous(), heads, D)
 
@@ -782,17 +725,9 @@ def _(kqvs, k_weight, v_weight, src_pos, widx, heads):
 def hgt_relation_backward(grad: Tensor, kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor,
                           src_pos: List[int], widx: List[int],
                           heads: int) -> Tuple[List[Tensor], Tensor, Tensor]:
-    D = k_weight.size(-1)
-    F = heads * D
-    kqvs = [_native._f32_rows(x, 'kqv') for x in kqvs]
-    ks, vs = _hgt_blocks(kqvs, src_pos, F)
-    bufs = [torch.empty_like(x, memory_format=torch.contiguous_format) for x in kqvs]
-    for b in bufs:
-        b[:, F:2 * F].zero_()
-    g_wk, g_wv = _native.hgt_relation_backward(
-        ks, vs, widx, src_pos, k_weight.contiguous(), v_weight.contiguous(), heads, D,
-        grad.contiguous(), [b[:, :F] for b in bufs], [b[:, 2 * F:] for b in bufs])
-    return bufs, g_wk, g_wv
+    return _onepass.hgt_backward([_native._f32_rows(x, 'kqv') for x in kqvs],
+                                 k_weight.contiguous(), v_weight.contiguous(), src_pos, widx,
+                                 heads, grad.contiguous())
 
 
 @hgt_relation_backward.register_fake

@@ -134,3 +134,44 @@ def assert_close_rows(got, ref, tol=2e-5, max_bad_rows=8, what=''):
     assert bad_rows <= max_bad_rows, (f'{what}: {bad_rows} rows differ by > {tol:g} x scale '
                                       f'(max abs err {float(err.max()):.3e}, scale {scale:.3e})')
     assert float(err.max()) <= 0.05 * scale, f'{what}: gross mismatch {float(err.max()):.3e}'
+
+
+class CountingLib:
+    """Stands in for the ctypes library object and counts the C-ABI calls made through it."""
+
+    def __init__(self, lib):
+        self._lib, self.calls, self.order = lib, {}, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith('pygamd_') or not callable(fn):
+            return fn
+
+        def counted(*args):
+            self.calls[name] = self.calls.get(name, 0) + 1
+            self.order.append(name)
+            return fn(*args)
+        return counted
+
+
+def _counted(monkeypatch, fn, sink=None):
+    """The :class:`CountingLib` that saw the C-ABI calls of ``fn()``.  ``sink``: also collect the
+    per-launch records of ``_native.timing_sink`` (the dense products run through the compiled
+    binding, not through ctypes: their records are how they are counted)"""
+    from pytorch_geometric_amd import _lib, _native
+    counter = CountingLib(_lib.load())
+    monkeypatch.setattr(_lib, 'load', lambda: counter)
+    if sink is not None:
+        monkeypatch.setattr(_native, 'timing_sink', sink)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        monkeypatch.undo()
+    return counter
+
+
+def _call_counts(monkeypatch, fn):
+    """``{C function: calls}`` of ``fn()`` without the error-text queries"""
+    info = ('pygamd_status_string', 'pygamd_last_hip_error')
+    return {k: v for k, v in _counted(monkeypatch, fn).calls.items() if k not in info}

@@ -8,7 +8,8 @@ import pytest
 import torch
 
 import _gatv2_ref as R
-from _util import assert_close, assert_close_scaled, assert_sum_close, gen, random_graph
+from _util import (_counted, assert_close, assert_close_scaled, assert_sum_close, gen,
+                   random_graph)
 
 pytestmark = pytest.mark.gpu
 
@@ -263,36 +264,6 @@ def test_fused_route_keeps_nothing_of_edge_times_width(dev):
 
 
 # ---- launch counts ------------------------------------------------------------------------------------
-class CountingLib:
-    """Stands in for the ctypes library object and counts the C-ABI calls made through it."""
-
-    def __init__(self, lib):
-        self._lib, self.calls, self.order = lib, {}, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith('pygamd_') or not callable(fn):
-            return fn
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            self.order.append(name)
-            return fn(*args)
-        return counted
-
-
-def _counted(monkeypatch, fn):
-    from pytorch_geometric_amd import _lib
-    counter = CountingLib(_lib.load())
-    monkeypatch.setattr(_lib, 'load', lambda: counter)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        monkeypatch.undo()
-    return counter
-
-
 def test_launch_counts(dev, monkeypatch):
     from pytorch_geometric_amd import as_edge_index
     from pytorch_geometric_amd._functions import Gatv2AttendFunction

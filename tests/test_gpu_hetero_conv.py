@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 import _hetero_conv_ref as R
 from pytorch_geometric_amd.nn import HeteroConv, HeteroDictLinear, SAGEConv
+from _util import _call_counts as _counted
 from _util import assert_close, assert_close_scaled, assert_sum_close, random_graph
 from test_hetero_conv_host import build_layer, load_golden
 
@@ -323,37 +324,6 @@ def test_end_to_end_sampled_training_step(dev):
 
 
 # ---- 6. launch structure ----------------------------------------------------------------------------------
-class CountingLib:
-    """Stands in for the ctypes library object and counts the C-ABI calls made through it."""
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, {}
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith('pygamd_') or not callable(fn):
-            return fn
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
-def _counted(monkeypatch, fn):
-    from pytorch_geometric_amd import _lib
-    real = _lib.load()
-    counter = CountingLib(real)
-    monkeypatch.setattr(_lib, 'load', lambda: counter)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        monkeypatch.undo()
-    info = ('pygamd_status_string', 'pygamd_last_hip_error')
-    return {k: v for k, v in counter.calls.items() if k not in info}
-
-
 def test_launch_count_does_not_depend_on_the_number_of_edge_types(dev, monkeypatch):
     num_nodes = {'a': 3000, 'b': 2000}
     K = 32

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import _hgt_ref as R
+from _util import _call_counts as _counted
 from _util import assert_close, assert_close_scaled, gen, random_graph
 
 pytestmark = pytest.mark.gpu
@@ -240,36 +241,6 @@ def test_hub_destination_fed_by_two_edge_types(dev, monkeypatch):
 
 
 # ---- launch structure ---------------------------------------------------------------------------------
-class CountingLib:
-    """Stands in for the ctypes library object and counts the C-ABI calls made through it."""
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, {}
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith('pygamd_') or not callable(fn):
-            return fn
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return fn(*args)
-        return counted
-
-
-def _counted(monkeypatch, fn):
-    from pytorch_geometric_amd import _lib
-    counter = CountingLib(_lib.load())
-    monkeypatch.setattr(_lib, 'load', lambda: counter)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        monkeypatch.undo()
-    info = ('pygamd_status_string', 'pygamd_last_hip_error')
-    return {k: v for k, v in counter.calls.items() if k not in info}
-
-
 def _split_graph(dev, parts):
     base = {('a', 'b'): random_graph(3000, 2000, 24000, 90), ('b', 'a'): random_graph(2000, 3000,
                                                                                     24000, 91)}

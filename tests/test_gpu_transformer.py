@@ -10,7 +10,8 @@ import pytest
 import torch
 
 import _transformer_ref as R
-from _util import assert_close, assert_close_scaled, assert_sum_close, gen, random_graph
+from _util import (_counted, assert_close, assert_close_scaled, assert_sum_close, gen,
+                   random_graph)
 
 pytestmark = pytest.mark.gpu
 
@@ -316,40 +317,6 @@ def test_fused_route_keeps_nothing_of_edge_times_width(dev):
 
 
 # ---- launch counts ------------------------------------------------------------------------------------
-class CountingLib:
-    """Stands in for the ctypes library object and counts the C-ABI calls made through it."""
-
-    def __init__(self, lib):
-        self._lib, self.calls, self.order = lib, {}, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith('pygamd_') or not callable(fn):
-            return fn
-
-        def counted(*args):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            self.order.append(name)
-            return fn(*args)
-        return counted
-
-
-def _counted(monkeypatch, fn, sink=None):
-    """``sink``: also collect the per-launch records of ``_native.timing_sink`` (the dense products
-    run through the compiled binding, not through ctypes: their records are how they are counted)"""
-    from pytorch_geometric_amd import _lib, _native
-    counter = CountingLib(_lib.load())
-    monkeypatch.setattr(_lib, 'load', lambda: counter)
-    if sink is not None:
-        monkeypatch.setattr(_native, 'timing_sink', sink)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        monkeypatch.undo()
-    return counter
-
-
 def _gemms(sink, op):
     return sum(1 for i, _, _ in sink if i.get('kind') == 'gemm' and i.get('op') == op)
 
