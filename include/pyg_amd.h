@@ -802,6 +802,66 @@ PYGAMD_API int pygamd_pna_backward(const pygamd_csr* g, const void* edge_id_t, c
                                    float* grad_wc, void* workspace, size_t workspace_bytes,
                                    void* stream);
 
+/* ---- GENConv's softmax aggregation (gen_conv.py:203-239, aggr/basic.py:142-215) ------------------
+ * For slot k of destination i with source j = col[k] and original edge edge_id[k] (NULL: slot
+ * order), column c:
+ *   e_k = 0                                        (PYGAMD_GEN_EDGE_NONE:   edge_attr NULL, De = 0)
+ *       = edge_attr[edge_id[k], :]                 (PYGAMD_GEN_EDGE_WIDE:   edge_attr [E, F], De = 0)
+ *       = W a_k + b, a_k = edge_attr[edge_id[k], :De]  (PYGAMD_GEN_EDGE_LINEAR: W [F, De] in
+ *                                                  torch.nn.Linear's layout, b [F] or NULL)
+ *   m_k = max(x_src[j,:] + e_k, 0) + eps_msg                       (gen_conv.py:231-239, message)
+ *   out[i,c] = sum_k alpha_kc m_kc,  alpha_kc = exp(t_c m_kc - M_ic) / (sum_k exp(t_c m_kc - M_ic)
+ *              + 1e-16),  M_ic = max_k t_c m_kc                    (aggr/basic.py:205-215)
+ * t is a DEVICE pointer to t_len = 1 or F values of any sign (it may be a parameter; no host
+ * read).  forward (replaces gen_conv.py:213, propagate): ONE launch over the by-destination
+ * handle g, one 64-lane wave per row, lanes over the F columns; every lane keeps a running
+ * (M, L, acc) per column and takes a slot in with one expf per element.  No [E, F] value is formed.
+ * out is exactly 0 for a row without slots.  `saved` takes the planes M and 1 / (L + 1e-16) of
+ * [n_rows, F] each and, if want_s2, a third plane S2 = sum_k alpha m^2 (the gradient of t is
+ * sum_i g (S2 - out^2), the caller's reduction).  A split row's chunks leave (M, L, acc, S2) in
+ * the workspace and are merged per column in chunk order.  Logits of +inf or NaN poison their own
+ * (row, column), as the reference's softmax does.
+ *
+ * backward (the gradient of gen_conv.py:213): ONE launch over the by-source handle g (col = the
+ * destination of every out-slot, edge_id_t = that form's slot -> original edge map, NULL: slot
+ * order).  `coef` [n_dst, 3, F] is a packed row per destination: M, G = grad_out[i,:] / (L +
+ * 1e-16) and out[i,:]; with semi_grad [n_dst, 2, F]: M and G (the softmax weights are constants,
+ * aggr/basic.py:209).  The launch rebuilds m_k and
+ *   gm = (x_src[j,:] + e_k > 0) exp(t m_k - M) G (1 + t (m_k - out))   (semi_grad: without the
+ *                                                                       last factor)
+ *   grad_x_src[j,:] = sum_s gm                         (zeros for rows without out-slots)
+ *   wide:   grad_edge_attr[k,:] = gm                   (original edge order)
+ *   linear: grad_edge_attr[k,d] = sum_f gm_f W[f,d],  grad_weight[f,d] = sum_k gm_f a_k[d],
+ *           grad_bias[f] = sum_k gm_f (NULL iff bias is)
+ * grad_edge_attr is written iff want_grad_edge_attr (NULL otherwise); grad_weight / grad_bias
+ * leave one partial per workgroup and are reduced in workgroup order inside the call; the grid is
+ * a function of (n_src, n_chunks) only.
+ *
+ * pygamd_gen_supported(F, De) (De = 0 without lin_edge): F <= 512 and, in linear mode, De <= 32
+ * and F * De <= 4096; otherwise status 2.  x_src has row stride ld_src (floats), everything else is
+ * contiguous; fp32 data, int32 / int64 indices.  No float atomics: bitwise reproducible.  Status
+ * 1 / 2 / 3 before any device work; n_rows == 0 returns 0.                                        */
+#define PYGAMD_GEN_EDGE_NONE 0
+#define PYGAMD_GEN_EDGE_WIDE 1
+#define PYGAMD_GEN_EDGE_LINEAR 2
+PYGAMD_API int pygamd_gen_supported(int64_t F, int64_t De);
+PYGAMD_API int pygamd_gen_workspace_bytes(int64_t n_chunks, int64_t F, int64_t De,
+                                          size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_gen_forward(const pygamd_csr* g, const void* edge_id, const float* x_src,
+                                  int64_t ld_src, int edge_mode, const float* edge_attr,
+                                  const float* weight, const float* bias, const float* t,
+                                  int64_t t_len, float eps_msg, int64_t n_src, int64_t F,
+                                  int64_t De, int want_s2, float* out, float* saved,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_gen_backward(const pygamd_csr* g, const void* edge_id_t, const float* x_src,
+                                   int64_t ld_src, int edge_mode, const float* edge_attr,
+                                   const float* weight, const float* bias, const float* t,
+                                   int64_t t_len, float eps_msg, int semi_grad, const float* coef,
+                                   int64_t n_dst, int64_t F, int64_t De, int want_grad_edge_attr,
+                                   float* grad_x_src, float* grad_edge_attr, float* grad_weight,
+                                   float* grad_bias, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

@@ -845,6 +845,43 @@ class GineAggregateFunction(Function):
             want_weight=need[4], want_bias=need[5]) + (None, None)
 
 
+class GenAggregateFunction(Function):
+    """The propagate step of GENConv under SoftmaxAggregation (gen_conv.py:213, 231-239 with
+    aggr/basic.py:205-215) in ONE pass over the by-destination slots:
+
+        out[i] = sum_{k of i} alpha_k m_k,   m_k = relu(x_src[j_k] + e_k) + eps_msg,
+        alpha = softmax over the slots of i of t * m, per column
+
+    with ``e_k`` = 0 (``edge_attr=None``), ``edge_attr[k]`` (width ``F``) or ``weight @ edge_attr[k]
+    + bias`` (``lin_edge``), rebuilt per slot in registers (csrc/gen.hip).  ``t`` is a tensor of 1
+    or ``F`` values.  ``edge_attr`` stays in the caller's edge order.  Saved for the backward: the
+    inputs, ``out`` and two ``[n_dst, F]`` planes (three when ``t`` takes a gradient), nothing per
+    edge.  The backward is an elementwise pre-pass and one pass over the by-source slots."""
+
+    @staticmethod
+    def forward(ctx, x_src: Tensor, edge_attr: Optional[Tensor], weight: Optional[Tensor],
+                bias: Optional[Tensor], t: Tensor, graph: EdgeIndex, n_dst: int,
+                eps_msg: float = 1e-7, semi_grad: bool = False):
+        _check_rows(graph, n_dst, 'x_src', x_src, 'x_dst', None)
+        fwd = graph.by_dst()
+        out, saved = _native.gen_forward(fwd.ptr, fwd.idx, fwd.perm, x_src, edge_attr, weight,
+                                         bias, t, eps_msg=eps_msg,
+                                         want_s2=ctx.needs_input_grad[4], hub=fwd.hub)
+        ctx.save_for_backward(x_src, edge_attr, weight, bias, t, out, saved)
+        ctx.graph, ctx.eps_msg, ctx.semi_grad = graph, eps_msg, semi_grad
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        need = ctx.needs_input_grad
+        return _onepass.gen_backward(
+            Slots.of_graph(ctx.graph), *ctx.saved_tensors, grad_out.contiguous(),
+            eps_msg=ctx.eps_msg, semi_grad=ctx.semi_grad, want_x_src=need[0],
+            want_edge_attr=need[1], want_weight=need[2], want_bias=need[3],
+            want_t=need[4]) + (None, None, None, None)
+
+
 class PnaAggregateFunction(Function):
     """The aggregation of PNAConv with a linear message (pna_conv.py:175-188 under
     aggr/scaler.py:82) in ONE pass over the by-destination slots.  The message of slot ``k`` of

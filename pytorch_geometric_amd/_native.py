@@ -1714,6 +1714,124 @@ def pna_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], p
     return grad_p, grad_edge, grad_wc
 
 
+# ---- GENConv's softmax aggregation (csrc/gen.hip) --------------------------------------------------
+GEN_EDGE_NONE, GEN_EDGE_WIDE, GEN_EDGE_LINEAR = 0, 1, 2
+
+
+def gen_supported(F: int, De: int = 0) -> bool:
+    """The kernel pair serves ``F <= 512`` and, with ``lin_edge`` (``De >= 1``), ``De <= 32`` and
+    ``F * De <= 4096``; ``De = 0`` for edge features of width ``F`` or none."""
+    return bool(_lib.load().pygamd_gen_supported(int(F), int(De)))
+
+
+def _gen_edge(edge_attr: Optional[Tensor], weight: Optional[Tensor], bias: Optional[Tensor],
+              F: int, E: int):
+    """(mode, edge_attr, weight, bias, De) checked; everything None without an edge term."""
+    if edge_attr is None:
+        if weight is not None or bias is not None:
+            raise ValueError("'weight' and 'bias' need 'edge_attr'")
+        return GEN_EDGE_NONE, None, None, None, 0
+    edge_attr, weight, bias, De = _gine_edge(edge_attr, weight, bias, F, E)
+    return (GEN_EDGE_LINEAR if De else GEN_EDGE_WIDE), edge_attr, weight, bias, De
+
+
+def _gen_t(t: Tensor, F: int) -> Tensor:
+    if t.dtype != torch.float32 or t.numel() not in (1, F):
+        raise ValueError(f"'t' must hold 1 or {F} float32 values (got {t.dtype} "
+                         f"{tuple(t.shape)})")
+    return t.reshape(-1).contiguous()
+
+
+def gen_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], x_src: Tensor,
+                edge_attr: Optional[Tensor], weight: Optional[Tensor], bias: Optional[Tensor],
+                t: Tensor, *, eps_msg: float = 1e-7, want_s2: bool = False, hub=None):
+    """``(out [n_rows, F], saved [2 | 3, n_rows, F])`` on a by-destination handle: ``out[i] =
+    sum_k alpha_k m_k`` with ``m_k = relu(x_src[col[k]] + e_k) + eps_msg`` and ``alpha`` the softmax
+    of ``t * m`` over the slots of ``i`` PER COLUMN; ``e_k`` is 0 (``edge_attr=None``),
+    ``edge_attr[edge_id[k]]`` (width ``F``) or ``weight @ edge_attr[edge_id[k]] + bias``.  ``t`` is
+    a device tensor of 1 or ``F`` values.  ``saved`` holds the running maximum ``M``, ``1 / (L +
+    1e-16)`` and, with ``want_s2``, ``sum_k alpha m^2``.  Rows without slots are exactly 0.
+    ``x_src`` may be a column block of a wider tensor (its row stride is passed)."""
+    _require_device(rowptr, col, edge_id, x_src, edge_attr, weight, bias, t)
+    lib = _lib.load()
+    if x_src.dim() != 2:
+        raise ValueError("'x_src' must be two-dimensional")
+    F = x_src.size(1)
+    x_src = _strided_rows(x_src, 'x_src', F)
+    n_rows = rowptr.numel() - 1
+    mode, edge_attr, weight, bias, De = _gen_edge(edge_attr, weight, bias, F, col.numel())
+    t = _gen_t(t, F)
+    edge_id = _edge_id(edge_id, rowptr, col)
+    dev = x_src.device
+    planes = 3 if want_s2 else 2
+    if n_rows == 0 or col.numel() == 0:  # no slot anywhere: zeros, nothing to launch
+        return (torch.zeros(n_rows, F, dtype=torch.float32, device=dev),
+                torch.zeros(planes, n_rows, F, dtype=torch.float32, device=dev))
+    out = torch.empty(n_rows, F, dtype=torch.float32, device=dev)
+    saved = torch.empty(planes, n_rows, F, dtype=torch.float32, device=dev)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_gen_workspace_bytes, (g.n_chunks, F, 0), dev,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'gen', 'op': 'forward', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'De': De, 'ld': _ld(x_src), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': False, 'grad_t': bool(want_s2)}, x_src):
+        check(lib.pygamd_gen_forward(
+            ctypes.byref(g), _p(edge_id), _p(x_src), _ld(x_src), mode, _p(edge_attr), _p(weight),
+            _p(bias), _p(t), t.numel(), float(eps_msg), x_src.size(0), F, De, int(want_s2),
+            _p(out), _p(saved), _p(ws), ws_bytes, _stream(x_src)), 'gen_forward')
+    return out, saved
+
+
+def gen_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], x_src: Tensor,
+                 edge_attr: Optional[Tensor], weight: Optional[Tensor], bias: Optional[Tensor],
+                 t: Tensor, coef: Tensor, *, eps_msg: float = 1e-7, semi_grad: bool = False,
+                 want_grad_edge_attr: bool = True, grad_t: bool = False, hub=None):
+    """``(grad_x_src [n_src, F], grad_edge_attr | None, grad_weight | None, grad_bias | None)`` on
+    the by-SOURCE handle (``col_t`` = the destination of every out-slot, ``edge_id_t`` = that
+    form's slot -> edge map) from the packed rows ``coef [n_dst, 3, F]`` = ``M``, ``grad_out / (L +
+    1e-16)``, ``out`` (``semi_grad``: ``[n_dst, 2, F]`` without ``out``).  ``grad_edge_attr`` comes
+    in the caller's edge order.  ``grad_t`` only marks the timing record: the gradient of ``t`` is
+    the caller's reduction."""
+    _require_device(rowptr_t, col_t, edge_id_t, x_src, edge_attr, weight, bias, t, coef)
+    lib = _lib.load()
+    F = x_src.size(1)
+    x_src = _strided_rows(x_src, 'x_src', F)
+    n_src = rowptr_t.numel() - 1
+    if x_src.size(0) != n_src:
+        raise ValueError(f"'x_src' needs {n_src} rows")
+    planes = 2 if semi_grad else 3
+    if coef.dtype != torch.float32 or coef.dim() != 3 or tuple(coef.shape[1:]) != (planes, F):
+        raise ValueError(f"'coef' must be a float32 [n_dst, {planes}, {F}] tensor (got "
+                         f"{coef.dtype} {tuple(coef.shape)})")
+    coef = coef.contiguous()
+    mode, edge_attr, weight, bias, De = _gen_edge(edge_attr, weight, bias, F, col_t.numel())
+    t = _gen_t(t, F)
+    edge_id_t = _edge_id(edge_id_t, rowptr_t, col_t, 'edge_id_t')
+    want_grad_edge_attr = bool(want_grad_edge_attr) and mode != GEN_EDGE_NONE
+    dev = x_src.device
+    if n_src == 0 or col_t.numel() == 0:
+        return (torch.zeros(n_src, F, dtype=torch.float32, device=dev),
+                torch.zeros_like(edge_attr) if want_grad_edge_attr else None,
+                None if weight is None else torch.zeros_like(weight),
+                None if bias is None else torch.zeros_like(bias))
+    grad_x = torch.empty(n_src, F, dtype=torch.float32, device=dev)
+    grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
+    grad_w = torch.empty_like(weight) if weight is not None else None
+    grad_b = torch.empty_like(bias) if bias is not None else None
+    g = _csr(rowptr_t, col_t, n_src, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_gen_workspace_bytes, (g.n_chunks, F, De), dev,
+                              g.n_chunks > 0 or De > 0)
+    with _timed({'kind': 'gen', 'op': 'backward', 'n_rows': n_src, 'E': col_t.numel(), 'F': F,
+                 'De': De, 'ld': _ld(x_src), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': want_grad_edge_attr, 'grad_t': bool(grad_t)}, x_src):
+        check(lib.pygamd_gen_backward(
+            ctypes.byref(g), _p(edge_id_t), _p(x_src), _ld(x_src), mode, _p(edge_attr),
+            _p(weight), _p(bias), _p(t), t.numel(), float(eps_msg), int(bool(semi_grad)),
+            _p(coef), coef.size(0), F, De, int(want_grad_edge_attr), _p(grad_x), _p(grad_edge),
+            _p(grad_w), _p(grad_b), _p(ws), ws_bytes, _stream(x_src)), 'gen_backward')
+    return grad_x, grad_edge, grad_w, grad_b
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

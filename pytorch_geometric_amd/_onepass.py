@@ -191,6 +191,33 @@ def pna_backward(slots, p_src, edge_attr, wc, saved, stats, grads, dst_rows, *, 
             g_wc if want_wc else None)
 
 
+def gen_backward(slots, x_src, edge_attr, weight, bias, t, out, saved, grad_out, *, eps_msg=1e-7,
+                 semi_grad=False, want_x_src=True, want_edge_attr=True, want_weight=True,
+                 want_bias=True, want_t=False):
+    """``(grad_x_src, grad_edge_attr, grad_weight, grad_bias, grad_t)``, None where not wanted or
+    not given.  An elementwise pre-pass packs one row per destination — the forward's ``M``,
+    ``grad_out / (L + 1e-16)`` and, unless ``semi_grad``, ``out`` — and one launch by source
+    rebuilds the message and its softmax weight per out-slot.  ``grad_t = sum_i grad_out (S2 -
+    out^2)`` needs no per-edge work: column sums in fp64 (the two terms nearly cancel)."""
+    g_x = g_a = g_w = g_b = g_t = None
+    if want_x_src or want_edge_attr or want_weight or want_bias:
+        planes = [saved[0], grad_out * saved[1]] + ([] if semi_grad else [out])
+        coef = torch.stack(planes, dim=1)
+        bwd = slots.by_src()
+        g_x, g_a, g_w, g_b = _native.gen_backward(
+            bwd.ptr, bwd.idx, slots.edge_id_t(), x_src, edge_attr, weight, bias, t, coef,
+            eps_msg=eps_msg, semi_grad=semi_grad,
+            want_grad_edge_attr=want_edge_attr and edge_attr is not None, grad_t=want_t,
+            hub=bwd.hub)
+    if want_t:
+        if saved.size(0) < 3:
+            raise ValueError("the gradient of 't' needs the forward's third plane (want_s2)")
+        cols = (grad_out * (saved[2] - out * out)).double().sum(dim=0)
+        g_t = (cols.sum() if t.numel() == 1 else cols).to(t.dtype).reshape(t.shape)
+    return (g_x if want_x_src else None, g_a if want_edge_attr else None,
+            g_w if want_weight else None, g_b if want_bias else None, g_t)
+
+
 def hgt_blocks(kqvs, src_pos, F):
     """``(ks, vs)`` per edge type: the key and value column blocks of its ``[N, 3 * F]`` source"""
     return [kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos]

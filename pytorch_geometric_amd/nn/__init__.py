@@ -2,9 +2,10 @@ from .aggr import (Aggregation, DegreeScalerAggregation, FusedAggregation, MaxAg
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
 from .conv import (FastRGCNConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HeteroConv, HGTConv,
-                   MessagePassing, PNAConv, RGCNConv, SAGEConv, TransformerConv, gcn_norm, group)
+                   GENConv, MessagePassing, PNAConv, RGCNConv, SAGEConv, TransformerConv, gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
-from .models import GAT, GCN, BasicGNN, GraphSAGE
+from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
+from .norm import MessageNorm
 from . import functional  # noqa: F401
 
 __all__ = [
@@ -12,6 +13,6 @@ __all__ = [
     'MulAggregation', 'VarAggregation', 'StdAggregation', 'FusedAggregation',
     'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
     'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
-    'PNAConv', 'DegreeScalerAggregation',
+    'PNAConv', 'DegreeScalerAggregation', 'GENConv', 'MessageNorm', 'DeepGCNLayer',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

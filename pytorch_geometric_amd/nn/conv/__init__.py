@@ -10,7 +10,8 @@ from .hetero_conv import HeteroConv, group
 from .hgt_conv import HGTConv
 from .gin_conv import GINConv, GINEConv
 from .pna_conv import PNAConv
+from .gen_conv import GENConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
-           'PNAConv']
+           'PNAConv', 'GENConv']

@@ -1,3 +1,4 @@
 from .basic_gnn import GAT, GCN, BasicGNN, GraphSAGE
+from .deepgcn import DeepGCNLayer
 
-__all__ = ['BasicGNN', 'GCN', 'GraphSAGE', 'GAT']
+__all__ = ['BasicGNN', 'GCN', 'GraphSAGE', 'GAT', 'DeepGCNLayer']

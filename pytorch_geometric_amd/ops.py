@@ -42,6 +42,9 @@ Operators (all index tensors int32 / int64, features float32):
 ``pna_aggregate``           ``(Tensor p_src, Tensor p_dst, Tensor? edge_attr, Tensor? wc,
                             Tensor rowptr, Tensor col, Tensor? edge_id, int stats)
                             -> (Tensor out, Tensor saved)``
+``gen_aggregate``           ``(Tensor x_src, Tensor? edge_attr, Tensor? weight, Tensor? bias,
+                            Tensor t, Tensor rowptr, Tensor col, Tensor? edge_id, float eps_msg,
+                            bool semi_grad, bool grad_t) -> (Tensor out, Tensor saved)``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -697,6 +700,85 @@ def _pna_bwd(ctx, grad, _grad_saved):
 register_autograd('pyg_amd::pna_aggregate', _pna_bwd, setup_context=_pna_setup)
 
 
+# ---- GENConv's softmax aggregation on a CSR pair (rows = destinations) -----------------------------
+@custom_op('pyg_amd::gen_aggregate', mutates_args=(), device_types=_DEV)
+def gen_aggregate(x_src: Tensor, edge_attr: Optional[Tensor], weight: Optional[Tensor],
+                  bias: Optional[Tensor], t: Tensor, rowptr: Tensor, col: Tensor,
+                  edge_id: Optional[Tensor], eps_msg: float = 1e-7, semi_grad: bool = False,
+                  grad_t: bool = False) -> Tuple[Tensor, Tensor]:
+    """GENConv's propagate under SoftmaxAggregation (gen_conv.py:213, 231-239; aggr/basic.py:
+    205-215): ``out [n_dst, F] = sum_k alpha_k m_k`` with ``m_k = relu(x_src[col[k]] + e_k) +
+    eps_msg`` and ``alpha`` the per-column softmax of ``t * m`` over a row's slots; ``e_k`` is 0
+    (``edge_attr=None``), ``edge_attr[edge_id[k]]`` for ``edge_attr [E, F]``, or ``weight @
+    edge_attr[edge_id[k]] + bias`` for ``edge_attr [E, De]`` and ``weight [F, De]``.  ``t`` holds 1
+    or ``F`` values.  Also returned: ``saved [2, n_dst, F]``, the planes the backward reads (no
+    gradient flows through them); ``grad_t`` adds the third plane the gradient of ``t`` needs.
+    ``semi_grad`` treats the softmax weights as constants in the backward.  ``edge_id=None``:
+    ``edge_attr`` follows the slots of ``col``."""
+    F = x_src.size(1)
+    De = 0 if weight is None else edge_attr.size(1)
+    if not _native.gen_supported(F, De):
+        raise NotImplementedError(
+            f'gen_aggregate serves F <= 512 and, with a weight, De <= 32 and F * De <= 4096 '
+            f'(got F = {F}, De = {De})')
+    return _native.gen_forward(rowptr, col, edge_id, x_src, edge_attr, weight, bias, t,
+                               eps_msg=eps_msg, want_s2=grad_t, hub=_native.hub_plan(rowptr))
+
+
+@gen_aggregate.register_fake
+def _(x_src, edge_attr, weight, bias, t, rowptr, col, edge_id, eps_msg=1e-7, semi_grad=False,
+      grad_t=False):
+    n, F = rowptr.numel() - 1, x_src.shape[1]
+    return x_src.new_empty(n, F), x_src.new_empty(3 if grad_t else 2, n, F)
+
+
+@custom_op('pyg_amd::gen_aggregate_backward', mutates_args=(), device_types=_DEV)
+def gen_aggregate_backward(grad: Tensor, x_src: Tensor, edge_attr: Optional[Tensor],
+                           weight: Optional[Tensor], bias: Optional[Tensor], t: Tensor,
+                           out: Tensor, saved: Tensor, rowptr: Tensor, col: Tensor,
+                           edge_id: Optional[Tensor], eps_msg: float, semi_grad: bool,
+                           grad_t: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The gradients of ``(x_src, edge_attr, weight, bias, t)``; an input that was not given, and
+    ``t`` without ``grad_t``, gets an empty tensor."""
+    grads = _onepass.gen_backward(Slots.of_csr(rowptr, col, x_src.size(0), edge_id), x_src,
+                                  edge_attr, weight, bias, t, out, saved, grad, eps_msg=eps_msg,
+                                  semi_grad=semi_grad, want_t=grad_t)
+    # (one empty tensor EACH: an operator's outputs must not alias one another)
+    return tuple(grad.new_empty(0) if g is None else g for g in grads)
+
+
+@gen_aggregate_backward.register_fake
+def _(grad, x_src, edge_attr, weight, bias, t, out, saved, rowptr, col, edge_id, eps_msg,
+      semi_grad, grad_t):
+    none = grad.new_empty(0)
+    return (torch.empty_like(x_src, memory_format=torch.contiguous_format),
+            none if edge_attr is None else torch.empty_like(edge_attr),
+            none if weight is None else torch.empty_like(weight),
+            none if bias is None else torch.empty_like(bias),
+            torch.empty_like(t) if grad_t else none)
+
+
+def _gen_setup(ctx, inputs, output):
+    x_src, edge_attr, weight, bias, t, rowptr, col, edge_id, eps_msg, semi_grad, grad_t = inputs
+    ctx.static = (eps_msg, semi_grad, grad_t)
+    ctx.given = (edge_attr is not None, weight is not None, bias is not None)
+    ctx.save_for_backward(x_src, edge_attr, weight, bias, t, output[0], output[1], rowptr, col,
+                          edge_id)
+
+
+def _gen_bwd(ctx, grad, _grad_saved):
+    x_src, edge_attr, weight, bias, t, out, saved, rowptr, col, edge_id = ctx.saved_tensors
+    g_x, g_a, g_w, g_b, g_t = gen_aggregate_backward(
+        grad.contiguous(), x_src, edge_attr, weight, bias, t, out, saved, rowptr, col, edge_id,
+        *ctx.static)
+    has_a, has_w, has_b = ctx.given
+    return (g_x, g_a if has_a else None, g_w if has_w else None, g_b if has_b else None,
+            g_t if ctx.static[2] else None, None, None, None, None, None, None)
+
+
+register_autograd('pyg_amd::gen_aggregate', _gen_bwd, setup_context=_gen_setup)
+
+
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
 @custom_op('pyg_amd::hgt_relation', mutates_args=(), device_types=_DEV)
 def hgt_relation(kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor, src_pos: List[int],
@@ -757,4 +839,5 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
        'transformer_attend_backward', 'transformer_edge_attend',
        'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward',
-       'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward')
+       'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward',
+       'gen_aggregate', 'gen_aggregate_backward')
