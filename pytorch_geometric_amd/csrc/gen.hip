@@ -31,13 +31,6 @@ struct GenSlots {  // slots in flight per wave
   static constexpr int bwd = (EPL * DE >= 64) ? 1 : 2;
 };
 
-struct GenEdge {
-  const float* edge_attr;  // [E, F] (wide), [E, De] (linear) or NULL (no edge term)
-  const float* weight;     // [F, De] or NULL
-  const float* bias;       // [F] or NULL
-  int De;
-};
-
 // the lane's entries of t: a row of F values, or one value for every column
 template <int EPL, bool VEC>
 __device__ __forceinline__ void load_t(const float* __restrict__ t, int t_len, const Lay& L,
@@ -83,7 +76,7 @@ __device__ __forceinline__ void online_take(float m, float p, float& M, float& L
 template <typename IdxT, int EPL, bool VEC, int DE>
 __global__ void __launch_bounds__(kBlock)
     gen_fwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col, const IdxT* __restrict__ edge_id,
-                   const float* __restrict__ x_src, int64_t ld, GenEdge ed,
+                   const float* __restrict__ x_src, int64_t ld, EdgeArgs ed,
                    const float* __restrict__ t, int t_len, float eps_msg, int F, int lph,
                    float* __restrict__ out, float* __restrict__ saved, int want_s2,
                    float* __restrict__ part) {
@@ -96,11 +89,9 @@ __global__ void __launch_bounds__(kBlock)
   load_t<EPL, VEC>(t, t_len, L, tt);
   const bool has_edge = ed.edge_attr != nullptr;  // (wave-uniform)
   const int lane = lane_id();
-  const int64_t n_items = it.n_chunks + it.n_rows;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+  const Walk wk = item_walk(it);
   const int64_t plane = it.n_rows * static_cast<int64_t>(F);
-  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
-       item += stride) {
+  for (int64_t item = wk.first; item < wk.n; item += wk.stride) {
     Span s;
     if (!decode(it, item, s)) continue;
     float M[EPL], Ls[EPL], acc[EPL], s2[EPL];
@@ -115,10 +106,10 @@ __global__ void __launch_bounds__(kBlock)
       for (int u = 0; u < U; ++u) {
         if (k + u < s.k1) {
           const int64_t j = static_cast<int64_t>(col[k + u]);
-          const int64_t id = edge_id ? static_cast<int64_t>(edge_id[k + u]) : k + u;
+          const int64_t id = slot_edge(edge_id, k + u);
           load_row<EPL, VEC>(x_src + j * ld, L, xx[u]);
           if constexpr (LIN) {
-            av[u] = lane < ed.De ? ed.edge_attr[id * ed.De + lane] : 0.f;
+            av[u] = edge_lane(ed, id, lane);
           } else {
             if (has_edge) {
               load_row<EPL, VEC>(ed.edge_attr + id * F, L, ee[u]);
@@ -208,7 +199,7 @@ template <typename IdxT, int EPL, bool VEC, int DE>
 __global__ void __launch_bounds__(kBlock)
     gen_bwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col_t,
                    const IdxT* __restrict__ edge_id_t, const float* __restrict__ x_src, int64_t ld,
-                   GenEdge ed, const float* __restrict__ t, int t_len, float eps_msg,
+                   EdgeArgs ed, const float* __restrict__ t, int t_len, float eps_msg,
                    const float* __restrict__ coef, int planes, int F, int lph,
                    float* __restrict__ grad_x, float* __restrict__ grad_edge,
                    float* __restrict__ part, float* __restrict__ wpart) {
@@ -231,11 +222,9 @@ __global__ void __launch_bounds__(kBlock)
   const bool has_edge = ed.edge_attr != nullptr;  // (wave-uniform)
   const bool full = planes == 3;                  // (wave-uniform)
   const int lane = lane_id();
-  const int64_t n_items = it.n_chunks + it.n_rows;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+  const Walk wk = item_walk(it);
   const int64_t ldc = static_cast<int64_t>(planes) * F;
-  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
-       item += stride) {
+  for (int64_t item = wk.first; item < wk.n; item += wk.stride) {
     Span s;
     if (!decode(it, item, s)) continue;
     float x[EPL], gx[EPL];
@@ -249,7 +238,7 @@ __global__ void __launch_bounds__(kBlock)
       for (int u = 0; u < U; ++u) {
         if (q + u < s.k1) {
           const int64_t i = static_cast<int64_t>(col_t[q + u]);
-          id[u] = edge_id_t ? static_cast<int64_t>(edge_id_t[q + u]) : q + u;
+          id[u] = slot_edge(edge_id_t, q + u);
           const float* c = coef + i * ldc;
           load_row<EPL, VEC>(c, L, cm[u]);
           load_row<EPL, VEC>(c + F, L, cp[u]);
@@ -260,7 +249,7 @@ __global__ void __launch_bounds__(kBlock)
             for (int e = 0; e < EPL; ++e) cq[u][e] = 0.f;
           }
           if constexpr (LIN) {
-            av[u] = lane < ed.De ? ed.edge_attr[id[u] * ed.De + lane] : 0.f;
+            av[u] = edge_lane(ed, id[u], lane);
           } else {
             if (has_edge) {
               load_row<EPL, VEC>(ed.edge_attr + id[u] * F, L, ee[u]);
@@ -285,6 +274,7 @@ __global__ void __launch_bounds__(kBlock)
             gx[e] += mg[e];
           }
           if constexpr (LIN) {
+            // (gine_device.h's edge_grad_take, written out: as a call it cost this kernel 1 %)
 #pragma unroll
             for (int d = 0; d < DE; ++d) {
               const float a = bcast_uniform(av[u], d);
@@ -344,50 +334,11 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-template <typename IdxT>
-__global__ void __launch_bounds__(kWave)
-    gen_bwd_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
-                         int64_t F, const float* __restrict__ part, float* __restrict__ grad_x) {
-  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), F, part, F, grad_x, F);
-}
-
-// the workgroups' partials (grad_W [F * De], then grad_b [F]) summed in workgroup order
-__global__ void __launch_bounds__(kBlock)
-    gen_param_reduce_kernel(const float* __restrict__ wpart, int n_blocks, int FD, int F,
-                            float* __restrict__ grad_weight, float* __restrict__ grad_bias) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  const int S = FD + F;
-  if (i >= S) return;
-  float acc = 0.f;
-  for (int g = 0; g < n_blocks; ++g) acc += wpart[static_cast<int64_t>(g) * S + i];
-  if (i < FD) {
-    grad_weight[i] = acc;
-  } else if (grad_bias) {
-    grad_bias[i - FD] = acc;
-  }
-}
-
 // ---- host side -------------------------------------------------------------------------------
 size_t gen_ws_bytes(int64_t n_chunks, int64_t F, int64_t De) {
   // four rows per chunk (the forward's running state; the backward uses the first n_chunks rows
   // for its partial sums); in linear mode the backward's partials of (grad_W, grad_b) follow
-  const int64_t wpart = De > 0 ? static_cast<int64_t>(kGineBwdBlocks) * (F * De + F) : 0;
-  return sizeof(float) * static_cast<size_t>(n_chunks * 4 * F + wpart);
-}
-
-// the edge arguments against the mode; 0 = go on
-int gen_check_edge(int edge_mode, int64_t De, const float* edge_attr, const float* weight,
-                   const float* bias) {
-  switch (edge_mode) {
-    case PYGAMD_GEN_EDGE_NONE:
-      return (De == 0 && !edge_attr && !weight && !bias) ? PYGAMD_OK : PYGAMD_ERR_INVALID_ARG;
-    case PYGAMD_GEN_EDGE_WIDE:
-      return (De == 0 && edge_attr && !weight && !bias) ? PYGAMD_OK : PYGAMD_ERR_INVALID_ARG;
-    case PYGAMD_GEN_EDGE_LINEAR:
-      return (De > 0 && edge_attr && weight) ? PYGAMD_OK : PYGAMD_ERR_INVALID_ARG;
-    default:
-      return PYGAMD_ERR_INVALID_ARG;
-  }
+  return sizeof(float) * static_cast<size_t>(n_chunks * 4 * F + wpart_floats(F, De, true));
 }
 
 int gen_check(const pygamd_csr* g, int64_t n_other, int64_t F, int64_t De, int edge_mode,
@@ -427,7 +378,8 @@ int pygamd_gen_forward(const pygamd_csr* g, const void* edge_id, const float* x_
   if (ld_src < F) return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
   if (!g->rowptr || !g->col || !x_src || !t || !out || !saved) return PYGAMD_ERR_INVALID_ARG;
-  const int rce = gen_check_edge(edge_mode, De, edge_attr, weight, bias);
+  const EdgeArgs ed{edge_attr, weight, bias, static_cast<int>(De)};
+  const int rce = check_edge(edge_mode, ed);
   if (rce != PYGAMD_OK) return rce;
   if (n_chunks > 0 && (!workspace || workspace_bytes < sizeof(float) * n_chunks * 4 * F))
     return PYGAMD_ERR_WORKSPACE;
@@ -439,7 +391,6 @@ int pygamd_gen_forward(const pygamd_csr* g, const void* edge_id, const float* x_
   if (!gine_shape(F, De, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
-  const GenEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
   return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(gine_grid(n_rows + n_chunks, De > 0, kGineFwdBlocks)), block(kBlock);
@@ -469,12 +420,13 @@ int pygamd_gen_backward(const pygamd_csr* g, const void* edge_id_t, const float*
                         void* workspace, size_t workspace_bytes, void* stream) {
   const int rc = gen_check(g, n_dst, F, De, edge_mode, t_len);
   if (rc != PYGAMD_OK) return rc;
-  const int64_t n_src = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
+  const int64_t n_src = g->n_rows, n_chunks = g->n_chunks;
   if (ld_src < F) return PYGAMD_ERR_INVALID_ARG;
   if (n_src == 0) return PYGAMD_OK;
   if (!g->rowptr || !g->col || !x_src || !t || !coef || !grad_x_src)
     return PYGAMD_ERR_INVALID_ARG;
-  const int rce = gen_check_edge(edge_mode, De, edge_attr, weight, bias);
+  const EdgeArgs ed{edge_attr, weight, bias, static_cast<int>(De)};
+  const int rce = check_edge(edge_mode, ed);
   if (rce != PYGAMD_OK) return rce;
   const bool want_edge = want_grad_edge_attr != 0;
   if ((want_edge && edge_mode == PYGAMD_GEN_EDGE_NONE) || want_edge != (grad_edge_attr != nullptr))
@@ -494,7 +446,6 @@ int pygamd_gen_backward(const pygamd_csr* g, const void* edge_id_t, const float*
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   float* wpart = part + n_chunks * 4 * F;
-  const GenEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
   return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
     const Items<IdxT> it = make_items<IdxT>(*g);
     const unsigned n_blocks = gine_grid(n_src + n_chunks, De > 0, kGineBwdBlocks);
@@ -506,19 +457,8 @@ int pygamd_gen_backward(const pygamd_csr* g, const void* edge_id_t, const float*
                          static_cast<int>(F), sh.lph, grad_x_src, grad_edge_attr, part, wpart);
     });
     PYGAMD_LAUNCH_CHECK();
-    if (n_hub > 0) {
-      hipLaunchKernelGGL((gen_bwd_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
-                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, F, part, grad_x_src);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    if (De > 0) {
-      const int S = static_cast<int>(F * De + F);
-      hipLaunchKernelGGL(gen_param_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(S, kBlock))),
-                         block, 0, st, wpart, static_cast<int>(n_blocks),
-                         static_cast<int>(F * De), static_cast<int>(F), grad_weight, grad_bias);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    return PYGAMD_OK;
+    return launch_backward_tail<IdxT>(it, F, De, true, n_blocks, part, grad_x_src, wpart,
+                                      grad_weight, grad_bias, st);
   });
 }
 

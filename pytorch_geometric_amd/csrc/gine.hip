@@ -30,20 +30,13 @@ struct GineSlots {  // slots in flight per wave
   static constexpr int n = (EPL >= 8 || DE > 0) ? 2 : 4;
 };
 
-struct GineEdge {
-  const float* edge_attr;  // [E, F] (wide) or [E, De] (linear), original edge order
-  const float* weight;     // [F, De] or NULL (wide)
-  const float* bias;       // [F] or NULL
-  int De;
-};
-
 // ---- forward ---------------------------------------------------------------------------------
 template <typename IdxT, int EPL, bool VEC, int DE>
 __global__ void __launch_bounds__(kBlock)
     gine_fwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col,
                     const IdxT* __restrict__ edge_id, const float* __restrict__ x_src, int64_t ld,
                     const float* __restrict__ x_root, int64_t ld_root,
-                    const float* __restrict__ eps, GineEdge ed, int F, int lph,
+                    const float* __restrict__ eps, EdgeArgs ed, int F, int lph,
                     float* __restrict__ out, float* __restrict__ part) {
   constexpr int U = GineSlots<EPL, DE>::n;
   constexpr bool LIN = DE > 0;
@@ -51,10 +44,8 @@ __global__ void __launch_bounds__(kBlock)
   float w[LIN ? EPL : 1][LIN ? DE : 1], b[EPL];
   if constexpr (LIN) load_weight<EPL, VEC, DE>(ed.weight, ed.bias, L, ed.De, w, b);
   const int lane = lane_id();
-  const int64_t n_items = it.n_chunks + it.n_rows;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
-  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
-       item += stride) {
+  const Walk wk = item_walk(it);
+  for (int64_t item = wk.first; item < wk.n; item += wk.stride) {
     Span s;
     if (!decode(it, item, s)) continue;
     float acc[EPL];
@@ -66,10 +57,10 @@ __global__ void __launch_bounds__(kBlock)
       for (int u = 0; u < U; ++u) {
         if (k + u < s.k1) {
           const int64_t j = static_cast<int64_t>(col[k + u]);
-          const int64_t id = edge_id ? static_cast<int64_t>(edge_id[k + u]) : k + u;
+          const int64_t id = slot_edge(edge_id, k + u);
           load_row<EPL, VEC>(x_src + j * ld, L, xx[u]);
           if constexpr (LIN) {
-            av[u] = lane < ed.De ? ed.edge_attr[id * ed.De + lane] : 0.f;
+            av[u] = edge_lane(ed, id, lane);
           } else {
             load_row<EPL, VEC>(ed.edge_attr + id * F, L, ee[u]);
           }
@@ -127,7 +118,7 @@ template <typename IdxT, int EPL, bool VEC, int DE>
 __global__ void __launch_bounds__(kBlock)
     gine_bwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col_t,
                     const IdxT* __restrict__ edge_id_t, const float* __restrict__ x_src,
-                    int64_t ld, GineEdge ed, const float* __restrict__ grad_out, int F, int lph,
+                    int64_t ld, EdgeArgs ed, const float* __restrict__ grad_out, int F, int lph,
                     float* __restrict__ grad_x, float* __restrict__ grad_edge,
                     float* __restrict__ part, float* __restrict__ wpart) {
   constexpr int U = GineSlots<EPL, DE>::n;
@@ -145,10 +136,8 @@ __global__ void __launch_bounds__(kBlock)
     }
   }
   const int lane = lane_id();
-  const int64_t n_items = it.n_chunks + it.n_rows;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
-  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
-       item += stride) {
+  const Walk wk = item_walk(it);
+  for (int64_t item = wk.first; item < wk.n; item += wk.stride) {
     Span s;
     if (!decode(it, item, s)) continue;
     float x[EPL], gx[EPL];
@@ -162,10 +151,10 @@ __global__ void __launch_bounds__(kBlock)
       for (int u = 0; u < U; ++u) {
         if (t + u < s.k1) {
           const int64_t i = static_cast<int64_t>(col_t[t + u]);
-          id[u] = edge_id_t ? static_cast<int64_t>(edge_id_t[t + u]) : t + u;
+          id[u] = slot_edge(edge_id_t, t + u);
           load_row<EPL, VEC>(grad_out + i * F, L, gg[u]);
           if constexpr (LIN) {
-            av[u] = lane < ed.De ? ed.edge_attr[id[u] * ed.De + lane] : 0.f;
+            av[u] = edge_lane(ed, id[u], lane);
           } else {
             load_row<EPL, VEC>(ed.edge_attr + id[u] * F, L, ee[u]);
           }
@@ -182,28 +171,7 @@ __global__ void __launch_bounds__(kBlock)
             gx[e] += mg[e];
           }
           if constexpr (LIN) {
-#pragma unroll
-            for (int d = 0; d < DE; ++d) {
-              const float a = bcast_uniform(av[u], d);
-#pragma unroll
-              for (int e = 0; e < EPL; ++e) gw[e][d] = fmaf(mg[e], a, gw[e][d]);
-            }
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) gb[e] += mg[e];
-            if (grad_edge) {  // (wave-uniform)
-              float mine = 0.f;
-#pragma unroll
-              for (int d = 0; d < DE; ++d) {
-                if (d < ed.De) {
-                  float p = 0.f;
-#pragma unroll
-                  for (int e = 0; e < EPL; ++e) p = fmaf(mg[e], w[e][d], p);
-                  p = group_sum(p, kWave);
-                  if (lane == d) mine = p;
-                }
-              }
-              if (lane < ed.De) grad_edge[id[u] * ed.De + lane] = mine;
-            }
+            edge_grad_take<true, EPL, DE>(mg, av[u], w, ed.De, lane, grad_edge, id[u], gw, gb);
           } else {
             if (grad_edge) store_row<EPL, VEC>(grad_edge + id[u] * F, L, mg);
           }
@@ -241,34 +209,10 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-template <typename IdxT>
-__global__ void __launch_bounds__(kWave)
-    gine_bwd_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
-                          int64_t F, const float* __restrict__ part, float* __restrict__ grad_x) {
-  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), F, part, F, grad_x, F);
-}
-
-// the workgroups' partials (grad_W [F * De], then grad_b [F]) summed in workgroup order
-__global__ void __launch_bounds__(kBlock)
-    gine_param_reduce_kernel(const float* __restrict__ wpart, int n_blocks, int FD, int F,
-                             float* __restrict__ grad_weight, float* __restrict__ grad_bias) {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  const int S = FD + F;
-  if (t >= S) return;
-  float acc = 0.f;
-  for (int g = 0; g < n_blocks; ++g) acc += wpart[static_cast<int64_t>(g) * S + t];
-  if (t < FD) {
-    grad_weight[t] = acc;
-  } else if (grad_bias) {
-    grad_bias[t - FD] = acc;
-  }
-}
-
 // ---- host side -------------------------------------------------------------------------------
 size_t gine_ws_bytes(int64_t n_chunks, int64_t F, int64_t De) {
   // a chunk's partial row; in linear mode the backward's partials of (grad_W, grad_b) follow
-  const int64_t wpart = De > 0 ? static_cast<int64_t>(kGineBwdBlocks) * (F * De + F) : 0;
-  return sizeof(float) * static_cast<size_t>(n_chunks * F + wpart);
+  return sizeof(float) * static_cast<size_t>(n_chunks * F + wpart_floats(F, De, true));
 }
 
 }  // namespace
@@ -297,9 +241,11 @@ int pygamd_gine_forward(const pygamd_csr* g, const void* edge_id, const float* x
   const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld_src < F || (x_root && ld_root < F)) return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
-  if (!g->rowptr || !g->col || !x_src || !edge_attr || !out || (De > 0 && !weight) ||
-      (De == 0 && (weight || bias)))
-    return PYGAMD_ERR_INVALID_ARG;
+  const EdgeArgs ed{edge_attr, weight, bias, static_cast<int>(De)};
+  if (!g->rowptr || !g->col || !x_src || !out) return PYGAMD_ERR_INVALID_ARG;
+  // (the mode constants are the public ones of GEN; GINE has the wide and the linear mode)
+  const int rce = check_edge(De > 0 ? PYGAMD_GEN_EDGE_LINEAR : PYGAMD_GEN_EDGE_WIDE, ed);
+  if (rce != PYGAMD_OK) return rce;
   if (n_chunks > 0 && (!workspace || workspace_bytes < sizeof(float) * n_chunks * F))
     return PYGAMD_ERR_WORKSPACE;
   const bool al = aligned16(x_src) && ld_src % 4 == 0 && aligned16(out) &&
@@ -310,7 +256,6 @@ int pygamd_gine_forward(const pygamd_csr* g, const void* edge_id, const float* x
   if (!gine_shape(F, De, al, &sh)) return PYGAMD_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
-  const GineEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
   return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(gine_grid(n_rows + n_chunks, De > 0, kGineFwdBlocks)), block(kBlock);
@@ -337,13 +282,16 @@ int pygamd_gine_backward(const pygamd_csr* g, const void* edge_id_t, const float
                          float* grad_bias, void* workspace, size_t workspace_bytes, void* stream) {
   const int rc = gine_check(g, n_dst, F, De);
   if (rc != PYGAMD_OK) return rc;
-  const int64_t n_src = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
+  const int64_t n_src = g->n_rows, n_chunks = g->n_chunks;
   if (ld_src < F) return PYGAMD_ERR_INVALID_ARG;
   if (n_src == 0) return PYGAMD_OK;
-  if (!g->rowptr || !g->col || !x_src || !edge_attr || !grad_out || !grad_x_src ||
-      (De > 0 && (!weight || !grad_weight)) ||
-      (De == 0 && (weight || bias || grad_weight || grad_bias)) || (grad_bias && !bias))
+  const EdgeArgs ed{edge_attr, weight, bias, static_cast<int>(De)};
+  if (!g->rowptr || !g->col || !x_src || !grad_out || !grad_x_src ||
+      (De > 0) != (grad_weight != nullptr) || (grad_bias && !bias))
     return PYGAMD_ERR_INVALID_ARG;
+  // (the mode constants are the public ones of GEN; GINE has the wide and the linear mode)
+  const int rce = check_edge(De > 0 ? PYGAMD_GEN_EDGE_LINEAR : PYGAMD_GEN_EDGE_WIDE, ed);
+  if (rce != PYGAMD_OK) return rce;
   if ((n_chunks > 0 || De > 0) &&
       (!workspace || workspace_bytes < gine_ws_bytes(n_chunks, F, De)))
     return PYGAMD_ERR_WORKSPACE;
@@ -356,7 +304,6 @@ int pygamd_gine_backward(const pygamd_csr* g, const void* edge_id_t, const float
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   float* wpart = part + n_chunks * F;
-  const GineEdge ed{edge_attr, weight, bias, static_cast<int>(De)};
   return PYGAMD_DISPATCH_IDX(g->idx_dtype, [&]() -> int {
     const Items<IdxT> it = make_items<IdxT>(*g);
     const unsigned n_blocks = gine_grid(n_src + n_chunks, De > 0, kGineBwdBlocks);
@@ -368,19 +315,8 @@ int pygamd_gine_backward(const pygamd_csr* g, const void* edge_id_t, const float
                          grad_edge_attr, part, wpart);
     });
     PYGAMD_LAUNCH_CHECK();
-    if (n_hub > 0) {
-      hipLaunchKernelGGL((gine_bwd_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
-                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, F, part, grad_x_src);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    if (De > 0) {
-      const int S = static_cast<int>(F * De + F);
-      hipLaunchKernelGGL(gine_param_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(S, kBlock))),
-                         block, 0, st, wpart, static_cast<int>(n_blocks),
-                         static_cast<int>(F * De), static_cast<int>(F), grad_weight, grad_bias);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    return PYGAMD_OK;
+    return launch_backward_tail<IdxT>(it, F, De, true, n_blocks, part, grad_x_src, wpart,
+                                      grad_weight, grad_bias, st);
   });
 }
 

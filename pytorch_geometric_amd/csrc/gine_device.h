@@ -1,7 +1,14 @@
-// gine_device.h — what the kernels with a per-slot linear edge term share (gine.hip, pna.hip): the
-// envelope, a lane's rows of the edge weight in registers, the edge term from a slot's raw
-// features, the lane shape with its register capacity for De, the capped grid and the dispatch
-// over the instantiations.  Lane layout, work items and merges: attn_device.h.
+// gine_device.h — what the kernels with a per-slot linear edge term W a_k (+ b) share (gine.hip,
+// pna.hip, gen.hip).  Forward side: the envelope, the edge arguments, a slot's edge id and raw
+// features, a lane's rows of the edge weight in registers, the edge term, the lane shape with its
+// register capacity for De, the walk over the items, the capped grid and the dispatch over the
+// instantiations.  Backward side: the update of the parameter gradients in registers by a slot
+// (gine.hip and pna.hip; gen.hip keeps it written out, the call cost its backward 1 %), the
+// reduce of the workgroups' partials in workgroup order, the sum merge of a hub row's chunks
+// and the launch of those two.  Each kernel keeps its own loop, loads and arithmetic in its own
+// file — and the fold of a workgroup's waves into its partial through LDS, which as a function
+// changed the register allocation of the backward (CHANGELOG).  Lane layout, work items and
+// merges: attn_device.h.
 #pragma once
 #include "attn_device.h"
 #include "common.h"
@@ -54,6 +61,101 @@ __device__ __forceinline__ void edge_term(const float (&w)[EPL][DE], const float
     const float a = bcast_uniform(av, d);
 #pragma unroll
     for (int e = 0; e < EPL; ++e) ev[e] = fmaf(w[e][d], a, ev[e]);
+  }
+}
+
+// ---- the edge arguments and a slot's fetch ---------------------------------------------------
+struct EdgeArgs {
+  const float* edge_attr;  // [E, F] (wide), [E, De] (linear) or NULL (no edge term)
+  const float* weight;     // [F, De] or NULL
+  const float* bias;       // [F] or NULL
+  int De;
+};
+
+// the edge of slot k in the original edge order
+template <typename IdxT>
+__device__ __forceinline__ int64_t slot_edge(const IdxT* __restrict__ edge_id, int64_t k) {
+  return edge_id ? static_cast<int64_t>(edge_id[k]) : k;
+}
+
+// this lane's entry of a_k, the raw features of edge `id` (0 beyond De)
+__device__ __forceinline__ float edge_lane(const EdgeArgs& ed, int64_t id, int lane) {
+  return lane < ed.De ? ed.edge_attr[id * ed.De + lane] : 0.f;
+}
+
+// the items of a wave: for (item = wk.first; item < wk.n; item += wk.stride)
+struct Walk {
+  int64_t n, stride, first;
+};
+
+template <typename IdxT>
+__device__ __forceinline__ Walk item_walk(const Items<IdxT>& it) {
+  return Walk{it.n_chunks + it.n_rows, static_cast<int64_t>(gridDim.x) * kWavesPerBlock,
+              xcd_logical_block() * kWavesPerBlock + wave_in_block()};
+}
+
+// ---- backward of the linear edge term ---------------------------------------------------------
+// grad_W[f, d] = sum_k g_k[f] a_k[d] and grad_b[f] = sum_k g_k[f] accumulate in the lane's registers
+// gw and gb (the kernel zeroes them) over all items of the wave.  BIAS = false: no grad_b, gb is
+// not touched and may be any array of the lane.
+//
+// One slot with the gradient g of its edge term (already masked) and its raw features `av` (lane
+// d holds a[d]): gw and gb take it in, and grad_edge_attr[id, d] = sum_f g[f] W[f, d], a wave sum
+// per d, goes to row `id` of grad_edge (NULL, wave-uniform: not wanted).
+template <bool BIAS, int EPL, int DE>
+__device__ __forceinline__ void edge_grad_take(const float (&g)[EPL], float av,
+                                               const float (&w)[EPL][DE], int De, int lane,
+                                               float* grad_edge, int64_t id,
+                                               float (&gw)[EPL][DE], float (&gb)[EPL]) {
+#pragma unroll
+  for (int d = 0; d < DE; ++d) {
+    const float a = bcast_uniform(av, d);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) gw[e][d] = fmaf(g[e], a, gw[e][d]);
+  }
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) gb[e] += g[e];
+  }
+  if (grad_edge) {
+    float mine = 0.f;
+#pragma unroll
+    for (int d = 0; d < DE; ++d) {
+      if (d < De) {
+        float p = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) p = fmaf(g[e], w[e][d], p);
+        p = group_sum(p, kWave);
+        if (lane == d) mine = p;
+      }
+    }
+    if (lane < De) grad_edge[id * De + lane] = mine;
+  }
+}
+
+// (the two kernels are static: every file that launches them carries its own copy)
+// hub rows, backward: the chunks' partial rows summed in chunk order
+template <typename IdxT>
+static __global__ void __launch_bounds__(kWave)
+    sum_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
+                     int64_t F, const float* __restrict__ part, float* __restrict__ grad_x) {
+  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), F, part, F, grad_x, F);
+}
+
+// the workgroups' partials (grad_W [FD], then grad_b [F]; F = 0: no bias block) summed in
+// workgroup order
+static __global__ void __launch_bounds__(kBlock)
+    param_reduce_kernel(const float* __restrict__ wpart, int n_blocks, int FD, int F,
+                        float* __restrict__ grad_weight, float* __restrict__ grad_bias) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  const int S = FD + F;
+  if (t >= S) return;
+  float acc = 0.f;
+  for (int g = 0; g < n_blocks; ++g) acc += wpart[static_cast<int64_t>(g) * S + t];
+  if (t < FD) {
+    grad_weight[t] = acc;
+  } else if (grad_bias) {
+    grad_bias[t - FD] = acc;
   }
 }
 
@@ -116,6 +218,49 @@ inline unsigned gine_grid(int64_t n_items, bool linear, unsigned cap) {
     GINE_CASE(8, false, 16, __VA_ARGS__) GINE_CASE(8, true, 16, __VA_ARGS__)         \
     { return PYGAMD_ERR_UNSUPPORTED; }                                               \
   } while (0)
+
+// the edge arguments against the mode (PYGAMD_GEN_EDGE_*: none, wide, linear); 0 = go on
+inline int check_edge(int edge_mode, const EdgeArgs& ed) {
+  switch (edge_mode) {
+    case PYGAMD_GEN_EDGE_NONE:
+      return (ed.De == 0 && !ed.edge_attr && !ed.weight && !ed.bias) ? PYGAMD_OK
+                                                                      : PYGAMD_ERR_INVALID_ARG;
+    case PYGAMD_GEN_EDGE_WIDE:
+      return (ed.De == 0 && ed.edge_attr && !ed.weight && !ed.bias) ? PYGAMD_OK
+                                                                     : PYGAMD_ERR_INVALID_ARG;
+    case PYGAMD_GEN_EDGE_LINEAR:
+      return (ed.De > 0 && ed.edge_attr && ed.weight) ? PYGAMD_OK : PYGAMD_ERR_INVALID_ARG;
+    default:
+      return PYGAMD_ERR_INVALID_ARG;
+  }
+}
+
+// floats of the backward's per-workgroup partials of (grad_W[, grad_b]) in the workspace
+inline int64_t wpart_floats(int64_t F, int64_t De, bool bias_block) {
+  return De > 0 ? static_cast<int64_t>(kGineBwdBlocks) * (F * De + (bias_block ? F : 0)) : 0;
+}
+
+// what follows a backward's main launch of n_blocks workgroups: the hub rows' chunks into grad_x,
+// then (linear mode) the workgroups' partials into grad_weight and grad_bias (may be NULL)
+template <typename IdxT>
+inline int launch_backward_tail(const Items<IdxT>& it, int64_t F, int64_t De, bool bias_block,
+                                unsigned n_blocks, const float* part, float* grad_x,
+                                const float* wpart, float* grad_weight, float* grad_bias,
+                                hipStream_t st) {
+  if (it.n_hub > 0) {
+    hipLaunchKernelGGL((sum_merge_kernel<IdxT>), dim3(static_cast<unsigned>(it.n_hub)),
+                       dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, F, part, grad_x);
+    PYGAMD_LAUNCH_CHECK();
+  }
+  if (De > 0) {
+    const int FD = static_cast<int>(F * De), Fb = bias_block ? static_cast<int>(F) : 0;
+    hipLaunchKernelGGL(param_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(FD + Fb, kBlock))),
+                       dim3(kBlock), 0, st, wpart, static_cast<int>(n_blocks), FD, Fb, grad_weight,
+                       grad_bias);
+    PYGAMD_LAUNCH_CHECK();
+  }
+  return PYGAMD_OK;
+}
 
 inline int gine_check(const pygamd_csr* g, int64_t n_other, int64_t F, int64_t De) {
   if (De < 0) return PYGAMD_ERR_INVALID_ARG;

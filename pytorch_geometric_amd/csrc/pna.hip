@@ -76,19 +76,16 @@ template <typename IdxT, int EPL, bool VEC, int DE>
 __global__ void __launch_bounds__(kBlock)
     pna_fwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col, const IdxT* __restrict__ edge_id,
                    const float* __restrict__ p_src, int64_t ld, const float* __restrict__ p_dst,
-                   int64_t ld_dst, const float* __restrict__ edge_attr,
-                   const float* __restrict__ wc, int De, int W, int lph, PnaOut o,
+                   int64_t ld_dst, EdgeArgs ed, int W, int lph, PnaOut o,
                    float* __restrict__ part) {
   constexpr int U = PnaFwdSlots<EPL, DE>::n;
   constexpr bool LIN = DE > 0;
   const Lay L = make_lay(1, W, lph);
   float w[LIN ? EPL : 1][LIN ? DE : 1], unused[EPL];
-  if constexpr (LIN) load_weight<EPL, VEC, DE>(wc, nullptr, L, De, w, unused);
+  if constexpr (LIN) load_weight<EPL, VEC, DE>(ed.weight, nullptr, L, ed.De, w, unused);
   const int lane = lane_id();
-  const int64_t n_items = it.n_chunks + it.n_rows;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
-  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
-       item += stride) {
+  const Walk wk = item_walk(it);
+  for (int64_t item = wk.first; item < wk.n; item += wk.stride) {
     Span s;
     if (!decode(it, item, s)) continue;  // (a row without slots is an item: it gets its zeros)
     float sh[EPL], s1[EPL], s2[EPL], mn[EPL], mx[EPL], cmn[EPL], cmx[EPL];
@@ -105,10 +102,7 @@ __global__ void __launch_bounds__(kBlock)
         if (k + u < s.k1) {
           const int64_t j = static_cast<int64_t>(col[k + u]);
           load_row<EPL, VEC>(p_src + j * ld, L, xx[u]);
-          if constexpr (LIN) {
-            const int64_t id = edge_id ? static_cast<int64_t>(edge_id[k + u]) : k + u;
-            av[u] = lane < De ? edge_attr[id * De + lane] : 0.f;
-          }
+          if constexpr (LIN) av[u] = edge_lane(ed, slot_edge(edge_id, k + u), lane);
         }
       }
 #pragma unroll
@@ -247,8 +241,7 @@ template <typename IdxT, int EPL, bool VEC, int DE>
 __global__ void __launch_bounds__(kBlock)
     pna_bwd_kernel(Items<IdxT> it, const IdxT* __restrict__ col_t,
                    const IdxT* __restrict__ edge_id_t, const float* __restrict__ p_src, int64_t ld,
-                   const float* __restrict__ edge_attr, const float* __restrict__ wc, int De,
-                   const float* __restrict__ coef, int stats, int W, int lph,
+                   EdgeArgs ed, const float* __restrict__ coef, int stats, int W, int lph,
                    float* __restrict__ grad_p, float* __restrict__ grad_edge,
                    float* __restrict__ part, float* __restrict__ wpart) {
   constexpr int U = PnaBwdSlots<EPL, DE>::n;
@@ -256,7 +249,7 @@ __global__ void __launch_bounds__(kBlock)
   const Lay L = make_lay(1, W, lph);
   float w[LIN ? EPL : 1][LIN ? DE : 1], gw[LIN ? EPL : 1][LIN ? DE : 1], unused[EPL];
   if constexpr (LIN) {
-    load_weight<EPL, VEC, DE>(wc, nullptr, L, De, w, unused);
+    load_weight<EPL, VEC, DE>(ed.weight, nullptr, L, ed.De, w, unused);
 #pragma unroll
     for (int e = 0; e < EPL; ++e) {
 #pragma unroll
@@ -266,10 +259,8 @@ __global__ void __launch_bounds__(kBlock)
   const bool has_a = (stats & (kPnaMean | kPnaStd)) != 0, has_b = (stats & kPnaStd) != 0;
   const bool has_min = (stats & kPnaMin) != 0, has_max = (stats & kPnaMax) != 0;
   const int lane = lane_id();
-  const int64_t n_items = it.n_chunks + it.n_rows;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
-  for (int64_t item = xcd_logical_block() * kWavesPerBlock + wave_in_block(); item < n_items;
-       item += stride) {
+  const Walk wk = item_walk(it);
+  for (int64_t item = wk.first; item < wk.n; item += wk.stride) {
     Span s;
     if (!decode(it, item, s)) continue;
     float x[EPL], gx[EPL];
@@ -285,7 +276,7 @@ __global__ void __launch_bounds__(kBlock)
         for (int e = 0; e < EPL; ++e) ca[u][e] = cb[u][e] = gn[u][e] = gm[u][e] = vn[u][e] = vm[u][e] = 0.f;
         if (t + u < s.k1) {
           const int64_t i = static_cast<int64_t>(col_t[t + u]);
-          id[u] = edge_id_t ? static_cast<int64_t>(edge_id_t[t + u]) : t + u;
+          id[u] = slot_edge(edge_id_t, t + u);
           const float* c = coef + i * kPnaCoef * W;
           if (has_a) load_row<EPL, VEC>(c, L, ca[u]);
           if (has_b) load_row<EPL, VEC>(c + W, L, cb[u]);
@@ -297,7 +288,7 @@ __global__ void __launch_bounds__(kBlock)
             load_row<EPL, VEC>(c + 3 * W, L, gm[u]);
             load_row<EPL, VEC>(c + 5 * W, L, vm[u]);
           }
-          if constexpr (LIN) av[u] = lane < De ? edge_attr[id[u] * De + lane] : 0.f;
+          if constexpr (LIN) av[u] = edge_lane(ed, id[u], lane);
         }
       }
 #pragma unroll
@@ -318,27 +309,8 @@ __global__ void __launch_bounds__(kBlock)
             gu[e] = g;
             gx[e] += g;
           }
-          if constexpr (LIN) {
-#pragma unroll
-            for (int d = 0; d < DE; ++d) {
-              const float a = bcast_uniform(av[u], d);
-#pragma unroll
-              for (int e = 0; e < EPL; ++e) gw[e][d] = fmaf(gu[e], a, gw[e][d]);
-            }
-            if (grad_edge) {  // (wave-uniform)
-              float mine = 0.f;
-#pragma unroll
-              for (int d = 0; d < DE; ++d) {
-                if (d < De) {
-                  float p = 0.f;
-#pragma unroll
-                  for (int e = 0; e < EPL; ++e) p = fmaf(gu[e], w[e][d], p);
-                  p = group_sum(p, kWave);
-                  if (lane == d) mine = p;
-                }
-              }
-              if (lane < De) grad_edge[id[u] * De + lane] = mine;
-            }
+          if constexpr (LIN) {  // (no bias: `unused` stays untouched)
+            edge_grad_take<false, EPL, DE>(gu, av[u], w, ed.De, lane, grad_edge, id[u], gw, unused);
           }
         }
       }
@@ -351,6 +323,7 @@ __global__ void __launch_bounds__(kBlock)
   }
   if constexpr (LIN) {
     __shared__ float red[kGineMaxWeight];
+    const int De = ed.De;
     const int WD = W * De;
     for (int wv = 0; wv < kWavesPerBlock; ++wv) {
       if (wave_in_block() == wv) {
@@ -372,32 +345,14 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-template <typename IdxT>
-__global__ void __launch_bounds__(kWave)
-    pna_bwd_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
-                         int64_t W, const float* __restrict__ part, float* __restrict__ grad_p) {
-  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), W, part, W, grad_p, W);
-}
-
-// the workgroups' partials of grad_Wc [W * De] summed in workgroup order
-__global__ void __launch_bounds__(kBlock)
-    pna_param_reduce_kernel(const float* __restrict__ wpart, int n_blocks, int WD,
-                            float* __restrict__ grad_wc) {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  if (t >= WD) return;
-  float acc = 0.f;
-  for (int g = 0; g < n_blocks; ++g) acc += wpart[static_cast<int64_t>(g) * WD + t];
-  grad_wc[t] = acc;
-}
-
 // ---- host side -------------------------------------------------------------------------------
 // the chunks' partials of the forward (the backward's single row per chunk fits inside them), then
 // the backward's per-workgroup partials of grad_Wc
 int64_t pna_chunk_floats(int64_t n_chunks, int64_t W) { return n_chunks * kPnaParts * W; }
 
 size_t pna_ws_bytes(int64_t n_chunks, int64_t W, int64_t De) {
-  const int64_t wpart = De > 0 ? static_cast<int64_t>(kGineBwdBlocks) * W * De : 0;
-  return sizeof(float) * static_cast<size_t>(pna_chunk_floats(n_chunks, W) + wpart);
+  return sizeof(float) *
+         static_cast<size_t>(pna_chunk_floats(n_chunks, W) + wpart_floats(W, De, false));
 }
 
 }  // namespace
@@ -426,9 +381,11 @@ int pygamd_pna_forward(const pygamd_csr* g, const void* edge_id, const float* p_
   const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
   if (ld_src < W || ld_dst < W || stats < 1 || stats > 15) return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
-  if (!g->rowptr || !g->col || !p_src || !p_dst || !out || !saved ||
-      (De > 0 && (!wc || !edge_attr)) || (De == 0 && (wc || edge_attr)))
-    return PYGAMD_ERR_INVALID_ARG;
+  const EdgeArgs ed{edge_attr, wc, nullptr, static_cast<int>(De)};
+  if (!g->rowptr || !g->col || !p_src || !p_dst || !out || !saved) return PYGAMD_ERR_INVALID_ARG;
+  // (the mode constants are the public ones of GEN; PNA has no edge term or the linear one)
+  const int rce = check_edge(De > 0 ? PYGAMD_GEN_EDGE_LINEAR : PYGAMD_GEN_EDGE_NONE, ed);
+  if (rce != PYGAMD_OK) return rce;
   if (n_chunks > 0 && (!workspace || workspace_bytes < pna_ws_bytes(n_chunks, W, 0)))
     return PYGAMD_ERR_WORKSPACE;
   const bool al = aligned16(p_src) && ld_src % 4 == 0 && aligned16(p_dst) && ld_dst % 4 == 0 &&
@@ -451,8 +408,7 @@ int pygamd_pna_forward(const pygamd_csr* g, const void* edge_id, const float* p_
     GINE_DISPATCH({
       hipLaunchKernelGGL((pna_fwd_kernel<IdxT, EPL, VEC, DE>), grid, block, 0, st, it,
                          typed_col<IdxT>(*g), static_cast<const IdxT*>(edge_id), p_src, ld_src,
-                         p_dst, ld_dst, edge_attr, wc, static_cast<int>(De), static_cast<int>(W),
-                         sh.lph, o, part);
+                         p_dst, ld_dst, ed, static_cast<int>(W), sh.lph, o, part);
     });
     PYGAMD_LAUNCH_CHECK();
     if (n_hub > 0) {
@@ -471,13 +427,16 @@ int pygamd_pna_backward(const pygamd_csr* g, const void* edge_id_t, const float*
                         size_t workspace_bytes, void* stream) {
   const int rc = gine_check(g, n_dst, W, De);
   if (rc != PYGAMD_OK) return rc;
-  const int64_t n_src = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
+  const int64_t n_src = g->n_rows, n_chunks = g->n_chunks;
   if (ld_src < W || stats < 1 || stats > 15) return PYGAMD_ERR_INVALID_ARG;
   if (n_src == 0) return PYGAMD_OK;
+  const EdgeArgs ed{edge_attr, wc, nullptr, static_cast<int>(De)};
   if (!g->rowptr || !g->col || !p_src || !coef || !grad_p_src ||
-      (De > 0 && (!wc || !edge_attr || !grad_wc)) ||
-      (De == 0 && (wc || edge_attr || grad_wc || grad_edge_attr)))
+      (De > 0) != (grad_wc != nullptr) || (De == 0 && grad_edge_attr))
     return PYGAMD_ERR_INVALID_ARG;
+  // (the mode constants are the public ones of GEN; PNA has no edge term or the linear one)
+  const int rce = check_edge(De > 0 ? PYGAMD_GEN_EDGE_LINEAR : PYGAMD_GEN_EDGE_NONE, ed);
+  if (rce != PYGAMD_OK) return rce;
   if ((n_chunks > 0 || De > 0) && (!workspace || workspace_bytes < pna_ws_bytes(n_chunks, W, De)))
     return PYGAMD_ERR_WORKSPACE;
   const bool al = aligned16(p_src) && ld_src % 4 == 0 && aligned16(coef) &&
@@ -494,23 +453,12 @@ int pygamd_pna_backward(const pygamd_csr* g, const void* edge_id_t, const float*
     GINE_DISPATCH({
       hipLaunchKernelGGL((pna_bwd_kernel<IdxT, EPL, VEC, DE>), grid, block, 0, st, it,
                          typed_col<IdxT>(*g), static_cast<const IdxT*>(edge_id_t), p_src, ld_src,
-                         edge_attr, wc, static_cast<int>(De), coef, stats, static_cast<int>(W),
-                         sh.lph, grad_p_src, grad_edge_attr, part, wpart);
+                         ed, coef, stats, static_cast<int>(W), sh.lph, grad_p_src, grad_edge_attr,
+                         part, wpart);
     });
     PYGAMD_LAUNCH_CHECK();
-    if (n_hub > 0) {
-      hipLaunchKernelGGL((pna_bwd_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
-                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, W, part, grad_p_src);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    if (De > 0) {
-      const int WD = static_cast<int>(W * De);
-      hipLaunchKernelGGL(pna_param_reduce_kernel,
-                         dim3(static_cast<unsigned>(ceil_div(WD, kBlock))), block, 0, st, wpart,
-                         static_cast<int>(n_blocks), WD, grad_wc);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    return PYGAMD_OK;
+    return launch_backward_tail<IdxT>(it, W, De, false, n_blocks, part, grad_p_src, wpart, grad_wc,
+                                      nullptr, st);
   });
 }
 
