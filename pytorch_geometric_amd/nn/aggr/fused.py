@@ -186,6 +186,10 @@ class MultiAggregation(Aggregation):
             fused_outs = iter(self.fused_aggr(x, index, ptr, dim_size, dim))
             outs = [next(fused_outs) if f else a(x, index, ptr, dim_size, dim)
                     for a, f in zip(self.aggrs, self.is_fused)]
+        return self.combine(outs)
+
+    def combine(self, outs: List[Tensor]) -> Tensor:
+        """the members' results under ``mode``"""
         if len(outs) == 1:
             return outs[0]
         if self.mode == 'cat':

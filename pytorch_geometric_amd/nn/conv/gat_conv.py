@@ -9,7 +9,8 @@ from torch.nn import Parameter
 from ..._functions import (GatAttendFunction, GatEdgeSoftmaxFunction, HeadDotFunction,
                            SpmmFunction, bias_act)
 from ...edge_index import EdgeIndex, as_edge_index
-from ...utils import add_self_loops, remove_self_loops, softmax
+from ...utils import add_self_loops, remove_self_loops
+from .._host import softmax
 from ..dense.linear import Linear
 from ..inits import glorot, zeros
 from ._act_request import requested_activation
@@ -63,6 +64,7 @@ class GATConv(MessagePassing):
         self.res = _glorot_linear(dst_in, out_width) if residual else None
         self.register_parameter('bias', Parameter(torch.empty(out_width)) if bias else None)
         self._loop_cache = None
+        self.fuse = True
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -199,11 +201,7 @@ class GATConv(MessagePassing):
         else:
             alpha = self.edge_updater(edge_index, alpha=(a_src, a_dst), edge_attr=edge_attr,
                                       size=size)
-            keep, self.fuse = self.fuse, False
-            try:
-                out = self.propagate(edge_index, x=(x_src, x_dst), alpha=alpha, size=size)
-            finally:
-                self.fuse = keep
+            out = self.propagate(edge_index, x=(x_src, x_dst), alpha=alpha, size=size)
 
         out = out.reshape(-1, H * C) if self.concat else out.mean(dim=1)
         if res is not None:
@@ -236,9 +234,6 @@ class GATConv(MessagePassing):
 
     def message(self, x_j: Tensor, alpha: Tensor) -> Tensor:
         return alpha.unsqueeze(-1) * x_j
-
-    def message_and_aggregate(self, graph: EdgeIndex, x, alpha) -> Tensor:
-        raise NotImplementedError  # fusion is driven from forward() (needs slot-ordered alpha)
 
     def __repr__(self) -> str:
         return (f'{type(self).__name__}({self.in_channels}, {self.out_channels}, '

@@ -9,7 +9,8 @@ from torch.nn import Parameter
 from ... import _native
 from ..._functions import Gatv2AttendFunction, Gatv2ScoreFunction, SpmmFunction, bias_act
 from ...edge_index import EdgeIndex, as_edge_index
-from ...utils import add_self_loops, remove_self_loops, softmax
+from ...utils import add_self_loops, remove_self_loops
+from .._host import softmax
 from ..dense.linear import Linear
 from ..inits import glorot, zeros
 from ._act_request import requested_activation
@@ -35,8 +36,8 @@ class GATv2Conv(MessagePassing):
       online softmax and the weighted sum (``Gatv2AttendFunction``);
     * score mode (dropout on the coefficients in training, ``return_attention_weights``): the same
       kernel writes ``alpha [E, H]`` only, the multi-head weighted SpMM aggregates;
-    * generic gather -> ``edge_update`` -> scatter for ``edge_dim``, CPU tensors, ``fuse = False``,
-      ``target_to_source`` and head layouts the kernels do not serve (``H * C > 512``).
+    * generic gather -> ``edge_update`` -> scatter for ``edge_dim``, host tensors, ``fuse =
+      False``, ``target_to_source`` and head layouts the kernels do not serve (``H * C > 512``).
     """
 
     def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int,
@@ -65,6 +66,7 @@ class GATv2Conv(MessagePassing):
         else:
             self.register_parameter('res', None)
         self.register_parameter('bias', Parameter(torch.empty(out_width)) if bias else None)
+        self.fuse = True
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -186,15 +188,9 @@ class GATv2Conv(MessagePassing):
                     alpha[graph.by_dst().perm.long()] = weights
             else:
                 out = Gatv2AttendFunction.apply(x_l, x_r, att, graph, self.negative_slope, n_dst)
-        elif not x_l.is_cuda:
-            out, alpha = self._attend_host(x_l, x_r, att, edge_index, edge_attr)
         else:
-            keep, self.fuse = self.fuse, False
-            try:
-                alpha = self.edge_updater(edge_index, x=(x_l, x_r), edge_attr=edge_attr)
-                out = self.propagate(edge_index, x=(x_l, x_r), alpha=alpha)
-            finally:
-                self.fuse = keep
+            alpha = self.edge_updater(edge_index, x=(x_l, x_r), edge_attr=edge_attr)
+            out = self.propagate(edge_index, x=(x_l, x_r), alpha=alpha)
 
         out = out.reshape(-1, H * C) if self.concat else out.mean(dim=1)
         if res is not None:
@@ -212,33 +208,6 @@ class GATv2Conv(MessagePassing):
         coo = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
         return out, (coo, alpha)
 
-    def _attend_host(self, x_l: Tensor, x_r: Tensor, att: Tensor, edge_index,
-                     edge_attr: Optional[Tensor]):
-        """Host tensors: ``edge_update`` + ``message`` + the sum aggregation written out in plain
-        torch, with the reference's softmax (maximum subtracted, ``1e-16`` on the denominator,
-        utils/_softmax.py).  The layer computes where its tensors live; nothing on the device
-        path comes here."""
-        ei = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
-        i, j = self._ij()
-        index = ei[i].long()
-        n = x_r.size(0)
-        pre = x_r.index_select(0, index) + x_l.index_select(0, ei[j].long())
-        if edge_attr is not None:
-            e = edge_attr.view(-1, 1) if edge_attr.dim() == 1 else edge_attr
-            assert self.lin_edge is not None
-            pre = pre + self.lin_edge(e).view(-1, self.heads, self.out_channels)
-        score = (F.leaky_relu(pre, self.negative_slope) * att).sum(dim=-1)
-        where = index.view(-1, 1).expand_as(score)
-        top = score.new_full((n, self.heads), float('-inf')).scatter_reduce(
-            0, where, score.detach(), 'amax', include_self=True)
-        num = (score - top.index_select(0, index)).exp()
-        den = score.new_zeros(n, self.heads).index_add_(0, index, num) + 1e-16
-        alpha = F.dropout(num / den.index_select(0, index), p=self.dropout,
-                          training=self.training)
-        msg = x_l.index_select(0, ei[j].long()) * alpha.unsqueeze(-1)
-        out = msg.new_zeros(n, self.heads, self.out_channels).index_add_(0, index, msg)
-        return out, alpha
-
     def edge_update(self, x_j: Tensor, x_i: Tensor, edge_attr: Optional[Tensor], index: Tensor,
                     ptr: Optional[Tensor], dim_size: Optional[int]) -> Tensor:
         x = x_i + x_j
@@ -255,9 +224,6 @@ class GATv2Conv(MessagePassing):
 
     def message(self, x_j: Tensor, alpha: Tensor) -> Tensor:
         return x_j * alpha.unsqueeze(-1)
-
-    def message_and_aggregate(self, graph: EdgeIndex, x, alpha) -> Tensor:
-        raise NotImplementedError  # fusion is driven from forward() (needs slot-ordered alpha)
 
     def __repr__(self) -> str:
         return (f'{type(self).__name__}({self.in_channels}, {self.out_channels}, '

@@ -6,19 +6,15 @@ from torch import Tensor
 
 from ... import _native
 from ..._functions import GenAggregateFunction
-from ...edge_index import EdgeIndex, as_edge_index
-from ..aggr import (Aggregation, MaxAggregation, MeanAggregation, MinAggregation,
-                    MultiAggregation, PowerMeanAggregation, SoftmaxAggregation, SumAggregation)
+from ...edge_index import as_edge_index
+from ..aggr import Aggregation, MultiAggregation, SoftmaxAggregation
 from ..dense.linear import Linear
 from ..inits import reset
 from ..norm import MessageNorm
-from .gin_conv import _LOW, _n_dst
-from .message_passing import MessagePassing
+from .message_passing import _FLOATS, _LOW, MessagePassing, _n_dst
 
 # PYGAMD_FUSE_GEN=0: GENConv layers start with ``fuse = False`` (read at import)
 FUSE_GEN = os.environ.get('PYGAMD_FUSE_GEN', '1') not in ('', '0')
-
-_FLOATS = (torch.float32, ) + _LOW
 
 
 class MLP(torch.nn.Sequential):
@@ -68,10 +64,9 @@ class GENConv(MessagePassing):
       registers and every column keeps its own running softmax: nothing of size ``E x F`` is
       formed or saved.  ``lin_src``, ``msg_norm``, ``+ lin_dst(x_dst)`` and the MLP stay in torch,
       in the reference's order;
-    * generic gather -> ``message`` -> ``aggr_module`` for everything else on the device
-      (``powermean``, ``add`` / ``mean`` / ``max``, lists, ``target_to_source``, ``fuse = False``,
-      ``F > 512``, ``edge_dim > 32`` or ``F * edge_dim > 4096``);
-    * host tensors compute in plain torch.
+    * generic gather -> ``message`` -> ``aggr_module`` for everything else (host tensors,
+      ``powermean``, ``add`` / ``mean`` / ``max``, lists, ``target_to_source``, ``fuse = False``,
+      ``F > 512``, ``edge_dim > 32`` or ``F * edge_dim > 4096``).
 
     Half and bfloat16 device inputs are widened to float32 and the aggregate handed back in
     their dtype outside autocast.  ``fuse`` is a per-layer attribute initialised from the
@@ -130,7 +125,7 @@ class GENConv(MessagePassing):
             if hasattr(self, name):
                 getattr(self, name).reset_parameters()
 
-    # -- the three routes of propagate ---------------------------------------------------------------
+    # -- the fused route of propagate --------------------------------------------------------------
     def _fusable(self, x_src: Tensor, edge_attr: Optional[Tensor]) -> bool:
         if not (self.fuse and x_src.is_cuda and x_src.dim() == 2 and x_src.dtype in _FLOATS
                 and self.flow == 'source_to_target'
@@ -166,19 +161,6 @@ class GENConv(MessagePassing):
         return GenAggregateFunction.apply(x_src.float(), edge_attr, weight, bias, t, graph, n_dst,
                                           float(self.eps), bool(mod.semi_grad))
 
-    def _host(self, x: Tuple[Tensor, Optional[Tensor]], edge_index, edge_attr, size) -> Tensor:
-        i, j = self._ij()
-        ei = self._raw(edge_index)
-        index = ei[i].long()
-        if isinstance(edge_index, EdgeIndex):
-            n = edge_index.num_dst_nodes if i == 1 else edge_index.num_src_nodes
-        elif size is not None and size[i] is not None:
-            n = int(size[i])
-        else:
-            n = (x[i] if x[i] is not None else x[j]).size(0)
-        msg = self.message(x[j].index_select(0, ei[j].long()), edge_attr)
-        return _host_aggregate(self.aggr_module, msg, index, n)
-
     def forward(self, x: Union[Tensor, Tuple[Tensor, Optional[Tensor]]], edge_index,
                 edge_attr: Optional[Tensor] = None, size=None) -> Tensor:
         if isinstance(x, Tensor):
@@ -192,8 +174,6 @@ class GENConv(MessagePassing):
                               _n_dst(self, x_src, x[1], edge_index, size))
             if low is not None and not torch.is_autocast_enabled():
                 out = out.to(low)
-        elif not x_src.is_cuda:
-            out = self._host(x, edge_index, edge_attr, size)
         else:
             out = self.propagate(edge_index, x=x, edge_attr=edge_attr, size=size)
         if hasattr(self, 'lin_aggr_out'):
@@ -221,46 +201,3 @@ class GENConv(MessagePassing):
         return (f'{self.__class__.__name__}({self.in_channels}, {self.out_channels}, '
                 f'aggr={self.aggr})')
 
-
-def _host_aggregate(mod: Aggregation, msg: Tensor, index: Tensor, n: int) -> Tensor:
-    """``mod`` over per-edge rows ``msg [E, F]`` with destinations ``index`` in plain torch"""
-    F = msg.size(1)
-    expand = index.view(-1, 1).expand(-1, F)
-
-    def reduce(src, how):
-        return src.new_zeros(n, F).scatter_reduce(0, expand, src, how, include_self=False)
-
-    def mean(src):
-        cnt = torch.bincount(index, minlength=n).clamp(min=1).to(src.dtype).view(-1, 1)
-        return reduce(src, 'sum') / cnt
-
-    if isinstance(mod, MultiAggregation):
-        outs = [_host_aggregate(a, msg, index, n) for a in mod.aggrs]
-        if len(outs) == 1:
-            return outs[0]
-        if mod.mode == 'cat':
-            return torch.cat(outs, dim=-1)
-        stacked = torch.stack(outs, dim=0)
-        return {'sum': stacked.sum(0), 'mean': stacked.mean(0), 'max': stacked.max(0).values,
-                'min': stacked.min(0).values}[mod.mode]
-    if type(mod) is SoftmaxAggregation:
-        t = mod.t.view(1, -1) if isinstance(mod.t, Tensor) else mod.t
-        with torch.set_grad_enabled(torch.is_grad_enabled() and not mod.semi_grad):
-            logits = msg * t
-            top = reduce(logits.detach(), 'amax')
-            e = (logits - top.index_select(0, index)).exp()
-            alpha = e / (reduce(e, 'sum').index_select(0, index) + 1e-16)
-        return reduce(msg * alpha, 'sum')
-    if type(mod) is PowerMeanAggregation:
-        p = mod.p.view(1, -1) if isinstance(mod.p, Tensor) else mod.p
-        if not isinstance(p, Tensor) and p == 1:
-            return mean(msg)
-        out = mean(msg.clamp(min=mod.min_value, max=mod.max_value).pow(p))
-        return out.clamp(min=mod.min_value, max=mod.max_value).pow(1. / p)
-    if type(mod) is SumAggregation:
-        return reduce(msg, 'sum')
-    if type(mod) is MeanAggregation:
-        return mean(msg)
-    if type(mod) in (MaxAggregation, MinAggregation):
-        return reduce(msg, 'amax' if type(mod) is MaxAggregation else 'amin')
-    raise NotImplementedError(f"the host route has no aggregation '{type(mod).__name__}'")

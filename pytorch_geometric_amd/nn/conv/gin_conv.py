@@ -6,42 +6,13 @@ from torch import Tensor
 
 from ... import _native
 from ..._functions import GineAggregateFunction, SpmmFunction
-from ...edge_index import EdgeIndex, as_edge_index
+from ...edge_index import as_edge_index
 from ..dense.linear import Linear
 from ..inits import reset
-from .message_passing import MessagePassing
+from .message_passing import _LOW, MessagePassing, _n_dst, _pair
 
 # PYGAMD_FUSE_GINE=0: GINEConv layers start with ``fuse = False`` (read at import)
 FUSE_GINE = os.environ.get('PYGAMD_FUSE_GINE', '1') not in ('', '0')
-
-_LOW = (torch.float16, torch.bfloat16)
-
-
-def _pair(x) -> Tuple[Tensor, Optional[Tensor]]:
-    return (x, x) if isinstance(x, Tensor) else (x[0], x[1])
-
-
-def _host_sum(layer: MessagePassing, msg: Tensor, edge_index, n_dst: int) -> Optional[Tensor]:
-    """sum / mean of per-edge rows over their destinations in plain torch (host tensors)"""
-    if layer.aggr not in ('add', 'sum', 'mean'):
-        return None
-    ei = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
-    index = ei[layer._ij()[0]].long()
-    out = msg.new_zeros(n_dst, msg.size(-1)).index_add_(0, index, msg)
-    if layer.aggr == 'mean':
-        deg = torch.bincount(index, minlength=n_dst).clamp(min=1)
-        out = out / deg.to(out.dtype).unsqueeze(-1)
-    return out
-
-
-def _n_dst(layer: MessagePassing, x_src: Tensor, x_dst: Optional[Tensor], edge_index,
-           size) -> int:
-    i = layer._ij()[0]
-    if isinstance(edge_index, EdgeIndex):
-        return edge_index.num_dst_nodes
-    if size is not None and size[i] is not None:
-        return int(size[i])
-    return (x_dst if x_dst is not None else x_src).size(0)
 
 
 class GINConv(MessagePassing):
@@ -54,8 +25,7 @@ class GINConv(MessagePassing):
     ``eps`` is a parameter with ``train_eps`` and a buffer otherwise.  ``x`` is a tensor,
     ``(x_src, x_dst)`` or ``(x_src, None)`` (no self term).  Routes: float32 device tensors with
     ``flow='source_to_target'`` and the sum aggregation take the CSR sum SpMM
-    (``SpmmFunction``); everything else on the device takes the generic ``propagate``; host
-    tensors compute in plain torch."""
+    (``SpmmFunction``); everything else takes the generic ``propagate``."""
 
     def __init__(self, nn: Callable, eps: float = 0., train_eps: bool = False, **kwargs):
         kwargs.setdefault('aggr', 'add')
@@ -84,18 +54,7 @@ class GINConv(MessagePassing):
             graph = as_edge_index(edge_index, x_src.size(0), n_dst)
             out = SpmmFunction.apply(x_src, None, graph, 'sum', 'coo')
         else:
-            out = None
-            if not x_src.is_cuda:
-                n_dst = _n_dst(self, x_src, x_dst, edge_index, size)
-                ei = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
-                x_j = x_src.index_select(0, ei[self._ij()[1]].long())
-                out = _host_sum(self, x_j, edge_index, n_dst)
-            if out is None:
-                keep, self.fuse = self.fuse, False
-                try:
-                    out = self.propagate(edge_index, x=(x_src, x_dst), size=size)
-                finally:
-                    self.fuse = keep
+            out = self.propagate(edge_index, x=(x_src, x_dst), size=size)
         if x_dst is not None:
             out = out + (1 + self.eps) * x_dst[:out.size(0)]
         return self.nn(out)
@@ -124,10 +83,9 @@ class GINEConv(MessagePassing):
       and the sum, so the message is rebuilt per slot in registers: with ``edge_dim`` every lane
       keeps its columns' rows of ``lin.weight`` and reads the RAW ``edge_dim`` features of a
       slot, and nothing of size ``E x F`` is formed or saved;
-    * generic gather -> ``message`` -> scatter for everything else on the device (``fuse =
+    * generic gather -> ``message`` -> scatter for everything else (host tensors, ``fuse =
       False``, ``target_to_source``, other aggregations, ``F > 512``, ``edge_dim > 32`` or
-      ``F * edge_dim > 4096``);
-    * host tensors compute in plain torch.
+      ``F * edge_dim > 4096``).
 
     Half and bfloat16 device inputs are widened to float32 and the aggregate handed back in
     their dtype outside autocast.  ``fuse`` is a per-layer attribute initialised from the
@@ -197,18 +155,7 @@ class GINEConv(MessagePassing):
             if low is not None and not torch.is_autocast_enabled():
                 out = out.to(low)
             return self.nn(out)
-        out = None
-        if not x_src.is_cuda and isinstance(edge_attr, Tensor):
-            n_dst = _n_dst(self, x_src, x_dst, edge_index, size)
-            ei = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
-            x_j = x_src.index_select(0, ei[self._ij()[1]].long())
-            out = _host_sum(self, self.message(x_j, edge_attr), edge_index, n_dst)
-        if out is None:
-            keep, self.fuse = self.fuse, False
-            try:
-                out = self.propagate(edge_index, x=(x_src, x_dst), edge_attr=edge_attr, size=size)
-            finally:
-                self.fuse = keep
+        out = self.propagate(edge_index, x=(x_src, x_dst), edge_attr=edge_attr, size=size)
         if x_dst is not None:
             out = out + (1 + self.eps) * x_dst[:out.size(0)]
         return self.nn(out)

@@ -9,7 +9,7 @@ from torch.nn import Parameter
 
 from ... import _hgt
 from ..._functions import HgtRelationPlan, HGTRelationFunction, TransformerAttendFunction
-from ...utils import softmax
+from .._host import softmax
 from ..dense.linear import HeteroDictLinear, HeteroLinear, hetero_linear_forward
 from .message_passing import MessagePassing
 
@@ -33,10 +33,9 @@ class HGTConv(MessagePassing):
       matrices); ONE attention launch over the cached stacked bipartite handle
       (``TransformerAttendFunction``); the epilogue in plain tensor code.  Nothing of size
       ``E x F`` exists, forward or backward;
-    * generic (everything else on the device): the reference's formulation over this package's
-      ``HeteroLinear``, ``softmax`` and ``propagate`` (half / bf16 rows are widened to float32
-      for it);
-    * host tensors compute in plain torch.
+    * generic (everything else, host tensors included): the reference's formulation over this
+      package's ``HeteroLinear``, ``softmax`` and ``propagate`` (half / bf16 device rows are
+      widened to float32 for it; host rows take a ``bmm`` over the gathered relation matrices).
 
     Not offered: lazy ``-1`` widths, ``SparseTensor`` inputs, ``to_hetero``, routing of the
     reference's own class through ``backend.install()``.
@@ -109,12 +108,10 @@ class HGTConv(MessagePassing):
         st = _hgt.Stacking({t: v.size(0) for t, v in kqv_dict.items()}, ets)
         first = next(iter(kqv_dict.values()))
         low = None
-        if not first.is_cuda:
-            out = self._attend_host(kqv_dict, st, eis)
-        elif _hgt.eligible(self, x_dict, ets, eis):
+        if first.is_cuda and _hgt.eligible(self, x_dict, ets, eis):
             out = self._attend_fused(kqv_dict, st, eis)
         else:
-            if first.dtype in (torch.float16, torch.bfloat16):
+            if first.is_cuda and first.dtype in (torch.float16, torch.bfloat16):
                 low = first.dtype
                 kqv_dict = {t: v.float() for t, v in kqv_dict.items()}
             out = self._attend_generic(kqv_dict, st, eis)
@@ -199,6 +196,9 @@ class HGTConv(MessagePassing):
     def _attend_generic(self, kqv_dict, st: _hgt.Stacking, eis) -> Tensor:
         q = self._query(kqv_dict)
         def relation(k_rows, v_rows, type_vec):
+            if not k_rows.is_cuda:
+                return (torch.bmm(k_rows.unsqueeze(1), self.k_rel.weight[type_vec]).squeeze(1),
+                        torch.bmm(v_rows.unsqueeze(1), self.v_rel.weight[type_vec]).squeeze(1))
             if self.k_rel.weight.dtype == torch.float32:
                 return self.k_rel(k_rows, type_vec), self.v_rel(v_rows, type_vec)
             # half / bf16 parameters: the grouped product computes in float32
@@ -217,32 +217,6 @@ class HGTConv(MessagePassing):
             else (st.num_dst, st.num_src)
         return self.propagate(edge_index, k=k.contiguous(), q=q.contiguous(), v=v.contiguous(),
                               edge_attr=prior.to(q.dtype), size=size)
-
-    def _attend_host(self, kqv_dict, st: _hgt.Stacking, eis) -> Tensor:
-        """Host tensors: the same formulation written out in plain torch, with the reference's
-        softmax (maximum subtracted, ``1e-16`` on the denominator, utils/_softmax.py).  The layer
-        computes where its tensors live; nothing on the device path comes here."""
-        H, D = self.heads, self.out_channels // self.heads
-
-        def relation(k_rows, v_rows, type_vec):
-            return (torch.bmm(k_rows.unsqueeze(1), self.k_rel.weight[type_vec]).squeeze(1),
-                    torch.bmm(v_rows.unsqueeze(1), self.v_rel.weight[type_vec]).squeeze(1))
-
-        q = self._query(kqv_dict)
-        k, v = self._source_features(kqv_dict, st, relation)
-        edge_index, prior = self._stacked_edges(st, eis, q.device)
-        source, index = edge_index[0], edge_index[1]
-        n = st.num_dst
-        score = (q.index_select(0, index) * k.index_select(0, source)).sum(dim=-1) * prior
-        score = score / math.sqrt(D)
-        where = index.view(-1, 1).expand_as(score)
-        top = score.new_full((n, H), float('-inf')).scatter_reduce(
-            0, where, score.detach(), 'amax', include_self=True)
-        num = (score - top.index_select(0, index)).exp()
-        den = score.new_zeros(n, H).index_add_(0, index, num) + 1e-16
-        alpha = num / den.index_select(0, index)
-        msg = v.index_select(0, source) * alpha.unsqueeze(-1)
-        return msg.new_zeros(n, H, D).index_add_(0, index, msg)
 
     def message(self, k_j: Tensor, q_i: Tensor, v_j: Tensor, edge_attr: Tensor, index: Tensor,
                 ptr: Optional[Tensor], size_i: Optional[int]) -> Tensor:

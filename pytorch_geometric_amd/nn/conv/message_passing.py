@@ -6,16 +6,34 @@ from torch import Tensor
 
 from ..._functions import GatherFunction
 from ...edge_index import EdgeIndex, as_edge_index
+from .. import _host
 from ..aggr import Aggregation, aggregation_resolver
 
 _SPECIAL = {'edge_index', 'edge_index_i', 'edge_index_j', 'size', 'size_i', 'size_j', 'ptr',
             'index', 'dim_size'}
 _INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+# the dtypes the one-pass layers widen to float32, and the ones their kernels take after that
+_LOW = (torch.float16, torch.bfloat16)
+_FLOATS = (torch.float32, ) + _LOW
 
 
 def _params(fn) -> List[str]:
     return [n for n, p in inspect.signature(fn).parameters.items()
             if p.kind in (p.POSITIONAL_OR_KEYWORD, p.KEYWORD_ONLY)]
+
+
+def _pair(x) -> Tuple[Tensor, Optional[Tensor]]:
+    return (x, x) if isinstance(x, Tensor) else (x[0], x[1])
+
+
+def _n_dst(layer: 'MessagePassing', x_src: Tensor, x_dst: Optional[Tensor], edge_index,
+           size) -> int:
+    i = layer._ij()[0]
+    if isinstance(edge_index, EdgeIndex):
+        return edge_index.num_dst_nodes
+    if size is not None and size[i] is not None:
+        return int(size[i])
+    return (x_dst if x_dst is not None else x_src).size(0)
 
 
 class MessagePassing(torch.nn.Module):
@@ -32,6 +50,10 @@ class MessagePassing(torch.nn.Module):
     steps run as ONE CSR SpMM kernel on a cached, destination-sorted handle instead of
     materialising ``[E, F]`` messages (the reference only fuses for sparse ``adj_t`` inputs,
     message_passing.py:469-479; here every plain ``edge_index`` tensor is sorted once and cached).
+
+    The gather -> ``message`` -> ``aggregate`` route computes where its tensors live: host tensors
+    are gathered by ``index_select`` and reduced by ``nn/_host.py`` in plain torch.  The fused
+    route and the operators have no CPU fallback.
     """
 
     def __init__(self, aggr: Optional[Union[str, Aggregation]] = 'sum', *,
@@ -93,12 +115,18 @@ class MessagePassing(torch.nn.Module):
         """``src.index_select(node_dim, index)`` with the reference's IndexError on bad indices
         (message_passing.py:263-290)."""
         d = self.node_dim + src.dim() if self.node_dim < 0 else self.node_dim
-        s0 = src if d == 0 else src.movedim(d, 0).contiguous()
+        host = not src.is_cuda
         try:
+            if host:
+                return src.index_select(d, index.long())
+            s0 = src if d == 0 else src.movedim(d, 0).contiguous()
             out = GatherFunction.apply(s0, index, True)
         except IndexError as e:
-            from ... import _native
-            lo, hi = _native.index_minmax(index)
+            if host:
+                lo, hi = int(index.min()), int(index.max())
+            else:
+                from ... import _native
+                lo, hi = _native.index_minmax(index)
             n = src.size(self.node_dim)
             if lo < 0:
                 raise IndexError(
@@ -254,6 +282,10 @@ class MessagePassing(torch.nn.Module):
 
     def aggregate(self, inputs: Tensor, index: Tensor, ptr: Optional[Tensor] = None,
                   dim_size: Optional[int] = None) -> Tensor:
+        if not inputs.is_cuda:
+            d = self.node_dim % inputs.dim()
+            out = _host.aggregate(self.aggr_module, inputs.movedim(d, 0), index, dim_size)
+            return out.movedim(0, d)
         return self.aggr_module(inputs, index, ptr=ptr, dim_size=dim_size, dim=self.node_dim)
 
     def message_and_aggregate(self, graph: EdgeIndex) -> Tensor:

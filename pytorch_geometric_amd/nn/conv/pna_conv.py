@@ -11,13 +11,10 @@ from ...edge_index import EdgeIndex, as_edge_index
 from ..aggr.scaler import DegreeScalerAggregation, degree_scale
 from ..dense.linear import Linear
 from ..inits import reset
-from .message_passing import MessagePassing
+from .message_passing import _FLOATS, _LOW, MessagePassing
 
 # PYGAMD_FUSE_PNA=0: PNAConv layers start with ``fuse = False`` (read at import)
 FUSE_PNA = os.environ.get('PYGAMD_FUSE_PNA', '1') not in ('', '0')
-
-_LOW = (torch.float16, torch.bfloat16)
-_FLOATS = (torch.float32, ) + _LOW
 
 
 class PNAConv(MessagePassing):
@@ -38,9 +35,8 @@ class PNAConv(MessagePassing):
       ONE kernel per direction (``PnaAggregateFunction``, csrc/pna.hip) yields every statistic
       from one gathered row per edge: nothing of size ``E x towers * F_in`` is formed or saved.
       Degrees come from the handle's row pointer;
-    * generic gather -> ``message`` -> ``aggregate`` for everything else on the device, with the
-      towers flattened to ``[E, towers * F_in]``;
-    * host tensors compute in plain torch.
+    * generic gather -> ``message`` -> ``aggregate`` for everything else, host tensors included,
+      with the towers flattened to ``[E, towers * F_in]``.
 
     Half and bfloat16 device inputs are widened to float32 and the result handed back in their
     dtype outside autocast.  ``fuse`` is a per-layer attribute initialised from the environment
@@ -152,26 +148,12 @@ class PNAConv(MessagePassing):
         mod = self.aggr_module
         return degree_scale(out, deg, mod.scaler, mod.avg_deg_lin, mod.avg_deg_log)
 
-    # -- the generic and the host route --------------------------------------------------------------
+    # -- the generic route -------------------------------------------------------------------------
     def _materialised(self, x: Tensor, edge_index, edge_attr: Optional[Tensor]) -> Tensor:
-        """``[N, T, S * A * F_in]`` from per-edge messages: ``propagate`` on the device, plain
-        torch on the host"""
+        """``[N, T, S * A * F_in]`` from per-edge messages through ``propagate``"""
         T, Fi = self.towers, self.F_in
         xt = x.view(-1, T, Fi) if self.divide_input else x.view(-1, 1, Fi).repeat(1, T, 1)
-        if x.is_cuda:
-            keep, self.fuse = self.fuse, False
-            try:
-                out = self.propagate(edge_index, x=xt, edge_attr=edge_attr)
-            finally:
-                self.fuse = keep
-        else:
-            ei = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
-            i, j = self._ij()
-            index = ei[i].long()
-            n = (edge_index.num_dst_nodes if isinstance(edge_index, EdgeIndex) and i == 1
-                 else x.size(0))
-            msg = self.message(xt[index], xt[ei[j].long()], edge_attr)
-            out = _host_aggregate(self, msg, index, n)
+        out = self.propagate(edge_index, x=xt, edge_attr=edge_attr)
         # [N, S * A * W] with the towers inside every block -> towers outermost
         blocks = out.size(1) // (T * Fi)
         return out.view(-1, blocks, T, Fi).transpose(1, 2).reshape(-1, T, blocks * Fi)
@@ -220,34 +202,3 @@ class PNAConv(MessagePassing):
                 hist += count
         return hist
 
-
-def _host_aggregate(layer: PNAConv, msg: Tensor, index: Tensor, n: int) -> Tensor:
-    """the aggregators and scalers of ``layer`` over per-edge rows ``msg [E, W]`` in plain torch"""
-    mod = layer.aggr_module
-    W = msg.size(1)
-    expand = index.view(-1, 1).expand(-1, W)
-    deg = torch.bincount(index, minlength=n)
-    cnt = deg.clamp(min=1).to(msg.dtype).view(-1, 1)
-
-    def reduce(src, how):
-        return msg.new_zeros(n, W).scatter_reduce(0, expand, src, how, include_self=False)
-
-    outs = []
-    for a in layer.aggregators:
-        if a in ('sum', 'add'):
-            outs.append(reduce(msg, 'sum'))
-        elif a == 'mean':
-            outs.append(reduce(msg, 'sum') / cnt)
-        elif a in ('min', 'max'):
-            outs.append(reduce(msg, 'a' + a))
-        elif a in ('var', 'std'):
-            mean = reduce(msg, 'sum') / cnt
-            var = reduce(msg * msg, 'sum') / cnt - mean * mean
-            if a == 'std':
-                std = var.clamp(min=1e-5).sqrt()
-                var = std.masked_fill(std <= 1e-5 ** 0.5, 0.0)
-            outs.append(var)
-        else:
-            raise ValueError(f"the host route has no aggregator '{a}'")
-    out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=-1)
-    return mod.scale(out, deg)

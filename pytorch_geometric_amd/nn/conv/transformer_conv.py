@@ -11,7 +11,7 @@ from ..._functions import (SegmentFunction, SpmmFunction, TransformerAttendFunct
                            TransformerEdgeAttendFunction, TransformerEdgeScoreFunction,
                            TransformerScoreFunction, linear)
 from ...edge_index import EdgeIndex, as_edge_index
-from ...utils import softmax
+from .._host import softmax
 from ..dense.linear import Linear
 from .message_passing import MessagePassing
 
@@ -56,8 +56,7 @@ class TransformerConv(MessagePassing):
       the segment sum over the destination rows);
     * generic gather -> ``message`` -> scatter for ``edge_dim`` layers with ``fuse_edge = False``,
       ``fuse = False``, ``target_to_source`` and layouts the kernels do not serve (``H * C >
-      512``, ``H > 64``, ``edge_dim`` beyond the edge registers); host tensors compute in plain
-      torch.
+      512``, ``H > 64``, ``edge_dim`` beyond the edge registers) and for host tensors.
 
     ``fuse_edge`` is a per-layer attribute initialised from the environment switch
     ``PYGAMD_FUSE_EDGE``, which is read at import and defaults to ``0``: with default settings
@@ -98,6 +97,7 @@ class TransformerConv(MessagePassing):
             self.lin_beta = Linear(3 * out_width, 1, bias=False)
         else:
             self.lin_beta = self.register_parameter('lin_beta', None)
+        self.fuse = True
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -179,16 +179,9 @@ class TransformerConv(MessagePassing):
             query = self.lin_query(x_dst).view(-1, H, C)
             key = self.lin_key(x_src).view(-1, H, C)
             value = self.lin_value(x_src).view(-1, H, C)
-            if not query.is_cuda:
-                out, alpha = self._attend_host(query, key, value, edge_index, edge_attr)
-            else:
-                keep, self.fuse = self.fuse, False
-                try:
-                    out = self.propagate(edge_index, query=query, key=key, value=value,
-                                         edge_attr=edge_attr)
-                finally:
-                    self.fuse = keep
-                alpha, self._alpha = self._alpha, None
+            out = self.propagate(edge_index, query=query, key=key, value=value,
+                                 edge_attr=edge_attr)
+            alpha, self._alpha = self._alpha, None
 
         out = out.reshape(-1, W) if self.concat else out.mean(dim=1)
         if low is not None:
@@ -248,32 +241,6 @@ class TransformerConv(MessagePassing):
             bias = torch.cat([self.lin_key.bias, self.lin_value.bias], dim=0)
         return linear(x_src, weight, bias)
 
-    def _attend_host(self, query: Tensor, key: Tensor, value: Tensor, edge_index,
-                     edge_attr: Optional[Tensor]):
-        """Host tensors: ``message`` + the sum aggregation written out in plain torch, with the
-        reference's softmax (maximum subtracted, ``1e-16`` on the denominator,
-        utils/_softmax.py).  The layer computes where its tensors live; nothing on the device
-        path comes here."""
-        ei = edge_index.edge_index if isinstance(edge_index, EdgeIndex) else edge_index
-        i, j = self._ij()
-        index, source = ei[i].long(), ei[j].long()
-        n = query.size(0)
-        key_j, out_j = key.index_select(0, source), value.index_select(0, source)
-        if self.lin_edge is not None:
-            assert edge_attr is not None
-            e = self.lin_edge(edge_attr).view(-1, self.heads, self.out_channels)
-            key_j, out_j = key_j + e, out_j + e
-        score = (query.index_select(0, index) * key_j).sum(dim=-1) / math.sqrt(self.out_channels)
-        where = index.view(-1, 1).expand_as(score)
-        top = score.new_full((n, self.heads), float('-inf')).scatter_reduce(
-            0, where, score.detach(), 'amax', include_self=True)
-        num = (score - top.index_select(0, index)).exp()
-        den = score.new_zeros(n, self.heads).index_add_(0, index, num) + 1e-16
-        alpha = num / den.index_select(0, index)
-        msg = out_j * F.dropout(alpha, p=self.dropout, training=self.training).unsqueeze(-1)
-        out = msg.new_zeros(n, self.heads, self.out_channels).index_add_(0, index, msg)
-        return out, alpha
-
     def message(self, query_i: Tensor, key_j: Tensor, value_j: Tensor,
                 edge_attr: Optional[Tensor], index: Tensor, ptr: Optional[Tensor],
                 size_i: Optional[int]) -> Tensor:
@@ -290,9 +257,6 @@ class TransformerConv(MessagePassing):
         if edge_attr is not None:
             out = out + edge_attr
         return out * alpha.view(-1, self.heads, 1)
-
-    def message_and_aggregate(self, graph: EdgeIndex, query, key, value, edge_attr) -> Tensor:
-        raise NotImplementedError  # fusion is driven from forward() (needs slot-ordered alpha)
 
     def __repr__(self) -> str:
         return (f'{type(self).__name__}({self.in_channels}, {self.out_channels}, '
