@@ -146,9 +146,10 @@ PYGAMD_API int pygamd_hub_plan(const void* rowptr, int idx_dtype, int64_t n_rows
                                size_t workspace_bytes, void* stream);
 
 /* A CSR handle with its hub plan: what the one-pass kernels (pygamd_gatv2_*, pygamd_transformer_*,
- * pygamd_gine_*) walk, one wave per row.  Row r owns the slots [rowptr[r], rowptr[r + 1]) and
- * col[k] is the row of the OTHER side that slot k reads; a by-destination handle has the
- * destinations as rows, a by-source handle (the `_src` / GINE backward passes) the sources.
+ * pygamd_gine_*, pygamd_pna_*, pygamd_gen_*, pygamd_resgated_*) walk, one wave per row.  Row r
+ * owns the slots [rowptr[r], rowptr[r + 1]) and col[k] is the row of the OTHER side that slot k
+ * reads; a by-destination handle has the destinations as rows, a by-source handle (the `_src` /
+ * GINE, PNA, GEN backward passes) the sources.
  * Rows of more than hub_threshold slots are walked as the plan's chunks of hub_chunk slots and
  * their partial results merged in chunk order; n_hub == 0 means that no row is split (the hub
  * pointers are then ignored and n_chunks must be 0).  The plan must come from pygamd_hub_plan on
@@ -861,6 +862,70 @@ PYGAMD_API int pygamd_gen_backward(const pygamd_csr* g, const void* edge_id_t, c
                                    float* grad_x_src, float* grad_edge_attr, float* grad_weight,
                                    float* grad_bias, void* workspace, size_t workspace_bytes,
                                    void* stream);
+
+/* ---- ResGatedGraphConv's gated sum (res_gated_graph_conv.py:107-148) ----------------------------
+ * out_i = sum_{j->i} sigmoid(k_i + q_j) * v_j, F = out_channels.  The algebra the kernels rest on:
+ *
+ * Without edge_dim (res_gated_graph_conv.py:119-122, 148) key, query and value are node-level:
+ *   K = lin_key(x_dst) [N_dst, F];  QV = [lin_query(x_src) | lin_value(x_src)] [N_src, 2F], ONE
+ *   dense transform with stacked weights.
+ * With edge_dim = De the reference runs three Linear(F_in + De, F) on cat([x, edge_attr]) PER EDGE
+ * (res_gated_graph_conv.py:143-146).  Each splits into its node and its edge columns,
+ *   lin_key(cat[x_i, a]) = Wk_x x_i + bk + Wk_e a       (query, value alike),
+ * so for slot k of destination i with source j = col[k], raw features a_k = edge_attr[edge_id[k]]
+ *   z_k = K_i + Q_j + Wg a_k,  Wg = Wk_e + Wq_e  [F, De]     (formed by the caller, differentiable)
+ *   u_k = V_j + Wv a_k,        Wv = Wv_e         [F, De]
+ *   out_i = sum_k sigmoid(z_k) * u_k                          (replaces :128, propagate, and :148)
+ * with all three biases folded into K, Q, V.  `weight` is the two bias-free matrices stacked,
+ * [2, F, De]: Wg, then Wv (torch.nn.Linear's layout each); NULL with edge_attr NULL and De = 0.
+ *
+ * forward: ONE launch over the by-destination handle g, one 64-lane wave per row, lanes over the F
+ * columns, K_i in registers, per slot ONE gathered 2F row of QV read in place at ld_qv; the edge
+ * terms are rebuilt per slot from the raw features with the lane's rows of Wg and Wv in registers.
+ * sigmoid is 1 / (1 + expf(-z)): exactly 0.5 at 0, exactly 0 or 1 beyond expf's range.  A split
+ * row's chunk partials are summed in chunk order.  out is exactly 0 for a row without slots.
+ * Nothing is saved: the backward recomputes the sigmoid from the inputs.
+ *
+ * backward, with s = sigmoid(z_k), gz = g_i u_k s (1 - s), gu = g_i s, g = grad_out:
+ *   pygamd_resgated_backward_dst (the forward's handle): grad_k[i,:] = sum_k gz; with De > 0 also
+ *     grad_edge_attr[edge_id[k],:] = Wg^T gz + Wv^T gu (NULL: not wanted), grad_weight [2, F, De]
+ *     = (sum gz a_k^T, sum gu a_k^T) from per-workgroup partials reduced in workgroup order; the
+ *     grid is a function of (n_rows, n_chunks) only.
+ *   pygamd_resgated_backward_src (the transposed handle: col = the destination of every out-slot,
+ *     edge_id_t = that form's slot -> original edge map): Q_j, V_j in registers, K_i and g_i
+ *     gathered per slot at ld_k and ld_g (two tensors in place, or the halves of one packed
+ *     [N_dst, 2F] plane), grad_qv [N_src, 2F] = [sum gz | sum gu], zeros for rows without slots.
+ *
+ * pygamd_resgated_supported(F, De): F <= 512 and, with De > 0, De <= 32 and F * De <= 2048 (two
+ * matrices share the registers gine.hip gives one; no instantiation uses scratch,
+ * profiles/resgated_conv.md); otherwise status 2.  k, qv and grad_out have row strides (floats),
+ * everything else is contiguous; fp32 data, int32 / int64 indices.  The workspace
+ * (pygamd_resgated_workspace_bytes) holds the chunks' partial rows and, with De > 0, the
+ * by-destination backward's per-workgroup partials.  No float atomics: bitwise reproducible.
+ * Status 1 / 2 / 3 before any device work; n_rows == 0 returns 0.                                */
+PYGAMD_API int pygamd_resgated_supported(int64_t F, int64_t De);
+PYGAMD_API int pygamd_resgated_workspace_bytes(int64_t n_chunks, int64_t F, int64_t De,
+                                               size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_resgated_forward(const pygamd_csr* g, const void* edge_id, const float* k,
+                                       int64_t ld_k, const float* qv, int64_t ld_qv,
+                                       const float* edge_attr, const float* weight, int64_t n_src,
+                                       int64_t F, int64_t De, float* out, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_resgated_backward_dst(const pygamd_csr* g, const void* edge_id,
+                                            const float* k, int64_t ld_k, const float* qv,
+                                            int64_t ld_qv, const float* edge_attr,
+                                            const float* weight, const float* grad_out,
+                                            int64_t ld_g, int64_t n_src, int64_t F, int64_t De,
+                                            float* grad_k, float* grad_edge_attr,
+                                            float* grad_weight, void* workspace,
+                                            size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_resgated_backward_src(const pygamd_csr* g, const void* edge_id_t,
+                                            const float* k, int64_t ld_k, const float* qv,
+                                            int64_t ld_qv, const float* edge_attr,
+                                            const float* weight, const float* grad_out,
+                                            int64_t ld_g, int64_t n_dst, int64_t F, int64_t De,
+                                            float* grad_qv, void* workspace,
+                                            size_t workspace_bytes, void* stream);
 
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)

@@ -882,6 +882,40 @@ class GenAggregateFunction(Function):
             want_t=need[4]) + (None, None, None, None)
 
 
+class ResGatedAggregateFunction(Function):
+    """The propagate step of ResGatedGraphConv (res_gated_graph_conv.py:128, 138-148) in ONE pass
+    over the by-destination slots:
+
+        out[i] = sum_{k of i} sigmoid(k[i] + q[j_k] + Wg a_k) * (v[j_k] + Wv a_k)
+
+    with the packed ``qv [N_src, 2F] = [q | v]`` gathered once per slot and ``a_k = edge_attr[k]``
+    the RAW edge features (``edge_attr``, ``Wg`` and ``Wv [F, De]`` all None: no edge terms),
+    rebuilt per slot in registers (csrc/resgated.hip).  ``k`` holds the destinations in a prefix of
+    its rows; ``k`` and ``qv`` may be column blocks of wider tensors.  ``edge_attr`` stays in the
+    caller's edge order.  Only the inputs are saved, nothing per edge: the backward, one pass by
+    destination and one by source, recomputes the sigmoid."""
+
+    @staticmethod
+    def forward(ctx, k: Tensor, qv: Tensor, edge_attr: Optional[Tensor], Wg: Optional[Tensor],
+                Wv: Optional[Tensor], graph: EdgeIndex, n_dst: int):
+        _check_rows(graph, n_dst, 'qv', qv, 'k', k)
+        fwd = graph.by_dst()
+        out = _native.resgated_forward(fwd.ptr, fwd.idx, fwd.perm, k, qv, edge_attr,
+                                       _onepass.resgated_weight(Wg, Wv), hub=fwd.hub)
+        ctx.save_for_backward(k, qv, edge_attr, Wg, Wv)
+        ctx.graph = graph
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        need = ctx.needs_input_grad
+        return _onepass.resgated_backward(
+            Slots.of_graph(ctx.graph), *ctx.saved_tensors, grad_out.contiguous(), want_k=need[0],
+            want_qv=need[1], want_edge_attr=need[2],
+            want_weights=need[3] or need[4]) + (None, None)
+
+
 class PnaAggregateFunction(Function):
     """The aggregation of PNAConv with a linear message (pna_conv.py:175-188 under
     aggr/scaler.py:82) in ONE pass over the by-destination slots.  The message of slot ``k`` of

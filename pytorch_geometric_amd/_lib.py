@@ -279,6 +279,15 @@ SIGNATURES = {
     'pygamd_gen_backward': (c_int, [_G, _P, _P, c_int64, c_int, _P, _P, _P, _P, c_int64, c_float,
                                     c_int, _P, c_int64, c_int64, c_int64, c_int, _P, _P, _P, _P,
                                     _P, c_size_t, _P]),
+    'pygamd_resgated_supported': (c_int, [c_int64, c_int64]),
+    'pygamd_resgated_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    'pygamd_resgated_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, c_int64,
+                                        c_int64, _P, _P, c_size_t, _P]),
+    'pygamd_resgated_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64,
+                                             c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t,
+                                             _P]),
+    'pygamd_resgated_backward_src': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64,
+                                             c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
 }
 
 # include/pyg_amd_lab.h: schedules measured and not adopted + timing probes (NOT the boundary;

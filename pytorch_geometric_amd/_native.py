@@ -1832,6 +1832,141 @@ def gen_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], x
     return grad_x, grad_edge, grad_w, grad_b
 
 
+# ---- ResGatedGraphConv's gated sum (csrc/resgated.hip) ----------------------------------------------
+def resgated_supported(F: int, De: int = 0) -> bool:
+    """The kernels serve ``F <= 512`` and, with ``edge_dim`` (``De >= 1``), ``De <= 32`` and
+    ``F * De <= 2048`` (two edge matrices share the registers gine.hip gives one)."""
+    return bool(_lib.load().pygamd_resgated_supported(int(F), int(De)))
+
+
+def _resgated_args(k: Tensor, qv: Tensor, edge_attr: Optional[Tensor], weight: Optional[Tensor],
+                   n_dst: int, E: int):
+    """(k, qv, edge_attr, weight, F, De) checked: ``k [>= n_dst, F]`` and the packed ``qv [n_src,
+    2F]`` with their row strides, ``weight [2, F, De]`` = ``Wg``, then ``Wv``; both edge arguments
+    None without an edge term (``De = 0``)."""
+    if k.dim() != 2:
+        raise ValueError("'k' must be two-dimensional")
+    F = k.size(1)
+    k, qv = _strided_rows(k, 'k', F), _strided_rows(qv, 'qv', 2 * F)
+    if k.size(0) < n_dst:
+        raise ValueError(f"'k' needs at least {n_dst} rows")
+    if (edge_attr is None) != (weight is None):
+        raise ValueError("'edge_attr' and 'weight' come together")
+    if weight is None:
+        return k, qv, None, None, F, 0
+    edge_attr = _edge_rows(edge_attr, E)
+    De = edge_attr.size(1)
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (2, F, De) or De < 1:
+        raise ValueError(f"'weight' must be float32 [2, {F}, {De}] (got {weight.dtype} "
+                         f"{tuple(weight.shape)})")
+    return k, qv, edge_attr, weight.contiguous(), F, De
+
+
+def resgated_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], k: Tensor,
+                     qv: Tensor, edge_attr: Optional[Tensor] = None,
+                     weight: Optional[Tensor] = None, *, hub=None) -> Tensor:
+    """``out [n_rows, F] = sum_k sigmoid(z_k) * u_k`` on a by-destination handle with ``z_k =
+    k[i] + qv[col[k], :F] + weight[0] @ a_k`` and ``u_k = qv[col[k], F:] + weight[1] @ a_k``, ``a_k =
+    edge_attr[edge_id[k]]`` (``edge_attr=None``: no edge terms).  Rows without slots are exactly
+    0.  ``k`` and ``qv`` may be column blocks of wider tensors (their row strides are passed);
+    ``edge_attr`` stays in the caller's edge order."""
+    _require_device(rowptr, col, edge_id, k, qv, edge_attr, weight)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    k, qv, edge_attr, weight, F, De = _resgated_args(k, qv, edge_attr, weight, n_rows,
+                                                     col.numel())
+    edge_id = _edge_id(edge_id, rowptr, col)
+    dev = k.device
+    if n_rows == 0 or col.numel() == 0:  # no slot anywhere: zeros, nothing to launch
+        return torch.zeros(n_rows, F, dtype=torch.float32, device=dev)
+    out = torch.empty(n_rows, F, dtype=torch.float32, device=dev)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_resgated_workspace_bytes, (g.n_chunks, F, 0), dev,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'resgated', 'op': 'forward', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'De': De, 'ld': _ld(qv), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': False}, k):
+        check(lib.pygamd_resgated_forward(
+            ctypes.byref(g), _p(edge_id), _p(k), _ld(k), _p(qv), _ld(qv), _p(edge_attr),
+            _p(weight), qv.size(0), F, De, _p(out), _p(ws), ws_bytes, _stream(k)),
+            'resgated_forward')
+    return out
+
+
+def resgated_backward_dst(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], k: Tensor,
+                          qv: Tensor, edge_attr: Optional[Tensor], weight: Optional[Tensor],
+                          grad_out: Tensor, *, want_grad_edge_attr: bool = True, hub=None):
+    """``(grad_k [rows of k, F], grad_edge_attr | None, grad_weight [2, F, De] | None)`` on the
+    forward's by-destination handle: ``grad_k[i] = sum_k g u s (1 - s)`` with ``s = sigmoid(z)``
+    recomputed, and with an edge term ``grad_edge_attr[k] = weight[0]^T (g u s (1 - s)) +
+    weight[1]^T (g s)`` in the caller's edge order and the gradients of both matrices from
+    per-workgroup partials reduced in workgroup order."""
+    _require_device(rowptr, col, edge_id, k, qv, edge_attr, weight, grad_out)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    k, qv, edge_attr, weight, F, De = _resgated_args(k, qv, edge_attr, weight, n_rows,
+                                                     col.numel())
+    grad_out = _strided_rows(grad_out, 'grad_out', F)
+    if grad_out.size(0) != n_rows:
+        raise ValueError(f"'grad_out' needs {n_rows} rows")
+    edge_id = _edge_id(edge_id, rowptr, col)
+    want_grad_edge_attr = bool(want_grad_edge_attr) and De > 0
+    dev = k.device
+    if n_rows == 0 or col.numel() == 0:
+        return (torch.zeros(k.size(0), F, dtype=torch.float32, device=dev),
+                torch.zeros_like(edge_attr) if want_grad_edge_attr else None,
+                None if weight is None else torch.zeros_like(weight))
+    grad_k = _grad_rows(k.size(0), n_rows, F, dev)
+    grad_edge = torch.empty_like(edge_attr) if want_grad_edge_attr else None
+    grad_w = torch.empty_like(weight) if weight is not None else None
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_resgated_workspace_bytes, (g.n_chunks, F, De), dev,
+                              g.n_chunks > 0 or De > 0)
+    with _timed({'kind': 'resgated', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(),
+                 'F': F, 'De': De, 'ld': _ld(qv), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': want_grad_edge_attr}, k):
+        check(lib.pygamd_resgated_backward_dst(
+            ctypes.byref(g), _p(edge_id), _p(k), _ld(k), _p(qv), _ld(qv), _p(edge_attr),
+            _p(weight), _p(grad_out), _ld(grad_out), qv.size(0), F, De, _p(grad_k),
+            _p(grad_edge), _p(grad_w), _p(ws), ws_bytes, _stream(k)), 'resgated_backward_dst')
+    return grad_k, grad_edge, grad_w
+
+
+def resgated_backward_src(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], k: Tensor,
+                          qv: Tensor, edge_attr: Optional[Tensor], weight: Optional[Tensor],
+                          grad_out: Tensor, *, hub=None) -> Tensor:
+    """The packed ``grad_qv [n_src, 2F] = [sum g u s (1 - s) | sum g s]`` on the by-SOURCE handle
+    (``col_t`` = the destination of every out-slot, ``edge_id_t`` = that form's slot -> edge
+    map).  ``k`` and ``grad_out`` are gathered per slot, each at its own row stride: two tensors
+    in place, or the two halves of one packed ``[n_dst, 2F]`` plane."""
+    _require_device(rowptr_t, col_t, edge_id_t, k, qv, edge_attr, weight, grad_out)
+    lib = _lib.load()
+    n_src = rowptr_t.numel() - 1
+    k, qv, edge_attr, weight, F, De = _resgated_args(k, qv, edge_attr, weight, 0, col_t.numel())
+    if qv.size(0) != n_src:
+        raise ValueError(f"'qv' needs {n_src} rows")
+    grad_out = _strided_rows(grad_out, 'grad_out', F)
+    n_dst = grad_out.size(0)
+    if k.size(0) < n_dst:
+        raise ValueError(f"'k' needs at least {n_dst} rows")
+    edge_id_t = _edge_id(edge_id_t, rowptr_t, col_t, 'edge_id_t')
+    dev = k.device
+    if n_src == 0 or col_t.numel() == 0:
+        return torch.zeros(n_src, 2 * F, dtype=torch.float32, device=dev)
+    grad_qv = torch.empty(n_src, 2 * F, dtype=torch.float32, device=dev)
+    g = _csr(rowptr_t, col_t, n_src, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_resgated_workspace_bytes, (g.n_chunks, F, 0), dev,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'resgated', 'op': 'backward_src', 'n_rows': n_src, 'E': col_t.numel(),
+                 'F': F, 'De': De, 'ld': _ld(k), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': False}, k):
+        check(lib.pygamd_resgated_backward_src(
+            ctypes.byref(g), _p(edge_id_t), _p(k), _ld(k), _p(qv), _ld(qv), _p(edge_attr),
+            _p(weight), _p(grad_out), _ld(grad_out), n_dst, F, De, _p(grad_qv), _p(ws), ws_bytes,
+            _stream(k)), 'resgated_backward_src')
+    return grad_qv
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

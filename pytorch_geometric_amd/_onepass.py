@@ -62,6 +62,10 @@ class Slots:
             return self._graph.src_slot_to_dst_slot()
         return _native.cast_index(self._sorted.perm, self.fwd.idx.dtype)
 
+    def edge_id(self):
+        """by-destination slot -> the caller's edge (None: the slots are the edges)"""
+        return self.fwd.perm if self._graph is not None else self._edge_id
+
     def edge_id_t(self):
         """by-source slot -> the caller's edge"""
         if self._graph is not None:
@@ -216,6 +220,33 @@ def gen_backward(slots, x_src, edge_attr, weight, bias, t, out, saved, grad_out,
         g_t = (cols.sum() if t.numel() == 1 else cols).to(t.dtype).reshape(t.shape)
     return (g_x if want_x_src else None, g_a if want_edge_attr else None,
             g_w if want_weight else None, g_b if want_bias else None, g_t)
+
+
+def resgated_weight(w_gate, w_value):
+    """the kernels' stacked ``[2, F, De]`` edge matrices (None without an edge term)"""
+    return None if w_gate is None else torch.stack([w_gate, w_value])
+
+
+def resgated_backward(slots, k, qv, edge_attr, w_gate, w_value, grad_out, *, want_k=True,
+                      want_qv=True, want_edge_attr=True, want_weights=True):
+    """``(grad_k, grad_qv, grad_edge_attr, grad_w_gate, grad_w_value)``, None where not wanted or
+    not given: one launch by destination (``grad_k`` and everything of the edge term), then one by
+    source (the packed ``grad_qv``).  Both recompute the sigmoid from the inputs."""
+    fwd = slots.fwd
+    weight = resgated_weight(w_gate, w_value)
+    g_k = g_qv = g_a = g_w = None
+    if want_k or (weight is not None and (want_edge_attr or want_weights)):
+        g_k, g_a, g_w = _native.resgated_backward_dst(
+            fwd.ptr, fwd.idx, slots.edge_id(), k, qv, edge_attr, weight, grad_out,
+            want_grad_edge_attr=want_edge_attr and edge_attr is not None, hub=fwd.hub)
+    if want_qv:
+        bwd = slots.by_src()
+        g_qv = _native.resgated_backward_src(
+            bwd.ptr, bwd.idx, None if edge_attr is None else slots.edge_id_t(), k, qv, edge_attr,
+            weight, grad_out, hub=bwd.hub)
+    give_w = want_weights and g_w is not None
+    return (g_k if want_k else None, g_qv, g_a if want_edge_attr else None,
+            g_w[0] if give_w else None, g_w[1] if give_w else None)
 
 
 def hgt_blocks(kqvs, src_pos, F):

@@ -1,9 +1,10 @@
 // gine_device.h — what the kernels with a per-slot linear edge term W a_k (+ b) share (gine.hip,
-// pna.hip, gen.hip).  Forward side: the envelope, the edge arguments, a slot's edge id and raw
-// features, a lane's rows of the edge weight in registers, the edge term, the lane shape with its
-// register capacity for De, the walk over the items, the capped grid and the dispatch over the
-// instantiations.  Backward side: the update of the parameter gradients in registers by a slot
-// (gine.hip and pna.hip; gen.hip keeps it written out, the call cost its backward 1 %), the
+// pna.hip, gen.hip, resgated.hip).  Forward side: the envelope, the edge arguments, a slot's edge
+// id and raw features, a lane's rows of the edge weight in registers, the edge term, the lane
+// shape with its register capacity for De, the walk over the items, the capped grid and the
+// dispatch over the instantiations.  Backward side: the update of the parameter gradients in
+// registers by a slot (gine.hip, pna.hip, resgated.hip; gen.hip keeps it written out, the call
+// cost its backward 1 %), the
 // reduce of the workgroups' partials in workgroup order, the sum merge of a hub row's chunks
 // and the launch of those two.  Each kernel keeps its own loop, loads and arithmetic in its own
 // file — and the fold of a workgroup's waves into its partial through LDS, which as a function
@@ -262,11 +263,13 @@ inline int launch_backward_tail(const Items<IdxT>& it, int64_t F, int64_t De, bo
   return PYGAMD_OK;
 }
 
-inline int gine_check(const pygamd_csr* g, int64_t n_other, int64_t F, int64_t De) {
+// (`envelope`: a kernel file with a narrower one than gine_envelope passes its own)
+inline int gine_check(const pygamd_csr* g, int64_t n_other, int64_t F, int64_t De,
+                      bool (*envelope)(int64_t, int64_t) = gine_envelope) {
   if (De < 0) return PYGAMD_ERR_INVALID_ARG;
   const int rc = check_args(g, n_other, 1, F < 1 ? F : 1);
   if (rc != PYGAMD_OK) return rc;
-  return gine_envelope(F, De) ? PYGAMD_OK : PYGAMD_ERR_UNSUPPORTED;
+  return envelope(F, De) ? PYGAMD_OK : PYGAMD_ERR_UNSUPPORTED;
 }
 
 }  // namespace gine

@@ -2,7 +2,8 @@ from .aggr import (Aggregation, DegreeScalerAggregation, FusedAggregation, MaxAg
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
 from .conv import (FastRGCNConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HeteroConv, HGTConv,
-                   GENConv, MessagePassing, PNAConv, RGCNConv, SAGEConv, TransformerConv, gcn_norm, group)
+                   GENConv, MessagePassing, PNAConv, ResGatedGraphConv, RGCNConv, SAGEConv, TransformerConv,
+                   gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
 from .norm import MessageNorm
@@ -14,5 +15,6 @@ __all__ = [
     'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
     'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
     'PNAConv', 'DegreeScalerAggregation', 'GENConv', 'MessageNorm', 'DeepGCNLayer',
+    'ResGatedGraphConv',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

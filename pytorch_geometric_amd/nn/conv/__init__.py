@@ -11,7 +11,8 @@ from .hgt_conv import HGTConv
 from .gin_conv import GINConv, GINEConv
 from .pna_conv import PNAConv
 from .gen_conv import GENConv
+from .res_gated_graph_conv import ResGatedGraphConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
-           'PNAConv', 'GENConv']
+           'PNAConv', 'GENConv', 'ResGatedGraphConv']

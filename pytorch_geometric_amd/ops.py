@@ -45,6 +45,9 @@ Operators (all index tensors int32 / int64, features float32):
 ``gen_aggregate``           ``(Tensor x_src, Tensor? edge_attr, Tensor? weight, Tensor? bias,
                             Tensor t, Tensor rowptr, Tensor col, Tensor? edge_id, float eps_msg,
                             bool semi_grad, bool grad_t) -> (Tensor out, Tensor saved)``
+``resgated_aggregate``      ``(Tensor k, Tensor qv, Tensor? edge_attr, Tensor? w_gate,
+                            Tensor? w_value, Tensor rowptr, Tensor col, Tensor? edge_id)
+                            -> Tensor``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -779,6 +782,74 @@ def _gen_bwd(ctx, grad, _grad_saved):
 register_autograd('pyg_amd::gen_aggregate', _gen_bwd, setup_context=_gen_setup)
 
 
+# ---- ResGatedGraphConv's gated sum on a CSR pair (rows = destinations) --------------------------------
+@custom_op('pyg_amd::resgated_aggregate', mutates_args=(), device_types=_DEV)
+def resgated_aggregate(k: Tensor, qv: Tensor, edge_attr: Optional[Tensor],
+                       w_gate: Optional[Tensor], w_value: Optional[Tensor], rowptr: Tensor,
+                       col: Tensor, edge_id: Optional[Tensor]) -> Tensor:
+    """ResGatedGraphConv's propagate (res_gated_graph_conv.py:128, 138-148): ``out [n_dst, F] =
+    sum_k sigmoid(k[i] + q[col[k]] + w_gate @ a_k) * (v[col[k]] + w_value @ a_k)`` with the packed
+    ``qv [n_src, 2F] = [q | v]`` and ``a_k = edge_attr[edge_id[k]]`` (``edge_attr [E, De]`` with
+    ``w_gate``, ``w_value [F, De]``, or all three None).  ``edge_id=None``: ``edge_attr`` follows the
+    slots of ``col``."""
+    F = k.size(1)
+    De = 0 if edge_attr is None else edge_attr.size(1)
+    if not _native.resgated_supported(F, De):
+        raise NotImplementedError(
+            f'resgated_aggregate serves F <= 512 and, with edge features, De <= 32 and F * De <= '
+            f'2048 (got F = {F}, De = {De})')
+    return _native.resgated_forward(rowptr, col, edge_id, k, qv, edge_attr,
+                                    _onepass.resgated_weight(w_gate, w_value),
+                                    hub=_native.hub_plan(rowptr))
+
+
+@resgated_aggregate.register_fake
+def _(k, qv, edge_attr, w_gate, w_value, rowptr, col, edge_id):
+    return k.new_empty(rowptr.numel() - 1, k.shape[1])
+
+
+@custom_op('pyg_amd::resgated_aggregate_backward', mutates_args=(), device_types=_DEV)
+def resgated_aggregate_backward(grad: Tensor, k: Tensor, qv: Tensor, edge_attr: Optional[Tensor],
+                                w_gate: Optional[Tensor], w_value: Optional[Tensor],
+                                rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor]
+                                ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The gradients of ``(k, qv, edge_attr, w_gate, w_value)``; an input that was not given gets
+    an empty tensor."""
+    grads = _onepass.resgated_backward(Slots.of_csr(rowptr, col, qv.size(0), edge_id), k, qv,
+                                       edge_attr, w_gate, w_value, grad)
+    # (one tensor EACH, none a view of another: an operator's outputs must not alias)
+    return tuple(grad.new_empty(0) if g is None else (g.clone() if g._base is not None else g)
+                 for g in grads)
+
+
+@resgated_aggregate_backward.register_fake
+def _(grad, k, qv, edge_attr, w_gate, w_value, rowptr, col, edge_id):
+    none = grad.new_empty(0)
+    return (torch.empty_like(k, memory_format=torch.contiguous_format),
+            torch.empty_like(qv, memory_format=torch.contiguous_format),
+            none if edge_attr is None else torch.empty_like(edge_attr),
+            none if w_gate is None else torch.empty_like(w_gate),
+            grad.new_empty(0) if w_value is None else torch.empty_like(w_value))
+
+
+def _resgated_setup(ctx, inputs, output):
+    k, qv, edge_attr, w_gate, w_value, rowptr, col, edge_id = inputs
+    ctx.given = edge_attr is not None
+    ctx.save_for_backward(k, qv, edge_attr, w_gate, w_value, rowptr, col, edge_id)
+
+
+def _resgated_bwd(ctx, grad):
+    k, qv, edge_attr, w_gate, w_value, rowptr, col, edge_id = ctx.saved_tensors
+    g_k, g_qv, g_a, g_wg, g_wv = resgated_aggregate_backward(
+        grad.contiguous(), k, qv, edge_attr, w_gate, w_value, rowptr, col, edge_id)
+    if not ctx.given:
+        g_a = g_wg = g_wv = None
+    return g_k, g_qv, g_a, g_wg, g_wv, None, None, None
+
+
+register_autograd('pyg_amd::resgated_aggregate', _resgated_bwd, setup_context=_resgated_setup)
+
+
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
 @custom_op('pyg_amd::hgt_relation', mutates_args=(), device_types=_DEV)
 def hgt_relation(kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor, src_pos: List[int],
@@ -840,4 +911,5 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'transformer_attend_backward', 'transformer_edge_attend',
        'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward',
        'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward',
-       'gen_aggregate', 'gen_aggregate_backward')
+       'gen_aggregate', 'gen_aggregate_backward', 'resgated_aggregate',
+       'resgated_aggregate_backward')
