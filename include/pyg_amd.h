@@ -622,6 +622,55 @@ PYGAMD_API int pygamd_gatv2_backward_src(const pygamd_csr* g, const void* slot_m
                                          float slope, float* grad_x_l, void* workspace,
                                          size_t workspace_bytes, void* stream);
 
+/* ---- a16h: HAN's typed additive attention, every edge type in one pass ------------------------
+ * nn/conv/han_conv.py:170-179 (message: GAT's additive score, the softmax per destination, the
+ * weighting of x_j) + the 'add' aggregation and the ReLU of han_conv.py:155, for all edge types of
+ * a layer call on ONE stacked dst-sorted handle.  Row r = row_begin[e] + i is destination i of edge
+ * type e (an empty neighbourhood is an empty row), column c is a stacked (edge type, source).
+ * For slot k of row r of edge type e with c = col[k]:
+ *   s[k,h]   = leaky_relu(a_src[c,h] + a_dst[r,h], slope)
+ *   alpha    = softmax over the row (maximum subtracted, 1e-16 on the denominator)
+ *   out[r,h] = sum_k alpha[k,h] * x_all[c + val_shift[e], h, :]        (ReLU on top if relu != 0)
+ * x_all [., H*C] holds every node type's projected rows once; a_src [n_cols, H], a_dst [n_rows, H],
+ * out [n_rows, H*C] and alpha [nnz, H] (SLOT order), all contiguous fp32.  row_begin [n_et + 1] and
+ * val_shift [n_et] are HOST arrays (n_et <= 64, otherwise status 2; row_begin[0] = 0,
+ * row_begin[n_et] = g->n_rows) and travel by value in the kernel arguments.  Every column must read
+ * a row of x_all: the caller checks the ids when it stacks the graph.  A -inf score has weight 0, a
+ * row of -inf scores is NaN, NaN / +inf poison their own (row, head), an empty row is 0, and the
+ * ReLU lets NaN through.  Supported: H*C <= 512 and H <= 64 (pygamd_han_supported), otherwise
+ * status 2.  The workspace (pygamd_han_workspace_bytes of g's n_chunks) holds the chunks' partial
+ * results.  No float atomics: all results are bitwise reproducible.
+ *
+ * backward_dst: with g = grad_out * [out > 0] (relu) or grad_out,
+ *   grad_s[k,h] = alpha * (<g[r,h,:], x[c,h,:]> - <g[r,h,:], out[r,h,:]>) * leaky_relu'(.) (slope
+ *   where the argument is <= 0), in slot order, and grad_a_dst[r] = sum_k grad_s[k].
+ * backward_src: g is the src-sorted handle (rows = the forward's columns; n_dst the row count of
+ *   the by-destination one), slot_map = by-source slot -> by-destination slot:
+ *   grad_a_src[c] = sum grad_s, grad_xv[c] = sum alpha * g[r]  ([n_cols, H*C]: the caller adds the
+ *   blocks of the edge types into the node types' rows).                                        */
+PYGAMD_API int pygamd_han_supported(int64_t H, int64_t C);
+PYGAMD_API int pygamd_han_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C,
+                                          size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_han_forward(const pygamd_csr* g, const int64_t* row_begin /*[host]*/,
+                                  const int64_t* val_shift /*[host]*/, int64_t n_et,
+                                  const float* x_all, const float* a_src, const float* a_dst,
+                                  int64_t n_cols, int64_t H, int64_t C, float slope, int relu,
+                                  float* alpha, float* out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_han_backward_dst(const pygamd_csr* g, const int64_t* row_begin /*[host]*/,
+                                       const int64_t* val_shift /*[host]*/, int64_t n_et,
+                                       const float* x_all, const float* a_src, const float* a_dst,
+                                       const float* alpha, const float* grad_out, const float* out,
+                                       int64_t n_cols, int64_t H, int64_t C, float slope, int relu,
+                                       float* grad_s, float* grad_a_dst, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_han_backward_src(const pygamd_csr* g, const void* slot_map,
+                                       const float* alpha, const float* grad_s,
+                                       const float* grad_out, const float* out, int64_t n_dst,
+                                       int64_t H, int64_t C, int relu, float* grad_a_src,
+                                       float* grad_xv, void* workspace, size_t workspace_bytes,
+                                       void* stream);
+
 /* ---- a16b: TransformerConv's dot-product attention in one pass --------------------------------
  * nn/conv/transformer_conv.py:263-283 (message: the scaled dot product, the softmax and the
  * weighting of value_j) + the 'add' aggregation of propagate (transformer_conv.py:234-235) on a

@@ -632,6 +632,46 @@ class Gatv2ScoreFunction(Function):
         return _gatv2_backward(ctx, xl2, xr2, att, alpha, grad_alpha=grad_alpha.contiguous())
 
 
+class HanAttendFunction(Function):
+    """HAN's node-level attention (han_conv.py:170-179, the 'add' aggregation and, under ``relu``,
+    the ReLU of han_conv.py:155) for every edge type of a layer call in ONE pass over the stacked
+    by-destination handle ``graph`` (``_han.stacked_graph``): ``x_all [S, H, D]`` holds every node
+    type's projected rows once, ``a_src [n_cols, H]`` / ``a_dst [n_rows, H]`` the stacked per-node
+    logits, ``types = (row_begin, src_begin, val_shift)`` the stacking plan.  Returns ``out
+    [n_rows, H * D]``.  The backward is one pass by destination and one by source (csrc/han.hip).
+    Saved: the inputs, ``alpha [E, H]`` and ``out`` — nothing of size ``E x H*D``."""
+
+    @staticmethod
+    def forward(ctx, x_all: Tensor, a_src: Tensor, a_dst: Tensor, graph: EdgeIndex, types,
+                slope: float, relu: bool):
+        _, H, C = x_all.shape
+        types = tuple(tuple(int(v) for v in t) for t in types)
+        _onepass.han_check_types(types, graph.num_dst_nodes, graph.num_src_nodes, x_all.size(0))
+        if a_src.size(0) != graph.num_src_nodes or a_dst.size(0) != graph.num_dst_nodes:
+            raise ValueError(f"'a_src' / 'a_dst' need {graph.num_src_nodes} / "
+                             f"{graph.num_dst_nodes} rows (got {a_src.size(0)} / {a_dst.size(0)})")
+        fwd = graph.by_dst()
+        x2 = x_all.reshape(-1, H * C)
+        alpha, out = _native.han_forward(fwd.ptr, fwd.idx, types[0], types[2], x2, a_src, a_dst,
+                                         H, C, slope, relu, hub=fwd.hub)
+        ctx.save_for_backward(x2, a_src, a_dst, alpha, out)
+        ctx.graph, ctx.types, ctx.slope, ctx.relu, ctx.dims = graph, types, slope, relu, (H, C)
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor, _grad_alpha):
+        x2, a_src, a_dst, alpha, out = ctx.saved_tensors
+        H, C = ctx.dims
+        g_x, g_src, g_dst = _onepass.han_backward(
+            Slots.of_graph(ctx.graph), ctx.types, x2, a_src, a_dst, alpha, out,
+            _rows(grad_out).contiguous(), H, C, ctx.slope, ctx.relu,
+            want_x=ctx.needs_input_grad[0], want_a_src=ctx.needs_input_grad[1])
+        return (None if g_x is None else g_x.view(-1, H, C), g_src, g_dst, None, None, None,
+                None)
+
+
 def _key_value(key: Tensor, value: Optional[Tensor], W: int):
     """``(key, value, packed)`` as ``[N_src, W]`` rows; ``value=None``: the halves of ``key``"""
     if value is None:

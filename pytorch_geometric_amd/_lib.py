@@ -241,6 +241,16 @@ SIGNATURES = {
                                           c_float, _P, _P, _P, _P, c_size_t, _P]),
     'pygamd_gatv2_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
                                           c_float, _P, _P, c_size_t, _P]),
+    'pygamd_han_supported': (c_int, [c_int64, c_int64]),
+    'pygamd_han_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    'pygamd_han_forward': (c_int, [_G, POINTER(c_int64), POINTER(c_int64), c_int64, _P, _P, _P,
+                                   c_int64, c_int64, c_int64, c_float, c_int, _P, _P, _P, c_size_t,
+                                   _P]),
+    'pygamd_han_backward_dst': (c_int, [_G, POINTER(c_int64), POINTER(c_int64), c_int64, _P, _P, _P,
+                                        _P, _P, _P, c_int64, c_int64, c_int64, c_float, c_int, _P,
+                                        _P, _P, c_size_t, _P]),
+    'pygamd_han_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int,
+                                        _P, _P, _P, c_size_t, _P]),
     'pygamd_transformer_supported': (c_int, [c_int64, c_int64]),
     'pygamd_transformer_workspace_bytes': (c_int, [c_int64, c_int64, c_int64,
                                                    POINTER(c_size_t)]),

@@ -1255,6 +1255,117 @@ def gatv2_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, x_l: T
     return grad_x_l
 
 
+# ---- HAN's typed additive attention (csrc/han.hip) -----------------------------------------------
+def han_supported(H: int, C: int) -> bool:
+    """The one-pass kernels serve this head layout (H * C <= 512, H <= 64)."""
+    return bool(_lib.load().pygamd_han_supported(int(H), int(C)))
+
+
+def _han_types(row_begin, val_shift, n_rows: int):
+    """The host arrays of the kernels' by-value type table."""
+    n_et = len(val_shift)
+    if not 1 <= n_et <= MAX_HETERO_TYPES or len(row_begin) != n_et + 1:
+        raise ValueError(f"'row_begin' needs one entry more than 'val_shift', which needs 1 to "
+                         f"{MAX_HETERO_TYPES} (got {len(row_begin)} and {n_et})")
+    if row_begin[0] != 0 or row_begin[-1] != n_rows or list(row_begin) != sorted(row_begin):
+        raise ValueError(f"'row_begin' must rise from 0 to the {n_rows} rows of the handle")
+    return ((ctypes.c_int64 * (n_et + 1))(*[int(v) for v in row_begin]),
+            (ctypes.c_int64 * n_et)(*[int(v) for v in val_shift]), n_et)
+
+
+def han_forward(rowptr: Tensor, col: Tensor, row_begin, val_shift, x_all: Tensor, a_src: Tensor,
+                a_dst: Tensor, H: int, C: int, slope: float, relu: bool, *, hub=None):
+    """``(alpha [nnz, H] in slot order, out [n_rows, H * C])`` of HAN's node-level attention for
+    every edge type of a call on the stacked by-destination handle (``row_begin``, ``val_shift``:
+    sequences of ints, see pygamd_han_forward).  The caller has range-checked the ids: column ``c``
+    of edge type ``e`` reads row ``c + val_shift[e]`` of ``x_all``."""
+    _require_device(rowptr, col, x_all, a_src, a_dst)
+    lib = _lib.load()
+    W = H * C
+    x_all = _dense_rows(x_all, 'x_all', W)
+    a_src, a_dst = _dense_rows(a_src, 'a_src', H), _dense_rows(a_dst, 'a_dst', H)
+    n_rows = rowptr.numel() - 1
+    if a_dst.size(0) != n_rows:
+        raise ValueError(f"'a_dst' needs one row per row of the handle ({n_rows})")
+    alpha = torch.empty(col.numel(), H, dtype=torch.float32, device=x_all.device)
+    out = torch.empty(n_rows, W, dtype=torch.float32, device=x_all.device)
+    if col.numel() == 0:  # no edges: every row is empty
+        return alpha, out.zero_()
+    rb, vs, n_et = _han_types(row_begin, val_shift, n_rows)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_han_workspace_bytes, (g.n_chunks, H, C), x_all.device,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'han', 'op': 'forward', 'n_rows': n_rows, 'E': col.numel(), 'H': H,
+                 'C': C, 'n_et': n_et, 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x_all):
+        check(lib.pygamd_han_forward(ctypes.byref(g), rb, vs, n_et, _p(x_all), _p(a_src),
+                                     _p(a_dst), a_src.size(0), H, C, float(slope), int(relu),
+                                     _p(alpha), _p(out), _p(ws), ws_bytes, _stream(x_all)),
+              'han_forward')
+    return alpha, out
+
+
+def han_backward_dst(rowptr: Tensor, col: Tensor, row_begin, val_shift, x_all: Tensor,
+                     a_src: Tensor, a_dst: Tensor, alpha: Tensor, grad_out: Tensor, out: Tensor,
+                     H: int, C: int, slope: float, relu: bool, *, hub=None):
+    """``(grad_s [nnz, H] in slot order, grad_a_dst [n_rows, H])``"""
+    _require_device(rowptr, col, x_all, a_src, a_dst, alpha, grad_out, out)
+    lib = _lib.load()
+    W = H * C
+    x_all = _dense_rows(x_all, 'x_all', W)
+    a_src, a_dst = _dense_rows(a_src, 'a_src', H), _dense_rows(a_dst, 'a_dst', H)
+    grad_out, out = _dense_rows(grad_out, 'grad_out', W), _dense_rows(out, 'out', W)
+    alpha = alpha.contiguous()
+    n_rows = rowptr.numel() - 1
+    if a_dst.size(0) != n_rows or out.size(0) != n_rows or grad_out.size(0) != n_rows:
+        raise ValueError(f"'a_dst', 'out' and 'grad_out' need one row per row of the handle "
+                         f"({n_rows})")
+    grad_s = torch.empty_like(alpha)
+    grad_a_dst = torch.empty(n_rows, H, dtype=torch.float32, device=x_all.device)
+    if col.numel() == 0:
+        return grad_s, grad_a_dst.zero_()
+    rb, vs, n_et = _han_types(row_begin, val_shift, n_rows)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_han_workspace_bytes, (g.n_chunks, H, C), x_all.device,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'han', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(), 'H': H,
+                 'C': C, 'n_et': n_et, 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x_all):
+        check(lib.pygamd_han_backward_dst(
+            ctypes.byref(g), rb, vs, n_et, _p(x_all), _p(a_src), _p(a_dst), _p(alpha),
+            _p(grad_out), _p(out), a_src.size(0), H, C, float(slope), int(relu), _p(grad_s),
+            _p(grad_a_dst), _p(ws), ws_bytes, _stream(x_all)), 'han_backward_dst')
+    return grad_s, grad_a_dst
+
+
+def han_backward_src(rowptr_t: Tensor, col_t: Tensor, slot_map: Tensor, alpha: Tensor,
+                     grad_s: Tensor, grad_out: Tensor, out: Tensor, H: int, C: int, relu: bool, *,
+                     hub=None):
+    """``(grad_a_src [n_cols, H], grad_xv [n_cols, H * C])`` on the by-source handle, whose rows
+    are the stacked (edge type, source) columns of the forward."""
+    _require_device(rowptr_t, col_t, slot_map, alpha, grad_s, grad_out, out)
+    lib = _lib.load()
+    W = H * C
+    grad_out, out = _dense_rows(grad_out, 'grad_out', W), _dense_rows(out, 'out', W)
+    alpha, grad_s = alpha.contiguous(), grad_s.contiguous()
+    n_cols = rowptr_t.numel() - 1
+    if slot_map.dtype != rowptr_t.dtype or grad_out.size(0) != out.size(0):
+        raise ValueError("'slot_map' must have the index dtype and 'grad_out' the rows of 'out'")
+    slot_map = slot_map.contiguous()
+    grad_a_src = torch.empty(n_cols, H, dtype=torch.float32, device=out.device)
+    grad_xv = torch.empty(n_cols, W, dtype=torch.float32, device=out.device)
+    if col_t.numel() == 0:
+        return grad_a_src.zero_(), grad_xv.zero_()
+    g = _csr(rowptr_t, col_t, n_cols, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_han_workspace_bytes, (g.n_chunks, H, C), out.device,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'han', 'op': 'backward_src', 'n_rows': n_cols, 'E': col_t.numel(),
+                 'H': H, 'C': C, 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, out):
+        check(lib.pygamd_han_backward_src(
+            ctypes.byref(g), _p(slot_map), _p(alpha), _p(grad_s), _p(grad_out), _p(out),
+            out.size(0), H, C, int(relu), _p(grad_a_src), _p(grad_xv), _p(ws), ws_bytes,
+            _stream(out)), 'han_backward_src')
+    return grad_a_src, grad_xv
+
+
 # ---- TransformerConv's dot-product attention (csrc/transformer.hip) ------------------------------
 def transformer_supported(H: int, C: int) -> bool:
     """The one-pass kernels serve this head layout (H * C <= 512, H <= 64)."""

@@ -92,6 +92,47 @@ def gatv2_backward(slots, x_l, x_r, att, alpha, H, C, slope, *, grad_out=None, o
     return g_l, g_r, g_att
 
 
+def han_check_types(types, n_rows, n_cols, n_x):
+    """``types = (row_begin [T + 1], src_begin [T + 1], val_shift [T])`` of a stacked HAN call
+    (sequences of ints): the row blocks tile the handle's rows, the column blocks its columns, and
+    every column block lands inside ``x_all`` — the bounds the kernels rely on."""
+    row_begin, src_begin, val_shift = types
+    T = len(val_shift)
+    ok = (T >= 1 and len(row_begin) == len(src_begin) == T + 1 and row_begin[0] == 0
+          and src_begin[0] == 0 and row_begin[-1] == n_rows and src_begin[-1] == n_cols)
+    for e in range(T if ok else 0):
+        ok = ok and (row_begin[e] <= row_begin[e + 1] and src_begin[e] <= src_begin[e + 1]
+                     and src_begin[e] + val_shift[e] >= 0
+                     and src_begin[e + 1] + val_shift[e] <= n_x)
+    if not ok:
+        raise ValueError("'row_begin' / 'src_begin' / 'val_shift' do not describe the stacked "
+                         f"graph ({n_rows} rows, {n_cols} columns) over {n_x} feature rows")
+
+
+def han_backward(slots, types, x_all, a_src, a_dst, alpha, out, grad_out, H, C, slope, relu, *,
+                 want_x=True, want_a_src=True):
+    """``(grad_x_all | None, grad_a_src | None, grad_a_dst)``, flat: one launch by destination,
+    then one by source whose ``[n_cols, H * C]`` blocks are added into the node types' rows of
+    ``x_all`` in edge-type order."""
+    row_begin, src_begin, val_shift = types
+    fwd = slots.fwd
+    grad_s, g_dst = _native.han_backward_dst(
+        fwd.ptr, fwd.idx, row_begin, val_shift, x_all, a_src, a_dst, alpha, grad_out, out, H, C,
+        slope, relu, hub=fwd.hub)
+    g_x = g_src = None
+    if want_x or want_a_src:
+        bwd = slots.by_src()
+        g_src, g_xv = _native.han_backward_src(bwd.ptr, bwd.idx, slots.slot_map(), alpha, grad_s,
+                                               grad_out, out, H, C, relu, hub=bwd.hub)
+        if want_x:
+            g_x = torch.zeros_like(x_all)
+            for e, shift in enumerate(val_shift):
+                lo, hi = src_begin[e], src_begin[e + 1]
+                if hi > lo:
+                    g_x[lo + shift:hi + shift] += g_xv[lo:hi]
+    return g_x, g_src if want_a_src else None, g_dst
+
+
 def transformer_backward(slots, query, key, value, alpha, H, C, scale, *, grad_out=None, out=None,
                          grad_alpha=None, edge_attr=None, bias=None, grad_z=None, z=None,
                          want_key=True, want_value=True, want_edge_attr=True, packed=False):

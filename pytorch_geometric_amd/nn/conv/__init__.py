@@ -8,6 +8,7 @@ from .rgcn_conv import FastRGCNConv, RGCNConv
 from .graph_conv import GraphConv
 from .hetero_conv import HeteroConv, group
 from .hgt_conv import HGTConv
+from .han_conv import HANConv
 from .gin_conv import GINConv, GINEConv
 from .pna_conv import PNAConv
 from .gen_conv import GENConv
@@ -15,4 +16,4 @@ from .res_gated_graph_conv import ResGatedGraphConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
-           'PNAConv', 'GENConv', 'ResGatedGraphConv']
+           'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv']

@@ -29,6 +29,9 @@ Operators (all index tensors int32 / int64, features float32):
 ``linear``                  ``(Tensor x, Tensor weight, Tensor? bias) -> Tensor``
 ``gatv2_attend``            ``(Tensor x_l, Tensor x_r, Tensor att, Tensor rowptr, Tensor col,
                             float negative_slope) -> (Tensor out, Tensor alpha)``
+``han_attend``              ``(Tensor x_all, Tensor a_src, Tensor a_dst, Tensor rowptr, Tensor col,
+                            int[] row_begin, int[] src_begin, int[] val_shift,
+                            float negative_slope, bool relu) -> (Tensor out, Tensor alpha)``
 ``transformer_attend``      ``(Tensor query, Tensor key, Tensor value, Tensor rowptr, Tensor col,
                             float scale) -> (Tensor out, Tensor alpha)``
 ``transformer_edge_attend`` ``(Tensor query, Tensor key, Tensor value, Tensor edge_attr,
@@ -434,6 +437,67 @@ def _gatv2_bwd(ctx, grad, _grad_alpha):
 
 
 register_autograd('pyg_amd::gatv2_attend', _gatv2_bwd, setup_context=_gatv2_setup)
+
+# ---- HAN's typed additive attention on a stacked CSR pair (rows = (edge type, destination)) -------
+@custom_op('pyg_amd::han_attend', mutates_args=(), device_types=_DEV)
+def han_attend(x_all: Tensor, a_src: Tensor, a_dst: Tensor, rowptr: Tensor, col: Tensor,
+               row_begin: List[int], src_begin: List[int], val_shift: List[int],
+               negative_slope: float, relu: bool) -> Tuple[Tensor, Tensor]:
+    """``(out [n_rows, H * D], alpha [nnz, H])`` of HAN's node-level attention (han_conv.py:170-179)
+    for every edge type of a call: rows ``row_begin[e] + i`` are the destinations of edge type
+    ``e``, columns ``src_begin[e] + j`` its sources, which read row ``col + val_shift[e]`` of
+    ``x_all [S, H, D]``; ``a_src [n_cols, H]`` / ``a_dst [n_rows, H]`` are the stacked logits.
+    ``alpha`` follows the slots of ``col`` and is returned for inspection (gradients flow through
+    ``out``).  ``col`` must hold ids below ``src_begin[-1]``."""
+    _, H, C = x_all.shape
+    if not _native.han_supported(H, C):
+        raise NotImplementedError(f'han_attend serves H * D <= 512 and H <= 64 (got {H} x {C})')
+    n_rows = rowptr.numel() - 1
+    _onepass.han_check_types((row_begin, src_begin, val_shift), n_rows, a_src.size(0),
+                             x_all.size(0))
+    alpha, out = _native.han_forward(rowptr, col, row_begin, val_shift, _rows(x_all), a_src, a_dst,
+                                     H, C, negative_slope, relu, hub=_native.hub_plan(rowptr))
+    return out, alpha
+
+
+@han_attend.register_fake
+def _(x_all, a_src, a_dst, rowptr, col, row_begin, src_begin, val_shift, negative_slope, relu):
+    return (x_all.new_empty(rowptr.numel() - 1, x_all.shape[1] * x_all.shape[2]),
+            x_all.new_empty(col.numel(), x_all.shape[1]))
+
+
+@custom_op('pyg_amd::han_attend_backward', mutates_args=(), device_types=_DEV)
+def han_attend_backward(grad: Tensor, x_all: Tensor, a_src: Tensor, a_dst: Tensor, alpha: Tensor,
+                        out: Tensor, rowptr: Tensor, col: Tensor, row_begin: List[int],
+                        src_begin: List[int], val_shift: List[int], negative_slope: float,
+                        relu: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    _, H, C = x_all.shape
+    g_x, g_src, g_dst = _onepass.han_backward(
+        Slots.of_csr(rowptr, col, a_src.size(0)), (row_begin, src_begin, val_shift), _rows(x_all),
+        a_src, a_dst, alpha, out, grad.contiguous(), H, C, negative_slope, relu)
+    return g_x.reshape(x_all.shape), g_src, g_dst
+
+
+@han_attend_backward.register_fake
+def _(grad, x_all, a_src, a_dst, alpha, out, rowptr, col, row_begin, src_begin, val_shift,
+      negative_slope, relu):
+    return torch.empty_like(x_all), torch.empty_like(a_src), torch.empty_like(a_dst)
+
+
+def _han_setup(ctx, inputs, output):
+    x_all, a_src, a_dst, rowptr, col, row_begin, src_begin, val_shift, slope, relu = inputs
+    ctx.static = (list(row_begin), list(src_begin), list(val_shift), slope, relu)
+    ctx.save_for_backward(x_all, a_src, a_dst, output[1], output[0], rowptr, col)
+
+
+def _han_bwd(ctx, grad, _grad_alpha):
+    x_all, a_src, a_dst, alpha, out, rowptr, col = ctx.saved_tensors
+    g_x, g_src, g_dst = han_attend_backward(grad.contiguous(), x_all, a_src, a_dst, alpha, out,
+                                            rowptr, col, *ctx.static)
+    return g_x, g_src, g_dst, None, None, None, None, None, None, None
+
+
+register_autograd('pyg_amd::han_attend', _han_bwd, setup_context=_han_setup)
 
 # ---- TransformerConv's dot-product attention on a CSR pair (rows = destinations) ------------------
 @custom_op('pyg_amd::transformer_attend', mutates_args=(), device_types=_DEV)
@@ -912,4 +976,4 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward',
        'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward',
        'gen_aggregate', 'gen_aggregate_backward', 'resgated_aggregate',
-       'resgated_aggregate_backward')
+       'resgated_aggregate_backward', 'han_attend', 'han_attend_backward')
