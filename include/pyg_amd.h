@@ -976,6 +976,46 @@ PYGAMD_API int pygamd_resgated_backward_src(const pygamd_csr* g, const void* edg
                                             float* grad_qv, void* workspace,
                                             size_t workspace_bytes, void* stream);
 
+/* ---- mixture messages, aggregate first (gmm_conv.py:154-165, nn_conv.py:119-122) -----------------
+ * GMMConv's message is m_e = sum_k w_k(e_attr) (x_j G_k) with Gaussian weights w_k, NNConv's is
+ * m_e = x_j reshape(nn(e_attr)), an affine map of the hidden edge features.  Both are a per-edge
+ * mixture of K linear maps, m_e = sum_k c[e, k] (x_j W_k), and the reference forms [E, K, M]
+ * (GMM) or [E, F, M] (NNConv).  Summing over the slots of a destination BEFORE the maps gives
+ *   Z[i, k, :] = sum_{slots s of i} c[edge_id[s], k] * x[col[s], :]     Z [n_rows, K * F]
+ *   out[i, :]  = Z[i].reshape(K F) @ W                                 W [K * F, M], by the caller
+ * so a slot gathers ONE row of F floats and everything wide is per node.  The gradients:
+ *   grad_x = expand over the TRANSPOSED handle (rows = sources, x := grad_out [n_dst, M], edge_id_t)
+ *            then a dense product with W's axes permuted;
+ *   grad_W = Z^T grad_out (Z recomputed by one more expand);
+ *   grad_c[edge_id[s], k] = <wide[i, k F : (k + 1) F], x[col[s], :]>,  wide = grad_out @ W^T.
+ *
+ * pygamd_mixture_expand: Z over the handle g, one 64-lane wave per row, lane l the columns l + 64 e.
+ *   k runs in compile-time tiles (tile * columns per lane <= 32 accumulators in registers); a row's
+ *   slots are walked once per tile, the repeated x rows being cache hits; the coefficients of a
+ *   slot and tile are loaded once by the first lanes and broadcast.  x [n_cols, F] is read at its
+ *   row stride ld_x, coef [E, K] is contiguous in the caller's edge order (edge_id NULL: the slots
+ *   are the edges), Z is contiguous.  A split row's chunk partials are summed in chunk order (the
+ *   workspace, pygamd_mixture_workspace_bytes = n_chunks * K * F floats).  Rows without slots: 0.
+ * pygamd_mixture_coef_grad: over the by-destination handle; wide [n_rows, K * F] contiguous, held
+ *   per tile in registers; per slot and tile one gather of x[col[s]], the tile's dot products
+ *   reduced across the wave together (halving exchanges, then a butterfly).  Every (edge, k) is
+ *   written exactly once; rows without slots load nothing.  No workspace.
+ *
+ * pygamd_mixture_supported(F, K): 1 <= F <= 512 and 1 <= K <= 256 (no instantiation uses scratch,
+ * profiles/mixture_conv.md); otherwise status 2.  fp32 data, int32 / int64 indices.  No float
+ * atomics: bitwise reproducible.  Status 1 / 2 / 3 before any device work; n_rows == 0 returns 0. */
+PYGAMD_API int pygamd_mixture_supported(int64_t F, int64_t K);
+PYGAMD_API int pygamd_mixture_workspace_bytes(int64_t n_chunks, int64_t F, int64_t K,
+                                              size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_mixture_expand(const pygamd_csr* g, const void* edge_id, const float* x,
+                                     int64_t ld_x, const float* coef, int64_t n_cols, int64_t F,
+                                     int64_t K, float* z, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+PYGAMD_API int pygamd_mixture_coef_grad(const pygamd_csr* g, const void* edge_id,
+                                        const float* wide, const float* x, int64_t ld_x,
+                                        int64_t n_cols, int64_t F, int64_t K, float* grad_coef,
+                                        void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

@@ -956,6 +956,41 @@ class ResGatedAggregateFunction(Function):
             want_weights=need[3] or need[4]) + (None, None)
 
 
+class MixtureConvFunction(Function):
+    """The propagate step of a layer whose message is a per-edge mixture of ``K`` linear maps —
+    GMMConv (gmm_conv.py:154-165) and NNConv (nn_conv.py:119-122) — aggregate first:
+
+        out[i] = (sum_{e: dst(e) = i} coef[e, :] (x) x_src[src(e)]).reshape(K * F) @ weight
+
+    with ``coef [E, K]`` in the caller's edge order and ``weight [K, F, M]``: one expand launch
+    that gathers ONE row of ``F`` floats per slot (csrc/mixture.hip) and one dense product on the
+    package's GEMM route.  Only the inputs are saved; the backward recomputes the wide plane with
+    one more expand, and nothing of size ``E x`` anything wider than ``K`` exists at any time.
+    What ``needs_input_grad`` does not ask for is not computed."""
+
+    @staticmethod
+    def forward(ctx, x_src: Tensor, coef: Tensor, weight: Tensor, graph: EdgeIndex, n_dst: int):
+        _check_rows(graph, n_dst, 'x_src', x_src, 'x_dst', None)
+        if (x_src.dim() != 2 or coef.dim() != 2 or weight.dim() != 3
+                or weight.size(1) != x_src.size(1) or weight.size(0) != coef.size(1)):
+            raise ValueError(f"'x_src' [N, F], 'coef' [E, K] and 'weight' [K, F, M] do not agree "
+                             f"(got {tuple(x_src.shape)}, {tuple(coef.shape)}, "
+                             f"{tuple(weight.shape)})")
+        fwd = graph.by_dst()
+        out = _onepass.mixture_forward(fwd, fwd.perm, x_src, coef, weight)
+        ctx.save_for_backward(x_src, coef, weight)
+        ctx.graph = graph
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        need = ctx.needs_input_grad
+        return _onepass.mixture_backward(
+            Slots.of_graph(ctx.graph), *ctx.saved_tensors, grad_out.contiguous(), want_x=need[0],
+            want_coef=need[1], want_weight=need[2]) + (None, None)
+
+
 class PnaAggregateFunction(Function):
     """The aggregation of PNAConv with a linear message (pna_conv.py:175-188 under
     aggr/scaler.py:82) in ONE pass over the by-destination slots.  The message of slot ``k`` of

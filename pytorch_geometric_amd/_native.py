@@ -2078,6 +2078,83 @@ def resgated_backward_src(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[T
     return grad_qv
 
 
+# ---- mixture messages, aggregate first (csrc/mixture.hip) ------------------------------------------
+def mixture_supported(F: int, K: int) -> bool:
+    """The kernels serve rows of ``1 <= F <= 512`` floats and ``1 <= K <= 256`` coefficients per
+    edge."""
+    return bool(_lib.load().pygamd_mixture_supported(int(F), int(K)))
+
+
+def _mixture_coef(coef: Tensor, E: int, name: str = 'coef') -> Tensor:
+    if coef.dtype != torch.float32 or coef.dim() != 2 or coef.size(0) != E or coef.size(1) < 1:
+        raise ValueError(f"'{name}' must be a float32 [{E}, K] tensor (got {coef.dtype} "
+                         f"{tuple(coef.shape)})")
+    return coef.contiguous()
+
+
+def mixture_expand(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], x: Tensor,
+                   coef: Tensor, *, hub=None) -> Tensor:
+    """``Z [n_rows, K * F]`` with ``Z[r, k * F + f] = sum_{slots s of r} coef[edge_id[s], k] *
+    x[col[s], f]`` over a sorted handle: the forward's by destination, or the transposed one with
+    ``x := grad_out`` for the gradient of ``x``.  ``x`` may be a column block of a wider tensor
+    (its row stride is passed); ``coef [E, K]`` stays in the caller's edge order (``edge_id=None``:
+    it follows the slots).  Rows without slots are exactly 0."""
+    _require_device(rowptr, col, edge_id, x, coef)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    if x.dim() != 2:
+        raise ValueError("'x' must be two-dimensional")
+    F = x.size(1)
+    x = _strided_rows(x, 'x', F)
+    coef = _mixture_coef(coef, col.numel())
+    K = coef.size(1)
+    edge_id = _edge_id(edge_id, rowptr, col)
+    dev = x.device
+    if n_rows == 0 or col.numel() == 0:  # no slot anywhere: zeros, nothing to launch
+        return torch.zeros(n_rows, K * F, dtype=torch.float32, device=dev)
+    z = torch.empty(n_rows, K * F, dtype=torch.float32, device=dev)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_mixture_workspace_bytes, (g.n_chunks, F, K), dev,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'mixture', 'op': 'expand', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'K': K, 'ld': _ld(x), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x):
+        check(lib.pygamd_mixture_expand(
+            ctypes.byref(g), _p(edge_id), _p(x), _ld(x), _p(coef), x.size(0), F, K, _p(z), _p(ws),
+            ws_bytes, _stream(x)), 'mixture_expand')
+    return z
+
+
+def mixture_coef_grad(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], wide: Tensor,
+                      x: Tensor, *, hub=None) -> Tensor:
+    """``grad_coef [E, K]`` with ``grad_coef[edge_id[s], k] = <wide[r, k * F : (k + 1) * F],
+    x[col[s], :]>`` for every slot ``s`` of every row ``r`` of the by-destination handle; ``wide
+    [n_rows, K * F]`` is contiguous, ``x`` may be a column block."""
+    _require_device(rowptr, col, edge_id, wide, x)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    if x.dim() != 2:
+        raise ValueError("'x' must be two-dimensional")
+    F = x.size(1)
+    x = _strided_rows(x, 'x', F)
+    if (wide.dtype != torch.float32 or wide.dim() != 2 or wide.size(0) != n_rows or F < 1
+            or wide.size(1) < F or wide.size(1) % F):
+        raise ValueError(f"'wide' must be a float32 [{n_rows}, K * {F}] tensor (got {wide.dtype} "
+                         f"{tuple(wide.shape)})")
+    wide = wide.contiguous()
+    K = wide.size(1) // F
+    edge_id = _edge_id(edge_id, rowptr, col)
+    grad = torch.empty(col.numel(), K, dtype=torch.float32, device=x.device)
+    if n_rows == 0 or col.numel() == 0:
+        return grad
+    g = _csr(rowptr, col, n_rows, hub)
+    with _timed({'kind': 'mixture', 'op': 'coef_grad', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'K': K, 'ld': _ld(x), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x):
+        check(lib.pygamd_mixture_coef_grad(
+            ctypes.byref(g), _p(edge_id), _p(wide), _p(x), _ld(x), x.size(0), F, K, _p(grad),
+            _stream(x)), 'mixture_coef_grad')
+    return grad
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

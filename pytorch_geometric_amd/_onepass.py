@@ -290,6 +290,51 @@ def resgated_backward(slots, k, qv, edge_attr, w_gate, w_value, grad_out, *, wan
             g_w[0] if give_w else None, g_w[1] if give_w else None)
 
 
+def _transposed_product(a, b):
+    """``a.T @ b`` (``a [n, p]``, ``b [n, q]``) on the package's weight-gradient GEMM from the
+    row count up at which :func:`_functions.linear` takes the own kernels"""
+    from ._functions import own_linear_eligible
+    if own_linear_eligible(a, b):
+        return _native.linear_wgrad(a, b)
+    return a.t() @ b
+
+
+def mixture_forward(fwd, edge_id, x_src, coef, weight):
+    """``out [n_dst, M]`` of a mixture message ``m_e = sum_k coef[e, k] (x_j weight[k])`` summed
+    over the slots of every destination, aggregate first: one expand launch (``Z [n_dst, K * F]``,
+    one gathered row of ``F`` floats per slot) and one dense product with ``weight [K, F, M]``."""
+    from ._functions import linear
+    K, F, M = weight.shape
+    z = _native.mixture_expand(fwd.ptr, fwd.idx, edge_id, x_src, coef, hub=fwd.hub)
+    return linear(z, weight.reshape(K * F, M).t().contiguous())
+
+
+def mixture_backward(slots, x_src, coef, weight, grad_out, *, want_x=True, want_coef=True,
+                     want_weight=True):
+    """``(grad_x_src, grad_coef, grad_weight)``, None where not wanted.  ``grad_weight = Z^T
+    grad_out`` with ``Z`` recomputed by one expand; ``grad_coef`` from ``gZ = grad_out @ W^T`` held
+    per destination (one launch); ``grad_x`` one expand of ``grad_out`` over the by-source form and
+    one dense product with ``weight``'s axes permuted.  Each reads ``F`` or ``M`` floats per edge."""
+    from ._functions import linear
+    K, F, M = weight.shape
+    fwd = slots.fwd
+    g_x = g_c = g_w = None
+    if want_weight:
+        z = _native.mixture_expand(fwd.ptr, fwd.idx, slots.edge_id(), x_src, coef, hub=fwd.hub)
+        g_w = _transposed_product(z, grad_out).view(K, F, M)
+        del z
+    if want_coef:
+        g_z = linear(grad_out, weight.reshape(K * F, M))
+        g_c = _native.mixture_coef_grad(fwd.ptr, fwd.idx, slots.edge_id(), g_z, x_src, hub=fwd.hub)
+        del g_z
+    if want_x:
+        bwd = slots.by_src()
+        t = _native.mixture_expand(bwd.ptr, bwd.idx, slots.edge_id_t(), grad_out, coef,
+                                   hub=bwd.hub)
+        g_x = linear(t, weight.permute(1, 0, 2).reshape(F, K * M))
+    return g_x, g_c, g_w
+
+
 def hgt_blocks(kqvs, src_pos, F):
     """``(ks, vs)`` per edge type: the key and value column blocks of its ``[N, 3 * F]`` source"""
     return [kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos]

@@ -13,7 +13,9 @@ from .gin_conv import GINConv, GINEConv
 from .pna_conv import PNAConv
 from .gen_conv import GENConv
 from .res_gated_graph_conv import ResGatedGraphConv
+from .gmm_conv import GMMConv
+from .nn_conv import NNConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
-           'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv']
+           'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv']

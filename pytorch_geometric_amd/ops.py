@@ -51,6 +51,8 @@ Operators (all index tensors int32 / int64, features float32):
 ``resgated_aggregate``      ``(Tensor k, Tensor qv, Tensor? edge_attr, Tensor? w_gate,
                             Tensor? w_value, Tensor rowptr, Tensor col, Tensor? edge_id)
                             -> Tensor``
+``mixture_conv``            ``(Tensor x_src, Tensor coef, Tensor weight, Tensor rowptr,
+                            Tensor col, Tensor? edge_id) -> Tensor``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -914,6 +916,62 @@ def _resgated_bwd(ctx, grad):
 register_autograd('pyg_amd::resgated_aggregate', _resgated_bwd, setup_context=_resgated_setup)
 
 
+# ---- mixture messages (GMMConv, NNConv) aggregate first, on a CSR pair (rows = destinations) -----
+@custom_op('pyg_amd::mixture_conv', mutates_args=(), device_types=_DEV)
+def mixture_conv(x_src: Tensor, coef: Tensor, weight: Tensor, rowptr: Tensor, col: Tensor,
+                 edge_id: Optional[Tensor]) -> Tensor:
+    """The propagate of GMMConv (gmm_conv.py:154-165) and NNConv (nn_conv.py:119-122): ``out
+    [n_dst, M] = Z.reshape(n_dst, K * F) @ weight`` with ``Z[i, k] = sum_s coef[edge_id[s], k] *
+    x_src[col[s]]`` over the slots of ``i``, ``coef [E, K]`` and ``weight [K, F, M]``.
+    ``edge_id=None``: ``coef`` follows the slots of ``col``."""
+    K, F, M = weight.shape
+    if not _native.mixture_supported(F, K):
+        raise NotImplementedError(
+            f'mixture_conv serves 1 <= F <= 512 and 1 <= K <= 256 (got F = {F}, K = {K})')
+    return _onepass.mixture_forward(_onepass._Form(rowptr, col), edge_id, x_src, coef, weight)
+
+
+@mixture_conv.register_fake
+def _(x_src, coef, weight, rowptr, col, edge_id):
+    return x_src.new_empty(rowptr.numel() - 1, weight.shape[2])
+
+
+@custom_op('pyg_amd::mixture_conv_backward', mutates_args=(), device_types=_DEV)
+def mixture_conv_backward(grad: Tensor, x_src: Tensor, coef: Tensor, weight: Tensor,
+                          rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], need_x: bool,
+                          need_coef: bool, need_weight: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """The gradients of ``(x_src, coef, weight)``; one that is not needed is an empty tensor."""
+    grads = _onepass.mixture_backward(Slots.of_csr(rowptr, col, x_src.size(0), edge_id), x_src,
+                                      coef, weight, grad, want_x=need_x, want_coef=need_coef,
+                                      want_weight=need_weight)
+    return tuple(grad.new_empty(0) if g is None else (g.clone() if g._base is not None else g)
+                 for g in grads)
+
+
+@mixture_conv_backward.register_fake
+def _(grad, x_src, coef, weight, rowptr, col, edge_id, need_x, need_coef, need_weight):
+    e = grad.new_empty(0)
+    return (torch.empty_like(x_src, memory_format=torch.contiguous_format) if need_x else e,
+            torch.empty_like(coef, memory_format=torch.contiguous_format) if need_coef else e,
+            torch.empty_like(weight, memory_format=torch.contiguous_format) if need_weight else e)
+
+
+def _mixture_setup(ctx, inputs, output):
+    x_src, coef, weight, rowptr, col, edge_id = inputs
+    ctx.save_for_backward(x_src, coef, weight, rowptr, col, edge_id)
+
+
+def _mixture_bwd(ctx, grad):
+    x_src, coef, weight, rowptr, col, edge_id = ctx.saved_tensors
+    need = ctx.needs_input_grad[:3]
+    grads = mixture_conv_backward(grad.contiguous(), x_src, coef, weight, rowptr, col, edge_id,
+                                  *need)
+    return tuple(g if n else None for g, n in zip(grads, need)) + (None, None, None)
+
+
+register_autograd('pyg_amd::mixture_conv', _mixture_bwd, setup_context=_mixture_setup)
+
+
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
 @custom_op('pyg_amd::hgt_relation', mutates_args=(), device_types=_DEV)
 def hgt_relation(kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor, src_pos: List[int],
@@ -976,4 +1034,5 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'transformer_edge_attend_backward', 'hgt_relation', 'hgt_relation_backward',
        'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward',
        'gen_aggregate', 'gen_aggregate_backward', 'resgated_aggregate',
-       'resgated_aggregate_backward', 'han_attend', 'han_attend_backward')
+       'resgated_aggregate_backward', 'han_attend', 'han_attend_backward', 'mixture_conv',
+       'mixture_conv_backward')
