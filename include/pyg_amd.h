@@ -976,6 +976,81 @@ PYGAMD_API int pygamd_resgated_backward_src(const pygamd_csr* g, const void* edg
                                             float* grad_qv, void* workspace,
                                             size_t workspace_bytes, void* stream);
 
+/* ---- CGConv's gated softplus sum (cg_conv.py:81-98) ---------------------------------------------
+ * out_i = x_i + aggr_{j->i} sigmoid(lin_f(z_ij)) * softplus(lin_s(z_ij)), z_ij = cat[x_i, x_j, e_ij],
+ * F = channels[1].  The reference forms z [E, F_dst + F_src + D], runs the two Linear over its E
+ * rows and keeps both results, both activations and the product (cg_conv.py:93-98).  Each Linear
+ * splits into its destination, source and edge columns,
+ *   lin_f(cat[x_i, x_j, a]) = Wf_i x_i + bf + Wf_j x_j + Wf_e a            (lin_s alike),
+ * so with the node-level products
+ *   P = [Pf | Ps] = x_dst @ [Wf_i ; Ws_i]^T + [bf ; bs]   [N_dst, 2F]
+ *   Q = [Qf | Qs] = x_src @ [Wf_j ; Ws_j]^T               [N_src, 2F]
+ * slot k of destination i with source j = col[k] and edge id = edge_id[k] has
+ *   zf_k = Pf_i + Qf_j + ef_k,  zs_k = Ps_i + Qs_j + es_k
+ *   out_i = epilogue( sum_k sigmoid(zf_k) * softplus(zs_k) )     (replaces :88, propagate, and :90)
+ * sigmoid(z) = 1 / (1 + expf(-z)); softplus(z) = z > 20 ? z : log1pf(expf(z)), the rule of
+ * torch.nn.functional.softplus.  The edge terms by edge_mode (PYGAMD_GEN_EDGE_*), De = 0 unless
+ * LINEAR:
+ *   NONE    no edge term: edge_attr = weight = NULL;
+ *   LINEAR  ef_k = Wf_e a_k, es_k = Ws_e a_k from the raw features a_k = edge_attr[id, :De];
+ *           weight [2, F, De] = Wf_e, then Ws_e (torch.nn.Linear's layout each) sits in registers;
+ *   WIDE    [ef_k | es_k] = edge_attr[id, :2F], where edge_attr is the caller's dense product
+ *           edge_terms [E, 2F] = a @ [Wf_e ; Ws_e]^T; weight = NULL.
+ * The epilogue, once per row (for a split row after its chunk partials were summed in chunk
+ * order): scale = 1 (mean) divides by the row's slot count, an empty row stays 0; residual !=
+ * NULL adds residual[i, :F] (row stride ld_r).  scale is 0 or 1.
+ *
+ * forward: ONE launch over the by-destination handle g, one 64-lane wave per row, lanes over the F
+ * columns, Pf_i and Ps_i in registers, per slot ONE gathered 2F row of Q read in place at ld_q.
+ * Nothing is saved: the backward recomputes both activations from the inputs.
+ *
+ * backward, with s = sigmoid(zf), p = softplus(zs), g = grad_out[i] (scale = 1: / slot count of i),
+ *   gzf = g p s (1 - s),  gzs = g s (zs > 20 ? 1 : sigmoid(zs)):
+ *   pygamd_cg_backward_dst (the forward's handle): grad_p[i, :2F] = [sum_k gzf | sum_k gzs] at row
+ *     stride ld_gp.  grad_edge (NULL: not wanted) is, LINEAR, grad_edge_attr [E, De] with row id =
+ *     Wf_e^T gzf + Ws_e^T gzs and, WIDE, grad_edge_terms [E, 2F] with row id = [gzf | gzs].
+ *     grad_weight [2, F, De] (LINEAR; NULL otherwise) = (sum gzf a_k^T, sum gzs a_k^T) from
+ *     per-workgroup partials reduced in workgroup order.
+ *   pygamd_cg_backward_src (the transposed handle: col = the destination of every out-slot,
+ *     edge_id_t = that form's slot -> original edge map): Qf_j, Qs_j in registers, the 2F row P_i
+ *     and g_i gathered per slot, grad_q [N_src, 2F] = [sum gzf | sum gzs] at row stride ld_gq,
+ *     zeros for rows without slots.  dst_rowptr: the by-destination rowptr at g's index type, for
+ *     the slot counts, with scale = 1; NULL with scale = 0.
+ * p, q, grad_out, residual, grad_p and grad_q have row strides (floats): with one x for both
+ * roles the caller makes ONE [N, 4F] projection [P | Q] and the two backward launches write the
+ * halves of ONE [N, 4F] gradient plane.  Everything else is contiguous; fp32 data, int32 / int64
+ * indices.
+ *
+ * pygamd_cg_supported(F, De): F <= 512 and, for LINEAR (De > 0), De <= 32 and F * De <= 2048: no
+ * instantiation uses scratch (profiles/cg_conv.md); otherwise status 2, and the caller uses WIDE.
+ * There is no workspace query of its own: the entry points take a workspace of
+ * pygamd_resgated_workspace_bytes(n_chunks, F, De) bytes (two F-wide partial rows per chunk and,
+ * by destination with De > 0, two [F, De] partial matrices per workgroup; forward and by source:
+ * De = 0 there) and return status 3 on a smaller one.  No float atomics, every grid a function of
+ * (n_rows, n_chunks) only: bitwise reproducible.  Status 1 / 2 / 3 before any device work;
+ * n_rows == 0 returns 0.                                                                         */
+PYGAMD_API int pygamd_cg_supported(int64_t F, int64_t De);
+PYGAMD_API int pygamd_cg_forward(const pygamd_csr* g, const void* edge_id, const float* p,
+                                 int64_t ld_p, const float* q, int64_t ld_q, int edge_mode,
+                                 const float* edge_attr, const float* weight,
+                                 const float* residual, int64_t ld_r, int scale, int64_t n_src,
+                                 int64_t F, int64_t De, float* out, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_cg_backward_dst(const pygamd_csr* g, const void* edge_id, const float* p,
+                                      int64_t ld_p, const float* q, int64_t ld_q, int edge_mode,
+                                      const float* edge_attr, const float* weight,
+                                      const float* grad_out, int64_t ld_g, int scale,
+                                      int64_t n_src, int64_t F, int64_t De, float* grad_p,
+                                      int64_t ld_gp, float* grad_edge, float* grad_weight,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_cg_backward_src(const pygamd_csr* g, const void* edge_id_t, const float* p,
+                                      int64_t ld_p, const float* q, int64_t ld_q, int edge_mode,
+                                      const float* edge_attr, const float* weight,
+                                      const float* grad_out, int64_t ld_g, int scale,
+                                      const void* dst_rowptr, int64_t n_dst, int64_t F,
+                                      int64_t De, float* grad_q, int64_t ld_gq, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 /* ---- mixture messages, aggregate first (gmm_conv.py:154-165, nn_conv.py:119-122) -----------------
  * GMMConv's message is m_e = sum_k w_k(e_attr) (x_j G_k) with Gaussian weights w_k, NNConv's is
  * m_e = x_j reshape(nn(e_attr)), an affine map of the hidden edge features.  Both are a per-edge

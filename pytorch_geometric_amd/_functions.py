@@ -956,6 +956,51 @@ class ResGatedAggregateFunction(Function):
             want_weights=need[3] or need[4]) + (None, None)
 
 
+class CGAggregateFunction(Function):
+    """The propagate step of CGConv (cg_conv.py:88, 93-98) with the residual of cg_conv.py:90 in
+    ONE pass over the by-destination slots:
+
+        out[i] = residual[i] + aggr_{k of i} sigmoid(zf_k) * softplus(zs_k)
+        [zf_k | zs_k] = p[i] + q[j_k] + (edge terms of k)
+
+    with the node-level ``p = [Pf | Ps] [>= n_dst, 2F]`` (both biases folded in) and ``q = [Qf |
+    Qs] [N_src, 2F]``, one gathered row per slot — or ``q=None`` and ``p`` the packed ``[N, 4F] =
+    [P | Q]`` of one node set in both roles, whose gradient is then ONE ``[N, 4F]`` plane.  Edge
+    terms: none; ``edge_attr [E, De]`` with ``w_f``, ``w_s [F, De]`` (raw features, rebuilt per
+    slot in registers); or ``edge_terms [E, 2F]`` (a dense product of the caller's; the backward
+    writes its ``[E, 2F]`` gradient).  ``mean`` divides by the slot count; ``residual [n_dst, F]``
+    may be None.  Only the inputs are saved; the backward, one pass by destination and one by
+    source, recomputes both activations (csrc/cg.hip)."""
+
+    @staticmethod
+    def forward(ctx, p: Tensor, q: Optional[Tensor], edge_attr: Optional[Tensor],
+                w_f: Optional[Tensor], w_s: Optional[Tensor], edge_terms: Optional[Tensor],
+                residual: Optional[Tensor], graph: EdgeIndex, n_dst: int, mean: bool = False):
+        if edge_terms is not None and edge_attr is not None:
+            raise ValueError("'edge_attr' (with 'w_f', 'w_s') and 'edge_terms' exclude each other")
+        P, Q = _onepass.cg_split(p, q)
+        _check_rows(graph, n_dst, 'q', Q, 'p', P)
+        fwd = graph.by_dst()
+        out = _native.cg_forward(fwd.ptr, fwd.idx, fwd.perm, P, Q,
+                                 edge_attr if edge_terms is None else edge_terms,
+                                 _onepass.cg_weight(w_f, w_s), residual=residual, mean=mean,
+                                 hub=fwd.hub)
+        ctx.save_for_backward(p, q, edge_attr, w_f, w_s, edge_terms)
+        ctx.graph, ctx.mean = graph, bool(mean)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        need = ctx.needs_input_grad
+        grad_out = grad_out.contiguous()
+        grads = _onepass.cg_backward(
+            Slots.of_graph(ctx.graph), *ctx.saved_tensors, grad_out, mean=ctx.mean,
+            want_p=need[0], want_q=need[1], want_edge_attr=need[2],
+            want_weights=need[3] or need[4], want_edge_terms=need[5])
+        return grads + (grad_out if need[6] else None, None, None, None)
+
+
 class MixtureConvFunction(Function):
     """The propagate step of a layer whose message is a per-edge mixture of ``K`` linear maps —
     GMMConv (gmm_conv.py:154-165) and NNConv (nn_conv.py:119-122) — aggregate first:

@@ -2078,6 +2078,177 @@ def resgated_backward_src(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[T
     return grad_qv
 
 
+# ---- CGConv's gated softplus sum (csrc/cg.hip) ------------------------------------------------------
+def cg_supported(F: int, De: int = 0) -> bool:
+    """The kernels serve ``F <= 512``; the raw-feature edge mode (``De >= 1``: both edge matrices
+    in registers) additionally needs ``De <= 32`` and ``F * De <= 2048``.  Past that a caller
+    passes the dense product ``edge_terms [E, 2F]`` instead (``De = 0``)."""
+    return bool(_lib.load().pygamd_cg_supported(int(F), int(De)))
+
+
+def _cg_args(p: Tensor, q: Tensor, edge_attr: Optional[Tensor], weight: Optional[Tensor],
+             n_dst: int, E: int):
+    """(p, q, mode, edge_attr, weight, F, De) checked: the packed ``p [>= n_dst, 2F]`` and ``q
+    [n_src, 2F]`` with their row strides; ``edge_attr [E, De]`` with ``weight [2, F, De]`` (raw
+    features, the two matrices in registers), ``edge_attr [E, 2F]`` alone (the dense edge terms)
+    or neither."""
+    if p.dim() != 2 or p.size(1) % 2:
+        raise ValueError("'p' must be a two-dimensional [n, 2F] tensor")
+    F = p.size(1) // 2
+    p, q = _strided_rows(p, 'p', 2 * F), _strided_rows(q, 'q', 2 * F)
+    if p.size(0) < n_dst:
+        raise ValueError(f"'p' needs at least {n_dst} rows")
+    if edge_attr is None:
+        if weight is not None:
+            raise ValueError("'weight' comes with 'edge_attr'")
+        return p, q, GEN_EDGE_NONE, None, None, F, 0
+    edge_attr = _edge_rows(edge_attr, E)
+    if weight is None:
+        if edge_attr.size(1) != 2 * F:
+            raise ValueError(f"without 'weight', 'edge_attr' holds the edge terms [{E}, {2 * F}] "
+                             f"(got {tuple(edge_attr.shape)})")
+        return p, q, GEN_EDGE_WIDE, edge_attr, None, F, 0
+    De = edge_attr.size(1)
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (2, F, De) or De < 1:
+        raise ValueError(f"'weight' must be float32 [2, {F}, {De}] (got {weight.dtype} "
+                         f"{tuple(weight.shape)})")
+    return p, q, GEN_EDGE_LINEAR, edge_attr, weight.contiguous(), F, De
+
+
+def _cg_plane(out: Optional[Tensor], rows: int, n_rows: int, F: int, device, name: str) -> Tensor:
+    """the ``[rows, 2F]`` gradient a backward launch writes: the caller's column block of a wider
+    plane (rows beyond ``n_rows`` are the caller's to zero) or a fresh tensor"""
+    if out is None:
+        return _grad_rows(rows, n_rows, 2 * F, device)
+    if (out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (rows, 2 * F)
+            or (out.numel() > 0 and (out.stride(1) != 1 or out.stride(0) < 2 * F))):
+        raise ValueError(f"'{name}' must be a float32 [{rows}, {2 * F}] tensor with unit column "
+                         f"stride")
+    return out
+
+
+def _cg_workspace(lib, n_chunks: int, F: int, De: int, device):
+    # (no query of its own: the cg entry points take resgated's workspace, include/pyg_amd.h)
+    return _workspace(lib.pygamd_resgated_workspace_bytes, (n_chunks, F, De), device,
+                      n_chunks > 0 or De > 0)
+
+
+def cg_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], p: Tensor, q: Tensor,
+               edge_attr: Optional[Tensor] = None, weight: Optional[Tensor] = None, *,
+               residual: Optional[Tensor] = None, mean: bool = False, hub=None) -> Tensor:
+    """``out [n_rows, F] = epilogue(sum_k sigmoid(zf_k) * softplus(zs_k))`` on a by-destination
+    handle with ``[zf_k | zs_k] = p[i] + q[col[k]] + (edge terms of edge_id[k])``; the edge modes
+    are :func:`_cg_args`'s.  ``mean`` divides by the row's slot count, ``residual [>= n_rows, F]``
+    is added after that; a row without slots is exactly its residual (or 0).  ``p``, ``q`` and
+    ``residual`` may be column blocks of wider tensors."""
+    _require_device(rowptr, col, edge_id, p, q, edge_attr, weight, residual)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    p, q, mode, edge_attr, weight, F, De = _cg_args(p, q, edge_attr, weight, n_rows, col.numel())
+    if residual is not None:
+        residual = _strided_rows(residual, 'residual', F)
+        if residual.size(0) < n_rows:
+            raise ValueError(f"'residual' needs at least {n_rows} rows")
+    edge_id = _edge_id(edge_id, rowptr, col)
+    dev = p.device
+    if n_rows == 0 or col.numel() == 0:  # no slot anywhere: the epilogue alone, nothing to launch
+        if residual is None:
+            return torch.zeros(n_rows, F, dtype=torch.float32, device=dev)
+        return residual[:n_rows].clone(memory_format=torch.contiguous_format)
+    out = torch.empty(n_rows, F, dtype=torch.float32, device=dev)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _cg_workspace(lib, g.n_chunks, F, 0, dev)
+    with _timed({'kind': 'cg', 'op': 'forward', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'De': De, 'mode': mode, 'ld': _ld(q), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': False}, p):
+        check(lib.pygamd_cg_forward(
+            ctypes.byref(g), _p(edge_id), _p(p), _ld(p), _p(q), _ld(q), mode, _p(edge_attr),
+            _p(weight), _p(residual), 0 if residual is None else _ld(residual), int(bool(mean)),
+            q.size(0), F, De, _p(out), _p(ws), ws_bytes, _stream(p)), 'cg_forward')
+    return out
+
+
+def cg_backward_dst(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], p: Tensor, q: Tensor,
+                    edge_attr: Optional[Tensor], weight: Optional[Tensor], grad_out: Tensor, *,
+                    mean: bool = False, want_grad_edge: bool = True,
+                    out: Optional[Tensor] = None, hub=None):
+    """``(grad_p [rows of p, 2F], grad_edge | None, grad_weight [2, F, De] | None)`` on the
+    forward's by-destination handle: ``grad_p[i] = [sum gzf | sum gzs]`` with both activations
+    recomputed.  ``grad_edge`` is ``grad_edge_attr [E, De]`` with raw features and the per-slot
+    ``[gzf | gzs]``, the gradient of the edge terms ``[E, 2F]``, with dense ones, in the caller's
+    edge order.  ``out``: the ``[rows of p, 2F]`` column block of a wider plane to write ``grad_p``
+    into (its rows past ``n_rows`` are left alone)."""
+    _require_device(rowptr, col, edge_id, p, q, edge_attr, weight, grad_out, out)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    p, q, mode, edge_attr, weight, F, De = _cg_args(p, q, edge_attr, weight, n_rows, col.numel())
+    grad_out = _strided_rows(grad_out, 'grad_out', F)
+    if grad_out.size(0) != n_rows:
+        raise ValueError(f"'grad_out' needs {n_rows} rows")
+    edge_id = _edge_id(edge_id, rowptr, col)
+    want_grad_edge = bool(want_grad_edge) and mode != GEN_EDGE_NONE
+    dev = p.device
+    grad_p = _cg_plane(out, p.size(0), n_rows, F, dev, 'out')
+    grad_edge = torch.empty_like(edge_attr) if want_grad_edge else None
+    grad_w = torch.empty_like(weight) if weight is not None else None
+    if n_rows == 0 or col.numel() == 0:
+        grad_p[:n_rows].zero_()
+        return (grad_p, None if grad_edge is None else grad_edge.zero_(),
+                None if grad_w is None else grad_w.zero_())
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _cg_workspace(lib, g.n_chunks, F, De, dev)
+    with _timed({'kind': 'cg', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'De': De, 'mode': mode, 'ld': _ld(q), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': want_grad_edge}, p):
+        check(lib.pygamd_cg_backward_dst(
+            ctypes.byref(g), _p(edge_id), _p(p), _ld(p), _p(q), _ld(q), mode, _p(edge_attr),
+            _p(weight), _p(grad_out), _ld(grad_out), int(bool(mean)), q.size(0), F, De,
+            _p(grad_p), _ld(grad_p), _p(grad_edge), _p(grad_w), _p(ws), ws_bytes, _stream(p)),
+            'cg_backward_dst')
+    return grad_p, grad_edge, grad_w
+
+
+def cg_backward_src(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], p: Tensor,
+                    q: Tensor, edge_attr: Optional[Tensor], weight: Optional[Tensor],
+                    grad_out: Tensor, *, dst_rowptr: Optional[Tensor] = None,
+                    out: Optional[Tensor] = None, hub=None) -> Tensor:
+    """``grad_q [n_src, 2F] = [sum gzf | sum gzs]`` on the by-SOURCE handle (``col_t`` = the
+    destination of every out-slot, ``edge_id_t`` = that form's slot -> edge map).  ``p`` and
+    ``grad_out`` are gathered per slot at their own row strides.  ``dst_rowptr``: the
+    by-destination ``rowptr`` of a mean aggregation (None: sum).  ``out``: the ``[n_src, 2F]``
+    column block of a wider plane to write into."""
+    _require_device(rowptr_t, col_t, edge_id_t, p, q, edge_attr, weight, grad_out, dst_rowptr, out)
+    lib = _lib.load()
+    n_src = rowptr_t.numel() - 1
+    p, q, mode, edge_attr, weight, F, De = _cg_args(p, q, edge_attr, weight, 0, col_t.numel())
+    if q.size(0) != n_src:
+        raise ValueError(f"'q' needs {n_src} rows")
+    grad_out = _strided_rows(grad_out, 'grad_out', F)
+    n_dst = grad_out.size(0)
+    if p.size(0) < n_dst:
+        raise ValueError(f"'p' needs at least {n_dst} rows")
+    if dst_rowptr is not None:
+        if dst_rowptr.dtype != rowptr_t.dtype or dst_rowptr.numel() != n_dst + 1:
+            raise ValueError(f"'dst_rowptr' must have the index dtype and {n_dst + 1} entries")
+        dst_rowptr = dst_rowptr.contiguous()
+    edge_id_t = _edge_id(edge_id_t, rowptr_t, col_t, 'edge_id_t')
+    dev = p.device
+    grad_q = _cg_plane(out, n_src, n_src, F, dev, 'out')
+    if n_src == 0 or col_t.numel() == 0:
+        return grad_q.zero_()
+    g = _csr(rowptr_t, col_t, n_src, hub)
+    ws, ws_bytes = _cg_workspace(lib, g.n_chunks, F, 0, dev)
+    with _timed({'kind': 'cg', 'op': 'backward_src', 'n_rows': n_src, 'E': col_t.numel(), 'F': F,
+                 'De': De, 'mode': mode, 'ld': _ld(p), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks,
+                 'grad_edge_attr': False}, p):
+        check(lib.pygamd_cg_backward_src(
+            ctypes.byref(g), _p(edge_id_t), _p(p), _ld(p), _p(q), _ld(q), mode, _p(edge_attr),
+            _p(weight), _p(grad_out), _ld(grad_out), int(dst_rowptr is not None),
+            _p(dst_rowptr), n_dst, F, De, _p(grad_q), _ld(grad_q), _p(ws), ws_bytes, _stream(p)),
+            'cg_backward_src')
+    return grad_q
+
+
 # ---- mixture messages, aggregate first (csrc/mixture.hip) ------------------------------------------
 def mixture_supported(F: int, K: int) -> bool:
     """The kernels serve rows of ``1 <= F <= 512`` floats and ``1 <= K <= 256`` coefficients per

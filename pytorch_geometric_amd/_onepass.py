@@ -290,6 +290,60 @@ def resgated_backward(slots, k, qv, edge_attr, w_gate, w_value, grad_out, *, wan
             g_w[0] if give_w else None, g_w[1] if give_w else None)
 
 
+def cg_weight(w_f, w_s):
+    """the kernels' stacked ``[2, F, De]`` edge matrices (None without raw edge features)"""
+    return None if w_f is None else torch.stack([w_f, w_s])
+
+
+def cg_split(p, q):
+    """``(P, Q)`` as the kernels read them: two tensors, or (``q`` None) the halves of the packed
+    ``p = [P | Q] [N, 4F]`` in place"""
+    if q is not None:
+        return p, q
+    half = p.size(1) // 2
+    return p[:, :half], p[:, half:]
+
+
+def cg_backward(slots, p, q, edge_attr, w_f, w_s, edge_terms, grad_out, *, mean=False,
+                want_p=True, want_q=True, want_edge_attr=True, want_weights=True,
+                want_edge_terms=True):
+    """``(grad_p, grad_q, grad_edge_attr, grad_w_f, grad_w_s, grad_edge_terms)``, None where not
+    wanted or not given: one launch by destination (``grad_P`` and everything of the edge term),
+    then one by source (``grad_Q``).  Both recompute the sigmoid and the softplus.  With the
+    packed ``p = [P | Q]`` (``q`` None) the two launches write the halves of ONE ``[N, 4F]``
+    plane, which is ``grad_p``.  The by-destination launch is skipped when none of its outputs
+    is wanted."""
+    fwd = slots.fwd
+    packed = q is None
+    P, Q = cg_split(p, q)
+    weight = cg_weight(w_f, w_s)
+    linear, wide = weight is not None, edge_terms is not None
+    edge = edge_terms if wide else (edge_attr if linear else None)
+    want_edge = (linear and want_edge_attr) or (wide and want_edge_terms)
+    out_p = out_q = g_p = g_q = g_e = g_w = None
+    if packed:
+        want_q = want_p
+        if want_p:
+            plane = torch.empty_like(p, memory_format=torch.contiguous_format)
+            out_p, out_q = cg_split(plane, None)
+            out_p[fwd.n_rows:].zero_()   # (sources that are no destination)
+    if want_p or want_edge or (linear and want_weights):
+        g_p, g_e, g_w = _native.cg_backward_dst(
+            fwd.ptr, fwd.idx, slots.edge_id(), P, Q, edge, weight, grad_out, mean=mean,
+            want_grad_edge=want_edge, out=out_p, hub=fwd.hub)
+    if want_q:
+        bwd = slots.by_src()
+        g_q = _native.cg_backward_src(
+            bwd.ptr, bwd.idx, None if edge is None else slots.edge_id_t(), P, Q, edge, weight,
+            grad_out, dst_rowptr=fwd.ptr if mean else None, out=out_q, hub=bwd.hub)
+    if packed:
+        g_p, g_q = (plane if want_p else None), None
+    give_w = want_weights and g_w is not None
+    return (g_p if want_p else None, g_q, g_e if linear and want_edge_attr else None,
+            g_w[0] if give_w else None, g_w[1] if give_w else None,
+            g_e if wide and want_edge_terms else None)
+
+
 def _transposed_product(a, b):
     """``a.T @ b`` (``a [n, p]``, ``b [n, q]``) on the package's weight-gradient GEMM from the
     row count up at which :func:`_functions.linear` takes the own kernels"""

@@ -15,7 +15,8 @@ from .gen_conv import GENConv
 from .res_gated_graph_conv import ResGatedGraphConv
 from .gmm_conv import GMMConv
 from .nn_conv import NNConv
+from .cg_conv import CGConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
-           'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv']
+           'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv']

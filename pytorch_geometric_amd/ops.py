@@ -53,6 +53,9 @@ Operators (all index tensors int32 / int64, features float32):
                             -> Tensor``
 ``mixture_conv``            ``(Tensor x_src, Tensor coef, Tensor weight, Tensor rowptr,
                             Tensor col, Tensor? edge_id) -> Tensor``
+``cg_aggregate``            ``(Tensor p, Tensor? q, Tensor? edge_attr, Tensor? w_f, Tensor? w_s,
+                            Tensor? edge_terms, Tensor? residual, Tensor rowptr, Tensor col,
+                            Tensor? edge_id, bool mean) -> Tensor``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -916,6 +919,85 @@ def _resgated_bwd(ctx, grad):
 register_autograd('pyg_amd::resgated_aggregate', _resgated_bwd, setup_context=_resgated_setup)
 
 
+# ---- CGConv's gated softplus sum on a CSR pair (rows = destinations) -----------------------------------
+def _cg_width(p: Tensor, q: Optional[Tensor]) -> int:
+    return p.size(1) // (2 if q is not None else 4)
+
+
+@custom_op('pyg_amd::cg_aggregate', mutates_args=(), device_types=_DEV)
+def cg_aggregate(p: Tensor, q: Optional[Tensor], edge_attr: Optional[Tensor],
+                 w_f: Optional[Tensor], w_s: Optional[Tensor], edge_terms: Optional[Tensor],
+                 residual: Optional[Tensor], rowptr: Tensor, col: Tensor,
+                 edge_id: Optional[Tensor], mean: bool) -> Tensor:
+    """CGConv's propagate and residual (cg_conv.py:88-98): ``out [n_dst, F] = residual + aggr_k
+    sigmoid(zf_k) * softplus(zs_k)`` with ``[zf_k | zs_k] = p[i] + q[col[k]] +`` the edge terms of
+    ``edge_id[k]``: ``p [>= n_dst, 2F]``, ``q [n_src, 2F]`` (or ``q`` None and ``p`` the packed
+    ``[n_src, 4F] = [P | Q]``); ``edge_attr [E, De]`` with ``w_f``, ``w_s [F, De]``, or
+    ``edge_terms [E, 2F]``, or neither.  ``mean``: divide by the slot count.  ``edge_id=None``:
+    the edge tensors follow the slots of ``col``."""
+    F = _cg_width(p, q)
+    De = 0 if edge_attr is None else edge_attr.size(1)
+    if not _native.cg_supported(F, De):
+        raise NotImplementedError(
+            f'cg_aggregate serves F <= 512 and, with raw edge features, De <= 32 and F * De <= '
+            f'2048 (got F = {F}, De = {De}); pass edge_terms [E, 2F] beyond that')
+    if edge_terms is not None and edge_attr is not None:
+        raise ValueError("'edge_attr' (with 'w_f', 'w_s') and 'edge_terms' exclude each other")
+    P, Q = _onepass.cg_split(p, q)
+    return _native.cg_forward(rowptr, col, edge_id, P, Q,
+                              edge_attr if edge_terms is None else edge_terms,
+                              _onepass.cg_weight(w_f, w_s), residual=residual, mean=mean,
+                              hub=_native.hub_plan(rowptr))
+
+
+@cg_aggregate.register_fake
+def _(p, q, edge_attr, w_f, w_s, edge_terms, residual, rowptr, col, edge_id, mean):
+    return p.new_empty(rowptr.numel() - 1, _cg_width(p, q))
+
+
+@custom_op('pyg_amd::cg_aggregate_backward', mutates_args=(), device_types=_DEV)
+def cg_aggregate_backward(grad: Tensor, p: Tensor, q: Optional[Tensor],
+                          edge_attr: Optional[Tensor], w_f: Optional[Tensor],
+                          w_s: Optional[Tensor], edge_terms: Optional[Tensor], rowptr: Tensor,
+                          col: Tensor, edge_id: Optional[Tensor], mean: bool
+                          ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The gradients of ``(p, q, edge_attr, w_f, w_s, edge_terms)``; an input that was not given
+    gets an empty tensor.  (The residual's gradient is ``grad`` itself.)"""
+    n_src = p.size(0) if q is None else q.size(0)
+    grads = _onepass.cg_backward(Slots.of_csr(rowptr, col, n_src, edge_id), p, q, edge_attr, w_f,
+                                 w_s, edge_terms, grad, mean=mean)
+    # (one tensor EACH, none a view of another: an operator's outputs must not alias)
+    return tuple(grad.new_empty(0) if g is None else (g.clone() if g._base is not None else g)
+                 for g in grads)
+
+
+@cg_aggregate_backward.register_fake
+def _(grad, p, q, edge_attr, w_f, w_s, edge_terms, rowptr, col, edge_id, mean):
+    def like(t):
+        return (grad.new_empty(0) if t is None
+                else torch.empty_like(t, memory_format=torch.contiguous_format))
+    return tuple(like(t) for t in (p, q, edge_attr, w_f, w_s, edge_terms))
+
+
+def _cg_setup(ctx, inputs, output):
+    p, q, edge_attr, w_f, w_s, edge_terms, residual, rowptr, col, edge_id, mean = inputs
+    ctx.given = tuple(t is not None for t in (p, q, edge_attr, w_f, w_s, edge_terms))
+    ctx.mean, ctx.residual = mean, residual is not None
+    ctx.save_for_backward(p, q, edge_attr, w_f, w_s, edge_terms, rowptr, col, edge_id)
+
+
+def _cg_bwd(ctx, grad):
+    p, q, edge_attr, w_f, w_s, edge_terms, rowptr, col, edge_id = ctx.saved_tensors
+    grad = grad.contiguous()
+    grads = cg_aggregate_backward(grad, p, q, edge_attr, w_f, w_s, edge_terms, rowptr, col,
+                                  edge_id, ctx.mean)
+    grads = tuple(g if given else None for g, given in zip(grads, ctx.given))
+    return grads + (grad if ctx.residual else None, None, None, None, None)
+
+
+register_autograd('pyg_amd::cg_aggregate', _cg_bwd, setup_context=_cg_setup)
+
+
 # ---- mixture messages (GMMConv, NNConv) aggregate first, on a CSR pair (rows = destinations) -----
 @custom_op('pyg_amd::mixture_conv', mutates_args=(), device_types=_DEV)
 def mixture_conv(x_src: Tensor, coef: Tensor, weight: Tensor, rowptr: Tensor, col: Tensor,
@@ -1035,4 +1117,4 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward',
        'gen_aggregate', 'gen_aggregate_backward', 'resgated_aggregate',
        'resgated_aggregate_backward', 'han_attend', 'han_attend_backward', 'mixture_conv',
-       'mixture_conv_backward')
+       'mixture_conv_backward', 'cg_aggregate', 'cg_aggregate_backward')
