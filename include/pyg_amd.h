@@ -1051,6 +1051,80 @@ PYGAMD_API int pygamd_cg_backward_src(const pygamd_csr* g, const void* edge_id_t
                                       int64_t De, float* grad_q, int64_t ld_gq, void* workspace,
                                       size_t workspace_bytes, void* stream);
 
+/* ---- FiLMConv's typed feature modulation (film_conv.py:128-161) ----------------------------------
+ * x'_i = act(gs_i * W_skip x_i + bs_i) + sum_r aggr_{j in N_r(i)} act(gamma_{r,i} * W_r x_j + beta_{r,i}),
+ * [beta_{r,i} | gamma_{r,i}] = film_r(x_i), F = out_channels, R relations.  The reference runs one
+ * masked propagate per relation (film_conv.py:139-153), each with a mask, edge_index[:, mask], two
+ * [E_r, F] gathers of beta and gamma, one of x_j, the [E_r, F] message and its activation, and
+ * 2R + 2 dense transforms.  The activation sits inside the sum and depends on both ends, but every
+ * operand is node-level:
+ *   H = x_src @ [W_0 ; ... ; W_{R-1}]^T                  [N_src, R F], relation r = columns [rF, (r+1)F)
+ *   G = [film_0(x_dst) | ... | film_{R-1}(x_dst)]        [N_dst, R 2F], block r = [beta_r | gamma_r]:
+ *       beta first, gamma second, as split(out_channels) gives them (film_conv.py:135, 140).
+ * With the default Linear film nets both are one dense product with stacked weights, and with one
+ * x in both roles ONE [N, 3RF] plane [H | G] that the kernels read in place through row strides;
+ * the two backward launches then write ONE gradient plane of that shape, which feeds ONE
+ * input-gradient product.  With a caller's nn, G is the cat of the R module outputs: the module
+ * runs on nodes, never on edges.  The skip term act(gs * lin_skip(x_dst) + bs) is node-level too:
+ * the caller computes it from a second stacked product x_dst @ [lin_skip ; film_skip]^T [N_dst, 3F]
+ * and passes it as residual (row stride ld_r); its gradient is grad_out itself.
+ *
+ * Per slot k of destination i, with source j = col[k], edge e = edge_id[k] (NULL: e = k) and
+ * r = rel[e] (int32 [E], in [0, R): the caller drops other edges when it builds the handle, the
+ * kernels check no index, as the other one-pass kernels):
+ *   pre = fmaf(gamma_{r,i}, H[j, rF:(r+1)F], beta_{r,i}),   m = act(pre)
+ *   out_i = residual_i + sum_k scale[e] * m_k
+ * act_mode 0 is the identity (act=None), 1 is ReLU: pre > 0 ? pre : 0 with derivative pre > 0 (0 at
+ * exactly 0, as torch).  scale is NULL for add / sum; for mean it is the per-edge float
+ * 1 / |N_r(i)|.  The sum does not depend on the relation, so the hub plan and the in-order chunk
+ * merge apply unchanged; the residual is added once in the epilogue, for a split row after the
+ * merge.  A row without slots gives exactly residual_i (0 without one).
+ *
+ * pygamd_film_forward: ONE launch over the by-destination handle g of all edges, one 64-lane wave
+ *   per row, lanes over the F columns.  A slot gathers ONE F-wide row of H; the lane's
+ *   [beta | gamma] stay in registers and are loaded again only when a slot's relation differs from
+ *   the one before.  Any in-row order is correct; in a row grouped by relation (a stable
+ *   by-destination sort of edges pre-sorted by relation) a wave reloads once per relation present.
+ *   Nothing is saved: the backward recomputes the activation from the inputs.
+ * pygamd_film_backward_dst: ONE launch over the (relation, destination) pair rows: row p of g holds
+ *   the slots of relation pair_rel[p] into destination pair_dst[p] (index arrays at g's index
+ *   type, one entry per row; the rows are the non-empty pairs, col = the sources).  With
+ *   gm = grad_out_i * act'(pre):  grad_gb[i, r 2F:(r+1) 2F] = [sum gm | sum gm * h], with mean = 1
+ *   divided by the pair row's length (once, after the merge for a split row).
+ * pygamd_film_backward_src: ONE launch over the (relation, source) pair rows of the flipped graph
+ *   (pair_rel, pair_src; col = the destinations; edge_id_t = that handle's slot -> edge map, for
+ *   scale): grad_h[j, rF:(r+1)F] = sum scale[e] * grad_out_i * act'(pre) * gamma_{r,i}.
+ * Neither backward launch writes the block of a pair that does not occur: the caller zero-fills
+ * grad_h and grad_gb once.  h, gb, residual, grad_out, grad_h and grad_gb have row strides
+ * (floats); everything else is contiguous; fp32 data, int32 / int64 indices.
+ *
+ * pygamd_film_supported(F): F <= 512, the lane shapes of the resgated kernels without an edge term
+ * (no instantiation uses scratch: profiles/film_conv.md); otherwise status 2.  There is no
+ * workspace query of its own: the three entry points take a workspace of
+ * pygamd_resgated_workspace_bytes(n_chunks, F, 0) bytes, whose two F-wide partial rows per chunk
+ * cover all three launches (F forward and by source, 2F by destination), and return status 3 on a
+ * smaller one.  No float atomics, every grid a function of (n_rows, n_chunks) only: bitwise
+ * reproducible.  Status 1 / 2 / 3 before any device work; n_rows == 0 returns 0.                  */
+PYGAMD_API int pygamd_film_supported(int64_t F);
+PYGAMD_API int pygamd_film_forward(const pygamd_csr* g, const void* edge_id, const int32_t* rel,
+                                   const float* h, int64_t ld_h, const float* gb, int64_t ld_gb,
+                                   const float* scale, const float* residual, int64_t ld_r,
+                                   int act_mode, int64_t n_src, int64_t F, int64_t R, float* out,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_film_backward_dst(const pygamd_csr* g, const void* pair_rel,
+                                        const void* pair_dst, const float* h, int64_t ld_h,
+                                        const float* gb, int64_t ld_gb, const float* grad_out,
+                                        int64_t ld_g, int act_mode, int mean, int64_t n_src,
+                                        int64_t F, int64_t R, float* grad_gb, int64_t ld_ggb,
+                                        void* workspace, size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_film_backward_src(const pygamd_csr* g, const void* edge_id_t,
+                                        const void* pair_rel, const void* pair_src,
+                                        const float* h, int64_t ld_h, const float* gb,
+                                        int64_t ld_gb, const float* scale, const float* grad_out,
+                                        int64_t ld_g, int act_mode, int64_t n_dst, int64_t F,
+                                        int64_t R, float* grad_h, int64_t ld_gh, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+
 /* ---- mixture messages, aggregate first (gmm_conv.py:154-165, nn_conv.py:119-122) -----------------
  * GMMConv's message is m_e = sum_k w_k(e_attr) (x_j G_k) with Gaussian weights w_k, NNConv's is
  * m_e = x_j reshape(nn(e_attr)), an affine map of the hidden edge features.  Both are a per-edge

@@ -26,7 +26,8 @@ BUILD_DIR = os.path.join(os.path.dirname(PKG_DIR), 'build', 'pyg_amd')
 SOURCES = ['capi.hip', 'graph.hip', 'spmm.hip', 'scatter.hip', 'softmax.hip', 'segmm.hip',
            'sample.hip', 'minibatch.hip', 'train.hip', 'gemm.hip', 'sage_fused.hip',
            'hetero_conv.hip', 'gatv2.hip', 'transformer.hip', 'hgt.hip', 'gine.hip',
-           'pna.hip', 'gen.hip', 'resgated.hip', 'han.hip', 'mixture.hip', 'cg.hip']
+           'pna.hip', 'gen.hip', 'resgated.hip', 'han.hip', 'mixture.hip', 'cg.hip',
+           'film.hip']
 LAB_SOURCES = SOURCES + ['sage_fused_lab.hip']
 LAB_FLAGS = {'gemm.hip': ['-DPYGAMD_LAB=1']}   # the weight-gradient variants and probes
 ARCH = 'gfx950'

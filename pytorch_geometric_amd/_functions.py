@@ -1001,6 +1001,39 @@ class CGAggregateFunction(Function):
         return grads + (grad_out if need[6] else None, None, None, None)
 
 
+class FiLMAggregateFunction(Function):
+    """The R masked propagate steps of FiLMConv (film_conv.py:134-153, its message at 157-161) and
+    the sum with the skip term in ONE pass over the by-destination slots of all edges:
+
+        out[i] = residual[i] + sum_{k of i} scale[e_k] * act(gamma_{r,i} * H[j_k, block r] + beta_{r,i})
+
+    with ``r`` the relation of slot ``k``'s edge, the node-level ``h = H [N_src, R * F]`` and ``g =
+    G [>= n_dst, R * 2F]`` (block ``r`` = ``[beta_r | gamma_r]``) — or ``g=None`` and ``h`` the
+    packed ``[N, 3 R F] = [H | G]`` of one node set in both roles, whose gradient is then ONE
+    plane of that shape.  ``forms`` (:class:`_onepass.FilmForms`) carries the handle, ``rel``,
+    the mean normaliser and the two pair forms of the backward; ``relu=False``: no activation.
+    Only the inputs are saved; the backward, one pass over the ``(relation, destination)`` pair
+    rows and one over the ``(relation, source)`` pair rows, recomputes the activation's mask
+    (csrc/film.hip)."""
+
+    @staticmethod
+    def forward(ctx, h: Tensor, g: Optional[Tensor], residual: Optional[Tensor], forms,
+                relu: bool = True):
+        out = _onepass.film_forward(forms, h, g, residual, bool(relu))
+        ctx.save_for_backward(h, g)
+        ctx.forms, ctx.relu = forms, bool(relu)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        need = ctx.needs_input_grad
+        grad_out = grad_out.contiguous()
+        grads = _onepass.film_backward(ctx.forms, *ctx.saved_tensors, grad_out, relu=ctx.relu,
+                                       want_h=need[0], want_g=need[1])
+        return grads + (grad_out if need[2] else None, None, None)
+
+
 class MixtureConvFunction(Function):
     """The propagate step of a layer whose message is a per-edge mixture of ``K`` linear maps —
     GMMConv (gmm_conv.py:154-165) and NNConv (nn_conv.py:119-122) — aggregate first:

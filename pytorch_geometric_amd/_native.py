@@ -2249,6 +2249,165 @@ def cg_backward_src(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor]
     return grad_q
 
 
+# ---- FiLMConv's typed feature modulation (csrc/film.hip) -------------------------------------------
+def film_supported(F: int) -> bool:
+    """The kernels serve ``1 <= F <= 512``."""
+    return bool(_lib.load().pygamd_film_supported(int(F)))
+
+
+def _film_args(h: Tensor, gb: Tensor, R: int):
+    """(h, gb, F) checked: ``h [n_src, R * F]`` and ``gb [>= n_dst, R * 2F]`` (block ``r`` =
+    ``[beta_r | gamma_r]``) with their row strides — two tensors or column blocks of one plane."""
+    R = int(R)
+    if R < 1 or h.dim() != 2 or h.size(1) % R or h.size(1) == 0:
+        raise ValueError(f"'h' must be a two-dimensional [n, R * F] tensor with R = {R}")
+    F = h.size(1) // R
+    return _strided_rows(h, 'h', R * F), _strided_rows(gb, 'gb', 2 * R * F), F
+
+
+def _film_rel(rel: Tensor, E: int) -> Tensor:
+    if rel.dtype != torch.int32 or rel.dim() != 1 or rel.numel() != E:
+        raise ValueError(f"'rel' must be an int32 [{E}] tensor (got {rel.dtype} "
+                         f"{tuple(rel.shape)})")
+    return rel.contiguous()
+
+
+def _film_scale(scale: Optional[Tensor], E: int) -> Optional[Tensor]:
+    if scale is None:
+        return None
+    if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != E:
+        raise ValueError(f"'scale' must be a float32 [{E}] tensor (got {scale.dtype} "
+                         f"{tuple(scale.shape)})")
+    return scale.contiguous()
+
+
+def _film_pairs(rowptr: Tensor, pair_rel: Tensor, pair_node: Tensor):
+    n = rowptr.numel() - 1
+    for name, t in (('pair_rel', pair_rel), ('pair_node', pair_node)):
+        if t.dtype != rowptr.dtype or t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"'{name}' must have the index dtype and one entry per pair row")
+    return pair_rel.contiguous(), pair_node.contiguous()
+
+
+def _film_plane(out: Tensor, rows: int, width: int, name: str) -> Tensor:
+    """the zero-filled ``[rows, width]`` gradient block a backward launch writes into: a tensor of
+    the caller's, or a column block of a wider plane"""
+    if (out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (rows, width)
+            or (out.numel() > 0 and (out.stride(1) != 1 or out.stride(0) < width))):
+        raise ValueError(f"'{name}' must be a float32 [{rows}, {width}] tensor with unit column "
+                         f"stride")
+    return out
+
+
+def _film_workspace(lib, n_chunks: int, F: int, device):
+    # (no query of its own: the film entry points take resgated's workspace, include/pyg_amd.h)
+    return _workspace(lib.pygamd_resgated_workspace_bytes, (n_chunks, F, 0), device, n_chunks > 0)
+
+
+def film_forward(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], rel: Tensor, h: Tensor,
+                 gb: Tensor, R: int, *, scale: Optional[Tensor] = None,
+                 residual: Optional[Tensor] = None, relu: bool = True, hub=None) -> Tensor:
+    """``out [n_rows, F] = residual + sum_k scale[e] * act(gamma * h[col[k], rF:(r+1)F] + beta)`` on
+    a by-destination handle with ``e = edge_id[k]``, ``r = rel[e]`` (int32, in ``[0, R)``: the
+    caller's to guarantee) and ``[beta | gamma] = gb[i, r * 2F:(r + 1) * 2F]``.  ``scale [E]``: the
+    per-edge mean normaliser (None: sum).  ``relu=False``: no activation.  A row without slots is
+    exactly its residual (or 0).  ``h``, ``gb`` and ``residual`` may be column blocks of wider
+    tensors."""
+    _require_device(rowptr, col, edge_id, rel, h, gb, scale, residual)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    h, gb, F = _film_args(h, gb, R)
+    if gb.size(0) < n_rows:
+        raise ValueError(f"'gb' needs at least {n_rows} rows")
+    E = col.numel()
+    rel, scale = _film_rel(rel, E), _film_scale(scale, E)
+    if residual is not None:
+        residual = _strided_rows(residual, 'residual', F)
+        if residual.size(0) < n_rows:
+            raise ValueError(f"'residual' needs at least {n_rows} rows")
+    edge_id = _edge_id(edge_id, rowptr, col)
+    dev = h.device
+    if n_rows == 0 or E == 0:  # no slot anywhere: the epilogue alone, nothing to launch
+        if residual is None:
+            return torch.zeros(n_rows, F, dtype=torch.float32, device=dev)
+        return residual[:n_rows].clone(memory_format=torch.contiguous_format)
+    out = torch.empty(n_rows, F, dtype=torch.float32, device=dev)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _film_workspace(lib, g.n_chunks, F, dev)
+    with _timed({'kind': 'film', 'op': 'forward', 'n_rows': n_rows, 'E': E, 'F': F, 'R': int(R),
+                 'ld': _ld(h), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, h):
+        check(lib.pygamd_film_forward(
+            ctypes.byref(g), _p(edge_id), _p(rel), _p(h), _ld(h), _p(gb), _ld(gb), _p(scale),
+            _p(residual), 0 if residual is None else _ld(residual), int(bool(relu)), h.size(0),
+            F, int(R), _p(out), _p(ws), ws_bytes, _stream(h)), 'film_forward')
+    return out
+
+
+def film_backward_dst(rowptr: Tensor, col: Tensor, pair_rel: Tensor, pair_dst: Tensor, h: Tensor,
+                      gb: Tensor, R: int, grad_out: Tensor, out: Tensor, *, mean: bool = False,
+                      relu: bool = True, hub=None) -> Tensor:
+    """Writes ``out[i, r * 2F:(r + 1) * 2F] = [sum gm | sum gm * h]`` (``gm = grad_out[i] *
+    act'(pre)``, for ``mean`` divided by the pair row's length) for every row ``p`` of the
+    ``(relation, destination)`` pair handle, ``r = pair_rel[p]``, ``i = pair_dst[p]``, ``col`` =
+    the sources of its slots.  ``out [rows of gb, R * 2F]`` is the caller's zero-filled plane, or
+    a column block of one: blocks of pairs that do not occur are left alone."""
+    _require_device(rowptr, col, pair_rel, pair_dst, h, gb, grad_out, out)
+    lib = _lib.load()
+    n_rows = rowptr.numel() - 1
+    h, gb, F = _film_args(h, gb, R)
+    grad_out = _strided_rows(grad_out, 'grad_out', F)
+    if gb.size(0) < grad_out.size(0):
+        raise ValueError(f"'gb' needs at least {grad_out.size(0)} rows")
+    out = _film_plane(out, gb.size(0), 2 * int(R) * F, 'out')
+    pair_rel, pair_dst = _film_pairs(rowptr, pair_rel, pair_dst)
+    if n_rows == 0 or col.numel() == 0:
+        return out
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _film_workspace(lib, g.n_chunks, F, h.device)
+    with _timed({'kind': 'film', 'op': 'backward_dst', 'n_rows': n_rows, 'E': col.numel(), 'F': F,
+                 'R': int(R), 'ld': _ld(h), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, h):
+        check(lib.pygamd_film_backward_dst(
+            ctypes.byref(g), _p(pair_rel), _p(pair_dst), _p(h), _ld(h), _p(gb), _ld(gb),
+            _p(grad_out), _ld(grad_out), int(bool(relu)), int(bool(mean)), h.size(0), F, int(R),
+            _p(out), _ld(out), _p(ws), ws_bytes, _stream(h)), 'film_backward_dst')
+    return out
+
+
+def film_backward_src(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor],
+                      pair_rel: Tensor, pair_src: Tensor, h: Tensor, gb: Tensor, R: int,
+                      grad_out: Tensor, out: Tensor, *, scale: Optional[Tensor] = None,
+                      relu: bool = True, hub=None) -> Tensor:
+    """Writes ``out[j, r * F:(r + 1) * F] = sum scale[e] * grad_out[i] * act'(pre) * gamma_{r,i}``
+    for every row ``p`` of the ``(relation, source)`` pair handle of the flipped graph, ``r =
+    pair_rel[p]``, ``j = pair_src[p]``, ``col_t`` = the destinations of its slots, ``edge_id_t`` =
+    that handle's slot -> edge map (for ``scale``).  ``out [n_src, R * F]`` is the caller's
+    zero-filled plane, or a column block of one."""
+    _require_device(rowptr_t, col_t, edge_id_t, pair_rel, pair_src, h, gb, scale, grad_out, out)
+    lib = _lib.load()
+    n_rows = rowptr_t.numel() - 1
+    h, gb, F = _film_args(h, gb, R)
+    grad_out = _strided_rows(grad_out, 'grad_out', F)
+    n_dst = grad_out.size(0)
+    if gb.size(0) < n_dst:
+        raise ValueError(f"'gb' needs at least {n_dst} rows")
+    out = _film_plane(out, h.size(0), int(R) * F, 'out')
+    pair_rel, pair_src = _film_pairs(rowptr_t, pair_rel, pair_src)
+    scale = _film_scale(scale, col_t.numel())
+    edge_id_t = _edge_id(edge_id_t, rowptr_t, col_t, 'edge_id_t')
+    if n_rows == 0 or col_t.numel() == 0:
+        return out
+    g = _csr(rowptr_t, col_t, n_rows, hub)
+    ws, ws_bytes = _film_workspace(lib, g.n_chunks, F, h.device)
+    with _timed({'kind': 'film', 'op': 'backward_src', 'n_rows': n_rows, 'E': col_t.numel(),
+                 'F': F, 'R': int(R), 'ld': _ld(gb), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks},
+                h):
+        check(lib.pygamd_film_backward_src(
+            ctypes.byref(g), _p(edge_id_t), _p(pair_rel), _p(pair_src), _p(h), _ld(h), _p(gb),
+            _ld(gb), _p(scale), _p(grad_out), _ld(grad_out), int(bool(relu)), n_dst, F, int(R),
+            _p(out), _ld(out), _p(ws), ws_bytes, _stream(h)), 'film_backward_src')
+    return out
+
+
 # ---- mixture messages, aggregate first (csrc/mixture.hip) ------------------------------------------
 def mixture_supported(F: int, K: int) -> bool:
     """The kernels serve rows of ``1 <= F <= 512`` floats and ``1 <= K <= 256`` coefficients per

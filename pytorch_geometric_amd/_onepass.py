@@ -344,6 +344,126 @@ def cg_backward(slots, p, q, edge_attr, w_f, w_s, edge_terms, grad_out, *, mean=
             g_e if wide and want_edge_terms else None)
 
 
+class _PairForm:
+    """The ``(relation, node)`` pair rows of a typed edge list (``RelationalHandle.pair_graph``):
+    ``ptr`` over the non-empty pairs, ``idx`` = the other endpoint per slot, ``edge_id`` = slot ->
+    edge, ``pair_rel`` / ``pair_node`` = the pair of every row, ``pair_of_slot`` = slot -> row."""
+
+    def __init__(self, node, other, rel, n_node, n_other, R, edge_of=None):
+        from .nn.conv.rgcn_conv import RelationalHandle
+        handle = RelationalHandle(torch.stack([other, node]), rel, n_other, n_node, R)
+        self._csr = handle.pair_graph.by_dst()
+        self.ptr, self.idx = self._csr.ptr, self._csr.idx
+        self.pair_rel, self.pair_node = handle.pair_rel, handle.pair_dst
+        self.pair_of_slot = handle._pair_of_edge
+        self.edge_id = (handle._perm if edge_of is None
+                        else _native.permute_index(edge_of.to(torch.int64), handle._perm))
+
+    @property
+    def hub(self):
+        return self._csr.hub
+
+
+class FilmForms:
+    """What the three FiLM launches walk: the by-destination form of ALL edges (``fwd``, with its
+    slot -> edge map ``edge_id``, the per-edge int32 ``rel`` in ``[0, R)`` and, for mean, the
+    per-edge ``scale = 1 / |N_r(i)|``) and the two pair forms of the backward, by ``(relation,
+    destination)`` and by ``(relation, source)``.  The pair forms are given (a layer's cached
+    ones) or, for a CSR pair of the operator route, built when the backward first asks."""
+
+    def __init__(self, fwd, edge_id, rel, scale, R, n_src, pairs=None):
+        self.fwd, self.edge_id, self.rel, self.scale = fwd, edge_id, rel, scale
+        self.R, self.n_src, self._given = int(R), int(n_src), pairs
+
+    @classmethod
+    def of_edges(cls, src, dst, rel, n_src, n_dst, R, mean):
+        """The forms of an edge list whose ``rel`` (int32) lies in ``[0, R)`` and is sorted: the
+        stable by-destination sort then leaves every row grouped by relation."""
+        from .edge_index import EdgeIndex
+        fwd = EdgeIndex(torch.stack([src, dst]), (n_src, n_dst)).by_dst()
+        src64, dst64 = src.to(torch.int64), dst.to(torch.int64)
+        pairs = (_PairForm(dst64, src64, rel, n_dst, n_src, R),
+                 _PairForm(src64, dst64, rel, n_src, n_dst, R))
+        scale = film_mean_scale(pairs[0]) if mean else None
+        return cls(fwd, fwd.perm, rel, scale, R, n_src, pairs)
+
+    @classmethod
+    def of_csr(cls, rowptr, col, edge_id, rel, scale, n_src, R):
+        return cls(_Form(rowptr, col), edge_id, rel, scale, R, n_src)
+
+    @functools.cached_property
+    def pairs(self):
+        """``(by (relation, destination), by (relation, source))``"""
+        if self._given is not None:
+            return self._given
+        ptr, col = self.fwd.ptr, self.fwd.idx
+        dst = _native.ptr2index(ptr, col.numel()).to(torch.int64)
+        src = col.to(torch.int64)
+        rel = self.rel if self.edge_id is None else self.rel[self.edge_id.to(torch.int64)]
+        n_dst = self.fwd.n_rows
+        return (_PairForm(dst, src, rel, n_dst, self.n_src, self.R),
+                _PairForm(src, dst, rel, self.n_src, n_dst, self.R, edge_of=self.edge_id))
+
+
+def film_mean_scale(by_dst_pairs):
+    """the per-edge mean normaliser ``1 / |N_r(i)|`` (float32 ``[E]``, in edge order) from the
+    lengths of the ``(relation, destination)`` pair rows"""
+    ptr = by_dst_pairs.ptr
+    inv = 1.0 / (ptr[1:] - ptr[:-1]).to(torch.float32)
+    scale = torch.empty(by_dst_pairs.idx.numel(), dtype=torch.float32, device=ptr.device)
+    scale[by_dst_pairs.edge_id] = inv[by_dst_pairs.pair_of_slot]
+    return scale
+
+
+def film_split(h, g):
+    """``(H, G)`` as the kernels read them: two tensors, or (``g`` None) the column blocks of the
+    packed ``h = [H | G] [N, 3 R F]`` in place"""
+    if g is not None:
+        return h, g
+    third = h.size(1) // 3
+    return h[:, :third], h[:, third:]
+
+
+def film_forward(forms, h, g, residual, relu):
+    """``out [n_dst, F]`` of :func:`_native.film_forward` on ``forms``; the rows the handle's
+    indices reach are checked here, the kernels check none"""
+    H, G = film_split(h, g)
+    fwd = forms.fwd
+    if H.size(0) < forms.n_src:
+        raise ValueError(f"'h' needs {forms.n_src} rows (got {H.size(0)})")
+    return _native.film_forward(fwd.ptr, fwd.idx, forms.edge_id, forms.rel, H, G, forms.R,
+                                scale=forms.scale, residual=residual, relu=relu, hub=fwd.hub)
+
+
+def film_backward(forms, h, g, grad_out, *, relu=True, want_h=True, want_g=True):
+    """``(grad_h, grad_g)``, None where not wanted: one launch over the ``(relation, destination)``
+    pair rows (``grad_G``), one over the ``(relation, source)`` pair rows (``grad_H``), both into
+    zero-filled planes and both recomputing the activation's mask.  With the packed ``h = [H | G]``
+    (``g`` None) they write the column blocks of ONE ``[N, 3 R F]`` plane, which is ``grad_h``."""
+    H, G = film_split(h, g)
+    if grad_out.size(0) != forms.fwd.n_rows or H.size(0) < forms.n_src:
+        raise ValueError(f"'grad_out' needs {forms.fwd.n_rows} rows and 'h' {forms.n_src}")
+    packed = g is None
+    out_h = out_g = plane = None
+    if packed:
+        if want_h:
+            plane = torch.zeros_like(h, memory_format=torch.contiguous_format)
+            out_h, out_g = film_split(plane, None)
+    else:
+        out_h = torch.zeros_like(h, memory_format=torch.contiguous_format) if want_h else None
+        out_g = torch.zeros_like(g, memory_format=torch.contiguous_format) if want_g else None
+    by_dst, by_src = forms.pairs
+    if out_g is not None:
+        _native.film_backward_dst(by_dst.ptr, by_dst.idx, by_dst.pair_rel, by_dst.pair_node, H, G,
+                                  forms.R, grad_out, out_g, mean=forms.scale is not None,
+                                  relu=relu, hub=by_dst.hub)
+    if out_h is not None:
+        _native.film_backward_src(by_src.ptr, by_src.idx, by_src.edge_id, by_src.pair_rel,
+                                  by_src.pair_node, H, G, forms.R, grad_out, out_h,
+                                  scale=forms.scale, relu=relu, hub=by_src.hub)
+    return (plane, None) if packed else (out_h, out_g)
+
+
 def _transposed_product(a, b):
     """``a.T @ b`` (``a [n, p]``, ``b [n, q]``) on the package's weight-gradient GEMM from the
     row count up at which :func:`_functions.linear` takes the own kernels"""

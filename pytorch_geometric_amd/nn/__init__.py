@@ -1,7 +1,7 @@
 from .aggr import (Aggregation, DegreeScalerAggregation, FusedAggregation, MaxAggregation, MeanAggregation,
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
-from .conv import (CGConv, FastRGCNConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HANConv, HeteroConv, HGTConv,
+from .conv import (CGConv, FastRGCNConv, FiLMConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HANConv, HeteroConv, HGTConv,
                    GENConv, GMMConv, MessagePassing, NNConv, PNAConv, ResGatedGraphConv, RGCNConv, SAGEConv, TransformerConv,
                    gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
@@ -15,6 +15,6 @@ __all__ = [
     'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
     'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
     'PNAConv', 'DegreeScalerAggregation', 'GENConv', 'MessageNorm', 'DeepGCNLayer',
-    'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv',
+    'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv', 'FiLMConv',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

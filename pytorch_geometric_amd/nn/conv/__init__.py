@@ -16,7 +16,9 @@ from .res_gated_graph_conv import ResGatedGraphConv
 from .gmm_conv import GMMConv
 from .nn_conv import NNConv
 from .cg_conv import CGConv
+from .film_conv import FiLMConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
-           'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv']
+           'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv',
+           'FiLMConv']

@@ -60,6 +60,7 @@ class RelationalHandle:
         self.num_pairs = S
         pair_rel = torch.div(pair_key, num_dst, rounding_mode='floor')
         pair_dst = pair_key - pair_rel * num_dst
+        self.pair_rel, self.pair_dst = pair_rel, pair_dst  # [S] each: the pair of every segment
         src_sorted = _native.permute_index(src.to(torch.int64), perm)
         # edges -> pairs (rows = pairs).  The COO form is only needed for the transposed handle.
         pair_of_edge = _native.ptr2index(seg_ptr, E)

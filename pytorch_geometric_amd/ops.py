@@ -56,6 +56,9 @@ Operators (all index tensors int32 / int64, features float32):
 ``cg_aggregate``            ``(Tensor p, Tensor? q, Tensor? edge_attr, Tensor? w_f, Tensor? w_s,
                             Tensor? edge_terms, Tensor? residual, Tensor rowptr, Tensor col,
                             Tensor? edge_id, bool mean) -> Tensor``
+``film_aggregate``          ``(Tensor h, Tensor? g, Tensor? residual, Tensor rowptr, Tensor col,
+                            Tensor? edge_id, Tensor rel, Tensor? scale, int num_relations,
+                            bool relu) -> Tensor``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -998,6 +1001,79 @@ def _cg_bwd(ctx, grad):
 register_autograd('pyg_amd::cg_aggregate', _cg_bwd, setup_context=_cg_setup)
 
 
+# ---- FiLMConv's typed feature modulation on a CSR pair (rows = destinations) ---------------------------
+def _film_forms(h, g, rowptr, col, edge_id, rel, scale, num_relations):
+    n_src = h.size(0)
+    return _onepass.FilmForms.of_csr(rowptr, col, edge_id, rel, scale, n_src, num_relations)
+
+
+@custom_op('pyg_amd::film_aggregate', mutates_args=(), device_types=_DEV)
+def film_aggregate(h: Tensor, g: Optional[Tensor], residual: Optional[Tensor], rowptr: Tensor,
+                   col: Tensor, edge_id: Optional[Tensor], rel: Tensor, scale: Optional[Tensor],
+                   num_relations: int, relu: bool) -> Tensor:
+    """FiLMConv's per-relation propagates and the sum with the skip term (film_conv.py:128-161):
+    ``out [n_dst, F] = residual + sum_k scale[e] * act(gamma * h[col[k], r F:(r + 1) F] + beta)``
+    with ``e = edge_id[k]``, ``r = rel[e]`` (int32 ``[E]``, in ``[0, num_relations)``: checked) and
+    ``[beta | gamma] = g[i, r * 2F:(r + 1) * 2F]``: ``h [n_src, R * F]``, ``g [>= n_dst, R * 2F]``
+    (or ``g`` None and ``h`` the packed ``[n_src, 3 R F] = [H | G]``).  ``scale [E]``: the
+    per-edge mean normaliser ``1 / |N_r(i)|`` (None: sum).  ``relu=False``: no activation.
+    ``edge_id=None``: ``rel`` and ``scale`` follow the slots of ``col``.  The slots of a row may
+    come in any order of relations."""
+    R = int(num_relations)
+    width = h.size(1) // (R if g is not None else 3 * R)
+    if not _native.film_supported(width):
+        raise NotImplementedError(f'film_aggregate serves 1 <= F <= 512 (got F = {width})')
+    if rel.numel() > 0:
+        lo, hi = _native.index_minmax(rel)
+        if lo < 0 or hi >= R:
+            raise ValueError(f"'rel' must lie in [0, {R}) (got values in [{lo}, {hi}])")
+    forms = _film_forms(h, g, rowptr, col, edge_id, rel, scale, R)
+    return _onepass.film_forward(forms, h, g, residual, relu)
+
+
+@film_aggregate.register_fake
+def _(h, g, residual, rowptr, col, edge_id, rel, scale, num_relations, relu):
+    return h.new_empty(rowptr.numel() - 1,
+                       h.size(1) // (num_relations if g is not None else 3 * num_relations))
+
+
+@custom_op('pyg_amd::film_aggregate_backward', mutates_args=(), device_types=_DEV)
+def film_aggregate_backward(grad: Tensor, h: Tensor, g: Optional[Tensor], rowptr: Tensor,
+                            col: Tensor, edge_id: Optional[Tensor], rel: Tensor,
+                            scale: Optional[Tensor], num_relations: int,
+                            relu: bool) -> Tuple[Tensor, Tensor]:
+    """The gradients of ``(h, g)``; ``g`` not given gets an empty tensor.  (The residual's
+    gradient is ``grad`` itself.)"""
+    forms = _film_forms(h, g, rowptr, col, edge_id, rel, scale, num_relations)
+    grads = _onepass.film_backward(forms, h, g, grad, relu=relu)
+    return tuple(grad.new_empty(0) if t is None else t for t in grads)
+
+
+@film_aggregate_backward.register_fake
+def _(grad, h, g, rowptr, col, edge_id, rel, scale, num_relations, relu):
+    return (torch.empty_like(h, memory_format=torch.contiguous_format),
+            grad.new_empty(0) if g is None
+            else torch.empty_like(g, memory_format=torch.contiguous_format))
+
+
+def _film_setup(ctx, inputs, output):
+    h, g, residual, rowptr, col, edge_id, rel, scale, num_relations, relu = inputs
+    ctx.static = (num_relations, relu)
+    ctx.given, ctx.residual = g is not None, residual is not None
+    ctx.save_for_backward(h, g, rowptr, col, edge_id, rel, scale)
+
+
+def _film_bwd(ctx, grad):
+    h, g, rowptr, col, edge_id, rel, scale = ctx.saved_tensors
+    grad = grad.contiguous()
+    g_h, g_g = film_aggregate_backward(grad, h, g, rowptr, col, edge_id, rel, scale, *ctx.static)
+    return (g_h, g_g if ctx.given else None, grad if ctx.residual else None, None, None, None,
+            None, None, None, None)
+
+
+register_autograd('pyg_amd::film_aggregate', _film_bwd, setup_context=_film_setup)
+
+
 # ---- mixture messages (GMMConv, NNConv) aggregate first, on a CSR pair (rows = destinations) -----
 @custom_op('pyg_amd::mixture_conv', mutates_args=(), device_types=_DEV)
 def mixture_conv(x_src: Tensor, coef: Tensor, weight: Tensor, rowptr: Tensor, col: Tensor,
@@ -1117,4 +1193,5 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'gine_aggregate', 'gine_aggregate_backward', 'pna_aggregate', 'pna_aggregate_backward',
        'gen_aggregate', 'gen_aggregate_backward', 'resgated_aggregate',
        'resgated_aggregate_backward', 'han_attend', 'han_attend_backward', 'mixture_conv',
-       'mixture_conv_backward', 'cg_aggregate', 'cg_aggregate_backward')
+       'mixture_conv_backward', 'cg_aggregate', 'cg_aggregate_backward', 'film_aggregate',
+       'film_aggregate_backward')
