@@ -1271,15 +1271,17 @@ def spmm_node(x: Tensor, w: Optional[Tensor], graph: EdgeIndex, reduce: str,
             and (w is None or (w.dim() == 1 and not w.requires_grad
                                and w.numel() == graph.num_edges))):
         fwd, bwd = graph.by_dst(), graph.by_src()
-        eid = eid_t = None
-        if w is not None:
-            eid = fwd.perm if w_order == 'coo' else None
-            eid_t = bwd.perm if w_order == 'coo' else graph.src_slot_to_dst_slot()
-        (h_rows, h_cptr, n_hub, n_chunks), (t_rows, t_cptr, t_hub, t_chunks) = fwd.hub, bwd.hub
-        inv = fwd.inv_degree() if reduce == 'mean' else None
-        return C.spmm_ag(x, w, fwd.ptr, fwd.idx, eid, h_rows, h_cptr, n_hub, n_chunks, bwd.ptr,
-                         bwd.idx, eid_t, t_rows, t_cptr, t_hub, t_chunks, inv,
-                         _native.REDUCE_IDS[reduce], _native.HUB_THRESHOLD, _native.HUB_CHUNK)
+        hub, hub_t = fwd.hub, bwd.hub
+        # (the node's schema takes ONE threshold and chunk for its two plans: plans made at
+        # different settings go through the Python node, which launches each with its own)
+        if (hub.threshold, hub.chunk) == (hub_t.threshold, hub_t.chunk):
+            eid = eid_t = None
+            if w is not None:
+                eid = fwd.perm if w_order == 'coo' else None
+                eid_t = bwd.perm if w_order == 'coo' else graph.src_slot_to_dst_slot()
+            inv = fwd.inv_degree() if reduce == 'mean' else None
+            return C.spmm_ag(x, w, fwd.ptr, fwd.idx, eid, *hub[:4], bwd.ptr, bwd.idx, eid_t,
+                             *hub_t[:4], inv, _native.REDUCE_IDS[reduce], hub.threshold, hub.chunk)
     return SpmmFunction.apply(x, w, graph, reduce, w_order)
 
 

@@ -8,7 +8,7 @@ import collections
 import ctypes
 import os
 import threading
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -73,24 +73,53 @@ def _plain(*tensors) -> bool:
     return True
 
 
-def _hub4(hub):
-    """(rows, chunk_ptr, n_hub, n_chunks) -> the same with Nones for 'no hub rows'"""
-    if hub is not None and hub[2] > 0:
-        return hub
-    return None, None, 0, 0
+class HubPlan(NamedTuple):
+    """The split of one row pointer's long rows: the hub rows, the exclusive scan of their chunk
+    counts and the ``(threshold, chunk)`` the scan was computed for.  The three only mean something
+    together, so a launch takes all of them from here (:func:`_csr`, :func:`_hub_args`,
+    :func:`_hub6`) and never pairs a cached plan with the module's current settings."""
+    rows: Optional[Tensor]         # None when n_hub == 0
+    chunk_ptr: Optional[Tensor]    # [n_hub + 1]; None when n_hub == 0
+    n_hub: int
+    n_chunks: int
+    threshold: int
+    chunk: int
 
 
-def _csr(rowptr: Tensor, col: Tensor, n_rows: int, hub) -> Csr:
+def no_hubs(threshold: Optional[int] = None, chunk: Optional[int] = None) -> HubPlan:
+    """The plan of a row pointer none of whose rows needs splitting at these settings (default,
+    as for :func:`hub_plan`: the module's, read now)."""
+    return HubPlan(None, None, 0, 0, HUB_THRESHOLD if threshold is None else threshold,
+                   HUB_CHUNK if chunk is None else chunk)
+
+
+def _hub6(hub: Optional[HubPlan]) -> HubPlan:
+    """The six loose hub arguments of a compiled route (``*_hub6(hub)``, in the plan's field
+    order); None: no hub rows, and the module's pair, which no kernel reads without them."""
+    return no_hubs() if hub is None else hub
+
+
+def _hub_args(a: SpmmArgs, hub: Optional[HubPlan]) -> None:
+    """The hub fields of a ``pygamd_spmm_args`` from a plan; without hub rows they stay zero.  The
+    caller keeps ``hub`` bound until the launch has returned."""
+    if hub is not None and hub.n_hub > 0:
+        a.hub_rows, a.hub_chunk_ptr = hub.rows.data_ptr(), hub.chunk_ptr.data_ptr()
+        a.n_hub, a.n_chunks = hub.n_hub, hub.n_chunks
+        a.hub_threshold, a.hub_chunk = hub.threshold, hub.chunk
+
+
+def _csr(rowptr: Tensor, col: Tensor, n_rows: int, hub: Optional[HubPlan]) -> Csr:
     """``pygamd_csr`` of a handle and its hub plan (``hub``: what :func:`hub_plan` returned for
-    this ``rowptr``, or None), split at this module's ``HUB_THRESHOLD`` / ``HUB_CHUNK``.  The
-    struct holds raw addresses and keeps nothing alive: the caller keeps every tensor given here
-    (and the result of any ``.contiguous()`` it passes) bound to a local until the call that
-    takes the struct has returned."""
-    h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
-    return Csr(rowptr=rowptr.data_ptr(), col=col.data_ptr(), idx_dtype=_idx_dtype(rowptr),
-               n_rows=n_rows, hub_rows=None if h_rows is None else h_rows.data_ptr(),
-               hub_chunk_ptr=None if h_cptr is None else h_cptr.data_ptr(), n_hub=n_hub,
-               n_chunks=n_chunks, hub_threshold=HUB_THRESHOLD, hub_chunk=HUB_CHUNK)
+    this ``rowptr``, or None: no hub rows), split at the plan's own threshold and chunk.  The
+    struct keeps the tensors given here alive; the result of a ``.contiguous()`` the caller made
+    for another argument of the launch is still the caller's to keep."""
+    rows, cptr, n_hub, n_chunks, threshold, chunk = _hub6(hub)
+    g = Csr(rowptr=rowptr.data_ptr(), col=col.data_ptr(), idx_dtype=_idx_dtype(rowptr),
+            n_rows=n_rows, hub_rows=None if rows is None else rows.data_ptr(),
+            hub_chunk_ptr=None if cptr is None else cptr.data_ptr(), n_hub=n_hub,
+            n_chunks=n_chunks, hub_threshold=threshold, hub_chunk=chunk)
+    g._keep = (rowptr, col, hub)
+    return g
 
 
 def _workspace(size_fn, dims, device, needed: bool = True):
@@ -262,15 +291,17 @@ def cumsum(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
-def hub_plan(rowptr: Tensor, threshold: int = None, chunk: int = None):
-    """Returns (hub_rows, hub_chunk_ptr, n_hub, n_chunks); tensors are None when n_hub == 0."""
+def hub_plan(rowptr: Tensor, threshold: Optional[int] = None,
+             chunk: Optional[int] = None) -> HubPlan:
+    """The :class:`HubPlan` of ``rowptr`` at ``(threshold, chunk)`` (default: the module's, read
+    now); without a hub row the tensors are None and the counts 0."""
     _require_device(rowptr)
-    threshold = HUB_THRESHOLD if threshold is None else threshold
-    chunk = HUB_CHUNK if chunk is None else chunk
-    lib = _lib.load()
+    none = no_hubs(threshold, chunk)
+    threshold, chunk = none.threshold, none.chunk
     n_rows = rowptr.numel() - 1
     if n_rows <= 0:
-        return None, None, 0, 0
+        return none
+    lib = _lib.load()
     nbytes = ctypes.c_size_t(0)
     check(lib.pygamd_hub_plan_workspace_bytes(_idx_dtype(rowptr), n_rows, ctypes.byref(nbytes)))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=rowptr.device)
@@ -281,9 +312,9 @@ def hub_plan(rowptr: Tensor, threshold: int = None, chunk: int = None):
                               _p(cptr), n_rows, ctypes.byref(n_hub), ctypes.byref(n_chunks),
                               _p(ws), nbytes.value, _stream(rowptr)), 'hub_plan')
     if n_hub.value == 0:
-        return None, None, 0, 0
-    return (rows[:n_hub.value].clone(), cptr[:n_hub.value + 1].clone(), n_hub.value,
-            n_chunks.value)
+        return none
+    return HubPlan(rows[:n_hub.value].clone(), cptr[:n_hub.value + 1].clone(), n_hub.value,
+                   n_chunks.value, threshold, chunk)
 
 
 # ---- CSR SpMM --------------------------------------------------------------------------------------
@@ -367,16 +398,15 @@ def spmm_csr(rowptr: Tensor, col: Optional[Tensor], x: Tensor, reduce: str, *,
             arg32 = None
             if save_arg32 and reduce in ('min', 'max'):
                 arg32 = torch.empty(nr, F, dtype=torch.int32, device=x.device)
-            h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+            hub = _hub6(hub)
             with _timed({'n_rows': nr, 'n_src': x.size(0),
                          'nnz': col.numel() if col is not None else x.size(0), 'F': F,
                          'reduce': reduce, 'idx_bytes': rowptr.element_size(),
                          'weighted': w is not None, 'src_scale': src_scale is not None,
                          'accumulate': bool(accumulate), 'relu_mask': relu_mask is not None,
-                         'relu_bits': relu_bits is not None, 'n_hub': n_hub}, x):
-                C.spmm_csr(rowptr, col, x, REDUCE_IDS[reduce], nr, eid, w, src_scale, h_rows,
-                           h_cptr, n_hub, n_chunks, HUB_THRESHOLD, HUB_CHUNK, out, accumulate,
-                           hub_phase, arg32, relu_mask, relu_bits)
+                         'relu_bits': relu_bits is not None, 'n_hub': hub.n_hub}, x):
+                C.spmm_csr(rowptr, col, x, REDUCE_IDS[reduce], nr, eid, w, src_scale, *hub, out,
+                           accumulate, hub_phase, arg32, relu_mask, relu_bits)
             return (out, arg32) if save_arg32 else out
     lib = _lib.load()
     x2 = _f32_rows(x, 'x')
@@ -433,16 +463,12 @@ def spmm_csr(rowptr: Tensor, col: Optional[Tensor], x: Tensor, reduce: str, *,
     if src_bits is not None:
         a.src_bits = src_bits.data_ptr()
         a.src_bits_set = 0 if src_bits_set is None else src_bits_set.data_ptr()
+    _hub_args(a, hub)
     ws, ws_bytes = None, 0
-    if hub is not None and hub[2] > 0:
-        hub_rows, hub_cptr, n_hub, n_chunks = hub
-        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), hub_cptr.data_ptr()
-        a.n_hub, a.n_chunks = n_hub, n_chunks
-        a.hub_threshold, a.hub_chunk = HUB_THRESHOLD, HUB_CHUNK
-        # (min / max take the hub list only to schedule those rows first: no workspace)
-        if hub_phase != 1 and red in (_lib.SUM, _lib.MEAN):
-            ws_bytes = n_chunks * F * 4
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    # (min / max take the hub list only to schedule those rows first: no workspace)
+    if a.n_hub > 0 and hub_phase != 1 and red in (_lib.SUM, _lib.MEAN):
+        ws_bytes = a.n_chunks * F * 4
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
     sink = timing_sink
     if sink is not None:
         ev0 = torch.cuda.Event(enable_timing=True)
@@ -513,15 +539,11 @@ def _spmm_csr_compressed(rowptr, col, z, reduce, F, n_rows, hub, out, hub_phase)
     a.w_heads, a.head_dim = 1, max(F, 1)
     a.hub_phase = hub_phase
     a.x_format = _lib.X_COMPRESSED
+    _hub_args(a, hub)
     ws, ws_bytes = None, 0
-    if hub is not None and hub[2] > 0:
-        hub_rows, hub_cptr, n_hub, n_chunks = hub
-        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), hub_cptr.data_ptr()
-        a.n_hub, a.n_chunks = n_hub, n_chunks
-        a.hub_threshold, a.hub_chunk = HUB_THRESHOLD, HUB_CHUNK
-        if hub_phase != 1:
-            ws_bytes = n_chunks * F * 4
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=z.device)
+    if a.n_hub > 0 and hub_phase != 1:
+        ws_bytes = a.n_chunks * F * 4
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=z.device)
     sink = timing_sink
     if sink is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -2580,8 +2602,7 @@ AGG_GIVEN = _lib.AGG_GIVEN
 
 def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Tensor, w: Tensor,
                        bias: Optional[Tensor], reduce: str, relu: bool, agg: Tensor, out: Tensor,
-                       hub=None, save_agg=True, hub_threshold: int = None,
-                       hub_chunk: int = None, relu_bits: Optional[Tensor] = None,
+                       hub=None, save_agg=True, relu_bits: Optional[Tensor] = None,
                        mask_bits: Optional[Tensor] = None, row_scale: Optional[Tensor] = None,
                        out_scaled: Optional[Tensor] = None, variant: Optional[int] = None,
                        gather_width: Optional[int] = None,
@@ -2624,11 +2645,11 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
         if ok:
             _check_bits(relu_bits, n_rows, Fo)
             _check_bits(mask_bits, n_rows, Fo)
-            h_rows, h_cptr, n_hub, n_chunks = _hub4(hub)
+            hub = _hub6(hub)
             with _timed({'n_rows': n_rows, 'n_src': x_gather.size(0),
                          'nnz': 0 if given else col.numel(), 'F': F,
                          'reduce': reduce, 'idx_bytes': rowptr.element_size(), 'weighted': False,
-                         'src_scale': False, 'accumulate': False, 'n_hub': n_hub,
+                         'src_scale': False, 'accumulate': False, 'n_hub': hub.n_hub,
                          'fused_gemm': {'Fo': Fo, 'K': 2 * F, 'save_agg': bool(save_agg),
                                         'backward': mask_bits is not None,
                                         'scaled_copy': out_scaled is not None}}, x_gather):
@@ -2638,10 +2659,7 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
                 else:
                     C.sage_layer_fused(
                         rowptr, col, x_gather, x_root, w, bias, REDUCE_IDS[reduce], relu, agg,
-                        out, h_rows, h_cptr, n_hub, n_chunks,
-                        HUB_THRESHOLD if hub_threshold is None else hub_threshold,
-                        HUB_CHUNK if hub_chunk is None else hub_chunk, save_agg, relu_bits,
-                        mask_bits, row_scale, out_scaled)
+                        out, *hub, save_agg, relu_bits, mask_bits, row_scale, out_scaled)
             return out
     lib = _lib.load_lab() if lab else _lib.load()
     xr, w2 = _f32_rows(x_root, 'x_root'), _f32_rows(w, 'weight')
@@ -2672,12 +2690,7 @@ def sage_layer_forward(rowptr: Tensor, col: Tensor, x_gather: Tensor, x_root: Te
     a.w_heads, a.head_dim = 1, F
     if gather_width is not None:
         a.x_format = _lib.X_COMPRESSED
-    if hub is not None and hub[2] > 0:
-        hub_rows, hub_cptr, n_hub, n_chunks = hub
-        a.hub_rows, a.hub_chunk_ptr = hub_rows.data_ptr(), hub_cptr.data_ptr()
-        a.n_hub, a.n_chunks = n_hub, n_chunks
-        a.hub_threshold = HUB_THRESHOLD if hub_threshold is None else hub_threshold
-        a.hub_chunk = HUB_CHUNK if hub_chunk is None else hub_chunk
+    _hub_args(a, hub)
     if bias is not None:
         bias = bias.contiguous()
     _check_bits(relu_bits, n_rows, Fo)

@@ -172,7 +172,7 @@ class EdgeIndex(Tensor):
         self.atomic_backward = True
         csr = self.by_dst()
         if max_in_degree is not None and max_in_degree <= _native.HUB_THRESHOLD:
-            csr._hub = (None, None, 0, 0)  # fan-out bounded: no row needs splitting
+            csr._hub = _native.no_hubs()  # fan-out bounded: no row needs splitting
         return self
 
     def record_stream(self, stream) -> None:
@@ -184,7 +184,7 @@ class EdgeIndex(Tensor):
             if csr is not None:
                 tensors += [csr.ptr, csr.idx, csr.perm, csr._inv_deg]
                 if csr._hub is not None:
-                    tensors += [csr._hub[0], csr._hub[1]]
+                    tensors += [csr._hub.rows, csr._hub.chunk_ptr]
         for t in tensors:
             if isinstance(t, Tensor) and t.is_cuda:
                 t.record_stream(stream)
@@ -205,8 +205,8 @@ class EdgeIndex(Tensor):
         ptr = full.ptr.narrow(0, 0, num_nodes + 1).clamp(max=num_edges)
         csr = CSR(ptr, full.idx.narrow(0, 0, num_edges), full.perm.narrow(0, 0, num_edges),
                   num_nodes, num_nodes)
-        if full._hub is not None and full._hub[2] == 0:
-            csr._hub = (None, None, 0, 0)
+        if full._hub is not None and full._hub.n_hub == 0:  # no long row: nor in a prefix
+            csr._hub = _native.no_hubs(full._hub.threshold, full._hub.chunk)
         out._csr = csr
         return out
 

@@ -101,14 +101,18 @@ def clear_aggregation_cache() -> None:
     _agg0_handles.clear()
 
 
-def _agg0_key(x: Tensor, aggr: str):
+def _agg0_key(handle, x: Tensor, aggr: str):
+    # the settings the stored rows were summed under are those of the handle's plan, whatever the
+    # module says by now.  A handle without a plan (`hub` None) launches without hub rows, which
+    # reads neither setting: it keys as None.
+    hub = handle.hub
     return (x._version, x.data_ptr(), tuple(x.shape), tuple(x.stride()), aggr,
-            _native.HUB_THRESHOLD, _native.HUB_CHUNK)
+            None if hub is None else (hub.threshold, hub.chunk))
 
 
 def _agg0_lookup(handle, x: Tensor, aggr: str) -> Optional[Tensor]:
     hit = getattr(handle, '_agg0', None)
-    if hit is not None and hit[0]() is x and hit[1] == _agg0_key(x, aggr):
+    if hit is not None and hit[0]() is x and hit[1] == _agg0_key(handle, x, aggr):
         return hit[2]
     return None
 
@@ -121,7 +125,7 @@ def _agg0_store(handle, x: Tensor, aggr: str, buf: Tensor) -> None:
         if h is not None and getattr(h, '_agg0', None) is not None and h._agg0[0] is ref:
             h._agg0 = None
 
-    handle._agg0 = (weakref.ref(x, _drop), _agg0_key(x, aggr), buf)
+    handle._agg0 = (weakref.ref(x, _drop), _agg0_key(handle, x, aggr), buf)
     _agg0_handles.add(handle)
 
 

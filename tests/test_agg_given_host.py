@@ -285,7 +285,7 @@ def test_cache_hits_from_the_second_step_on_and_changes_nothing(recorder, monkey
     assert graph.by_dst()._agg0[0]() is x
 
 
-def test_cache_key(recorder):
+def test_cache_key(recorder, monkeypatch):
     from pytorch_geometric_amd import _native
     from pytorch_geometric_amd.nn.models import _fused_sage
     ei = random_graph(N, N, 600, seed=3, skew=True)
@@ -320,13 +320,18 @@ def test_cache_key(recorder):
     want = _step(x.clone(), _Graph(ei, N), params, 'sum')
     assert miss and all(torch.equal(a, b) for a, b in zip(got, want))
     assert not misses(_step, x, graph, params, 'sum')[0]
-    # ... and so are the hub plan's settings
-    old = _native.HUB_THRESHOLD
-    try:
-        _native.HUB_THRESHOLD = old + 1
-        assert misses(_step, x, graph, params, 'sum')[0]
-    finally:
-        _native.HUB_THRESHOLD = old
+    # ... and so are the hub plan's settings: those of the handle's plan (a handle without one
+    # keys as None, so giving it one is a miss as well)
+    fwd = graph.by_dst()
+    fwd.hub = _native.no_hubs()
+    assert misses(_step, x, graph, params, 'sum')[0]
+    assert not misses(_step, x, graph, params, 'sum')[0]
+    fwd.hub = fwd.hub._replace(threshold=fwd.hub.threshold + 1)
+    assert misses(_step, x, graph, params, 'sum')[0]
+    # ... and not the module's: with the handle's plan unchanged, another module value is a hit
+    with monkeypatch.context() as m:
+        m.setattr(_native, 'HUB_THRESHOLD', _native.HUB_THRESHOLD + 1)
+        assert not misses(_step, x, graph, params, 'sum')[0]
     # an input that takes a gradient is never served from, nor stored in, the cache
     xg = x.clone().requires_grad_(True)
     assert misses(_step, xg, graph, params)[0] and misses(_step, xg, graph, params)[0]

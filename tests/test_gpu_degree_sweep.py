@@ -138,7 +138,8 @@ def test_hub_plan_matches_the_cpu(dev, setting, index_dtype):
     ei, n, _ = D.build(0, thr, chunk)
     for deg in D.degrees(ei, n):
         ptr = torch.cat([torch.zeros(1, dtype=torch.long), deg.cumsum(0)]).to(index_dtype).to(dev)
-        rows, cptr, n_hub, n_chunks = _native.hub_plan(ptr, thr, chunk)
+        plan = _native.hub_plan(ptr, thr, chunk)
+        rows, cptr, n_hub, n_chunks = plan.rows, plan.chunk_ptr, plan.n_hub, plan.n_chunks
         want = D.expected_plan(deg, thr, chunk)
         assert (n_hub, n_chunks) == (want['n_hub'], want['n_chunks'])
         assert rows.dtype == index_dtype and cptr.dtype == index_dtype

@@ -126,13 +126,15 @@ def test_hub_plan(dev):
     from pytorch_geometric_amd import _native
     deg = torch.tensor([0, 5, 2049, 1024, 1025, 0, 7000, 3])
     ptr = torch.cat([torch.zeros(1, dtype=torch.long), deg.cumsum(0)]).to(dev)
-    rows, cptr, n_hub, n_chunks = _native.hub_plan(ptr, threshold=1024, chunk=1024)
+    plan = _native.hub_plan(ptr, threshold=1024, chunk=1024)
+    rows, cptr, n_hub, n_chunks = plan.rows, plan.chunk_ptr, plan.n_hub, plan.n_chunks
     assert n_hub == 3 and rows.tolist() == [2, 4, 6]
     assert cptr.tolist() == [0, 3, 5, 12] and n_chunks == 12
     assert _native.hub_plan(ptr, threshold=10_000, chunk=1024)[2] == 0
     big = torch.full((3000, ), 40, dtype=torch.int32)  # more hubs than one scan tile
     ptr = torch.cat([torch.zeros(1, dtype=torch.int32), big.cumsum(0).int()]).to(dev)
-    rows, cptr, n_hub, n_chunks = _native.hub_plan(ptr, threshold=16, chunk=16)
+    plan = _native.hub_plan(ptr, threshold=16, chunk=16)
+    rows, cptr, n_hub, n_chunks = plan.rows, plan.chunk_ptr, plan.n_hub, plan.n_chunks
     assert n_hub == 3000 and n_chunks == 9000
     assert cptr.tolist() == list(range(0, 9001, 3))
 
