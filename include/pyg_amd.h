@@ -1125,6 +1125,91 @@ PYGAMD_API int pygamd_film_backward_src(const pygamd_csr* g, const void* edge_id
                                         int64_t R, float* grad_h, int64_t ld_gh, void* workspace,
                                         size_t workspace_bytes, void* stream);
 
+/* ---- RGATConv's additive relational attention (rgat_conv.py:373-505) ------------------------------
+ * The reference's message gathers one weight matrix per edge (rgat_conv.py:397-399:
+ * index_select(w, 0, edge_type) is [E, in, H C]), runs two bmm over it, materialises outi and outj
+ * as [E, H C] and makes several [E, H] passes for the softmax (rgat_conv.py:401-437).  With dim = 1
+ * (additive mode forces it, rgat_conv.py:226-229) every per-edge operand is node-level, W = H C:
+ *   P  = x @ [W_0 | ... | W_{R-1}]           [N, R W]   outj[e] = P[j, rW:(r+1)W], outi[e] = P[i, ..]
+ *   QI[:, r] = P[:, r] @ q,  KJ[:, r] = P[:, r] @ k   [N, R H]   (rgat_conv.py:401-402; q and k are
+ *       full [W, H] matrices that mix heads)
+ *   B  = edge_attr @ (W_e^T e)               [E, H]     alpha_edge of rgat_conv.py:405-416
+ *   s[e,h] = leaky_relu(QI[i,r,h] + KJ[j,r,h] (+ B[e,h]))           (rgat_conv.py:418-423)
+ *   alpha  = softmax of s over ALL edges into i ("across-relation", rgat_conv.py:436-437)
+ *   out[i,h,:] = sum_e alpha[e,h] * P[j,r,h,:]                      (rgat_conv.py:500-502)
+ * or over those of relation r only ("within-relation", rgat_conv.py:430-435).  The degree factors
+ * of mod = 'scaled' / 'f-scaled' (rgat_conv.py:459-471, 488-492) depend on the destination only and
+ * are the caller's node-level code on `out`.
+ *
+ * pygamd_rgat_forward: ONE launch over the by-destination handle g of all edges, one 64-lane wave
+ *   per row or per chunk of a long row.  rel is int32 [nnz] in SLOT order, in [0, R): the caller's
+ *   to guarantee, the kernels check no index.  The lane keeps QI[i, r, h] of the current relation
+ *   in a register and loads it again only when a slot's relation differs from the one before: any
+ *   in-row order is correct, a row grouped by relation (a stable by-destination sort of edges
+ *   pre-sorted by relation) reloads once per relation present.  Per slot one scalar of KJ, the
+ *   optional b [nnz, H] (slot order, NULL: none) and ONE gathered W row of P; online softmax,
+ *   non-finite rules (a -inf score has weight 0; a row whose every score is -inf is NaN in its own
+ *   (row, head); an empty row is 0), the 1e-16 and the in-order merge of a long row's chunks as
+ *   pygamd_han_forward.  Writes out [n_rows, W] and alpha [nnz, H] in slot order.  p, qi and kj
+ *   have row strides (floats): three tensors, or the column blocks of one packed [P | QI | KJ].
+ * pygamd_rgat_backward_dst: ONE launch over the same rows: d alpha = <g[i,h], P[j,r,h]>,
+ *   D = <g[i,h], out[i,h]>, grad_s [nnz, H] = alpha (d alpha - D) * leaky_relu'(pre), the slope
+ *   where pre <= 0 — this is also the gradient of b.  No workspace.
+ * pygamd_rgat_backward_src: ONE launch over the (relation, node) pair rows of a pair handle g: row
+ *   p holds the slots of relation pair_rel[p] at node pair_node[p] (index arrays at g's index
+ *   type), col = the other endpoint, slot_map = pair slot -> by-destination slot.  Writes
+ *   grad_a[node, r H:(r+1) H] = sum grad_s and, unless grad_p is NULL,
+ *   grad_p[node, r W:(r+1) W] = sum alpha * grad_out[col].  On the (relation, source) rows that is
+ *   grad_KJ and grad_P; on the (relation, destination) rows with grad_p = NULL (alpha and grad_out
+ *   are then not read) it is grad_QI.  Blocks of pairs that do not occur are not written: the
+ *   caller zero-fills the planes once.  grad_a and grad_p have row strides, so the three launches
+ *   of a backward write ONE gradient plane of the packed plane's shape.
+ * pygamd_rgat_pair_scalar: the within-relation normaliser, ONE scalar launch over the (relation,
+ *   destination) pair rows (pair_rel, pair_dst, slot_map as above, col = the sources), every pair
+ *   row whole.  alpha == NULL (forward): writes pair_stats [n_dst, R, 2H] = the pair's (maximum [H],
+ *   1 / (sum + 1e-16) [H]); pairs that do not occur are not written and never read.  Handed to
+ *   pygamd_rgat_forward as pair_stats (NULL there: across-relation), a slot's weight is
+ *   exp(s - m_pair) / (l_pair + 1e-16): no rescaling, chunk partials merge by addition.  alpha
+ *   given (backward): grad_s holds the raw d alpha that pygamd_rgat_backward_dst writes with
+ *   within = 1; it becomes alpha (d alpha - D_pair) * leaky_relu'(pre) in place, D_pair = sum alpha
+ *   * d alpha over the pair (rgat_conv.py:430-435 differentiated), and grad_qi[i, r H:(r+1) H] =
+ *   sum grad_s — this launch then stands in for pygamd_rgat_backward_src on those rows.
+ * Launches: across-relation ONE forward, within-relation two; three backward in either mode.
+ * Envelope: H C <= 512, H <= 64, otherwise status 2; no limit on R.  There is no workspace query
+ * of its own: forward and backward_src take a workspace of pygamd_han_workspace_bytes(n_chunks, H,
+ * C) bytes for the launch's handle (a chunk's partial row and its 2 H statistics, the same layout)
+ * and return status 3 on a smaller one.
+ * No float atomics, every grid a function of (n_rows, n_chunks) only: bitwise reproducible.
+ * Status 1 / 2 / 3 before any device work; n_rows == 0 returns 0.                                   */
+PYGAMD_API int pygamd_rgat_supported(int64_t H, int64_t C);
+PYGAMD_API int pygamd_rgat_forward(const pygamd_csr* g, const int32_t* rel, const float* p,
+                                   int64_t ld_p, const float* qi, int64_t ld_qi, const float* kj,
+                                   int64_t ld_kj, const float* b, const float* pair_stats,
+                                   int64_t n_src, int64_t H, int64_t C, int64_t R, float slope,
+                                   float* alpha, float* out, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_rgat_backward_dst(const pygamd_csr* g, const int32_t* rel, const float* p,
+                                        int64_t ld_p, const float* qi, int64_t ld_qi,
+                                        const float* kj, int64_t ld_kj, const float* b,
+                                        const float* alpha, const float* grad_out,
+                                        const float* out, int64_t n_src, int64_t H, int64_t C,
+                                        int64_t R, float slope, int within, float* grad_s,
+                                        void* stream);
+PYGAMD_API int pygamd_rgat_pair_scalar(const pygamd_csr* g, const void* slot_map,
+                                       const void* pair_rel, const void* pair_dst,
+                                       const float* qi, int64_t ld_qi, const float* kj,
+                                       int64_t ld_kj, const float* b, const float* alpha,
+                                       int64_t n_src, int64_t H, int64_t R, float slope,
+                                       float* grad_s, float* pair_stats, float* grad_qi,
+                                       int64_t ld_gqi, void* stream);
+PYGAMD_API int pygamd_rgat_backward_src(const pygamd_csr* g, const void* slot_map,
+                                        const void* pair_rel, const void* pair_node,
+                                        const float* alpha, const float* grad_s,
+                                        const float* grad_out, int64_t n_other, int64_t H,
+                                        int64_t C, int64_t R, float* grad_a, int64_t ld_ga,
+                                        float* grad_p, int64_t ld_gp, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+
 /* ---- mixture messages, aggregate first (gmm_conv.py:154-165, nn_conv.py:119-122) -----------------
  * GMMConv's message is m_e = sum_k w_k(e_attr) (x_j G_k) with Gaussian weights w_k, NNConv's is
  * m_e = x_j reshape(nn(e_attr)), an affine map of the hidden edge features.  Both are a per-edge

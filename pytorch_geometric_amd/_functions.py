@@ -1034,6 +1034,49 @@ class FiLMAggregateFunction(Function):
         return grads + (grad_out if need[2] else None, None, None)
 
 
+class RGATAggregateFunction(Function):
+    """RGATConv's additive message with the softmax across all relations of a destination, or
+    (``within``) within every relation (rgat_conv.py:397-437, 500-502), and the 'add' aggregation
+    in ONE pass over the by-destination slots of all edges (``within``: after one scalar launch
+    over the ``(relation, destination)`` pair rows):
+
+        out[i, h] = sum_k softmax_k(leaky_relu(QI[i, r, h] + KJ[j, r, h] + B[e, h])) * P[j, r, h]
+
+    with ``r`` the relation of slot ``k``'s edge: ``p = P [N, R * H * C]``, ``qi`` / ``kj [N, R *
+    H]`` — or ``qi = kj = None`` and ``p`` the packed ``[N, R (H C + 2 H)] = [P | QI | KJ]``, whose
+    gradient is then ONE plane of that shape.  ``b [E, H]`` (or None) is the per-edge score bias
+    in the CALLER's edge order.  ``forms`` is a :class:`_onepass.RgatForms`.  Returns ``(out [n_dst,
+    H * C], alpha [E, H])``, ``alpha`` in the caller's edge order and not differentiable.  Saved:
+    the inputs, ``alpha`` and ``out`` — nothing of size ``E x H*C``.  The backward is one pass over
+    the same rows and one over each of the two pair forms (csrc/rgat.hip)."""
+
+    @staticmethod
+    def forward(ctx, p: Tensor, qi: Optional[Tensor], kj: Optional[Tensor], b: Optional[Tensor],
+                forms, H: int, C: int, slope: float, within: bool = False):
+        if (qi is None) != (kj is None):
+            raise ValueError("'qi' and 'kj' are given together or not at all")
+        if b is not None and forms.perm is not None:
+            b = b.index_select(0, forms.perm)   # slot order
+        alpha, out = _onepass.rgat_forward(forms, p, qi, kj, b, H, C, slope, bool(within))
+        ctx.save_for_backward(p, qi, kj, b, alpha, out)
+        ctx.forms, ctx.dims, ctx.within = forms, (int(H), int(C), float(slope)), bool(within)
+        alpha_e = alpha if forms.inv is None else alpha.index_select(0, forms.inv)
+        ctx.mark_non_differentiable(alpha_e)
+        return out, alpha_e
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor, _grad_alpha):
+        p, qi, kj, b, alpha, out = ctx.saved_tensors
+        H, C, slope = ctx.dims
+        g_p, g_qi, g_kj, g_b = _onepass.rgat_backward(
+            ctx.forms, p, qi, kj, b, alpha, out, grad_out.contiguous(), H, C, slope,
+            within=ctx.within, want_b=b is not None and ctx.needs_input_grad[3])
+        if g_b is not None and ctx.forms.inv is not None:
+            g_b = g_b.index_select(0, ctx.forms.inv)
+        return g_p, g_qi, g_kj, g_b, None, None, None, None, None
+
+
 class MixtureConvFunction(Function):
     """The propagate step of a layer whose message is a per-edge mixture of ``K`` linear maps —
     GMMConv (gmm_conv.py:154-165) and NNConv (nn_conv.py:119-122) — aggregate first:

@@ -316,6 +316,18 @@ SIGNATURES = {
     'pygamd_film_backward_src': (c_int, [_G, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P,
                                          c_int64, c_int, c_int64, c_int64, c_int64, _P, c_int64,
                                          _P, c_size_t, _P]),
+    'pygamd_rgat_supported': (c_int, [c_int64, c_int64]),
+    'pygamd_rgat_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P,
+                                    c_int64, c_int64, c_int64, c_int64, c_float, _P, _P, _P,
+                                    c_size_t, _P]),
+    'pygamd_rgat_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P,
+                                         _P, _P, c_int64, c_int64, c_int64, c_int64, c_float,
+                                         c_int, _P, _P]),
+    'pygamd_rgat_pair_scalar': (c_int, [_G, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P,
+                                        c_int64, c_int64, c_int64, c_float, _P, _P, _P, c_int64,
+                                        _P]),
+    'pygamd_rgat_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
+                                         c_int64, _P, c_int64, _P, c_int64, _P, c_size_t, _P]),
     'pygamd_mixture_supported': (c_int, [c_int64, c_int64]),
     'pygamd_mixture_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     'pygamd_mixture_expand': (c_int, [_G, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, _P, _P,

@@ -2430,6 +2430,198 @@ def film_backward_src(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tenso
     return out
 
 
+# ---- RGATConv's additive relational attention (csrc/rgat.hip) --------------------------------------
+def rgat_supported(H: int, C: int) -> bool:
+    """The one-pass kernels serve this head layout (H * C <= 512, H <= 64)."""
+    return bool(_lib.load().pygamd_rgat_supported(int(H), int(C)))
+
+
+# (no workspace query of its own: the rgat entry points take han's workspace, include/pyg_amd.h)
+def _rgat_planes(p: Tensor, qi: Tensor, kj: Tensor, R: int, H: int, C: int):
+    """``P [n, R * H * C]``, ``QI`` and ``KJ [n, R * H]`` with their row strides: three tensors or
+    the column blocks of one packed plane"""
+    return (_strided_rows(p, 'p', R * H * C), _strided_rows(qi, 'qi', R * H),
+            _strided_rows(kj, 'kj', R * H))
+
+
+def _rgat_bias(b: Optional[Tensor], E: int, H: int) -> Optional[Tensor]:
+    if b is None:
+        return None
+    if b.dtype != torch.float32 or tuple(b.shape) != (E, H):
+        raise ValueError(f"'b' must be a float32 [{E}, {H}] tensor (got {b.dtype} "
+                         f"{tuple(b.shape)})")
+    return b.contiguous()
+
+
+def _rgat_slots(rel: Tensor, b: Optional[Tensor], E: int, H: int):
+    return _film_rel(rel, E), _rgat_bias(b, E, H)
+
+
+def rgat_forward(rowptr: Tensor, col: Tensor, rel: Tensor, p: Tensor, qi: Tensor, kj: Tensor,
+                 b: Optional[Tensor], R: int, H: int, C: int, slope: float, *,
+                 pair_stats: Optional[Tensor] = None, hub=None):
+    """``(alpha [nnz, H] in slot order, out [n_rows, H * C])`` of RGAT's additive attention on a
+    by-destination handle: ``rel`` (int32, per SLOT, in ``[0, R)``: the caller's to guarantee, as
+    the range of ``col``), ``p [n_src, R * H * C]``, ``qi [>= n_rows, R * H]``, ``kj [n_src, R *
+    H]`` (column blocks of wider tensors are read in place), ``b [nnz, H]`` the optional score
+    bias in slot order.  ``pair_stats`` None: the softmax across all relations of a destination;
+    the ``[n_rows, R, 2 H]`` of :func:`rgat_pair_stats`: within every relation."""
+    _require_device(rowptr, col, rel, p, qi, kj, b, pair_stats)
+    lib = _lib.load()
+    R, H, C = int(R), int(H), int(C)
+    p, qi, kj = _rgat_planes(p, qi, kj, R, H, C)
+    n_rows, E = rowptr.numel() - 1, col.numel()
+    if qi.size(0) < n_rows or kj.size(0) != p.size(0):
+        raise ValueError(f"'qi' needs at least {n_rows} rows and 'kj' the rows of 'p'")
+    rel, b = _rgat_slots(rel, b, E, H)
+    if pair_stats is not None and (pair_stats.dtype != torch.float32
+                                   or not pair_stats.is_contiguous()
+                                   or pair_stats.numel() != n_rows * R * 2 * H):
+        raise ValueError(f"'pair_stats' must be a contiguous float32 [{n_rows}, {R}, {2 * H}]")
+    alpha = torch.empty(E, H, dtype=torch.float32, device=p.device)
+    out = torch.empty(n_rows, H * C, dtype=torch.float32, device=p.device)
+    if E == 0 or n_rows == 0:  # no edges: every row is empty
+        return alpha, out.zero_()
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_han_workspace_bytes, (g.n_chunks, H, C), p.device,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'rgat', 'op': 'forward', 'n_rows': n_rows, 'E': E, 'H': H, 'C': C,
+                 'R': R, 'ld': _ld(p), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, p):
+        check(lib.pygamd_rgat_forward(
+            ctypes.byref(g), _p(rel), _p(p), _ld(p), _p(qi), _ld(qi), _p(kj), _ld(kj), _p(b),
+            _p(pair_stats), p.size(0), H, C, R, float(slope), _p(alpha), _p(out), _p(ws),
+            ws_bytes, _stream(p)), 'rgat_forward')
+    return alpha, out
+
+
+def rgat_backward_dst(rowptr: Tensor, col: Tensor, rel: Tensor, p: Tensor, qi: Tensor, kj: Tensor,
+                      b: Optional[Tensor], alpha: Tensor, grad_out: Tensor, out: Tensor, R: int,
+                      H: int, C: int, slope: float, *, within: bool = False, hub=None) -> Tensor:
+    """``grad_s [nnz, H]`` in slot order (also the gradient of ``b``) on the forward's handle;
+    ``within``: the raw ``d alpha`` that :func:`rgat_pair_finish` turns into ``grad_s``."""
+    _require_device(rowptr, col, rel, p, qi, kj, b, alpha, grad_out, out)
+    lib = _lib.load()
+    R, H, C = int(R), int(H), int(C)
+    p, qi, kj = _rgat_planes(p, qi, kj, R, H, C)
+    n_rows, E = rowptr.numel() - 1, col.numel()
+    grad_out, out = _dense_rows(grad_out, 'grad_out', H * C), _dense_rows(out, 'out', H * C)
+    if (qi.size(0) < n_rows or kj.size(0) != p.size(0) or out.size(0) != n_rows
+            or grad_out.size(0) != n_rows or tuple(alpha.shape) != (E, H)):
+        raise ValueError(f"'qi', 'out' and 'grad_out' need the {n_rows} rows of the handle, "
+                         f"'alpha' one row per slot")
+    rel, b = _rgat_slots(rel, b, E, H)
+    alpha = alpha.contiguous()
+    grad_s = torch.empty_like(alpha)
+    if E == 0 or n_rows == 0:
+        return grad_s
+    g = _csr(rowptr, col, n_rows, hub)
+    with _timed({'kind': 'rgat', 'op': 'backward_dst', 'n_rows': n_rows, 'E': E, 'H': H, 'C': C,
+                 'R': R, 'ld': _ld(p), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, p):
+        check(lib.pygamd_rgat_backward_dst(
+            ctypes.byref(g), _p(rel), _p(p), _ld(p), _p(qi), _ld(qi), _p(kj), _ld(kj), _p(b),
+            _p(alpha), _p(grad_out), _p(out), p.size(0), H, C, R, float(slope),
+            int(bool(within)), _p(grad_s), _stream(p)), 'rgat_backward_dst')
+    return grad_s
+
+
+def _rgat_pair_call(rowptr, col, slot_map, pair_rel, pair_dst, qi, kj, b, alpha, R, H, slope,
+                    grad_s, stats, grad_qi, op):
+    _require_device(rowptr, col, slot_map, pair_rel, pair_dst, qi, kj, b, alpha, grad_s, stats,
+                    grad_qi)
+    lib = _lib.load()
+    R, H = int(R), int(H)
+    n_rows, E = rowptr.numel() - 1, col.numel()
+    qi, kj = _strided_rows(qi, 'qi', R * H), _strided_rows(kj, 'kj', R * H)
+    pair_rel, pair_dst = _film_pairs(rowptr, pair_rel, pair_dst)
+    if slot_map.dtype != rowptr.dtype or slot_map.numel() != E:
+        raise ValueError("'slot_map' must have the index dtype and one entry per slot")
+    slot_map = slot_map.contiguous()
+    b = _rgat_bias(b, E, H)
+    if n_rows == 0 or E == 0:
+        return
+    g = _csr(rowptr, col, n_rows, None)   # (every pair row whole)
+    with _timed({'kind': 'rgat', 'op': op, 'n_rows': n_rows, 'E': E, 'H': H, 'R': R}, qi):
+        check(lib.pygamd_rgat_pair_scalar(
+            ctypes.byref(g), _p(slot_map), _p(pair_rel), _p(pair_dst), _p(qi), _ld(qi), _p(kj),
+            _ld(kj), _p(b), _p(alpha), kj.size(0), H, R, float(slope), _p(grad_s), _p(stats),
+            _p(grad_qi), 0 if grad_qi is None else _ld(grad_qi), _stream(qi)), 'rgat_' + op)
+
+
+def rgat_pair_stats(rowptr: Tensor, col: Tensor, slot_map: Tensor, pair_rel: Tensor,
+                    pair_dst: Tensor, qi: Tensor, kj: Tensor, b: Optional[Tensor], n_dst: int,
+                    R: int, H: int, slope: float) -> Tensor:
+    """The within-relation normaliser ``[n_dst, R, 2 H]`` = per ``(destination, relation)`` pair
+    the (maximum ``[H]``, ``1 / (sum + 1e-16) [H]``) of its scores, from one scalar launch over the
+    ``(relation, destination)`` pair rows; pairs that do not occur stay uninitialised (and are
+    never read)."""
+    stats = torch.empty(int(n_dst), int(R), 2 * int(H), dtype=torch.float32, device=qi.device)
+    if qi.size(0) < n_dst:
+        raise ValueError(f"'qi' needs at least {n_dst} rows")
+    _rgat_pair_call(rowptr, col, slot_map, pair_rel, pair_dst, qi, kj, b, None, R, H, slope, None,
+                    stats, None, 'pair_stats')
+    return stats
+
+
+def rgat_pair_finish(rowptr: Tensor, col: Tensor, slot_map: Tensor, pair_rel: Tensor,
+                     pair_dst: Tensor, qi: Tensor, kj: Tensor, b: Optional[Tensor], alpha: Tensor,
+                     grad_s: Tensor, R: int, H: int, slope: float, grad_qi: Tensor) -> None:
+    """Within-relation backward over the ``(relation, destination)`` pair rows: ``grad_s`` (the
+    raw ``d alpha`` of :func:`rgat_backward_dst` with ``within``) becomes ``alpha (d alpha - D) *
+    leaky_relu'`` in place, ``D`` the pair's ``sum alpha * d alpha``, and ``grad_qi[i, r * H:(r +
+    1) * H] = sum grad_s`` (the caller's zero-filled plane, or a column block of one)."""
+    E = col.numel()
+    if (tuple(alpha.shape) != (E, H) or tuple(grad_s.shape) != (E, H)
+            or not alpha.is_contiguous() or not grad_s.is_contiguous()):
+        raise ValueError(f"'alpha' and 'grad_s' must be contiguous [{E}, {H}]")
+    grad_qi = _film_plane(grad_qi, grad_qi.size(0), int(R) * int(H), 'grad_qi')
+    if grad_qi.size(0) != qi.size(0):
+        raise ValueError("'grad_qi' needs the rows of 'qi'")
+    _rgat_pair_call(rowptr, col, slot_map, pair_rel, pair_dst, qi, kj, b, alpha, R, H, slope,
+                    grad_s, None, grad_qi, 'pair_finish')
+
+
+def rgat_backward_src(rowptr: Tensor, col: Tensor, slot_map: Tensor, pair_rel: Tensor,
+                      pair_node: Tensor, alpha: Tensor, grad_s: Tensor,
+                      grad_out: Optional[Tensor], R: int, H: int, C: int, grad_a: Tensor,
+                      grad_p: Optional[Tensor] = None, *, hub=None) -> None:
+    """Over the ``(relation, node)`` pair rows of a pair handle (``col`` = the other endpoint,
+    ``slot_map`` = pair slot -> by-destination slot): ``grad_a[node, r * H:(r + 1) * H] = sum
+    grad_s`` and, with ``grad_p``, ``grad_p[node, r * H * C:(r + 1) * H * C] = sum alpha *
+    grad_out[col]``.  Both are the caller's zero-filled planes, or column blocks of one: blocks of
+    pairs that do not occur are left alone."""
+    _require_device(rowptr, col, slot_map, pair_rel, pair_node, alpha, grad_s, grad_out, grad_a,
+                    grad_p)
+    lib = _lib.load()
+    R, H, C = int(R), int(H), int(C)
+    n_rows, E = rowptr.numel() - 1, col.numel()
+    pair_rel, pair_node = _film_pairs(rowptr, pair_rel, pair_node)
+    if slot_map.dtype != rowptr.dtype or slot_map.numel() != E:
+        raise ValueError("'slot_map' must have the index dtype and one entry per slot")
+    slot_map = slot_map.contiguous()
+    if tuple(alpha.shape) != (E, H) or tuple(grad_s.shape) != (E, H):
+        raise ValueError(f"'alpha' and 'grad_s' must be [{E}, {H}]")
+    alpha, grad_s = alpha.contiguous(), grad_s.contiguous()
+    grad_a = _film_plane(grad_a, grad_a.size(0), R * H, 'grad_a')
+    n_other = 0
+    if grad_p is not None:
+        grad_p = _film_plane(grad_p, grad_a.size(0), R * H * C, 'grad_p')
+        grad_out = _dense_rows(grad_out, 'grad_out', H * C)
+        n_other = grad_out.size(0)
+    if n_rows == 0 or E == 0:
+        return
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_han_workspace_bytes, (g.n_chunks, H, C), alpha.device,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'rgat', 'op': 'backward_src', 'n_rows': n_rows, 'E': E, 'H': H, 'C': C,
+                 'R': R, 'rows': grad_p is not None, 'n_hub': g.n_hub, 'n_chunks': g.n_chunks},
+                alpha):
+        check(lib.pygamd_rgat_backward_src(
+            ctypes.byref(g), _p(slot_map), _p(pair_rel), _p(pair_node), _p(alpha), _p(grad_s),
+            _p(grad_out) if grad_p is not None else None, n_other, H, C, R, _p(grad_a),
+            _ld(grad_a), _p(grad_p), 0 if grad_p is None else _ld(grad_p), _p(ws), ws_bytes,
+            _stream(alpha)), 'rgat_backward_src')
+
+
 # ---- mixture messages, aggregate first (csrc/mixture.hip) ------------------------------------------
 def mixture_supported(F: int, K: int) -> bool:
     """The kernels serve rows of ``1 <= F <= 512`` floats and ``1 <= K <= 256`` coefficients per

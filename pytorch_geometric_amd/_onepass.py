@@ -464,6 +464,130 @@ def film_backward(forms, h, g, grad_out, *, relu=True, want_h=True, want_g=True)
     return (plane, None) if packed else (out_h, out_g)
 
 
+class RgatForms:
+    """What the RGAT launches walk: the by-destination form of ALL edges (``fwd``), the int32
+    relation of every SLOT (``rel``, in ``[0, R)``), ``perm`` = slot -> the caller's edge and
+    ``inv`` = the caller's edge -> slot (both int64; None: the slots are the edges), the float
+    in-degree ``deg [n_dst]`` and, built when the backward first asks, the ``(relation,
+    destination)`` and ``(relation, source)`` pair forms of the SLOTS: their ``edge_id`` is the map
+    from a pair slot to its by-destination slot."""
+
+    def __init__(self, fwd, rel, perm, R, n_src):
+        self.fwd, self.rel, self.perm = fwd, rel, perm
+        self.R, self.n_src = int(R), int(n_src)
+
+    @classmethod
+    def of_edges(cls, src, dst, et, n_src, n_dst, R):
+        """The forms of an edge list with relations ``et`` (int64, in ``[0, R)``: checked by the
+        caller).  The edges are sorted by relation first: the stable by-destination sort then
+        leaves every row grouped by relation."""
+        from .edge_index import EdgeIndex
+        if src.numel() > 0:
+            lo, hi = _native.index_minmax(src)
+            lo_d, hi_d = _native.index_minmax(dst)
+            if lo < 0 or hi >= n_src or lo_d < 0 or hi_d >= n_dst:
+                raise IndexError(f"'edge_index' must point into [0, {n_src}) x [0, {n_dst}) "
+                                 f"(got sources in [{lo}, {hi}], destinations in [{lo_d}, {hi_d}])")
+        _, first = _native.index_sort(et, max_value=R - 1)
+        fwd = EdgeIndex(torch.stack([src[first], dst[first]]), (n_src, n_dst)).by_dst()
+        perm = first[fwd.perm.to(torch.int64)]
+        return cls(fwd, et[perm].to(torch.int32), perm, R, n_src)
+
+    @classmethod
+    def of_csr(cls, rowptr, col, rel, n_src, R):
+        return cls(_Form(rowptr, col), rel, None, R, n_src)
+
+    @functools.cached_property
+    def inv(self):
+        if self.perm is None:
+            return None
+        inv = torch.empty_like(self.perm)
+        inv[self.perm] = torch.arange(self.perm.numel(), device=self.perm.device)
+        return inv
+
+    @functools.cached_property
+    def deg(self):
+        ptr = self.fwd.ptr
+        return (ptr[1:] - ptr[:-1]).to(torch.float32)
+
+    @functools.cached_property
+    def pairs(self):
+        """``(by (relation, destination), by (relation, source))`` with their slot maps"""
+        ptr, col = self.fwd.ptr, self.fwd.idx
+        dst = _native.ptr2index(ptr, col.numel()).to(torch.int64)
+        src = col.to(torch.int64)
+        n_dst = self.fwd.n_rows
+        pairs = (_PairForm(dst, src, self.rel, n_dst, self.n_src, self.R),
+                 _PairForm(src, dst, self.rel, self.n_src, n_dst, self.R))
+        for form in pairs:
+            form.slot_map = form.edge_id.to(form.ptr.dtype).contiguous()
+        return pairs
+
+
+def rgat_split(p, qi, kj, R, H, C):
+    """``(P, QI, KJ)`` as the kernels read them: three tensors, or (``qi`` None) the column blocks
+    of the packed ``p = [P | QI | KJ] [N, R (H C + 2 H)]`` in place"""
+    if qi is not None:
+        return p, qi, kj
+    w, h = R * H * C, R * H
+    if p.dim() != 2 or p.size(1) != w + 2 * h:
+        raise ValueError(f"the packed plane must be [N, {w + 2 * h}] (got {tuple(p.shape)})")
+    return p[:, :w], p[:, w:w + h], p[:, w + h:]
+
+
+def rgat_forward(forms, p, qi, kj, b, H, C, slope, within=False):
+    """``(alpha [E, H] in SLOT order, out [n_dst, H * C])`` of :func:`_native.rgat_forward` on
+    ``forms``; ``b`` is in slot order.  ``within``: one scalar launch over the ``(relation,
+    destination)`` pair rows first (the pairs' normalisers).  The rows the handle's indices reach
+    are checked here, the kernels check none."""
+    P, QI, KJ = rgat_split(p, qi, kj, forms.R, H, C)
+    fwd = forms.fwd
+    if P.size(0) < forms.n_src or QI.size(0) < fwd.n_rows:
+        raise ValueError(f"the planes need {forms.n_src} source and {fwd.n_rows} destination rows")
+    stats = None
+    if within and fwd.idx.numel() > 0:
+        by_dst = forms.pairs[0]
+        stats = _native.rgat_pair_stats(by_dst.ptr, by_dst.idx, by_dst.slot_map, by_dst.pair_rel,
+                                        by_dst.pair_node, QI, KJ, b, fwd.n_rows, forms.R, H, slope)
+    return _native.rgat_forward(fwd.ptr, fwd.idx, forms.rel, P, QI, KJ, b, forms.R, H, C, slope,
+                                pair_stats=stats, hub=fwd.hub)
+
+
+def rgat_backward(forms, p, qi, kj, b, alpha, out, grad_out, H, C, slope, *, within=False,
+                  want_b=False):
+    """``(grad_p, grad_qi, grad_kj, grad_s)``: one launch over the forward's rows (``grad_s``,
+    which is the gradient of ``b`` in slot order; None unless ``want_b``), one over the ``(relation,
+    destination)`` pair rows (``grad_QI``; ``within``: the scalar launch that also finishes
+    ``grad_s`` with the pair's sum) and one over the ``(relation, source)`` pair rows (``grad_P``,
+    ``grad_KJ``), all into zero-filled planes.  With the packed ``p`` (``qi`` None) they write the
+    column blocks of ONE plane of its shape, which is ``grad_p``."""
+    R = forms.R
+    P, QI, KJ = rgat_split(p, qi, kj, R, H, C)
+    fwd = forms.fwd
+    grad_s = _native.rgat_backward_dst(fwd.ptr, fwd.idx, forms.rel, P, QI, KJ, b, alpha, grad_out,
+                                       out, R, H, C, slope, within=within, hub=fwd.hub)
+    if qi is None:
+        plane = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        g_p, g_qi, g_kj = rgat_split(plane, None, None, R, H, C)
+    else:
+        plane = None
+        g_p, g_qi, g_kj = (torch.zeros_like(t, memory_format=torch.contiguous_format)
+                           for t in (p, qi, kj))
+    by_dst, by_src = forms.pairs
+    if within:
+        _native.rgat_pair_finish(by_dst.ptr, by_dst.idx, by_dst.slot_map, by_dst.pair_rel,
+                                 by_dst.pair_node, QI, KJ, b, alpha, grad_s, R, H, slope, g_qi)
+    else:
+        _native.rgat_backward_src(by_dst.ptr, by_dst.idx, by_dst.slot_map, by_dst.pair_rel,
+                                  by_dst.pair_node, alpha, grad_s, None, R, H, C, g_qi, None,
+                                  hub=by_dst.hub)
+    _native.rgat_backward_src(by_src.ptr, by_src.idx, by_src.slot_map, by_src.pair_rel,
+                              by_src.pair_node, alpha, grad_s, grad_out, R, H, C, g_kj, g_p,
+                              hub=by_src.hub)
+    grad_b = grad_s if want_b else None
+    return (plane, None, None, grad_b) if qi is None else (g_p, g_qi, g_kj, grad_b)
+
+
 def _transposed_product(a, b):
     """``a.T @ b`` (``a [n, p]``, ``b [n, q]``) on the package's weight-gradient GEMM from the
     row count up at which :func:`_functions.linear` takes the own kernels"""

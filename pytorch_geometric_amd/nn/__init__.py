@@ -2,7 +2,7 @@ from .aggr import (Aggregation, DegreeScalerAggregation, FusedAggregation, MaxAg
                    MinAggregation, MulAggregation, MultiAggregation, PowerMeanAggregation,
                    SoftmaxAggregation, StdAggregation, SumAggregation, VarAggregation)
 from .conv import (CGConv, FastRGCNConv, FiLMConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HANConv, HeteroConv, HGTConv,
-                   GENConv, GMMConv, MessagePassing, NNConv, PNAConv, ResGatedGraphConv, RGCNConv, SAGEConv, TransformerConv,
+                   GENConv, GMMConv, MessagePassing, NNConv, PNAConv, ResGatedGraphConv, RGATConv, RGCNConv, SAGEConv, TransformerConv,
                    gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
@@ -15,6 +15,6 @@ __all__ = [
     'MultiAggregation', 'SoftmaxAggregation', 'PowerMeanAggregation', 'MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv', 'GraphConv', 'Linear', 'HeteroLinear',
     'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
     'PNAConv', 'DegreeScalerAggregation', 'GENConv', 'MessageNorm', 'DeepGCNLayer',
-    'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv', 'FiLMConv',
+    'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv', 'FiLMConv', 'RGATConv',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
 ]

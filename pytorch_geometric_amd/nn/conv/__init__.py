@@ -17,8 +17,9 @@ from .gmm_conv import GMMConv
 from .nn_conv import NNConv
 from .cg_conv import CGConv
 from .film_conv import FiLMConv
+from .rgat_conv import RGATConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
            'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv',
-           'FiLMConv']
+           'FiLMConv', 'RGATConv']

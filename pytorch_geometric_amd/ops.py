@@ -59,6 +59,9 @@ Operators (all index tensors int32 / int64, features float32):
 ``film_aggregate``          ``(Tensor h, Tensor? g, Tensor? residual, Tensor rowptr, Tensor col,
                             Tensor? edge_id, Tensor rel, Tensor? scale, int num_relations,
                             bool relu) -> Tensor``
+``rgat_aggregate``          ``(Tensor p, Tensor? qi, Tensor? kj, Tensor? b, Tensor rowptr,
+                            Tensor col, Tensor rel, int num_relations, int heads,
+                            float negative_slope, bool within) -> (Tensor, Tensor)``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -1074,6 +1077,88 @@ def _film_bwd(ctx, grad):
 register_autograd('pyg_amd::film_aggregate', _film_bwd, setup_context=_film_setup)
 
 
+# ---- RGATConv's additive relational attention on a CSR pair (rows = destinations) ---------------------
+def _rgat_dims(p, qi, num_relations, heads):
+    R, H = int(num_relations), int(heads)
+    width = p.size(1) // R if qi is not None else p.size(1) // R - 2 * H
+    if width < H or width % H:
+        raise ValueError(f"'p' [., {p.size(1)}] does not hold {R} relations of {H} heads")
+    return R, H, width // H
+
+
+@custom_op('pyg_amd::rgat_aggregate', mutates_args=(), device_types=_DEV)
+def rgat_aggregate(p: Tensor, qi: Optional[Tensor], kj: Optional[Tensor], b: Optional[Tensor],
+                   rowptr: Tensor, col: Tensor, rel: Tensor, num_relations: int, heads: int,
+                   negative_slope: float, within: bool) -> Tuple[Tensor, Tensor]:
+    """RGATConv's additive message, softmax and sum (rgat_conv.py:397-437, 500-502): ``(out [n_dst,
+    H * C], alpha [nnz, H])`` with ``out[i, h] = sum_k alpha[k, h] * p[col[k], r, h]``, ``alpha``
+    the softmax of ``leaky_relu(qi[i, r, h] + kj[col[k], r, h] + b[k, h])`` over the slots of row
+    ``i`` (``within``: over those of relation ``r``) and ``r = rel[k]`` (int32 ``[nnz]``, in ``[0,
+    num_relations)``: checked): ``p [n_src, R * H * C]``, ``qi`` / ``kj [n_src, R * H]`` (or both
+    None and ``p`` the packed ``[n_src, R (H C + 2 H)] = [P | QI | KJ]``).  ``rel``, ``b`` and
+    ``alpha`` follow the slots of ``col``, which may come in any order of relations."""
+    R, H, C = _rgat_dims(p, qi, num_relations, heads)
+    if not _native.rgat_supported(H, C):
+        raise NotImplementedError(f'rgat_aggregate serves H * C <= 512 and H <= 64 (got H = {H}, '
+                                  f'C = {C})')
+    if rel.numel() > 0:
+        lo, hi = _native.index_minmax(rel)
+        if lo < 0 or hi >= R:
+            raise ValueError(f"'rel' must lie in [0, {R}) (got values in [{lo}, {hi}])")
+    forms = _onepass.RgatForms.of_csr(rowptr, col, rel, p.size(0), R)
+    alpha, out = _onepass.rgat_forward(forms, p, qi, kj, b, H, C, negative_slope, within)
+    return out, alpha
+
+
+@rgat_aggregate.register_fake
+def _(p, qi, kj, b, rowptr, col, rel, num_relations, heads, negative_slope, within):
+    _, H, C = _rgat_dims(p, qi, num_relations, heads)
+    return p.new_empty(rowptr.numel() - 1, H * C), p.new_empty(col.numel(), H)
+
+
+@custom_op('pyg_amd::rgat_aggregate_backward', mutates_args=(), device_types=_DEV)
+def rgat_aggregate_backward(grad: Tensor, p: Tensor, qi: Optional[Tensor], kj: Optional[Tensor],
+                            b: Optional[Tensor], alpha: Tensor, out: Tensor, rowptr: Tensor,
+                            col: Tensor, rel: Tensor, num_relations: int, heads: int,
+                            negative_slope: float,
+                            within: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The gradients of ``(p, qi, kj, b)``; an input not given gets an empty tensor."""
+    R, H, C = _rgat_dims(p, qi, num_relations, heads)
+    forms = _onepass.RgatForms.of_csr(rowptr, col, rel, p.size(0), R)
+    grads = _onepass.rgat_backward(forms, p, qi, kj, b, alpha, out, grad, H, C, negative_slope,
+                                   within=within, want_b=b is not None)
+    return tuple(grad.new_empty(0) if t is None else t for t in grads)
+
+
+@rgat_aggregate_backward.register_fake
+def _(grad, p, qi, kj, b, alpha, out, rowptr, col, rel, num_relations, heads, negative_slope,
+      within):
+    def like(t):
+        return (grad.new_empty(0) if t is None
+                else torch.empty_like(t, memory_format=torch.contiguous_format))
+    return like(p), like(qi), like(kj), like(b)
+
+
+def _rgat_setup(ctx, inputs, output):
+    p, qi, kj, b, rowptr, col, rel, num_relations, heads, negative_slope, within = inputs
+    out, alpha = output
+    ctx.static = (num_relations, heads, negative_slope, within)
+    ctx.given = (qi is not None, b is not None)
+    ctx.save_for_backward(p, qi, kj, b, alpha, out, rowptr, col, rel)
+
+
+def _rgat_bwd(ctx, grad, _grad_alpha):
+    p, qi, kj, b, alpha, out, rowptr, col, rel = ctx.saved_tensors
+    g_p, g_qi, g_kj, g_b = rgat_aggregate_backward(grad.contiguous(), p, qi, kj, b, alpha, out,
+                                                   rowptr, col, rel, *ctx.static)
+    split, biased = ctx.given
+    return (g_p, g_qi if split else None, g_kj if split else None, g_b if biased else None, None,
+            None, None, None, None, None, None)
+
+
+register_autograd('pyg_amd::rgat_aggregate', _rgat_bwd, setup_context=_rgat_setup)
+
+
 # ---- mixture messages (GMMConv, NNConv) aggregate first, on a CSR pair (rows = destinations) -----
 @custom_op('pyg_amd::mixture_conv', mutates_args=(), device_types=_DEV)
 def mixture_conv(x_src: Tensor, coef: Tensor, weight: Tensor, rowptr: Tensor, col: Tensor,
@@ -1194,4 +1279,4 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'gen_aggregate', 'gen_aggregate_backward', 'resgated_aggregate',
        'resgated_aggregate_backward', 'han_attend', 'han_attend_backward', 'mixture_conv',
        'mixture_conv_backward', 'cg_aggregate', 'cg_aggregate_backward', 'film_aggregate',
-       'film_aggregate_backward')
+       'film_aggregate_backward', 'rgat_aggregate', 'rgat_aggregate_backward')
