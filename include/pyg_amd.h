@@ -258,8 +258,13 @@ typedef struct {
   const void* rowend;        /* NULL, or [n_rows]: the slots of row r are [rowptr[r], rowend[r])
                                 instead of [rowptr[r], rowptr[r + 1]) — rows that own fixed-stride,
                                 partly filled slot blocks (a sampled batch at its static fan-out
-                                capacity: pygamd_sample_slots).  SUM / MEAN without hubs, dense
-                                rows; also honoured by pygamd_sage_layer_fused.                  */
+                                capacity: pygamd_sample_slots), or the live-source lists of
+                                pygamd_live_lists_build.  SUM / MEAN, dense rows; also honoured by
+                                pygamd_sage_layer_fused.  With a hub plan or with src_bits: plain
+                                SUM only (no w / src_scale), every hub row must carry rowend[r] ==
+                                rowptr[r + 1] (the hub kernels read rowptr alone), and with
+                                src_bits rowptr has n_rows + 1 entries and the lists hold live
+                                sources only (hub rows excepted: their bits are still looked up).  */
   int64_t accumulate_rows;   /* with accumulate: only rows < accumulate_rows have an old value, the
                                 others start from 0 (0 = every row) — the root gradient of a
                                 sampled layer exists for its destination rows only.  No hubs.   */
@@ -292,6 +297,44 @@ PYGAMD_API int pygamd_rows_pack(const float* g, int64_t ldg, int64_t n_rows, int
                                 const float* row_scale, float* scaled, int64_t ld_scaled,
                                 int64_t F_scaled, float* copy, int64_t ld_copy, int64_t F_copy,
                                 uint32_t* row_bits, int64_t* n_set, void* stream);
+
+/* Live-source lists of a CSR handle: the stored lists with the entries that point at a dead source
+ * row moved out of the way, for the sums whose source is known to be zero in those rows (the
+ * backward of a loss taken on a training split: the same rows every step).  Kept by the caller in
+ * persistent buffers and walked through pygamd_spmm_args.col / .rowend; built and revalidated on
+ * the device, with no read-back:
+ *
+ *   pygamd_live_lists_flag   *flag = [bits differs from stored] (n_src bits, the layout of
+ *       pygamd_rows_pack.row_bits; the bits past n_src are ignored), or 1 when `force`; `stored`
+ *       then receives `bits`.
+ *   pygamd_live_lists_build  returns at once, in every workgroup, when *flag == 0.  Otherwise, with
+ *       live(c) = bit c of `live` | bit c of `live2` (live2 NULL: no second bitmap):
+ *         - a row of at most hub_threshold entries (every row when hub_threshold == 0):
+ *           col_live[rowptr[r] .. rowend_live[r]) = the entries of col[rowptr[r] .. rowptr[r + 1])
+ *           with live(col[k]), in stored order; the slots behind them hold the row's other
+ *           entries (valid column ids, order unspecified);
+ *         - a longer row (a hub of the handle's plan) is copied whole, rowend_live[r] =
+ *           rowptr[r + 1]: the plan, its chunk offsets and the `deg > hub_threshold` test of the
+ *           row kernels classify every row as they do on the stored lists;
+ *         - with n_set given and 2 * *n_set >= n_src (a dense bitmap: the test pygamd_spmm_csr
+ *           makes on src_bits_set) every row is copied whole;
+ *         - row_has_live (NULL: skipped; ceil(n_rows / 32) words, same layout) bit r = [some
+ *           entry of row r is live], hub rows included.
+ *       col_live / rowend_live may both be NULL (only row_has_live is wanted).  Plain stores, one
+ *       wave per 8 rows, 64 entries at a time (ballot / mbcnt compaction).
+ *   pygamd_live_lists_builds [sync] the number of pygamd_live_lists_build launches that ran for
+ *       real on this device since the library was loaded (tests).
+ * A sum that walks the live lists adds the same values in the same order as one that skips the
+ * dead rows of the stored lists; a dead row that is NOT zero (non-finite weights upstream) is
+ * skipped all the same.  No reference equivalent.                                                 */
+PYGAMD_API int pygamd_live_lists_flag(const uint32_t* bits, uint32_t* stored, int64_t n_src,
+                                      int force, int32_t* flag, void* stream);
+PYGAMD_API int pygamd_live_lists_build(const void* rowptr, const void* col, int idx_dtype,
+                                       int64_t n_rows, int64_t n_src, int64_t hub_threshold,
+                                       const uint32_t* live, const uint32_t* live2,
+                                       const int64_t* n_set, const int32_t* flag, void* col_live,
+                                       void* rowend_live, uint32_t* row_has_live, void* stream);
+PYGAMD_API int pygamd_live_lists_builds(int64_t* count /*[host]*/);
 
 PYGAMD_API int pygamd_spmm_csr_workspace_bytes(const pygamd_spmm_args* args, size_t* bytes);
 PYGAMD_API int pygamd_spmm_csr(const pygamd_spmm_args* args, void* workspace,

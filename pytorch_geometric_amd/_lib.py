@@ -86,6 +86,10 @@ SIGNATURES = {
     'pygamd_rows_compress': (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P]),
     'pygamd_rows_pack': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64, _P,
                                  c_int64, c_int64, _P, _P, _P]),
+    'pygamd_live_lists_flag': (c_int, [_P, _P, c_int64, c_int, _P, _P]),
+    'pygamd_live_lists_build': (c_int, [_P, _P, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P,
+                                        _P, _P, _P, _P]),
+    'pygamd_live_lists_builds': (c_int, [POINTER(c_int64)]),
     'pygamd_spmm_csr_workspace_bytes': (c_int, [POINTER(SpmmArgs), POINTER(c_size_t)]),
     'pygamd_spmm_csr': (c_int, [POINTER(SpmmArgs), _P, c_size_t, _P]),
     'pygamd_spmm_csr_tie_count': (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, c_int64,

@@ -592,6 +592,69 @@ def rows_pack(g: Tensor, row_scale: Optional[Tensor] = None, *, scaled: Optional
     return bits, n_set
 
 
+def live_lists_flag(bits: Tensor, stored: Tensor, n_src: int, flag: Tensor,
+                    force: bool = False) -> None:
+    """``flag[0] = [bits != stored]`` over ``n_src`` bits (1 as well when ``force``), decided on
+    the device; ``stored`` then holds ``bits`` (``pygamd_live_lists_flag``)."""
+    _require_device(bits, stored, flag)
+    words = (n_src + 31) // 32
+    for name, t in (('bits', bits), ('stored', stored)):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < words:
+            raise ValueError(f"'{name}' must be contiguous int32 with one bit per row ({words} "
+                             'words)')
+    if flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError("'flag' must be one int32")
+    check(_lib.load().pygamd_live_lists_flag(_p(bits), _p(stored), n_src, int(bool(force)),
+                                             _p(flag), _stream(bits)), 'live_lists_flag')
+
+
+def live_lists_build(rowptr: Tensor, col: Tensor, n_src: int, live: Tensor, flag: Tensor, *,
+                     hub=None, live2: Optional[Tensor] = None, n_set: Optional[Tensor] = None,
+                     col_live: Optional[Tensor] = None, rowend_live: Optional[Tensor] = None,
+                     row_has_live: Optional[Tensor] = None) -> None:
+    """The live-source lists of a CSR handle into the caller's persistent buffers, or nothing at
+    all when ``flag[0] == 0`` (``pygamd_live_lists_build``: a stable per-row partition by the bits
+    ``live | live2``; rows longer than the plan's threshold and every row of a dense bitmap are
+    copied whole)."""
+    _require_device(rowptr, col, live, live2, n_set, flag, col_live, rowend_live, row_has_live)
+    n_rows, words = rowptr.numel() - 1, (n_src + 31) // 32
+    for name, t in (('live', live), ('live2', live2)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()
+                              or t.numel() < words):
+            raise ValueError(f"'{name}' must be contiguous int32 with one bit per source row")
+    if not rowptr.is_contiguous() or not col.is_contiguous() or col.dtype != rowptr.dtype:
+        raise ValueError("'rowptr' / 'col' must be contiguous and share a dtype")
+    if (col_live is None) != (rowend_live is None):
+        raise ValueError("'col_live' and 'rowend_live' go together")
+    if col_live is not None and (col_live.dtype != col.dtype or rowend_live.dtype != col.dtype
+                                 or not col_live.is_contiguous()
+                                 or not rowend_live.is_contiguous()
+                                 or col_live.numel() < col.numel()
+                                 or rowend_live.numel() < n_rows):
+        raise ValueError("'col_live' / 'rowend_live' need the dtype of 'col', one slot per stored "
+                         'entry and one end per row')
+    if row_has_live is not None and (row_has_live.dtype != torch.int32
+                                     or not row_has_live.is_contiguous()
+                                     or row_has_live.numel() < (n_rows + 31) // 32):
+        raise ValueError("'row_has_live' must be contiguous int32 with one bit per row")
+    if flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError("'flag' must be one int32")
+    if n_set is not None and (n_set.dtype != torch.int64 or n_set.numel() != 1):
+        raise ValueError("'n_set' must be one int64")
+    threshold = hub.threshold if (hub is not None and hub.n_hub > 0) else 0
+    check(_lib.load().pygamd_live_lists_build(
+        _p(rowptr), _p(col), _idx_dtype(rowptr), n_rows, n_src, threshold, _p(live), _p(live2),
+        _p(n_set), _p(flag), _p(col_live), _p(rowend_live), _p(row_has_live), _stream(rowptr)),
+        'live_lists_build')
+
+
+def live_lists_builds() -> int:
+    """Builder launches that ran for real on this device so far (synchronises; test use only)."""
+    n = ctypes.c_int64(0)
+    check(_lib.load().pygamd_live_lists_builds(ctypes.byref(n)), 'live_lists_builds')
+    return n.value
+
+
 def multi_reduce_csr(rowptr: Tensor, perm: Optional[Tensor], x: Tensor, want):
     """{'sum' | 'pow_sum' | 'min' | 'max': [n_groups, F]} for the requested names in ONE read of the
     rows (group g = rows x[perm[k]], k in [rowptr[g], rowptr[g+1]); ``perm=None``: rows are already

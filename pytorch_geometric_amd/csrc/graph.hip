@@ -447,11 +447,152 @@ static int hub_plan_impl(const void* rowptr_v, int64_t n_rows, int64_t threshold
   return PYGAMD_OK;
 }
 
+// ---- live-source lists of a CSR handle (include/pyg_amd.h: pygamd_live_lists_build) -------------
+// flag word: 0 = the lists on the handle were built for this bitmap, 1 = they have to be rebuilt
+constexpr int kLiveRowsPerWave = 8;  // 4 waves x 8 rows = one word of row_has_live per workgroup
+
+__device__ unsigned long long g_live_builds = 0;  // builder launches that ran for real (tests)
+
+// stored[] := bits[] (the tail bits of the last word cleared); *flag |= 1 where they differed
+__global__ void __launch_bounds__(kBlock)
+    live_compare_kernel(const uint32_t* __restrict__ bits, uint32_t* __restrict__ stored,
+                        int64_t words, uint32_t last_mask, int force, int32_t* __restrict__ flag) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  bool diff = false;
+  if (i < words) {
+    uint32_t w = bits[i];
+    if (i == words - 1) w &= last_mask;
+    diff = stored[i] != w;
+    if (diff || force) stored[i] = w;
+  }
+  if (i == 0 && force) diff = true;
+  if (__ballot(diff) != 0ull && lane_id() == 0) atomicOr(flag, 1);
+}
+
+__device__ __forceinline__ bool live_bit(const uint32_t* __restrict__ bits, int64_t c) {
+  return ((bits[c >> 5] >> (c & 31)) & 1u) != 0;
+}
+
+// One workgroup per 32 rows, one wave per 8 of them, a row 64 slots at a time: the live slots go
+// to the front of the row's block in stored order (ballot + mbcnt, running offset), the others to
+// its back, so that every slot of col_live holds a stored column id of the row.  A hub row and
+// every row of a dense bitmap are copied whole.  Plain stores; no atomics on the lists.
+template <typename IdxT>
+__global__ void __launch_bounds__(kBlock)
+    live_lists_kernel(const IdxT* __restrict__ rowptr, const IdxT* __restrict__ col,
+                      int64_t n_rows, int64_t n_src, int64_t hub_threshold,
+                      const uint32_t* __restrict__ live, const uint32_t* __restrict__ live2,
+                      const int64_t* __restrict__ n_set, const int32_t* __restrict__ flag,
+                      IdxT* __restrict__ col_live, IdxT* __restrict__ rowend_live,
+                      uint32_t* __restrict__ row_has_live) {
+  __shared__ uint32_t part[kWavesPerBlock];
+  if (*flag == 0) return;  // unchanged: the lists on the handle stand
+  const int lane = lane_id();
+  const int wv = wave_in_block();
+  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&g_live_builds, 1ull);
+  const bool dense = n_set != nullptr && 2 * *n_set >= n_src;
+  const int64_t row0 = static_cast<int64_t>(blockIdx.x) * 32 + wv * kLiveRowsPerWave;
+  uint32_t has = 0;
+  for (int q = 0; q < kLiveRowsPerWave; ++q) {
+    const int64_t r = row0 + q;
+    if (r >= n_rows) break;
+    const IdxT start = rowptr[r];
+    const IdxT end = rowptr[r + 1];
+    const bool whole = dense || (hub_threshold > 0 && end - start > hub_threshold);
+    IdxT front = start, back = end;
+    bool any = false;
+    for (IdxT base = start; base < end; base += kWave) {
+      const IdxT k = base + lane;
+      const bool in = k < end;
+      const IdxT c = in ? col[k] : IdxT(0);
+      const bool ok = in && c >= 0 && static_cast<int64_t>(c) < n_src;
+      const bool keep = ok && (live_bit(live, c) || (live2 != nullptr && live_bit(live2, c)));
+      const uint64_t m = __ballot(keep);
+      any |= m != 0ull;
+      if (!col_live) continue;
+      if (whole) {
+        if (in) col_live[k] = c;
+        continue;
+      }
+      const uint64_t valid = __ballot(in);
+      const int before = __builtin_amdgcn_mbcnt_hi(
+          static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0));
+      const int n_live = __popcll(m);
+      const int n_in = __popcll(valid);
+      // (lanes in range are the low ones: `lane - before` counts the dead slots before this one)
+      if (keep) {
+        col_live[front + before] = c;
+      } else if (in) {
+        col_live[back - 1 - (lane - before)] = c;
+      }
+      front += n_live;
+      back -= n_in - n_live;
+    }
+    if (rowend_live && lane == 0) rowend_live[r] = (whole || !col_live) ? end : front;
+    if (any) has |= 1u << (wv * kLiveRowsPerWave + q);
+  }
+  if (row_has_live) {  // (uniform: no thread has left the workgroup since the flag test)
+    if (lane == 0) part[wv] = has;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t w = 0;
+      for (int i = 0; i < kWavesPerBlock; ++i) w |= part[i];
+      row_has_live[blockIdx.x] = w;
+    }
+  }
+}
+
 }  // namespace pygamd
 
 using namespace pygamd;
 
 extern "C" {
+
+int pygamd_live_lists_flag(const uint32_t* bits, uint32_t* stored, int64_t n_src, int force,
+                           int32_t* flag, void* stream) {
+  if (n_src < 0 || !flag || (n_src > 0 && (!bits || !stored))) return PYGAMD_ERR_INVALID_ARG;
+  hipStream_t st = as_stream(stream);
+  PYGAMD_HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int32_t), st));
+  const int64_t words = ceil_div(n_src, static_cast<int64_t>(32));
+  const uint32_t last_mask = (n_src & 31) ? ((1u << (n_src & 31)) - 1u) : ~0u;
+  const int64_t blocks = words > 0 ? ceil_div(words, static_cast<int64_t>(kBlock)) : 1;
+  hipLaunchKernelGGL(live_compare_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, st,
+                     bits, stored, words, last_mask, force ? 1 : 0, flag);
+  PYGAMD_LAUNCH_CHECK();
+  return PYGAMD_OK;
+}
+
+int pygamd_live_lists_build(const void* rowptr, const void* col, int idx_dtype, int64_t n_rows,
+                            int64_t n_src, int64_t hub_threshold, const uint32_t* live,
+                            const uint32_t* live2, const int64_t* n_set, const int32_t* flag,
+                            void* col_live, void* rowend_live, uint32_t* row_has_live,
+                            void* stream) {
+  if (n_rows < 0 || n_src < 0 || hub_threshold < 0) return PYGAMD_ERR_INVALID_ARG;
+  if (idx_dtype != PYGAMD_IDX_I64 && idx_dtype != PYGAMD_IDX_I32) return PYGAMD_ERR_INVALID_ARG;
+  if (n_rows == 0) return PYGAMD_OK;
+  if (!rowptr || !col || !live || !flag || n_src == 0) return PYGAMD_ERR_INVALID_ARG;
+  if ((col_live == nullptr) != (rowend_live == nullptr)) return PYGAMD_ERR_INVALID_ARG;
+  if (!col_live && !row_has_live) return PYGAMD_ERR_INVALID_ARG;
+  if (n_rows >= (static_cast<int64_t>(1) << 36)) return PYGAMD_ERR_INVALID_ARG;
+  const dim3 grid(static_cast<unsigned>(ceil_div(n_rows, static_cast<int64_t>(32))));
+  return PYGAMD_DISPATCH_IDX(idx_dtype, [&]() -> int {
+    hipLaunchKernelGGL((live_lists_kernel<IdxT>), grid, dim3(kBlock), 0, as_stream(stream),
+                       static_cast<const IdxT*>(rowptr), static_cast<const IdxT*>(col), n_rows,
+                       n_src, hub_threshold, live, live2, n_set, flag,
+                       static_cast<IdxT*>(col_live), static_cast<IdxT*>(rowend_live),
+                       row_has_live);
+    PYGAMD_LAUNCH_CHECK();
+    return PYGAMD_OK;
+  });
+}
+
+int pygamd_live_lists_builds(int64_t* count) {
+  if (!count) return PYGAMD_ERR_INVALID_ARG;
+  unsigned long long v = 0;
+  PYGAMD_HIP_CHECK(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_live_builds), sizeof(v)));
+  *count = static_cast<int64_t>(v);
+  return PYGAMD_OK;
+}
 
 int pygamd_index_sort_workspace_bytes(int idx_dtype, int64_t n, size_t* bytes) {
   if (!bytes || n < 0) return PYGAMD_ERR_INVALID_ARG;

@@ -373,7 +373,10 @@ inline int sage_fused_validate(const pygamd_spmm_args* graph, const pygamd_sage_
   const bool zsrc = graph->x_format == PYGAMD_X_COMPRESSED;
   if (graph->x_format != PYGAMD_X_DENSE && !zsrc) return PYGAMD_ERR_INVALID_ARG;
   if (given && zsrc) return PYGAMD_ERR_UNSUPPORTED;  // (the stored rows are dense)
-  if (graph->rowend && (graph->n_hub > 0 || zsrc)) return PYGAMD_ERR_UNSUPPORTED;
+  // rowend with a hub plan (live-source lists): plain sum, hub rows carry rowend[r] == rowptr[r + 1]
+  // (the hub pre-pass reads rowptr alone; `deg > hub_threshold` then classifies as on stored lists)
+  if (graph->rowend && (zsrc || (graph->n_hub > 0 && graph->reduce != PYGAMD_SUM)))
+    return PYGAMD_ERR_UNSUPPORTED;
   if (graph->accumulate_rows != 0) return PYGAMD_ERR_INVALID_ARG;
   if (zsrc && (graph->ldx < F + 12 || graph->src_bits)) return PYGAMD_ERR_INVALID_ARG;
   if (f->compressed_out && (Fo % 32 != 0 || f->ld_compressed < Fo + 12))

@@ -91,20 +91,27 @@ __global__ void __launch_bounds__(kBlock) spmm_sum_rows(SpmmDev<IdxT> a) {
 // three dependent round trips (its column ids, their bits, the two or three live rows) and almost
 // no bytes; the one-row kernel then runs at the latency of 3 trips per 8 waves per SIMD (1.0 ms for
 // the products graph).  Here the R index loads, then the R bit lookups, are in flight together.
-template <typename IdxT, int VW, int LPR, int CH, int R>
+// With a.rowend the lists hold live sources only (pygamd_live_lists_build; hub rows whole): the
+// lookups are skipped, as they are for a dense bitmap.
+template <typename IdxT, int VW, int LPR, int CH, int R, bool LISTS = false>
 __global__ void __launch_bounds__(kBlock) spmm_sum_rows_sparse(SpmmDev<IdxT> a) {
   const int lane = lane_id();
   const int64_t row0 = (xcd_logical_block() * kWavesPerBlock + wave_in_block()) * R;
   if (row0 >= a.n_rows) return;
-  const bool use_bits = a.src_bits_set == nullptr || 2 * *a.src_bits_set < a.n_src;
+  // LISTS (a.rowend given): the lists are pre-filtered (live sources only,
+  // pygamd_live_lists_build) — no lookup.  A template flag: as a run-time test it cost the
+  // stored-list launch 0.06 of its 0.82 ms at the products shape.
+  constexpr bool lists = LISTS;
+  const bool use_bits = !lists && (a.src_bits_set == nullptr || 2 * *a.src_bits_set < a.n_src);
   int fo[CH], head[CH];
   bool fv[CH];
   feature_slots<VW, LPR, CH>(lane, a.F, a.head_dim, fo, fv, head);
   // rowptr[row0 .. row0 + R], clamped to the last entry: rows past the end come out empty
-  IdxT myptr = 0;
+  IdxT myptr = 0, myend = 0;
   if (lane <= R) {
     const int64_t r = row0 + lane;
     myptr = a.rowptr[r < a.n_rows ? r : a.n_rows];
+    if (lists) myend = r < a.n_rows ? a.rowend[r] : myptr;
   }
   IdxT start[R], end[R], myc[R];
   int cnt[R];
@@ -121,7 +128,7 @@ __global__ void __launch_bounds__(kBlock) spmm_sum_rows_sparse(SpmmDev<IdxT> a) 
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     start[r] = bcast_uniform(myptr, r);
-    end[r] = bcast_uniform(myptr, r + 1);
+    end[r] = lists ? bcast_uniform(myend, r) : bcast_uniform(myptr, r + 1);
     const IdxT deg = end[r] - start[r];
     hub[r] = a.hub_threshold > 0 && deg > a.hub_threshold;  // owned by the hub path
     cnt[r] = hub[r] ? 0 : (deg < kWave ? static_cast<int>(deg) : kWave);
@@ -188,8 +195,13 @@ __global__ void __launch_bounds__(kBlock) spmm_sum_rows_sparse(SpmmDev<IdxT> a) 
                                                      fv, head, acc);
     }
     if (end[r] - start[r] > kWave) {  // the slots past the first 64, one chunk at a time
-      spmm_accumulate<IdxT, VW, LPR, CH, 3, false>(a, start[r] + kWave, end[r], lane, fo, fv,
-                                                    head, acc);
+      if (lists) {
+        spmm_accumulate<IdxT, VW, LPR, CH, 0, false>(a, start[r] + kWave, end[r], lane, fo, fv,
+                                                      head, acc);
+      } else {
+        spmm_accumulate<IdxT, VW, LPR, CH, 3, false>(a, start[r] + kWave, end[r], lane, fo, fv,
+                                                      head, acc);
+      }
     }
     combine_subgroups<VW, LPR, CH>(acc);
     if (lane < LPR) {
@@ -1308,8 +1320,13 @@ static int launch_sum(const pygamd_spmm_args* p, const Shape& s, float* partial,
       if (!p->accumulate && !p->relu_mask && !p->relu_bits && p->n_src > 0) {
         constexpr int R = 4;
         dim3 grid(wave_grid(ceil_div(p->n_rows, static_cast<int64_t>(R))), s.tiles);
-        hipLaunchKernelGGL((spmm_sum_rows_sparse<IdxT, VW, LPR, CH, R>), grid, dim3(kBlock), 0,
-                           st, a);
+        if (p->rowend) {
+          hipLaunchKernelGGL((spmm_sum_rows_sparse<IdxT, VW, LPR, CH, R, true>), grid,
+                             dim3(kBlock), 0, st, a);
+        } else {
+          hipLaunchKernelGGL((spmm_sum_rows_sparse<IdxT, VW, LPR, CH, R>), grid, dim3(kBlock), 0,
+                             st, a);
+        }
         done = true;
       }
     }
@@ -1580,8 +1597,13 @@ static int validate(const pygamd_spmm_args* p) {
   if (p->x_format != PYGAMD_X_DENSE && p->x_format != PYGAMD_X_COMPRESSED)
     return PYGAMD_ERR_INVALID_ARG;
   // fixed-stride slot blocks / a row limit on `accumulate`: the plain and weighted sum kernels of
-  // rows without hubs (what a sampled batch needs)
-  if (p->rowend && (mm || p->n_hub > 0 || p->src_bits || p->x_format != PYGAMD_X_DENSE))
+  // rows without hubs (what a sampled batch needs); with a hub plan or src_bits (live-source lists:
+  // hub rows carry rowend[r] == rowptr[r + 1], so the hub kernels, which read rowptr alone, and
+  // the `deg > hub_threshold` test of the row kernels see what they see on the stored lists) the
+  // plain sum only
+  if (p->rowend && (mm || p->x_format != PYGAMD_X_DENSE)) return PYGAMD_ERR_UNSUPPORTED;
+  if (p->rowend && (p->n_hub > 0 || p->src_bits) &&
+      (p->reduce != PYGAMD_SUM || p->w || p->src_scale))
     return PYGAMD_ERR_UNSUPPORTED;
   if (p->accumulate_rows < 0 || (p->accumulate_rows > 0 && (!p->accumulate || p->n_hub > 0)))
     return PYGAMD_ERR_INVALID_ARG;

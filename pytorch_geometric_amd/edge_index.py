@@ -34,6 +34,7 @@ class CSR:
         self._hub = None
         self._inv_deg = None
         self._agg0 = None  # nn/models/_fused_sage.py: the first SAGE layer's cached aggregation
+        self._live = None  # nn/models/_fused_sage.py: live-source lists of the backward's gather
 
     @property
     def hub(self):

@@ -95,10 +95,77 @@ def cache_agg0_enabled() -> bool:
 
 
 def clear_aggregation_cache() -> None:
-    """Drop every cached first-layer aggregation (see ``PYGAMD_CACHE_AGG0``)."""
+    """Drop every cached first-layer aggregation (see ``PYGAMD_CACHE_AGG0``) and every set of
+    live-source lists (see ``PYGAMD_LIVE_LISTS``)."""
     for handle in list(_agg0_handles):
         handle._agg0 = None
     _agg0_handles.clear()
+    for handle in list(_live_handles):
+        handle._live = None
+    _live_handles.clear()
+
+
+# The gradient of a loss taken on a training split T is zero outside T, so the input gradient that
+# the 'pre' output layer hands down (`linear_dgrad(gy)`) is exactly zero in every row outside
+# S1 = T + {rows with a stored by-source entry that points into T}: the one-launch input gradient of
+# the layer below gathers those rows only to add zeros (12 % of the stored entries at the products
+# shape).  In full-batch training T is the same every step, so the by-source lists with the dead
+# entries moved behind a per-row end (`_native.live_lists_build`: stable, so the sums keep their
+# order and their bits) are kept on the handle, like `_agg0`, and the launch walks them through
+# `rowend`.  Whether they still match this step's row bitmap is decided on the device
+# (`live_lists_flag` against the stored copy; the builders return at once when it does): no host
+# decision, no read-back, the same launches every step.  A dense gradient makes pass-through lists.
+# Used only where the skipped rows cannot change a bit of the result: a gather with one lane group
+# per row (more than 128 columns) adds a row's entries one after the other.  Bypassed under stream
+# capture.  PYGAMD_LIVE_LISTS=0 (read at every call) switches it off.
+_live_handles = weakref.WeakSet()
+
+
+def live_lists_enabled() -> bool:
+    return os.environ.get('PYGAMD_LIVE_LISTS', '1') != '0'
+
+
+class _LiveLists:
+    """The S1 lists of one by-source handle and the device state that validates them."""
+
+    def __init__(self, handle, n: int):
+        ptr, idx = handle.ptr, handle.idx
+        dev = ptr.device
+        words = (n + 31) // 32
+        self.key = _live_key(handle, n)
+        self.stored = torch.zeros(words, dtype=torch.int32, device=dev)  # the bitmap built for
+        self.has = torch.zeros(words, dtype=torch.int32, device=dev)     # row has an entry in T
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.col = torch.empty_like(idx)
+        self.end = torch.empty(n, dtype=ptr.dtype, device=dev)
+        self.fresh = True   # nothing built yet: the first flag launch is forced to "changed"
+
+
+def _live_key(handle, n: int):
+    hub = handle.hub
+    return (n, handle.ptr.data_ptr(), handle.idx.data_ptr(), handle.idx.numel(),
+            None if hub is None else (hub.threshold, hub.chunk, hub.n_hub))
+
+
+def _live_lists(handle, n: int) -> '_LiveLists':
+    lists = getattr(handle, '_live', None)
+    if lists is None or lists.key != _live_key(handle, n):
+        lists = handle._live = _LiveLists(handle, n)
+        _live_handles.add(handle)
+    return lists
+
+
+def _live_update(handle, n: int, row_bits: Tensor, n_set: Tensor) -> '_LiveLists':
+    """Revalidate (and, on the device, rebuild where needed) the S1 lists for this step's bitmap."""
+    lists = _live_lists(handle, n)
+    _native.live_lists_flag(row_bits, lists.stored, n, lists.flag, force=lists.fresh)
+    lists.fresh = False
+    _native.live_lists_build(handle.ptr, handle.idx, n, row_bits, lists.flag, hub=handle.hub,
+                             n_set=n_set, row_has_live=lists.has)
+    _native.live_lists_build(handle.ptr, handle.idx, n, row_bits, lists.flag, hub=handle.hub,
+                             live2=lists.has, n_set=n_set, col_live=lists.col,
+                             rowend_live=lists.end)
+    return lists
 
 
 def _agg0_key(handle, x: Tensor, aggr: str):
@@ -355,10 +422,12 @@ class FusedSageStack(Function):
                     and _native.sage_layer_forward_supported(Fo, Fi, 'sum'))
 
         g_scaled = None  # g * (1 / deg) per row, when the producer of `g` wrote it as well
+        live_src = None  # the live-source lists that cover the zero rows of `g` / `g_scaled`
         for layer in reversed(range(L)):
             buf, wmat = bufs[layer], wmats[layer]
             Fi, Fo = ctx.dims[layer]
             want_b = ctx.has_bias[layer]
+            live, live_src = live_src, None  # (lists made by the layer above serve this one only)
             if not masked:  # ReLU backward and this layer's bias gradient in one pass
                 h_next = FusedSageStack._input_view(ctx, bufs, layer + 1)  # post-ReLU output
                 g, grads[3 * layer + 1] = _native.relu_backward_colsum(g, h_next, want_b)
@@ -417,11 +486,15 @@ class FusedSageStack(Function):
                     # before it writes its result)
                     scratch = gin if Fi == Fo else torch.empty(N, Fo, dtype=torch.float32,
                                                                device=g.device)
-                    _native.sage_layer_forward(bwd.ptr, bwd.idx, gsrc, g, wc, None, 'sum', False,
+                    # (`live`: the gather source came from the 'pre' layer above and is zero
+                    # outside the rows its lists keep — same sums, fewer rows read)
+                    lists = {} if live is None else {'rowend': live.end}
+                    _native.sage_layer_forward(bwd.ptr, bwd.idx if live is None else live.col,
+                                               gsrc, g, wc, None, 'sum', False,
                                                scratch, gin, hub=bwd.hub, save_agg=False,
                                                mask_bits=bits_in,
                                                row_scale=scale if gin_s is not None else None,
-                                               out_scaled=gin_s)
+                                               out_scaled=gin_s, **lists)
                     grads[3 * layer] = gw[:, :Fi]
                     grads[3 * layer + 2] = gw[:, Fi:]
                     g, g_scaled = gin, gin_s
@@ -514,6 +587,13 @@ class FusedSageStack(Function):
                 grads[3 * layer + 2] = gw[Fp:Fp + Fo]
                 g_scaled = None
                 if need_input_grad:  # [N, Fi]
+                    # `gy` is zero outside T and the rows with an entry into T, and so is the
+                    # dgrad below: the one-launch input gradient of the layer underneath walks the
+                    # lists that leave those rows out (see `_live_update`; its gather is Fi wide)
+                    if (own and row_bits is not None and layer > 0 and Fi > 128 and g.is_cuda
+                            and fused_bwd(layer - 1) and live_lists_enabled()
+                            and not torch.cuda.is_current_stream_capturing()):
+                        live_src = _live_update(bwd, N, row_bits, n_set)
                     if own:
                         if scaled_for_next:
                             g_scaled = torch.empty(N, Fi, dtype=torch.float32, device=g.device)
