@@ -251,16 +251,18 @@ typedef struct {
                                 costs more than it saves) — decided on the device, no host sync    */
   int32_t x_format;          /* PYGAMD_X_DENSE (0), or PYGAMD_X_COMPRESSED: `x` is the block written
                                 by pygamd_rows_compress / pygamd_sage_layer_fused.compressed_out
-                                ([n_src, ldx] 32-bit words, F <= 256, F % 4 == 0, ldx >= F + 12);
-                                SUM/MEAN without w / src_scale / src_bits; same sums, bit for bit,
-                                as the dense rows                                                 */
+                                ([n_src, ldx] 32-bit words, F <= 256, F % 4 == 0, F + 12 <= ldx
+                                < 2^30, n_src < 2^32); SUM/MEAN without w / src_scale /
+                                src_bits, with or without rowend; same sums, bit for bit, as the
+                                dense rows.  pygamd_sage_layer_fused takes it on both schedules
+                                (the split schedule for F > 128, the fp32 one otherwise)          */
   int32_t reserved0;         /* 0 */
   const void* rowend;        /* NULL, or [n_rows]: the slots of row r are [rowptr[r], rowend[r])
                                 instead of [rowptr[r], rowptr[r + 1]) — rows that own fixed-stride,
                                 partly filled slot blocks (a sampled batch at its static fan-out
                                 capacity: pygamd_sample_slots), or the live-source lists of
-                                pygamd_live_lists_build.  SUM / MEAN, dense rows; also honoured by
-                                pygamd_sage_layer_fused.  With a hub plan or with src_bits: plain
+                                pygamd_live_lists_build.  SUM / MEAN, dense or compressed rows;
+                                also honoured by pygamd_sage_layer_fused.  With a hub plan or with src_bits: plain
                                 SUM only (no w / src_scale), every hub row must carry rowend[r] ==
                                 rowptr[r + 1] (the hub kernels read rowptr alone), and with
                                 src_bits rowptr has n_rows + 1 entries and the lists hold live
@@ -282,6 +284,13 @@ typedef struct {
  * (nn/models/basic_gnn.py:262-263).                                                              */
 PYGAMD_API int pygamd_rows_compress(const float* x, int64_t ldx, int64_t n_rows, int64_t F,
                                     uint32_t* out, int64_t ld_out, void* stream);
+/* The same block of x[i, c] * row_scale[i] (row_scale: [n_rows] or NULL = pygamd_rows_compress):
+ * one fp32 multiply per element, the value a dgrad epilogue writes into its row-scaled copy — the
+ * 1/deg-scaled gradient rows that the one-launch input gradient of a mean layer gathers, without
+ * the dense scaled copy in between.                                                              */
+PYGAMD_API int pygamd_rows_compress_scaled(const float* x, int64_t ldx, int64_t n_rows, int64_t F,
+                                           const float* row_scale, uint32_t* out, int64_t ld_out,
+                                           void* stream);
 
 /* Row-sparsity of a gradient block, found in the pass that lays it out for the backward of a
  * transform-then-aggregate layer: for every row i < n_rows of g ([n_rows, ldg], F columns)

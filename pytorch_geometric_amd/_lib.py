@@ -84,6 +84,7 @@ SIGNATURES = {
     'pygamd_hub_plan': (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, _P, c_int64,
                                 POINTER(c_int64), POINTER(c_int64), _P, c_size_t, _P]),
     'pygamd_rows_compress': (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P]),
+    'pygamd_rows_compress_scaled': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, c_int64, _P]),
     'pygamd_rows_pack': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64, _P,
                                  c_int64, c_int64, _P, _P, _P]),
     'pygamd_live_lists_flag': (c_int, [_P, _P, c_int64, c_int, _P, _P]),

@@ -377,7 +377,7 @@ def spmm_csr(rowptr: Tensor, col: Optional[Tensor], x: Tensor, reduce: str, *,
             raise ValueError("'src_bits_set' must be one int64")
     if compressed_width is not None:
         return _spmm_csr_compressed(rowptr, col, x, reduce, compressed_width, n_rows, hub, out,
-                                    hub_phase)
+                                    hub_phase, rowend)
     if rowend is not None:
         _require_device(rowend)
         if rowend.dtype != rowptr.dtype or not rowend.is_contiguous() or n_rows is None \
@@ -503,26 +503,42 @@ def _check_compressed(z: Tensor, F: int, name: str):
         raise ValueError('compressed rows hold at most 256 columns, a multiple of 4')
 
 
-def rows_compress(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
+def rows_compress(x: Tensor, out: Optional[Tensor] = None,
+                  row_scale: Optional[Tensor] = None) -> Tensor:
     """``x`` ([n, F <= 256] float32) as compressed rows ``[8 mask words | kept values]`` — the
-    lossless zero-skipping layout the row gathers read (``pygamd_rows_compress``)."""
-    _require_device(x, out)
+    lossless zero-skipping layout the row gathers read (``pygamd_rows_compress``).  ``row_scale``
+    (float32, one entry per row): the rows of ``x * row_scale[:, None]`` instead, one fp32 multiply
+    per element (``pygamd_rows_compress_scaled``)."""
+    _require_device(x, out, row_scale)
     x2 = _f32_rows(x, 'x')
     n, F = x2.shape
     if F > 256:
         raise ValueError('compressed rows hold at most 256 columns')
+    if row_scale is not None:
+        if row_scale.dtype != torch.float32 or row_scale.numel() != n:
+            raise ValueError("'row_scale' must be float32 with one entry per row")
+        row_scale = row_scale.contiguous()
     if out is None:
         out = torch.empty(n, compressed_pitch(F), dtype=torch.int32, device=x.device)
     elif (out.dim() != 2 or out.dtype != torch.int32 or out.size(0) != n or out.size(1) < F + 12
           or (out.size(1) > 1 and out.stride(1) != 1)):
         raise ValueError(f"'out' must be int32 [{n}, >= {F + 12}]")
-    check(_lib.load().pygamd_rows_compress(_p(x2), _ld(x2), n, F, _p(out), _ld(out), _stream(x)),
-          'rows_compress')
+    if row_scale is None:
+        check(_lib.load().pygamd_rows_compress(_p(x2), _ld(x2), n, F, _p(out), _ld(out),
+                                               _stream(x)), 'rows_compress')
+    else:
+        check(_lib.load().pygamd_rows_compress_scaled(_p(x2), _ld(x2), n, F, _p(row_scale),
+                                                      _p(out), _ld(out), _stream(x)),
+              'rows_compress')
     return out
 
 
-def _spmm_csr_compressed(rowptr, col, z, reduce, F, n_rows, hub, out, hub_phase):
-    _require_device(rowptr, col, z, out)
+def _spmm_csr_compressed(rowptr, col, z, reduce, F, n_rows, hub, out, hub_phase, rowend=None):
+    _require_device(rowptr, col, z, out, rowend)
+    if rowend is not None and (rowend.dtype != rowptr.dtype or not rowend.is_contiguous()
+                               or n_rows is None or rowend.numel() < n_rows
+                               or rowptr.numel() < n_rows):
+        raise ValueError("'rowend' needs 'n_rows', the dtype of 'rowptr' and one entry per row")
     _check_compressed(z, F, 'x')
     if reduce not in ('sum', 'mean'):
         raise ValueError("compressed rows: reduce must be 'sum' or 'mean'")
@@ -539,6 +555,8 @@ def _spmm_csr_compressed(rowptr, col, z, reduce, F, n_rows, hub, out, hub_phase)
     a.w_heads, a.head_dim = 1, max(F, 1)
     a.hub_phase = hub_phase
     a.x_format = _lib.X_COMPRESSED
+    if rowend is not None:
+        a.rowend = rowend.data_ptr()
     _hub_args(a, hub)
     ws, ws_bytes = None, 0
     if a.n_hub > 0 and hub_phase != 1:

@@ -166,8 +166,10 @@ __device__ __forceinline__ void split_store4(uint32_t* __restrict__ p, int pstri
 }
 
 // fused_gather_row with the finished row going to the term planes (`prow` = the row's first dword
-// in plane 0)
-template <typename IdxT, int LPR>
+// in plane 0).  ZSRC: a.g.x holds compressed rows (spmm_device.h); the decoder hands the sum back
+// in this lane shape (64 lanes x 4 consecutive columns), so the planes and the saved row receive
+// the fp32 values of the dense gather.
+template <typename IdxT, int LPR, bool ZSRC = false>
 __device__ __forceinline__ void split_gather_row(const SageFusedArgs<IdxT>& a, int64_t row,
                                                  uint32_t* __restrict__ prow, int pstride,
                                                  int lane) {
@@ -195,7 +197,8 @@ __device__ __forceinline__ void split_gather_row(const SageFusedArgs<IdxT>& a, i
     }
     return;
   }
-  spmm_accumulate<IdxT, VW, LPR, CH, 0, false>(a.g, start, end, lane, fo, fv, head, acc);
+  spmm_accumulate<IdxT, VW, LPR, CH, ZSRC ? 4 : 0, false>(a.g, start, end, lane, fo, fv, head,
+                                                          acc);
   combine_subgroups<VW, LPR, CH>(acc);
   if (lane < LPR && fv[0]) {
     const float cntf = static_cast<float>(deg > 0 ? deg : 1);
@@ -280,8 +283,10 @@ __device__ __forceinline__ void split_pass(const u32x4* __restrict__ wq,
 // accumulators take 124 registers).
 // GIVEN: the aggregated rows come from the global agg buffer, spread over the threads like the root
 // rows and loaded with them before the first barrier (see the head of this file).
+// ZSRC: the gather source is a block of compressed rows (LPR = 64, two passes); the root rows stay
+// dense.
 template <typename IdxT, int LPR, int NPASS, bool PROBE, bool OCC3 = (NPASS == 1),
-          bool GIVEN = false>
+          bool GIVEN = false, bool ZSRC = false>
 __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
     sage_fused_split_kernel(SageFusedArgs<IdxT> a) {
   constexpr int D = OCC3 ? 2 : 4;
@@ -371,7 +376,7 @@ __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
       if (lane == 0) r = atomicAdd(&next_row, 1);
       r = __builtin_amdgcn_readfirstlane(r);
       if (r >= kFTile) break;
-      split_gather_row<IdxT, LPR>(a, row0 + r, pl + r * row_dw, pstride, lane);
+      split_gather_row<IdxT, LPR, ZSRC>(a, row0 + r, pl + r * row_dw, pstride, lane);
     }
   }
   __syncthreads();  // aggregated half (and, one pass: the root half) visible to every wave
@@ -422,7 +427,7 @@ static int launch_fused(const SageFusedArgs<IdxT>& a, hipStream_t st, bool zsrc)
 }
 
 template <typename IdxT, int LPR, int NPASS>
-static int launch_split(const SageFusedArgs<IdxT>& a, hipStream_t st) {
+static int launch_split(const SageFusedArgs<IdxT>& a, hipStream_t st, bool zsrc) {
   const int KT = NPASS == 1 ? 2 * a.f_half : a.f_half;
   const size_t lds = sizeof(uint32_t) * 3 * kFTile * (KT / 2 + 4);
   void (*k)(SageFusedArgs<IdxT>) = a.probe ? sage_fused_split_kernel<IdxT, LPR, NPASS, true>
@@ -432,6 +437,9 @@ static int launch_split(const SageFusedArgs<IdxT>& a, hipStream_t st) {
   }
   if (a.save_agg == PYGAMD_AGG_GIVEN)  // (no gather to probe: the probe bits do not apply)
     k = sage_fused_split_kernel<IdxT, LPR, NPASS, false, NPASS == 1, true>;
+  if constexpr (LPR == kWave && NPASS == 2) {  // (validation: never together with the rows given)
+    if (zsrc) k = sage_fused_split_kernel<IdxT, LPR, NPASS, false, false, false, true>;
+  }
   PYGAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds)));
@@ -442,9 +450,14 @@ static int launch_split(const SageFusedArgs<IdxT>& a, hipStream_t st) {
   return PYGAMD_OK;
 }
 
-// the split schedule takes dense rows in and writes dense rows out
+// the split schedule writes dense rows out; it gathers dense rows, or compressed rows of more than
+// 128 columns (a whole wave decodes a row: the two-pass kernel's lane shape)
+static bool split_source_ok(const pygamd_spmm_args* graph) {
+  return graph->x_format == PYGAMD_X_DENSE ||
+         (graph->x_format == PYGAMD_X_COMPRESSED && graph->F > 128);
+}
 static bool split_eligible(const pygamd_spmm_args* graph, const pygamd_sage_fused_args* f) {
-  return pygamd_get_gemm_mode() == PYGAMD_GEMM_SPLIT_BF16 && graph->x_format == PYGAMD_X_DENSE &&
+  return pygamd_get_gemm_mode() == PYGAMD_GEMM_SPLIT_BF16 && split_source_ok(graph) &&
          !f->compressed_out;
 }
 
@@ -468,7 +481,7 @@ int sage_layer_fused_run(const pygamd_spmm_args* graph, const pygamd_sage_fused_
   const bool zsrc = graph->x_format == PYGAMD_X_COMPRESSED;
   u32x4* wp = nullptr;
   if (split) {
-    if (zsrc || f->compressed_out) return PYGAMD_ERR_UNSUPPORTED;
+    if (!split_source_ok(graph) || f->compressed_out) return PYGAMD_ERR_UNSUPPORTED;
     const size_t off = hub_bytes_aligned(graph, f);
     if (!workspace || workspace_bytes < off + split_planes_bytes(F, Fo))
       return PYGAMD_ERR_WORKSPACE;
@@ -494,11 +507,11 @@ int sage_layer_fused_run(const pygamd_spmm_args* graph, const pygamd_sage_fused_
     a.f_half = fh;
     if (split) {
       switch (lpr) {
-        case 4: return launch_split<IdxT, 4, 1>(a, st);
-        case 8: return launch_split<IdxT, 8, 1>(a, st);
-        case 16: return launch_split<IdxT, 16, 1>(a, st);
-        case 32: return launch_split<IdxT, 32, 1>(a, st);
-        default: return launch_split<IdxT, 64, 2>(a, st);
+        case 4: return launch_split<IdxT, 4, 1>(a, st, false);
+        case 8: return launch_split<IdxT, 8, 1>(a, st, false);
+        case 16: return launch_split<IdxT, 16, 1>(a, st, false);
+        case 32: return launch_split<IdxT, 32, 1>(a, st, false);
+        default: return launch_split<IdxT, 64, 2>(a, st, zsrc);
       }
     }
     switch (lpr) {
@@ -531,7 +544,7 @@ int pygamd_sage_layer_fused_workspace_bytes(const pygamd_spmm_args* graph,
   if (f->save_agg != PYGAMD_AGG_GIVEN) pygamd_spmm_csr_workspace_bytes(graph, &hub);
   // (sized for the split schedule whatever the current mode: the mode may change between the
   // query and the launch)
-  const bool planes = graph->x_format == PYGAMD_X_DENSE && !f->compressed_out &&
+  const bool planes = split_source_ok(graph) && !f->compressed_out &&
                       pygamd_sage_layer_forward_supported(graph->F, f->Fo, graph->reduce);
   *bytes = planes ? hub_bytes_aligned(graph, f) + split_planes_bytes(graph->F, f->Fo) : hub;
   return PYGAMD_OK;

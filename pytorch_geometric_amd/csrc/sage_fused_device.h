@@ -375,10 +375,12 @@ inline int sage_fused_validate(const pygamd_spmm_args* graph, const pygamd_sage_
   if (given && zsrc) return PYGAMD_ERR_UNSUPPORTED;  // (the stored rows are dense)
   // rowend with a hub plan (live-source lists): plain sum, hub rows carry rowend[r] == rowptr[r + 1]
   // (the hub pre-pass reads rowptr alone; `deg > hub_threshold` then classifies as on stored lists)
-  if (graph->rowend && (zsrc || (graph->n_hub > 0 && graph->reduce != PYGAMD_SUM)))
+  if (graph->rowend && graph->n_hub > 0 && graph->reduce != PYGAMD_SUM)
     return PYGAMD_ERR_UNSUPPORTED;
   if (graph->accumulate_rows != 0) return PYGAMD_ERR_INVALID_ARG;
-  if (zsrc && (graph->ldx < F + 12 || graph->src_bits)) return PYGAMD_ERR_INVALID_ARG;
+  if (zsrc && (graph->ldx < F + 12 || graph->ldx >= (int64_t{1} << 30) ||
+               graph->n_src >= (int64_t{1} << 32) || graph->src_bits))
+    return PYGAMD_ERR_INVALID_ARG;
   if (f->compressed_out && (Fo % 32 != 0 || f->ld_compressed < Fo + 12))
     return PYGAMD_ERR_INVALID_ARG;
   if (graph->n_rows == 0) return PYGAMD_OK;

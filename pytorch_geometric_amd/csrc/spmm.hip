@@ -1601,7 +1601,7 @@ static int validate(const pygamd_spmm_args* p) {
   // hub rows carry rowend[r] == rowptr[r + 1], so the hub kernels, which read rowptr alone, and
   // the `deg > hub_threshold` test of the row kernels see what they see on the stored lists) the
   // plain sum only
-  if (p->rowend && (mm || p->x_format != PYGAMD_X_DENSE)) return PYGAMD_ERR_UNSUPPORTED;
+  if (p->rowend && mm) return PYGAMD_ERR_UNSUPPORTED;
   if (p->rowend && (p->n_hub > 0 || p->src_bits) &&
       (p->reduce != PYGAMD_SUM || p->w || p->src_scale))
     return PYGAMD_ERR_UNSUPPORTED;
@@ -1609,7 +1609,9 @@ static int validate(const pygamd_spmm_args* p) {
     return PYGAMD_ERR_INVALID_ARG;
   if (p->x_format == PYGAMD_X_COMPRESSED) {
     if (mm || p->w || p->src_scale || p->src_bits || !p->col) return PYGAMD_ERR_UNSUPPORTED;
-    if (p->F > 256 || p->F % 4 != 0 || p->ldx < p->F + 12 || p->ldo % 4 != 0 ||
+    // (the decoder forms row offsets in bytes from 32-bit factors)
+    if (p->F > 256 || p->F % 4 != 0 || p->ldx < p->F + 12 || p->ldx >= (int64_t{1} << 30) ||
+        p->n_src >= (int64_t{1} << 32) || p->ldo % 4 != 0 ||
         (reinterpret_cast<uintptr_t>(p->out) & 15u) != 0)
       return PYGAMD_ERR_UNSUPPORTED;
   }
@@ -1705,33 +1707,56 @@ __global__ void __launch_bounds__(1024)
   }
 }
 
-// One wave per row: x[row, :F] (F <= 256) -> the compressed row [8 mask words | kept values] of
-// spmm_device.h ("compressed rows").  Kept = bit pattern other than +0.0.
+// One wave per kZipRows rows: x[row, :F] (F <= 256), times row_scale[row] when given (one fp32
+// multiply per element, what the dgrad epilogue does for its row-scaled copy) -> the compressed row
+// [8 mask words | kept values] of spmm_device.h ("compressed rows").  Kept = bit pattern other than
+// +0.0.  The loads of all kZipRows rows are issued before the first row is packed (one row per
+// wave left a single 1 KiB request in flight per wave; cf. rows_pack_kernel above).
+constexpr int kZipRows = 4;
 __global__ void __launch_bounds__(kBlock)
     rows_compress_kernel(const float* __restrict__ x, int64_t ldx, int64_t n_rows, int F,
-                         uint32_t* __restrict__ out, int64_t ldo) {
+                         const float* __restrict__ row_scale, uint32_t* __restrict__ out,
+                         int64_t ldo) {
   const int lane = lane_id();
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block();
-  if (row >= n_rows) return;
-  uint32_t v[4];
-  uint32_t nib = 0;
+  const int64_t row0 =
+      (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_in_block()) * kZipRows;
+  if (row0 >= n_rows) return;
+  float xv[kZipRows][4], sc[kZipRows];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = 4 * lane + i;
-    v[i] = c < F ? __float_as_uint(x[row * ldx + c]) : 0u;
-    nib |= (v[i] != 0u ? 1u : 0u) << i;
+  for (int r = 0; r < kZipRows; ++r) {
+    int64_t row = row0 + r;
+    row = row < n_rows ? row : n_rows - 1;  // (clamped: the loads are unconditional)
+    sc[r] = row_scale ? row_scale[row] : 1.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = 4 * lane + i;
+      xv[r][i] = c < F ? x[row * ldx + c] : 0.f;
+    }
   }
-  uint32_t word = nib << (4 * (lane & 7));
-  word |= __shfl_xor(word, 1, kWave);
-  word |= __shfl_xor(word, 2, kWave);
-  word |= __shfl_xor(word, 4, kWave);
-  uint32_t nib2;
-  int off = zrow_lane_offset(word, lane, nib2);
-  uint32_t* __restrict__ orow = out + row * ldo;
-  if ((lane & 7) == 0) orow[lane >> 3] = word;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (nib & (1u << i)) orow[kZrowHdr + off++] = v[i];
+  for (int r = 0; r < kZipRows; ++r) {
+    const int64_t row = row0 + r;
+    if (row >= n_rows) break;  // (uniform)
+    uint32_t v[4];
+    uint32_t nib = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = 4 * lane + i;
+      v[i] = c < F ? __float_as_uint(row_scale ? __fmul_rn(xv[r][i], sc[r]) : xv[r][i]) : 0u;
+      nib |= (v[i] != 0u ? 1u : 0u) << i;
+    }
+    uint32_t word = nib << (4 * (lane & 7));
+    word |= __shfl_xor(word, 1, kWave);
+    word |= __shfl_xor(word, 2, kWave);
+    word |= __shfl_xor(word, 4, kWave);
+    uint32_t nib2;
+    int off = zrow_lane_offset(word, lane, nib2);
+    uint32_t* __restrict__ orow = out + row * ldo;
+    if ((lane & 7) == 0) orow[lane >> 3] = word;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (nib & (1u << i)) orow[kZrowHdr + off++] = v[i];
+    }
   }
 }
 
@@ -1774,16 +1799,23 @@ int pygamd_spmm_csr(const pygamd_spmm_args* args, void* workspace, size_t worksp
   });
 }
 
-int pygamd_rows_compress(const float* x, int64_t ldx, int64_t n_rows, int64_t F, uint32_t* out,
-                         int64_t ld_out, void* stream) {
+int pygamd_rows_compress_scaled(const float* x, int64_t ldx, int64_t n_rows, int64_t F,
+                                const float* row_scale, uint32_t* out, int64_t ld_out,
+                                void* stream) {
   if (n_rows < 0 || F < 0 || F > 256 || ldx < F || ld_out < F + 12) return PYGAMD_ERR_INVALID_ARG;
   if (n_rows == 0) return PYGAMD_OK;
   if (!out || (F > 0 && !x)) return PYGAMD_ERR_INVALID_ARG;
-  dim3 grid(static_cast<unsigned>(ceil_div(n_rows, static_cast<int64_t>(kWavesPerBlock))));
+  dim3 grid(static_cast<unsigned>(
+      ceil_div(n_rows, static_cast<int64_t>(kWavesPerBlock) * kZipRows)));
   hipLaunchKernelGGL(rows_compress_kernel, grid, dim3(kBlock), 0, as_stream(stream), x, ldx,
-                     n_rows, static_cast<int>(F), out, ld_out);
+                     n_rows, static_cast<int>(F), row_scale, out, ld_out);
   PYGAMD_LAUNCH_CHECK();
   return PYGAMD_OK;
+}
+
+int pygamd_rows_compress(const float* x, int64_t ldx, int64_t n_rows, int64_t F, uint32_t* out,
+                         int64_t ld_out, void* stream) {
+  return pygamd_rows_compress_scaled(x, ldx, n_rows, F, nullptr, out, ld_out, stream);
 }
 
 int pygamd_rows_pack(const float* g, int64_t ldg, int64_t n_rows, int64_t F,

@@ -144,11 +144,20 @@ __device__ __forceinline__ void spmm_batch(const SpmmDev<IdxT>& a, int j, int cn
 // row gather on this chip is proportional to the lines it touches (scripts/gather_lines_probe.py:
 // 10.1 ms for 8 lines per row, 6.0 ms for 5, 4.6 ms for 4 at the products shape).  Lossless: the
 // sums below add the same values in the same order as the dense gather (a dropped +0.0 changes no
-// sum).  Lane l of the wave that reads a row owns columns 4 l .. 4 l + 3: its mask nibble is bits
-// 4 (l & 7) .. + 3 of word l >> 3, its values start at (kept in the words below) + (kept in the
-// lower nibbles of its word).
+// sum).
+//
+// The writers (rows_compress_kernel, fused_compress_tile) own columns 4 l .. 4 l + 3 per lane
+// (zrow_lane_offset).  The READER does not: lane l of the wave that decodes a row owns columns
+// l, l + 64, l + 128, l + 192.  The mask of column chunk k is then the 64-bit lane mask made of
+// header words 2 k, 2 k + 1 — the same for the whole wave, so the eight header words of a row come
+// in as ONE scalar load of 32 bytes (the source row id is wave-uniform) — and lane l's value of
+// chunk k sits at word  8 + kept(chunks < k) + (set bits of mask_k below lane l): scalar popcounts
+// plus v_mbcnt_lo / v_mbcnt_hi.  The lanes whose bit is set read consecutive dwords: one coalesced
+// request of exactly the kept bytes per chunk (the slack words behind a row are never read).
 constexpr int kZrowHdr = 8;
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+typedef const __attribute__((address_space(4))) u32x8* zrow_hdr_ptr;  // read-only: scalar loads
+typedef const __attribute__((address_space(1))) uint32_t* zrow_ptr;   // (global, not flat, loads)
 
 // exclusive prefix over the eight 8-lane groups of a wave of a value `t` that is equal inside each
 // group (three DPP adds: the other half of the 16-lane row, then row 0 -> 1 / 2 -> 3, then the
@@ -160,7 +169,8 @@ __device__ __forceinline__ int group8_exclusive_prefix(int t) {
   return a3 - t;
 }
 
-// (offset of the lane's first kept value, its mask nibble) from the lane's mask word
+// writers: (offset of the lane's first kept value, its mask nibble) from the mask word that holds
+// the nibble of the lane's columns 4 l .. 4 l + 3
 __device__ __forceinline__ int zrow_lane_offset(uint32_t hw, int lane, uint32_t& nib) {
   const int sh = (lane & 7) * 4;
   nib = (hw >> sh) & 15u;
@@ -168,47 +178,93 @@ __device__ __forceinline__ int zrow_lane_offset(uint32_t hw, int lane, uint32_t&
   return group8_exclusive_prefix(__popc(hw)) + below;
 }
 
-// the lane's four columns from its (up to four) kept values p[0..]
-__device__ __forceinline__ void zrow_expand(uint32_t nib, const f32x4u& p, float (&o)[4]) {
-  const bool b0 = nib & 1u, b1 = nib & 2u, b2 = nib & 4u, b3 = nib & 8u;
-  const int r2 = (b0 ? 1 : 0) + (b1 ? 1 : 0);
-  const int r3 = r2 + (b2 ? 1 : 0);
-  o[0] = b0 ? p[0] : 0.f;
-  o[1] = b1 ? (b0 ? p[1] : p[0]) : 0.f;
-  o[2] = b2 ? (r2 == 0 ? p[0] : (r2 == 1 ? p[1] : p[2])) : 0.f;
-  o[3] = b3 ? (r3 == 0 ? p[0] : (r3 == 1 ? p[1] : (r3 == 2 ? p[2] : p[3]))) : 0.f;
+// the headers of the U source rows of slots j .. j + U - 1 (past cnt: the last slot's again).
+// PIN: the slot number passes through an opaque scalar, which keeps the loads at this point of the
+// program (hipcc otherwise merges the in-loop call with the one in front of the loop and issues the
+// loads at the loop head, behind the wait for the previous batch's values).
+// (row id and pitch in bytes are below 2^32: one 32 x 32 -> 64 bit product on the scalar unit)
+template <typename IdxT, int U, bool PIN>
+__device__ __forceinline__ void zrows_headers(const SpmmDev<IdxT>& a, int j, int cnt, IdxT myc,
+                                              zrow_ptr (&base)[U], u32x8 (&h)[U]) {
+  const __attribute__((address_space(1))) char* rows =
+      (const __attribute__((address_space(1))) char*)(a.x);
+  const uint32_t pitch = static_cast<uint32_t>(a.ldx) * 4u;  // bytes
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    int k = j + u;
+    k = k < cnt ? k : cnt - 1;
+    if constexpr (PIN) asm volatile("" : "+s"(k));
+    const uint32_t c = static_cast<uint32_t>(bcast_uniform(static_cast<int32_t>(myc), k));
+    base[u] = (zrow_ptr)(rows + static_cast<uint64_t>(c) * pitch);
+    h[u] = *(zrow_hdr_ptr)(base[u]);
+  }
 }
 
-// U source rows of a compressed block into acc (one wave per destination row, 64 lanes x 4 columns):
-// the U mask words are in flight together, then the U value loads.
-template <typename IdxT, bool FULL, int U>
-__device__ __forceinline__ void spmm_batch_zrows(const SpmmDev<IdxT>& a, int j, int cnt, IdxT myc,
-                                                  int lane, float (&acc)[1][4]) {
-  const uint32_t* __restrict__ rows = reinterpret_cast<const uint32_t*>(a.x);
-  const uint32_t* base[U];
-  uint32_t hw[U];
+// One batch: the 4 U value loads are issued under the chunk masks (a lane whose bit is clear
+// issues nothing and keeps +0.0), then the header loads of the NEXT batch — the masks are dead once
+// the value loads are out, and the headers complete under them: the mask round trip is paid once
+// per staged index chunk, not once per batch — then the values are added in slot order.
+// FULL: all U slots exist; otherwise the slots from cnt on add +0.0.
+template <typename IdxT, int U, bool FULL>
+__device__ __forceinline__ void zrows_batch(const SpmmDev<IdxT>& a, int j, int cnt, IdxT myc,
+                                            zrow_ptr (&base)[U], u32x8 (&h)[U],
+                                            float (&zacc)[4]) {
+  float v[U][4];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int k = j + u;
-    const int kk = FULL ? k : (k < cnt ? k : cnt - 1);
-    const IdxT c = bcast_uniform(myc, kk);
-    base[u] = rows + static_cast<int64_t>(c) * a.ldx;
-    hw[u] = base[u][lane >> 3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[u][k] = 0.f;
+    if (FULL || j + u < cnt) {  // (uniform: a slot past the end is one scalar branch)
+      int kept = kZrowHdr;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t lo = h[u][2 * k], hi = h[u][2 * k + 1];
+        const uint64_t m = (static_cast<uint64_t>(hi) << 32) | lo;
+        if (__builtin_amdgcn_inverse_ballot_w64(m)) {
+          const int off = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0)) + kept;
+          v[u][k] = __uint_as_float(base[u][off]);
+        }
+        kept += __popcll(m);
+      }
+    }
   }
-  f32x4u v[U];
-  uint32_t nib[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int off = zrow_lane_offset(hw[u], lane, nib[u]);
-    if (!FULL && j + u >= cnt) nib[u] = 0u;
-    v[u] = *reinterpret_cast<const f32x4u*>(base[u] + kZrowHdr + off);
+  if constexpr (FULL) {  // (a partial batch is the chunk's last)
+    __builtin_amdgcn_sched_barrier(0);
+    zrows_headers<IdxT, U, true>(a, j + U, cnt, myc, base, h);
+    __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    float o[4];
-    zrow_expand(nib[u], v[u], o);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc[0][i] += o[i];
+    for (int k = 0; k < 4; ++k) zacc[k] += v[u][k];
+  }
+}
+
+// The slots [0, cnt) of one staged index chunk, U source rows at a time, into zacc[k] = column
+// lane + 64 k.
+template <typename IdxT, int U>
+__device__ __forceinline__ void spmm_zrows(const SpmmDev<IdxT>& a, int cnt, IdxT myc,
+                                           float (&zacc)[4]) {
+  zrow_ptr base[U];
+  u32x8 h[U];
+  zrows_headers<IdxT, U, false>(a, 0, cnt, myc, base, h);
+  int j = 0;
+  for (; j + U <= cnt; j += U) zrows_batch<IdxT, U, true>(a, j, cnt, myc, base, h, zacc);
+  if (j < cnt) zrows_batch<IdxT, U, false>(a, j, cnt, myc, base, h, zacc);
+}
+
+// zacc[k] = column lane + 64 k  ->  o[i] = column 4 lane + i (the lane shape of the dense row
+// kernels: 64 lanes x 4 consecutive columns).  Column 4 l + i lives in lane (4 l + i) & 63,
+// chunk l >> 4.  Once per destination row.
+__device__ __forceinline__ void zrows_to_vec4(const float (&zacc)[4], int lane, float (&o)[4]) {
+  const int src = (lane & 15) * 4;
+  const int kq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = __shfl(zacc[k], src + i, kWave);
+    o[i] = kq == 0 ? t[0] : (kq == 1 ? t[1] : (kq == 2 ? t[2] : t[3]));
   }
 }
 
@@ -227,6 +283,7 @@ __device__ __forceinline__ void spmm_accumulate(const SpmmDev<IdxT>& a, IdxT sta
   constexpr int STEP = EPI * U;
   const int sub = lane / LPR;
   bool sparse_src = false;
+  float zacc[4] = {0.f, 0.f, 0.f, 0.f};  // WMODE 4: column lane + 64 k (see "compressed rows")
   if constexpr (WMODE == 3) {
     sparse_src = a.src_bits_set == nullptr || 2 * *a.src_bits_set < a.n_src;
   }
@@ -272,8 +329,7 @@ __device__ __forceinline__ void spmm_accumulate(const SpmmDev<IdxT>& a, IdxT sta
     int j = 0;
     if constexpr (WMODE == 4) {
       static_assert(LPR == kWave && VW == 4 && CH == 1 && !IDENT, "compressed rows: 64 lanes x 4");
-      for (; j + U <= cnt; j += U) spmm_batch_zrows<IdxT, true, U>(a, j, cnt, myc, lane, acc);
-      if (j < cnt) spmm_batch_zrows<IdxT, false, U>(a, j, cnt, myc, lane, acc);
+      spmm_zrows<IdxT, U>(a, cnt, myc, zacc);
     } else {
       for (; j + STEP <= cnt; j += STEP) {
         spmm_batch<IdxT, VW, LPR, CH, WMODE, IDENT, true, UF>(a, j, cnt, sub, myc, mye, mym, fo,
@@ -284,6 +340,12 @@ __device__ __forceinline__ void spmm_accumulate(const SpmmDev<IdxT>& a, IdxT sta
                                                                fv, head, acc);
       }
     }
+  }
+  if constexpr (WMODE == 4) {  // (an accumulator that starts at +0.0 never becomes -0.0: the
+    float o[4];                // sum added to a zero acc keeps its bits)
+    zrows_to_vec4(zacc, lane, o);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[0][i] += o[i];
   }
 }
 

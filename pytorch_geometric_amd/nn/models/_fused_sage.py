@@ -64,12 +64,34 @@ OVERLAP_WGS = int(os.environ.get('PYGAMD_OVERLAP_WGS', '1'))  # workgroups per C
 # as compressed rows (8 mask words + the non-zero values, csrc/spmm_device.h) and the next layer
 # gathers those: a row gather costs what the 128-byte lines it touches cost (10.1 ms for 8 lines per
 # row, 6.0 ms for 5: scripts/gather_lines_probe.py) and half of a ReLU output is exact zeros.
-# Lossless, same sums bit for bit — but NOT faster inside the one-kernel layer on this chip
-# (products shape: 16.8 ms against 12.9 ms for the layer that gathers, +0.8 ms for the layer that
-# writes): decoding a row is ~35 VALU instructions per lane against 4 adds, and the mask word has to
-# arrive before the values can be addressed (two dependent loads per source row with 4 waves per
-# SIMD).  CHANGELOG.md §5a.
+# Lossless, same sums bit for bit — but NOT faster in this form (measured in round 3 with the
+# nibble-per-lane decoder on the fp32 schedule, products shape: 16.8 ms against 12.9 ms for the
+# layer that gathers, +0.8 ms for the layer that writes; CHANGELOG.md §5a).  The decoder has since
+# been replaced (one 64-column chunk per load, csrc/spmm_device.h) and the default route below does
+# gain; this switch still selects the epilogue writer, whose launches run the fp32 schedule, and
+# takes precedence when set.
 COMPRESS_ROWS = os.environ.get('PYGAMD_COMPRESS_ROWS', '0') != '0'
+
+
+# What does pay is the stand-alone pass (`_native.rows_compress`, ~1 ms for a [2.45 M, 256] block)
+# in front of a one-kernel layer on the split schedule, whose gather decodes with one lane per
+# column of a 64-column chunk (scalar header loads, mbcnt offsets, coalesced value loads:
+# csrc/spmm_device.h "compressed rows"):
+#   forward   a one-kernel 'post' layer of more than 128 input columns gathers the compressed copy
+#             of the ReLU output below it (the dense rows stay the root operand);
+#   backward  the one-launch input gradient gathers the compressed copy of the masked gradient that
+#             `linear_dgrad(relu_bits=...)` hands down, scaled by 1/deg in the compress pass — the
+#             dgrad then writes no dense scaled copy.
+# Same sums bit for bit (tests/test_gpu_compressed_gather.py).  A hidden activation with few zeros
+# makes it a loss (the pass, then 9 lines per row instead of 8): PYGAMD_COMPRESS_GATHER=0 (read at
+# every call) switches it off.  The compressed block takes N x 1152 bytes while it lives.
+def compress_gather_enabled() -> bool:
+    return os.environ.get('PYGAMD_COMPRESS_GATHER', '1') != '0'
+
+
+def _compress_gather_ok(t: Tensor, width: int) -> bool:
+    return (t.is_cuda and width > 128 and width % 4 == 0 and compress_gather_enabled()
+            and _native.SAGE_FUSED_VARIANT <= 1 and not _native.SAGE_FUSED_PROBE)
 # backward of a 'pre' layer: find the all-zero rows of the incoming gradient in the pass that lays
 # it out and skip them in the transposed aggregation (PYGAMD_SPARSE_GRAD=0: read every row)
 SPARSE_GRAD = os.environ.get('PYGAMD_SPARSE_GRAD', '1') != '0'
@@ -316,6 +338,8 @@ class FusedSageStack(Function):
                                 and one_kernel_post(layer + 1)):
                             znext = torch.empty(N, _native.compressed_pitch(Fo),
                                                 dtype=torch.int32, device=dev)
+                    if zsrc is None and layer > 0 and not lone and _compress_gather_ok(inp, Fi):
+                        zsrc = _native.rows_compress(inp)  # (`inp`: the ReLU output below)
                     # the aggregated rows are stored once (write-only) for the weight gradient
                     _native.sage_layer_forward(fwd.ptr, fwd.idx, src if zsrc is None else zsrc,
                                                inp if lone else buf[:, Fi:],
@@ -422,12 +446,14 @@ class FusedSageStack(Function):
                     and _native.sage_layer_forward_supported(Fo, Fi, 'sum'))
 
         g_scaled = None  # g * (1 / deg) per row, when the producer of `g` wrote it as well
+        g_z = None       # ... or the same rows as a compressed block (see compress_gather_enabled)
         live_src = None  # the live-source lists that cover the zero rows of `g` / `g_scaled`
         for layer in reversed(range(L)):
             buf, wmat = bufs[layer], wmats[layer]
             Fi, Fo = ctx.dims[layer]
             want_b = ctx.has_bias[layer]
             live, live_src = live_src, None  # (lists made by the layer above serve this one only)
+            gz, g_z = g_z, None              # (and so does its compressed copy of `g`)
             if not masked:  # ReLU backward and this layer's bias gradient in one pass
                 h_next = FusedSageStack._input_view(ctx, bufs, layer + 1)  # post-ReLU output
                 g, grads[3 * layer + 1] = _native.relu_backward_colsum(g, h_next, want_b)
@@ -471,7 +497,9 @@ class FusedSageStack(Function):
                     else:
                         gw = torch.mm(g.t(), buf)
                 if one_launch:
-                    if scale is None:
+                    if gz is not None:
+                        gsrc = gz
+                    elif scale is None:
                         gsrc = g
                     elif g_scaled is not None:
                         gsrc = g_scaled
@@ -489,6 +517,8 @@ class FusedSageStack(Function):
                     # (`live`: the gather source came from the 'pre' layer above and is zero
                     # outside the rows its lists keep — same sums, fewer rows read)
                     lists = {} if live is None else {'rowend': live.end}
+                    if gz is not None:
+                        lists['gather_width'] = Fo
                     _native.sage_layer_forward(bwd.ptr, bwd.idx if live is None else live.col,
                                                gsrc, g, wc, None, 'sum', False,
                                                scratch, gin, hub=bwd.hub, save_agg=False,
@@ -595,12 +625,18 @@ class FusedSageStack(Function):
                             and not torch.cuda.is_current_stream_capturing()):
                         live_src = _live_update(bwd, N, row_bits, n_set)
                     if own:
-                        if scaled_for_next:
+                        # the masked gradient goes down as compressed rows (1/deg applied by the
+                        # compress pass) instead of as a dense scaled copy
+                        zip_next = (layer > 0 and bits_in is not None and fused_bwd(layer - 1)
+                                    and _compress_gather_ok(g, Fi))
+                        if scaled_for_next and not zip_next:
                             g_scaled = torch.empty(N, Fi, dtype=torch.float32, device=g.device)
                         g = _native.linear_dgrad(gy, wmat.t().contiguous(),
-                                                 row_scale=scale if scaled_for_next else None,
+                                                 row_scale=scale if g_scaled is not None else None,
                                                  relu_mask=mask_f, relu_bits=bits_in,
                                                  out_scaled=g_scaled)
+                        if zip_next:
+                            g_z = _native.rows_compress(g, row_scale=scale)
                     else:
                         g = torch.mm(gy, wmat)
             masked = mask_in is not None
