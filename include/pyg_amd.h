@@ -1302,6 +1302,58 @@ PYGAMD_API int pygamd_mixture_coef_grad(const pygamd_csr* g, const void* edge_id
                                         int64_t n_cols, int64_t F, int64_t K, float* grad_coef,
                                         void* stream);
 
+/* ---- per-graph normalisation: GraphNorm and LayerNorm(mode='graph') --------------------------------
+ * (nn/norm/graph_norm.py:72-76, nn/norm/layer_norm.py:82-108).  The reference forms the statistics
+ * with two scatters, broadcasts them back with two index selects and makes about eight elementwise
+ * passes over [N, F], keeping several of those planes for the backward.  Here the handle g is the
+ * BY-GRAPH pointer of a sorted batch vector: rowptr = ptr [B + 1] (pygamd_index2ptr), graph b owns
+ * the rows [ptr[b], ptr[b + 1]) of x, col is not read (NULL), and the hub plan over ptr cuts a graph
+ * of more than hub_threshold nodes into chunks of hub_chunk nodes.  n is the row count of x.
+ *   PYGAMD_NORM_CHANNEL (GraphNorm), per (graph, column): m = mean(x), u = x - mean_scale m,
+ *       v = mean(u^2), y = weight u / sqrt(v + eps) + bias;
+ *   PYGAMD_NORM_GRAPH (LayerNorm), one mean and variance per graph over its n_g F elements (counts
+ *       max(n_g, 1) F): y = (x - m) / sqrt(v + eps) weight + bias; std_eps = 1 divides by
+ *       sqrt(v) + eps instead, the reference's formula without a batch vector (layer_norm.py:87-88).
+ * weight, bias, mean_scale are [F] or NULL (1, 0, 1); mean_scale must be NULL in GRAPH mode and
+ * std_eps 0 in CHANNEL mode.  x, y, grad_y and grad_x have row strides (floats): a column block of
+ * a wider plane is read and written in place, all index arithmetic is 64-bit.
+ * Statistics: ONE pass of sums shifted by the graph's first row, s1 = sum(x - k), s2 = sum((x -
+ * k)^2); GraphNorm's v = sigma^2 + (1 - mean_scale)^2 m^2 needs no pass over u.
+ * forward: ONE launch when no graph is a hub — a 64-lane wave per graph, lanes over the columns,
+ *   statistics and then y from the same rows; with hub graphs three: the chunks' partial sums go to
+ *   the workspace, a merge adds them in chunk order, an apply launch covers the chunks.  Saved for
+ *   the backward: mean (m, not mean_scale m) and rstd = 1 / sqrt(v + eps), [B, F] in CHANNEL and
+ *   [B] in GRAPH mode.  Empty graphs are legal anywhere and own no rows.
+ * backward: the same launch shape over (x, grad_y): with g = grad_y weight, u^ = u rstd,
+ *   grad_u = (g - u^ mean_graph(g u^)) rstd and, CHANNEL, grad_x = grad_u - mean_scale
+ *   mean_graph(grad_u); GRAPH: both means over all elements of the graph.  grad_weight = sum grad_y
+ *   u^, grad_bias = sum grad_y, grad_mean_scale = -sum_graphs m sum_i grad_u (each [F] or NULL: not
+ *   wanted; grad_mean_scale NULL in GRAPH mode) come from per-workgroup partials summed by one more
+ *   launch in an order that depends on their number only.
+ * pygamd_graph_norm_supported(F): 1 <= F <= 512, otherwise status 2.  There is no workspace query:
+ *   forward   8 F n_chunks bytes (none without hub graphs),
+ *   backward  4 F (2 n_chunks + 3 n_hub + 3 PYGAMD_GRAPH_NORM_BLOCKS) bytes,
+ * and a smaller workspace is status 3.  No float atomics, every grid a function of (B, n_chunks)
+ * only: bitwise reproducible, and a graph's rows depend on that graph's rows only.  Status 1 / 2 / 3
+ * before any device work; n_rows == 0 returns 0.  fp32 data, int32 / int64 ptr.                    */
+typedef enum { PYGAMD_NORM_CHANNEL = 0, PYGAMD_NORM_GRAPH = 1 } pygamd_norm_mode;
+#define PYGAMD_GRAPH_NORM_BLOCKS 1024
+PYGAMD_API int pygamd_graph_norm_supported(int64_t F);
+PYGAMD_API int pygamd_graph_norm_forward(const pygamd_csr* g, int mode, const float* x, int64_t ldx,
+                                         int64_t n, int64_t F, const float* weight,
+                                         const float* bias, const float* mean_scale, float eps,
+                                         int std_eps, float* y, int64_t ldy, float* mean,
+                                         float* rstd, void* workspace, size_t workspace_bytes,
+                                         void* stream);
+PYGAMD_API int pygamd_graph_norm_backward(const pygamd_csr* g, int mode, const float* x,
+                                          int64_t ldx, const float* grad_y, int64_t ldg, int64_t n,
+                                          int64_t F, const float* weight, const float* mean_scale,
+                                          float eps, int std_eps, const float* mean,
+                                          const float* rstd, float* grad_x, int64_t ldgx,
+                                          float* grad_weight, float* grad_bias,
+                                          float* grad_mean_scale, void* workspace,
+                                          size_t workspace_bytes, void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

@@ -1413,3 +1413,40 @@ def cross_entropy(logits: Tensor, target: Tensor, index: Optional[Tensor] = None
     if index is None:
         return torch.nn.functional.cross_entropy(logits, target)
     return torch.nn.functional.cross_entropy(logits[index], target[index])
+
+
+class GraphNormFunction(Function):
+    """Per-graph normalisation of the rows of ``x [N, F]`` over the graphs of a by-graph handle
+    (``_norm.BatchHandle``: ``ptr`` and its hub plan), csrc/graph_norm.hip:
+
+    * ``mode='channel'`` — GraphNorm (graph_norm.py:72-76): ``weight * u / sqrt(mean(u^2) + eps) +
+      bias`` with ``u = x - mean_scale * mean(x)``, statistics per graph and column;
+    * ``mode='graph'`` — LayerNorm over whole graphs (layer_norm.py:82-108); ``std_eps`` selects
+      the reference's formula without a batch vector, ``/ (std + eps)``.
+
+    One launch forward and two backward when no graph is longer than the plan's threshold (three
+    and four otherwise).  Saved: ``x``, the parameters and the per-graph ``mean`` and ``rstd`` —
+    nothing of size ``N x F``."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                mean_scale: Optional[Tensor], handle, eps: float, mode: str,
+                std_eps: bool = False):
+        y, mean, rstd = _native.graph_norm_forward(handle.ptr, x, weight, bias, mean_scale, eps,
+                                                   mode, std_eps=std_eps, hub=handle.hub)
+        ctx.save_for_backward(x, weight, mean_scale, mean, rstd)
+        ctx.handle, ctx.eps, ctx.mode, ctx.std_eps = handle, eps, mode, bool(std_eps)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y: Tensor):
+        x, weight, mean_scale, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_x, g_w, g_b, g_ms = _native.graph_norm_backward(
+            ctx.handle.ptr, x, grad_y, mean, rstd, weight, mean_scale, ctx.eps, ctx.mode,
+            std_eps=ctx.std_eps, hub=ctx.handle.hub, want_weight=need[1] and weight is not None,
+            want_bias=need[2] and ctx.has_bias,
+            want_mean_scale=need[3] and mean_scale is not None)
+        return g_x if need[0] else None, g_w, g_b, g_ms, None, None, None, None

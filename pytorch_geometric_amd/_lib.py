@@ -339,6 +339,12 @@ SIGNATURES = {
                                       c_size_t, _P]),
     'pygamd_mixture_coef_grad': (c_int, [_G, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P,
                                          _P]),
+    'pygamd_graph_norm_supported': (c_int, [c_int64]),
+    'pygamd_graph_norm_forward': (c_int, [_G, c_int, _P, c_int64, c_int64, c_int64, _P, _P, _P,
+                                          c_float, c_int, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    'pygamd_graph_norm_backward': (c_int, [_G, c_int, _P, c_int64, _P, c_int64, c_int64, c_int64,
+                                           _P, _P, c_float, c_int, _P, _P, _P, c_int64, _P, _P,
+                                           _P, _P, c_size_t, _P]),
 }
 
 # include/pyg_amd_lab.h: schedules measured and not adopted + timing probes (NOT the boundary;

@@ -2780,6 +2780,147 @@ def mixture_coef_grad(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], wi
     return grad
 
 
+# ---- per-graph normalisation (csrc/graph_norm.hip) -------------------------------------------------
+# The hub plan over a by-graph pointer: a graph of more than GRAPH_NORM_THRESHOLD nodes is walked as
+# chunks of GRAPH_NORM_CHUNK nodes, one wave each (profiles/graph_norm.md).
+GRAPH_NORM_THRESHOLD = 256
+GRAPH_NORM_CHUNK = 128
+GRAPH_NORM_BLOCKS = 1024   # PYGAMD_GRAPH_NORM_BLOCKS of include/pyg_amd.h
+NORM_MODES = {'channel': 0, 'graph': 1}
+
+
+def graph_norm_supported(F: int) -> bool:
+    """The per-graph normalisation kernels serve rows of ``1 <= F <= 512`` floats."""
+    return bool(_lib.load().pygamd_graph_norm_supported(int(F)))
+
+
+def graph_norm_workspace_bytes(n_chunks: int, n_hub: int, F: int, backward: bool) -> int:
+    """The workspace formula include/pyg_amd.h states for ``pygamd_graph_norm_*`` (there is no
+    query in the C ABI): the chunks' partial sums and, backward, the hub graphs' coefficients and
+    the workgroups' partials of the parameter gradients."""
+    if backward:
+        return 4 * F * (2 * n_chunks + 3 * n_hub + 3 * GRAPH_NORM_BLOCKS)
+    return 8 * F * n_chunks
+
+
+def graph_norm_plan(ptr: Tensor) -> HubPlan:
+    """The hub plan of a by-graph pointer at this kernel's threshold and chunk."""
+    return hub_plan(ptr, GRAPH_NORM_THRESHOLD, GRAPH_NORM_CHUNK)
+
+
+def _norm_handle(ptr: Tensor, hub: Optional[HubPlan]) -> Csr:
+    """``pygamd_csr`` of a by-graph pointer: no column array, the plan's own threshold and chunk"""
+    if hub is None:
+        hub = no_hubs(GRAPH_NORM_THRESHOLD, GRAPH_NORM_CHUNK)
+    rows, cptr, n_hub, n_chunks, threshold, chunk = hub
+    g = Csr(rowptr=ptr.data_ptr(), col=None, idx_dtype=_idx_dtype(ptr), n_rows=ptr.numel() - 1,
+            hub_rows=None if rows is None else rows.data_ptr(),
+            hub_chunk_ptr=None if cptr is None else cptr.data_ptr(), n_hub=n_hub,
+            n_chunks=n_chunks, hub_threshold=threshold, hub_chunk=chunk)
+    g._keep = (ptr, hub)
+    return g
+
+
+def _norm_param(t: Optional[Tensor], F: int, name: str) -> Optional[Tensor]:
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or tuple(t.shape) != (F, ):
+        raise ValueError(f"'{name}' must be a float32 [{F}] tensor (got {t.dtype} "
+                         f"{tuple(t.shape)})")
+    return t.contiguous()
+
+
+def _norm_mode(mode: str, mean_scale, std_eps: bool) -> int:
+    if mode not in NORM_MODES:
+        raise ValueError(f"'mode' must be 'channel' or 'graph' (got {mode!r})")
+    if mode == 'graph' and mean_scale is not None:
+        raise ValueError("'mean_scale' belongs to mode='channel'")
+    if mode == 'channel' and std_eps:
+        raise ValueError("'std_eps' belongs to mode='graph'")
+    return NORM_MODES[mode]
+
+
+def graph_norm_forward(ptr: Tensor, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+                       mean_scale: Optional[Tensor], eps: float, mode: str, *,
+                       std_eps: bool = False, hub: Optional[HubPlan] = None):
+    """``(y [N, F], mean, rstd)`` of GraphNorm (``mode='channel'``: statistics per graph and column,
+    ``mean`` / ``rstd [B, F]``) or of LayerNorm over whole graphs (``mode='graph'``: ``[B]``) for
+    the graphs ``ptr [B + 1]`` of the rows of ``x``, which may be a column block of a wider tensor;
+    ``std_eps``: divide by ``sqrt(var) + eps``.  ``hub``: :func:`graph_norm_plan` of ``ptr``."""
+    _require_device(ptr, x, weight, bias, mean_scale)
+    lib = _lib.load()
+    if x.dim() != 2:
+        raise ValueError("'x' must be two-dimensional")
+    N, F = x.shape
+    x = _strided_rows(x, 'x', F)
+    weight, bias = _norm_param(weight, F, 'weight'), _norm_param(bias, F, 'bias')
+    mean_scale = _norm_param(mean_scale, F, 'mean_scale')
+    m = _norm_mode(mode, mean_scale, std_eps)
+    B = ptr.numel() - 1
+    dev = x.device
+    y = torch.empty(N, F, dtype=torch.float32, device=dev)
+    stats = (B, F) if mode == 'channel' else (B, )
+    if B <= 0 or F == 0 or N == 0:   # no row anywhere: nothing to launch
+        return y, x.new_zeros(stats), x.new_zeros(stats)
+    mean = torch.empty(stats, dtype=torch.float32, device=dev)
+    rstd = torch.empty(stats, dtype=torch.float32, device=dev)
+    g = _norm_handle(ptr, hub)
+    ws_bytes = graph_norm_workspace_bytes(g.n_chunks, g.n_hub, F, False)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    with _timed({'kind': 'graph_norm', 'op': 'forward', 'mode': mode, 'B': B, 'N': N, 'F': F,
+                 'ld': _ld(x), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x):
+        check(lib.pygamd_graph_norm_forward(
+            ctypes.byref(g), m, _p(x), _ld(x), N, F, _p(weight), _p(bias), _p(mean_scale),
+            float(eps), int(bool(std_eps)), _p(y), F, _p(mean), _p(rstd), _p(ws), ws_bytes,
+            _stream(x)), 'graph_norm_forward')
+    return y, mean, rstd
+
+
+def graph_norm_backward(ptr: Tensor, x: Tensor, grad_y: Tensor, mean: Tensor, rstd: Tensor,
+                        weight: Optional[Tensor], mean_scale: Optional[Tensor], eps: float,
+                        mode: str, *, std_eps: bool = False, hub: Optional[HubPlan] = None,
+                        want_weight: bool = False, want_bias: bool = False,
+                        want_mean_scale: bool = False):
+    """``(grad_x [N, F], grad_weight, grad_bias, grad_mean_scale)`` from the forward's inputs and
+    its saved ``mean`` and ``rstd``; a parameter gradient that is not wanted is None."""
+    _require_device(ptr, x, grad_y, mean, rstd, weight, mean_scale)
+    lib = _lib.load()
+    if x.dim() != 2:
+        raise ValueError("'x' must be two-dimensional")
+    N, F = x.shape
+    x, grad_y = _strided_rows(x, 'x', F), _strided_rows(grad_y, 'grad_y', F)
+    if grad_y.size(0) != N:
+        raise ValueError(f"'grad_y' needs the {N} rows of 'x'")
+    weight, mean_scale = _norm_param(weight, F, 'weight'), _norm_param(mean_scale, F, 'mean_scale')
+    m = _norm_mode(mode, mean_scale, std_eps)
+    if want_mean_scale and mode != 'channel':
+        raise ValueError("'grad_mean_scale' belongs to mode='channel'")
+    B = ptr.numel() - 1
+    stats = (B, F) if mode == 'channel' else (B, )
+    for t, name in ((mean, 'mean'), (rstd, 'rstd')):
+        if t.dtype != torch.float32 or tuple(t.shape) != stats or not t.is_contiguous():
+            raise ValueError(f"'{name}' must be the forward's contiguous float32 {stats} tensor")
+    dev = x.device
+    grad_x = torch.empty(N, F, dtype=torch.float32, device=dev)
+    nothing = B <= 0 or F == 0 or N == 0
+    alloc = torch.zeros if nothing else torch.empty
+    g_w = alloc(F, dtype=torch.float32, device=dev) if want_weight else None
+    g_b = alloc(F, dtype=torch.float32, device=dev) if want_bias else None
+    g_ms = alloc(F, dtype=torch.float32, device=dev) if want_mean_scale else None
+    if nothing:
+        return grad_x, g_w, g_b, g_ms
+    g = _norm_handle(ptr, hub)
+    ws_bytes = graph_norm_workspace_bytes(g.n_chunks, g.n_hub, F, True)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with _timed({'kind': 'graph_norm', 'op': 'backward', 'mode': mode, 'B': B, 'N': N, 'F': F,
+                 'ld': _ld(x), 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x):
+        check(lib.pygamd_graph_norm_backward(
+            ctypes.byref(g), m, _p(x), _ld(x), _p(grad_y), _ld(grad_y), N, F, _p(weight),
+            _p(mean_scale), float(eps), int(bool(std_eps)), _p(mean), _p(rstd), _p(grad_x), F,
+            _p(g_w), _p(g_b), _p(g_ms), _p(ws), ws_bytes, _stream(x)), 'graph_norm_backward')
+    return grad_x, g_w, g_b, g_ms
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

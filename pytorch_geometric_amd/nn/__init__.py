@@ -6,7 +6,8 @@ from .conv import (CGConv, FastRGCNConv, FiLMConv, GINConv, GINEConv, GATConv, G
                    gcn_norm, group)
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
-from .norm import MessageNorm
+from .norm import BatchNorm, GraphNorm, LayerNorm, MessageNorm
+from .pool import global_add_pool, global_max_pool, global_mean_pool
 from . import functional  # noqa: F401
 
 __all__ = [
@@ -16,5 +17,6 @@ __all__ = [
     'HeteroDictLinear', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
     'PNAConv', 'DegreeScalerAggregation', 'GENConv', 'MessageNorm', 'DeepGCNLayer',
     'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv', 'FiLMConv', 'RGATConv',
-    'BasicGNN', 'GCN', 'GraphSAGE', 'GAT',
+    'BasicGNN', 'GCN', 'GraphSAGE', 'GAT', 'GraphNorm', 'LayerNorm', 'BatchNorm',
+    'global_add_pool', 'global_mean_pool', 'global_max_pool',
 ]

@@ -1,4 +1,6 @@
-from typing import Callable, List, Optional, Union
+import copy
+import inspect
+from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 from torch import Tensor
@@ -7,6 +9,7 @@ from torch.nn import ModuleList
 from ...utils import trim_to_layer
 from ..conv import GATConv, GATv2Conv, GCNConv, MessagePassing, SAGEConv
 from ..conv._act_request import has_forward_hooks, request_activation
+from ..norm import normalization_resolver
 
 _ACTS = {'relu': torch.nn.ReLU, 'elu': torch.nn.ELU, 'leaky_relu': torch.nn.LeakyReLU,
          'gelu': torch.nn.GELU, 'tanh': torch.nn.Tanh, 'sigmoid': torch.nn.Sigmoid}
@@ -23,19 +26,35 @@ def activation_resolver(act, **kwargs):
 class BasicGNN(torch.nn.Module):
     r"""Stack of ``num_layers`` message-passing layers with activation / dropout between them —
     the layer loop of ``torch_geometric.nn.models.BasicGNN``
-    (torch_geometric/nn/models/basic_gnn.py:69-274), restricted to ``norm=None`` and ``jk=None``:
+    (torch_geometric/nn/models/basic_gnn.py:69-274), restricted to ``jk=None``:
     ``in -> hidden -> ... -> hidden -> (out_channels or hidden)``; the last layer has no
-    activation; ``num_sampled_*_per_hop`` enables ``trim_to_layer``."""
+    activation; ``num_sampled_*_per_hop`` enables ``trim_to_layer``.
+
+    ``norm`` (a name such as ``'graph_norm'``, ``'layer_norm'``, ``'batch_norm'``, resolved among
+    this package's ``nn.norm`` classes with ``norm_kwargs``, or a module) puts a normalisation
+    layer behind every layer but the last, in the reference's order: activation first if
+    ``act_first``, the norm, the activation otherwise, dropout (basic_gnn.py:258-267).  The copies
+    live in ``self.norms`` (an ``Identity`` for the last layer) and ``supports_norm_batch`` says
+    whether they take the batch vector.  With a norm the layers are not asked to apply bias + ReLU
+    themselves and :class:`GraphSAGE` does not take its fused stack.  With ``norm=None`` there is
+    no ``norms`` attribute and nothing differs from a model built before norms were offered.
+
+    ``forward`` takes ``batch`` and ``batch_size`` for those layers as KEYWORD-ONLY arguments.
+    The reference has them at positions 5 and 6; this class already had
+    ``num_sampled_nodes_per_hop`` and ``num_sampled_edges_per_hop`` there, and positional callers
+    keep their meaning."""
     supports_edge_weight: bool = False
     supports_edge_attr: bool = False
+    supports_norm_batch: bool = False
 
     def __init__(self, in_channels: int, hidden_channels: int, num_layers: int,
                  out_channels: Optional[int] = None, dropout: float = 0.0,
                  act: Union[str, Callable, None] = 'relu', act_first: bool = False,
-                 act_kwargs=None, norm=None, jk: Optional[str] = None, **kwargs):
+                 act_kwargs=None, norm=None, norm_kwargs: Optional[Dict[str, Any]] = None,
+                 jk: Optional[str] = None, **kwargs):
         super().__init__()
-        if norm is not None or jk is not None:
-            raise NotImplementedError("only norm=None and jk=None are supported")
+        if jk is not None:
+            raise NotImplementedError("only jk=None is supported")
         self.in_channels = in_channels
         self.hidden_channels = hidden_channels
         self.num_layers = num_layers
@@ -55,6 +74,14 @@ class BasicGNN(torch.nn.Module):
             self.convs.append(self.init_conv(in_channels, out_channels, **kwargs))
         else:
             self.convs.append(self.init_conv(in_channels, hidden_channels, **kwargs))
+        self.norm = norm if isinstance(norm, str) else None
+        self.norm_kwargs = norm_kwargs
+        if norm is not None:
+            layer = normalization_resolver(norm, hidden_channels, **(norm_kwargs or {}))
+            if hasattr(layer, 'forward'):
+                self.supports_norm_batch = 'batch' in inspect.signature(layer.forward).parameters
+            self.norms = ModuleList([copy.deepcopy(layer) for _ in range(num_layers - 1)])
+            self.norms.append(torch.nn.Identity())
 
     def init_conv(self, in_channels: int, out_channels: int, **kwargs) -> MessagePassing:
         raise NotImplementedError
@@ -62,11 +89,16 @@ class BasicGNN(torch.nn.Module):
     def reset_parameters(self):
         for conv in self.convs:
             conv.reset_parameters()
+        for norm in getattr(self, 'norms', ()):
+            if hasattr(norm, 'reset_parameters'):
+                norm.reset_parameters()
 
     def forward(self, x: Tensor, edge_index, edge_weight: Optional[Tensor] = None,
                 edge_attr: Optional[Tensor] = None,
                 num_sampled_nodes_per_hop: Optional[List[int]] = None,
-                num_sampled_edges_per_hop: Optional[List[int]] = None) -> Tensor:
+                num_sampled_edges_per_hop: Optional[List[int]] = None, *,
+                batch: Optional[Tensor] = None, batch_size: Optional[int] = None) -> Tensor:
+        norms = getattr(self, 'norms', None)
         if (num_sampled_nodes_per_hop is not None and isinstance(edge_weight, Tensor)
                 and isinstance(edge_attr, Tensor)):
             raise NotImplementedError("'trim_to_layer' functionality does not yet support "
@@ -78,7 +110,7 @@ class BasicGNN(torch.nn.Module):
         # nn/conv/_act_request.py), never module state; a layer with forward hooks is not asked
         # (its hooks must see the reference's pre-activation output).
         fuse_ok = isinstance(self.act, torch.nn.ReLU) and isinstance(x, Tensor) and x.is_cuda \
-            and x.dtype == torch.float32 and not has_forward_hooks(self.act)
+            and x.dtype == torch.float32 and not has_forward_hooks(self.act) and norms is None
         for i, conv in enumerate(self.convs):
             if num_sampled_nodes_per_hop is not None:
                 x, edge_index, value = trim_to_layer(
@@ -103,7 +135,14 @@ class BasicGNN(torch.nn.Module):
                 else:
                     x = conv(x, edge_index)
             if i < self.num_layers - 1:
-                if self.act is not None and not fused:
+                if norms is not None:
+                    if self.act is not None and self.act_first:
+                        x = self.act(x)
+                    x = norms[i](x, batch, batch_size) if self.supports_norm_batch \
+                        else norms[i](x)
+                    if self.act is not None and not self.act_first:
+                        x = self.act(x)
+                elif self.act is not None and not fused:
                     x = self.act(x)
                 x = self.dropout(x)
         return x
@@ -133,8 +172,13 @@ class GraphSAGE(BasicGNN):
     def forward(self, x: Tensor, edge_index, edge_weight: Optional[Tensor] = None,
                 edge_attr: Optional[Tensor] = None,
                 num_sampled_nodes_per_hop: Optional[List[int]] = None,
-                num_sampled_edges_per_hop: Optional[List[int]] = None) -> Tensor:
+                num_sampled_edges_per_hop: Optional[List[int]] = None, *,
+                batch: Optional[Tensor] = None, batch_size: Optional[int] = None) -> Tensor:
         from . import _fused_sage, _fused_sage_hops
+        if getattr(self, 'norms', None) is not None:  # the fused stack has no place for a norm
+            return super().forward(x, edge_index, edge_weight, edge_attr,
+                                   num_sampled_nodes_per_hop, num_sampled_edges_per_hop,
+                                   batch=batch, batch_size=batch_size)
         if _fused_sage_hops.eligible(self, x, edge_index, num_sampled_nodes_per_hop,
                                      num_sampled_edges_per_hop):
             return _fused_sage_hops.run(self, x, edge_index, num_sampled_nodes_per_hop,

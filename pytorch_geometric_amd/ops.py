@@ -62,6 +62,9 @@ Operators (all index tensors int32 / int64, features float32):
 ``rgat_aggregate``          ``(Tensor p, Tensor? qi, Tensor? kj, Tensor? b, Tensor rowptr,
                             Tensor col, Tensor rel, int num_relations, int heads,
                             float negative_slope, bool within) -> (Tensor, Tensor)``
+``graph_norm``              ``(Tensor x, Tensor ptr, Tensor? weight, Tensor? bias,
+                            Tensor? mean_scale, float eps, str mode, bool std_eps)
+                            -> (Tensor y, Tensor mean, Tensor rstd)``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -1270,6 +1273,79 @@ def _hgt_bwd(ctx, grad):
 
 register_autograd('pyg_amd::hgt_relation', _hgt_bwd, setup_context=_hgt_setup)
 
+# ---- per-graph normalisation over a by-graph pointer ---------------------------------------------------
+def _norm_stats_shape(x: Tensor, ptr: Tensor, mode: str):
+    B = ptr.numel() - 1
+    return (B, x.size(1)) if mode == 'channel' else (B, )
+
+
+@custom_op('pyg_amd::graph_norm', mutates_args=(), device_types=_DEV)
+def graph_norm(x: Tensor, ptr: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
+               mean_scale: Optional[Tensor], eps: float, mode: str,
+               std_eps: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """GraphNorm (``mode='channel'``, graph_norm.py:72-76) or LayerNorm over whole graphs
+    (``mode='graph'``, layer_norm.py:82-108; ``std_eps``: its formula without a batch vector) of
+    ``x [N, F]`` for the graphs ``ptr [B + 1]`` of its rows.  Returns ``(y, mean, rstd)``; the
+    per-graph statistics (``[B, F]`` / ``[B]``) are what the backward takes and are not
+    differentiable.  The operator builds the hub plan of ``ptr`` itself, which reads two counts
+    back: ONE host synchronisation per call, and one more in the backward operator.  The layers
+    (``nn.norm.GraphNorm`` / ``LayerNorm``) do not pay it: they cache ``ptr`` and its plan per
+    ``batch`` tensor (``_norm.batch_handle``)."""
+    if not _native.graph_norm_supported(x.size(1)):
+        raise NotImplementedError(f'graph_norm serves 1 <= F <= 512 (got F = {x.size(1)})')
+    return _native.graph_norm_forward(ptr, x, weight, bias, mean_scale, eps, mode,
+                                      std_eps=std_eps, hub=_native.graph_norm_plan(ptr))
+
+
+@graph_norm.register_fake
+def _(x, ptr, weight, bias, mean_scale, eps, mode, std_eps):
+    stats = _norm_stats_shape(x, ptr, mode)
+    return (torch.empty_like(x, memory_format=torch.contiguous_format), x.new_empty(stats),
+            x.new_empty(stats))
+
+
+@custom_op('pyg_amd::graph_norm_backward', mutates_args=(), device_types=_DEV)
+def graph_norm_backward(grad: Tensor, x: Tensor, ptr: Tensor, weight: Optional[Tensor],
+                        mean_scale: Optional[Tensor], mean: Tensor, rstd: Tensor, eps: float,
+                        mode: str, std_eps: bool, affine_bias: bool
+                        ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The gradients of ``(x, weight, bias, mean_scale)``; a parameter that was not given gets an
+    empty tensor (``affine_bias``: the forward had a bias)."""
+    grads = _native.graph_norm_backward(
+        ptr, x, grad, mean, rstd, weight, mean_scale, eps, mode, std_eps=std_eps,
+        hub=_native.graph_norm_plan(ptr), want_weight=weight is not None, want_bias=affine_bias,
+        want_mean_scale=mean_scale is not None)
+    return tuple(grad.new_empty(0) if g is None else g for g in grads)
+
+
+@graph_norm_backward.register_fake
+def _(grad, x, ptr, weight, mean_scale, mean, rstd, eps, mode, std_eps, affine_bias):
+    F = x.size(1)
+    return (torch.empty_like(x, memory_format=torch.contiguous_format),
+            grad.new_empty(F if weight is not None else 0),
+            grad.new_empty(F if affine_bias else 0),
+            grad.new_empty(F if mean_scale is not None else 0))
+
+
+def _graph_norm_setup(ctx, inputs, output):
+    x, ptr, weight, bias, mean_scale, eps, mode, std_eps = inputs
+    _, mean, rstd = output
+    ctx.static = (eps, mode, std_eps, bias is not None)
+    ctx.given = (weight is not None, bias is not None, mean_scale is not None)
+    ctx.mark_non_differentiable(mean, rstd)
+    ctx.save_for_backward(x, ptr, weight, mean_scale, mean, rstd)
+
+
+def _graph_norm_bwd(ctx, grad, grad_mean, grad_rstd):
+    x, ptr, weight, mean_scale, mean, rstd = ctx.saved_tensors
+    g_x, g_w, g_b, g_ms = graph_norm_backward(grad.contiguous(), x, ptr, weight, mean_scale, mean,
+                                              rstd, *ctx.static)
+    g_w, g_b, g_ms = (g if given else None for g, given in zip((g_w, g_b, g_ms), ctx.given))
+    return g_x, None, g_w, g_b, g_ms, None, None, None
+
+
+register_autograd('pyg_amd::graph_norm', _graph_norm_bwd, setup_context=_graph_norm_setup)
+
 OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_backward',
        'segment_csr', 'segment_csr_backward', 'softmax_csr', 'softmax_csr_backward', 'spmm',
        'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
@@ -1279,4 +1355,5 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'gen_aggregate', 'gen_aggregate_backward', 'resgated_aggregate',
        'resgated_aggregate_backward', 'han_attend', 'han_attend_backward', 'mixture_conv',
        'mixture_conv_backward', 'cg_aggregate', 'cg_aggregate_backward', 'film_aggregate',
-       'film_aggregate_backward', 'rgat_aggregate', 'rgat_aggregate_backward')
+       'film_aggregate_backward', 'rgat_aggregate', 'rgat_aggregate_backward', 'graph_norm',
+       'graph_norm_backward')
