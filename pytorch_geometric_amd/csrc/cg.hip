@@ -22,20 +22,19 @@
 //     P[i] and g[i], and grad_Q[j,:] = [sum gzf | sum gzs] is written once.
 // grad_P and grad_Q carry row strides: the two launches may write the halves of one plane.
 //
-// Lane layout, work items, hub chunks and in-order merges: attn_device.h.  Edge term, lane shape,
-// capped grid, dispatch and the reduce of the parameter partials: gine_device.h.  No float atomics
-// anywhere and every grid depends on the problem's sizes only: every result is bitwise
+// Lane layout, work items, hub chunks, in-order merges and the reduce of the parameter partials:
+// rowwalk_device.h.  Edge term, lane shape, capped grid and dispatch: gine_device.h.  No float
+// atomics anywhere and every grid depends on the problem's sizes only: every result is bitwise
 // reproducible.
 #include <math.h>
 
-#include "attn_device.h"
 #include "common.h"
 #include "gine_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;
 using namespace gine;
 
 // Two matrices and, by destination, their two gradients in registers next to FIVE rows (Pf, Ps,
@@ -435,7 +434,7 @@ unsigned cg_grid(int64_t n_items, bool linear, unsigned linear_cap) {
 }
 
 bool cg_envelope(int64_t F, int64_t De) {
-  if (F < 1 || F > kGineMaxWidth || De < 0) return false;
+  if (F < 1 || F > kMaxWidth || De < 0) return false;
   return De == 0 || (De <= kCgMaxDe && F * De <= kCgMaxWeight);
 }
 
@@ -576,15 +575,10 @@ int pygamd_cg_backward_dst(const pygamd_csr* g, const void* edge_id, const float
     });
     PYGAMD_LAUNCH_CHECK();
     const int rcm = launch_merge<IdxT>(it, 2 * F, part, 0, nullptr, 0, grad_p, ld_gp, st);
-    if (rcm != PYGAMD_OK) return rcm;
-    if (De > 0) {  // the workgroups' partials of both matrices (2 F De floats) in workgroup order
-      const int FD = static_cast<int>(2 * F * De);
-      hipLaunchKernelGGL(param_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(FD, kBlock))),
-                         dim3(kBlock), 0, st, wpart, static_cast<int>(n_blocks), FD, 0,
-                         grad_weight, nullptr);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    return PYGAMD_OK;
+    if (rcm != PYGAMD_OK || De <= 0) return rcm;
+    // the workgroups' partials of both matrices (2 F De floats) in workgroup order
+    return launch_param_reduce(wpart, n_blocks, static_cast<int>(2 * F * De), 0, grad_weight,
+                               nullptr, st);
   });
 }
 

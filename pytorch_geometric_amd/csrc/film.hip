@@ -21,20 +21,19 @@
 //     slot, grad_H[j, rF:(r+1)F] = sum scale[e] * g_i * act'(pre) * gamma_{r,i}.
 // Pairs that do not occur are not written: the caller zero-fills both planes once.
 //
-// Lane layout, work items, hub chunks and in-order merges: attn_device.h.  Lane shape, the walk
-// over the items, capped grid and dispatch: gine_device.h (resgated.hip's shapes without an edge
-// term).  No float atomics anywhere and every grid depends on the problem's sizes only: every
-// result is bitwise reproducible.
+// Lane layout, work items, their walk, hub chunks and in-order merges: rowwalk_device.h.  Lane
+// shape, capped grid, dispatch and a slot's edge id: gine_device.h (resgated.hip's shapes without
+// an edge term).  No float atomics anywhere and every grid depends on the problem's sizes only:
+// every result is bitwise reproducible.
 #include <math.h>
 
-#include "attn_device.h"
 #include "common.h"
 #include "gine_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;
 using namespace gine;
 
 template <int EPL>
@@ -261,7 +260,7 @@ constexpr unsigned kFilmBlocks = 2048;
 
 unsigned film_grid(int64_t n_items) { return gine_grid(n_items, true, kFilmBlocks); }
 
-bool film_envelope(int64_t F, int64_t) { return F >= 1 && F <= kGineMaxWidth; }
+bool film_envelope(int64_t F, int64_t) { return F >= 1 && F <= kMaxWidth; }
 
 // pygamd_resgated_workspace_bytes(n_chunks, F, 0): a chunk's partial row of up to 2F
 size_t film_ws_bytes(int64_t n_chunks, int64_t F) {

@@ -3,13 +3,8 @@
 //     s[i<-j, h] = sum_c att[h,c] * leaky_relu(x_l[j,h,c] + x_r[i,h,c])
 // needs the full source row per edge, and so does the aggregation: ONE pass per destination keeps
 // x_r[i] in registers, gathers every x_l[j] once, runs an online softmax per head and (AGG)
-// accumulates the weighted row.  Nothing of size E x H*C is ever written.
-//
-// Lane layout (wave64, one wave per row or per chunk of a long row): `lph` lanes per head, a power
-// of two with H * lph <= 64; lane l serves head l / lph and the channels sub + lph * r (scalar) or
-// the float4 units sub + lph * q (VEC) of that head, EPL registers per row.  A head's dot product
-// is an xor-butterfly over its lph lanes, so heads that are narrower or wider than a lane's share,
-// odd C and H*C < 64 all take the same code.
+// accumulates the weighted row.  Nothing of size E x H*C is ever written.  Lane layout (`lph`
+// lanes per head, one wave per row or per chunk of a long row): rowwalk_device.h.
 //
 // Long rows (more slots than the handle's hub threshold) are split into the hub plan's chunks: one
 // wave per chunk leaves a partial (m, l, acc) — or a partial gradient row — in the workspace and a
@@ -23,10 +18,9 @@
 namespace pygamd {
 namespace {
 
-using namespace attn;  // layout, work items and merges: attn_device.h
+using namespace rowwalk;  // layout, work items and the sum merge: rowwalk_device.h
+using namespace attn;     // online softmax and its merge: attn_device.h
 
-constexpr int kGv2MaxWidth = kAttnMaxWidth;
-constexpr int kGv2MaxHeads = kAttnMaxHeads;
 constexpr int kGv2MaxBlocks = 1024;  // persistent grid of the by-destination backward
 
 template <int EPL>
@@ -115,17 +109,9 @@ __global__ void __launch_bounds__(kWave)
                            const IdxT* __restrict__ hub_cptr, int H, int C,
                            const float* __restrict__ part, float* __restrict__ alpha,
                            float* __restrict__ out) {
-  __shared__ float sm[kGv2MaxHeads], sinv[kGv2MaxHeads];
+  __shared__ float sm[kAttnMaxHeads], sinv[kAttnMaxHeads];
   merge_softmax_row(rowptr, hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), H, C, part,
                     alpha, out, sm, sinv, 0, static_cast<int64_t>(H) * C, true, nullptr);
-}
-
-// partial rows of a hub row summed in chunk order
-template <typename IdxT>
-__global__ void __launch_bounds__(kWave)
-    gatv2_sum_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
-                           int64_t W, const float* __restrict__ part, float* __restrict__ dst) {
-  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), W, part, W, dst, W);
 }
 
 // ---- backward, by destination -------------------------------------------------------------------
@@ -142,7 +128,7 @@ __global__ void __launch_bounds__(kBlock)
                          float* __restrict__ ds, float* __restrict__ gxr,
                          float* __restrict__ part, float* __restrict__ att_part) {
   constexpr int U = InFlight<EPL>::src;
-  __shared__ __attribute__((aligned(16))) float sm[kWavesPerBlock][kGv2MaxWidth];
+  __shared__ __attribute__((aligned(16))) float sm[kWavesPerBlock][kMaxWidth];
   const Lay L = make_lay(H, C, lph);
   const int64_t W = static_cast<int64_t>(H) * C;
   float a[EPL], ga[EPL];
@@ -220,16 +206,6 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-__global__ void __launch_bounds__(kBlock)
-    gatv2_att_reduce_kernel(const float* __restrict__ att_part, int64_t n_part, int64_t W,
-                            float* __restrict__ gatt) {
-  const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (t >= W) return;
-  float acc = 0.f;
-  for (int64_t b = 0; b < n_part; ++b) acc += att_part[b * W + t];
-  gatt[t] = acc;
-}
-
 // ---- backward, by source ---------------------------------------------------------------------
 // grad_x_l[j] = sum over the edges j -> i of alpha * grad_out[i] (not in SCORE mode) + d pre.
 template <typename IdxT, int EPL, bool VEC, bool SCORE>
@@ -281,8 +257,6 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---- host side -------------------------------------------------------------------------------
-#define GV2_DISPATCH_SHAPE ATTN_DISPATCH_SHAPE
-
 size_t gv2_ws_bytes(int64_t n_chunks, int64_t H, int64_t C) {
   const int64_t W = H * C;
   return sizeof(float) * static_cast<size_t>(n_chunks * (W + 2 * H) + kGv2MaxBlocks * W);
@@ -302,7 +276,7 @@ int pygamd_gatv2_supported(int64_t H, int64_t C) {
 
 int pygamd_gatv2_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C, size_t* bytes) {
   if (!bytes || n_chunks < 0 || H < 1 || C < 1) return PYGAMD_ERR_INVALID_ARG;
-  if (H * C > kGv2MaxWidth || H > kGv2MaxHeads) return PYGAMD_ERR_UNSUPPORTED;
+  if (H * C > kMaxWidth || H > kAttnMaxHeads) return PYGAMD_ERR_UNSUPPORTED;
   *bytes = gv2_ws_bytes(n_chunks, H, C);
   return PYGAMD_OK;
 }
@@ -327,7 +301,7 @@ int pygamd_gatv2_forward(const pygamd_csr* g, const float* x_l, const float* x_r
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    GV2_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (out) {
         hipLaunchKernelGGL((gatv2_fwd_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it, c,
                            x_l, x_r, att, static_cast<int>(H), static_cast<int>(C), sh.lph, slope,
@@ -357,7 +331,7 @@ int pygamd_gatv2_backward_dst(const pygamd_csr* g, const float* x_l, const float
                               void* stream) {
   const int rc = check_args(g, n_src, H, C);
   if (rc != PYGAMD_OK) return rc;
-  const int64_t n_rows = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
+  const int64_t n_rows = g->n_rows, n_chunks = g->n_chunks;
   if (!grad_att) return PYGAMD_ERR_INVALID_ARG;
   // exactly one of (grad_out, out) and grad_alpha says where d alpha comes from
   const bool score = grad_alpha != nullptr;
@@ -384,7 +358,7 @@ int pygamd_gatv2_backward_dst(const pygamd_csr* g, const float* x_l, const float
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(static_cast<unsigned>(blocks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    GV2_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (score) {
         hipLaunchKernelGGL((gatv2_bwd_dst_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it,
                            n_items, c, x_l, x_r, att, alpha, grad_out, out, grad_alpha,
@@ -398,15 +372,11 @@ int pygamd_gatv2_backward_dst(const pygamd_csr* g, const float* x_l, const float
       }
     });
     PYGAMD_LAUNCH_CHECK();
-    if (n_hub > 0) {
-      hipLaunchKernelGGL((gatv2_sum_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
-                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, W, part, grad_x_r);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(gatv2_att_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(W, kBlock))),
-                       block, 0, st, att_part, blocks, W, grad_att);
-    PYGAMD_LAUNCH_CHECK();
-    return PYGAMD_OK;
+    const int rc = launch_sum_merge(it, W, part, grad_x_r, st);
+    if (rc != PYGAMD_OK) return rc;
+    // (the workgroups' att partials in workgroup order; no bias block)
+    return launch_param_reduce(att_part, static_cast<unsigned>(blocks), static_cast<int>(W), 0,
+                               grad_att, nullptr, st);
   });
 }
 
@@ -417,7 +387,7 @@ int pygamd_gatv2_backward_src(const pygamd_csr* g, const void* slot_map, const f
                               size_t workspace_bytes, void* stream) {
   const int rc = check_args(g, n_dst, H, C);
   if (rc != PYGAMD_OK) return rc;
-  const int64_t n_src = g->n_rows, n_hub = g->n_hub, n_chunks = g->n_chunks;
+  const int64_t n_src = g->n_rows, n_chunks = g->n_chunks;
   if (n_src == 0) return PYGAMD_OK;
   if (!g->rowptr || !g->col || !slot_map || !x_l || !x_r || !att || !alpha || !grad_s || !grad_x_l)
     return PYGAMD_ERR_INVALID_ARG;
@@ -435,7 +405,7 @@ int pygamd_gatv2_backward_src(const pygamd_csr* g, const void* slot_map, const f
     const dim3 grid(wave_grid(n_src + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
     const IdxT* sm = static_cast<const IdxT*>(slot_map);
-    GV2_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (!grad_out) {
         hipLaunchKernelGGL((gatv2_bwd_src_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it,
                            c, sm, x_l, x_r, att, alpha, grad_s, grad_out, static_cast<int>(H),
@@ -447,12 +417,7 @@ int pygamd_gatv2_backward_src(const pygamd_csr* g, const void* slot_map, const f
       }
     });
     PYGAMD_LAUNCH_CHECK();
-    if (n_hub > 0) {
-      hipLaunchKernelGGL((gatv2_sum_merge_kernel<IdxT>), dim3(static_cast<unsigned>(n_hub)),
-                         dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, W, part, grad_x_l);
-      PYGAMD_LAUNCH_CHECK();
-    }
-    return PYGAMD_OK;
+    return launch_sum_merge(it, W, part, grad_x_l, st);
   });
 }
 

@@ -10,19 +10,21 @@
 // exists anywhere.  The forward leaves M and 1 / (L + 1e-16) per (destination, column) — and, for
 // a learned t, S2 = sum_k alpha m^2 — from which the backward rebuilds alpha per out-slot.
 //
-// Lane layout, work items, hub chunks and in-order merges: attn_device.h.  Edge term, envelope,
-// capped grid and dispatch: gine_device.h.  No float atomics anywhere and every grid depends on the
-// problem's sizes only: every result is bitwise reproducible.
+// Lane layout, work items, hub chunks and in-order merges: rowwalk_device.h.  Edge term, envelope,
+// capped grid and dispatch: gine_device.h.  The softmax weight of a score: attn_device.h.  No float
+// atomics anywhere and every grid depends on the problem's sizes only: every result is bitwise
+// reproducible.
 #include <math.h>
 
-#include "attn_device.h"
+#include "attn_device.h"  // softmax_weight
 #include "common.h"
 #include "gine_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;
+using attn::softmax_weight;
 using namespace gine;
 
 template <int EPL, int DE>
@@ -310,7 +312,7 @@ __global__ void __launch_bounds__(kBlock)
     }
   }
   if constexpr (LIN) {
-    __shared__ float red[kGineMaxWeight + kGineMaxWidth];
+    __shared__ float red[kGineMaxWeight + kMaxWidth];
     const int De = ed.De;
     const int FD = F * De;
     for (int wv = 0; wv < kWavesPerBlock; ++wv) {

@@ -8,21 +8,20 @@
 // linear mode every lane keeps the rows of W of ITS columns in registers for the whole launch and
 // a slot's raw features reach the lanes by v_readlane: no [E, F] value exists anywhere.
 //
-// Lanes run over the F columns (attn_device.h's layout with one head): scalar registers for any
+// Lanes run over the F columns (rowwalk_device.h's layout with one head): scalar registers for any
 // F, float4 units where F % 4 == 0 and every row is 16-byte aligned.  Work items, the hub plan's
-// chunks and the in-order merge of a long row's partials: attn_device.h.  The forward walks the
+// chunks and the in-order merge of a long row's partials: rowwalk_device.h.  The forward walks the
 // CSR by destination, the backward the CSR by source and visits every edge exactly once.  No float
 // atomics anywhere: every result is bitwise reproducible.
 #include <math.h>
 
-#include "attn_device.h"
 #include "common.h"
 #include "gine_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;
 using namespace gine;
 
 template <int EPL, int DE>
@@ -185,7 +184,7 @@ __global__ void __launch_bounds__(kBlock)
     }
   }
   if constexpr (LIN) {
-    __shared__ float red[kGineMaxWeight + kGineMaxWidth];
+    __shared__ float red[kGineMaxWeight + kMaxWidth];
     const int De = ed.De;
     const int FD = F * De;
     for (int wv = 0; wv < kWavesPerBlock; ++wv) {

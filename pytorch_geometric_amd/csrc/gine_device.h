@@ -1,25 +1,23 @@
-// gine_device.h — what the kernels with a per-slot linear edge term W a_k (+ b) share (gine.hip,
-// pna.hip, gen.hip, resgated.hip).  Forward side: the envelope, the edge arguments, a slot's edge
+// gine_device.h — what the kernels with a per-slot linear edge term W a_k (+ b) share, on top of
+// the row walk of rowwalk_device.h.  Forward side: the envelope, the edge arguments, a slot's edge
 // id and raw features, a lane's rows of the edge weight in registers, the edge term, the lane
-// shape with its register capacity for De, the walk over the items, the capped grid and the
-// dispatch over the instantiations.  Backward side: the update of the parameter gradients in
-// registers by a slot (gine.hip, pna.hip, resgated.hip; gen.hip keeps it written out, the call
-// cost its backward 1 %), the
-// reduce of the workgroups' partials in workgroup order, the sum merge of a hub row's chunks
-// and the launch of those two.  Each kernel keeps its own loop, loads and arithmetic in its own
-// file — and the fold of a workgroup's waves into its partial through LDS, which as a function
-// changed the register allocation of the backward (CHANGELOG).  Lane layout, work items and
-// merges: attn_device.h.
+// shape with its register capacity for De, the capped grid and the dispatch over the
+// instantiations.  Backward side: the update of the parameter gradients in registers by a slot
+// (gine.hip, pna.hip, resgated.hip; gen.hip keeps it written out, the call cost its backward 1 %)
+// and the launches that follow a backward's main one.  Each kernel keeps its own loop, loads and
+// arithmetic in its own file — and the fold of a workgroup's waves into its partial through LDS,
+// which as a function changed the register allocation of the backward (CHANGELOG).
+// Included by gine.hip, pna.hip, gen.hip, resgated.hip and cg.hip; by film.hip for the shape, the
+// capped grid and gine_check without an edge term; by mixture.hip for slot_edge.
 #pragma once
-#include "attn_device.h"
 #include "common.h"
+#include "rowwalk_device.h"
 
 namespace pygamd {
 namespace gine {
 
-using namespace attn;
+using namespace rowwalk;
 
-constexpr int kGineMaxWidth = 512;
 constexpr int kGineMaxDe = 32;
 constexpr int kGineMaxWeight = 4096;  // F * De: 64 registers per lane at 64 busy lanes
 // Linear mode: a wave loads its 64 * EPL * De weights once and then walks items at the stride of
@@ -27,13 +25,6 @@ constexpr int kGineMaxWeight = 4096;  // F * De: 64 registers per lane at 64 bus
 // of workgroups of a launch on the problem's sizes only (grad_W is reduced in workgroup order).
 constexpr unsigned kGineFwdBlocks = 1024;
 constexpr unsigned kGineBwdBlocks = 512;
-
-// the column of register e of this lane
-template <bool VEC>
-__device__ __forceinline__ int lane_col(const Lay& L, int e) {
-  if constexpr (VEC) return (L.sub + L.lph * (e >> 2)) * 4 + (e & 3);
-  return L.sub + L.lph * e;
-}
 
 // rows of W [F, De] (torch.nn.Linear's layout) and entries of b [F] (or NULL) of the lane's columns
 template <int EPL, bool VEC, int DE>
@@ -84,17 +75,6 @@ __device__ __forceinline__ float edge_lane(const EdgeArgs& ed, int64_t id, int l
   return lane < ed.De ? ed.edge_attr[id * ed.De + lane] : 0.f;
 }
 
-// the items of a wave: for (item = wk.first; item < wk.n; item += wk.stride)
-struct Walk {
-  int64_t n, stride, first;
-};
-
-template <typename IdxT>
-__device__ __forceinline__ Walk item_walk(const Items<IdxT>& it) {
-  return Walk{it.n_chunks + it.n_rows, static_cast<int64_t>(gridDim.x) * kWavesPerBlock,
-              xcd_logical_block() * kWavesPerBlock + wave_in_block()};
-}
-
 // ---- backward of the linear edge term ---------------------------------------------------------
 // grad_W[f, d] = sum_k g_k[f] a_k[d] and grad_b[f] = sum_k g_k[f] accumulate in the lane's registers
 // gw and gb (the kernel zeroes them) over all items of the wave.  BIAS = false: no grad_b, gb is
@@ -134,32 +114,6 @@ __device__ __forceinline__ void edge_grad_take(const float (&g)[EPL], float av,
   }
 }
 
-// (the two kernels are static: every file that launches them carries its own copy)
-// hub rows, backward: the chunks' partial rows summed in chunk order
-template <typename IdxT>
-static __global__ void __launch_bounds__(kWave)
-    sum_merge_kernel(const IdxT* __restrict__ hub_rows, const IdxT* __restrict__ hub_cptr,
-                     int64_t F, const float* __restrict__ part, float* __restrict__ grad_x) {
-  merge_sum_row(hub_rows, hub_cptr, static_cast<int64_t>(blockIdx.x), F, part, F, grad_x, F);
-}
-
-// the workgroups' partials (grad_W [FD], then grad_b [F]; F = 0: no bias block) summed in
-// workgroup order
-static __global__ void __launch_bounds__(kBlock)
-    param_reduce_kernel(const float* __restrict__ wpart, int n_blocks, int FD, int F,
-                        float* __restrict__ grad_weight, float* __restrict__ grad_bias) {
-  const int t = blockIdx.x * kBlock + threadIdx.x;
-  const int S = FD + F;
-  if (t >= S) return;
-  float acc = 0.f;
-  for (int g = 0; g < n_blocks; ++g) acc += wpart[static_cast<int64_t>(g) * S + t];
-  if (t < FD) {
-    grad_weight[t] = acc;
-  } else if (grad_bias) {
-    grad_bias[t - FD] = acc;
-  }
-}
-
 // ---- host side -------------------------------------------------------------------------------
 struct GineShape {
   int lph, epl, de;  // de: the register capacity for De (0: wide mode)
@@ -167,7 +121,7 @@ struct GineShape {
 };
 
 inline bool gine_envelope(int64_t F, int64_t De) {
-  if (F < 1 || F > kGineMaxWidth || De < 0) return false;
+  if (F < 1 || F > kMaxWidth || De < 0) return false;
   return De == 0 || (De <= kGineMaxDe && F * De <= kGineMaxWeight);
 }
 
@@ -248,26 +202,17 @@ inline int launch_backward_tail(const Items<IdxT>& it, int64_t F, int64_t De, bo
                                 unsigned n_blocks, const float* part, float* grad_x,
                                 const float* wpart, float* grad_weight, float* grad_bias,
                                 hipStream_t st) {
-  if (it.n_hub > 0) {
-    hipLaunchKernelGGL((sum_merge_kernel<IdxT>), dim3(static_cast<unsigned>(it.n_hub)),
-                       dim3(kWave), 0, st, it.hub_rows, it.hub_cptr, F, part, grad_x);
-    PYGAMD_LAUNCH_CHECK();
-  }
-  if (De > 0) {
-    const int FD = static_cast<int>(F * De), Fb = bias_block ? static_cast<int>(F) : 0;
-    hipLaunchKernelGGL(param_reduce_kernel, dim3(static_cast<unsigned>(ceil_div(FD + Fb, kBlock))),
-                       dim3(kBlock), 0, st, wpart, static_cast<int>(n_blocks), FD, Fb, grad_weight,
-                       grad_bias);
-    PYGAMD_LAUNCH_CHECK();
-  }
-  return PYGAMD_OK;
+  const int rc = launch_sum_merge(it, F, part, grad_x, st);
+  if (rc != PYGAMD_OK || De <= 0) return rc;
+  return launch_param_reduce(wpart, n_blocks, static_cast<int>(F * De),
+                             bias_block ? static_cast<int>(F) : 0, grad_weight, grad_bias, st);
 }
 
 // (`envelope`: a kernel file with a narrower one than gine_envelope passes its own)
 inline int gine_check(const pygamd_csr* g, int64_t n_other, int64_t F, int64_t De,
                       bool (*envelope)(int64_t, int64_t) = gine_envelope) {
-  if (De < 0) return PYGAMD_ERR_INVALID_ARG;
-  const int rc = check_args(g, n_other, 1, F < 1 ? F : 1);
+  if (De < 0 || F < 1) return PYGAMD_ERR_INVALID_ARG;
+  const int rc = check_handle(g, n_other);
   if (rc != PYGAMD_OK) return rc;
   return envelope(F, De) ? PYGAMD_OK : PYGAMD_ERR_UNSUPPORTED;
 }

@@ -15,7 +15,7 @@
 // sigma^2 = s2 / n - d^2 — the cancelling form only ever sees data shifted by one of its own
 // samples.  GraphNorm needs no second pass over u: v = sigma^2 + (1 - alpha)^2 m^2.
 //
-// Lanes own columns (attn_device.h's layout with one head), so CHANNEL needs no cross-lane step
+// Lanes own columns (rowwalk_device.h's layout with one head), so CHANNEL needs no cross-lane step
 // and GRAPH one xor-butterfly per graph.  A graph at or under the plan's threshold is one wave's:
 // statistics, then its rows again (from L2) for y, in the same launch.  A longer graph is the
 // plan's chunks: the chunks' partial sums (all about the graph's pivot) go to the workspace, a merge
@@ -26,15 +26,13 @@
 // only: bitwise reproducible, and a graph's rows depend on nothing but that graph.
 #include <math.h>
 
-#include "attn_device.h"
 #include "common.h"
-#include "gine_device.h"
+#include "rowwalk_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
-using namespace gine;
+using namespace rowwalk;
 
 constexpr int kNormMaxWidth = 512;
 constexpr unsigned kNormBlocks = PYGAMD_GRAPH_NORM_BLOCKS;  // cap of the backward's main grid
@@ -605,9 +603,9 @@ __global__ void __launch_bounds__(kMergeBlock)
 }
 
 // ---- host side -------------------------------------------------------------------------------
-// `...` sees the constants EPL and VEC of the shape.  ATTN_DISPATCH_SHAPE without its 16-register
-// case: with one head and F <= 512 a lane has at most 8, and these kernels hold several rows of
-// EPL registers at once — the case would be compiled for nothing.
+// `...` sees the constants EPL and VEC of the shape.  ROWWALK_DISPATCH_SHAPE without its
+// 16-register case: with one head and F <= 512 a lane has at most 8, and these kernels hold
+// several rows of EPL registers at once — the case would be compiled for nothing.
 #define NORM_DISPATCH_SHAPE(shape, ...)                                                         \
   do {                                                                                          \
     if ((shape).vec) {                                                                          \
@@ -637,9 +635,10 @@ inline int64_t bwd_ws_floats(int64_t n_chunks, int64_t n_hub, int64_t F) {
 
 // what forward and backward share: 0 = go on
 inline int norm_check(const pygamd_csr* g, int mode, int64_t n, int64_t F) {
-  const int rc = check_args(g, n, 1, F < 1 ? F : 1);
+  const int rc = check_handle(g, n);
   if (rc != PYGAMD_OK) return rc;
-  if (mode != PYGAMD_NORM_CHANNEL && mode != PYGAMD_NORM_GRAPH) return PYGAMD_ERR_INVALID_ARG;
+  if (F < 1 || (mode != PYGAMD_NORM_CHANNEL && mode != PYGAMD_NORM_GRAPH))
+    return PYGAMD_ERR_INVALID_ARG;
   return F > kNormMaxWidth ? PYGAMD_ERR_UNSUPPORTED : PYGAMD_OK;
 }
 

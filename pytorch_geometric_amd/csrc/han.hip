@@ -15,9 +15,9 @@
 //   out[r,h]  = relu?(sum_k alpha[k,h] * x_all[col[k] + val_shift[e], h, :])
 //
 // ONE pass per row keeps a_dst[r] in registers and gathers every source row once; nothing of size
-// E x H*C is written.  Lane layout, online softmax, non-finite rules, work items and the in-order
-// merges of the chunks of a long row are those of attn_device.h.  No float atomics: every result is
-// bitwise reproducible.
+// E x H*C is written.  Lane layout, work items and the in-order sum merge of the chunks of a
+// long row: rowwalk_device.h.  Online softmax, non-finite rules and its merge: attn_device.h.  No
+// float atomics: every result is bitwise reproducible.
 #include <math.h>
 
 #include "attn_device.h"
@@ -26,7 +26,8 @@
 namespace pygamd {
 namespace {
 
-using namespace attn;  // layout, work items and merges: attn_device.h
+using namespace rowwalk;  // layout, work items and the sum merge: rowwalk_device.h
+using namespace attn;     // online softmax and its merge: attn_device.h
 
 constexpr int kHanMaxTypes = 64;
 
@@ -313,7 +314,7 @@ int pygamd_han_supported(int64_t H, int64_t C) {
 
 int pygamd_han_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C, size_t* bytes) {
   if (!bytes || n_chunks < 0 || H < 1 || C < 1) return PYGAMD_ERR_INVALID_ARG;
-  if (H * C > kAttnMaxWidth || H > kAttnMaxHeads) return PYGAMD_ERR_UNSUPPORTED;
+  if (H * C > kMaxWidth || H > kAttnMaxHeads) return PYGAMD_ERR_UNSUPPORTED;
   *bytes = han_ws_bytes(n_chunks, H, C);
   return PYGAMD_OK;
 }
@@ -343,7 +344,7 @@ int pygamd_han_forward(const pygamd_csr* g, const int64_t* row_begin, const int6
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       hipLaunchKernelGGL((han_fwd_kernel<IdxT, EPL, VEC>), grid, block, 0, st, it, c, tab, x_all,
                          a_src, a_dst, static_cast<int>(H), static_cast<int>(C), sh.lph, slope,
                          relu, alpha, out, part);
@@ -386,7 +387,7 @@ int pygamd_han_backward_dst(const pygamd_csr* g, const int64_t* row_begin,
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       hipLaunchKernelGGL((han_bwd_dst_kernel<IdxT, EPL, VEC>), grid, block, 0, st, it, c, tab,
                          x_all, a_src, a_dst, alpha, grad_out, out, static_cast<int>(H),
                          static_cast<int>(C), sh.lph, slope, relu, grad_s, grad_a_dst, part);
@@ -430,7 +431,7 @@ int pygamd_han_backward_src(const pygamd_csr* g, const void* slot_map, const flo
     const dim3 grid(wave_grid(n_cols + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
     const IdxT* sm = static_cast<const IdxT*>(slot_map);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       hipLaunchKernelGGL((han_bwd_src_kernel<IdxT, EPL, VEC>), grid, block, 0, st, it, c, sm,
                          alpha, grad_s, grad_out, out, static_cast<int>(H), static_cast<int>(C),
                          sh.lph, relu, grad_a_src, grad_xv, part, part_h);

@@ -13,18 +13,17 @@
 // l + 64 e, e < EPL.  k runs in compile-time tiles of KT (KT * EPL <= 32 registers) so that the
 // accumulators are named registers; a row's slots are walked once per tile and the repeated x rows
 // are L2 hits.  The coefficients of a slot and tile are loaded by the first KT lanes once and
-// broadcast from there.  Work items, hub chunks and the in-order merge: attn_device.h and
-// gine_device.h.  No float atomics and every grid depends on the problem's sizes only: every
-// result is bitwise reproducible.
-#include "attn_device.h"
+// broadcast from there.  Work items, hub chunks and the in-order merge: rowwalk_device.h; a slot's
+// edge id: gine_device.h.  No float atomics and every grid depends on the problem's sizes only:
+// every result is bitwise reproducible.
 #include "common.h"
 #include "gine_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
-using namespace gine;
+using namespace rowwalk;
+using gine::slot_edge;
 
 constexpr int kMixMaxWidth = 512;  // F
 constexpr int kMixMaxK = 256;      // K
@@ -223,7 +222,7 @@ MixShape mix_shape(int64_t F, int64_t K) {
 // the checks both entry points share; 0 = go on
 int mix_check(const pygamd_csr* g, int64_t n_cols, int64_t F, int64_t K, int64_t ld_x) {
   if (F < 1 || K < 1) return PYGAMD_ERR_INVALID_ARG;
-  const int rc = check_args(g, n_cols, 1, 1);
+  const int rc = check_handle(g, n_cols);
   if (rc != PYGAMD_OK) return rc;
   if (!mix_envelope(F, K)) return PYGAMD_ERR_UNSUPPORTED;
   return ld_x < F ? PYGAMD_ERR_INVALID_ARG : PYGAMD_OK;
@@ -268,8 +267,7 @@ int pygamd_mixture_expand(const pygamd_csr* g, const void* edge_id, const float*
     });
     PYGAMD_LAUNCH_CHECK();
     // (hub rows: the chunks' partial wide rows in chunk order)
-    return launch_backward_tail<IdxT>(it, K * F, 0, false, 0, part, z, nullptr, nullptr, nullptr,
-                                      st);
+    return launch_sum_merge(it, K * F, part, z, st);
   });
 }
 

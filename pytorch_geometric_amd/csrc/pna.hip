@@ -13,18 +13,17 @@
 // each.  The backward walks the CSR by source, rebuilds u_k with the same operations in the same
 // order (u_k == min u is then a bitwise test) and needs one packed coefficient row per destination:
 //     grad_u = A + B u + Gmin [u == min u] + Gmax [u == max u]
-// Lane layout, weights in registers, schedule and dispatch: gine_device.h / attn_device.h.  No
+// Lane layout, weights in registers, schedule and dispatch: rowwalk_device.h / gine_device.h.  No
 // float atomics anywhere: every result is bitwise reproducible.
 #include <math.h>
 
-#include "attn_device.h"
 #include "common.h"
 #include "gine_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;
 using namespace gine;
 
 enum { kPnaMean = 1, kPnaMin = 2, kPnaMax = 4, kPnaStd = 8 };

@@ -19,20 +19,19 @@
 //     (each pointer-plus-stride: two rows in place, or the halves of one packed row), and the
 //     packed grad_QV[j,:] = [sum gz | sum gu] is written once.
 //
-// Lane layout, work items, hub chunks and in-order merges: attn_device.h.  Edge term, lane shape,
-// capped grid, dispatch and the reduce of the parameter partials: gine_device.h.  No float atomics
-// anywhere and every grid depends on the problem's sizes only: every result is bitwise
+// Lane layout, work items, hub chunks, in-order merges and the reduce of the parameter partials:
+// rowwalk_device.h.  Edge term, lane shape, capped grid and dispatch: gine_device.h.  No float
+// atomics anywhere and every grid depends on the problem's sizes only: every result is bitwise
 // reproducible.
 #include <math.h>
 
-#include "attn_device.h"
 #include "common.h"
 #include "gine_device.h"
 
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;
 using namespace gine;
 
 // Two matrices share the registers gine.hip gives one: 2 * 2048 / 64 = 64 registers per lane for
@@ -312,7 +311,7 @@ __global__ void __launch_bounds__(kBlock)
 
 // ---- host side -------------------------------------------------------------------------------
 bool res_envelope(int64_t F, int64_t De) {
-  if (F < 1 || F > kGineMaxWidth || De < 0) return false;
+  if (F < 1 || F > kMaxWidth || De < 0) return false;
   return De == 0 || (De <= kGineMaxDe && F * De <= kResMaxWeight);
 }
 
@@ -379,7 +378,7 @@ int pygamd_resgated_forward(const pygamd_csr* g, const void* edge_id, const floa
     });
     PYGAMD_LAUNCH_CHECK();
     // (hub rows: the chunks' partial sums in chunk order)
-    return launch_backward_tail<IdxT>(it, F, 0, false, 0, part, out, nullptr, nullptr, nullptr, st);
+    return launch_sum_merge(it, F, part, out, st);
   });
 }
 
@@ -463,8 +462,7 @@ int pygamd_resgated_backward_src(const pygamd_csr* g, const void* edge_id_t, con
     });
     PYGAMD_LAUNCH_CHECK();
     // (hub rows: the chunks' packed partial rows of 2F in chunk order)
-    return launch_backward_tail<IdxT>(it, 2 * F, 0, false, 0, part, grad_qv, nullptr, nullptr,
-                                      nullptr, st);
+    return launch_sum_merge(it, 2 * F, part, grad_qv, st);
   });
 }
 

@@ -34,9 +34,9 @@
 // raw d alpha, and the scalar launch over the pair rows subtracts the PAIR's sum alpha * d alpha,
 // applies the slope and sums grad_QI (it stands in for the pair launch over those rows).
 //
-// Lane layout, online softmax, non-finite rules, work items, hub chunks and their in-order merges:
-// attn_device.h.  No float atomics and every grid depends on the problem's sizes only: every result
-// is bitwise reproducible.
+// Lane layout, work items, hub chunks and their in-order sum merge: rowwalk_device.h.  Online
+// softmax, non-finite rules and its merge: attn_device.h.  No float atomics and every grid depends
+// on the problem's sizes only: every result is bitwise reproducible.
 #include <math.h>
 
 #include "attn_device.h"
@@ -45,7 +45,8 @@
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;  // layout, work items and the sum merge: rowwalk_device.h
+using namespace attn;     // online softmax and its merge: attn_device.h
 
 template <int EPL>
 struct RgatInFlight {
@@ -421,7 +422,7 @@ int pygamd_rgat_forward(const pygamd_csr* g, const int32_t* rel, const float* p,
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       hipLaunchKernelGGL((rgat_fwd_kernel<IdxT, EPL, VEC>), grid, block, 0, st, it, c, rel, p,
                          ld_p, qi, ld_qi, kj, ld_kj, b, pair_stats, R, static_cast<int>(H),
                          static_cast<int>(C), sh.lph, slope, alpha, out, part);
@@ -460,7 +461,7 @@ int pygamd_rgat_backward_dst(const pygamd_csr* g, const int32_t* rel, const floa
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       hipLaunchKernelGGL((rgat_bwd_dst_kernel<IdxT, EPL, VEC>), grid, block, 0, st, it, c, rel, p,
                          ld_p, qi, ld_qi, kj, ld_kj, b, alpha, grad_out, out,
                          static_cast<int>(H), static_cast<int>(C), sh.lph, slope, within, grad_s);
@@ -530,7 +531,7 @@ int pygamd_rgat_backward_src(const pygamd_csr* g, const void* slot_map, const vo
     const IdxT* sm = static_cast<const IdxT*>(slot_map);
     const IdxT* prel = static_cast<const IdxT*>(pair_rel);
     const IdxT* pnode = static_cast<const IdxT*>(pair_node);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       hipLaunchKernelGGL((rgat_bwd_pair_kernel<IdxT, EPL, VEC>), grid, block, 0, st, it, c, sm,
                          prel, pnode, alpha, grad_s, grad_out, static_cast<int>(H),
                          static_cast<int>(C), sh.lph, grad_a, ld_ga, grad_p, ld_gp, part, part_h);

@@ -9,8 +9,9 @@
 // ever written.  key and value are two pointers with one row stride `ld` (floats): the two halves
 // of one [N_src, 2*H*C] projection are read in place, a slot's gather being one contiguous span.
 //
-// Lane layout, work items, long rows and their in-order merges: attn_device.h (shared with
-// gatv2.hip).  No float atomics anywhere: every result is bitwise reproducible.
+// Lane layout, work items, long rows and their in-order sum merge: rowwalk_device.h.  Online
+// softmax, its merge and the edge registers: attn_device.h (shared with gatv2.hip).  No float
+// atomics anywhere: every result is bitwise reproducible.
 #include <math.h>
 
 #include "attn_device.h"
@@ -19,7 +20,8 @@
 namespace pygamd {
 namespace {
 
-using namespace attn;
+using namespace rowwalk;  // layout, work items and the sum merge: rowwalk_device.h
+using namespace attn;     // online softmax and its merge: attn_device.h
 
 // slots in flight per wave: every slot gathers TWO rows (key and value, or query and grad_out), so
 // half of what gatv2's one-row forward keeps
@@ -540,7 +542,7 @@ int pygamd_transformer_supported(int64_t H, int64_t C) {
 
 int pygamd_transformer_workspace_bytes(int64_t n_chunks, int64_t H, int64_t C, size_t* bytes) {
   if (!bytes || n_chunks < 0 || H < 1 || C < 1) return PYGAMD_ERR_INVALID_ARG;
-  if (H * C > kAttnMaxWidth || H > kAttnMaxHeads) return PYGAMD_ERR_UNSUPPORTED;
+  if (H * C > kMaxWidth || H > kAttnMaxHeads) return PYGAMD_ERR_UNSUPPORTED;
   *bytes = tf_ws_bytes(n_chunks, H, C);
   return PYGAMD_OK;
 }
@@ -569,7 +571,7 @@ int pygamd_transformer_forward(const pygamd_csr* g, const float* query, const fl
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (out) {
         hipLaunchKernelGGL((transformer_fwd_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st, it,
                            c, query, key, value, ld, static_cast<int>(H), static_cast<int>(C),
@@ -634,7 +636,7 @@ int pygamd_transformer_backward_dst(const pygamd_csr* g, const float* key, const
                          it, alpha, grad_alpha, static_cast<int>(H), dpart);
       PYGAMD_LAUNCH_CHECK();
     }
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (score) {
         hipLaunchKernelGGL((transformer_bwd_dst_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st,
                            it, c, key, value, ld, alpha, grad_out, out, grad_alpha,
@@ -686,7 +688,7 @@ int pygamd_transformer_backward_src(const pygamd_csr* g, const void* slot_map, c
     const dim3 grid(wave_grid(n_src + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
     const IdxT* sm = static_cast<const IdxT*>(slot_map);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (score) {
         hipLaunchKernelGGL((transformer_bwd_src_kernel<IdxT, EPL, VEC, true>), grid, block, 0, st,
                            it, c, sm, query, alpha, grad_s, grad_out, static_cast<int>(H),
@@ -752,7 +754,7 @@ int pygamd_transformer_edge_forward(const pygamd_csr* g, const float* query, con
     const Items<IdxT> it = make_items<IdxT>(*g);
     const dim3 grid(wave_grid(n_rows + n_chunks)), block(kBlock);
     const IdxT* c = typed_col<IdxT>(*g);
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (out) {
         hipLaunchKernelGGL((transformer_edge_fwd_kernel<IdxT, EPL, VEC, true>), grid, block, 0,
                            st, it, c, query, key, value, ld, static_cast<int>(H),
@@ -821,7 +823,7 @@ int pygamd_transformer_edge_backward_dst(
                          it, alpha, grad_alpha, static_cast<int>(H), dpart);
       PYGAMD_LAUNCH_CHECK();
     }
-    ATTN_DISPATCH_SHAPE(sh, {
+    ROWWALK_DISPATCH_SHAPE(sh, {
       if (score) {
         hipLaunchKernelGGL((transformer_edge_bwd_dst_kernel<IdxT, EPL, VEC, true>), grid, block,
                            0, st, it, c, key, value, ld, alpha, grad_out, out, grad_alpha,
