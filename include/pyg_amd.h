@@ -1354,6 +1354,55 @@ PYGAMD_API int pygamd_graph_norm_backward(const pygamd_csr* g, int mode, const f
                                           float* grad_mean_scale, void* workspace,
                                           size_t workspace_bytes, void* stream);
 
+/* ---- one step of a linear propagation with its combination as the row epilogue ---------------------
+ * The body of the layers that iterate x <- A^ x and combine the iterates (nn/conv/appnp.py:111-133,
+ * sg_conv.py:93-95, ssg_conv.py:102-106, tag_conv.py:87-91, lg_conv.py:50, gcn2_conv.py:138-153).
+ * The reference runs a step as one propagate and two to three elementwise launches over [N, F];
+ * here the combination is the epilogue of the row that was just summed.  Row i of the handle g
+ * (pygamd_csr; NULL: status 1), slot k with e(k) = edge_id ? edge_id[k] : k:
+ *   t[i,:]   = sum_{k in row i, slot order} (w ? w[e(k)] : 1) * x[col[k],:]
+ *   out[i,:] = a * t[i,:]  (+ b * y[i,:] if y)  (+ c * z[i,:] if z)            (if out)
+ *   sum[i,:] = (sum_init ? 0 : sum[i,:]) + d * (that value)                      (if sum)
+ * Every product and sum is rounded on its own (no contraction), in the order written; a term with a
+ * NULL pointer is left out, no coefficient value is special (0 * NaN is NaN) and a row without
+ * slots has t = +0.0 and still gets its epilogue.  x is [n_src, ldx]; y, z, out and sum have
+ * g->n_rows rows at their own pitches (floats, each >= F): column blocks of wider planes are read
+ * and written in place; every row offset is 64-bit.  out may be y or z (the epilogue is row-local);
+ * out == x, sum == x and out == sum are status 1.  One wave per row (per group of rows below 64
+ * lanes' worth of columns), column tiles past 512 floats; rows of more than hub_threshold slots are
+ * walked as the plan's chunks into the workspace (n_chunks * F floats,
+ * pygamd_hop_workspace_size) and a second launch adds a row's chunks in chunk order and applies
+ * the epilogue once.  The backward of a step is the same call on the by-source handle:
+ * grad_x = a * A^T grad_out.  No float atomics: bitwise reproducible.
+ * Every width F >= 1 is served.  Before any launch: NULL g / args / x, out and sum both NULL, F < 1,
+ * a pitch below F, a negative size, a forbidden alias or a non-zero reserved field -> status 1; a
+ * hub plan (n_hub > 0) with a workspace below n_chunks * F floats -> status 3.  n_rows == 0
+ * returns 0.  fp32 data, int32 / int64 indices.                                                   */
+typedef struct pygamd_hop_args {
+  const float* w;     /* [n_edges] or NULL                         */
+  const float* x;     /* [n_src, ldx]                              */
+  int64_t ldx;
+  int64_t n_src;
+  int64_t F;
+  float a;
+  const float* y;     /* [n_rows, ldy] or NULL                     */
+  int64_t ldy;
+  float b;
+  const float* z;     /* [n_rows, ldz] or NULL                     */
+  int64_t ldz;
+  float c;
+  float* out;         /* [n_rows, ldo] or NULL (only sum is wanted) */
+  int64_t ldo;
+  float* sum;         /* [n_rows, lds] or NULL                     */
+  int64_t lds;
+  float d;
+  int32_t sum_init;   /* 1: sum starts from 0 instead of its old value */
+  int64_t reserved[4]; /* 0 */
+} pygamd_hop_args;
+PYGAMD_API int pygamd_hop_workspace_size(int64_t n_chunks, int64_t F, size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_hop(const pygamd_csr* g, const void* edge_id, const pygamd_hop_args* a,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- §8(f)-1 (next): one hop of uniform neighbour sampling ------------------------------------
  * Device-side counterpart of torch.ops.pyg.neighbor_sample (sampler/neighbor_sampler.py:550-577)
  * on a CSC graph (colptr over destinations, row = source of every slot).  For frontier node

@@ -1450,3 +1450,93 @@ class GraphNormFunction(Function):
             want_bias=need[2] and ctx.has_bias,
             want_mean_scale=need[3] and mean_scale is not None)
         return g_x if need[0] else None, g_w, g_b, g_ms, None, None, None, None
+
+
+def _check_hop(graph: EdgeIndex, x: Tensor, w: Optional[Tensor], square: bool = False):
+    if x.size(0) != graph.num_src_nodes:
+        raise ValueError(f"'x' has {x.size(0)} rows but the graph has {graph.num_src_nodes} "
+                         f"source nodes")
+    if square and graph.num_src_nodes != graph.num_dst_nodes:
+        raise ValueError(f"a repeated propagation needs a square graph (got sparse_size="
+                         f"{graph.sparse_size})")
+    if w is not None and w.numel() != graph.num_edges:
+        raise ValueError(f"'w' needs one value per edge ({graph.num_edges}), got {w.numel()}")
+
+
+class HopFunction(Function):
+    """One propagation step with its combination as the row epilogue (csrc/hop.hip; lg_conv.py:50,
+    gcn2_conv.py:138-141, one iteration of appnp.py:129-131 and tag_conv.py:90):
+
+        out[i] = a * sum_{(j -> i)} w_e x[j]  (+ b * y[i])  (+ c * z[i])
+
+    ONE launch over the by-destination slots; ``w`` (one value per edge in the graph's edge order,
+    or None) takes no gradient here — a layer whose weights require one runs its generic route.
+    ``y`` / ``z``: one row per destination, column blocks of wider tensors are read in place.  The
+    backward is the same launch over the by-source slots, ``grad_x = a * A^T grad_out``, and one
+    elementwise pass per ``y`` / ``z`` that wants a gradient; nothing but ``w`` is saved."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, w: Optional[Tensor], y: Optional[Tensor], z: Optional[Tensor],
+                graph: EdgeIndex, a: float, b: float, c: float):
+        _check_hop(graph, x, w)
+        fwd = graph.by_dst()
+        out = _onepass.hop_forward(fwd, fwd.perm, w, x, a, y, b, z, c)
+        ctx.save_for_backward(w)
+        ctx.graph, ctx.coef = graph, (a, b, c)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        w, = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        a, b, c = ctx.coef
+        g_x, g_y, g_z = _onepass.hop_backward(Slots.of_graph(ctx.graph), w, grad_out.contiguous(),
+                                              a, b, c, want_x=need[0], want_y=need[2],
+                                              want_z=need[3])
+        return g_x, None, g_y, g_z, None, None, None, None
+
+
+class HopsFunction(Function):
+    """``K >= 1`` propagation steps ``x_k = a * A x_{k-1} + b * h`` (appnp.py:111-133 with ``h =
+    x_0``, sg_conv.py:93-95 with ``b = 0``) and, with ``want_sum``, the running combination ``s =
+    d0 * x_0 + d * (x_1 + ... + x_K)`` of ssg_conv.py:102-106, on a square graph.  Returns ``x_K``
+    or ``(x_K, s)``.  ``h``: a tensor, None (no second term) or — ``tied`` — ``x`` itself.
+
+    Forward: exactly K launches, the combination and the running sum being their epilogue.
+    Backward: exactly K launches over the by-source slots and at most two elementwise passes,
+    whatever K (:func:`_onepass.hops_backward`).  The recurrence is linear in ``x`` and ``h``, so
+    the backward needs no iterate: only ``w`` is saved."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, h: Optional[Tensor], w: Optional[Tensor], graph: EdgeIndex,
+                K: int, a: float, b: float, d0: float, d: float, want_sum: bool, tied: bool):
+        if K < 1:
+            raise ValueError("'K' must be at least 1 (K = 0 is the identity: no call)")
+        if tied and h is not None:
+            raise ValueError("'tied' takes 'x' as 'h': pass h=None")
+        _check_hop(graph, x, w, square=True)
+        if h is not None and h.shape != x.shape:
+            raise ValueError(f"'h' must have the shape of 'x' (got {tuple(h.shape)})")
+        fwd = graph.by_dst()
+        xk, s = _onepass.hops_forward(fwd, fwd.perm, w, x, x if tied else h, K, a, b, d0, d,
+                                      want_sum)
+        ctx.save_for_backward(w)
+        ctx.graph, ctx.args = graph, (K, a, b, d0, d)
+        ctx.has_h, ctx.tied, ctx.want_sum = tied or h is not None, tied, want_sum
+        ctx.set_materialize_grads(False)  # (an unused x_K or s costs no pass over zeros)
+        return (xk, s) if want_sum else xk
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_x: Optional[Tensor], grad_s: Optional[Tensor] = None):
+        w, = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if grad_x is None and grad_s is None:
+            return (None, ) * 11
+        g_x, g_h = _onepass.hops_backward(
+            Slots.of_graph(ctx.graph), w, *ctx.args,
+            None if grad_x is None else grad_x.contiguous(),
+            None if grad_s is None else grad_s.contiguous(), has_h=ctx.has_h, tied=ctx.tied,
+            want_x=need[0], want_h=need[1] and not ctx.tied)
+        return (g_x, g_h) + (None, ) * 9

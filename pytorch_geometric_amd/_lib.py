@@ -50,6 +50,16 @@ class Csr(Structure):
     ]
 
 
+class HopArgs(Structure):
+    """Mirror of ``pygamd_hop_args`` (include/pyg_amd.h): one propagation step and its epilogue."""
+    _fields_ = [
+        ('w', c_void_p), ('x', c_void_p), ('ldx', c_int64), ('n_src', c_int64), ('F', c_int64),
+        ('a', c_float), ('y', c_void_p), ('ldy', c_int64), ('b', c_float), ('z', c_void_p),
+        ('ldz', c_int64), ('c', c_float), ('out', c_void_p), ('ldo', c_int64), ('sum', c_void_p),
+        ('lds', c_int64), ('d', c_float), ('sum_init', c_int32), ('reserved', c_int64 * 4),
+    ]
+
+
 class SageFusedArgs(Structure):
     """Mirror of ``pygamd_sage_fused_args`` (include/pyg_amd.h)."""
     _fields_ = [
@@ -345,6 +355,8 @@ SIGNATURES = {
     'pygamd_graph_norm_backward': (c_int, [_G, c_int, _P, c_int64, _P, c_int64, c_int64, c_int64,
                                            _P, _P, c_float, c_int, _P, _P, _P, c_int64, _P, _P,
                                            _P, _P, c_size_t, _P]),
+    'pygamd_hop_workspace_size': (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    'pygamd_hop': (c_int, [_G, _P, POINTER(HopArgs), _P, c_size_t, _P]),
 }
 
 # include/pyg_amd_lab.h: schedules measured and not adopted + timing probes (NOT the boundary;

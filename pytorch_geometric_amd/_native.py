@@ -2921,6 +2921,77 @@ def graph_norm_backward(ptr: Tensor, x: Tensor, grad_y: Tensor, mean: Tensor, rs
     return grad_x, g_w, g_b, g_ms
 
 
+# ---- one propagation step with its combination as the epilogue (csrc/hop.hip) ----------------------
+def _hop_plane(t: Optional[Tensor], name: str, n_rows: int, F: int) -> Optional[Tensor]:
+    if t is None:
+        return None
+    t = _strided_rows(t, name, F)
+    if t.size(0) < n_rows:
+        raise ValueError(f"'{name}' needs at least {n_rows} rows (got {t.size(0)})")
+    return t
+
+
+def hop(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], w: Optional[Tensor], x: Tensor,
+        a: float = 1.0, *, y: Optional[Tensor] = None, b: float = 0.0,
+        z: Optional[Tensor] = None, c: float = 0.0, out: Optional[Tensor] = None,
+        want_out: bool = True, sum: Optional[Tensor] = None, d: float = 1.0,
+        sum_init: bool = False, hub: Optional[HubPlan] = None) -> Optional[Tensor]:
+    """``out [n_rows, F] = a * sum_k w[edge_id[k]] x[col[k]]  (+ b y)  (+ c z)`` over the rows of
+    the handle and, with ``sum``, ``sum = (0 if sum_init else sum) + d * out`` in the same launch.
+    ``w`` (one value per edge, in the caller's edge order through ``edge_id``; None: 1), ``y``,
+    ``z`` may be None; every plane may be a column block of a wider tensor (its row stride is
+    passed) and is read or written in place.  ``out`` may be given (it may be ``y`` or ``z``, not
+    ``x`` or ``sum``); ``want_out=False`` with ``sum`` writes the sum alone and returns None."""
+    _require_device(rowptr, col, edge_id, w, x, y, z, out, sum)
+    lib = _lib.load()
+    if x.dim() != 2:
+        raise ValueError("'x' must be two-dimensional")
+    F = x.size(1)
+    if F < 1:
+        raise ValueError("'x' needs at least one column")
+    x = _strided_rows(x, 'x', F)
+    n_rows = rowptr.numel() - 1
+    y, z = _hop_plane(y, 'y', n_rows, F), _hop_plane(z, 'z', n_rows, F)
+    if w is not None:
+        if w.dtype != torch.float32 or w.dim() != 1:
+            raise ValueError(f"'w' must be a one-dimensional float32 tensor (got {w.dtype} "
+                             f"{tuple(w.shape)})")
+        if edge_id is None and w.numel() != col.numel():
+            raise ValueError("'w' needs one value per slot")
+        w = w.contiguous()
+    edge_id = _edge_id(edge_id, rowptr, col) if w is not None else None
+    for name, t in (('out', out), ('sum', sum)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.size(1) != F
+                              or t.size(0) < n_rows or t.stride(1) != 1 or t.stride(0) < F):
+            raise ValueError(f"'{name}' must be a float32 [>= {n_rows}, {F}] tensor with unit "
+                             f"column stride")
+    if not want_out and sum is None:
+        raise ValueError("nothing to compute: neither 'out' nor 'sum' is wanted")
+    if out is None and want_out:
+        out = torch.empty(n_rows, F, dtype=torch.float32, device=x.device)
+    if not want_out:
+        out = None
+    if n_rows == 0:
+        return out
+    if col.numel() == 0:  # no slots: every row is its epilogue; the launch reads no slot
+        col, w, edge_id = rowptr.new_zeros(1), None, None
+    g = _csr(rowptr, col, n_rows, hub)
+    args = _lib.HopArgs(
+        w=_p(w), x=_p(x), ldx=_ld(x), n_src=x.size(0), F=F, a=float(a),
+        y=_p(y), ldy=0 if y is None else _ld(y), b=float(b),
+        z=_p(z), ldz=0 if z is None else _ld(z), c=float(c),
+        out=_p(out), ldo=0 if out is None else _ld(out),
+        sum=_p(sum), lds=0 if sum is None else _ld(sum), d=float(d), sum_init=int(bool(sum_init)))
+    ws, ws_bytes = _workspace(lib.pygamd_hop_workspace_size, (g.n_chunks, F), x.device,
+                              g.n_chunks > 0)
+    with _timed({'kind': 'hop', 'n_rows': n_rows, 'E': col.numel(), 'F': F, 'ld': _ld(x),
+                 'w': w is not None, 'y': y is not None, 'z': z is not None,
+                 'sum': sum is not None, 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, x):
+        check(lib.pygamd_hop(ctypes.byref(g), _p(edge_id), ctypes.byref(args), _p(ws), ws_bytes,
+                             _stream(x)), 'hop')
+    return out
+
+
 # ---- dense feature transform (fp32 MFMA GEMM, csrc/gemm.hip) -------------------------------------
 def _nt_workspace(lib, M: int, n_out: int, k_red: int, device):
     """Partial-tile slabs of a launch split over its reduction (few row tiles: sampled blocks,

@@ -653,3 +653,87 @@ def hgt_backward(kqvs, wk, wv, src_pos, widx, H, grad_kv, *, want_kqvs=True, wan
         ks, vs, widx, src_pos, wk, wv, H, D, grad_kv, [b[:, :F] for b in bufs],
         [b[:, 2 * F:] for b in bufs], weight_grads=want_weights)
     return bufs, g_wk, g_wv
+
+
+def hop_forward(fwd, edge_id, w, x, a, y=None, b=0.0, z=None, c=0.0):
+    """One propagation step ``a * A x (+ b y) (+ c z)`` over a by-destination form: one launch.
+    ``w`` is in the caller's edge order (``edge_id``: slot -> edge, None: slot order)."""
+    return _native.hop(fwd.ptr, fwd.idx, edge_id if w is not None else None, w, x, a, y=y, b=b,
+                       z=z, c=c, hub=fwd.hub)
+
+
+def hop_backward(slots, w, grad_out, a, b, c, *, want_x=True, want_y=False, want_z=False):
+    """``(grad_x, grad_y, grad_z)`` of :func:`hop_forward`, None where not wanted: ``grad_x = a *
+    A^T grad_out`` is the same launch over the by-source form; the other two are one elementwise
+    pass each."""
+    g_x = g_y = g_z = None
+    if want_x:
+        bwd = slots.by_src()
+        g_x = _native.hop(bwd.ptr, bwd.idx, slots.edge_id_t() if w is not None else None, w,
+                          grad_out, a, hub=bwd.hub)
+    if want_y:
+        g_y = grad_out * b
+    if want_z:
+        g_z = grad_out * c
+    return g_x, g_y, g_z
+
+
+def hops_forward(fwd, edge_id, w, x, h, K, a, b, d0=0.0, d=0.0, want_sum=False):
+    """``(x_K, s | None)`` of the recurrence ``x_k = a * A x_{k-1} + b * h`` (``h`` None: no second
+    term), ``s = d0 * x_0 + d * sum_{k >= 1} x_k``: exactly ``K >= 1`` launches, each of which adds
+    its iterate to ``s`` in its epilogue; two planes alternate as the iterates."""
+    edge_id = edge_id if w is not None else None
+    s = x * d0 if want_sum else None
+    planes = [None, None]
+    cur = x
+    for k in range(K):
+        if planes[k & 1] is None:
+            planes[k & 1] = torch.empty(fwd.n_rows, x.size(1), dtype=x.dtype, device=x.device)
+        cur = _native.hop(fwd.ptr, fwd.idx, edge_id, w, cur, a, y=h, b=b, out=planes[k & 1],
+                          sum=s, d=d, hub=fwd.hub)
+    return cur, s
+
+
+def hops_backward(slots, w, K, a, b, d0, d, grad_x, grad_s, *, has_h=False, tied=False,
+                  want_x=True, want_h=False):
+    """``(grad_x0, grad_h)`` of :func:`hops_forward`, None where not wanted.  With ``T = A^T`` the
+    adjoints are ``G_K = grad_x + d grad_s``, ``G_{k-1} = a T G_k + d grad_s`` and ``G_0 = a T G_1
+    + d0 grad_s``: ``K`` launches over the by-source form (``grad_s`` is their ``y`` term), no
+    iterate of the forward is needed.  ``grad_h = b (G_1 + ... + G_K)``: the launches that write
+    ``G_{K-1} .. G_1`` add ``b`` times their output to one plane in their epilogue, ``b G_K`` joins
+    it in one elementwise pass.  ``tied`` (``h`` is ``x_0``, APPNP): the last launch takes that
+    plane and ``G_K`` as its ``y`` / ``z`` terms and writes the whole gradient.  Besides the
+    launches: one pass for ``G_K`` when both gradients arrive, one for ``grad_h``."""
+    bwd = slots.by_src()
+    edge_id_t = slots.edge_id_t() if w is not None else None
+    if grad_x is None:
+        g = grad_s * d
+    elif grad_s is None:
+        g = grad_x
+    else:
+        g = torch.add(grad_x, grad_s, alpha=d)
+    g_last = g
+    need_h = has_h and (want_h or (tied and want_x))
+    fold = tied and need_h and grad_s is None
+    n, F = bwd.n_rows, g.size(1)
+    acc = (torch.empty(n, F, dtype=g.dtype, device=g.device) if need_h and K >= 2 else None)
+    planes = [None, None]
+    for j in range(K, 0, -1):
+        last = j == 1
+        if last and not (want_x or fold):
+            g = None
+            break
+        y, by, z, cz = grad_s, (d0 if last else d), None, 0.0
+        if last and fold:  # grad = G_0 + b (G_1 + ... + G_K)
+            y, by, z, cz = (g_last, b, None, 0.0) if acc is None else (acc, 1.0, g_last, b)
+        if planes[j & 1] is None:
+            planes[j & 1] = torch.empty(n, F, dtype=g.dtype, device=g.device)
+        g = _native.hop(bwd.ptr, bwd.idx, edge_id_t, w, g, a, y=y, b=by, z=z, c=cz,
+                        out=planes[j & 1], sum=None if last else acc, d=b, sum_init=j == K,
+                        hub=bwd.hub)
+    g_h = None
+    if need_h and not fold:
+        g_h = g_last * b if acc is None else torch.add(acc, g_last, alpha=b)
+        if tied:
+            g, g_h = g + g_h, None
+    return (g if want_x else None), (g_h if want_h and not tied else None)

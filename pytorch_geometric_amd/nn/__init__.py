@@ -4,6 +4,7 @@ from .aggr import (Aggregation, DegreeScalerAggregation, FusedAggregation, MaxAg
 from .conv import (CGConv, FastRGCNConv, FiLMConv, GINConv, GINEConv, GATConv, GATv2Conv, GCNConv, GraphConv, HANConv, HeteroConv, HGTConv,
                    GENConv, GMMConv, MessagePassing, NNConv, PNAConv, ResGatedGraphConv, RGATConv, RGCNConv, SAGEConv, TransformerConv,
                    gcn_norm, group)
+from .conv import APPNP, GCN2Conv, LGConv, SGConv, SSGConv, TAGConv
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
 from .norm import BatchNorm, GraphNorm, LayerNorm, MessageNorm
@@ -19,4 +20,5 @@ __all__ = [
     'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv', 'FiLMConv', 'RGATConv',
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT', 'GraphNorm', 'LayerNorm', 'BatchNorm',
     'global_add_pool', 'global_mean_pool', 'global_max_pool',
+    'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv',
 ]

@@ -18,8 +18,14 @@ from .nn_conv import NNConv
 from .cg_conv import CGConv
 from .film_conv import FiLMConv
 from .rgat_conv import RGATConv
+from .appnp import APPNP
+from .sg_conv import SGConv
+from .ssg_conv import SSGConv
+from .tag_conv import TAGConv
+from .lg_conv import LGConv
+from .gcn2_conv import GCN2Conv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
            'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv',
-           'FiLMConv', 'RGATConv']
+           'FiLMConv', 'RGATConv', 'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv']

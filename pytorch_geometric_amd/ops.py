@@ -65,6 +65,8 @@ Operators (all index tensors int32 / int64, features float32):
 ``graph_norm``              ``(Tensor x, Tensor ptr, Tensor? weight, Tensor? bias,
                             Tensor? mean_scale, float eps, str mode, bool std_eps)
                             -> (Tensor y, Tensor mean, Tensor rstd)``
+``hop``                     ``(Tensor rowptr, Tensor col, Tensor? edge_id, Tensor? w, Tensor x,
+                            float a, Tensor? y, float b, Tensor? z, float c) -> Tensor``
 ==========================  ===========================================================
 """
 from typing import List, Optional, Tuple
@@ -1346,6 +1348,63 @@ def _graph_norm_bwd(ctx, grad, grad_mean, grad_rstd):
 
 register_autograd('pyg_amd::graph_norm', _graph_norm_bwd, setup_context=_graph_norm_setup)
 
+
+# ---- one propagation step on a CSR pair (rows = destinations) --------------------------------------
+@custom_op('pyg_amd::hop', mutates_args=(), device_types=_DEV)
+def hop(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], w: Optional[Tensor], x: Tensor,
+        a: float, y: Optional[Tensor], b: float, z: Optional[Tensor], c: float) -> Tensor:
+    """``out [n_dst, F] = a * sum_k w[edge_id[k]] x[col[k]] (+ b * y) (+ c * z)`` (lg_conv.py:50,
+    gcn2_conv.py:138-141, one iteration of appnp.py:129-131): one launch, the combination being
+    the epilogue of the row sum.  ``w`` (None: 1) is in the caller's edge order (``edge_id=None``:
+    in slot order) and takes no gradient; ``y`` / ``z`` have one row per destination."""
+    n_dst = rowptr.numel() - 1
+    for name, t in (('y', y), ('z', z)):
+        if t is not None and tuple(t.shape) != (n_dst, x.size(1)):
+            raise ValueError(f"'{name}' must be [{n_dst}, {x.size(1)}] (got {tuple(t.shape)})")
+    return _native.hop(rowptr, col, edge_id, w, x, a, y=y, b=b, z=z, c=c,
+                       hub=_native.hub_plan(rowptr))
+
+
+@hop.register_fake
+def _(rowptr, col, edge_id, w, x, a, y, b, z, c):
+    return x.new_empty(rowptr.numel() - 1, x.shape[1])
+
+
+@custom_op('pyg_amd::hop_backward', mutates_args=(), device_types=_DEV)
+def hop_backward(grad: Tensor, rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor],
+                 w: Optional[Tensor], n_src: int, a: float, b: float, c: float, need_x: bool,
+                 need_y: bool, need_z: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """The gradients of ``(x, y, z)``; one that is not needed is an empty tensor."""
+    grads = _onepass.hop_backward(Slots.of_csr(rowptr, col, n_src, edge_id), w, grad, a, b, c,
+                                  want_x=need_x, want_y=need_y, want_z=need_z)
+    return tuple(grad.new_empty(0) if g is None else g for g in grads)
+
+
+@hop_backward.register_fake
+def _(grad, rowptr, col, edge_id, w, n_src, a, b, c, need_x, need_y, need_z):
+    none = grad.new_empty(0)
+    return (grad.new_empty(n_src, grad.shape[1]) if need_x else none,
+            torch.empty_like(grad) if need_y else grad.new_empty(0),
+            torch.empty_like(grad) if need_z else grad.new_empty(0))
+
+
+def _hop_setup(ctx, inputs, output):
+    rowptr, col, edge_id, w, x, a, y, b, z, c = inputs
+    ctx.coef, ctx.n_src = (a, b, c), x.size(0)
+    ctx.save_for_backward(rowptr, col, edge_id, w)
+
+
+def _hop_bwd(ctx, grad):
+    rowptr, col, edge_id, w = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    g_x, g_y, g_z = hop_backward(grad.contiguous(), rowptr, col, edge_id, w, ctx.n_src, *ctx.coef,
+                                 need[4], need[6], need[8])
+    return (None, None, None, None, g_x if need[4] else None, None, g_y if need[6] else None,
+            None, g_z if need[8] else None, None)
+
+
+register_autograd('pyg_amd::hop', _hop_bwd, setup_context=_hop_setup)
+
 OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_backward',
        'segment_csr', 'segment_csr_backward', 'softmax_csr', 'softmax_csr_backward', 'spmm',
        'spmm_backward', 'linear', 'linear_backward', 'gatv2_attend', 'gatv2_attend_backward', 'transformer_attend',
@@ -1356,4 +1415,4 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'resgated_aggregate_backward', 'han_attend', 'han_attend_backward', 'mixture_conv',
        'mixture_conv_backward', 'cg_aggregate', 'cg_aggregate_backward', 'film_aggregate',
        'film_aggregate_backward', 'rgat_aggregate', 'rgat_aggregate_backward', 'graph_norm',
-       'graph_norm_backward')
+       'graph_norm_backward', 'hop', 'hop_backward')
