@@ -2064,6 +2064,55 @@ PYGAMD_API int pygamd_sage_layer_fused(const pygamd_spmm_args* graph,
                                        const pygamd_sage_fused_args* f, void* workspace,
                                        size_t workspace_bytes, void* stream);
 
+/* ---- geometric searches: knn, radius, fps — csrc/cluster.hip ---------------------------------------
+ * The reference's fps / knn / knn_graph / radius / radius_graph / nearest only forward to
+ * torch.ops.pyg.fps / knn / radius / nearest (nn/pool/__init__.py:85, 140, 199, 265, 331, 375) and
+ * DynamicEdgeConv calls torch.ops.pyg.knn in every forward (nn/conv/edge_conv.py:138): pyg-lib,
+ * which has no ROCm build.  These three entry points are those operators.
+ * Examples are contiguous row ranges: example e owns the rows [ptr_x[e], ptr_x[e + 1]) of x and the
+ * rows [ptr_y[e], ptr_y[e + 1]) of y (pointer vectors of B + 1 entries, pygamd_index2ptr of a
+ * non-decreasing batch vector; int32 / int64 by idx_dtype).  A search never crosses an example.
+ * x [N, ldx] and y [M, ldy] are read in place at their pitches (floats, >= F; 64-bit row offsets):
+ * a column block of a wider plane needs no copy.  float32, no float atomics, bitwise reproducible.
+ * Distance: sum_c (x_c - y_c)^2 accumulated in float32 in column order, in the DIFFERENCE form — a
+ * point is at distance exactly 0 from itself, and the value is within (F + 4) 2^-23 (relative) of
+ * the exact one.  knn's cosine distance is 1 - x.y / (|x| |y|), its three sums taken in one pass.
+ *
+ * pygamd_knn: for every row q of y the k rows of x of q's example with the smallest distance,
+ *   ascending by (distance, index of x) — ties go to the smaller index.  out_index [M, k] holds
+ *   global row indices of x in that order, padded with -1, out_count [M] the number found
+ *   (min(k, candidates)).  exclude_same_index != 0 skips the candidate whose global row index
+ *   equals q (knn_graph(loop=False)).  One query per wave at a time, four queries register-blocked
+ *   per wave over candidate tiles of 64 staged in LDS; the running best k sits one slot per lane.
+ *   Envelope: 1 <= k <= 64, 1 <= F <= 512; example sizes below 2^31.
+ * pygamd_radius: for every row q of y the rows of x of q's example with distance < r * r (STRICT;
+ *   r * r formed in float32), in ascending index; at most max_num_neighbors (>= 1), the FIRST ones
+ *   in index order.  out_index [M, max_num_neighbors] padded with -1, out_count [M].  r >= 0.
+ * pygamd_fps: farthest point sampling, one workgroup per example.  Example e yields the
+ *   out_ptr[e + 1] - out_ptr[e] picks out[out_ptr[e] ...) (global row indices, selection order;
+ *   the host computes the counts, ceil(ratio n_e), at most n_e), starting from the global row
+ *   start[e].  Each step picks the not yet picked point with the largest minimum distance to the
+ *   picked set, ties to the lowest index, so duplicates are picked at distance 0 rather than an
+ *   index twice.  total = out_ptr[B].  Workspace: pygamd_fps_workspace_size(N) (the running minima
+ *   of examples too large for LDS).  Envelope: 1 <= F <= 512.
+ * Before any device work: k outside 1..64, max_num_neighbors < 1, r < 0 or NaN, F outside 1..512,
+ * a pitch below F, a negative size, an unknown idx_dtype, or a NULL pointer with a non-empty size
+ * -> status 1; a short fps workspace -> status 3.  M == 0 (fps: no pick wanted) returns 0.        */
+PYGAMD_API int pygamd_knn(const float* x, int64_t ldx, int64_t N, const float* y, int64_t ldy,
+                          int64_t M, int64_t F, const void* ptr_x, const void* ptr_y,
+                          int idx_dtype, int64_t B, int k, int cosine, int exclude_same_index,
+                          int64_t* out_index, int32_t* out_count, void* stream);
+PYGAMD_API int pygamd_radius(const float* x, int64_t ldx, int64_t N, const float* y, int64_t ldy,
+                             int64_t M, int64_t F, const void* ptr_x, const void* ptr_y,
+                             int idx_dtype, int64_t B, float r, int64_t max_num_neighbors,
+                             int exclude_same_index, int64_t* out_index, int32_t* out_count,
+                             void* stream);
+PYGAMD_API int pygamd_fps_workspace_size(int64_t N, size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_fps(const float* x, int64_t ldx, int64_t N, int64_t F, const void* ptr,
+                          const void* out_ptr, const void* start, int idx_dtype, int64_t B,
+                          int64_t total, int64_t* out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -357,6 +357,13 @@ SIGNATURES = {
                                            _P, _P, c_size_t, _P]),
     'pygamd_hop_workspace_size': (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
     'pygamd_hop': (c_int, [_G, _P, POINTER(HopArgs), _P, c_size_t, _P]),
+    'pygamd_knn': (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int,
+                           c_int64, c_int, c_int, c_int, _P, _P, _P]),
+    'pygamd_radius': (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int,
+                              c_int64, c_float, c_int64, c_int, _P, _P, _P]),
+    'pygamd_fps_workspace_size': (c_int, [c_int64, POINTER(c_size_t)]),
+    'pygamd_fps': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int, c_int64, c_int64,
+                           _P, _P, c_size_t, _P]),
 }
 
 # include/pyg_amd_lab.h: schedules measured and not adopted + timing probes (NOT the boundary;

@@ -4288,3 +4288,91 @@ def hgt_relation_backward(ks, vs, widx, src_type, wk: Tensor, wv: Tensor, H: int
             len(grad_ks), _p(grad_wk), _p(grad_wv), _p(ws), ws_bytes, _stream(wk)),
             'hgt_relation_backward')
     return grad_wk, grad_wv
+
+
+# ---- geometric searches (csrc/cluster.hip) -----------------------------------------------------------
+KNN_MAX_K = 64        # the running best k sits one slot per lane
+CLUSTER_MAX_F = 512
+
+
+def cluster_supported(F: int, k: int = 1) -> bool:
+    """The envelope of ``pygamd_knn`` / ``pygamd_radius`` / ``pygamd_fps``."""
+    return 1 <= int(F) <= CLUSTER_MAX_F and 1 <= int(k) <= KNN_MAX_K
+
+
+def _cluster_rows(t: Tensor, name: str) -> Tensor:
+    if t.dim() != 2:
+        raise ValueError(f"'{name}' must be two-dimensional (got {t.dim()} dimensions)")
+    return _strided_rows(t, name, t.size(1))
+
+
+def _cluster_ptrs(ptr_x: Tensor, ptr_y: Tensor):
+    if ptr_x.dtype != ptr_y.dtype or ptr_x.numel() != ptr_y.numel() or ptr_x.numel() < 1:
+        raise ValueError("'ptr_x' and 'ptr_y' need one index dtype and B + 1 entries each")
+    return ptr_x.contiguous(), ptr_y.contiguous(), ptr_x.numel() - 1
+
+
+def knn(x: Tensor, y: Tensor, ptr_x: Tensor, ptr_y: Tensor, k: int, cosine: bool = False,
+        exclude_same_index: bool = False) -> Tuple[Tensor, Tensor]:
+    """``pygamd_knn``: ``(index [M, k] int64, count [M] int32)`` — for every row of ``y`` the ``k``
+    nearest rows of ``x`` of its example, ascending by (distance, index), padded with -1.  ``x`` and
+    ``y`` may be column blocks of wider tensors."""
+    _require_device(x, y, ptr_x, ptr_y)
+    x, y = _cluster_rows(x, 'x'), _cluster_rows(y, 'y')
+    if x.size(1) != y.size(1):
+        raise ValueError(f"'x' and 'y' differ in width ({x.size(1)} and {y.size(1)})")
+    ptr_x, ptr_y, B = _cluster_ptrs(ptr_x, ptr_y)
+    N, M, F = x.size(0), y.size(0), x.size(1)
+    index = torch.empty(M, int(k), dtype=torch.int64, device=y.device)
+    count = torch.empty(M, dtype=torch.int32, device=y.device)
+    with _timed({'kind': 'cluster', 'op': 'knn', 'N': N, 'M': M, 'F': F, 'k': int(k), 'B': B}, y):
+        check(_lib.load().pygamd_knn(
+            _p(x), _ld(x), N, _p(y), _ld(y), M, F, _p(ptr_x), _p(ptr_y), _idx_dtype(ptr_x), B,
+            int(k), int(bool(cosine)), int(bool(exclude_same_index)), _p(index), _p(count),
+            _stream(y)), 'knn')
+    return index, count
+
+
+def radius(x: Tensor, y: Tensor, ptr_x: Tensor, ptr_y: Tensor, r: float, max_num_neighbors: int,
+           exclude_same_index: bool = False) -> Tuple[Tensor, Tensor]:
+    """``pygamd_radius``: ``(index [M, max_num_neighbors] int64, count [M] int32)`` — for every row
+    of ``y`` the rows of ``x`` of its example with squared distance ``< r * r`` (float32), in
+    ascending index, the first ``max_num_neighbors`` of them, padded with -1."""
+    _require_device(x, y, ptr_x, ptr_y)
+    x, y = _cluster_rows(x, 'x'), _cluster_rows(y, 'y')
+    if x.size(1) != y.size(1):
+        raise ValueError(f"'x' and 'y' differ in width ({x.size(1)} and {y.size(1)})")
+    ptr_x, ptr_y, B = _cluster_ptrs(ptr_x, ptr_y)
+    N, M, F = x.size(0), y.size(0), x.size(1)
+    cap = int(max_num_neighbors)
+    index = torch.empty(M, max(cap, 0), dtype=torch.int64, device=y.device)
+    count = torch.empty(M, dtype=torch.int32, device=y.device)
+    with _timed({'kind': 'cluster', 'op': 'radius', 'N': N, 'M': M, 'F': F, 'cap': cap, 'B': B},
+                y):
+        check(_lib.load().pygamd_radius(
+            _p(x), _ld(x), N, _p(y), _ld(y), M, F, _p(ptr_x), _p(ptr_y), _idx_dtype(ptr_x), B,
+            float(r), cap, int(bool(exclude_same_index)), _p(index), _p(count), _stream(y)),
+            'radius')
+    return index, count
+
+
+def fps(x: Tensor, ptr: Tensor, out_ptr: Tensor, start: Tensor, total: int) -> Tensor:
+    """``pygamd_fps``: the ``total = out_ptr[-1]`` picks of farthest point sampling, example ``e``
+    yielding ``out_ptr[e + 1] - out_ptr[e]`` global row indices in selection order from the global
+    row ``start[e]``.  ``ptr``, ``out_ptr`` and ``start`` share one index dtype."""
+    _require_device(x, ptr, out_ptr, start)
+    x = _cluster_rows(x, 'x')
+    B = ptr.numel() - 1
+    if not (ptr.dtype == out_ptr.dtype == start.dtype) or out_ptr.numel() != B + 1 \
+            or start.numel() != B or B < 0:
+        raise ValueError("'ptr' and 'out_ptr' need B + 1 entries, 'start' B, in one index dtype")
+    ptr, out_ptr, start = ptr.contiguous(), out_ptr.contiguous(), start.contiguous()
+    N, F = x.shape
+    lib = _lib.load()
+    out = torch.empty(int(total), dtype=torch.int64, device=x.device)
+    ws, ws_bytes = _workspace(lib.pygamd_fps_workspace_size, (N, ), x.device)
+    with _timed({'kind': 'cluster', 'op': 'fps', 'N': N, 'F': F, 'B': B, 'total': int(total)}, x):
+        check(lib.pygamd_fps(_p(x), _ld(x), N, F, _p(ptr), _p(out_ptr), _p(start),
+                             _idx_dtype(ptr), B, int(total), _p(out), _p(ws), ws_bytes,
+                             _stream(x)), 'fps')
+    return out

@@ -5,10 +5,12 @@ from .conv import (CGConv, FastRGCNConv, FiLMConv, GINConv, GINEConv, GATConv, G
                    GENConv, GMMConv, MessagePassing, NNConv, PNAConv, ResGatedGraphConv, RGATConv, RGCNConv, SAGEConv, TransformerConv,
                    gcn_norm, group)
 from .conv import APPNP, GCN2Conv, LGConv, SGConv, SSGConv, TAGConv
+from .conv import DynamicEdgeConv, EdgeConv, PointConv, PointNetConv
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
 from .norm import BatchNorm, GraphNorm, LayerNorm, MessageNorm
 from .pool import global_add_pool, global_max_pool, global_mean_pool
+from .pool import fps, knn, knn_graph, nearest, radius, radius_graph
 from . import functional  # noqa: F401
 
 __all__ = [
@@ -21,4 +23,6 @@ __all__ = [
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT', 'GraphNorm', 'LayerNorm', 'BatchNorm',
     'global_add_pool', 'global_mean_pool', 'global_max_pool',
     'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv',
+    'EdgeConv', 'DynamicEdgeConv', 'PointNetConv', 'PointConv',
+    'fps', 'knn', 'knn_graph', 'radius', 'radius_graph', 'nearest',
 ]

@@ -24,8 +24,11 @@ from .ssg_conv import SSGConv
 from .tag_conv import TAGConv
 from .lg_conv import LGConv
 from .gcn2_conv import GCN2Conv
+from .edge_conv import DynamicEdgeConv, EdgeConv
+from .point_conv import PointConv, PointNetConv
 
 __all__ = ['MessagePassing', 'SAGEConv', 'GCNConv', 'gcn_norm', 'GATConv', 'GATv2Conv', 'TransformerConv', 'RGCNConv', 'FastRGCNConv',
            'GraphConv', 'HeteroConv', 'group', 'HGTConv', 'GINConv', 'GINEConv',
            'PNAConv', 'GENConv', 'ResGatedGraphConv', 'HANConv', 'GMMConv', 'NNConv', 'CGConv',
-           'FiLMConv', 'RGATConv', 'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv']
+           'FiLMConv', 'RGATConv', 'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv',
+           'EdgeConv', 'DynamicEdgeConv', 'PointNetConv', 'PointConv']

@@ -2,13 +2,17 @@
 arguments of ``torch_geometric.nn.pool`` (torch_geometric/nn/pool/glob.py:9-106).  Each is one
 ``scatter`` over the batch vector; ``batch=None`` reduces all nodes into one graph.  The node
 dimension is ``-2``, or ``-1`` for a one-dimensional ``x``.  Float32 device tensors go through this
-package's ``scatter``; host tensors and other dtypes through the same reduction in plain torch."""
+package's ``scatter``; host tensors and other dtypes through the same reduction in plain torch.
+
+The geometric searches ``fps``, ``knn``, ``knn_graph``, ``radius``, ``radius_graph`` and ``nearest``
+live in :mod:`.cluster`."""
 from typing import Optional
 
 import torch
 from torch import Tensor
 
 from ...utils import scatter
+from .cluster import fps, knn, knn_graph, nearest, radius, radius_graph
 
 
 def _node_dim(x: Tensor) -> int:
@@ -55,4 +59,5 @@ def global_max_pool(x: Tensor, batch: Optional[Tensor], size: Optional[int] = No
     return _scatter(x, batch, dim, size, 'max')
 
 
-__all__ = ['global_add_pool', 'global_mean_pool', 'global_max_pool']
+__all__ = ['global_add_pool', 'global_mean_pool', 'global_max_pool',
+           'fps', 'knn', 'knn_graph', 'radius', 'radius_graph', 'nearest']
