@@ -5,375 +5,68 @@ fallback: if the library is missing (and cannot be built) or a call fails, we ra
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64,
-                    c_size_t, c_uint64, c_void_p)
+from ctypes import Structure
 
-from . import _build
+from . import _build, _header
+from ._header import PygAmdError
 
-ABI_VERSION = 11
-X_DENSE, X_COMPRESSED = 0, 1  # pygamd_x_format  # PYGAMD_ABI_VERSION of include/pyg_amd.h
-AGG_GIVEN = 2  # PYGAMD_AGG_GIVEN: save_agg of the one-kernel SAGE layer, "rows given"
-IDX_I32, IDX_I64 = 0, 1
-SUM, MEAN, MIN, MAX, MUL, ANY = 0, 1, 2, 3, 4, 5
+
+def _read(name):
+    path = os.path.join(os.path.dirname(_build.PKG_DIR), 'include', name)
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError as e:
+        raise PygAmdError(f"{path} is missing: the ctypes binding of the library is derived from "
+                          f"the header that declares it ({e})") from None
+
+
+# Everything below that mirrors the C boundary — constants, argument structs, signatures — is read
+# from the two headers, once, here.
+_H = _header.parse(_read('pyg_amd.h'))
+_LAB = _header.parse(_read('pyg_amd_lab.h'), included=_H)
+CONSTANTS = _H.constants  # every `#define PYGAMD_X <integer>` and enumerator of include/pyg_amd.h
+
+ABI_VERSION = CONSTANTS['PYGAMD_ABI_VERSION']
+X_DENSE, X_COMPRESSED = CONSTANTS['PYGAMD_X_DENSE'], CONSTANTS['PYGAMD_X_COMPRESSED']
+AGG_GIVEN = CONSTANTS['PYGAMD_AGG_GIVEN']  # save_agg of the one-kernel SAGE layer, "rows given"
+IDX_I32, IDX_I64 = CONSTANTS['PYGAMD_IDX_I32'], CONSTANTS['PYGAMD_IDX_I64']
+SUM, MEAN, MIN, MAX, MUL, ANY = (CONSTANTS['PYGAMD_' + r]
+                                 for r in ('SUM', 'MEAN', 'MIN', 'MAX', 'MUL', 'ANY'))
 REDUCE_IDS = {'sum': SUM, 'add': SUM, 'mean': MEAN, 'min': MIN, 'amin': MIN, 'max': MAX,
               'amax': MAX, 'mul': MUL, 'any': ANY}
-
-
-class PygAmdError(RuntimeError):
-    pass
+ERR_UNSUPPORTED, ERR_HIP = CONSTANTS['PYGAMD_ERR_UNSUPPORTED'], CONSTANTS['PYGAMD_ERR_HIP']
+GEMM_MODES = {'fp32': CONSTANTS['PYGAMD_GEMM_FP32'], 'split': CONSTANTS['PYGAMD_GEMM_SPLIT_BF16']}
 
 
 class SpmmArgs(Structure):
     """Mirror of ``pygamd_spmm_args`` (include/pyg_amd.h)."""
-    _fields_ = [
-        ('rowptr', c_void_p), ('col', c_void_p), ('eid', c_void_p), ('w', c_void_p),
-        ('src_scale', c_void_p), ('x', c_void_p), ('out', c_void_p), ('arg_out', c_void_p),
-        ('n_rows', c_int64), ('n_src', c_int64), ('F', c_int64), ('ldx', c_int64),
-        ('ldo', c_int64), ('idx_dtype', c_int32), ('reduce', c_int32), ('w_heads', c_int32),
-        ('head_dim', c_int32), ('hub_rows', c_void_p), ('hub_chunk_ptr', c_void_p),
-        ('n_hub', c_int64), ('n_chunks', c_int64), ('hub_threshold', c_int64),
-        ('hub_chunk', c_int64), ('accumulate', c_int32), ('hub_phase', c_int32),
-        ('arg32_out', c_void_p), ('relu_mask', c_void_p), ('ld_mask', c_int64),
-        ('relu_bits', c_void_p), ('ld_bits', c_int64), ('src_bits', c_void_p),
-        ('src_bits_set', c_void_p), ('x_format', c_int32), ('reserved0', c_int32),
-        ('rowend', c_void_p), ('accumulate_rows', c_int64),
-    ]
+    _fields_ = _header.fields(_H.structs['pygamd_spmm_args'])
 
 
 class Csr(Structure):
     """Mirror of ``pygamd_csr`` (include/pyg_amd.h): a CSR handle with its hub plan."""
-    _fields_ = [
-        ('rowptr', c_void_p), ('col', c_void_p), ('idx_dtype', c_int32), ('reserved0', c_int32),
-        ('n_rows', c_int64), ('hub_rows', c_void_p), ('hub_chunk_ptr', c_void_p),
-        ('n_hub', c_int64), ('n_chunks', c_int64), ('hub_threshold', c_int64),
-        ('hub_chunk', c_int64),
-    ]
+    _fields_ = _header.fields(_H.structs['pygamd_csr'])
 
 
 class HopArgs(Structure):
     """Mirror of ``pygamd_hop_args`` (include/pyg_amd.h): one propagation step and its epilogue."""
-    _fields_ = [
-        ('w', c_void_p), ('x', c_void_p), ('ldx', c_int64), ('n_src', c_int64), ('F', c_int64),
-        ('a', c_float), ('y', c_void_p), ('ldy', c_int64), ('b', c_float), ('z', c_void_p),
-        ('ldz', c_int64), ('c', c_float), ('out', c_void_p), ('ldo', c_int64), ('sum', c_void_p),
-        ('lds', c_int64), ('d', c_float), ('sum_init', c_int32), ('reserved', c_int64 * 4),
-    ]
+    _fields_ = _header.fields(_H.structs['pygamd_hop_args'])
 
 
 class SageFusedArgs(Structure):
     """Mirror of ``pygamd_sage_fused_args`` (include/pyg_amd.h)."""
-    _fields_ = [
-        ('x_root', c_void_p), ('ld_root', c_int64), ('w', c_void_p), ('ldw', c_int64),
-        ('bias', c_void_p), ('Fo', c_int64), ('relu', c_int32), ('save_agg', c_int32),
-        ('y', c_void_p), ('ldy', c_int64), ('relu_bits_out', c_void_p), ('ld_bits_out', c_int64),
-        ('mask_bits', c_void_p), ('ld_mask_bits', c_int64), ('row_scale', c_void_p),
-        ('y_scaled', c_void_p), ('ldy_scaled', c_int64),
-        ('compressed_out', c_void_p), ('ld_compressed', c_int64),
-    ]
+    _fields_ = _header.fields(_H.structs['pygamd_sage_fused_args'])
 
 
-# name -> (restype, argtypes); must list every PYGAMD_API symbol of include/pyg_amd.h
-_P = c_void_p
-_G = POINTER(Csr)
-SIGNATURES = {
-    'pygamd_abi_version': (c_int, []),
-    'pygamd_status_string': (c_char_p, [c_int]),
-    'pygamd_last_hip_error': (c_int, []),
-    'pygamd_build_arch': (c_char_p, []),
-    'pygamd_index_sort_workspace_bytes': (c_int, [c_int, c_int64, POINTER(c_size_t)]),
-    'pygamd_index_sort': (c_int, [_P, c_int, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
-    'pygamd_index2ptr': (c_int, [_P, c_int, c_int64, c_int64, _P, _P]),
-    'pygamd_ptr2index': (c_int, [_P, c_int, c_int64, c_int64, _P, _P]),
-    'pygamd_index_minmax': (c_int, [_P, c_int, c_int64, _P, _P]),
-    'pygamd_permute_index': (c_int, [_P, c_int, _P, c_int64, _P, _P]),
-    'pygamd_cast_index': (c_int, [_P, c_int64, c_int, _P, _P]),
-    'pygamd_index_guard': (c_int, [_P, c_int, c_int64, c_int64, _P, c_int, _P, _P]),
-    'pygamd_cumsum_workspace_bytes': (c_int, [c_int, c_int64, POINTER(c_size_t)]),
-    'pygamd_cumsum': (c_int, [_P, c_int, c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_hub_plan_workspace_bytes': (c_int, [c_int, c_int64, POINTER(c_size_t)]),
-    'pygamd_hub_plan': (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, _P, c_int64,
-                                POINTER(c_int64), POINTER(c_int64), _P, c_size_t, _P]),
-    'pygamd_rows_compress': (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P]),
-    'pygamd_rows_compress_scaled': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, c_int64, _P]),
-    'pygamd_rows_pack': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, c_int64, c_int64, _P,
-                                 c_int64, c_int64, _P, _P, _P]),
-    'pygamd_live_lists_flag': (c_int, [_P, _P, c_int64, c_int, _P, _P]),
-    'pygamd_live_lists_build': (c_int, [_P, _P, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P,
-                                        _P, _P, _P, _P]),
-    'pygamd_live_lists_builds': (c_int, [POINTER(c_int64)]),
-    'pygamd_spmm_csr_workspace_bytes': (c_int, [POINTER(SpmmArgs), POINTER(c_size_t)]),
-    'pygamd_spmm_csr': (c_int, [POINTER(SpmmArgs), _P, c_size_t, _P]),
-    'pygamd_spmm_csr_tie_count': (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, c_int64,
-                                          c_int64, c_int, _P, _P]),
-    'pygamd_spmm_csr_minmax_backward': (c_int, [_P, _P, c_int, _P, c_int64, _P, _P, _P, c_int64,
-                                                c_int64, c_int64, _P, c_int64, _P]),
-    'pygamd_spmm_csr_minmax_backward_dst': (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P,
-                                                    c_int64, c_int64, c_int64, c_int64, c_int, _P,
-                                                    c_int64, _P]),
-    'pygamd_multi_reduce_csr': (c_int, [_P, _P, c_int, _P, c_int64, c_int64, c_int64, _P, _P, _P,
-                                        _P, c_int64, _P]),
-    'pygamd_minmax_backward_src_workspace_bytes': (c_size_t, [c_int64, c_int64, c_int64]),
-    'pygamd_spmm_csr_minmax_backward_src': (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_int64, _P,
-                                                    c_int64, _P, c_int64, c_int64, c_int64,
-                                                    c_int64, c_int64, c_int, _P, c_size_t, _P,
-                                                    c_int64, _P]),
-    'pygamd_spmm_csr_minmax_backward_arg': (c_int, [_P, _P, c_int, _P, _P, c_int64, _P, c_int64, _P,
-                                                    c_int64, c_int64, c_int64, c_int64, c_int, _P,
-                                                    c_int64, _P]),
-    'pygamd_sddmm_csr': (c_int, [_P, _P, _P, c_int, _P, c_int64, _P, c_int64, c_int64, c_int64,
-                                 c_int32, c_int32, _P, _P]),
-    'pygamd_sddmm_spmm_csr': (c_int, [_P, _P, _P, c_int, _P, c_int64, _P, c_int64, c_int64,
-                                      c_int64, c_int32, c_int32, _P, _P, _P, c_int64, _P]),
-    'pygamd_colsum': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P]),
-    'pygamd_bias_act': (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int, _P, c_int64, _P]),
-    'pygamd_relu_backward_colsum': (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, _P,
-                                            c_int64, _P, _P]),
-    'pygamd_sage_layer_forward_supported': (c_int, [c_int64, c_int64, c_int]),
-    'pygamd_sage_layer_forward': (c_int, [POINTER(SpmmArgs), _P, c_int64, _P, c_int64, _P, c_int64,
-                                          c_int, c_int, _P, c_int64, _P, c_int64, _P, c_size_t,
-                                          _P]),
-    'pygamd_sage_layer_fused': (c_int, [POINTER(SpmmArgs), POINTER(SageFusedArgs), _P, c_size_t,
-                                        _P]),
-    'pygamd_sage_layer_fused_workspace_bytes': (c_int, [POINTER(SpmmArgs), POINTER(SageFusedArgs),
-                                                        POINTER(c_size_t)]),
-    'pygamd_linear_nt_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_linear_forward': (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64,
-                                      c_int, c_int, _P, c_int64, _P, c_size_t, _P]),
-    'pygamd_set_gemm_mode': (c_int, [c_int]),
-    'pygamd_get_gemm_mode': (c_int, []),
-    'pygamd_linear_dgrad': (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64,
-                                    c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P]),
-    'pygamd_linear_dgrad2': (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int64,
-                                     c_int64, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P,
-                                     c_int64, _P, c_size_t, _P]),
-    'pygamd_linear_wgrad_workspace_bytes': (c_int, [c_int64, c_int64, c_int64,
-                                                    POINTER(c_size_t)]),
-    'pygamd_linear_wgrad': (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, c_int,
-                                    c_int, _P, c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_linear_wgrad2': (c_int, [_P, c_int64, _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                     c_int64, c_int64, c_int, c_int, _P, c_int64, _P, _P,
-                                     c_size_t, _P]),
-    'pygamd_segment_matmul_tile_rows': (c_int, []),
-    'pygamd_segment_matmul_workspace_bytes': (c_int, [c_int64, c_int64, c_int64,
-                                                      POINTER(c_size_t)]),
-    'pygamd_segment_matmul': (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int64,
-                                      _P, c_int64, c_int64, c_int64, c_int64, _P, c_int64, _P,
-                                      c_size_t, _P]),
-    'pygamd_segment_matmul_wgrad': (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int64,
-                                            c_int64, c_int64, c_int64, _P, _P]),
-    'pygamd_sample_max_fanout': (c_int, []),
-    'pygamd_sample_neighbors': (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, c_uint64, c_int,
-                                        _P, _P, _P, _P, _P]),
-    'pygamd_sample_neighbors_weighted': (c_int, [_P, _P, c_int, _P, _P, c_int64, _P, c_int64,
-                                                 c_uint64, c_int, _P, _P, _P, _P, _P]),
-    'pygamd_sample_temporal_window': (c_int, [_P, _P, c_int, _P, c_int, _P, _P, c_int64, c_int64,
-                                              c_int, c_int, _P, _P, _P, _P, _P]),
-    'pygamd_sample_neighbors_temporal': (c_int, [_P, c_int, _P, c_int64, _P, _P, _P, c_int64,
-                                                 c_uint64, c_int, _P, _P, _P, _P, _P]),
-    'pygamd_slots_max_fanout': (c_int, []),
-    'pygamd_slots_max_hops': (c_int, []),
-    'pygamd_slots_seed': (c_int, [_P, c_int, c_int64, _P, _P, _P, _P]),
-    'pygamd_slots_sample': (c_int, [_P, _P, c_int, _P, c_int64, c_int64, c_int, c_int64, c_int64,
-                                    c_uint64, c_int, _P, _P, _P, _P, _P, _P]),
-    'pygamd_slots_resolve': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, c_int,
-                                     _P]),
-    'pygamd_slots_gather': (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P]),
-    'pygamd_slots_transpose': (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    'pygamd_cross_entropy_step_workspace_bytes': (c_int, [c_int64, _P]),
-    'pygamd_cross_entropy_step': (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, _P,
-                                          c_int64, _P, _P, c_size_t, _P, _P, _P]),
-    'pygamd_adam_step': (c_int, [_P, _P, _P, _P, c_int64, _P, c_int64, c_double, c_double,
-                                 c_double, c_double, c_double, c_double, _P, c_int, _P, _P, _P,
-                                 _P, _P]),
-    'pygamd_edge_key': (c_int, [_P, _P, c_int, c_int64, c_int64, c_int, _P, _P]),
-    'pygamd_run_flags': (c_int, [_P, c_int64, _P, _P]),
-    'pygamd_edge_unkey': (c_int, [_P, _P, _P, c_int64, c_int64, c_int, c_int, _P, _P, _P, _P]),
-    'pygamd_sample_counts': (c_int, [_P, c_int, _P, c_int64, c_int64, c_int, _P, _P, _P]),
-    'pygamd_relabel': (c_int, [c_int, _P, c_int, c_int64, _P, _P, _P, c_int64, _P, _P, _P]),
-    'pygamd_sample_negatives': (c_int, [c_int64, c_int64, c_uint64, _P, _P, _P, _P, c_int64,
-                                        c_int64, c_int, _P, _P]),
-    'pygamd_unique_inverse': (c_int, [_P, _P, c_int, c_int64, _P, _P, c_size_t, _P, _P, _P, _P]),
-    'pygamd_hetero_sample_counts': (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, _P, _P]),
-    'pygamd_hetero_sample_neighbors': (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_uint64,
-                                               c_int, _P, _P, _P, _P, _P]),
-    'pygamd_hetero_split': (c_int, [c_int, _P, c_int, c_int64, _P, _P, _P, c_int, _P, _P, _P,
-                                    c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'pygamd_hetero_spmm': (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int, c_int64, _P, _P]),
-    'pygamd_hetero_spmm_backward': (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, _P,
-                                            c_int, c_int64, _P]),
-    'pygamd_hgt_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_hgt_workspace_bytes': (c_int, [_P, c_int, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_hgt_relation_forward': (c_int, [_P, _P, _P, c_int, _P, _P, c_int64, c_int64, c_int64,
-                                            _P, _P]),
-    'pygamd_hgt_relation_backward': (c_int, [_P, _P, _P, c_int, _P, _P, c_int64, c_int64, c_int64,
-                                             _P, _P, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
-    'pygamd_hetero_sample_temporal_window': (c_int, [_P, _P, c_int, _P, c_int, _P, _P, _P, _P,
-                                                     c_int, c_uint64, c_int, c_int, _P, _P, _P,
-                                                     _P]),
-    'pygamd_hetero_sample_neighbors_temporal': (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P,
-                                                        c_int, c_uint64, c_int, _P, _P, _P, _P,
-                                                        _P]),
-    'pygamd_hetero_link_seeds': (c_int, [_P, _P, c_int, c_int64, c_int64, c_int, _P, _P, _P, _P,
-                                         _P, _P, c_uint64, _P, _P, _P]),
-    'pygamd_gather_rows': (c_int, [_P, c_int64, c_int64, _P, c_int, c_int64, c_int64, _P,
-                                   c_int64, _P, _P]),
-    'pygamd_gather_scatter_add': (c_int, [_P, c_int64, _P, _P, c_int, _P, _P, c_int64, _P,
-                                          c_int64, _P, c_int64, _P]),
-    'pygamd_scatter_init': (c_int, [_P, c_int64, c_int64, c_int64, c_int, _P, _P]),
-    'pygamd_scatter_rows': (c_int, [_P, c_int64, _P, c_int, c_int64, c_int64, _P, c_int64,
-                                    c_int64, c_int, _P, _P, _P]),
-    'pygamd_scatter_finalize': (c_int, [_P, c_int64, c_int64, c_int64, c_int, _P, _P]),
-    'pygamd_scatter_minmax_tie_count': (c_int, [_P, c_int64, _P, c_int, c_int64, c_int64, _P,
-                                                c_int64, c_int64, _P, _P]),
-    'pygamd_scatter_minmax_backward': (c_int, [_P, c_int64, _P, c_int, c_int64, c_int64, _P, _P,
-                                               _P, c_int64, c_int64, _P, c_int64, _P]),
-    'pygamd_scatter_mul_backward_workspace_bytes': (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_scatter_mul_backward': (c_int, [_P, c_int64, _P, c_int, c_int64, c_int64, _P, _P,
-                                            c_int64, c_int64, _P, c_int64, _P, c_size_t, _P]),
-    'pygamd_scatter_argmax': (c_int, [_P, _P, c_int, c_int64, c_int64, _P, _P, _P]),
-    'pygamd_softmax_index_forward': (c_int, [_P, _P, c_int, c_int64, c_int64, c_int64, _P, _P,
-                                             _P, _P]),
-    'pygamd_softmax_index_backward': (c_int, [_P, _P, _P, c_int, c_int64, c_int64, c_int64, _P,
-                                              _P, _P]),
-    'pygamd_segment_softmax_forward': (c_int, [_P, _P, c_int, c_int64, c_int64, _P, _P]),
-    'pygamd_segment_softmax_backward': (c_int, [_P, _P, _P, c_int, c_int64, c_int64, _P, _P]),
-    'pygamd_segment_logsumexp_forward': (c_int, [_P, _P, c_int, c_int64, c_int64, _P, _P]),
-    'pygamd_segment_logsumexp_backward': (c_int, [_P, _P, _P, _P, c_int, c_int64, c_int64, _P,
-                                                  _P]),
-    'pygamd_head_dot_forward': (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, c_int64, _P, _P,
-                                        _P]),
-    'pygamd_head_dot_backward': (c_int, [_P, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_int64,
-                                         _P, c_int64, c_int, _P, _P, _P]),
-    'pygamd_gat_edge_softmax_forward': (c_int, [_P, _P, c_int, _P, _P, c_int64, c_int64,
-                                                c_float, _P, _P]),
-    'pygamd_gat_edge_softmax_backward': (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int64,
-                                                 c_int64, c_float, _P, _P, _P]),
-    'pygamd_gatv2_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_gatv2_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_gatv2_forward': (c_int, [_G, _P, _P, _P, c_int64, c_int64, c_int64, c_float, _P, _P, _P,
-                                     c_size_t, _P]),
-    'pygamd_gatv2_backward_dst': (c_int, [_G, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
-                                          c_float, _P, _P, _P, _P, c_size_t, _P]),
-    'pygamd_gatv2_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
-                                          c_float, _P, _P, c_size_t, _P]),
-    'pygamd_han_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_han_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_han_forward': (c_int, [_G, POINTER(c_int64), POINTER(c_int64), c_int64, _P, _P, _P,
-                                   c_int64, c_int64, c_int64, c_float, c_int, _P, _P, _P, c_size_t,
-                                   _P]),
-    'pygamd_han_backward_dst': (c_int, [_G, POINTER(c_int64), POINTER(c_int64), c_int64, _P, _P, _P,
-                                        _P, _P, _P, c_int64, c_int64, c_int64, c_float, c_int, _P,
-                                        _P, _P, c_size_t, _P]),
-    'pygamd_han_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int,
-                                        _P, _P, _P, c_size_t, _P]),
-    'pygamd_transformer_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_transformer_workspace_bytes': (c_int, [c_int64, c_int64, c_int64,
-                                                   POINTER(c_size_t)]),
-    'pygamd_transformer_forward': (c_int, [_G, _P, _P, _P, c_int64, c_int64, c_int64, c_int64,
-                                           c_float, _P, _P, _P, c_size_t, _P]),
-    'pygamd_transformer_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, _P, _P, _P, c_int64,
-                                                c_int64, c_int64, c_float, _P, _P, _P, c_size_t,
-                                                _P]),
-    'pygamd_transformer_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
-                                                c_float, _P, _P, c_int64, _P, c_size_t, _P]),
-    'pygamd_transformer_edge_supported': (c_int, [c_int64, c_int64, c_int64]),
-    'pygamd_transformer_edge_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, c_int64,
-                                                        POINTER(c_size_t)]),
-    'pygamd_transformer_edge_forward': (c_int, [_G, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64,
-                                                c_int64, c_int64, c_float, _P, _P, _P, _P, c_size_t,
-                                                _P]),
-    'pygamd_transformer_edge_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, _P, _P, _P, _P, _P,
-                                                     _P, _P, c_int64, c_int64, c_int64, c_int64,
-                                                     c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
-    'pygamd_gine_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_gine_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_gine_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int64,
-                                    c_int64, c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_gine_backward': (c_int, [_G, _P, _P, c_int64, _P, _P, _P, _P, c_int64, c_int64, c_int64,
-                                     _P, _P, _P, _P, _P, c_size_t, _P]),
-    'pygamd_pna_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_pna_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_pna_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, c_int64,
-                                   c_int64, c_int, _P, _P, _P, c_size_t, _P]),
-    'pygamd_pna_backward': (c_int, [_G, _P, _P, c_int64, _P, _P, _P, c_int64, c_int64, c_int64,
-                                    c_int, _P, _P, _P, _P, c_size_t, _P]),
-    'pygamd_gen_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_gen_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_gen_forward': (c_int, [_G, _P, _P, c_int64, c_int, _P, _P, _P, _P, c_int64, c_float,
-                                   c_int64, c_int64, c_int64, c_int, _P, _P, _P, c_size_t, _P]),
-    'pygamd_gen_backward': (c_int, [_G, _P, _P, c_int64, c_int, _P, _P, _P, _P, c_int64, c_float,
-                                    c_int, _P, c_int64, c_int64, c_int64, c_int, _P, _P, _P, _P,
-                                    _P, c_size_t, _P]),
-    'pygamd_resgated_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_resgated_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_resgated_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, c_int64,
-                                        c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_resgated_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64,
-                                             c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t,
-                                             _P]),
-    'pygamd_resgated_backward_src': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_int64,
-                                             c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_cg_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_cg_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, c_int, _P, _P, _P, c_int64,
-                                  c_int, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_cg_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, c_int64, c_int, _P, _P, _P,
-                                       c_int64, c_int, c_int64, c_int64, c_int64, _P, c_int64, _P,
-                                       _P, _P, c_size_t, _P]),
-    'pygamd_cg_backward_src': (c_int, [_G, _P, _P, c_int64, _P, c_int64, c_int, _P, _P, _P,
-                                       c_int64, c_int, _P, c_int64, c_int64, c_int64, _P, c_int64,
-                                       _P, c_size_t, _P]),
-    'pygamd_film_supported': (c_int, [c_int64]),
-    'pygamd_film_forward': (c_int, [_G, _P, _P, _P, c_int64, _P, c_int64, _P, _P, c_int64, c_int,
-                                    c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
-    'pygamd_film_backward_dst': (c_int, [_G, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, c_int,
-                                         c_int, c_int64, c_int64, c_int64, _P, c_int64, _P,
-                                         c_size_t, _P]),
-    'pygamd_film_backward_src': (c_int, [_G, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P,
-                                         c_int64, c_int, c_int64, c_int64, c_int64, _P, c_int64,
-                                         _P, c_size_t, _P]),
-    'pygamd_rgat_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_rgat_forward': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P,
-                                    c_int64, c_int64, c_int64, c_int64, c_float, _P, _P, _P,
-                                    c_size_t, _P]),
-    'pygamd_rgat_backward_dst': (c_int, [_G, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P,
-                                         _P, _P, c_int64, c_int64, c_int64, c_int64, c_float,
-                                         c_int, _P, _P]),
-    'pygamd_rgat_pair_scalar': (c_int, [_G, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P,
-                                        c_int64, c_int64, c_int64, c_float, _P, _P, _P, c_int64,
-                                        _P]),
-    'pygamd_rgat_backward_src': (c_int, [_G, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64,
-                                         c_int64, _P, c_int64, _P, c_int64, _P, c_size_t, _P]),
-    'pygamd_mixture_supported': (c_int, [c_int64, c_int64]),
-    'pygamd_mixture_workspace_bytes': (c_int, [c_int64, c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_mixture_expand': (c_int, [_G, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, _P, _P,
-                                      c_size_t, _P]),
-    'pygamd_mixture_coef_grad': (c_int, [_G, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P,
-                                         _P]),
-    'pygamd_graph_norm_supported': (c_int, [c_int64]),
-    'pygamd_graph_norm_forward': (c_int, [_G, c_int, _P, c_int64, c_int64, c_int64, _P, _P, _P,
-                                          c_float, c_int, _P, c_int64, _P, _P, _P, c_size_t, _P]),
-    'pygamd_graph_norm_backward': (c_int, [_G, c_int, _P, c_int64, _P, c_int64, c_int64, c_int64,
-                                           _P, _P, c_float, c_int, _P, _P, _P, c_int64, _P, _P,
-                                           _P, _P, c_size_t, _P]),
-    'pygamd_hop_workspace_size': (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
-    'pygamd_hop': (c_int, [_G, _P, POINTER(HopArgs), _P, c_size_t, _P]),
-    'pygamd_knn': (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int,
-                           c_int64, c_int, c_int, c_int, _P, _P, _P]),
-    'pygamd_radius': (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, _P, _P, c_int,
-                              c_int64, c_float, c_int64, c_int, _P, _P, _P]),
-    'pygamd_fps_workspace_size': (c_int, [c_int64, POINTER(c_size_t)]),
-    'pygamd_fps': (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, c_int, c_int64, c_int64,
-                           _P, _P, c_size_t, _P]),
-}
+MIRRORS = {'pygamd_spmm_args': SpmmArgs, 'pygamd_csr': Csr, 'pygamd_hop_args': HopArgs,
+           'pygamd_sage_fused_args': SageFusedArgs}
 
+# name -> (restype, argtypes) of every PYGAMD_API symbol of include/pyg_amd.h, and of
 # include/pyg_amd_lab.h: schedules measured and not adopted + timing probes (NOT the boundary;
 # exported by libpyg_amd_lab.so only)
-LAB_SIGNATURES = {
-    'pygamd_lab_sage_layer_fused': (c_int, [POINTER(SpmmArgs), POINTER(SageFusedArgs), c_int,
-                                            c_int, _P, c_size_t, _P]),
-    'pygamd_lab_set_wgrad_variant': (c_int, [c_int]),
-    'pygamd_lab_copy': (c_int, [_P, _P, c_int64, c_int, c_int, _P]),
-}
+SIGNATURES = _header.signatures(_H, MIRRORS)
+LAB_SIGNATURES = _header.signatures(_LAB, MIRRORS)
 
 _lib = None       # libpyg_amd.so: the product library (include/pyg_amd.h, nothing else)
 _lab = None       # libpyg_amd_lab.so: the same sources + the laboratory entry points
@@ -382,9 +75,6 @@ _use_lab = False  # route load() to the laboratory build (tests / scripts that s
 
 def lib_path():
     return _build.LIB_PATH
-
-
-GEMM_MODES = {'fp32': 0, 'split': 1}  # PYGAMD_GEMM_FP32 / PYGAMD_GEMM_SPLIT_BF16
 
 
 def _open(path, signatures):
@@ -475,5 +165,5 @@ def check(rc, what=''):
     if rc != 0:
         lib = load()
         msg = lib.pygamd_status_string(rc).decode()
-        extra = f' (hipError {lib.pygamd_last_hip_error()})' if rc == 4 else ''
+        extra = f' (hipError {lib.pygamd_last_hip_error()})' if rc == ERR_HIP else ''
         raise PygAmdError(f'{what or "pygamd call"} failed: {msg}{extra}')

@@ -750,7 +750,7 @@ def spmm_minmax_backward_src(fwd, bwd, slot_map: Tensor, x: Tensor, out: Tensor,
         _p(fwd.ptr), _p(fwd.idx), _p(bwd.ptr), _p(bwd.idx), _p(slot_map), _idx_dtype(fwd.ptr),
         _p(a32), _p(x2), _ld(x2), _p(o2), _ld(o2), _p(g2), _ld(g2), fwd.ptr.numel() - 1, n_src,
         nnz, F, int(count_self), _p(ws), nbytes, _p(grad_x), _ld(grad_x), _stream(x))
-    if rc == 2:  # PYGAMD_ERR_UNSUPPORTED
+    if rc == _lib.ERR_UNSUPPORTED:
         return None
     check(rc, 'spmm_minmax_backward_src')
     return grad_x
@@ -1929,7 +1929,8 @@ def pna_backward(rowptr_t: Tensor, col_t: Tensor, edge_id_t: Optional[Tensor], p
 
 
 # ---- GENConv's softmax aggregation (csrc/gen.hip) --------------------------------------------------
-GEN_EDGE_NONE, GEN_EDGE_WIDE, GEN_EDGE_LINEAR = 0, 1, 2
+GEN_EDGE_NONE, GEN_EDGE_WIDE, GEN_EDGE_LINEAR = (_lib.CONSTANTS['PYGAMD_GEN_EDGE_' + m]
+                                                 for m in ('NONE', 'WIDE', 'LINEAR'))
 
 
 def gen_supported(F: int, De: int = 0) -> bool:
@@ -2785,8 +2786,9 @@ def mixture_coef_grad(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], wi
 # chunks of GRAPH_NORM_CHUNK nodes, one wave each (profiles/graph_norm.md).
 GRAPH_NORM_THRESHOLD = 256
 GRAPH_NORM_CHUNK = 128
-GRAPH_NORM_BLOCKS = 1024   # PYGAMD_GRAPH_NORM_BLOCKS of include/pyg_amd.h
-NORM_MODES = {'channel': 0, 'graph': 1}
+GRAPH_NORM_BLOCKS = _lib.CONSTANTS['PYGAMD_GRAPH_NORM_BLOCKS']
+NORM_MODES = {'channel': _lib.CONSTANTS['PYGAMD_NORM_CHANNEL'],
+              'graph': _lib.CONSTANTS['PYGAMD_NORM_GRAPH']}
 
 
 def graph_norm_supported(F: int) -> bool:
@@ -3816,7 +3818,10 @@ def _i64_host(values):
     return arr
 
 
-LINK_NEG_MODES = {None: 0, 'none': 0, 'binary': 1, 'triplet': 2}
+LINK_NEG_MODES = {None: _lib.CONSTANTS['PYGAMD_LINK_NEG_NONE'],
+                  'none': _lib.CONSTANTS['PYGAMD_LINK_NEG_NONE'],
+                  'binary': _lib.CONSTANTS['PYGAMD_LINK_NEG_BINARY'],
+                  'triplet': _lib.CONSTANTS['PYGAMD_LINK_NEG_TRIPLET']}
 
 
 def hetero_link_seeds(src: Tensor, dst: Tensor, num_neg: int, mode, seed: int, endpoints,

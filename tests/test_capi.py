@@ -215,47 +215,50 @@ def test_torch_binding_builds_loads_and_declares_its_operators():
                                  False) is None
 
 
+def _headers():
+    from pytorch_geometric_amd import _header
+    main, lab = (open(os.path.join(ROOT, 'include', h)).read()
+                 for h in ('pyg_amd.h', 'pyg_amd_lab.h'))
+    main = _header.parse(main)
+    return main, _header.parse(lab, included=main)
+
+
 def test_struct_mirrors_match_the_header_field_for_field(tmp_path):
-    """`_lib.SpmmArgs` / `_lib.SageFusedArgs` / `_lib.Csr` are hand-written mirrors of the argument
-    structs of include/pyg_amd.h.  Compile the header with gcc and compare size and every field offset: a field
-    added on one side only would silently shift everything behind it."""
+    """`_lib.SpmmArgs` / `_lib.SageFusedArgs` / `_lib.Csr` / `_lib.HopArgs` mirror the argument
+    structs of include/pyg_amd.h.  Compile the header with gcc and compare size and every field
+    offset, for every struct the header reader finds: a field lost or mistyped on the way would
+    silently shift everything behind it."""
     import ctypes
-    import re
     import subprocess
     from pytorch_geometric_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, 'include', 'pyg_amd.h')).read()
-
-    def c_fields(struct_body):
-        body = re.sub(r'/\*.*?\*/', '', struct_body, flags=re.S)
-        names = []
-        for decl in body.split(';'):
-            decl = decl.strip()
-            if decl:
-                names.append(re.split(r'[\s\*]+', decl)[-1])
-        return names
-
-    m1 = re.search(r'typedef struct \{(.*?)\} pygamd_spmm_args;', header, flags=re.S)
-    m2 = re.search(r'typedef struct pygamd_sage_fused_args \{(.*?)\} pygamd_sage_fused_args;',
-                   header, flags=re.S)
-    m3 = re.search(r'typedef struct pygamd_csr \{(.*?)\} pygamd_csr;', header, flags=re.S)
-    assert m1 and m2 and m3
-    structs = {'pygamd_spmm_args': (c_fields(m1.group(1)), _lib.SpmmArgs),
-               'pygamd_sage_fused_args': (c_fields(m2.group(1)), _lib.SageFusedArgs),
-               'pygamd_csr': (c_fields(m3.group(1)), _lib.Csr)}
+    main, _ = _headers()
+    assert sorted(main.structs) == sorted(_lib.MIRRORS) == [
+        'pygamd_csr', 'pygamd_hop_args', 'pygamd_sage_fused_args', 'pygamd_spmm_args']
+    structs = {name: ([f for f, _, _ in body], _lib.MIRRORS[name])
+               for name, body in main.structs.items()}
+    assert _lib.MIRRORS == {
+        'pygamd_spmm_args': _lib.SpmmArgs, 'pygamd_csr': _lib.Csr,
+        'pygamd_hop_args': _lib.HopArgs, 'pygamd_sage_fused_args': _lib.SageFusedArgs}
     assert structs['pygamd_csr'][0] == ['rowptr', 'col', 'idx_dtype', 'reserved0', 'n_rows',
                                         'hub_rows', 'hub_chunk_ptr', 'n_hub', 'n_chunks',
                                         'hub_threshold', 'hub_chunk']
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "pyg_amd.h"', 'int main(void) {']
+    assert main.structs['pygamd_hop_args'][-1] == ('reserved', 'int64_t', 4)
+    assert _lib.HopArgs._fields_[-1] == ('reserved', ctypes.c_int64 * 4)
+    assert {name: len(fields) for name, (fields, _) in structs.items()} == {
+        'pygamd_csr': 11, 'pygamd_spmm_args': 36, 'pygamd_hop_args': 19,
+        'pygamd_sage_fused_args': 19}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "pyg_amd.h"',
+             'int main(void) {']
     for name, (fields, _) in structs.items():
         lines.append(f'  printf("{name} %zu\\n", sizeof({name}));')
         for f in fields:
             lines.append(f'  printf("{name}.{f} %zu\\n", offsetof({name}, {f}));')
+            lines.append(f'  printf("{name}.{f}.size %zu\\n", sizeof((({name}*)0)->{f}));')
     lines += ['  return 0;', '}']
     src = tmp_path / 'layout.c'
     src.write_text('\n'.join(lines))
     exe = tmp_path / 'layout'
-    subprocess.run(['gcc', '-I', os.path.join(root, 'include'), str(src), '-o', str(exe)],
+    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)],
                    check=True)
     got = dict(line.rsplit(' ', 1) for line in
                subprocess.run([str(exe)], check=True, capture_output=True,
@@ -265,3 +268,160 @@ def test_struct_mirrors_match_the_header_field_for_field(tmp_path):
         assert int(got[name]) == ctypes.sizeof(mirror), f'{name}: size'
         for f in fields:
             assert int(got[f'{name}.{f}']) == getattr(mirror, f).offset, f'{name}.{f}: offset'
+            assert int(got[f'{name}.{f}.size']) == getattr(mirror, f).size, f'{name}.{f}: size'
+
+
+def test_reader_prototypes_agree_with_the_compiler(tmp_path):
+    """Every prototype the header reader returns, from both headers, is handed back to gcc next to
+    the header it came from: gcc — not the reader — decides whether the split into parameters and
+    the spelling of each type are those of the declaration."""
+    main, lab = _headers()
+    assert len(main.functions) == len(declared_symbols()) and len(lab.functions) == 3
+    lines = ['#include "pyg_amd_lab.h"']
+    for functions in (main.functions, lab.functions):
+        for name, (ret, params) in functions.items():
+            lines.append(f'_Static_assert(__builtin_types_compatible_p(__typeof__({name}), '
+                         f'{ret} ({", ".join(params) or "void"})), "{name}");')
+    src = tmp_path / 'prototypes.c'
+    src.write_text('\n'.join(lines) + '\n')
+    done = subprocess.run(['gcc', '-fsyntax-only', '-I', os.path.join(ROOT, 'include'), str(src)],
+                          capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr[-2000:]
+
+
+def test_type_map_known_answers():
+    """Literal (restype, argtypes) of entries that between them use every row of the C type ->
+    ctypes map: `const char*`, a `size_t` result, a run of doubles, `const int64_t*`, a float in
+    mid-list, `uint64_t`, two struct pointers, `float* const*`."""
+    from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64,
+                        c_void_p)
+    from pytorch_geometric_amd import _lib
+    P, I, L, G = c_void_p, c_int, c_int64, POINTER(_lib.Csr)
+    S = _lib.SIGNATURES
+    assert S['pygamd_status_string'] == (c_char_p, [I])
+    assert S['pygamd_build_arch'] == (c_char_p, [])
+    assert S['pygamd_minmax_backward_src_workspace_bytes'] == (c_size_t, [L, L, L])
+    assert S['pygamd_adam_step'] == (I, [P, P, P, P, L, P, L] + [c_double] * 6 +
+                                     [P, I, P, P, P, P, P])
+    assert S['pygamd_gen_forward'] == (I, [G, P, P, L, I, P, P, P, P, L, c_float, L, L, L, I, P, P,
+                                           P, c_size_t, P])
+    assert S['pygamd_sample_neighbors'] == (I, [P, P, I, P, L, P, L, c_uint64, I, P, P, P, P, P])
+    assert S['pygamd_hop'] == (I, [G, P, POINTER(_lib.HopArgs), P, c_size_t, P])
+    assert S['pygamd_hetero_spmm_backward'] == (I, [P, P, P, I, P, P, P, I, P, P, P, I, L, P])
+    assert S['pygamd_hub_plan_workspace_bytes'] == (I, [I, L, P])
+    assert _lib.LAB_SIGNATURES['pygamd_lab_sage_layer_fused'] == (
+        I, [POINTER(_lib.SpmmArgs), POINTER(_lib.SageFusedArgs), I, I, P, c_size_t, P])
+    main, _ = _headers()
+    assert main.functions['pygamd_hetero_spmm_backward'][1][5] == 'const float* const*'
+    assert main.functions['pygamd_hetero_spmm_backward'][1][9] == 'float* const*'
+    assert main.functions['pygamd_adam_step'][1][5] == 'const int64_t*'
+    assert main.functions['pygamd_hop'] == ('int', ['const pygamd_csr*', 'const void*',
+                                                    'const pygamd_hop_args*', 'void*', 'size_t',
+                                                    'void*'])
+
+
+SYNTHETIC_HEADER = '''
+/* a comment with , ; ( and PYGAMD_API int not_a_function(int x); inside */
+#ifndef T_H
+#define T_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PYGAMD_API __attribute__((visibility("default")))
+#define PYGAMD_T_VERSION 7 /* trailing, comment; ( */
+#define PYGAMD_T_MASK 0x10 // PYGAMD_API int also_not(int y);
+typedef enum { PYGAMD_T_A = 0, PYGAMD_T_B = 1 } pygamd_t_one;
+typedef enum {
+  PYGAMD_T_C = 2,   /* why, exactly; */
+  PYGAMD_T_D = -3
+} pygamd_t_two;
+typedef struct pygamd_t_args {
+  const float* x;      /* [n, ldx] */
+  int64_t ldx;
+  uint32_t *bits;
+  float a;
+  int64_t reserved[4]; /* 0 */
+} pygamd_t_args;
+PYGAMD_API int pygamd_t_version(void);
+PYGAMD_API const char* pygamd_t_name(int which);
+// PYGAMD_API int commented_out(int z);
+PYGAMD_API int pygamd_t_run(const pygamd_t_args* a, float *const *planes,
+                            const int64_t* sizes /*[host]*/, uint64_t seed, double lr,
+                            size_t* bytes,
+                            void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+'''
+
+
+def test_header_reader_on_synthetic_text():
+    from pytorch_geometric_amd import _header
+    from pytorch_geometric_amd._lib import PygAmdError
+    h = _header.parse(SYNTHETIC_HEADER)
+    assert h.functions == {
+        'pygamd_t_version': ('int', []),
+        'pygamd_t_name': ('const char*', ['int']),
+        'pygamd_t_run': ('int', ['const pygamd_t_args*', 'float* const*', 'const int64_t*',
+                                 'uint64_t', 'double', 'size_t*', 'void*'])}
+    assert h.structs == {'pygamd_t_args': [('x', 'const float*', None), ('ldx', 'int64_t', None),
+                                           ('bits', 'uint32_t*', None), ('a', 'float', None),
+                                           ('reserved', 'int64_t', 4)]}
+    assert h.constants == {'PYGAMD_T_VERSION': 7, 'PYGAMD_T_MASK': 16, 'PYGAMD_T_A': 0,
+                           'PYGAMD_T_B': 1, 'PYGAMD_T_C': 2, 'PYGAMD_T_D': -3}
+
+    def refused(text, *names):
+        with pytest.raises(PygAmdError) as e:
+            _header.parse(text)
+        for name in names:
+            assert name in str(e.value), str(e.value)
+
+    refused('PYGAMD_API int pygamd_t_f(int a, unsigned b);', 'pygamd_t_f', 'unsigned')
+    refused('PYGAMD_API long pygamd_t_g(int a);', 'pygamd_t_g', 'long')
+    refused('PYGAMD_API int pygamd_t_h(const char* s);', 'pygamd_t_h', 'const char*')
+    refused('PYGAMD_API int pygamd_t_i(const pygamd_t_nowhere* s);', 'pygamd_t_i',
+            'pygamd_t_nowhere')
+    refused('PYGAMD_API int pygamd_t_j(int);', 'pygamd_t_j')
+    refused('typedef struct { int a; short b; } pygamd_t_s;', 'pygamd_t_s', 'short')
+    refused('typedef enum { PYGAMD_T_E = 0, PYGAMD_T_F } pygamd_t_three;', 'PYGAMD_T_F')
+    refused('#define PYGAMD_T_SHIFT (1 << 3)', 'PYGAMD_T_SHIFT')
+    refused('PYGAMD_API int pygamd_t_k(void (*done)(int), int a);', 'pygamd_t_k')
+    refused('PYGAMD_API int pygamd_t_l(int a)\nPYGAMD_API int pygamd_t_m(void);', 'pygamd_t_l')
+    refused('int pygamd_t_n(int a);', 'pygamd_t_n')
+    # a struct pointer needs the struct: from this header or from the one it includes
+    lab = 'PYGAMD_API int pygamd_t_lab(const pygamd_t_args* a);'
+    refused(lab, 'pygamd_t_lab', 'pygamd_t_args')
+    assert _header.parse(lab, included=h).functions == {
+        'pygamd_t_lab': ('int', ['const pygamd_t_args*'])}
+    with pytest.raises(PygAmdError, match='pygamd_t_args'):
+        _header.signatures(h, {})
+
+
+def test_constants_keep_their_values():
+    """The Python constants take their values from the header; these are the values they had as
+    literals.  A renamed or renumbered header constant fails here (or at import) instead of
+    shifting a value."""
+    from pytorch_geometric_amd import _lib, _native
+    assert _lib.ABI_VERSION == 11
+    assert (_lib.X_DENSE, _lib.X_COMPRESSED, _lib.AGG_GIVEN) == (0, 1, 2)
+    assert (_lib.IDX_I32, _lib.IDX_I64) == (0, 1)
+    assert (_lib.SUM, _lib.MEAN, _lib.MIN, _lib.MAX, _lib.MUL, _lib.ANY) == (0, 1, 2, 3, 4, 5)
+    assert _lib.REDUCE_IDS == {'sum': 0, 'add': 0, 'mean': 1, 'min': 2, 'amin': 2, 'max': 3,
+                               'amax': 3, 'mul': 4, 'any': 5}
+    assert _lib.GEMM_MODES == {'fp32': 0, 'split': 1}
+    assert (_lib.ERR_UNSUPPORTED, _lib.ERR_HIP) == (2, 4)
+    assert (_native.GEN_EDGE_NONE, _native.GEN_EDGE_WIDE, _native.GEN_EDGE_LINEAR) == (0, 1, 2)
+    assert _native.GRAPH_NORM_BLOCKS == 1024
+    assert _native.NORM_MODES == {'channel': 0, 'graph': 1}
+    assert _native.LINK_NEG_MODES == {None: 0, 'none': 0, 'binary': 1, 'triplet': 2}
+    assert _native.AGG_GIVEN == 2
+    assert _lib.CONSTANTS['PYGAMD_ADAM_MAX_SEGMENTS'] == 8
+
+
+def test_missing_header_is_an_error_with_its_path(monkeypatch, tmp_path):
+    from pytorch_geometric_amd import _build, _lib
+    monkeypatch.setattr(_build, 'PKG_DIR', str(tmp_path / 'pkg'))
+    with pytest.raises(_lib.PygAmdError, match=os.path.join(str(tmp_path), 'include', 'pyg_amd.h')):
+        _lib._read('pyg_amd.h')
