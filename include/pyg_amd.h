@@ -2113,6 +2113,76 @@ PYGAMD_API int pygamd_fps(const float* x, int64_t ldx, int64_t N, int64_t F, con
                           int64_t total, int64_t* out, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- hierarchical pooling: top-k select, gather-scale, edge filter — csrc/pool.hip ----------------
+ * The three steps TopKPooling and SAGPooling run after every conv block.  float32 values, int64
+ * node ids, 64-bit row offsets at each plane's own pitch, no float atomics: every output element
+ * has exactly one writer and every result is a function of the inputs only.
+ *
+ * pygamd_topk_select: the reference's topk(x, ratio, batch) (nn/pool/select/topk.py:28-45: a global
+ *   sort of the scores, a stable sort of the gathered batch vector, four [N] temporaries and a
+ *   mask) in ONE launch that never leaves the graph.  Graph g owns the nodes [ptr[g], ptr[g + 1])
+ *   (pygamd_index2ptr of a non-decreasing batch vector; int32 / int64 by idx_dtype) and the output
+ *   slots [out_ptr[g], out_ptr[g + 1]), out_ptr [B + 1] (int64) the exclusive prefix of
+ *   min(k[g], n_g), M = out_ptr[B].  perm [M] (int64) receives the graph's nodes ordered by
+ *   SCORE DESCENDING, THEN NODE INDEX ASCENDING, the first min(k[g], n_g) of them; weight [M] =
+ *   score[perm] (may be NULL).  Any NaN ranks above every number (torch.sort(descending=True)
+ *   does the same); -0.0 and +0.0 are equal.  A score maps to a monotone uint32 with -0 and NaN
+ *   canonicalised and pairs with the local index into a unique 64-bit key; node i goes to slot
+ *   out_ptr[g] + #{j : key_j > key_i} when that rank is below its graph's count.  Ranks are a
+ *   permutation, so every slot has one writer.  A graph of at most PYGAMD_TOPK_WAVE_NODES nodes is
+ *   one wave's (keys in registers, PYGAMD_TOPK_GROUP graphs per workgroup); a longer one is its
+ *   workgroup's (keys in LDS, rank by counting), up to PYGAMD_TOPK_MAX_NODES nodes.  max_nodes is
+ *   the caller's bound on the largest graph: above the envelope -> status 2 before any launch (the
+ *   caller takes its generic route for the whole batch); a graph that is larger than the envelope
+ *   all the same (a max_nodes below the true maximum) is skipped by the kernel: its slots of perm
+ *   and weight are LEFT UNWRITTEN although the call returns 0, so max_nodes must be the true
+ *   bound.  Pointer values are clamped to [0, N] and [0, M].
+ * pygamd_gather_scale_forward: out[i, :] = multiplier * (score[perm[i]] * x[perm[i], :]), the two
+ *   products in that order — bit for bit x[perm] * score.view(-1, 1) followed by multiplier * x
+ *   (nn/pool/topk_pool.py:121-122, sag_pool.py:135-136: two or three [M, F] passes); weight [M] =
+ *   score[perm] (may be NULL).  perm [M] int64 without duplicates; a perm[i] outside [0, N) yields
+ *   a zero row.  Any F >= 1 (a column loop; several rows per wave for F < 64).
+ * pygamd_gather_scale_backward: the reference's index_put + broadcast multiply + row sum:
+ *   grad_x[perm[i], :] = multiplier * weight[i] * grad_out[i, :] with weight[i] = score[perm[i]],
+ *   grad_score[perm[i]] = multiplier * dot(grad_out[i], x[perm[i]]) + grad_weight[i] (grad_weight
+ *   may be NULL: 0).  Only the rows in perm are written: the caller zero-fills grad_x and
+ *   grad_score, and the rows outside perm stay exactly zero.  Either output may be NULL.
+ * pygamd_filter_edges: the reference's filter_adj (nn/pool/connect/filter_edges.py:25-36: four [E]
+ *   gathers, a mask and three boolean-mask compactions, each with its own scan and host read).
+ *   row / col are the two rows of edge_index (int32 / int64 by idx_dtype), element e of each at
+ *   e * its stride (in elements: a transposed [E, 2] tensor or a column slice is read in place);
+ *   node_map [N] (int64) holds a node's new id or -1.  An edge survives when both endpoints map to
+ *   a non-negative id (an endpoint outside [0, N) counts as dropped).  out_row / out_col [E]
+ *   (int64) receive the relabelled endpoints of the survivors IN THE ORIGINAL EDGE ORDER, kept [E]
+ *   (int64) their edge ids; total [1] (int64, device) their number.  Three launches over chunks of
+ *   4,096 edges: the chunks' counts, one workgroup's scan of them, the write (ballot + prefix
+ *   popcount inside a wave).  Workspace: pygamd_filter_edges_workspace_size(E).
+ * Before any device work: an unknown idx_dtype, a negative size, F < 1, a pitch below F, a stride
+ * below 1 or a NULL pointer with a non-empty size -> status 1; a short workspace -> status 3.
+ * Empty inputs (M == 0, E == 0) return 0 without a launch (total is then not written: the caller
+ * knows the count).                                                                               */
+#define PYGAMD_TOPK_WAVE_NODES 64
+#define PYGAMD_TOPK_MAX_NODES 1024
+#define PYGAMD_TOPK_GROUP 4
+PYGAMD_API int pygamd_topk_select(const float* score, int64_t N, const void* ptr, int idx_dtype,
+                                  int64_t B, const int64_t* k, const int64_t* out_ptr, int64_t M,
+                                  int64_t max_nodes, int64_t* perm, float* weight, void* stream);
+PYGAMD_API int pygamd_gather_scale_forward(const float* x, int64_t ldx, int64_t N, int64_t F,
+                                           const float* score, const int64_t* perm, int64_t M,
+                                           float multiplier, float* out, int64_t ldo,
+                                           float* weight, void* stream);
+PYGAMD_API int pygamd_gather_scale_backward(const float* x, int64_t ldx, int64_t N, int64_t F,
+                                            const float* score, const int64_t* perm, int64_t M,
+                                            float multiplier, const float* grad_out, int64_t ldg,
+                                            const float* grad_weight, float* grad_x, int64_t ldgx,
+                                            float* grad_score, void* stream);
+PYGAMD_API int pygamd_filter_edges_workspace_size(int64_t E, size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_filter_edges(const void* row, int64_t row_stride, const void* col,
+                                   int64_t col_stride, int idx_dtype, int64_t E,
+                                   const int64_t* node_map, int64_t N, int64_t* out_row,
+                                   int64_t* out_col, int64_t* kept, int64_t* total,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,8 @@ SOURCES = ['capi.hip', 'graph.hip', 'spmm.hip', 'scatter.hip', 'softmax.hip', 's
            'sample.hip', 'minibatch.hip', 'train.hip', 'gemm.hip', 'sage_fused.hip',
            'hetero_conv.hip', 'gatv2.hip', 'transformer.hip', 'hgt.hip', 'gine.hip',
            'pna.hip', 'gen.hip', 'resgated.hip', 'han.hip', 'mixture.hip', 'cg.hip',
-           'film.hip', 'rgat.hip', 'graph_norm.hip', 'hop.hip', 'cluster.hip']
+           'film.hip', 'rgat.hip', 'graph_norm.hip', 'hop.hip', 'cluster.hip',
+           'pool.hip']
 LAB_SOURCES = SOURCES + ['sage_fused_lab.hip']
 LAB_FLAGS = {'gemm.hip': ['-DPYGAMD_LAB=1']}   # the weight-gradient variants and probes
 ARCH = 'gfx950'

@@ -1452,6 +1452,34 @@ class GraphNormFunction(Function):
         return g_x if need[0] else None, g_w, g_b, g_ms, None, None, None, None
 
 
+class GatherScaleFunction(Function):
+    """``(multiplier * (x[perm] * score[perm].view(-1, 1)), score[perm])`` of the pooling layers
+    (topk_pool.py:118-122, sag_pool.py:132-136), csrc/pool.hip: one launch forward and — after the
+    one memset of the two gradients' shared buffer — one backward, where the reference has two or
+    three ``[M, F]`` passes and an ``index_put``, a broadcast multiply and a row sum.  ``perm``
+    holds no node twice.  Saved: ``x``, ``score`` and ``perm`` — nothing of size ``M x F``."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, score: Tensor, perm: Tensor, multiplier: float):
+        out, weight = _native.gather_scale_forward(x, score, perm, multiplier)
+        ctx.save_for_backward(x, score, perm)
+        ctx.multiplier = float(multiplier)
+        return out, weight
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor, grad_weight: Optional[Tensor]):
+        """When both gradients are wanted they are views of ONE zero-filled buffer (one memset):
+        ``grad_x`` keeps the storage of the ``[N]`` score gradient alive and the reverse."""
+        x, score, perm = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not (need[0] or need[1]):
+            return None, None, None, None
+        g_x, g_s = _native.gather_scale_backward(x, score, perm, ctx.multiplier, grad_out,
+                                                 grad_weight, want_x=need[0], want_score=need[1])
+        return g_x, g_s, None, None
+
+
 def _check_hop(graph: EdgeIndex, x: Tensor, w: Optional[Tensor], square: bool = False):
     if x.size(0) != graph.num_src_nodes:
         raise ValueError(f"'x' has {x.size(0)} rows but the graph has {graph.num_src_nodes} "

@@ -4381,3 +4381,131 @@ def fps(x: Tensor, ptr: Tensor, out_ptr: Tensor, start: Tensor, total: int) -> T
                              _idx_dtype(ptr), B, int(total), _p(out), _p(ws), ws_bytes,
                              _stream(x)), 'fps')
     return out
+
+
+# ---- hierarchical pooling (csrc/pool.hip) --------------------------------------------------------
+# the select kernel's size thresholds: a graph up to TOPK_WAVE_NODES nodes is one wave's, a longer
+# one its workgroup's up to TOPK_MAX_NODES; a batch with a longer graph takes the generic route
+TOPK_WAVE_NODES = _lib.CONSTANTS['PYGAMD_TOPK_WAVE_NODES']
+TOPK_MAX_NODES = _lib.CONSTANTS['PYGAMD_TOPK_MAX_NODES']
+TOPK_GROUP = _lib.CONSTANTS['PYGAMD_TOPK_GROUP']
+
+
+def _i64_vector(t: Tensor, name: str, n: int) -> Tensor:
+    if t.dtype != torch.int64 or t.dim() != 1 or t.numel() != n:
+        raise ValueError(f"'{name}' must be an int64 vector of {n} entries (got {t.dtype} "
+                         f"{tuple(t.shape)})")
+    return t.contiguous()
+
+
+def _f32_vector(t: Tensor, name: str, n: int) -> Tensor:
+    if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n:
+        raise ValueError(f"'{name}' must be a float32 vector of {n} entries (got {t.dtype} "
+                         f"{tuple(t.shape)})")
+    return t.contiguous()
+
+
+def topk_select(score: Tensor, ptr: Tensor, k: Tensor, out_ptr: Tensor, total: int,
+                max_nodes: int, want_weight: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """``pygamd_topk_select``: ``(perm [total] int64, weight [total] = score[perm])`` (``weight``
+    None unless ``want_weight``) — of every
+    graph ``g`` (nodes ``ptr[g] .. ptr[g + 1]``) the first ``min(k[g], n_g)`` nodes by score
+    descending, then node index ascending (NaN above every number, ``-0.0 == +0.0``), at the slots
+    ``out_ptr[g] ..``.  ``max_nodes``: the largest graph, at most ``TOPK_MAX_NODES``."""
+    _require_device(score, ptr, k, out_ptr)
+    B = ptr.numel() - 1
+    if B < 0 or ptr.dim() != 1:
+        raise ValueError("'ptr' needs B + 1 entries")
+    score = _f32_vector(score, 'score', score.numel())
+    ptr = ptr.contiguous()
+    k, out_ptr = _i64_vector(k, 'k', B), _i64_vector(out_ptr, 'out_ptr', B + 1)
+    N, M = score.numel(), int(total)
+    perm = torch.empty(M, dtype=torch.int64, device=score.device)
+    weight = torch.empty(M, dtype=torch.float32, device=score.device) if want_weight else None
+    with _timed({'kind': 'pool', 'op': 'topk_select', 'N': N, 'B': B, 'M': M}, score):
+        check(_lib.load().pygamd_topk_select(
+            _p(score), N, _p(ptr), _idx_dtype(ptr), B, _p(k), _p(out_ptr), M, int(max_nodes),
+            _p(perm), _p(weight), _stream(score)), 'topk_select')
+    return perm, weight
+
+
+def _gather_scale_args(x: Tensor, score: Tensor, perm: Tensor):
+    _require_device(x, score, perm)
+    x = _f32_rows(x, 'x')
+    if x.size(1) < 1:
+        raise ValueError("'x' needs at least one column")
+    score = _f32_vector(score, 'score', x.size(0))
+    perm = _i64_vector(perm, 'perm', perm.numel())
+    return x, score, perm
+
+
+def gather_scale_forward(x: Tensor, score: Tensor, perm: Tensor,
+                         multiplier: float) -> Tuple[Tensor, Tensor]:
+    """``pygamd_gather_scale_forward``: ``(multiplier * (score[perm, None] * x[perm]),
+    score[perm])`` in one launch; ``perm`` int64 without duplicates."""
+    x, score, perm = _gather_scale_args(x, score, perm)
+    N, F, M = x.size(0), x.size(1), perm.numel()
+    out = torch.empty(M, F, dtype=torch.float32, device=x.device)
+    weight = torch.empty(M, dtype=torch.float32, device=x.device)
+    with _timed({'kind': 'pool', 'op': 'gather_scale_forward', 'N': N, 'F': F, 'M': M}, x):
+        check(_lib.load().pygamd_gather_scale_forward(
+            _p(x), _ld(x), N, F, _p(score), _p(perm), M, float(multiplier), _p(out), F,
+            _p(weight), _stream(x)), 'gather_scale_forward')
+    return out, weight
+
+
+def gather_scale_backward(x: Tensor, score: Tensor, perm: Tensor, multiplier: float,
+                          grad_out: Tensor, grad_weight: Optional[Tensor], want_x: bool = True,
+                          want_score: bool = True):
+    """``pygamd_gather_scale_backward``: ``(grad_x [N, F], grad_score [N])`` (None where not
+    wanted) from ``grad_out [M, F]`` and the optional ``grad_weight [M]``; the rows outside
+    ``perm`` are exactly zero.  Both gradients live in ONE zero-filled buffer: one memset."""
+    x, score, perm = _gather_scale_args(x, score, perm)
+    N, F, M = x.size(0), x.size(1), perm.numel()
+    _require_device(grad_out, grad_weight)
+    grad_out = _strided_rows(grad_out, 'grad_out', F)
+    if grad_out.size(0) != M:
+        raise ValueError(f"'grad_out' must have {M} rows (got {grad_out.size(0)})")
+    if grad_weight is not None:
+        grad_weight = _f32_vector(grad_weight, 'grad_weight', M)
+    buf = torch.zeros(N * (F * bool(want_x) + bool(want_score)), dtype=torch.float32,
+                      device=x.device)
+    grad_x = buf[:N * F].view(N, F) if want_x else None
+    grad_score = buf[buf.numel() - N:] if want_score else None
+    with _timed({'kind': 'pool', 'op': 'gather_scale_backward', 'N': N, 'F': F, 'M': M}, x):
+        check(_lib.load().pygamd_gather_scale_backward(
+            _p(x), _ld(x), N, F, _p(score), _p(perm), M, float(multiplier), _p(grad_out),
+            _ld(grad_out), _p(grad_weight), _p(grad_x), F, _p(grad_score), _stream(x)),
+            'gather_scale_backward')
+    return grad_x, grad_score
+
+
+def filter_edges(edge_index: Tensor, node_map: Tensor) -> Tuple[Tensor, Tensor]:
+    """``pygamd_filter_edges``: ``(edge_index' [2, E'] int64, kept [E'] int64)`` — the edges whose
+    two endpoints both map to a non-negative entry of ``node_map [N]`` (int64: the new id or -1),
+    relabelled, in the original order, and their edge ids.  The two rows of ``edge_index`` (int32 /
+    int64) are read in place at their strides.  The outputs are allocated at ``E`` and narrowed
+    after the ONE host read of ``E'``."""
+    _require_device(edge_index, node_map)
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError(f"'edge_index' must be [2, E] (got {tuple(edge_index.shape)})")
+    node_map = _i64_vector(node_map, 'node_map', node_map.numel())
+    E, N = edge_index.size(1), node_map.numel()
+    row, col = edge_index[0], edge_index[1]
+    if E > 1 and row.stride(0) < 1:   # (a broadcast view)
+        row, col = row.contiguous(), col.contiguous()
+    stride = max(int(row.stride(0)), 1) if E > 1 else 1
+    out = torch.empty(2, E, dtype=torch.int64, device=edge_index.device)
+    kept = torch.empty(E, dtype=torch.int64, device=edge_index.device)
+    if E == 0:
+        return out, kept
+    lib = _lib.load()
+    total = torch.empty(1, dtype=torch.int64, device=edge_index.device)
+    ws, ws_bytes = _workspace(lib.pygamd_filter_edges_workspace_size, (E, ), edge_index.device)
+    with _timed({'kind': 'pool', 'op': 'filter_edges', 'E': E, 'N': N}, edge_index):
+        check(lib.pygamd_filter_edges(
+            _p(row), stride, _p(col), stride, _idx_dtype(edge_index), E, _p(node_map), N,
+            _p(out[0]), _p(out[1]), _p(kept), _p(total), _p(ws), ws_bytes, _stream(edge_index)),
+            'filter_edges')
+    n_kept = int(total.item())
+    return out[:, :n_kept], kept[:n_kept]

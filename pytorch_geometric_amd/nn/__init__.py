@@ -11,6 +11,7 @@ from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
 from .norm import BatchNorm, GraphNorm, LayerNorm, MessageNorm
 from .pool import global_add_pool, global_max_pool, global_mean_pool
 from .pool import fps, knn, knn_graph, nearest, radius, radius_graph
+from .pool import SAGPooling, TopKPooling, filter_adj, topk
 from . import functional  # noqa: F401
 
 __all__ = [
@@ -25,4 +26,5 @@ __all__ = [
     'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv',
     'EdgeConv', 'DynamicEdgeConv', 'PointNetConv', 'PointConv',
     'fps', 'knn', 'knn_graph', 'radius', 'radius_graph', 'nearest',
+    'TopKPooling', 'SAGPooling', 'topk', 'filter_adj',
 ]

@@ -5,7 +5,9 @@ dimension is ``-2``, or ``-1`` for a one-dimensional ``x``.  Float32 device tens
 package's ``scatter``; host tensors and other dtypes through the same reduction in plain torch.
 
 The geometric searches ``fps``, ``knn``, ``knn_graph``, ``radius``, ``radius_graph`` and ``nearest``
-live in :mod:`.cluster`."""
+live in :mod:`.cluster`; the hierarchical pooling layers ``TopKPooling`` and ``SAGPooling`` in
+:mod:`.topk_pool` and :mod:`.sag_pool`, over ``topk`` / ``SelectTopK`` (:mod:`.select`) and
+``filter_adj`` / ``FilterEdges`` (:mod:`.connect`)."""
 from typing import Optional
 
 import torch
@@ -13,6 +15,10 @@ from torch import Tensor
 
 from ...utils import scatter
 from .cluster import fps, knn, knn_graph, nearest, radius, radius_graph
+from .connect import FilterEdges, filter_adj
+from .sag_pool import SAGPooling
+from .select import SelectTopK, topk
+from .topk_pool import TopKPooling
 
 
 def _node_dim(x: Tensor) -> int:
@@ -60,4 +66,5 @@ def global_max_pool(x: Tensor, batch: Optional[Tensor], size: Optional[int] = No
 
 
 __all__ = ['global_add_pool', 'global_mean_pool', 'global_max_pool',
-           'fps', 'knn', 'knn_graph', 'radius', 'radius_graph', 'nearest']
+           'fps', 'knn', 'knn_graph', 'radius', 'radius_graph', 'nearest',
+           'TopKPooling', 'SAGPooling', 'SelectTopK', 'FilterEdges', 'topk', 'filter_adj']
