@@ -2183,6 +2183,58 @@ PYGAMD_API int pygamd_filter_edges(const void* row, int64_t row_stride, const vo
                                    int64_t* out_col, int64_t* kept, int64_t* total,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sparse-sparse product (csrc/spgemm.hip) --------------------------------------------------
+ * C[M x N] = A[M x K] * B[K x N], all three CSR: the reference's `adj @ adj` on torch.sparse CSR
+ * tensors in GraphUNet.augment_adj (torch_geometric/models/graph_unet.py:138-148) and
+ * `EdgeIndex.matmul(EdgeIndex)` (torch_geometric/edge_index.py:2011).  Values float32, a NULL value
+ * pointer = all ones; indices int32 / int64 by idx_dtype, shared by all three matrices; N < 2^31,
+ * M < 2^31.  A is any CSR (duplicates and unsorted columns within a row are fine); every row of B
+ * has UNIQUE columns inside [0, N) (any order; the caller coalesces); an entry of A whose column is
+ * outside [0, K) is skipped.  C has ascending unique columns in every row, one stored entry per
+ * structurally reachable (i, j): an entry whose terms cancel to 0.0 is kept.  No float atomics: a
+ * value is a fixed-order sum (csrc/spgemm.hip) and bit-identical from run to run.
+ *
+ * Rows are tiered by ub[i] = the number of products of row i: 0 -> nothing runs; up to
+ * PYGAMD_SPGEMM_WAVE_UB -> one wave, hash table in its slice of LDS; up to
+ * PYGAMD_SPGEMM_GROUP_SMALL_UB / PYGAMD_SPGEMM_GROUP_UB -> one workgroup, one key table and a value
+ * plane per wave in LDS (two table sizes); above -> expand, sort, compress in global memory (the
+ * column count of such a row comes from a bitmap window of PYGAMD_SPGEMM_BITMAP_COLS columns in
+ * LDS, one pass over the row's products per window).
+ *
+ * pygamd_spgemm_workspace_size: plan_bytes for (M) — the workspace of both calls below, which
+ *   carries the row plan from the first to the second — and long_bytes for the long tier of the
+ *   numeric call (long_rows, long_products as pygamd_spgemm_symbolic returned them; 0, 0 before).
+ * pygamd_spgemm_symbolic [sync]: the bound, the grouping of the rows by tier (pygamd_index_sort in
+ *   one radix pass + pygamd_index2ptr) and the count of every row's distinct columns; rowptr_c
+ *   [M + 1] is written (pygamd_cumsum) and totals [host, 4] = {nnz of C, products of the long rows,
+ *   long rows, long_bytes for these two} after ONE device-to-host copy.  Products of the long rows above 2^31 - 1, or an nnz
+ *   that does not fit idx_dtype -> status 2 (the caller takes its generic route).
+ * pygamd_spgemm_numeric: the same walk with values; col_c / val_c [nnz_c] are written at rowptr_c.
+ *   The operands, rowptr_c and `workspace` are those of the symbolic call, untouched in between.
+ * Before any device work: an unknown idx_dtype, a negative size, a NULL pointer with a non-empty
+ * size -> status 1; N >= 2^31 -> status 2; a short workspace -> status 3.                        */
+#define PYGAMD_SPGEMM_WAVE_UB 256
+#define PYGAMD_SPGEMM_GROUP_SMALL_UB 1024
+#define PYGAMD_SPGEMM_GROUP_UB 2048
+#define PYGAMD_SPGEMM_TIERS 5
+#define PYGAMD_SPGEMM_BITMAP_COLS 524288
+PYGAMD_API int pygamd_spgemm_workspace_size(int idx_dtype, int64_t M, int64_t long_rows,
+                                             int64_t long_products, size_t* plan_bytes /*[host]*/,
+                                             size_t* long_bytes /*[host]*/);
+PYGAMD_API int pygamd_spgemm_symbolic(const void* rowptr_a, const void* col_a,
+                                      const void* rowptr_b, const void* col_b, int idx_dtype,
+                                      int64_t M, int64_t K, int64_t N, int64_t nnz_a,
+                                      int64_t nnz_b, void* rowptr_c, int64_t* totals /*[host]*/,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_spgemm_numeric(const void* rowptr_a, const void* col_a, const float* val_a,
+                                     const void* rowptr_b, const void* col_b, const float* val_b,
+                                     int idx_dtype, int64_t M, int64_t K, int64_t N,
+                                     int64_t nnz_a, int64_t nnz_b, const void* rowptr_c,
+                                     int64_t nnz_c, void* col_c, float* val_c, int64_t long_rows,
+                                     int64_t long_products, void* workspace,
+                                     size_t workspace_bytes, void* long_workspace,
+                                     size_t long_workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

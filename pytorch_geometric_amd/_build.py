@@ -28,7 +28,7 @@ SOURCES = ['capi.hip', 'graph.hip', 'spmm.hip', 'scatter.hip', 'softmax.hip', 's
            'hetero_conv.hip', 'gatv2.hip', 'transformer.hip', 'hgt.hip', 'gine.hip',
            'pna.hip', 'gen.hip', 'resgated.hip', 'han.hip', 'mixture.hip', 'cg.hip',
            'film.hip', 'rgat.hip', 'graph_norm.hip', 'hop.hip', 'cluster.hip',
-           'pool.hip']
+           'pool.hip', 'spgemm.hip']
 LAB_SOURCES = SOURCES + ['sage_fused_lab.hip']
 LAB_FLAGS = {'gemm.hip': ['-DPYGAMD_LAB=1']}   # the weight-gradient variants and probes
 ARCH = 'gfx950'
@@ -39,7 +39,10 @@ FLAGS = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-fvisibility=h
 FLAGS += os.environ.get('PYGAMD_EXTRA_HIPCC_FLAGS', '').split()
 # Per-file additions (none at present; -fno-slp-vectorize on sage_fused.hip — no v_pk_add_f32 in
 # the gather loop — was measured neutral to slightly negative, profiles/r04_fused_noslp_probe.txt).
-EXTRA_FLAGS = {}
+EXTRA_FLAGS = {
+    # one product per lane and step: nothing for v_pk_*_f32 to pack, so the file is built without
+    'spgemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+}
 
 
 def find_hipcc():

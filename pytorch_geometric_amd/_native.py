@@ -4509,3 +4509,73 @@ def filter_edges(edge_index: Tensor, node_map: Tensor) -> Tuple[Tensor, Tensor]:
             'filter_edges')
     n_kept = int(total.item())
     return out[:, :n_kept], kept[:n_kept]
+
+
+# ---- sparse-sparse product (csrc/spgemm.hip) -----------------------------------------------------
+# the tiers' bounds on a row's products: one wave, the two workgroup tables, above them the long tier
+SPGEMM_WAVE_UB = _lib.CONSTANTS['PYGAMD_SPGEMM_WAVE_UB']
+SPGEMM_GROUP_SMALL_UB = _lib.CONSTANTS['PYGAMD_SPGEMM_GROUP_SMALL_UB']
+SPGEMM_GROUP_UB = _lib.CONSTANTS['PYGAMD_SPGEMM_GROUP_UB']
+
+
+class SpgemmUnsupported(PygAmdError):
+    """The product is outside the kernels' envelope (status 2): the caller's generic route."""
+
+
+def _csr_operand(rowptr: Tensor, col: Tensor, val: Optional[Tensor], rows: int, name: str):
+    if rowptr.dim() != 1 or rowptr.numel() != rows + 1:
+        raise ValueError(f"'rowptr_{name}' needs {rows + 1} entries (got {tuple(rowptr.shape)})")
+    if col.dim() != 1 or col.dtype != rowptr.dtype:
+        raise ValueError(f"'col_{name}' must be a vector of rowptr_{name}'s dtype")
+    if val is not None:
+        val = _f32_vector(val, f'val_{name}', col.numel())
+    return rowptr.contiguous(), col.contiguous(), val
+
+
+def spgemm(rowptr_a: Tensor, col_a: Tensor, val_a: Optional[Tensor], rowptr_b: Tensor,
+           col_b: Tensor, val_b: Optional[Tensor], M: int, K: int,
+           N: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """``pygamd_spgemm_symbolic`` + ``pygamd_spgemm_numeric``: ``(rowptr_c, col_c, val_c)`` of
+    ``C[M, N] = A[M, K] @ B[K, N]``, all CSR, float32 values (None: ones), one index dtype.  ``A``
+    is any CSR; every row of ``B`` has unique columns.  ``C`` has ascending unique columns per row
+    and keeps entries that cancel to zero.  ONE host read (inside the symbolic call): the total
+    ``nnz`` together with the long tier's row and product counts, which size the outputs and the
+    long tier's workspace.  Raises :class:`SpgemmUnsupported` outside the envelope (``N >= 2^31``,
+    more than ``2^31 - 1`` products in the long rows)."""
+    _require_device(rowptr_a, col_a, val_a, rowptr_b, col_b, val_b)
+    M, K, N = int(M), int(K), int(N)
+    rowptr_a, col_a, val_a = _csr_operand(rowptr_a, col_a, val_a, M, 'a')
+    rowptr_b, col_b, val_b = _csr_operand(rowptr_b, col_b, val_b, K, 'b')
+    if rowptr_b.dtype != rowptr_a.dtype:
+        raise ValueError('the two operands must share one index dtype')
+    idx, dev = _idx_dtype(rowptr_a), rowptr_a.device
+    lib = _lib.load()
+    plan, none = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    status = lib.pygamd_spgemm_workspace_size(idx, M, 0, 0, ctypes.byref(plan),
+                                               ctypes.byref(none))
+    if status == _lib.ERR_UNSUPPORTED:
+        raise SpgemmUnsupported('spgemm: outside the envelope of the kernels')
+    check(status, 'spgemm_workspace_size')
+    plan_bytes = plan.value
+    ws = torch.empty(plan_bytes, dtype=torch.uint8, device=dev)
+    rowptr_c = torch.empty(M + 1, dtype=rowptr_a.dtype, device=dev)
+    totals = (ctypes.c_int64 * 4)()
+    nnz_a, nnz_b = col_a.numel(), col_b.numel()
+    info = {'kind': 'spgemm', 'M': M, 'K': K, 'N': N, 'nnz_a': nnz_a, 'nnz_b': nnz_b}
+    with _timed(dict(info, op='symbolic'), rowptr_a):
+        status = lib.pygamd_spgemm_symbolic(
+            _p(rowptr_a), _p(col_a), _p(rowptr_b), _p(col_b), idx, M, K, N, nnz_a, nnz_b,
+            _p(rowptr_c), totals, _p(ws), plan_bytes, _stream(rowptr_a))
+    if status == _lib.ERR_UNSUPPORTED:
+        raise SpgemmUnsupported('spgemm: outside the envelope of the kernels')
+    check(status, 'spgemm_symbolic')
+    nnz_c, long_products, long_rows, long_bytes = (int(t) for t in totals)
+    col_c = torch.empty(nnz_c, dtype=rowptr_a.dtype, device=dev)
+    val_c = torch.empty(nnz_c, dtype=torch.float32, device=dev)
+    long_ws = torch.empty(long_bytes, dtype=torch.uint8, device=dev) if long_bytes else None
+    with _timed(dict(info, op='numeric', nnz_c=nnz_c, long_products=long_products), rowptr_a):
+        check(lib.pygamd_spgemm_numeric(
+            _p(rowptr_a), _p(col_a), _p(val_a), _p(rowptr_b), _p(col_b), _p(val_b), idx, M, K, N,
+            nnz_a, nnz_b, _p(rowptr_c), nnz_c, _p(col_c), _p(val_c), long_rows, long_products,
+            _p(ws), plan_bytes, _p(long_ws), long_bytes, _stream(rowptr_a)), 'spgemm_numeric')
+    return rowptr_c, col_c, val_c

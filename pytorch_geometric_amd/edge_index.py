@@ -150,6 +150,9 @@ class EdgeIndex(Tensor):
         # True: the backward of an aggregation runs the edge-parallel atomic kernel on the COO
         # list instead of building the source-sorted form (graphs used once: sampled batches)
         self.atomic_backward = False
+        # True: sorted by row with ascending unique columns (a result of `matmul(EdgeIndex)` or of
+        # `utils.coalesce` on a handle): the sparse-sparse product takes it as it is
+        self._coalesced = False
 
     @classmethod
     def from_csr(cls, rowptr: Tensor, col: Tensor, sparse_size: Tuple[int, int]) -> 'EdgeIndex':
@@ -269,12 +272,26 @@ class EdgeIndex(Tensor):
         out = EdgeIndex(ei, self.sparse_size, sort_order=sort_order, validate=False)
         return out, c.perm
 
-    def matmul(self, other: Tensor, input_value: Optional[Tensor] = None, reduce: str = 'sum',
-               transpose: bool = False) -> Tensor:
+    def matmul(self, other: Tensor, input_value: Optional[Tensor] = None,
+               other_value: Optional[Tensor] = None, reduce: str = 'sum',
+               transpose: bool = False, fuse: Optional[bool] = None):
         r"""Sparse-dense product with the handle as the matrix ``A[edge_index[0], edge_index[1]]``
         (``EdgeIndex.matmul``, edge_index.py:970-1026): ``A @ other`` reduces ``other[col]`` onto
         the rows; ``transpose=True`` gives ``A^T @ other``, i.e. what ``propagate`` computes
-        (messages from ``edge_index[0]`` onto ``edge_index[1]``)."""
+        (messages from ``edge_index[0]`` onto ``edge_index[1]``).
+
+        With an ``EdgeIndex`` as ``other`` it is the sparse-sparse product (edge_index.py:1973-2032)
+        and returns ``(EdgeIndex, value)``: the handle sorted by row with ascending unique columns,
+        its row pointer cached and its ``sparse_size`` set.  ``fuse`` (None: ``PYGAMD_FUSE_SPGEMM``
+        or the measured default) allows the kernels of csrc/spgemm.hip; host tensors, values that
+        are not float32 or require a gradient and ``N >= 2^31`` take ``torch.sparse``."""
+        if isinstance(other, EdgeIndex):
+            if reduce not in ('sum', 'add'):
+                raise NotImplementedError(f"`reduce='{reduce}'` not yet supported for "
+                                          f"sparse-sparse matrix multiplication")
+            return self._sparse_matmul(other, input_value, other_value, transpose, fuse)
+        if other_value is not None:
+            raise ValueError("'other_value' not supported for sparse-dense matrix multiplication")
         from ._functions import SpmmFunction
         reduce = 'sum' if reduce == 'add' else reduce
         if reduce not in ('sum', 'mean', 'min', 'max'):
@@ -287,6 +304,51 @@ class EdgeIndex(Tensor):
             flipped._csr, flipped._csc = self._csc, self._csr  # the sorted forms swap roles
             self._flipped = flipped
         return SpmmFunction.apply(other, input_value, self._flipped, reduce, 'coo')
+
+    def _sparse_matmul(self, other: 'EdgeIndex', input_value: Optional[Tensor],
+                       other_value: Optional[Tensor], transpose: bool, fuse: Optional[bool]):
+        """``(EdgeIndex, value)`` of ``A @ B`` (``A^T @ B``): ``A`` in its cached sorted form, ``B``
+        coalesced (``utils.coalesce``) unless it carries the mark that it is."""
+        from . import _spgemm
+        ei, oi = self.edge_index, other.edge_index
+        M, K = self.sparse_size[::-1] if transpose else self.sparse_size
+        N = other.sparse_size[1]
+        if other.sparse_size[0] != K or oi.dtype != ei.dtype:
+            raise ValueError(f"cannot multiply sparse sizes {(M, K)} and {other.sparse_size} "
+                             f"(or their index dtypes differ)")
+        for v, h, name in ((input_value, self, 'input_value'), (other_value, other, 'other_value')):
+            if v is not None and (v.dim() != 1 or v.numel() != h.num_edges):
+                raise ValueError(f"'{name}' must hold one value per edge")
+        fuse = _spgemm.fuse_default() if fuse is None else fuse
+        out = None
+        if fuse and oi.is_cuda and _spgemm.eligible(ei, N, input_value, other_value):
+            a = self.by_dst() if transpose else self.by_src()
+            val_a = None if input_value is None else input_value[a.perm.long()]
+            if other._coalesced:
+                b = other.by_src()
+                val_b = None if other_value is None else other_value[b.perm.long()]
+                ptr_b, col_b = b.ptr, b.idx
+            else:
+                from .utils import coalesce
+                ones = oi.new_ones(oi.size(1), dtype=torch.float32)
+                (row_b, col_b), val_b = coalesce(
+                    (oi[0], oi[1]), ones if other_value is None else other_value,
+                    num_nodes=max(K, N, 1))
+                ptr_b = _native.index2ptr(row_b.contiguous(), K)
+            try:
+                out = _native.spgemm(a.ptr, a.idx, val_a, ptr_b, col_b, val_b, M, K, N)
+            except _native.SpgemmUnsupported:   # the long tier's envelope
+                out = None
+        if out is None:
+            rows_a, cols_a = (ei[1], ei[0]) if transpose else (ei[0], ei[1])
+            out = _spgemm.generic(rows_a, cols_a, input_value, oi[0], oi[1], other_value, M, K, N)
+        rowptr, col, value = out
+        row = _spgemm.ptr2index(rowptr, col.numel())
+        prod = EdgeIndex(torch.stack([row, col]), (M, N), sort_order='row', validate=False)
+        perm = torch.arange(col.numel(), dtype=col.dtype, device=col.device)
+        prod._csc = CSR(rowptr, col, perm, M, N)
+        prod._coalesced = True
+        return prod, value
 
     def derived(self, key, build):
         """Per-handle cache of graphs DERIVED from this one by a layer (``gcn_norm``'s

@@ -7,7 +7,7 @@ from .conv import (CGConv, FastRGCNConv, FiLMConv, GINConv, GINEConv, GATConv, G
 from .conv import APPNP, GCN2Conv, LGConv, SGConv, SSGConv, TAGConv
 from .conv import DynamicEdgeConv, EdgeConv, PointConv, PointNetConv
 from .dense import HeteroDictLinear, HeteroLinear, Linear
-from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE
+from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE, GraphUNet
 from .norm import BatchNorm, GraphNorm, LayerNorm, MessageNorm
 from .pool import global_add_pool, global_max_pool, global_mean_pool
 from .pool import fps, knn, knn_graph, nearest, radius, radius_graph
@@ -26,5 +26,5 @@ __all__ = [
     'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv',
     'EdgeConv', 'DynamicEdgeConv', 'PointNetConv', 'PointConv',
     'fps', 'knn', 'knn_graph', 'radius', 'radius_graph', 'nearest',
-    'TopKPooling', 'SAGPooling', 'topk', 'filter_adj',
+    'TopKPooling', 'SAGPooling', 'topk', 'filter_adj', 'GraphUNet',
 ]

@@ -36,6 +36,17 @@ def _like_input(edge_index, out: Tensor):
     return (out[0], out[1]) if isinstance(edge_index, tuple) else out
 
 
+def _marked(edge_index, out, sort_by_row: bool):
+    """the coalesced list of a handle as a handle that says so (EdgeIndex.matmul reads the mark)"""
+    from ..edge_index import EdgeIndex
+    if not isinstance(edge_index, EdgeIndex) or not sort_by_row:
+        return out
+    size = edge_index.sparse_size
+    out = EdgeIndex(out, size, sort_order='row', validate=False)
+    out._coalesced = True
+    return out
+
+
 def _take(edge_attr: Attr, perm: Tensor) -> Attr:
     if isinstance(edge_attr, Tensor):
         return edge_attr[perm]
@@ -91,12 +102,13 @@ def coalesce(edge_index, edge_attr: Attr = MISSING, num_nodes: Optional[int] = N
         if perm is None:
             return _result(edge_index, edge_attr)
         out, _ = _native.edge_unkey(key, n, sort_by_row, row.dtype)
-        return _result(_like_input(edge_index, out), _take(edge_attr, perm))
+        return _result(_marked(edge_index, _like_input(edge_index, out), sort_by_row),
+                       _take(edge_attr, perm))
     has_attr = isinstance(edge_attr, Tensor) or (isinstance(edge_attr, (list, tuple))
                                                  and len(edge_attr) > 0)
     out, gid = _native.edge_unkey(key, n, sort_by_row, row.dtype, scan=scan, perm=perm,
                                   n_out=n_unique, want_groups=has_attr)
-    out = _like_input(edge_index, out)
+    out = _marked(edge_index, _like_input(edge_index, out), sort_by_row)
     if isinstance(edge_attr, Tensor):
         return out, scatter(edge_attr, gid, 0, n_unique, reduce)
     if isinstance(edge_attr, (list, tuple)):
