@@ -1302,6 +1302,70 @@ PYGAMD_API int pygamd_mixture_coef_grad(const pygamd_csr* g, const void* edge_id
                                         int64_t n_cols, int64_t F, int64_t K, float* grad_coef,
                                         void* stream);
 
+/* ---- SplineConv: bin-collect and bin-expand (spline_conv.py:150-153) -------------------------------
+ * The reference's message is spline_weighting(x_j, weight, *spline_basis(pseudo, kernel_size,
+ * is_open_spline, degree)) (spline_conv.py:150-153), two pyg-lib operators.  For edge e and entry
+ * s < S = (degree + 1)^dim, with the digits of s in base degree + 1 being k_d (dimension 0 lowest):
+ *   v_d = pseudo[e, d] * (kernel_size[d] - degree * is_open_spline[d])            (float32)
+ *   idx_d = (int64(v_d) + k_d) mod kernel_size[d],  f_d = v_d - floor(v_d)
+ *   basis[e, s] = prod_d B_degree(f_d, k_d),  wi[e, s] = sum_d idx_d * prod_{d' < d} kernel_size[d']
+ *   m_e = sum_s basis[e, s] * x_j W[wi[e, s]],  W [K, F_in, F_out], K = prod kernel_size
+ * B: degree 1: 1-f, f; degree 2: f^2/2-f+1/2, -f^2+f+1/2, f^2/2; degree 3: (1-f)^3/6,
+ * (3f^3-6f^2+4)/6, (-3f^3+3f^2+3f+1)/6, f^3/6.  Every idx_d is wrapped into [0, kernel_size[d])
+ * non-negatively and wi clamped below K, whatever pseudo holds: no input makes a kernel read or
+ * write out of range (NaN: int64(v_d) taken as 0, the basis NaN).  kernel_size is int64 [dim] and
+ * is_open_spline uint8 [dim], both on the device.  The handle-walking kernels rebuild (basis, wi)
+ * per slot, lane s entry s; no [E, S] tensor exists on that route.
+ *
+ * pygamd_spline_basis: basis [E, S] float32 and weight_index [E, S] int64, one thread per entry.
+ * pygamd_spline_collect (spline_conv.py:150-153 transform first): over the by-destination handle,
+ *   out[i] = row_scale[i] * sum_slots sum_s basis_s * h[col, wi_s * F_out : +F_out] + root[i] + bias
+ *   with h = x_src @ W [n_cols, K * F_out] at row stride ld_h; row_scale (1 / deg for mean), root
+ *   [n_rows, F_out] at ld_root and bias [F_out] may each be NULL.  One wave per row or hub chunk,
+ *   lane l the columns l + 64 e, two slots in flight; a split row's partials are summed in chunk
+ *   order and the epilogue applied once (workspace: n_chunks * F_out floats).
+ * pygamd_spline_expand (the backward of spline_conv.py:150-153): over the by-SOURCE handle,
+ *   gh[j, k, :] = sum_{slots of j} sum_{s: wi_s = k} basis_s * col_scale[i] * grad_out[i, :]
+ *   (i = col of the slot; col_scale may be NULL).  ONE wave per workgroup keeps the row's
+ *   K * F_out bins in LDS, lane l owning the columns l + 64 e of every bin, zeroes them, walks the
+ *   slots in order and writes the row coalesced; hub chunks write partial rows that are summed in
+ *   chunk order (workspace: n_chunks * K * F_out floats).  Rows without slots: 0.
+ * pygamd_spline_pseudo_grad (spline_conv.py:150-153 by pseudo): over the by-destination handle,
+ *   grad_pseudo[edge, d] = sum_s <h[col, wi_s], row_scale[i] grad_out[i]> d basis_s / d pseudo_d;
+ *   every edge's row is written exactly once.  No workspace.
+ *
+ * pygamd_spline_supported(F_in, F_out, K, S): 1 <= F_in, F_out <= 512, 1 <= S <= 64 (a lane per
+ * entry; hence dim <= 6) and K * F_out <= 16384: expand's bins are the 64 KiB of LDS a workgroup
+ * gets without opting in to more, all of it one wave's.  Otherwise status 2.  fp32 data, int32 /
+ * int64 indices.  No float atomics, grids from sizes only: bitwise reproducible.  Status 1 / 2 / 3
+ * before any device work; n_rows == 0 returns 0. */
+PYGAMD_API int pygamd_spline_supported(int64_t F_in, int64_t F_out, int64_t K, int64_t S);
+PYGAMD_API int pygamd_spline_workspace_size(int64_t n_chunks, int64_t F_out, int64_t K,
+                                             size_t* bytes /*[host]*/);
+PYGAMD_API int pygamd_spline_basis(const float* pseudo, const int64_t* kernel_size,
+                                   const void* is_open_spline, int64_t E, int64_t dim,
+                                   int64_t degree, int64_t K, float* basis,
+                                   int64_t* weight_index, void* stream);
+PYGAMD_API int pygamd_spline_collect(const pygamd_csr* g, const void* edge_id, const float* pseudo,
+                                     const int64_t* kernel_size, const void* is_open_spline,
+                                     int64_t dim, int64_t degree, int64_t K, const float* h,
+                                     int64_t ld_h, int64_t n_cols, int64_t F_out,
+                                     const float* row_scale, const float* root, int64_t ld_root,
+                                     const float* bias, float* out, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_spline_expand(const pygamd_csr* g, const void* edge_id, const float* pseudo,
+                                    const int64_t* kernel_size, const void* is_open_spline,
+                                    int64_t dim, int64_t degree, int64_t K, const float* grad_out,
+                                    int64_t ld_g, int64_t n_cols, int64_t F_out,
+                                    const float* col_scale, float* gh, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+PYGAMD_API int pygamd_spline_pseudo_grad(const pygamd_csr* g, const void* edge_id,
+                                         const float* pseudo, const int64_t* kernel_size,
+                                         const void* is_open_spline, int64_t dim, int64_t degree,
+                                         int64_t K, const float* h, int64_t ld_h, int64_t n_cols,
+                                         int64_t F_out, const float* grad_out, int64_t ld_g,
+                                         const float* row_scale, float* grad_pseudo, void* stream);
+
 /* ---- per-graph normalisation: GraphNorm and LayerNorm(mode='graph') --------------------------------
  * (nn/norm/graph_norm.py:72-76, nn/norm/layer_norm.py:82-108).  The reference forms the statistics
  * with two scatters, broadcasts them back with two index selects and makes about eight elementwise

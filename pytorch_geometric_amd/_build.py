@@ -28,7 +28,7 @@ SOURCES = ['capi.hip', 'graph.hip', 'spmm.hip', 'scatter.hip', 'softmax.hip', 's
            'hetero_conv.hip', 'gatv2.hip', 'transformer.hip', 'hgt.hip', 'gine.hip',
            'pna.hip', 'gen.hip', 'resgated.hip', 'han.hip', 'mixture.hip', 'cg.hip',
            'film.hip', 'rgat.hip', 'graph_norm.hip', 'hop.hip', 'cluster.hip',
-           'pool.hip', 'spgemm.hip']
+           'pool.hip', 'spgemm.hip', 'spline.hip']
 LAB_SOURCES = SOURCES + ['sage_fused_lab.hip']
 LAB_FLAGS = {'gemm.hip': ['-DPYGAMD_LAB=1']}   # the weight-gradient variants and probes
 ARCH = 'gfx950'
@@ -42,6 +42,8 @@ FLAGS += os.environ.get('PYGAMD_EXTRA_HIPCC_FLAGS', '').split()
 EXTRA_FLAGS = {
     # one product per lane and step: nothing for v_pk_*_f32 to pack, so the file is built without
     'spgemm.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
+    # one fmaf per lane, column and entry: likewise
+    'spline.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops'],
 }
 
 

@@ -1112,6 +1112,52 @@ class MixtureConvFunction(Function):
             want_coef=need[1], want_weight=need[2]) + (None, None)
 
 
+class SplineConvFunction(Function):
+    """SplineConv's propagate with its epilogue (spline_conv.py:139-153), transform first:
+
+        out[i] = scale_i * sum_{e: dst(e) = i} sum_s basis[e, s] (x_src[src(e)] weight[wi[e, s]])
+                 + root[i] + bias
+
+    with ``pseudo [E, dim]`` in the caller's edge order, ``weight [K, F, M]``, ``scale_i = 1 /
+    deg(i)`` when ``mean``, ``root [n_dst, M]`` (``lin(x_dst)``) and ``bias [M]`` optional: one
+    dense product and one collect launch (csrc/spline.hip), which rebuilds the ``S`` pairs
+    ``(basis, wi)`` of a slot in registers.  Only the inputs are saved; the backward is one expand
+    launch over the by-source form and two dense products, plus one dense product and one launch
+    for ``grad_pseudo`` when it is asked for.  No ``[E, S]`` tensor exists."""
+
+    @staticmethod
+    def forward(ctx, x_src: Tensor, pseudo: Tensor, weight: Tensor, root: Optional[Tensor],
+                bias: Optional[Tensor], kernel_size: Tensor, is_open_spline: Tensor, degree: int,
+                graph: EdgeIndex, n_dst: int, mean: bool):
+        _check_rows(graph, n_dst, 'x_src', x_src, 'x_dst', None)
+        if x_src.dim() != 2 or weight.dim() != 3 or weight.size(1) != x_src.size(1):
+            raise ValueError(f"'x_src' [N, F] and 'weight' [K, F, M] do not agree (got "
+                             f"{tuple(x_src.shape)}, {tuple(weight.shape)})")
+        fwd = graph.by_dst()
+        bins = _native.spline_bins(pseudo, kernel_size, is_open_spline, degree, weight.size(0),
+                                   E=graph.num_edges)
+        scale = fwd.inv_degree() if mean else None
+        out = _onepass.spline_forward(fwd, fwd.perm, x_src, bins, weight, scale, root, bias)
+        ctx.save_for_backward(x_src, pseudo, weight, kernel_size, is_open_spline)
+        ctx.graph, ctx.degree, ctx.mean = graph, int(degree), bool(mean)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        x_src, pseudo, weight, kernel_size, is_open_spline = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grad_out = grad_out.contiguous()
+        bins = _native.spline_bins(pseudo, kernel_size, is_open_spline, ctx.degree,
+                                   weight.size(0))
+        scale = ctx.graph.by_dst().inv_degree() if ctx.mean else None
+        g_x, g_p, g_w = _onepass.spline_backward(
+            Slots.of_graph(ctx.graph), x_src, bins, weight, grad_out, scale, want_x=need[0],
+            want_pseudo=need[1], want_weight=need[2])
+        return (g_x, g_p, g_w, grad_out if need[3] else None,
+                grad_out.sum(0) if need[4] else None, None, None, None, None, None, None)
+
+
 class PnaAggregateFunction(Function):
     """The aggregation of PNAConv with a linear message (pna_conv.py:175-188 under
     aggr/scaler.py:82) in ONE pass over the by-destination slots.  The message of slot ``k`` of

@@ -2781,6 +2781,170 @@ def mixture_coef_grad(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], wi
     return grad
 
 
+# ---- SplineConv: bin-collect and bin-expand (csrc/spline.hip) --------------------------------------
+def spline_supported(F_in: int, F_out: int, K: int, S: int) -> bool:
+    """The kernels serve ``1 <= F_in, F_out <= 512``, ``1 <= S <= 64`` entries per edge and ``K *
+    F_out <= 16384`` (a source row's bins in one wave's LDS)."""
+    return bool(_lib.load().pygamd_spline_supported(int(F_in), int(F_out), int(K), int(S)))
+
+
+class SplineBins(NamedTuple):
+    """How edges select and weight their bins: ``pseudo [E, dim]`` float32, the layer's buffers
+    ``kernel_size`` (int64) and ``is_open_spline`` (uint8) on the device, ``degree`` and ``K``."""
+    pseudo: Tensor
+    kernel_size: Tensor
+    is_open_spline: Tensor
+    degree: int
+    K: int
+
+    @property
+    def dim(self) -> int:
+        return self.pseudo.size(1)
+
+    def args(self):
+        return (_p(self.pseudo), _p(self.kernel_size), _p(self.is_open_spline), self.dim,
+                self.degree, self.K)
+
+
+def spline_bins(pseudo: Tensor, kernel_size: Tensor, is_open_spline: Tensor, degree: int,
+                K: int, E: Optional[int] = None) -> SplineBins:
+    _require_device(pseudo, kernel_size, is_open_spline)
+    if pseudo.dtype != torch.float32 or pseudo.dim() != 2 or (E is not None and pseudo.size(0) != E):
+        raise ValueError(f"'pseudo' must be a float32 [{'E' if E is None else E}, dim] tensor (got "
+                         f"{pseudo.dtype} {tuple(pseudo.shape)})")
+    dim = pseudo.size(1)
+    if kernel_size.numel() != dim or is_open_spline.numel() != dim:
+        raise ValueError(f"'kernel_size' and 'is_open_spline' must have dim = {dim} entries")
+    if degree not in (1, 2, 3):
+        raise ValueError(f"'degree' must be 1, 2 or 3 (got {degree})")
+    return SplineBins(pseudo.contiguous(), kernel_size.to(torch.int64).contiguous(),
+                      is_open_spline.to(torch.uint8).contiguous(), int(degree), int(K))
+
+
+def spline_basis(pseudo: Tensor, kernel_size: Tensor, is_open_spline: Tensor,
+                 degree: int, K: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """``(basis [E, S] float32, weight_index [E, S] int64)`` of spline_conv.py:151, one launch
+    (``K = prod(kernel_size)``, read from the device when not given)."""
+    K = int(kernel_size.prod()) if K is None else K
+    b = spline_bins(pseudo, kernel_size, is_open_spline, degree, K)
+    E, S = pseudo.size(0), (degree + 1) ** b.dim
+    basis = torch.empty(E, S, dtype=torch.float32, device=pseudo.device)
+    index = torch.empty(E, S, dtype=torch.int64, device=pseudo.device)
+    if E > 0:
+        with _timed({'kind': 'spline', 'op': 'basis', 'E': E, 'S': S}, pseudo):
+            check(_lib.load().pygamd_spline_basis(
+                _p(b.pseudo), _p(b.kernel_size), _p(b.is_open_spline), E, b.dim, b.degree, b.K,
+                _p(basis), _p(index), _stream(pseudo)), 'spline_basis')
+    return basis, index
+
+
+def spline_collect(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], bins: SplineBins,
+                   h: Tensor, *, scale: Optional[Tensor] = None, root: Optional[Tensor] = None,
+                   bias: Optional[Tensor] = None, hub=None) -> Tensor:
+    """``out [n_rows, M]`` with ``out[i] = scale[i] * sum_{slots s of i} sum_t basis[s, t] *
+    h[col[s], wi[s, t] * M : (wi[s, t] + 1) * M] + root[i] + bias`` over the by-destination handle,
+    ``h [n_src, K * M]`` (a column block is taken in place), ``scale [n_rows]``, ``root [>= n_rows,
+    M]`` and ``bias [M]`` optional.  The pairs ``(basis, wi)`` are rebuilt per slot from ``bins``."""
+    _require_device(rowptr, col, edge_id, h, scale, root, bias)
+    lib = _lib.load()
+    n_rows, E, K = rowptr.numel() - 1, col.numel(), bins.K
+    if h.dim() != 2 or h.size(1) % K or h.size(1) < K:
+        raise ValueError(f"'h' must be a float32 [n_src, {K} * M] tensor (got {tuple(h.shape)})")
+    M = h.size(1) // K
+    h = _strided_rows(h, 'h', K * M)
+    if bins.pseudo.size(0) != E:
+        raise ValueError(f"'pseudo' must have one row per slot ({E})")
+    edge_id = _edge_id(edge_id, rowptr, col)
+    if root is not None:
+        root = _strided_rows(root, 'root', M)
+        if root.size(0) < n_rows:
+            raise ValueError(f"'root' must have at least {n_rows} rows")
+    if scale is not None and (scale.dtype != torch.float32 or scale.numel() != n_rows):
+        raise ValueError(f"'scale' must be a float32 [{n_rows}] tensor")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != M):
+        raise ValueError(f"'bias' must be a float32 [{M}] tensor")
+    out = torch.empty(n_rows, M, dtype=torch.float32, device=h.device)
+    if n_rows == 0:
+        return out
+    if E == 0:  # no slot anywhere: the epilogue alone, nothing to launch
+        out.zero_()
+        if root is not None:
+            out += root[:n_rows]
+        return out if bias is None else out + bias
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_spline_workspace_size, (g.n_chunks, M, 1), h.device,
+                              g.n_chunks > 0)
+    scale = None if scale is None else scale.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    with _timed({'kind': 'spline', 'op': 'collect', 'n_rows': n_rows, 'E': E, 'M': M, 'K': K,
+                 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, h):
+        check(lib.pygamd_spline_collect(
+            ctypes.byref(g), _p(edge_id), *bins.args(), _p(h), _ld(h), h.size(0), M, _p(scale),
+            _p(root), 0 if root is None else _ld(root), _p(bias), _p(out), _p(ws), ws_bytes,
+            _stream(h)), 'spline_collect')
+    return out
+
+
+def spline_expand(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], bins: SplineBins,
+                  grad_out: Tensor, *, scale: Optional[Tensor] = None, hub=None) -> Tensor:
+    """``GH [n_rows, K * M]`` with ``GH[j, k] = sum_{slots s of j} sum_{t: wi[s, t] = k} basis[s,
+    t] * scale[col[s]] * grad_out[col[s]]`` over the by-SOURCE handle (``col`` = destinations,
+    ``edge_id`` = by-source slot -> edge).  Rows without slots are exactly 0."""
+    _require_device(rowptr, col, edge_id, grad_out, scale)
+    lib = _lib.load()
+    n_rows, E, K = rowptr.numel() - 1, col.numel(), bins.K
+    if grad_out.dim() != 2:
+        raise ValueError("'grad_out' must be two-dimensional")
+    M = grad_out.size(1)
+    grad_out = _strided_rows(grad_out, 'grad_out', M)
+    if bins.pseudo.size(0) != E:
+        raise ValueError(f"'pseudo' must have one row per slot ({E})")
+    if scale is not None and (scale.dtype != torch.float32 or scale.numel() != grad_out.size(0)):
+        raise ValueError(f"'scale' must be a float32 [{grad_out.size(0)}] tensor")
+    edge_id = _edge_id(edge_id, rowptr, col)
+    if n_rows == 0 or E == 0:
+        return torch.zeros(n_rows, K * M, dtype=torch.float32, device=grad_out.device)
+    gh = torch.empty(n_rows, K * M, dtype=torch.float32, device=grad_out.device)
+    g = _csr(rowptr, col, n_rows, hub)
+    ws, ws_bytes = _workspace(lib.pygamd_spline_workspace_size, (g.n_chunks, M, K),
+                              grad_out.device, g.n_chunks > 0)
+    scale = None if scale is None else scale.contiguous()
+    with _timed({'kind': 'spline', 'op': 'expand', 'n_rows': n_rows, 'E': E, 'M': M, 'K': K,
+                 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, grad_out):
+        check(lib.pygamd_spline_expand(
+            ctypes.byref(g), _p(edge_id), *bins.args(), _p(grad_out), _ld(grad_out),
+            grad_out.size(0), M, _p(scale), _p(gh), _p(ws), ws_bytes, _stream(grad_out)),
+            'spline_expand')
+    return gh
+
+
+def spline_pseudo_grad(rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], bins: SplineBins,
+                       h: Tensor, grad_out: Tensor, *, scale: Optional[Tensor] = None,
+                       hub=None) -> Tensor:
+    """``grad_pseudo [E, dim]`` over the by-destination handle: ``sum_t <h[col[s], wi[s, t]],
+    scale[i] * grad_out[i]> * d basis[s, t] / d pseudo`` for every slot ``s`` of every row ``i``."""
+    _require_device(rowptr, col, edge_id, h, grad_out, scale)
+    lib = _lib.load()
+    n_rows, E, K = rowptr.numel() - 1, col.numel(), bins.K
+    M = grad_out.size(1)
+    grad_out = _strided_rows(grad_out, 'grad_out', M)
+    h = _strided_rows(h, 'h', K * M)
+    if bins.pseudo.size(0) != E or grad_out.size(0) < n_rows:
+        raise ValueError("'pseudo' must have one row per slot and 'grad_out' one per row")
+    edge_id = _edge_id(edge_id, rowptr, col)
+    grad = torch.empty(E, bins.dim, dtype=torch.float32, device=h.device)
+    if n_rows == 0 or E == 0:
+        return grad
+    g = _csr(rowptr, col, n_rows, hub)
+    scale = None if scale is None else scale.contiguous()
+    with _timed({'kind': 'spline', 'op': 'pseudo_grad', 'n_rows': n_rows, 'E': E, 'M': M, 'K': K,
+                 'n_hub': g.n_hub, 'n_chunks': g.n_chunks}, h):
+        check(lib.pygamd_spline_pseudo_grad(
+            ctypes.byref(g), _p(edge_id), *bins.args(), _p(h), _ld(h), h.size(0), M,
+            _p(grad_out), _ld(grad_out), _p(scale), _p(grad), _stream(h)), 'spline_pseudo_grad')
+    return grad
+
+
 # ---- per-graph normalisation (csrc/graph_norm.hip) -------------------------------------------------
 # The hub plan over a by-graph pointer: a graph of more than GRAPH_NORM_THRESHOLD nodes is walked as
 # chunks of GRAPH_NORM_CHUNK nodes, one wave each (profiles/graph_norm.md).

@@ -633,6 +633,49 @@ def mixture_backward(slots, x_src, coef, weight, grad_out, *, want_x=True, want_
     return g_x, g_c, g_w
 
 
+def spline_transform(x_src, weight):
+    """``H [n_src, K * M] = x_src @ weight`` with ``weight [K, F, M]`` stacked along the columns:
+    one dense product for all ``K`` bins"""
+    from ._functions import linear
+    K, F, M = weight.shape
+    return linear(x_src, weight.permute(0, 2, 1).reshape(K * M, F))
+
+
+def spline_forward(fwd, edge_id, x_src, bins, weight, scale=None, root=None, bias=None):
+    """``out [n_dst, M]`` of SplineConv's propagate with its epilogue, transform first: one dense
+    product (``H``) and one collect launch that gathers ``S`` rows of ``M`` floats per slot and
+    applies ``scale`` (``1 / deg`` for the mean), ``root`` (``lin(x_dst)``) and ``bias``."""
+    h = spline_transform(x_src, weight)
+    return _native.spline_collect(fwd.ptr, fwd.idx, edge_id, bins, h, scale=scale, root=root,
+                                  bias=bias, hub=fwd.hub)
+
+
+def spline_backward(slots, x_src, bins, weight, grad_out, scale=None, *, want_x=True,
+                    want_pseudo=False, want_weight=True):
+    """``(grad_x_src, grad_pseudo, grad_weight)``, None where not wanted.  One expand launch over
+    the by-source form gives ``GH [n_src, K * M]``, from which ``grad_weight = x_src^T GH`` and
+    ``grad_x_src = GH W^T`` are dense products; ``grad_pseudo`` recomputes ``H`` (one dense
+    product) and takes one launch over the by-destination form.  ``scale``: the forward's."""
+    from ._functions import linear
+    K, F, M = weight.shape
+    g_x = g_p = g_w = None
+    if want_x or want_weight:
+        bwd = slots.by_src()
+        gh = _native.spline_expand(bwd.ptr, bwd.idx, slots.edge_id_t(), bins, grad_out,
+                                   scale=scale, hub=bwd.hub)
+        if want_weight:
+            g_w = _transposed_product(x_src, gh).view(F, K, M).permute(1, 0, 2).contiguous()
+        if want_x:
+            g_x = linear(gh, weight.permute(1, 0, 2).reshape(F, K * M))
+        del gh
+    if want_pseudo:
+        fwd = slots.fwd
+        h = spline_transform(x_src, weight)
+        g_p = _native.spline_pseudo_grad(fwd.ptr, fwd.idx, slots.edge_id(), bins, h, grad_out,
+                                         scale=scale, hub=fwd.hub)
+    return g_x, g_p, g_w
+
+
 def hgt_blocks(kqvs, src_pos, F):
     """``(ks, vs)`` per edge type: the key and value column blocks of its ``[N, 3 * F]`` source"""
     return [kqvs[p][:, :F] for p in src_pos], [kqvs[p][:, 2 * F:] for p in src_pos]

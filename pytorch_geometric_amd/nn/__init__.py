@@ -6,6 +6,7 @@ from .conv import (CGConv, FastRGCNConv, FiLMConv, GINConv, GINEConv, GATConv, G
                    gcn_norm, group)
 from .conv import APPNP, GCN2Conv, LGConv, SGConv, SSGConv, TAGConv
 from .conv import DynamicEdgeConv, EdgeConv, PointConv, PointNetConv
+from .conv import SplineConv
 from .dense import HeteroDictLinear, HeteroLinear, Linear
 from .models import GAT, GCN, BasicGNN, DeepGCNLayer, GraphSAGE, GraphUNet
 from .norm import BatchNorm, GraphNorm, LayerNorm, MessageNorm
@@ -24,7 +25,7 @@ __all__ = [
     'BasicGNN', 'GCN', 'GraphSAGE', 'GAT', 'GraphNorm', 'LayerNorm', 'BatchNorm',
     'global_add_pool', 'global_mean_pool', 'global_max_pool',
     'APPNP', 'SGConv', 'SSGConv', 'TAGConv', 'LGConv', 'GCN2Conv',
-    'EdgeConv', 'DynamicEdgeConv', 'PointNetConv', 'PointConv',
+    'EdgeConv', 'DynamicEdgeConv', 'PointNetConv', 'PointConv', 'SplineConv',
     'fps', 'knn', 'knn_graph', 'radius', 'radius_graph', 'nearest',
     'TopKPooling', 'SAGPooling', 'topk', 'filter_adj', 'GraphUNet',
 ]

@@ -53,6 +53,9 @@ Operators (all index tensors int32 / int64, features float32):
                             -> Tensor``
 ``mixture_conv``            ``(Tensor x_src, Tensor coef, Tensor weight, Tensor rowptr,
                             Tensor col, Tensor? edge_id) -> Tensor``
+``spline_conv``             ``(Tensor x_src, Tensor pseudo, Tensor weight, Tensor? root,
+                            Tensor? bias, Tensor kernel_size, Tensor is_open_spline, int degree,
+                            Tensor rowptr, Tensor col, Tensor? edge_id, bool mean) -> Tensor``
 ``cg_aggregate``            ``(Tensor p, Tensor? q, Tensor? edge_attr, Tensor? w_f, Tensor? w_s,
                             Tensor? edge_terms, Tensor? residual, Tensor rowptr, Tensor col,
                             Tensor? edge_id, bool mean) -> Tensor``
@@ -1220,6 +1223,85 @@ def _mixture_bwd(ctx, grad):
 register_autograd('pyg_amd::mixture_conv', _mixture_bwd, setup_context=_mixture_setup)
 
 
+# ---- SplineConv (transform first) on a CSR pair (rows = destinations) ----------------------------
+def _spline_scale(rowptr: Tensor, mean: bool) -> Optional[Tensor]:
+    return 1.0 / (rowptr[1:] - rowptr[:-1]).clamp(min=1).to(torch.float32) if mean else None
+
+
+def _spline_S(pseudo: Tensor, degree: int) -> int:
+    return (degree + 1) ** pseudo.size(1)
+
+
+@custom_op('pyg_amd::spline_conv', mutates_args=(), device_types=_DEV)
+def spline_conv(x_src: Tensor, pseudo: Tensor, weight: Tensor, root: Optional[Tensor],
+                bias: Optional[Tensor], kernel_size: Tensor, is_open_spline: Tensor, degree: int,
+                rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], mean: bool) -> Tensor:
+    """SplineConv's propagate and epilogue (spline_conv.py:139-153): ``out [n_dst, M] = scale *
+    sum_slots sum_s basis_s (x_src[col] weight[wi_s]) + root + bias`` with ``pseudo [E, dim]``,
+    ``weight [K, F, M]``, the layer's buffers ``kernel_size`` / ``is_open_spline``, ``scale = 1 /
+    deg`` when ``mean``.  ``edge_id=None``: ``pseudo`` follows the slots of ``col``."""
+    K, F, M = weight.shape
+    if not _native.spline_supported(F, M, K, _spline_S(pseudo, degree)):
+        raise NotImplementedError(
+            f'spline_conv serves F_in, F_out <= 512, (degree + 1)^dim <= 64 and K * F_out <= 16384 '
+            f'(got F_in = {F}, F_out = {M}, K = {K}, dim = {pseudo.size(1)}, degree = {degree})')
+    bins = _native.spline_bins(pseudo, kernel_size, is_open_spline, degree, K, E=col.numel())
+    return _onepass.spline_forward(_onepass._Form(rowptr, col), edge_id, x_src, bins, weight,
+                                   _spline_scale(rowptr, mean), root, bias)
+
+
+@spline_conv.register_fake
+def _(x_src, pseudo, weight, root, bias, kernel_size, is_open_spline, degree, rowptr, col,
+      edge_id, mean):
+    return x_src.new_empty(rowptr.numel() - 1, weight.shape[2])
+
+
+@custom_op('pyg_amd::spline_conv_backward', mutates_args=(), device_types=_DEV)
+def spline_conv_backward(grad: Tensor, x_src: Tensor, pseudo: Tensor, weight: Tensor,
+                         kernel_size: Tensor, is_open_spline: Tensor, degree: int,
+                         rowptr: Tensor, col: Tensor, edge_id: Optional[Tensor], mean: bool,
+                         need_x: bool, need_pseudo: bool,
+                         need_weight: bool) -> Tuple[Tensor, Tensor, Tensor]:
+    """The gradients of ``(x_src, pseudo, weight)``; one that is not needed is an empty tensor."""
+    bins = _native.spline_bins(pseudo, kernel_size, is_open_spline, degree, weight.size(0))
+    grads = _onepass.spline_backward(Slots.of_csr(rowptr, col, x_src.size(0), edge_id), x_src,
+                                     bins, weight, grad, _spline_scale(rowptr, mean),
+                                     want_x=need_x, want_pseudo=need_pseudo,
+                                     want_weight=need_weight)
+    return tuple(grad.new_empty(0) if g is None else (g.clone() if g._base is not None else g)
+                 for g in grads)
+
+
+@spline_conv_backward.register_fake
+def _(grad, x_src, pseudo, weight, kernel_size, is_open_spline, degree, rowptr, col, edge_id,
+      mean, need_x, need_pseudo, need_weight):
+    e = grad.new_empty(0)
+    return (torch.empty_like(x_src, memory_format=torch.contiguous_format) if need_x else e,
+            torch.empty_like(pseudo, memory_format=torch.contiguous_format) if need_pseudo else e,
+            torch.empty_like(weight, memory_format=torch.contiguous_format) if need_weight else e)
+
+
+def _spline_setup(ctx, inputs, output):
+    (x_src, pseudo, weight, _, _, kernel_size, is_open_spline, degree, rowptr, col, edge_id,
+     mean) = inputs
+    ctx.static = (degree, mean)
+    ctx.save_for_backward(x_src, pseudo, weight, kernel_size, is_open_spline, rowptr, col, edge_id)
+
+
+def _spline_bwd(ctx, grad):
+    x_src, pseudo, weight, kernel_size, is_open_spline, rowptr, col, edge_id = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    degree, mean = ctx.static
+    grad = grad.contiguous()
+    grads = spline_conv_backward(grad, x_src, pseudo, weight, kernel_size, is_open_spline, degree,
+                                 rowptr, col, edge_id, mean, *need[:3])
+    return tuple(g if n else None for g, n in zip(grads, need[:3])) + (
+        grad if need[3] else None, grad.sum(0) if need[4] else None) + (None, ) * 7
+
+
+register_autograd('pyg_amd::spline_conv', _spline_bwd, setup_context=_spline_setup)
+
+
 # ---- HGTConv's typed relation transform (every edge type of a layer call in one launch) ----------
 @custom_op('pyg_amd::hgt_relation', mutates_args=(), device_types=_DEV)
 def hgt_relation(kqvs: List[Tensor], k_weight: Tensor, v_weight: Tensor, src_pos: List[int],
@@ -1415,4 +1497,4 @@ OPS = ('index_sort', 'index2ptr', 'ptr2index', 'gather', 'scatter', 'scatter_bac
        'resgated_aggregate_backward', 'han_attend', 'han_attend_backward', 'mixture_conv',
        'mixture_conv_backward', 'cg_aggregate', 'cg_aggregate_backward', 'film_aggregate',
        'film_aggregate_backward', 'rgat_aggregate', 'rgat_aggregate_backward', 'graph_norm',
-       'graph_norm_backward', 'hop', 'hop_backward')
+       'graph_norm_backward', 'hop', 'hop_backward', 'spline_conv', 'spline_conv_backward')
