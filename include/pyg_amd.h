@@ -2299,6 +2299,42 @@ PYGAMD_API int pygamd_spgemm_numeric(const void* rowptr_a, const void* col_a, co
                                      size_t workspace_bytes, void* long_workspace,
                                      size_t long_workspace_bytes, void* stream);
 
+/* ---- CSR aggregation over float16 / bfloat16 storage (csrc/spmm_lp.hip) -------------------------
+ * pygamd_spmm_csr for a 16-bit x and out: the fused gather -> message -> reduce of
+ * MessagePassing.propagate (nn/conv/message_passing.py:421-563, utils/_spmm.py:12-136,
+ * edge_index.py:1798-1810) when the features arrive in half or bfloat16 — under torch.autocast or
+ * after model.bfloat16() — which the reference hands to torch.sparse.mm / scatter_reduce_ in that
+ * dtype.  With T the storage type of x and out (x_dtype), everything else float32:
+ *
+ *   out[i, f] = narrow_T( post(i) * REDUCE_{k in row i} m(k) * widen(x[col[k], f]) )
+ *   m(k)      = (w ? w[e(k)] : 1) * (src_scale ? src_scale[col[k]] : 1)     (one weight per edge)
+ *   e(k)      = eid ? eid[k] : k
+ *   post(i)   = reduce == MEAN ? 1 / max(deg(i), 1) : 1
+ *
+ * over the rows of the handle g (pygamd_csr; NULL: status 1), hub rows by its plan.  Sums are
+ * accumulated in float32 in slot order and every output is rounded ONCE, at its store, to nearest
+ * even (hub rows: after the merge of their float32 chunk partials); NaN stays NaN, float16
+ * overflow gives +-inf, empty rows give 0.  MIN / MAX take no w / src_scale (status 2) and return
+ * one of the inputs bit for bit; arg32_out (optional, [n_rows, F] contiguous, MIN / MAX only) is
+ * written under the rules of pygamd_spmm_args.arg32_out, a tie being an extremum attained from
+ * two DIFFERENT source rows.  x is [n_src, ldx] and out [n_rows, ldo] elements of T, any pitch
+ * >= F and any 2-byte alignment (the kernel picks 16-, 4- or 2-byte accesses from F, the pitches
+ * and the pointers).  No float atomics: results are bit-identical from run to run.
+ * pygamd_spmm_lp_supported: 1 for x_dtype F16 / BF16 and 1 <= F < 2^31, else 0.
+ * pygamd_spmm_lp_workspace_size: 12 * n_chunks * F (0 without hub rows).
+ * An unknown idx_dtype, a negative size, a pitch below F, arg32_out with SUM / MEAN or a NULL
+ * pointer with a non-empty size -> status 1; another x_dtype -> status 2; a short workspace ->
+ * status 3.  n_rows == 0 or F == 0 return 0 without a launch.                                   */
+#define PYGAMD_DTYPE_F16 1
+#define PYGAMD_DTYPE_BF16 2
+PYGAMD_API int pygamd_spmm_lp_supported(int x_dtype, int64_t F);
+PYGAMD_API size_t pygamd_spmm_lp_workspace_size(const pygamd_csr* g, int64_t F);
+PYGAMD_API int pygamd_spmm_lp(const pygamd_csr* g, const void* eid, const float* w,
+                              const float* src_scale, const void* x, int x_dtype, int64_t ldx,
+                              int64_t n_src, void* out, int64_t ldo, int64_t F, int reduce,
+                              int32_t* arg32_out, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,100 @@ def _shaped(out2d: Tensor, shape) -> Tensor:
     return out2d.new_empty(0).set_(out2d.untyped_storage(), out2d.storage_offset(), shape)
 
 
+def _minmax_grad_x(graph: EdgeIndex, x2: Tensor, out: Tensor, g2: Tensor,
+                   arg32: Optional[Tensor]) -> Tensor:
+    """The min / max gradient of ``x`` (float32 operands) from the forward's saved ``arg32``."""
+    fwd = graph.by_dst()
+    grad_x = None
+    if arg32 is not None and not graph.atomic_backward:
+        # cached graph: winners as per-edge bit masks + a source-driven sum over
+        # the transposed CSR instead of N x F scattered atomics
+        grad_x = _native.spmm_minmax_backward_src(
+            fwd, graph.by_src(), graph.src_slot_to_dst_slot(), x2, out, g2, arg32)
+    if grad_x is None:
+        grad_x = _native.spmm_minmax_backward_dst(fwd.ptr, fwd.idx, x2, out, g2,
+                                                  graph.num_src_nodes, arg32=arg32)
+    return grad_x
+
+
+# 16-bit device features (torch.autocast, model.bfloat16()): PYGAMD_SPMM_LP=1 aggregates them in
+# their own storage (csrc/spmm_lp.hip), =0 widens to float32, runs the float32 kernels and narrows.
+# Unset: the native kernels — faster in 30 of the 36 cells of profiles/spmm_lp.md (up to 2.9 x at 256
+# columns; 0.88 at worst, bfloat16 at 64 columns on the arxiv-sized graph) at 0.4 of the peak memory.
+_LP_ENV = os.environ.get('PYGAMD_SPMM_LP')
+SPMM_LP = None if _LP_ENV is None else _LP_ENV != '0'
+_LOW = (torch.float16, torch.bfloat16)
+
+
+def _lp_route(x: Tensor, w: Optional[Tensor], graph: EdgeIndex, reduce: str) -> bool:
+    """A 16-bit ``x`` takes the native 16-bit kernels: one weight per edge that asks for no
+    gradient, a cached handle, and for min / max no deterministic-algorithms request (their
+    gradient then takes the source-driven float32 kernels from the start)."""
+    if x.dim() < 2 or x.numel() == 0 or SPMM_LP is False:
+        return False
+    if w is not None and (w.numel() != graph.num_edges
+                          or (w.requires_grad and torch.is_grad_enabled())):
+        return False  # per-head weights, or SDDMM for grad_w: float32 kernels
+    if graph.atomic_backward:
+        return False
+    if reduce in ('min', 'max'):
+        return w is None and not torch.are_deterministic_algorithms_enabled()
+    return True
+
+
+class SpmmLpFunction(Function):
+    r"""``SpmmFunction`` for a float16 / bfloat16 device ``x`` (``w``: float32, one per edge, no
+    gradient): forward and, for sum / mean / weighted sum, the gradient of ``x`` run on
+    ``pygamd_spmm_lp`` in the 16-bit storage — the gradient on the by-source handle with
+    ``src_scale = 1 / deg`` for mean and the transposed permutation for the weights.  Min / max:
+    the forward is the 16-bit kernel and saves ``arg32``; the BACKWARD is a widening route — ``g``,
+    ``x`` and ``out`` are widened to float32, the float32 backward kernels run and the result is
+    narrowed."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, w: Optional[Tensor], graph: EdgeIndex, reduce: str,
+                w_order: str):
+        fwd = graph.by_dst()
+        if x.size(0) != graph.num_src_nodes:
+            raise ValueError(f"'x' has {x.size(0)} rows but the graph has "
+                             f"{graph.num_src_nodes} source nodes")
+        ctx.graph, ctx.reduce, ctx.w_order, ctx.x_shape = graph, reduce, w_order, x.shape
+        x2 = _rows(x)
+        if reduce in ('min', 'max'):
+            out, arg32 = _native.spmm_csr_lp(fwd.ptr, fwd.idx, x2, reduce, n_rows=fwd.n_rows,
+                                             hub=fwd.hub, save_arg32=True)
+            # (the RETURNED tensor is saved, as in SpmmFunction)
+            res = _shaped(out, (fwd.n_rows, *x.shape[1:]))
+            ctx.save_for_backward(x2, res, arg32)
+            return res
+        eid = fwd.perm if (w is not None and w_order == 'coo') else None
+        out = _native.spmm_csr_lp(fwd.ptr, fwd.idx, x2, reduce, n_rows=fwd.n_rows, eid=eid, w=w,
+                                  hub=fwd.hub)
+        ctx.save_for_backward(w)
+        return _shaped(out, (fwd.n_rows, *x.shape[1:]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        graph, reduce = ctx.graph, ctx.reduce
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        g2 = _rows(grad_out)
+        if reduce in ('min', 'max'):
+            x2, out, arg32 = ctx.saved_tensors
+            grad_x = _minmax_grad_x(graph, x2.float(), _rows(out).float(), g2.float(), arg32)
+            return grad_x.to(x2.dtype).view(ctx.x_shape), None, None, None, None
+        w, = ctx.saved_tensors
+        bwd = graph.by_src()
+        eid = None
+        if w is not None:
+            eid = bwd.perm if ctx.w_order == 'coo' else graph.src_slot_to_dst_slot()
+        scale = graph.by_dst().inv_degree() if reduce == 'mean' else None
+        grad_x = _native.spmm_csr_lp(bwd.ptr, bwd.idx, g2, 'sum', n_rows=bwd.n_rows, eid=eid, w=w,
+                                     src_scale=scale, hub=bwd.hub)
+        return grad_x.view(ctx.x_shape), None, None, None, None
+
+
 class SpmmFunction(Function):
     r"""``out[i] = reduce_{(j -> i)} w_e * x[j]`` on an :class:`EdgeIndex` handle.
 
@@ -34,6 +128,20 @@ class SpmmFunction(Function):
     (edge_index.py:1903-1922).  ``w_order``: 'coo' (``w[e]`` follows ``edge_index`` order) or
     'slot' (``w`` follows the by-destination slot order, e.g. GAT's alpha).
     """
+
+    @classmethod
+    def apply(cls, x: Tensor, w: Optional[Tensor], graph: EdgeIndex, reduce: str,
+              w_order: str):
+        """A float16 / bfloat16 device ``x`` is aggregated in its storage (:class:`SpmmLpFunction`)
+        where :func:`_lp_route` allows, and is otherwise widened to float32, aggregated by the
+        kernels below and narrowed; the result and the gradient of ``x`` have its dtype."""
+        if isinstance(x, Tensor) and x.is_cuda and x.dtype in _LOW:
+            if _lp_route(x, w, graph, reduce):
+                w32 = None if w is None else w.detach().reshape(-1).float()
+                return SpmmLpFunction.apply(x, w32, graph, reduce, w_order)
+            w32 = w if w is None or w.dtype == torch.float32 else w.float()
+            return super().apply(x.float(), w32, graph, reduce, w_order).to(x.dtype)
+        return super().apply(x, w, graph, reduce, w_order)
 
     @staticmethod
     def forward(ctx, x: Tensor, w: Optional[Tensor], graph: EdgeIndex, reduce: str,
@@ -86,16 +194,7 @@ class SpmmFunction(Function):
                     ntie = _native.spmm_tie_count(fwd.ptr, fwd.idx, x2, out, count_self=True)
                     grad_x = _native.spmm_minmax_backward(bwd.ptr, bwd.idx, x2, out, g2, ntie)
                 else:
-                    grad_x = None
-                    if arg32 is not None and not graph.atomic_backward:
-                        # cached graph: winners as per-edge bit masks + a source-driven sum over
-                        # the transposed CSR instead of N x F scattered atomics
-                        grad_x = _native.spmm_minmax_backward_src(
-                            fwd, graph.by_src(), graph.src_slot_to_dst_slot(), x2, out, g2, arg32)
-                    if grad_x is None:
-                        grad_x = _native.spmm_minmax_backward_dst(fwd.ptr, fwd.idx, x2, out, g2,
-                                                                  graph.num_src_nodes,
-                                                                  arg32=arg32)
+                    grad_x = _minmax_grad_x(graph, x2, out, g2, arg32)
                 grad_x = grad_x.view(ctx.x_shape)
             return grad_x, None, None, None, None
         x2, w = ctx.saved_tensors

@@ -489,6 +489,73 @@ def spmm_csr(rowptr: Tensor, col: Optional[Tensor], x: Tensor, reduce: str, *,
     return (out, arg) if return_arg else out
 
 
+LP_DTYPES = {torch.float16: _lib.CONSTANTS['PYGAMD_DTYPE_F16'],
+             torch.bfloat16: _lib.CONSTANTS['PYGAMD_DTYPE_BF16']}
+
+
+def spmm_lp_supported(dtype: torch.dtype, F: int) -> bool:
+    """The envelope of :func:`spmm_csr_lp`: float16 / bfloat16 rows of ``F >= 1`` columns."""
+    return dtype in LP_DTYPES and bool(_lib.load().pygamd_spmm_lp_supported(LP_DTYPES[dtype], F))
+
+
+def spmm_csr_lp(rowptr: Tensor, col: Tensor, x: Tensor, reduce: str, *,
+                n_rows: Optional[int] = None, eid: Optional[Tensor] = None,
+                w: Optional[Tensor] = None, src_scale: Optional[Tensor] = None,
+                hub: Optional[HubPlan] = None, out: Optional[Tensor] = None,
+                save_arg32: bool = False):
+    """``out[i] = narrow(reduce_k m(k) * widen(x[col[k]]))`` over float16 / bfloat16 rows — see
+    pygamd_spmm_lp in include/pyg_amd.h.  ``x`` ([n_src, F], unit column stride: a column block of
+    a wider plane is read in place) and ``out`` share the 16-bit dtype; ``w`` (one float32 per
+    edge) and ``src_scale`` (one float32 per row of ``x``) are for sum / mean.  ``save_arg32``
+    (min / max): returns ``(out, arg32)``."""
+    _require_device(rowptr, col, x, eid, w, src_scale, out)
+    lib = _lib.load()
+    if x.dtype not in LP_DTYPES or x.dim() != 2:
+        raise ValueError(f"'x' must be a two-dimensional float16 or bfloat16 tensor (got {x.dtype} "
+                         f"with {x.dim()} dimensions)")
+    F = x.size(1)
+    if x.size(0) > 0 and F > 0 and (x.stride(1) != 1 or x.stride(0) < F):
+        x = x.contiguous()
+    n_rows = rowptr.numel() - 1 if n_rows is None else n_rows
+    red = REDUCE_IDS[reduce]
+    if red not in (_lib.SUM, _lib.MEAN, _lib.MIN, _lib.MAX):
+        raise ValueError(f"reduce '{reduce}' is not an aggregation of spmm_csr_lp")
+    for name, t, n in (('w', w, None), ('src_scale', src_scale, x.size(0))):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1
+                              or (n is not None and t.numel() != n)):
+            raise ValueError(f"'{name}' must be a one-dimensional float32 tensor"
+                             + ('' if n is None else f' of {n} entries'))
+    if w is not None:
+        if eid is None and w.numel() != col.numel():
+            raise ValueError("'w' needs one value per slot")
+        w = w.contiguous()
+    eid = _edge_id(eid, rowptr, col, 'eid') if w is not None else None
+    src_scale = None if src_scale is None else src_scale.contiguous()
+    if out is None:
+        out = torch.empty(n_rows, F, dtype=x.dtype, device=x.device)
+    elif (out.dtype != x.dtype or out.dim() != 2 or tuple(out.shape) != (n_rows, F)
+          or (out.numel() > 0 and (out.stride(1) != 1 or out.stride(0) < F))):
+        raise ValueError(f"'out' must be a {x.dtype} [{n_rows}, {F}] tensor with unit column "
+                         f"stride")
+    arg32 = None
+    if save_arg32 and red in (_lib.MIN, _lib.MAX):
+        arg32 = torch.empty(n_rows, F, dtype=torch.int32, device=x.device)
+    if n_rows > 0 and F > 0:
+        if col.numel() == 0:  # no slots: every row is empty; the launch reads no slot
+            col, w, eid = rowptr.new_zeros(1), None, None
+        g = _csr(rowptr, col, n_rows, hub)
+        ws_bytes = lib.pygamd_spmm_lp_workspace_size(ctypes.byref(g), F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+        with _timed({'kind': 'spmm_lp', 'n_rows': n_rows, 'n_src': x.size(0), 'nnz': col.numel(),
+                     'F': F, 'reduce': reduce, 'idx_bytes': rowptr.element_size(),
+                     'elem_bytes': 2, 'weighted': w is not None,
+                     'src_scale': src_scale is not None, 'n_hub': g.n_hub}, x):
+            check(lib.pygamd_spmm_lp(ctypes.byref(g), _p(eid), _p(w), _p(src_scale), _p(x),
+                                     LP_DTYPES[x.dtype], _ld(x), x.size(0), _p(out), _ld(out), F,
+                                     red, _p(arg32), _p(ws), ws_bytes, _stream(x)), 'spmm_lp')
+    return (out, arg32) if save_arg32 else out
+
+
 def compressed_pitch(F: int) -> int:
     """Row pitch (32-bit words) of a compressed block of ``F`` columns: 8 mask words + F values + 4
     words of slack for the 16-byte value loads, rounded up to 128-byte lines (288 for F = 256)."""

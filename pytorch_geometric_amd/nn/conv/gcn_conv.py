@@ -11,7 +11,7 @@ from ...utils.num_nodes import maybe_num_nodes
 from ..dense.linear import Linear
 from ..inits import zeros
 from ._act_request import requested_activation
-from .message_passing import MessagePassing
+from .message_passing import _LOW, MessagePassing
 
 
 def gcn_norm(edge_index: Tensor, edge_weight: Optional[Tensor] = None,
@@ -93,11 +93,17 @@ class GCNConv(MessagePassing):
         zeros(self.bias)
         self._cached_edge_index = None
 
+    @staticmethod
+    def _weight_dtype(x: Tensor) -> torch.dtype:
+        # half / bfloat16 device features: the edge weights stay float32 (one per edge; the
+        # aggregation kernels take them in float32 whatever the features' storage)
+        return torch.float32 if x.is_cuda and x.dtype in _LOW else x.dtype
+
     def _normalized(self, x: Tensor, edge_index: Tensor, edge_weight: Optional[Tensor]):
         if self._cached_edge_index is not None:
             return self._cached_edge_index
         out = gcn_norm(edge_index, edge_weight, x.size(self.node_dim), self.improved,
-                       self.add_self_loops, self.flow, x.dtype)
+                       self.add_self_loops, self.flow, self._weight_dtype(x))
         if self.cached:
             self._cached_edge_index = out
         return out
@@ -110,7 +116,7 @@ class GCNConv(MessagePassing):
 
         def build():
             ei, w = gcn_norm(handle.edge_index, edge_weight, n, self.improved,
-                             self.add_self_loops, self.flow, x.dtype)
+                             self.add_self_loops, self.flow, self._weight_dtype(x))
             return EdgeIndex(ei, (n, n), validate=False), w
 
         if edge_weight is not None:  # values (and maybe a graph of gradients) differ per call

@@ -9,7 +9,7 @@ from ..._functions import GineAggregateFunction, SpmmFunction
 from ...edge_index import as_edge_index
 from ..dense.linear import Linear
 from ..inits import reset
-from .message_passing import _LOW, MessagePassing, _n_dst, _pair
+from .message_passing import _FLOATS, _LOW, MessagePassing, _n_dst, _pair
 
 # PYGAMD_FUSE_GINE=0: GINEConv layers start with ``fuse = False`` (read at import)
 FUSE_GINE = os.environ.get('PYGAMD_FUSE_GINE', '1') not in ('', '0')
@@ -23,9 +23,10 @@ class GINConv(MessagePassing):
     .. math:: x_i' = h_\Theta\big((1 + \epsilon) x_i + \sum_{j \in N(i)} x_j\big)
 
     ``eps`` is a parameter with ``train_eps`` and a buffer otherwise.  ``x`` is a tensor,
-    ``(x_src, x_dst)`` or ``(x_src, None)`` (no self term).  Routes: float32 device tensors with
-    ``flow='source_to_target'`` and the sum aggregation take the CSR sum SpMM
-    (``SpmmFunction``); everything else takes the generic ``propagate``."""
+    ``(x_src, x_dst)`` or ``(x_src, None)`` (no self term).  Routes: float32, float16 and
+    bfloat16 device tensors with ``flow='source_to_target'`` and the sum aggregation take the CSR
+    sum SpMM (``SpmmFunction``, 16-bit rows in their own storage); everything else takes the
+    generic ``propagate``."""
 
     def __init__(self, nn: Callable, eps: float = 0., train_eps: bool = False, **kwargs):
         kwargs.setdefault('aggr', 'add')
@@ -47,7 +48,7 @@ class GINConv(MessagePassing):
     def forward(self, x: Union[Tensor, Tuple[Tensor, Optional[Tensor]]], edge_index,
                 size=None) -> Tensor:
         x_src, x_dst = _pair(x)
-        if (x_src.is_cuda and x_src.dtype == torch.float32 and self.fuse
+        if (x_src.is_cuda and x_src.dtype in _FLOATS and self.fuse
                 and self.flow == 'source_to_target' and self.aggr in ('add', 'sum')
                 and x_src.dim() == 2):
             n_dst = _n_dst(self, x_src, x_dst, edge_index, size)

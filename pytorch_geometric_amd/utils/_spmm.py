@@ -56,7 +56,9 @@ def spmm(src: Union[EdgeIndex, Tensor], other: Tensor, reduce: str = 'sum',
     reduce = 'sum' if reduce == 'add' else reduce
     if reduce not in ('sum', 'mean', 'min', 'max'):
         raise ValueError(f"`reduce` argument '{reduce}' not supported")
-    _require_fp32(other, 'spmm')
+    # (float16 / bfloat16 DEVICE tensors are aggregated in their storage: SpmmFunction.apply)
+    if not (other.is_cuda and other.dtype in (torch.float16, torch.bfloat16)):
+        _require_fp32(other, 'spmm')
     if isinstance(src, EdgeIndex):
         return SpmmFunction.apply(other, value, src, reduce, 'coo')
     if isinstance(src, Tensor) and src.layout in (torch.sparse_csr, torch.sparse_coo,
