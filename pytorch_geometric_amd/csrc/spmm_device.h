@@ -205,10 +205,23 @@ __device__ __forceinline__ void zrows_headers(const SpmmDev<IdxT>& a, int j, int
 // the value loads are out, and the headers complete under them: the mask round trip is paid once
 // per staged index chunk, not once per batch — then the values are added in slot order.
 // FULL: all U slots exist; otherwise the slots from cnt on add +0.0.
+//
+// The predication is written out: `if (bit) v = base[off]` compiles to s_and_saveexec_b64 /
+// s_cbranch_execz / s_or_b64 exec around every load (hipcc keeps the branch around any memory
+// instruction), 12 scalar instructions and 4 branches per source row in a loop that is bound by
+// instruction issue.  One asm block per row instead saves exec, moves each chunk mask into exec in
+// front of its load and puts exec back: 6 scalar instructions, no branch, and the block leaves
+// exec as it found it.  The offsets are computed in front of the block with every lane enabled.
+// The compiler does not count loads issued inside an asm block, so the waits are written out as
+// well: a row's values pass through an asm that waits until at most the loads of the later rows
+// of the batch are outstanding (vector memory loads return in order; an instruction the compiler
+// issues in between only makes the wait stronger).  In a partial batch the absent slots issue
+// nothing, so every wait there is for all loads.
 template <typename IdxT, int U, bool FULL>
 __device__ __forceinline__ void zrows_batch(const SpmmDev<IdxT>& a, int j, int cnt, IdxT myc,
                                             zrow_ptr (&base)[U], u32x8 (&h)[U],
                                             float (&zacc)[4]) {
+  static_assert(4 * (U - 1) < 64, "the vmcnt field counts to 63");
   float v[U][4];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -216,16 +229,36 @@ __device__ __forceinline__ void zrows_batch(const SpmmDev<IdxT>& a, int j, int c
     for (int k = 0; k < 4; ++k) v[u][k] = 0.f;
     if (FULL || j + u < cnt) {  // (uniform: a slot past the end is one scalar branch)
       int kept = kZrowHdr;
+      uint32_t off[4];  // bytes
+      uint64_t m[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const uint32_t lo = h[u][2 * k], hi = h[u][2 * k + 1];
-        const uint64_t m = (static_cast<uint64_t>(hi) << 32) | lo;
-        if (__builtin_amdgcn_inverse_ballot_w64(m)) {
-          const int off = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0)) + kept;
-          v[u][k] = __uint_as_float(base[u][off]);
-        }
-        kept += __popcll(m);
+        m[k] = (static_cast<uint64_t>(hi) << 32) | lo;
+        off[k] = static_cast<uint32_t>(
+                     __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0)) + kept)
+                 << 2;
+        kept += __popcll(m[k]);
       }
+      uint64_t saved;
+      asm volatile(
+          "s_mov_b64 %[sv], exec\n\t"
+          "s_mov_b64 exec, %[m0]\n\t"
+          "global_load_dword %[v0], %[o0], %[b]\n\t"
+          "s_mov_b64 exec, %[m1]\n\t"
+          "global_load_dword %[v1], %[o1], %[b]\n\t"
+          "s_mov_b64 exec, %[m2]\n\t"
+          "global_load_dword %[v2], %[o2], %[b]\n\t"
+          "s_mov_b64 exec, %[m3]\n\t"
+          "global_load_dword %[v3], %[o3], %[b]\n\t"
+          "s_mov_b64 exec, %[sv]"
+          : [v0] "+v"(v[u][0]), [v1] "+v"(v[u][1]), [v2] "+v"(v[u][2]), [v3] "+v"(v[u][3]),
+            [sv] "=&s"(saved)
+          : [o0] "v"(off[0]), [o1] "v"(off[1]), [o2] "v"(off[2]), [o3] "v"(off[3]),
+            [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]), [b] "s"(base[u]));
+      // (row by row: without it the offsets of all U rows are computed first, 4 U registers that
+      // cost the stand-alone aggregation two waves per SIMD)
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
   if constexpr (FULL) {  // (a partial batch is the chunk's last)
@@ -235,6 +268,9 @@ __device__ __forceinline__ void zrows_batch(const SpmmDev<IdxT>& a, int j, int c
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
+    asm volatile("s_waitcnt vmcnt(%[n])"
+                 : "+v"(v[u][0]), "+v"(v[u][1]), "+v"(v[u][2]), "+v"(v[u][3])
+                 : [n] "n"(FULL ? 4 * (U - 1 - u) : 0));
 #pragma unroll
     for (int k = 0; k < 4; ++k) zacc[k] += v[u][k];
   }
