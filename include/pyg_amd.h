@@ -2335,6 +2335,36 @@ PYGAMD_API int pygamd_spmm_lp(const pygamd_csr* g, const void* eid, const float*
                               int32_t* arg32_out, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ---- one-kernel SAGE layer forward over float16 / bfloat16 storage (csrc/sage_fused_lp.hip) -----
+ * SAGEConv.forward (nn/conv/sage_conv.py:131-152) on a square graph after model.half() /
+ * model.bfloat16(): with T the one 16-bit type (dtype: PYGAMD_DTYPE_F16 / _BF16) of x [n_rows, ldx],
+ * w_l and w_r ([Fo, F] contiguous), bias ([Fo] or NULL), out [n_rows, ldo] and agg,
+ *
+ *   agg[i, :] = narrow_T( post(i) * SUM_{k in row i} widen(x[col[k], :]) )        (as pygamd_spmm_lp)
+ *   out[i, :] = narrow_T( widen(agg[i]) @ widen(w_l)^T + widen(x[i]) @ widen(w_r)^T + widen(bias) )
+ *
+ * over the rows of the handle g (n_rows is also the row count of x), hub rows by its plan.  agg is
+ * bit for bit what pygamd_spmm_lp writes for the same x, handle and reduce; it lives in LDS and is
+ * also written to `agg` ([n_rows, F] contiguous) when that is not NULL.  Products are exact in
+ * float32, sums are accumulated in float32 by the matrix instructions and every output is rounded
+ * ONCE to nearest even.  No float atomics: results are bit-identical from run to run.
+ * pygamd_sage_layer_lp_supported: 1 for dtype F16 / BF16, 8 <= F <= 512 with F % 8 == 0,
+ * 1 <= Fo <= 512 and reduce SUM / MEAN, else 0.
+ * pygamd_sage_layer_lp_workspace_size: 4 * n_chunks * F, the float32 partials of the hub chunks
+ * (0 without hub rows).
+ * x, w_l, w_r and agg must be 16-byte aligned and ldx a multiple of 8 elements (16-byte rows);
+ * out and bias take any 2-byte alignment and ldo any pitch >= Fo.  An unknown idx_dtype, a
+ * negative size, a pitch below the width, a misaligned or NULL pointer with n_rows > 0 -> status 1;
+ * outside the envelope -> status 2; a short workspace -> status 3.  n_rows == 0 returns 0 without
+ * a launch.                                                                                      */
+PYGAMD_API int pygamd_sage_layer_lp_supported(int dtype, int64_t F, int64_t Fo, int reduce);
+PYGAMD_API size_t pygamd_sage_layer_lp_workspace_size(const pygamd_csr* g, int64_t F);
+PYGAMD_API int pygamd_sage_layer_lp(const pygamd_csr* g, const void* x, int64_t ldx,
+                                    const void* w_l, const void* w_r, const void* bias /*nullable*/,
+                                    void* out, int64_t ldo, void* agg /*nullable*/, int dtype,
+                                    int64_t F, int64_t Fo, int reduce, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

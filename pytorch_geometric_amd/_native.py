@@ -556,6 +556,72 @@ def spmm_csr_lp(rowptr: Tensor, col: Tensor, x: Tensor, reduce: str, *,
     return (out, arg32) if save_arg32 else out
 
 
+def sage_layer_lp_supported(dtype: torch.dtype, F: int, Fo: int, reduce: str) -> bool:
+    """The envelope of :func:`sage_layer_lp`: float16 / bfloat16, ``8 <= F <= 512`` in multiples
+    of 8, ``1 <= Fo <= 512``, sum or mean."""
+    red = REDUCE_IDS.get(reduce)
+    return (dtype in LP_DTYPES and red is not None and bool(
+        _lib.load().pygamd_sage_layer_lp_supported(LP_DTYPES[dtype], F, Fo, red)))
+
+
+def _rows16(t: Tensor) -> bool:
+    """Rows the layer kernel reads in 16-byte pieces: unit column stride, pitch and base aligned."""
+    return (t.stride(1) == 1 and (t.size(0) <= 1 or (t.stride(0) >= t.size(1)
+                                                     and t.stride(0) % 8 == 0))
+            and t.data_ptr() % 16 == 0)
+
+
+def sage_layer_lp(rowptr: Tensor, col: Tensor, x: Tensor, w_l: Tensor, w_r: Tensor,
+                  bias: Optional[Tensor], reduce: str, *, hub: Optional[HubPlan] = None,
+                  out: Optional[Tensor] = None, save_agg: bool = False):
+    """``out = narrow([aggr x | x] @ [W_l | W_r]^T + b)`` of a square graph in ONE kernel over
+    float16 / bfloat16 storage — see pygamd_sage_layer_lp in include/pyg_amd.h.  ``x`` ([N, F]) may
+    be a column block of a wider tensor and ``out`` ([N, Fo], given or allocated) likewise; all
+    operands share the 16-bit dtype.  Returns ``(out, agg)``; ``agg`` ([N, F], the rounded
+    aggregation the backward needs) is None unless ``save_agg``."""
+    _require_device(rowptr, col, x, w_l, w_r, bias, out)
+    lib = _lib.load()
+    if x.dim() != 2 or w_l.dim() != 2 or w_r.dim() != 2:
+        raise ValueError("'x', 'w_l' and 'w_r' must be two-dimensional")
+    N, F = x.shape
+    Fo = w_l.size(0)
+    if any(t.dtype != x.dtype for t in (w_l, w_r) + (() if bias is None else (bias, ))):
+        raise ValueError(f"'w_l', 'w_r' and 'bias' must have the dtype of 'x' ({x.dtype})")
+    if tuple(w_l.shape) != (Fo, F) or tuple(w_r.shape) != (Fo, F) or (
+            bias is not None and tuple(bias.shape) != (Fo, )):
+        raise ValueError(f"'w_l' / 'w_r' must be [{Fo}, {F}] and 'bias' [{Fo}]")
+    if rowptr.numel() - 1 != N:
+        raise ValueError(f"the graph has {rowptr.numel() - 1} rows but 'x' has {N}")
+    if not sage_layer_lp_supported(x.dtype, F, Fo, reduce):
+        raise NotImplementedError(
+            f'sage_layer_lp takes float16 / bfloat16, 8 <= F <= 512 (F % 8 == 0), 1 <= Fo <= 512 '
+            f"and sum / mean (got {x.dtype}, F = {F}, Fo = {Fo}, '{reduce}')")
+    if N > 0 and not _rows16(x):
+        x = x.contiguous()
+    w_l, w_r = w_l.contiguous(), w_r.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    if out is None:
+        out = torch.empty(N, Fo, dtype=x.dtype, device=x.device)
+    elif (out.dtype != x.dtype or tuple(out.shape) != (N, Fo)
+          or (out.numel() > 0 and (out.stride(1) != 1 or (N > 1 and out.stride(0) < Fo)))):
+        raise ValueError(f"'out' must be a {x.dtype} [{N}, {Fo}] tensor with unit column stride")
+    agg = torch.empty(N, F, dtype=x.dtype, device=x.device) if save_agg else None
+    if N > 0:
+        if col.numel() == 0:  # no slots: every row is empty; the launch reads no slot
+            col = rowptr.new_zeros(1)
+        g = _csr(rowptr, col, N, hub)
+        ws_bytes = lib.pygamd_sage_layer_lp_workspace_size(ctypes.byref(g), F)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+        with _timed({'kind': 'sage_layer_lp', 'n_rows': N, 'nnz': col.numel(), 'F': F, 'Fo': Fo,
+                     'reduce': reduce, 'idx_bytes': rowptr.element_size(), 'elem_bytes': 2,
+                     'n_hub': g.n_hub}, x):
+            check(lib.pygamd_sage_layer_lp(ctypes.byref(g), _p(x), _ld(x), _p(w_l), _p(w_r),
+                                           _p(bias), _p(out), _ld(out), _p(agg),
+                                           LP_DTYPES[x.dtype], F, Fo, REDUCE_IDS[reduce], _p(ws),
+                                           ws_bytes, _stream(x)), 'sage_layer_lp')
+    return out, agg
+
+
 def compressed_pitch(F: int) -> int:
     """Row pitch (32-bit words) of a compressed block of ``F`` columns: 8 mask words + F values + 4
     words of slack for the 16-byte value loads, rounded up to 128-byte lines (288 for F = 256)."""

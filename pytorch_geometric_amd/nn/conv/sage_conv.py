@@ -19,6 +19,9 @@ class SAGEConv(MessagePassing):
 
     On a square graph with float32 device features the whole layer is ONE kernel and one autograd
     node (``nn/models/_fused_sage.py:layer_eligible``; ``fuse = False`` on the layer opts out).
+    With float16 / bfloat16 features and parameters the same holds on the 16-bit layer kernel
+    (``nn/models/_fused_sage_lp.py:layer_eligible_lp``) where ``fuse_lp`` is set — its initial value
+    comes from ``PYGAMD_FUSE_SAGE_LP``; ``fuse = False`` opts out of it too.
     Otherwise (bipartite pairs, ``project=True``, hooks on ``propagate``, other dtypes) the
     neighbourhood reduction runs at the INPUT width as one CSR SpMM launch
     (``message_and_aggregate``) and the linear maps on the repo's GEMM kernels.
@@ -40,6 +43,8 @@ class SAGEConv(MessagePassing):
         self.lin_l = Linear(src_dim, out_channels, bias=bias)
         if root_weight:
             self.lin_r = Linear(dst_dim, out_channels, bias=False)
+        from ..models import _fused_sage_lp
+        self.fuse_lp = _fused_sage_lp.FUSE_LP  # the one-kernel 16-bit layer (False: generic route)
         self.reset_parameters()
 
     def _linears(self):
@@ -53,10 +58,14 @@ class SAGEConv(MessagePassing):
     def forward(self, x: PairOrTensor, edge_index,
                 size: Optional[Tuple[int, int]] = None) -> Tensor:
         if isinstance(x, Tensor):
-            from ..models import _fused_sage
+            from ..models import _fused_sage, _fused_sage_lp
             if _fused_sage.layer_eligible(self, x, edge_index, size):
                 # aggregation, both linear maps and the bias in one kernel; one autograd node
                 h = _fused_sage.run_layer(self, x, edge_index)
+                return F.normalize(h, p=2.0, dim=-1) if self.normalize else h
+            if _fused_sage_lp.layer_eligible_lp(self, x, edge_index, size):
+                # float16 / bfloat16 storage: the same layer as one 16-bit kernel
+                h = _fused_sage_lp.run_layer_lp(self, x, edge_index)
                 return F.normalize(h, p=2.0, dim=-1) if self.normalize else h
         x_src, x_dst = (x, x) if isinstance(x, Tensor) else x
         if self.project:

@@ -702,7 +702,13 @@ def eligible(model, x, edge_index, trim: bool) -> bool:
 
 def _conv_ok(conv, x: Tensor, kinds=('SAGEConv', )) -> bool:
     """A plain mean / sum ``SAGEConv`` with a root weight (or, for a single layer, an unweighted
-    ``GraphConv``) whose ``propagate`` nobody observes."""
+    ``GraphConv``) whose ``propagate`` nobody observes, with float32 weights next to ``x``."""
+    return _conv_plain(conv, kinds) and params_ready(conv, x)
+
+
+def _conv_plain(conv, kinds) -> bool:
+    """:func:`_conv_ok` without the conditions on the parameters (the 16-bit layer route,
+    ``_fused_sage_lp.layer_eligible_lp``, has its own)."""
     kind = type(conv).__name__
     if kind not in kinds or not getattr(conv, 'fuse', True):
         return False
@@ -721,7 +727,7 @@ def _conv_ok(conv, x: Tensor, kinds=('SAGEConv', )) -> bool:
             or getattr(conv, '_aggregate_forward_pre_hooks', None)
             or getattr(conv, '_aggregate_forward_hooks', None)):
         return False
-    return params_ready(conv, x)
+    return True
 
 
 # A single-use batch handle (the loader's, `EdgeIndex.from_sorted_batch`) never reaches the
