@@ -2365,6 +2365,53 @@ PYGAMD_API int pygamd_sage_layer_lp(const pygamd_csr* g, const void* x, int64_t 
                                     int64_t F, int64_t Fo, int reduce, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* ---- segment_matmul over float16 / bfloat16 storage (csrc/segmm_lp.hip) -------------------------
+ * pygamd_segment_matmul / _wgrad for a 16-bit x, W and out (dtype: PYGAMD_DTYPE_F16 / _BF16, one
+ * type T for all three) — RGCNConv and HeteroLinear after model.half() / model.bfloat16() or
+ * under torch.autocast:
+ *
+ *   out[o(s), :]  = narrow_T( widen(x[i(s), :]) @ widen(W[g]) )       for the rows s of group g
+ *   grad_w[g]     = narrow_T( SUM_{s in g} widen(x[s, :])^T widen(grad[j(s), :]) )
+ *   i(s) = x_rows ? x_rows[s] : s,   o(s) = out_rows ? out_rows[s] : s,   j(s) likewise (g_rows);
+ *   _wgrad reads x[i(s), :] as well
+ *
+ * Products are exact in float32, sums are accumulated in float32 by v_mfma_f32_32x32x16_* and
+ * every output is rounded ONCE to nearest even.  `tiles`, `chunks`, `blocks`, the W addressing
+ * (w[g * w_seg_stride + k * w_stride_k + n * w_stride_n]: W^T is read where it lies) and x_rows /
+ * g_rows are those of pygamd_segment_matmul; tile rows are pygamd_segment_matmul_tile_rows().
+ * One of w_stride_k / w_stride_n must be 1 (status 2 otherwise).  out_rows (device int64, or
+ * NULL) scatters the output rows: with x_rows = out_rows = the sorting permutation a type-sorted
+ * HeteroLinear is one launch without a gathered copy on either side.  x, W and out take any
+ * 2-byte alignment and any pitch >= the width: the kernel picks 16-, 4- or 2-byte loads from the
+ * pointers, the pitches and K / N, and never reads past a row.
+ * _wgrad: no float atomics — every (chunk, output tile) writes a float32 partial into `workspace`
+ * ([n_chunks, K, N], pygamd_segment_matmul_lp_wgrad_workspace_size = 4 * n_chunks * K * N bytes,
+ * 4-byte aligned) and a merge kernel adds each group's partials in chunk-table order and rounds
+ * once; the table lists chunks by non-decreasing segment (group / blocks).  Groups without rows
+ * give 0; the result is bit-identical from run to run.  grad_w is [n_seg, K, N] contiguous.
+ * pygamd_segment_matmul_lp_supported: 1 for dtype F16 / BF16 and 1 <= K, N <= 2^22, else 0.
+ * A negative size or stride, blocks < 1, a pitch below blocks * K (blocks * N), a NULL pointer
+ * the call needs -> status 1; another dtype or K / N outside the envelope -> status 2; a short
+ * workspace -> status 3; all before any launch.  No tiles (n_seg == 0) or N == 0 (K or N == 0)
+ * return 0 without a launch.                                                                    */
+PYGAMD_API int pygamd_segment_matmul_lp_supported(int dtype, int64_t K, int64_t N);
+PYGAMD_API int pygamd_segment_matmul_lp(const void* x, int dtype, int64_t ldx,
+                                        const int64_t* x_rows /*nullable*/, const void* w,
+                                        int64_t w_seg_stride, int64_t w_stride_k,
+                                        int64_t w_stride_n, int64_t n_groups,
+                                        const int32_t* tiles, int64_t n_tiles, int64_t K,
+                                        int64_t N, int64_t blocks, void* out, int64_t ldo,
+                                        const int64_t* out_rows /*nullable*/, void* stream);
+PYGAMD_API size_t pygamd_segment_matmul_lp_wgrad_workspace_size(int64_t n_chunks, int64_t K,
+                                                                int64_t N);
+PYGAMD_API int pygamd_segment_matmul_lp_wgrad(const void* x, int64_t ldx,
+                                              const int64_t* x_rows /*nullable*/, const void* g,
+                                              int64_t ldg, const int64_t* g_rows /*nullable*/,
+                                              const int32_t* chunks, int64_t n_chunks,
+                                              int64_t n_seg, int64_t K, int64_t N, int64_t blocks,
+                                              int dtype, void* grad_w, void* workspace,
+                                              size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,7 @@ SOURCES = ['capi.hip', 'graph.hip', 'spmm.hip', 'scatter.hip', 'softmax.hip', 's
            'pna.hip', 'gen.hip', 'resgated.hip', 'han.hip', 'mixture.hip', 'cg.hip',
            'film.hip', 'rgat.hip', 'graph_norm.hip', 'hop.hip', 'cluster.hip',
            'pool.hip', 'spgemm.hip', 'spline.hip', 'spmm_lp.hip',
-           'sage_fused_lp.hip']
+           'sage_fused_lp.hip', 'segmm_lp.hip']
 LAB_SOURCES = SOURCES + ['sage_fused_lab.hip']
 LAB_FLAGS = {'gemm.hip': ['-DPYGAMD_LAB=1']}   # the weight-gradient variants and probes
 ARCH = 'gfx950'

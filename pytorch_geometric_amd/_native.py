@@ -3733,8 +3733,10 @@ WGRAD_CHUNK_ROWS = 2048
 
 
 def segmm_plan(ptr_host: tuple, device, blocks: int = 1):
-    """(tiles int32 [T,3], T, wgrad chunks int32 [C,3], C) on `device` for a host pointer tuple;
-    cached.  Tiles cover every non-empty segment in 64-row pieces, chunks in 2048-row pieces.
+    """(tiles int32 [T,3], T, wgrad chunks int32 [C,3], C, rows) on `device` for a host pointer
+    tuple; cached.  Tiles cover every non-empty segment in pieces of
+    ``pygamd_segment_matmul_tile_rows()`` rows, chunks in 2048-row pieces; ``rows`` is the row count
+    the tables address (``ptr_host[-1]``), which the 16-bit launches hold their operands to.
     With ``blocks`` > 1 every piece is listed once per column block, as group
     ``segment * blocks + b`` (the block-diagonal layout of ``pygamd_segment_matmul``)."""
     key = (ptr_host, str(device), blocks)
@@ -3757,7 +3759,7 @@ def segmm_plan(ptr_host: tuple, device, blocks: int = 1):
     c = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 3).to(device)
     if len(_segmm_plans) > 32:
         _segmm_plans.pop(next(iter(_segmm_plans)))
-    _segmm_plans[key] = (t, len(tiles), c, len(chunks))
+    _segmm_plans[key] = (t, len(tiles), c, len(chunks), ptr_host[-1] if ptr_host else 0)
     return _segmm_plans[key]
 
 
@@ -3820,6 +3822,89 @@ def segment_matmul_wgrad(x: Tensor, g: Tensor, plan, n_seg: int, blocks: int = 1
                                           _p(plan[2]), plan[3],
                                           n_seg, K, N, blocks, _p(gw), _stream(x)),
           'segment_matmul_wgrad')
+    return gw
+
+
+def segment_matmul_lp_supported(dtype: torch.dtype, K: int, N: int) -> bool:
+    """The envelope of :func:`segment_matmul_lp`: float16 / bfloat16, ``K >= 1``, ``N >= 1``."""
+    return dtype in LP_DTYPES and bool(
+        _lib.load().pygamd_segment_matmul_lp_supported(LP_DTYPES[dtype], K, N))
+
+
+def _lp_rows(t: Tensor, name: str) -> Tensor:
+    """2-D float16 / bfloat16 view with unit inner stride (row stride may exceed the width)."""
+    if t.dtype not in LP_DTYPES or t.dim() != 2:
+        raise ValueError(f"'{name}' must be a two-dimensional float16 or bfloat16 tensor (got "
+                         f"{t.dtype} with {t.dim()} dimensions)")
+    if t.size(1) > 0 and t.size(0) > 0 and (t.stride(1) != 1 or t.stride(0) < t.size(1)):
+        t = t.contiguous()
+    return t
+
+
+def segment_matmul_lp(x: Tensor, w: Tensor, plan, transpose_w: bool = False, blocks: int = 1,
+                      x_rows: Optional[Tensor] = None,
+                      out_rows: Optional[Tensor] = None) -> Tensor:
+    """:func:`segment_matmul` over float16 / bfloat16 storage (csrc/segmm_lp.hip): ``x``, ``w``
+    and the result share the 16-bit dtype, sums are float32, one rounding per output.  W^T is read
+    where it lies.  ``out_rows`` [S]: product row s is written to ``out[out_rows[s]]`` (a
+    permutation of the rows: every output row is written)."""
+    _require_device(x, w, x_rows, out_rows)
+    x_rows, out_rows = _row_index(x_rows, 'x_rows'), _row_index(out_rows, 'out_rows')
+    lib = _lib.load()
+    x2 = _lp_rows(x, 'x')
+    if w.dtype != x2.dtype or w.dim() != 3:
+        raise ValueError(f"'weight' must be a three-dimensional {x2.dtype} tensor")
+    w = w.contiguous()
+    if transpose_w:
+        w = w.transpose(1, 2)
+    G, K, N = w.shape
+    if not segment_matmul_lp_supported(x2.dtype, K, N):
+        raise NotImplementedError(f'segment_matmul_lp takes K >= 1 and N >= 1 (got {K}, {N})')
+    if x2.size(1) != blocks * K:
+        raise ValueError(f"'inputs' has {x2.size(1)} columns but the weights expect "
+                         f"{blocks * K}")
+    n_out = x2.size(0) if x_rows is None else x_rows.numel()
+    # the tile table addresses plan[4] rows of the operand and of `out`: anything else would be
+    # read or written past its end
+    if n_out != plan[4] or (out_rows is not None and out_rows.numel() != n_out):
+        raise ValueError(f"the plan covers {plan[4]} rows but 'inputs' / 'x_rows' has {n_out}"
+                         + ('' if out_rows is None else f" and 'out_rows' {out_rows.numel()}"))
+    out = torch.empty(n_out, blocks * N, dtype=x2.dtype, device=x.device)
+    seg_stride, sk, sn = w.stride()
+    check(lib.pygamd_segment_matmul_lp(_p(x2), LP_DTYPES[x2.dtype], _ld(x2), _p(x_rows), _p(w),
+                                       seg_stride, sk, sn, G, _p(plan[0]), plan[1], K, N, blocks,
+                                       _p(out), _ld(out), _p(out_rows), _stream(x)),
+          'segment_matmul_lp')
+    return out
+
+
+def segment_matmul_wgrad_lp(x: Tensor, g: Tensor, plan, n_seg: int, blocks: int = 1,
+                            g_rows: Optional[Tensor] = None,
+                            x_rows: Optional[Tensor] = None) -> Tensor:
+    """:func:`segment_matmul_wgrad` over float16 / bfloat16 storage: float32 chunk partials in a
+    workspace, merged in chunk order and rounded once — no atomics, bitwise reproducible.
+    ``x_rows`` / ``g_rows`` [S]: row s of either operand is gathered inside the kernel."""
+    _require_device(x, g, g_rows, x_rows)
+    g_rows, x_rows = _row_index(g_rows, 'g_rows'), _row_index(x_rows, 'x_rows')
+    lib = _lib.load()
+    x2, g2 = _lp_rows(x, 'x'), _lp_rows(g, 'grad')
+    if g2.dtype != x2.dtype:
+        raise ValueError(f"'grad' must have the dtype of 'x' ({x2.dtype})")
+    K, N = x2.size(1) // blocks, g2.size(1) // blocks
+    n_x = x2.size(0) if x_rows is None else x_rows.numel()
+    n_g = g2.size(0) if g_rows is None else g_rows.numel()
+    if n_x != plan[4] or n_g != plan[4]:
+        raise ValueError(f"the plan covers {plan[4]} rows but 'x' / 'x_rows' has {n_x} and "
+                         f"'grad' / 'g_rows' {n_g}")
+    if not segment_matmul_lp_supported(x2.dtype, K, N):
+        raise NotImplementedError(f'segment_matmul_wgrad_lp takes K >= 1 and N >= 1 (got {K}, {N})')
+    gw = torch.empty(n_seg, K, N, dtype=x2.dtype, device=x.device)
+    ws_bytes = lib.pygamd_segment_matmul_lp_wgrad_workspace_size(plan[3], K, N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    check(lib.pygamd_segment_matmul_lp_wgrad(_p(x2), _ld(x2), _p(x_rows), _p(g2), _ld(g2),
+                                             _p(g_rows), _p(plan[2]), plan[3], n_seg, K, N, blocks,
+                                             LP_DTYPES[x2.dtype], _p(gw), _p(ws), ws_bytes,
+                                             _stream(x)), 'segment_matmul_lp_wgrad')
     return gw
 
 

@@ -1,4 +1,5 @@
 import math
+from types import SimpleNamespace
 from typing import Any, Dict, Optional, Union
 
 import torch
@@ -74,11 +75,19 @@ class Linear(torch.nn.Module):
 def hetero_linear_forward(mod, x: Tensor, type_vec: Tensor) -> Tensor:
     """``HeteroLinear.forward`` (nn/dense/linear.py:287-329): sort the rows by type (stable HIP
     radix sort) unless ``is_sorted``, ONE grouped fp32-MFMA GEMM (``segment_matmul``), the per-type
-    bias, the original order restored.  ``mod``: this package's layer or the reference's (same
-    parameter names and shapes, linear.py:213-246) through ``backend.install()``."""
-    from ... import _native
+    bias, the original order restored.  float16 / bfloat16 device rows: the sorted order is handed
+    to the 16-bit grouped GEMM as its row index on both sides (csrc/segmm_lp.hip, ``x_rows`` =
+    ``out_rows`` = the permutation) — one launch, no gathered copy going in or coming out — unless
+    PYGAMD_SEGMM_LP=0 widens around the float32 route.  ``mod``: this package's layer or the
+    reference's (same parameter names and shapes, linear.py:213-246) through
+    ``backend.install()``."""
+    from ... import _functions, _native
     from ..._functions import GatherFunction
     from ...utils import segment_matmul
+    if x.is_cuda and x.dtype in (torch.float16, torch.bfloat16):
+        if _functions.SEGMM_LP is False:
+            return _hetero_linear_widened(mod, x, type_vec)
+        return _hetero_linear_lp(mod, x, type_vec)
     perm = None
     if type_vec.numel() > 0:
         # (the grouped GEMM reads the segment pointer on the host anyway: one more tiny sync)
@@ -100,12 +109,52 @@ def hetero_linear_forward(mod, x: Tensor, type_vec: Tensor) -> Tensor:
     return out
 
 
+def _checked_types(mod, type_vec: Tensor) -> None:
+    from ... import _native
+    if type_vec.numel() > 0:
+        lo, hi = _native.index_minmax(type_vec)
+        if lo < 0 or hi >= mod.num_types:
+            raise IndexError(f"'type_vec' must lie in [0, {mod.num_types}) "
+                             f"(got values in [{lo}, {hi}])")
+
+
+def _hetero_linear_lp(mod, x: Tensor, type_vec: Tensor) -> Tensor:
+    from ... import _native
+    from ...utils._segment_matmul import _route, _SegmentMatmul
+    _checked_types(mod, type_vec)
+    if x.dim() != 2 or mod.weight.dim() != 3 or x.size(1) != mod.weight.size(1):
+        raise ValueError("'x' must be [S, in_channels]")
+    if type_vec.dim() != 1 or type_vec.numel() != x.size(0):
+        raise ValueError(f"'type_vec' must hold one type per row of 'x' ({x.size(0)} rows, got "
+                         f"shape {tuple(type_vec.shape)})")
+    x, weight, _ = _route(x, mod.weight)
+    perm, sorted_types = None, type_vec
+    if not mod.is_sorted:
+        sorted_types, perm = _native.index_sort(type_vec, max_value=mod.num_types)
+    ptr = tuple(int(v) for v in _native.index2ptr(sorted_types, mod.num_types).tolist())
+    out = _SegmentMatmul.apply(x, ptr, weight, 1, perm)
+    if mod.bias is not None:  # rows are in their original order: the bias row of each one's type
+        out = out + mod.bias[type_vec].to(out.dtype)
+    return out
+
+
+def _hetero_linear_widened(mod, x: Tensor, type_vec: Tensor) -> Tensor:
+    """16-bit rows through the float32 route: widen, sort / multiply / restore as for float32,
+    narrow (differentiable casts: parameters keep the gradient dtype they have)."""
+    wide = SimpleNamespace(num_types=mod.num_types, is_sorted=mod.is_sorted,
+                           weight=mod.weight.float(),
+                           bias=None if mod.bias is None else mod.bias.float())
+    return hetero_linear_forward(wide, x.float(), type_vec).to(x.dtype)
+
+
 class HeteroLinear(torch.nn.Module):
     r"""One linear map per node/edge type: ``out[k] = x[k] @ W[type_vec[k]] + b[type_vec[k]]`` —
     constructor, parameters (``weight [T, in, out]``, ``bias [T, out]``) and forward of
     ``torch_geometric.nn.HeteroLinear`` (torch_geometric/nn/dense/linear.py:170-329).  Rows are
     stably sorted by type (HIP radix sort), transformed by ONE grouped fp32-MFMA GEMM
-    (``segment_matmul``) and restored to their original order."""
+    (``segment_matmul``) and restored to their original order.  float16 / bfloat16 device rows
+    (``model.half()`` / ``model.bfloat16()``, ``torch.autocast``) are multiplied in their storage
+    by one launch of the 16-bit grouped GEMM, which applies the sorted order itself."""
 
     def __init__(self, in_channels: int, out_channels: int, num_types: int,
                  is_sorted: bool = False, bias: bool = True,
