@@ -2114,9 +2114,11 @@ typedef struct pygamd_sage_fused_args {
   int64_t ldy_scaled;
   uint32_t* compressed_out;  /* NULL or [n_rows, ld_compressed] words: y once more, in the format
                                 of pygamd_rows_compress (the next layer's gather source).  Needs
-                                Fo % 32 == 0.  With graph->x_format = PYGAMD_X_COMPRESSED the
-                                gather source itself is such a block (F % 4 == 0, F <= 256).
-                                Both run the fp32-instruction schedule whatever the mode.      */
+                                Fo % 32 == 0, ld_compressed % 4 == 0 and a 16-byte aligned
+                                block; the slack behind a row's kept values is unspecified.
+                                With graph->x_format = PYGAMD_X_COMPRESSED the gather source
+                                itself is such a block (F % 4 == 0, F <= 256); compressed rows
+                                in AND out run the fp32-instruction schedule whatever the mode. */
   int64_t ld_compressed;
 } pygamd_sage_fused_args;
 /* hub partials (pygamd_spmm_csr_workspace_bytes) + the weight's bf16 term planes of the split

@@ -96,7 +96,10 @@ __global__ void __launch_bounds__(kFBlock, 4)
     }
   }
   __syncthreads();  // phase 1 complete: both tiles visible to every wave
-  fused_transform<IdxT, 1>(a, agg, xr, agg_ld, row0, wave, lane, a.zout ? zw : nullptr);
+  // (compressed rows out: the images overlay both tiles once the matrix loop has read them;
+  // launch_fused sizes the dynamic LDS for the larger of the two)
+  fused_transform<IdxT, 1>(a, agg, xr, agg_ld, row0, wave, lane, a.zout ? zw : nullptr,
+                           reinterpret_cast<uint32_t*>(smem));
 }
 
 // ---- (B) split arithmetic ----------------------------------------------------------------------------
@@ -285,8 +288,12 @@ __device__ __forceinline__ void split_pass(const u32x4* __restrict__ wq,
 // rows and loaded with them before the first barrier (see the head of this file).
 // ZSRC: the gather source is a block of compressed rows (LPR = 64, two passes); the root rows stay
 // dense.
+// ZOUT: a.zout receives the output tile once more as compressed rows (fused_compress_tile: the
+// rows' images overlay the planes after the last pass; two more barriers, which every wave of the
+// workgroup reaches).  A compile-time flag, so that the launches that write dense rows only keep
+// their code, registers and LDS.
 template <typename IdxT, int LPR, int NPASS, bool PROBE, bool OCC3 = (NPASS == 1),
-          bool GIVEN = false, bool ZSRC = false>
+          bool GIVEN = false, bool ZSRC = false, bool ZOUT = false>
 __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
     sage_fused_split_kernel(SageFusedArgs<IdxT> a) {
   constexpr int D = OCC3 ? 2 : 4;
@@ -401,16 +408,34 @@ __global__ void __launch_bounds__(kFBlock, OCC3 ? 6 : 4)
     __syncthreads();
     if (active) split_pass<D>(wq + static_cast<int64_t>(ns) * 3 * kWave, aq, pstride, ns, acc0, acc1);
   }
-  if (wave_col0 >= a.Fo) return;
+  if constexpr (!ZOUT) {
+    if (wave_col0 >= a.Fo) return;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) acc0[e] += acc1[e];
-  f32x16 vout;
-  fused_epilogue<IdxT>(a, acc0, row0, wave_col0, lane, vout);
+    for (int e = 0; e < 16; ++e) acc0[e] += acc1[e];
+    f32x16 vout;
+    fused_epilogue<IdxT>(a, acc0, row0, wave_col0, lane, vout);
+  } else {  // (every wave stays for the writer's barriers)
+    __shared__ uint32_t zw[kFWaves * 32];
+    const bool has_cols = wave_col0 < a.Fo;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc0[e] += acc1[e];
+    f32x16 vout = acc0;  // (a wave without a column block: zeros, which the writer ignores)
+    // the lane number is taken again behind an opaque operand: uses of the one from the kernel's
+    // head down here keep it and what derives from it in registers through the matrix loop, which
+    // has none to spare (one spilled register in 5 of the 22 instantiations otherwise)
+    uint32_t ones = ~0u;
+    asm volatile("" : "+s"(ones));
+    const int elane = __builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0));
+    if (has_cols) fused_epilogue<IdxT>(a, acc0, row0, wave_col0, elane, vout);
+    fused_compress_tile<IdxT>(a, vout, zw, pl, row0, wave, elane, has_cols);
+  }
 }
 
 template <typename IdxT, int LPR>
 static int launch_fused(const SageFusedArgs<IdxT>& a, hipStream_t st, bool zsrc) {
-  const size_t lds = sizeof(float) * 2 * kFTile * (a.f_pad + 4);
+  size_t lds = sizeof(float) * 2 * kFTile * (a.f_pad + 4);
+  // (the rows' images overlay the tiles: 36 KB at most, the workgroups per CU stay)
+  if (a.zout && fused_zimg_bytes(a.Fo) > lds) lds = fused_zimg_bytes(a.Fo);
   void (*k)(SageFusedArgs<IdxT>) = sage_fused_fwd_kernel<IdxT, LPR, false>;
   if constexpr (LPR == kWave) {
     if (zsrc) k = sage_fused_fwd_kernel<IdxT, LPR, true>;
@@ -429,15 +454,25 @@ static int launch_fused(const SageFusedArgs<IdxT>& a, hipStream_t st, bool zsrc)
 template <typename IdxT, int LPR, int NPASS>
 static int launch_split(const SageFusedArgs<IdxT>& a, hipStream_t st, bool zsrc) {
   const int KT = NPASS == 1 ? 2 * a.f_half : a.f_half;
-  const size_t lds = sizeof(uint32_t) * 3 * kFTile * (KT / 2 + 4);
-  void (*k)(SageFusedArgs<IdxT>) = a.probe ? sage_fused_split_kernel<IdxT, LPR, NPASS, true>
-                                           : sage_fused_split_kernel<IdxT, LPR, NPASS, false>;
+  size_t lds = sizeof(uint32_t) * 3 * kFTile * (KT / 2 + 4);
+  // compressed rows out (never under a probe: sage_layer_fused_run): the rows' images overlay the
+  // planes.  36 KB at most, below the planes from F = 84 on: with the kernel's 1 KB of mask words
+  // still three (one pass) / two (two passes) workgroups in a CU's 160 KB
+  const bool zout = a.zout != nullptr;
+  if (zout && fused_zimg_bytes(a.Fo) > lds) lds = fused_zimg_bytes(a.Fo);
+  constexpr bool O3 = NPASS == 1;
+  void (*k)(SageFusedArgs<IdxT>) =
+      zout      ? sage_fused_split_kernel<IdxT, LPR, NPASS, false, O3, false, false, true>
+      : a.probe ? sage_fused_split_kernel<IdxT, LPR, NPASS, true>
+                : sage_fused_split_kernel<IdxT, LPR, NPASS, false>;
   if constexpr (NPASS == 2) {  // (probe bit 4: the two-pass kernel at three workgroups per CU)
-    if (a.probe & 16) k = sage_fused_split_kernel<IdxT, LPR, NPASS, true, true>;
+    if (!zout && (a.probe & 16)) k = sage_fused_split_kernel<IdxT, LPR, NPASS, true, true>;
   }
   if (a.save_agg == PYGAMD_AGG_GIVEN)  // (no gather to probe: the probe bits do not apply)
-    k = sage_fused_split_kernel<IdxT, LPR, NPASS, false, NPASS == 1, true>;
-  if constexpr (LPR == kWave && NPASS == 2) {  // (validation: never together with the rows given)
+    k = zout ? sage_fused_split_kernel<IdxT, LPR, NPASS, false, O3, true, false, true>
+             : sage_fused_split_kernel<IdxT, LPR, NPASS, false, O3, true>;
+  // (validation: never together with the rows given; split_takes: nor with compressed rows out)
+  if constexpr (LPR == kWave && NPASS == 2) {
     if (zsrc) k = sage_fused_split_kernel<IdxT, LPR, NPASS, false, false, false, true>;
   }
   PYGAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k),
@@ -450,15 +485,16 @@ static int launch_split(const SageFusedArgs<IdxT>& a, hipStream_t st, bool zsrc)
   return PYGAMD_OK;
 }
 
-// the split schedule writes dense rows out; it gathers dense rows, or compressed rows of more than
-// 128 columns (a whole wave decodes a row: the two-pass kernel's lane shape)
-static bool split_source_ok(const pygamd_spmm_args* graph) {
-  return graph->x_format == PYGAMD_X_DENSE ||
-         (graph->x_format == PYGAMD_X_COMPRESSED && graph->F > 128);
+// the split schedule gathers dense rows, or compressed rows of more than 128 columns (a whole wave
+// decodes a row: the two-pass kernel's lane shape); it writes dense rows and, from dense sources
+// (a model's first hidden layer, gathering or with the rows given), compressed rows next to them.
+// Compressed rows in AND out stay on the fp32 schedule.
+static bool split_takes(const pygamd_spmm_args* graph, const pygamd_sage_fused_args* f) {
+  if (graph->x_format == PYGAMD_X_DENSE) return true;
+  return graph->x_format == PYGAMD_X_COMPRESSED && graph->F > 128 && !f->compressed_out;
 }
 static bool split_eligible(const pygamd_spmm_args* graph, const pygamd_sage_fused_args* f) {
-  return pygamd_get_gemm_mode() == PYGAMD_GEMM_SPLIT_BF16 && split_source_ok(graph) &&
-         !f->compressed_out;
+  return pygamd_get_gemm_mode() == PYGAMD_GEMM_SPLIT_BF16 && split_takes(graph, f);
 }
 
 // (rows given: no hub pre-pass, so no partials in front of the weight planes)
@@ -481,7 +517,8 @@ int sage_layer_fused_run(const pygamd_spmm_args* graph, const pygamd_sage_fused_
   const bool zsrc = graph->x_format == PYGAMD_X_COMPRESSED;
   u32x4* wp = nullptr;
   if (split) {
-    if (!split_source_ok(graph) || f->compressed_out) return PYGAMD_ERR_UNSUPPORTED;
+    // (the probes time the launches that write dense rows only)
+    if (!split_takes(graph, f) || (probe && f->compressed_out)) return PYGAMD_ERR_UNSUPPORTED;
     const size_t off = hub_bytes_aligned(graph, f);
     if (!workspace || workspace_bytes < off + split_planes_bytes(F, Fo))
       return PYGAMD_ERR_WORKSPACE;
@@ -544,7 +581,7 @@ int pygamd_sage_layer_fused_workspace_bytes(const pygamd_spmm_args* graph,
   if (f->save_agg != PYGAMD_AGG_GIVEN) pygamd_spmm_csr_workspace_bytes(graph, &hub);
   // (sized for the split schedule whatever the current mode: the mode may change between the
   // query and the launch)
-  const bool planes = split_source_ok(graph) && !f->compressed_out &&
+  const bool planes = split_takes(graph, f) &&
                       pygamd_sage_layer_forward_supported(graph->F, f->Fo, graph->reduce);
   *bytes = planes ? hub_bytes_aligned(graph, f) + split_planes_bytes(graph->F, f->Fo) : hub;
   return PYGAMD_OK;

@@ -100,14 +100,28 @@ __device__ __forceinline__ void fused_epilogue(const SageFusedArgs<IdxT>& a, con
 // ---- the output tile once more as compressed rows (spmm_device.h): [8 mask words | kept values].
 // Wave w holds the 32 x 32 block of columns [32 w, 32 w + 32) in the accumulator layout above; the
 // offset of its values inside a row is the number of kept values in the blocks before it, which the
-// waves exchange through `zw` ([8][32] mask words in LDS).  EVERY wave of the workgroup calls this
-// (one barrier inside); waves without a column block pass active = false.
+// waves exchange through `zw` ([8][32] mask words in LDS).
+// The rows are put together in LDS and leave from there: `img` ([32][Fo + 32] words, see
+// fused_zimg_bytes) overlays the caller's operand tiles.  Every wave drops its header words and its
+// kept values at their place in the row's image; then wave w streams rows 4 w .. 4 w + 3 out, 16
+// bytes per lane, the 8 + nnz words of a row rounded up to whole 128-byte lines (nothing reads the
+// slack words behind a row; those it writes are zero) — instead of one 4-byte store per kept value
+// at a data-dependent address.  Needs Fo % 32 == 0, ldz % 4 == 0 and a 16-byte aligned zout.
+// EVERY wave of the workgroup calls this, after its last read of the operand tiles (two barriers
+// inside; the first one also is where the tiles become free); waves without a column block pass
+// active = false.
+constexpr int kZimgSlack = 32;  // image pitch = Fo + 32 words: header + values, whole lines
+inline size_t fused_zimg_bytes(int64_t Fo) {
+  return sizeof(uint32_t) * kFTile * static_cast<size_t>(Fo + kZimgSlack);
+}
 template <typename IdxT>
 __device__ __forceinline__ void fused_compress_tile(const SageFusedArgs<IdxT>& a, const f32x16& v,
-                                                    uint32_t* __restrict__ zw, int64_t row0,
+                                                    uint32_t* __restrict__ zw,
+                                                    uint32_t* __restrict__ img, int64_t row0,
                                                     int wave, int lane, bool active) {
   const int li = lane & 31, lh = lane >> 5;
   const bool col_ok = active && wave * 32 + li < a.Fo;
+  const int ild = a.Fo + kZimgSlack;
   uint32_t my_word = 0;  // lane e < 16: row (e & 3) + 8 (e >> 2); lane 16 + e: that row + 4
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
@@ -119,26 +133,53 @@ __device__ __forceinline__ void fused_compress_tile(const SageFusedArgs<IdxT>& a
     const int e = lane & 15;
     zw[wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 4)] = my_word;
   }
-  __syncthreads();
+  __syncthreads();  // mask words visible; every wave is past its last read of the operand tiles
   // kept values of row li in the column blocks before this wave's
   int before = 0;
   for (int w = 0; w < wave; ++w) before += __popc(zw[w * 32 + li]);
-  // the mask words of rows 4 wave .. 4 wave + 3: 32 contiguous bytes per row
+  // the mask words of rows 4 wave .. 4 wave + 3
   if (lane < 32) {
     const int r = 4 * wave + (lane >> 3);
-    if (row0 + r < a.g.n_rows) a.zout[(row0 + r) * a.ldz + (lane & 7)] = zw[(lane & 7) * 32 + r];
+    img[r * ild + (lane & 7)] = zw[(lane & 7) * 32 + r];
   }
-  if (!active) return;
+  if (active) {
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
-    const bool keep = col_ok && __float_as_uint(v[e]) != 0u;
-    const uint64_t m = __ballot(keep);
-    const uint32_t half = lh ? static_cast<uint32_t>(m >> 32) : static_cast<uint32_t>(m);
-    const int rank = __popc(half & ((1u << li) - 1u));
-    const int pre = __shfl(before, r, kWave);
-    if (keep && row0 + r < a.g.n_rows)
-      a.zout[(row0 + r) * a.ldz + kZrowHdr + pre + rank] = __float_as_uint(v[e]);
+    for (int e = 0; e < 16; ++e) {
+      const int r = (e & 3) + 8 * (e >> 2) + 4 * lh;
+      const bool keep = col_ok && __float_as_uint(v[e]) != 0u;
+      const uint64_t m = __ballot(keep);
+      const uint32_t half = lh ? static_cast<uint32_t>(m >> 32) : static_cast<uint32_t>(m);
+      const int rank = __popc(half & ((1u << li) - 1u));
+      const int pre = __shfl(before, r, kWave);
+      if (keep) img[r * ild + kZrowHdr + pre + rank] = __float_as_uint(v[e]);
+    }
+  }
+  __syncthreads();  // the 32 images are complete
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int r = 4 * wave + i;
+    const int64_t row = row0 + r;
+    if (row >= a.g.n_rows) break;  // (uniform)
+    const uint32_t* __restrict__ irow = img + r * ild;
+    const u32x4 h0 = *reinterpret_cast<const u32x4*>(irow);
+    const u32x4 h1 = *reinterpret_cast<const u32x4*>(irow + 4);
+    int words = kZrowHdr;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) words += __popc(h0[q]) + __popc(h1[q]);
+    // whole lines inside the row's pitch; the last row of the block stops at the 16 bytes that hold
+    // its last kept value (its slack need not exist: only Fo + 12 words per row are asked for)
+    int lim = (words + 31) & ~31;
+    lim = lim < a.ldz ? lim : static_cast<int>(a.ldz);
+    if (row == a.g.n_rows - 1) lim = (words + 3) & ~3;
+    u32x4* __restrict__ orow = reinterpret_cast<u32x4*>(a.zout + row * a.ldz);
+    for (int u = lane; 4 * u < lim; u += kWave) {
+      u32x4 piece = *reinterpret_cast<const u32x4*>(irow + 4 * u);
+      // (the slack it does write is zero, not what the tiles left in LDS: the block is a function
+      // of the output alone)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) piece[q] = 4 * u + q < words ? piece[q] : 0u;
+      orow[u] = piece;
+    }
   }
 }
 
@@ -149,7 +190,8 @@ __device__ __forceinline__ void fused_transform(const SageFusedArgs<IdxT>& a,
                                                 const float* __restrict__ agg,
                                                 const float* __restrict__ xr, int agg_ld,
                                                 int64_t row0, int wave, int lane,
-                                                uint32_t* __restrict__ zw = nullptr) {
+                                                uint32_t* __restrict__ zw = nullptr,
+                                                uint32_t* __restrict__ zimg = nullptr) {
   const int F = static_cast<int>(a.g.F);
   // ---- phase 2: [32 x Fo] = [agg | x_root] @ w^T.  No staging and no barrier: wave w owns the
   // output columns [32 w, 32 w + 32), so of every weight chunk it needs exactly its own 32 rows x
@@ -163,7 +205,7 @@ __device__ __forceinline__ void fused_transform(const SageFusedArgs<IdxT>& a,
       f32x16 none;
 #pragma unroll
       for (int e = 0; e < 16; ++e) none[e] = 0.f;
-      fused_compress_tile<IdxT>(a, none, zw, row0, wave, lane, false);
+      fused_compress_tile<IdxT>(a, none, zw, zimg, row0, wave, lane, false);
     }
     return;
   }
@@ -250,7 +292,7 @@ __device__ __forceinline__ void fused_transform(const SageFusedArgs<IdxT>& a,
   }
   f32x16 vout;
   fused_epilogue<IdxT>(a, acc, row0, wave_col0, lane, vout);
-  if (zw) fused_compress_tile<IdxT>(a, vout, zw, row0, wave, lane, true);
+  if (zw) fused_compress_tile<IdxT>(a, vout, zw, zimg, row0, wave, lane, true);
 }
 
 // aggregated row -> LDS tile (+ global agg buffer); lanes < LPR hold VW features per CH
@@ -391,7 +433,8 @@ inline int sage_fused_validate(const pygamd_spmm_args* graph, const pygamd_sage_
   // 16-byte accesses everywhere
   if ((!given && ((graph->ldx % 4) || !aligned16f(graph->x))) || (graph->ldo % 4) ||
       (f->ld_root % 4) || (f->ldw % 4) || !aligned16f(graph->out) || !aligned16f(f->x_root) ||
-      !aligned16f(f->w))
+      !aligned16f(f->w) ||
+      (f->compressed_out && ((f->ld_compressed % 4) || !aligned16f(f->compressed_out))))
     return PYGAMD_ERR_UNSUPPORTED;
   *run = true;
   return PYGAMD_OK;

@@ -60,23 +60,28 @@ FUSE_BWD = os.environ.get('PYGAMD_FUSE_BWD', '1') != '0'
 # library GEMM that takes every wave slot: slower.  The own kernel's footprint is a parameter.)
 OVERLAP_WGRAD = os.environ.get('PYGAMD_OVERLAP_WGRAD', '0') != '0'
 OVERLAP_WGS = int(os.environ.get('PYGAMD_OVERLAP_WGS', '1'))  # workgroups per CU of that launch
-# OPT-IN (PYGAMD_COMPRESS_ROWS=1): a one-kernel layer with a ReLU writes its output a second time
-# as compressed rows (8 mask words + the non-zero values, csrc/spmm_device.h) and the next layer
-# gathers those: a row gather costs what the 128-byte lines it touches cost (10.1 ms for 8 lines per
-# row, 6.0 ms for 5: scripts/gather_lines_probe.py) and half of a ReLU output is exact zeros.
-# Lossless, same sums bit for bit — but NOT faster in this form (measured in round 3 with the
-# nibble-per-lane decoder on the fp32 schedule, products shape: 16.8 ms against 12.9 ms for the
-# layer that gathers, +0.8 ms for the layer that writes; CHANGELOG.md §5a).  The decoder has since
-# been replaced (one 64-column chunk per load, csrc/spmm_device.h) and the default route below does
-# gain; this switch still selects the epilogue writer, whose launches run the fp32 schedule, and
-# takes precedence when set.
-COMPRESS_ROWS = os.environ.get('PYGAMD_COMPRESS_ROWS', '0') != '0'
+# A one-kernel layer with a ReLU can write its output a second time as compressed rows (8 mask words
+# + the non-zero values, csrc/spmm_device.h) from its epilogue, and the next layer gathers those: a
+# row gather costs what the 128-byte lines it touches cost (10.1 ms for 8 lines per row, 6.0 ms for
+# 5: scripts/gather_lines_probe.py) and half of a ReLU output is exact zeros.  Lossless, same sums
+# bit for bit.  The writer puts each row together in LDS and stores whole 128-byte lines, on either
+# schedule (csrc/sage_fused_device.h `fused_compress_tile`; round 3's form — one 4-byte store per
+# kept value, fp32 schedule only — cost the writing layer +0.8 ms, CHANGELOG.md §5a).
+# PYGAMD_COMPRESS_ROWS, three states:
+#   unset  None   the epilogue writes wherever the next layer gathers compressed rows anyway (see
+#                 `_compress_gather_ok` below) and this layer runs the production kernel on the
+#                 split schedule: the stand-alone pass in front of the next layer does not run;
+#   0      False  the stand-alone pass (`_native.rows_compress`) everywhere;
+#   1      True   the epilogue writes in front of every one-kernel layer (whatever its width and the
+#                 arithmetic), as the switch has always done.
+_compress_rows_env = os.environ.get('PYGAMD_COMPRESS_ROWS')
+COMPRESS_ROWS = None if _compress_rows_env is None else _compress_rows_env != '0'
 
 
-# What does pay is the stand-alone pass (`_native.rows_compress`, ~1 ms for a [2.45 M, 256] block)
-# in front of a one-kernel layer on the split schedule, whose gather decodes with one lane per
-# column of a 64-column chunk (scalar header loads, mbcnt offsets, coalesced value loads:
-# csrc/spmm_device.h "compressed rows"):
+# Where no epilogue wrote the block, a stand-alone pass does (`_native.rows_compress`, ~1 ms for a
+# [2.45 M, 256] block) in front of a one-kernel layer on the split schedule, whose gather decodes
+# with one lane per column of a 64-column chunk (scalar header loads, mbcnt offsets, coalesced
+# value loads: csrc/spmm_device.h "compressed rows"):
 #   forward   a one-kernel 'post' layer of more than 128 input columns gathers the compressed copy
 #             of the ReLU output below it (the dense rows stay the root operand);
 #   backward  the one-launch input gradient gathers the compressed copy of the masked gradient that
@@ -332,14 +337,21 @@ class FusedSageStack(Function):
                                       and src.stride(0) % 4 == 0 and buf.stride(0) % 4 == 0)
                 znext = None
                 if one_kernel:
+                    if zsrc is None and layer > 0 and not lone and _compress_gather_ok(inp, Fi):
+                        zsrc = _native.rows_compress(inp)  # (`inp`: the ReLU output below)
                     if not last:
                         bits[layer + 1] = _native.relu_bits_like(N, Fo, dev)
-                        if (COMPRESS_ROWS and Fo % 32 == 0 and _native.SAGE_FUSED_VARIANT <= 1
+                        # (unset: only where the pass would run otherwise, and only from the
+                        # split schedule's launch, which takes dense gather sources: the fp32
+                        # schedule's writer has not been timed against the pass)
+                        writes = COMPRESS_ROWS or (
+                            COMPRESS_ROWS is None and zsrc is None
+                            and _compress_gather_ok(dst, Fo) and not _native.SAGE_FUSED_VARIANT
+                            and _native.get_gemm_mode() == 'split')
+                        if (writes and Fo % 32 == 0 and _native.SAGE_FUSED_VARIANT <= 1
                                 and one_kernel_post(layer + 1)):
                             znext = torch.empty(N, _native.compressed_pitch(Fo),
                                                 dtype=torch.int32, device=dev)
-                    if zsrc is None and layer > 0 and not lone and _compress_gather_ok(inp, Fi):
-                        zsrc = _native.rows_compress(inp)  # (`inp`: the ReLU output below)
                     # the aggregated rows are stored once (write-only) for the weight gradient
                     _native.sage_layer_forward(fwd.ptr, fwd.idx, src if zsrc is None else zsrc,
                                                inp if lone else buf[:, Fi:],
